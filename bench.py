@@ -807,6 +807,29 @@ class Rank:
             self.dist.destroy_process_group()
 
 
+DUMP_BUDGET_BYTES = 64 << 20       # --dump-outputs: at most this much in all
+DUMP_SAMPLE_SEED = 20240607        # rows kept of an output larger than its share: the same every run
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs DIR: the arrays a caller of the timed path receives after its last step, as DIR/<name>.npy in float32
+    (exact for status and Gt bytes).  Each array gets an equal share of the 64 MB budget; one that does not fit is replaced by a
+    fixed, seeded sample of its rows, and the row numbers kept go to DIR/<name>_rows.npy (float64)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // len(arrays)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        rows = a.shape[0]
+        row_bytes = 4 * (a.size // rows if rows else 1)
+        if rows * row_bytes > share:
+            keep = share // (row_bytes + 8)
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(rows, keep, replace=False))
+            np.save(os.path.join(dirname, name + "_rows.npy"), idx.astype(np.float64))
+            a = a[idx]
+        np.save(os.path.join(dirname, name + ".npy"), a.astype(np.float32))
+
+
 def corrupt_phase(rank, step):
     """which residue (mod CORRUPT_EVERY) of a shard carries the wrong signature: depends on the rank AND on the
     step parity, so a gather that returned another rank's or a stale step's statuses is caught"""
@@ -918,6 +941,8 @@ def run_verify(args, R):
     timed_clocks = eng.last_clocks() if clock_probe else None   # accumulated over the K timed steps, nothing else
     ok_last = check(args.warmup + args.steps - 1)            # the LAST step's pattern (differs from the one before)
     assert ok_last, "GPU status bytes of the last timed step differ from the expected pattern"
+    # the last timed step's statuses (every rank's, once gathered), taken before the clock-probe steps below overwrite them
+    last_status = (d_all if R.dist_on else d_status).cpu().numpy() if args.dump_outputs and rank == 0 else None
     clock_steps_after = 0
     if clock_capable and not clock_probe and args.clock_probe == "after":
         try:                                                 # four more steps, back to back, OUTSIDE the timed region, with the probe on
@@ -1141,6 +1166,8 @@ def run_verify(args, R):
             last = args.warmup + args.steps - 1
             result["cpu_baseline"] = cpu_baseline_verify(msgs, sig_sets[last & 1], pks, expected_for(0, last))
         result["pmc_as_of"] = pmc_as_of()
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"status": last_status})
         print(json.dumps(result))
     R.finish()
 
@@ -1434,6 +1461,8 @@ def run_pairing(args, R):
                                       "sample": "first %d pairings of the shard, oracle/bn254_oracle.c; canonical Gt bytes equal the GPU's" % sample,
                                       "single_thread_value": one / dt_one}
         result["pmc_as_of"] = pmc_as_of()
+        if args.dump_outputs:                                # statuses of every rank; Gt of rank 0's shard
+            dump_outputs(args.dump_outputs, {"status": (d_all if R.dist_on else d_st).cpu().numpy(), "gt": gt.cpu().numpy()})
         print(json.dumps(result))
     R.finish()
 
@@ -1460,11 +1489,19 @@ def main():
     ap.add_argument("--mgpu-gather", default="auto", choices=["auto", "rccl", "copy"],
                     help="--workload verify-mgpu: auto = RCCL for two or more distinct devices, else peer copies; rccl with ONE device = the one-rank "
                          "rehearsal of the RCCL calls")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="--workload verify / pairing: after the timed steps, write what the last timed step computed as DIR/<name>.npy "
+                         "(float32, 64 MB at most: status bytes of every rank; pairing also the Gt bytes of rank 0's shard, a fixed "
+                         "sample of rows when too large) — same arguments, same inputs, so two builds compare output for output")
     args = ap.parse_args()
     global PMC_WORKLOAD
     PMC_WORKLOAD = "verify" if args.workload in ("verify-host", "verify-compressed") else args.workload   # same kernels, same batch as the headline command
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
+    if args.dump_outputs and args.workload not in ("verify", "pairing"):
+        raise SystemExit("--dump-outputs is implemented for --workload verify and pairing")
     if args.workload == "verify-mgpu":                       # ONE process for all devices: no ranks, no torch.distributed
         PMC_WORKLOAD = "verify"
         return run_verify_mgpu(args)

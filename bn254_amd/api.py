@@ -7,6 +7,8 @@ bn254_amd/host/bn254.hpp (C++); INTEGRATION.md holds the Rust shim a maintainer 
     ECDSA.verify(message, signature, public_key) -> None/raise   src/ecdsa.rs:49-64
     ECDSA.batch_verify(messages, signatures, public_keys) -> [None | Error, ...]      (new)
     ECDSA.batch_verify_randomized(messages, signatures, public_keys, seed) -> same    (new, opt-in, probabilistic)
+    ECDSA.aggregate_verify(messages, signature, public_keys) -> None/raise              (new: distinct messages, one sum)
+    ECDSA.batch_aggregate_verify_distinct([(messages, signature, public_keys), ...]) -> [None | Error, ...]   (new)
     check_public_keys(public_key_g2, public_key_g1)              src/ecdsa.rs:78-93
     PrivateKey / PublicKey / PublicKeyG1 / Signature             src/types.rs:13,81,151,222
 
@@ -321,6 +323,35 @@ class ECDSA:
                                             b"".join(p.raw for p in public_keys), seed if seed is not None else os.urandom(32),
                                             flags=_engine.FLAG_RAND64 if rand64 else 0)
         return [None if s == 0 else Error(s) for s in st]
+
+    @staticmethod
+    def aggregate_verify(messages, signature, public_keys, engine=None):
+        """Aggregate signature over DISTINCT messages (the IRTF BLS draft's AggregateVerify): signature = the sum of the signatures of
+        public_keys[j] on messages[j] (`Add for Signature`, src/types.rs:264-270).  Returns None, or raises the Error of the first failing
+        check: signature, keys, messages, then VerificationFailed (include/bn254_hip.h: bn254_batch_aggregate_verify_distinct).
+        Assumes a proof of possession of every key; distinct messages are NOT enforced here."""
+        if len(messages) != len(public_keys):
+            raise Error(ErrorKind.InvalidLength)
+        _raise(ECDSA._distinct_status([(messages, signature, public_keys)], engine)[0])
+
+    @staticmethod
+    def _distinct_status(aggregates, engine):
+        msgs, pks, sigs, sizes = [], [], [], []
+        for messages, signature, public_keys in aggregates:
+            if len(messages) != len(public_keys):
+                raise Error(ErrorKind.InvalidLength)
+            msgs.extend(bytes(m) for m in messages)
+            pks.extend(p.raw for p in public_keys)
+            sigs.append(signature.raw)
+            sizes.append(len(messages))
+        eng = engine or _eng()
+        return eng.batch_aggregate_verify_distinct(msgs, b"".join(pks), b"".join(sigs), sizes)
+
+    @staticmethod
+    def batch_aggregate_verify_distinct(aggregates, engine=None):
+        """aggregates: a list of (messages, signature, public_keys); result[i] is None iff ECDSA.aggregate_verify on item i succeeds,
+        else the Error it would raise.  A length mismatch in any item raises Error(InvalidLength) before any device work."""
+        return [None if s == 0 else Error(s) for s in ECDSA._distinct_status(aggregates, engine)]
 
 
 def check_public_keys(public_key_g2, public_key_g1):

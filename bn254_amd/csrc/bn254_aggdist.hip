@@ -1,0 +1,292 @@
+// Translation unit of libbn254hip.so: aggregate verification over DISTINCT messages (include/bn254_hip.h:
+// bn254_batch_aggregate_verify_distinct[_device]) — the host side and the one-lane bookkeeping kernels.  Aggregate i owns the pairs
+// j in [agg_off[i], agg_off[i+1]) and passes iff  e(sigma_i, -G2::one()) * prod_j e(H(m_j), pk_j) == 1  (the IRTF draft's AggregateVerify;
+// the sums are the reference's `Add for Signature`, src/types.rs:264-270; the check is ECDSA::verify's, src/ecdsa.rs:49-64).
+//
+// Workspace: pair j at index j (key: Q planes, H(m_j): P1 planes, their decode / hash statuses), the partial products of the reduction
+// levels from pbase on, aggregate i at gbase + i (sigma_i: P1 planes, its running product: F planes, its status byte).  Steps:
+//   1. decode the signatures (P2 planes at i), then k_aggd_prep: the aggregate's range checked, sigma_i and its status moved to gbase + i,
+//      F = one there (an empty aggregate multiplies nothing into it); slot counts ceil(k_i / 2) for a device-side scan;
+//   2. decode the keys, hash the messages (launch_decode_g2, launch_hash_rounds: the kernels and statuses of a verify);
+//   3. k_aggd_map: per SLOT (two pairs of one aggregate) its aggregate by binary search of the scan; the first failing key / message of
+//      every aggregate by atomicMin on the pair index;
+//   4. Miller loops and the segmented product (bn254_pair.hip): level 0, then ceil(log_64) further levels over the partials — level 0 is
+//      the segmented Miller kernel (two pairs per lane pair) from AGGD_TWO_PER_PAIR_MIN_M pairs on, below that one Miller loop per pair
+//      (lane machine for the smallest m, lane pairs, or one lane with pair_lanes off) followed by the level kernel over the pairs;
+//   5. k_aggd_status, then per aggregate F_i * miller(sigma_i, -G2) (the randomised verify's tail) and the final exponentiation of a verify
+//      batch of n items, whose == one test gives 0 / 9 under the folded status.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <cstring>
+
+#include "../../include/bn254_hip.h"
+#include "bn254_pairing.h"
+
+using namespace bn254;
+
+#include "bn254_ws.h"
+#include "bn254_lane.h"
+#include "bn254_host.h"
+
+// ---- device-side scans over n aggregates (prefix maximum of the offsets, prefix sum of the slot counts) ---------------------------------
+#define AGGD_SCAN_WG 256
+#define KERNEL_SCAN __global__ __launch_bounds__(AGGD_SCAN_WG)
+struct AggdAdd { __device__ static uint64_t op(uint64_t a, uint64_t b) { return a + b; } };
+struct AggdMax { __device__ static uint64_t op(uint64_t a, uint64_t b) { return a > b ? a : b; } };
+// inclusive scan of one block of AGGD_SCAN_WG values in LDS (0 is the identity of both operations on unsigned values)
+template <class Op>
+__device__ __forceinline__ uint64_t aggd_block_scan(uint64_t v, uint64_t* lds) {
+  const unsigned t = threadIdx.x;
+  lds[t] = v;
+  __syncthreads();
+  for (unsigned d = 1; d < AGGD_SCAN_WG; d <<= 1) {
+    const uint64_t o = t >= d ? lds[t - d] : 0;
+    __syncthreads();
+    v = Op::op(o, v);
+    lds[t] = v;
+    __syncthreads();
+  }
+  return v;
+}
+template <class Op>
+KERNEL_SCAN void k_aggd_scan_block(const uint64_t* in, size_t n, uint64_t* out, uint64_t* tot) {
+  __shared__ uint64_t lds[AGGD_SCAN_WG];
+  const size_t i = (size_t)blockIdx.x * AGGD_SCAN_WG + threadIdx.x;
+  const uint64_t v = aggd_block_scan<Op>(i < n ? in[i] : 0, lds);
+  if (i < n) out[i] = v;
+  if (threadIdx.x == AGGD_SCAN_WG - 1) tot[blockIdx.x] = v;
+}
+// one workgroup: the block totals scanned in place, AGGD_SCAN_WG at a time with a carry
+template <class Op>
+KERNEL_SCAN void k_aggd_scan_totals(uint64_t* tot, size_t nb) {
+  __shared__ uint64_t lds[AGGD_SCAN_WG];
+  uint64_t carry = 0;
+  for (size_t b0 = 0; b0 < nb; b0 += AGGD_SCAN_WG) {
+    const size_t b = b0 + threadIdx.x;
+    const uint64_t v = Op::op(carry, aggd_block_scan<Op>(b < nb ? tot[b] : 0, lds));
+    if (b < nb) tot[b] = v;
+    carry = Op::op(carry, lds[AGGD_SCAN_WG - 1]);
+    __syncthreads();
+  }
+}
+template <class Op>
+KERNEL_SCAN void k_aggd_scan_add(uint64_t* out, size_t n, const uint64_t* tot) {
+  const size_t i = (size_t)blockIdx.x * AGGD_SCAN_WG + threadIdx.x;
+  if (blockIdx.x > 0 && i < n) out[i] = Op::op(tot[blockIdx.x - 1], out[i]);
+}
+template <class Op>
+static int aggd_scan(hipStream_t s, const uint64_t* in, size_t n, uint64_t* out, uint64_t* tot) {
+  const size_t nb = (n + AGGD_SCAN_WG - 1) / AGGD_SCAN_WG;
+  k_aggd_scan_block<Op><<<(unsigned)nb, AGGD_SCAN_WG, 0, s>>>(in, n, out, tot);
+  if (nb > 1) {
+    k_aggd_scan_totals<Op><<<1, AGGD_SCAN_WG, 0, s>>>(tot, nb);
+    k_aggd_scan_add<Op><<<(unsigned)nb, AGGD_SCAN_WG, 0, s>>>(out, n, tot);
+  }
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// ---- bookkeeping kernels (one lane per aggregate / slot) ---------------------------------------------------------------------------------
+// Aggregate i: its range [lo, hi) is accepted iff lo <= hi <= m and no earlier offset exceeds lo (mx = prefix maximum of the offsets) —
+// the accepted ranges are then disjoint, so their slots fit the (m + n) / 2 the workspace holds.  Anything else: IndexOutOfBounds, no pairs.
+KERNEL_SMALL void k_aggd_prep(size_t n, uint64_t m, const uint64_t* agg_off, const uint64_t* mx, uint64_t* cnt, uint64_t* lo_out, uint64_t* hi_out,
+                              uint32_t* first_pk, uint32_t* first_hash, Ws ws, size_t gbase) {
+  const size_t i = (size_t)blockIdx.x * BN_WAVE + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t lo = agg_off[i], hi = agg_off[i + 1];
+  const bool ok = lo <= hi && hi <= m && (i == 0 || mx[i - 1] <= lo);
+  lo_out[i] = lo;
+  hi_out[i] = ok ? hi : lo;
+  cnt[i] = ok ? (hi - lo + 1) / 2 : 0;
+  first_pk[i] = AGGD_SEG_NONE;
+  first_hash[i] = AGGD_SEG_NONE;
+  G1Affine sig;
+  ws_load_g1(ws, PL_P2X, BY_P2_INF, i, sig);
+  ws_store_g1(ws, PL_P1X, BY_P1_INF, gbase + i, sig);
+  ws_byte(ws, BY_ST_DECODE, gbase + i) = ok ? ws_byte(ws, BY_ST_DECODE, i) : (uint8_t)ST_INDEX_OOB;
+  Fp12 one;
+  fp12_set_one(one);
+  ws_store_f12(ws, gbase + i, one);
+}
+// slot e -> its aggregate (the first i whose inclusive slot count exceeds e; AGGD_SEG_NONE past the last slot) and its two pairs; the first
+// failing key and the first failing message of the aggregate in pair order ("first non-zero in order" is a minimum over the pair index)
+KERNEL_SMALL void k_aggd_map(size_t n_slots, size_t n, const uint64_t* incl, const uint64_t* lo, const uint64_t* hi, uint32_t* slot_agg,
+                             uint32_t* pair_agg, uint32_t* first_pk, uint32_t* first_hash, Ws ws) {
+  const size_t e = (size_t)blockIdx.x * BN_WAVE + threadIdx.x;
+  if (e >= n_slots) return;
+  size_t a = 0, b = n;
+  while (a < b) {
+    const size_t mid = (a + b) >> 1;
+    if (incl[mid] > e) b = mid; else a = mid + 1;
+  }
+  if (slot_agg) slot_agg[e] = a < n ? (uint32_t)a : AGGD_SEG_NONE;
+  if (a >= n) return;
+  const uint64_t l = lo[a], h = hi[a], j0 = l + 2 * (e - (incl[a] - (h - l + 1) / 2));
+  for (uint64_t j = j0; j < j0 + 2 && j < h; ++j) {
+    if (pair_agg) pair_agg[j] = (uint32_t)a;
+    if (ws_byte(ws, BY_ST_DECODE, j) != ST_OK) atomicMin(&first_pk[a], (uint32_t)j);
+    if (ws_byte(ws, BY_ST_HASH, j) != ST_OK) atomicMin(&first_hash[a], (uint32_t)j);
+  }
+}
+// status of aggregate i: its range / signature status, else the first failing key's, else the first failing message's (then the pairing check)
+KERNEL_SMALL void k_aggd_status(size_t n, Ws ws, size_t gbase, const uint32_t* first_pk, const uint32_t* first_hash) {
+  const size_t i = (size_t)blockIdx.x * BN_WAVE + threadIdx.x;
+  if (i >= n) return;
+  uint8_t st = ws_byte(ws, BY_ST_DECODE, gbase + i);
+  if (st == ST_OK && first_pk[i] != AGGD_SEG_NONE) st = ws_byte(ws, BY_ST_DECODE, first_pk[i]);
+  if (st == ST_OK && first_hash[i] != AGGD_SEG_NONE) st = ws_byte(ws, BY_ST_HASH, first_hash[i]);
+  ws_byte(ws, BY_ST_DECODE, gbase + i) = st;
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------------------------------
+static inline size_t round256(size_t x) { return (x + 255) & ~(size_t)255; }
+// entries of the partial array all levels need: a level of e elements runs ceil(e / 128) workgroups and, unless that is one, leaves two each
+static size_t aggd_partials(size_t e) {
+  size_t p = 0;
+  for (;;) {
+    const size_t g = (e + AGGD_WG_ELEMS - 1) / AGGD_WG_ELEMS;
+    if (g <= 1) return p;
+    p += 2 * g;
+    e = 2 * g;
+  }
+}
+static int aggd_reserve(bn254_ctx* c, size_t bytes) {
+  if (bytes <= c->aggd_cap) return 0;
+  { int rc_ = ctx_quiesce(c); if (rc_) return rc_; }
+  if (c->aggd_buf) { HIP_TRY(hipFree(c->aggd_buf)); c->aggd_buf = nullptr; c->aggd_cap = 0; }
+  const size_t cap = (bytes + 4095) & ~(size_t)4095;
+  HIP_TRY(hipMalloc((void**)&c->aggd_buf, cap));
+  c->aggd_cap = cap;
+  return 0;
+}
+
+static int aggd_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t* d_msg_off, const uint8_t* d_pks, size_t m, const uint8_t* d_sigs,
+                       const uint64_t* d_agg_off, size_t n, uint32_t flags, uint8_t* d_status, hipStream_t s) {
+  const uint32_t dflags = flags & (BN254_FLAG_G2_SUBGROUP_CHECK | BN254_FLAG_REJECT_IDENTITY);
+  // routes: small m -> one pairing per lane-machine verify (latency); pair_lanes off -> one pairing per lane; m below AGGD_TWO_PER_PAIR_MIN_M ->
+  // one pair per lane pair (fills the chip); else two pairs of an aggregate per lane pair, the first product fused into the Miller kernel
+  const bool lane_machine = c->pair_lanes && route_lane_machine_helpers(c, m);
+  const bool per_pair = lane_machine || !c->pair_lanes || m < AGGD_TWO_PER_PAIR_MIN_M;
+  const size_t n_slots = (m + n + 1) / 2;             // sum of ceil(k_i / 2) over disjoint ranges
+  const size_t e0 = per_pair ? m : n_slots;
+  const size_t n_part = m ? aggd_partials(e0) : 0;
+  const size_t pbase = round256(m), gbase = round256(pbase + n_part > n ? pbase + n_part : n);
+  int rc = ws_reserve(c, gbase + n);
+  if (rc) return rc;
+  const size_t nb = (n + AGGD_SCAN_WG - 1) / AGGD_SCAN_WG;
+  const size_t n_seg0 = per_pair ? m : n_slots;
+  const size_t u64_words = 4 * n + nb, u32_words = 2 * n + n_seg0 + n_part;
+  if ((rc = aggd_reserve(c, 8 * u64_words + 4 * u32_words))) return rc;
+  uint64_t* mx = (uint64_t*)c->aggd_buf;
+  uint64_t* incl = mx + n;
+  uint64_t* lo = incl + n;
+  uint64_t* hi = lo + n;
+  uint64_t* tot = hi + n;
+  uint32_t* first_pk = (uint32_t*)(tot + nb);
+  uint32_t* first_hash = first_pk + n;
+  uint32_t* seg0 = first_hash + n;
+  uint32_t* pseg = seg0 + n_seg0;
+  CallDone call_done(c, s);
+  PROF_MARK(0);
+  if ((rc = launch_decode_g1(c, s, d_sigs, n, dflags, PL_P2X, BY_P2_INF, 0))) return rc;
+  if ((rc = aggd_scan<AggdMax>(s, d_agg_off, n, mx, tot))) return rc;
+  k_aggd_prep<<<grid_for(n), BN_WAVE, 0, s>>>(n, (uint64_t)m, d_agg_off, mx, incl, lo, hi, first_pk, first_hash, c->ws, gbase);
+  if ((rc = aggd_scan<AggdAdd>(s, incl, n, incl, tot))) return rc;
+  if (m) {
+    if ((rc = launch_decode_g2(c, s, d_pks, m, dflags, 0))) return rc;
+    PROF_MARK(1);
+    if ((rc = launch_hash_rounds(c, s, d_msgs, d_msg_off, m, PL_P1X, BY_P1_INF, nullptr))) return rc;
+    PROF_MARK(2);
+    if (per_pair) HIP_TRY(hipMemsetAsync(seg0, 0xFF, 4 * m, s));          // pairs outside every accepted range belong to nobody
+    k_aggd_map<<<grid_for(n_slots), BN_WAVE, 0, s>>>(n_slots, n, incl, lo, hi, per_pair ? nullptr : seg0, per_pair ? seg0 : nullptr, first_pk,
+                                                       first_hash, c->ws);
+    // level 0 (Miller loops, and on lane pairs the first product), then the levels over the partials until one workgroup holds them all
+    size_t e = e0, ebase = 0, off = 0;
+    const uint32_t* seg = seg0;
+    bool level0 = true;
+    for (;;) {
+      const size_t g = (e + AGGD_WG_ELEMS - 1) / AGGD_WG_ELEMS;
+      const int last = g <= 1;
+      if (level0 && !per_pair) {
+        const AggdSlots sl = {seg0, incl, lo, hi};
+        if ((rc = bn254_pair_aggd_miller(e, c->ws, sl, gbase, pbase + off, pseg + off, last, s))) return rc;
+        PROF_MARK(3);
+      } else {
+        if (level0) {
+          if (lane_machine) rc = bn254_lm_miller_verify(m, c->ws, s, 2);    // a single pair e(P1, Q) per lane-machine verify
+          else if (c->pair_lanes) rc = bn254_pair_miller_var(m, c->ws, s);
+          else rc = launch_miller_var_lane(c, s, m);
+          if (rc) return rc;
+          PROF_MARK(3);
+        }
+        if ((rc = bn254_pair_aggd_level(e, c->ws, seg, ebase, gbase, pbase + off, pseg + off, last, s))) return rc;
+      }
+      level0 = false;
+      if (last) break;
+      e = 2 * g;
+      ebase = pbase + off;
+      seg = pseg + off;
+      off += 2 * g;
+    }
+  } else {
+    PROF_MARK(1);
+    PROF_MARK(2);
+    PROF_MARK(3);
+  }
+  k_aggd_status<<<grid_for(n), BN_WAVE, 0, s>>>(n, c->ws, gbase, first_pk, first_hash);
+  if (c->pair_lanes) {
+    // tail into index i (obase 0: everything below gbase is consumed by now), then the final exponentiation a verify of n items runs
+    if ((rc = bn254_pair_aggd_tail(n, c->ws, gbase, 0, s))) return rc;
+    if (route_for(c, n).fe == BN_FE_LANE_PAIRS) rc = bn254_pair_final_exp(n, c->ws, 0, d_status, nullptr, nullptr, s, 0);
+    else rc = launch_small_final_exp(c, s, n, 0, d_status);
+    if (rc) return rc;
+  } else {
+    if ((rc = launch_rand_tail_lane(c, s, n, gbase))) return rc;
+    if ((rc = launch_final_exp_lane(c, s, n, 1, 1, 1, 0, nullptr, d_status, 0, gbase, nullptr, nullptr))) return rc;
+  }
+  PROF_MARK(4);
+  if (c->profiling) { c->ev_valid = 1; c->ev_hash_first = 0; }
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+extern "C" {
+
+int bn254_batch_aggregate_verify_distinct_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t* d_msg_off, const uint8_t* d_pks, size_t m,
+                                                 const uint8_t* d_agg_sigs, const uint64_t* d_agg_off, size_t n, uint32_t flags, uint8_t* d_status,
+                                                 void* stream) {
+  MsgsLenScope msgs_len_scope(c);
+  if (!c || !d_agg_off || (n && (!d_agg_sigs || !d_status)) || (m && (!d_msgs || !d_msg_off || !d_pks))) return BN254_E_BAD_ARGUMENT;
+  if (m > 0xFFFFFFFFu || n > 0xFFFFFFFFu) return BN254_E_BAD_ARGUMENT;
+  if (n == 0) return 0;
+  if (misaligned(d_agg_sigs) || misaligned(d_pks) || ((uintptr_t)d_msg_off & 7u) || ((uintptr_t)d_agg_off & 7u)) return BN254_E_MISALIGNED;
+  HIP_TRY(hipSetDevice(c->device));
+  return aggd_device(c, d_msgs, d_msg_off, d_pks, m, d_agg_sigs, d_agg_off, n, flags, d_status, stream ? (hipStream_t)stream : c->stream);
+}
+
+int bn254_batch_aggregate_verify_distinct(bn254_ctx* c, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* pks, size_t m, const uint8_t* agg_sigs,
+                                          const uint64_t* agg_off, size_t n, uint32_t flags, uint8_t* status) {
+  MsgsLenScope msgs_len_scope(c);
+  if (!c || !msg_off || !agg_off || (n && (!agg_sigs || !status)) || (m && !pks)) return BN254_E_BAD_ARGUMENT;
+  if (m > 0xFFFFFFFFu || n > 0xFFFFFFFFu) return BN254_E_BAD_ARGUMENT;
+  if (agg_off[0] != 0 || agg_off[n] != m || !offsets_ok(agg_off, n) || !offsets_ok(msg_off, m)) return BN254_E_BAD_ARGUMENT;
+  if (n == 0) return 0;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t msg_bytes = (size_t)msg_off[m];
+  if (msg_bytes && !msgs) return BN254_E_BAD_ARGUMENT;
+  int rc;
+  if ((rc = stage_in(c, 0, msgs, msg_bytes))) return rc;
+  if ((rc = stage_in(c, 1, msg_off, (m + 1) * sizeof(uint64_t)))) return rc;
+  if ((rc = stage_in(c, 2, pks, m * 128))) return rc;
+  if ((rc = stage_in(c, 3, agg_sigs, n * 64))) return rc;
+  if ((rc = stage_in(c, 4, agg_off, (n + 1) * sizeof(uint64_t)))) return rc;
+  if ((rc = stage_reserve(c, 5, n))) return rc;
+  if ((rc = bn254_batch_aggregate_verify_distinct_device(c, c->stage[0], (const uint64_t*)c->stage[1], c->stage[2], m, c->stage[3],
+                                                         (const uint64_t*)c->stage[4], n, flags, c->stage[5], nullptr))) return rc;
+  if ((rc = stage_out(c, 5, status, n))) return rc;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+}  // extern "C"

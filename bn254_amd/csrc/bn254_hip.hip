@@ -555,6 +555,10 @@ int launch_decode_g1(bn254_ctx* c, hipStream_t s, const uint8_t* d_pts, size_t n
   k_decode_g1<<<grid_for(n), BN_WAVE, 0, s>>>(d_pts, n, flags, c->ws, px, inf_plane, accumulate);
   return 0;
 }
+int launch_miller_var_lane(bn254_ctx* c, hipStream_t s, size_t n) {
+  k_miller_var<<<grid_for(n), BN_WAVE, 0, s>>>(n, c->ws);
+  return 0;
+}
 int launch_miller_verify_lane(bn254_ctx* c, hipStream_t s, size_t n, const uint32_t* map, const uint32_t* count) {
   k_miller_verify<<<grid_for(n), BN_WAVE, 0, s>>>(n, c->ws, map, count);
   return 0;
@@ -642,6 +646,7 @@ void bn254_ctx_destroy(bn254_ctx* c) {
   if (c->key_xy) (void)hipFree(c->key_xy);
   if (c->key_st) (void)hipFree(c->key_st);
   if (c->key_inf) (void)hipFree(c->key_inf);
+  if (c->aggd_buf) (void)hipFree(c->aggd_buf);
   for (int i = 0; i < 5; ++i) (void)hipEventDestroy(c->ev[i]);
   (void)hipEventDestroy(c->copy_done);
   (void)hipEventDestroy(c->last_done);

@@ -68,6 +68,8 @@ struct bn254_ctx {
   int max_chunk;             // BN254_OPT_MAX_CHUNK: verify-shaped batches above this size are processed in slices (0 = only when the workspace would not fit)
   int assume_free_mb;        // test knob (BN254_OPT_ASSUME_FREE_MB): the automatic rule prices the workspace against this much free memory instead of hipMemGetInfo
   bool fits_w8, fits_quad, fits_trio;   // the device can hold a workgroup of the small-batch kernels (LDS), asked at creation
+  uint8_t* aggd_buf;         // aggregate verify over distinct messages: the per-aggregate scans, the slot map and the partials' ids (bn254_aggdist.hip)
+  size_t aggd_cap;
 };
 
 struct ScopedEvents {
@@ -161,6 +163,9 @@ BN_HIDDEN int launch_hash_rounds(bn254_ctx* c, hipStream_t s, const uint8_t* d_m
 BN_HIDDEN int launch_small_final_exp(bn254_ctx* c, hipStream_t s, size_t n, int use_hash, uint8_t* d_status);
 BN_HIDDEN int launch_pair_or_trio(bn254_ctx* c, hipStream_t s, size_t n, int use_hash, uint8_t* d_status, int mode, bool mark);
 // one lane per item: k_miller_verify (map / count: a device-side queue of items, or null) and k_final_exp (the arguments of the kernel)
+// one lane per pairing: k_miller_var (f = miller(P1, Q) at every index below n), k_rand_tail (bn254_rand.hip: F_g * miller(S_g, -G2) at gbase + g)
+BN_HIDDEN int launch_miller_var_lane(bn254_ctx* c, hipStream_t s, size_t n);
+BN_HIDDEN int launch_rand_tail_lane(bn254_ctx* c, hipStream_t s, size_t n_groups, size_t gbase);
 BN_HIDDEN int launch_miller_verify_lane(bn254_ctx* c, hipStream_t s, size_t n, const uint32_t* map, const uint32_t* count);
 BN_HIDDEN int launch_final_exp_lane(bn254_ctx* c, hipStream_t s, size_t n, size_t k, size_t item_stride, size_t pair_stride, int use_hash, uint8_t* gt_out,
                                     uint8_t* status_out, int raw_only, size_t base, const uint32_t* map, const uint32_t* count);

@@ -312,6 +312,123 @@ int bn254_pair_rand_tail(size_t n_groups, Ws ws, size_t gbase, hipStream_t s) {
   return 0;
 }
 
+// ---- aggregate verify over distinct messages (host side: bn254_aggdist.hip) on lane pairs -----------------------------------------------
+// ELEMENTS, one per lane pair and AGGD_WG_ELEMS per workgroup, carry a segment id (the aggregate) and an Fq12 value.  Along the element
+// array the ids of one aggregate are contiguous; AGGD_SEG_NONE marks elements of nobody (padding), which never take part in a product.
+// aggd_reduce multiplies every run of equal ids by a tree aligned to the run's first element — round d: the element at run position r
+// with r % 2d == 0 takes the product of the one d further on, if that is still in the run — 7 rounds of at most one fp12_mul per lane pair,
+// the tree of the randomised kernels on the same representation (an operand is never rewritten in the round that reads it, so the product
+// reads LDS in place).  Afterwards the first element of every run holds the run's product.
+// A run that neither starts the workgroup nor reaches its end is a whole aggregate: F at gbase + seg.  The first and the last run may go on
+// in a neighbouring workgroup: they become the workgroup's two PARTIALS (workspace index pbase + 2 block and + 1, ids in pseg; the second
+// is one when a single run covers the workgroup), which the next level reduces the same way.  last = 1: the launch is one workgroup and
+// every run is whole.  Both lanes of a pair take every branch together (the ids are per pair).
+__device__ __forceinline__ void aggd_reduce(Fp12PairSlot* lds_f, uint32_t* lds_seg, uint32_t seg, const Ws& ws, size_t gbase, size_t pbase, uint32_t* pseg,
+                                            int last) {
+  const unsigned pair = threadIdx.x >> 1, role = threadIdx.x & 1u;
+  Fp12& f = lds_f[threadIdx.x].v;
+  if (role == 0) lds_seg[pair] = seg;
+  __syncthreads();
+  unsigned head = 0, hi = pair;                      // the first element of this run (the ids of a run are contiguous)
+  while (head < hi) {
+    const unsigned mid = (head + hi) >> 1;
+    if (lds_seg[mid] == seg) hi = mid; else head = mid + 1;
+  }
+  const unsigned r = pair - head;
+  for (unsigned d = 1; d < AGGD_WG_ELEMS; d <<= 1) {
+    if (seg != AGGD_SEG_NONE && (r & (2 * d - 1)) == 0 && pair + d < AGGD_WG_ELEMS && lds_seg[pair + d] == seg)
+      fp12_mul(f, f, lds_f[threadIdx.x + 2 * d].v);
+    __syncthreads();
+  }
+  if (pair != 0 && lds_seg[pair - 1] == seg) return;   // not the head of its run
+  const bool first = pair == 0, reaches_end = lds_seg[AGGD_WG_ELEMS - 1] == seg;
+  if (last || (!first && !reaches_end)) {
+    if (seg != AGGD_SEG_NONE) ws_store_f12_own(ws, gbase + seg, f);
+    return;
+  }
+  const size_t p0 = pbase + 2 * (size_t)blockIdx.x;
+  if (first) {
+    ws_store_f12_own(ws, p0, f);
+    if (role == 0) pseg[2 * (size_t)blockIdx.x] = seg;
+    if (!reaches_end) return;
+    fp12_set_one(f);                                 // one run covers the workgroup: the second partial is one
+  }
+  ws_store_f12_own(ws, p0 + 1, f);
+  if (role == 0) pseg[2 * (size_t)blockIdx.x + 1] = seg;
+}
+// level 0 of the pair-layout route: element e = SLOT e, i.e. the pairs lo + 2 (e - excl) and the next one (if still in the aggregate) of
+// aggregate slot_agg[e], H(m) in the P1 planes and the key in the Q planes of their pair index, through ONE Miller loop that shares the
+// squarings (miller_loop_2var; an odd aggregate's last slot pads with an identity G1 point, as k_miller_rand2_pair pads)
+KERNEL_PAIR void k_aggd_miller_pair(size_t n_slots, Ws ws, AggdSlots sl, size_t gbase, size_t pbase, uint32_t* pseg, int last) {
+  const size_t e = ((size_t)blockIdx.x * BN_PAIR_WG + threadIdx.x) >> 1;
+  const uint32_t seg = e < n_slots ? sl.slot_agg[e] : AGGD_SEG_NONE;   // no early return: every lane reaches the barriers
+  size_t j0 = 0, j1 = 0;
+  bool has1 = false;
+  if (seg != AGGD_SEG_NONE) {
+    const uint64_t lo = sl.lo[seg], hi = sl.hi[seg];
+    j0 = (size_t)(lo + 2 * (e - (sl.incl[seg] - (hi - lo + 1) / 2)));
+    has1 = j0 + 1 < hi;
+    j1 = has1 ? j0 + 1 : j0;
+  }
+  G1Affine a0, a1;
+  G2Affine q0, q1;
+  ws_load_g1(ws, PL_P1X, BY_P1_INF, j0, a0);
+  ws_load_g1(ws, PL_P1X, BY_P1_INF, j1, a1);
+  if (seg == AGGD_SEG_NONE) a0.inf = true;
+  if (!has1) a1.inf = true;
+  q0.x = ws_load_fp2_own(ws, PL_QX0, j0); q0.y = ws_load_fp2_own(ws, PL_QY0, j0); q0.inf = ws_byte(ws, BY_Q_INF, j0) != 0;
+  q1.x = ws_load_fp2_own(ws, PL_QX0, j1); q1.y = ws_load_fp2_own(ws, PL_QY0, j1); q1.inf = ws_byte(ws, BY_Q_INF, j1) != 0;
+  __shared__ Fp12PairSlot lds_f[BN_PAIR_WG];
+  __shared__ uint32_t lds_seg[AGGD_WG_ELEMS];
+  miller_loop_2var<true>(lds_f[threadIdx.x].v, a0, q0, a1, q1);
+  aggd_reduce(lds_f, lds_seg, seg, ws, gbase, pbase, pseg, last);
+}
+// any later level (and level 0 of the per-pair routes): element e = the value at workspace index ebase + e with id seg[e]
+KERNEL_PAIR void k_aggd_level_pair(size_t n_elems, Ws ws, const uint32_t* seg_in, size_t ebase, size_t gbase, size_t pbase, uint32_t* pseg, int last) {
+  const size_t e = ((size_t)blockIdx.x * BN_PAIR_WG + threadIdx.x) >> 1;
+  const uint32_t seg = e < n_elems ? seg_in[e] : AGGD_SEG_NONE;
+  __shared__ Fp12PairSlot lds_f[BN_PAIR_WG];
+  __shared__ uint32_t lds_seg[AGGD_WG_ELEMS];
+  if (seg != AGGD_SEG_NONE) ws_load_f12_own(ws, ebase + e, lds_f[threadIdx.x].v);
+  else fp12_set_one(lds_f[threadIdx.x].v);
+  aggd_reduce(lds_f, lds_seg, seg, ws, gbase, pbase, pseg, last);
+}
+// per aggregate: F_i * miller(sigma_i, -G2) through the line table (k_rand_tail_pair), read at gbase + i and written with the aggregate's
+// status byte to obase + i, where the final exponentiations of a verify find item i (obase = 0)
+KERNEL_PAIR void k_aggd_tail_pair(size_t n, Ws ws, size_t gbase, size_t obase) {
+  size_t i = ((size_t)blockIdx.x * BN_PAIR_WG + threadIdx.x) >> 1;
+  if (i >= n) return;
+  G1Affine s, unused_g1;
+  G2Affine unused_g2;
+  ws_load_g1(ws, PL_P1X, BY_P1_INF, gbase + i, s);
+  unused_g1.x = fp_load_const(C_G1_GEN[0]); unused_g1.y = fp_load_const(C_G1_GEN[1]); unused_g1.inf = false;
+  unused_g2.x = fp2_load_const(C_G2_GEN[0]); unused_g2.y = fp2_load_const(C_G2_GEN[1]); unused_g2.inf = false;
+  Fp12 fg;
+  ws_load_f12_own(ws, gbase + i, fg);
+  __shared__ Fp12PairSlot lds_f[BN_PAIR_WG];
+  Fp12& f = lds_f[threadIdx.x].v;
+  miller_loop<false, true, true>(f, unused_g1, unused_g2, s);
+  fp12_mul(f, f, fg);
+  ws_store_f12_own(ws, obase + i, f);
+  if ((threadIdx.x & 1u) == 0) ws_byte(ws, BY_ST_DECODE, obase + i) = ws_byte(ws, BY_ST_DECODE, gbase + i);
+}
+static inline unsigned aggd_grid(size_t n_elems) { return (unsigned)((n_elems + AGGD_WG_ELEMS - 1) / AGGD_WG_ELEMS); }
+int bn254_pair_aggd_miller(size_t n_slots, Ws ws, AggdSlots sl, size_t gbase, size_t pbase, uint32_t* pseg, int last, hipStream_t s) {
+  k_aggd_miller_pair<<<aggd_grid(n_slots), BN_PAIR_WG, 0, s>>>(n_slots, ws, sl, gbase, pbase, pseg, last);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+int bn254_pair_aggd_level(size_t n_elems, Ws ws, const uint32_t* seg, size_t ebase, size_t gbase, size_t pbase, uint32_t* pseg, int last, hipStream_t s) {
+  k_aggd_level_pair<<<aggd_grid(n_elems), BN_PAIR_WG, 0, s>>>(n_elems, ws, seg, ebase, gbase, pbase, pseg, last);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+int bn254_pair_aggd_tail(size_t n, Ws ws, size_t gbase, size_t obase, hipStream_t s) {
+  k_aggd_tail_pair<<<(unsigned)((2 * n + BN_PAIR_WG - 1) / BN_PAIR_WG), BN_PAIR_WG, 0, s>>>(n, ws, gbase, obase);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 // Aggregation for config 3 on lane pairs (see k_aggregate in bn254_hip.hip): a pair walks the signer list of its
 // tuple two entries per iteration; each lane adds the signature of "its" entry (2t + role) to its own partial G1 sum and the
 // two partial sums are added at the end.  The public keys take one of two routes, chosen per wave:

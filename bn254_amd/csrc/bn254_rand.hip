@@ -207,6 +207,10 @@ KERNEL void k_rand_tail(size_t n_groups, Ws ws, size_t gbase) {
   fp12_mul(f, f, fg);
   ws_store_f12(ws, gbase + g, f);
 }
+int launch_rand_tail_lane(bn254_ctx* c, hipStream_t s, size_t n_groups, size_t gbase) {
+  k_rand_tail<<<grid_for(n_groups), BN_WAVE, 0, s>>>(n_groups, c->ws, gbase);
+  return 0;
+}
 // group verdicts for batches that were verified exactly: 1 iff no item of the group failed the pairing check
 KERNEL_SMALL void k_group_ok_from_status(size_t n_groups, size_t n, const uint8_t* status, uint8_t* group_ok_out) {
   size_t g = (size_t)blockIdx.x * BN_WAVE + threadIdx.x;

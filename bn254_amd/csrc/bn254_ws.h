@@ -59,6 +59,13 @@ static inline int bn_route_table(const BnRouteLimits& L, size_t* max_n, BnRoute*
 #define PINNED_STAGING_MIN_N ((size_t)8192)        // ... only batches whose transfer is worth overlapping
 #define RAND_MIN_BATCH_DEFAULT 131072              // randomised verify pays off from about here
 #define RAND_TWO_PER_LANE_MIN_N ((size_t)131072)   // randomised verify: two items per lane once that still fills 1024 SIMDs
+// aggregate verify over distinct messages (bn254_aggdist.hip): a 256-lane workgroup reduces 128 ELEMENTS (one per lane pair) by a segmented
+// product in LDS; the Miller kernel's elements are SLOTS of two pairs of one aggregate, so one workgroup takes up to AGGD_WG_PAIRS pairs
+#define AGGD_WG_ELEMS 128
+#define AGGD_WG_PAIRS 256
+#define AGGD_TWO_PER_PAIR_MIN_M 131072            // ... two pairs per lane pair (shared squarings) from this many pairs on: below, m / 2 lane pairs leave the
+                                                   //     1024 SIMDs at less than two waves each, and one pair per lane pair (k_miller_var_pair) is faster
+#define AGGD_SEG_NONE 0xFFFFFFFFu                  // segment id of an element that belongs to no aggregate (padding, gaps between ranges)
 // Register budget: amdgpu_waves_per_eu(W, W) on the kernels is propagated to every device function
 // they call (AMDGPU attributor), capping VGPR+AGPR at 512/W so that W waves fit on each SIMD.
 // In a pure-VALU microbenchmark two co-resident waves each keep the full single-wave issue rate
@@ -175,6 +182,15 @@ __attribute__((visibility("hidden"))) int bn254_pair_final_exp(size_t n, Ws ws, 
                                                                const uint32_t* count, hipStream_t s, size_t base = 0);
 __attribute__((visibility("hidden"))) int bn254_pair_miller_rand(size_t n, size_t n_groups, int items_per_pair, Ws ws, size_t gbase, hipStream_t s);
 __attribute__((visibility("hidden"))) int bn254_pair_rand_tail(size_t n_groups, Ws ws, size_t gbase, hipStream_t s);
+// aggregate verify over distinct messages (bn254_aggdist.hip): the segmented Miller kernel (level 0 over slots), the generic level kernel over
+// (segment, value) elements, and the sigma tail F_i * miller(sigma_i, -G2) from workspace index gbase + i to obase + i
+struct AggdSlots { const uint32_t* slot_agg; const uint64_t* incl; const uint64_t* lo; const uint64_t* hi; };   // slot -> aggregate; per aggregate the inclusive
+                                                                                                                // scan of its slot counts ceil((hi - lo) / 2) and its pair range [lo, hi)
+__attribute__((visibility("hidden"))) int bn254_pair_aggd_miller(size_t n_slots, Ws ws, AggdSlots sl, size_t gbase, size_t pbase, uint32_t* pseg, int last,
+                                                                 hipStream_t s);
+__attribute__((visibility("hidden"))) int bn254_pair_aggd_level(size_t n_elems, Ws ws, const uint32_t* seg, size_t ebase, size_t gbase, size_t pbase,
+                                                                 uint32_t* pseg, int last, hipStream_t s);
+__attribute__((visibility("hidden"))) int bn254_pair_aggd_tail(size_t n, Ws ws, size_t gbase, size_t obase, hipStream_t s);
 __attribute__((visibility("hidden"))) int bn254_pair_aggregate(const uint32_t* tuple_msg, const uint64_t* tuple_off, const uint32_t* signer_idx, size_t n,
                                                                size_t n_signers, size_t n_msgs, Pool pk_pool, Pool sig_pool, Pool h_pool, Pool sub_pool,
                                                                size_t n_groups, Pool sub1_pool, size_t groups4, Ws ws, hipStream_t s,

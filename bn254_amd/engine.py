@@ -271,6 +271,23 @@ class Engine:
                self._lib.bn254_batch_aggregate_verify(self._h, msgs, off, n_msgs, bytes(pk_pool), n_signers, bytes(sig_pool), tm, t_off, idx, n, flags, status))
         return status.raw[:n]
 
+    def batch_aggregate_verify_distinct(self, messages, pks, agg_sigs, agg_sizes, flags=0):
+        """Aggregates over distinct messages: aggregate i owns the next agg_sizes[i] of the (messages[j], pks[j*128:]) pairs and is
+        checked against agg_sigs[i*64:] (include/bn254_hip.h: bn254_batch_aggregate_verify_distinct).  Returns n status bytes."""
+        m, n = len(messages), len(agg_sizes)
+        assert len(pks) == m * G2_BYTES and len(agg_sigs) == n * G1_BYTES and sum(agg_sizes) == m
+        msgs, off = pack_messages(messages)
+        a_off = (ctypes.c_uint64 * (n + 1))()
+        pos = 0
+        for i, k in enumerate(agg_sizes):
+            a_off[i] = pos
+            pos += int(k)
+        a_off[n] = pos
+        status = ctypes.create_string_buffer(max(n, 1))
+        _check("bn254_batch_aggregate_verify_distinct",
+               self._lib.bn254_batch_aggregate_verify_distinct(self._h, msgs, off, bytes(pks), m, bytes(agg_sigs), a_off, n, flags, status))
+        return status.raw[:n]
+
     def register_pools(self, messages, pk_pool, sig_pool, expect_tuples, flags=0):
         """the pools of an aggregate verify decoded, hashed and tabulated ONCE (bn254_ctx_register_pools): for a fixed validator set / message
         set whose tuples keep arriving; `expect_tuples` = the batch size the subset-sum tables are chosen for"""
@@ -408,6 +425,11 @@ class Engine:
         _check("bn254_batch_aggregate_verify_device",
                self._lib.bn254_batch_aggregate_verify_device(self._h, d_msgs, d_msg_off, n_msgs, d_pk_pool, n_signers, d_sig_pool, d_tuple_msg,
                                                              d_tuple_off, d_signer_idx, n, flags, d_status, stream))
+
+    def batch_aggregate_verify_distinct_device(self, d_msgs, d_msg_off, d_pks, m, d_agg_sigs, d_agg_off, n, d_status, flags=0, stream=None):
+        _check("bn254_batch_aggregate_verify_distinct_device",
+               self._lib.bn254_batch_aggregate_verify_distinct_device(self._h, d_msgs, d_msg_off, d_pks, m, d_agg_sigs, d_agg_off, n, flags, d_status,
+                                                                      stream))
 
     def batch_sign_device(self, d_msgs, d_off, d_sks, n, d_sigs, d_status, stream=None):
         _check("bn254_batch_sign_device", self._lib.bn254_batch_sign_device(self._h, d_msgs, d_off, d_sks, n, d_sigs, d_status, stream))

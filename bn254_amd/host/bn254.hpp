@@ -2,6 +2,7 @@
 // over the C ABI of libbn254hip.so (include/bn254_hip.h).  Header-only; link with -lbn254hip.
 //
 //   bn254::ECDSA::sign / verify / batch_verify      /root/reference/src/ecdsa.rs:26-35, :49-64 (+ new batch entry)
+//   bn254::ECDSA::aggregate_verify / batch_aggregate_verify_distinct   (new: aggregates over distinct messages)
 //   bn254::check_public_keys                        /root/reference/src/ecdsa.rs:78-93
 //   bn254::PrivateKey / PublicKey / PublicKeyG1 / Signature   /root/reference/src/types.rs:13,81,151,222
 //   bn254::Error                                    /root/reference/src/error.rs:6-29
@@ -172,6 +173,35 @@ struct ECDSA {
     }
     off[n] = msgs.size();
     check_rc("bn254_batch_verify", bn254_batch_verify(e.raw(), msgs.data(), off.data(), sigs.data(), pks.data(), n, 0, status.data()));
+    return status;
+  }
+  // Aggregate signature over DISTINCT messages (the IRTF BLS draft's AggregateVerify): signature = the sum of the signatures of
+  // public_keys[j] on messages[j].  Throws the Error of the first failing check (signature, keys, messages, then VerificationFailed);
+  // include/bn254_hip.h: bn254_batch_aggregate_verify_distinct.  Assumes a proof of possession of every key; distinct messages are not enforced.
+  struct Aggregate { std::vector<std::vector<uint8_t>> messages; Signature signature; std::vector<PublicKey> public_keys; };
+  static void aggregate_verify(const std::vector<std::vector<uint8_t>>& messages, const Signature& signature, const std::vector<PublicKey>& public_keys,
+                               Engine& e = Engine::default_engine()) {
+    check_status(batch_aggregate_verify_distinct({Aggregate{messages, signature, public_keys}}, e)[0]);
+  }
+  // result[i] == 0 iff aggregate_verify on aggregates[i] succeeds, else the ErrorKind it would throw
+  static std::vector<uint8_t> batch_aggregate_verify_distinct(const std::vector<Aggregate>& aggregates, Engine& e = Engine::default_engine()) {
+    const size_t n = aggregates.size();
+    std::vector<uint64_t> msg_off(1, 0), agg_off(1, 0);
+    std::vector<uint8_t> msgs, pks, sigs(n * 64), status(n, 0);
+    for (size_t i = 0; i < n; ++i) {
+      const Aggregate& a = aggregates[i];
+      if (a.messages.size() != a.public_keys.size()) throw Error(ErrorKind::InvalidLength);
+      for (size_t j = 0; j < a.messages.size(); ++j) {
+        msgs.insert(msgs.end(), a.messages[j].begin(), a.messages[j].end());
+        msg_off.push_back(msgs.size());
+        pks.insert(pks.end(), a.public_keys[j].raw.begin(), a.public_keys[j].raw.end());
+      }
+      agg_off.push_back(msg_off.size() - 1);
+      std::memcpy(&sigs[64 * i], a.signature.raw.data(), 64);
+    }
+    const size_t m = msg_off.size() - 1;
+    check_rc("bn254_batch_aggregate_verify_distinct", bn254_batch_aggregate_verify_distinct(e.raw(), msgs.data(), msg_off.data(), pks.data(), m, sigs.data(),
+                                                                                            agg_off.data(), n, 0, status.data()));
     return status;
   }
   // the same over all the GPUs of a node: shard g of the batch on device entry g, statuses straight into result's slices

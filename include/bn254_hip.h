@@ -269,6 +269,31 @@ int bn254_batch_aggregate_verify_registered(bn254_ctx *ctx, const uint32_t *tupl
 int bn254_batch_aggregate_verify_registered_device(bn254_ctx *ctx, const uint32_t *d_tuple_msg, const uint64_t *d_tuple_off, const uint32_t *d_signer_idx,
                                                    size_t n, uint8_t *d_status, void *stream);
 
+/* Aggregate signatures over DISTINCT messages (the IRTF BLS draft's AggregateVerify, cited at src/lib.rs:26-31): the pairs j in
+ * [agg_off[i], agg_off[i+1]) belong to aggregate i — message m_j = msgs[msg_off[j] .. msg_off[j+1]), key pk_j = pks[j*128] — whose
+ * signature agg_sigs[i*64] is the sum of the signers' signatures (`Add for Signature`, src/types.rs:264-270).  status[i] is the first of:
+ *   1. sigma_i's decode status, exactly as bn254_batch_verify decodes a signature (same flags);
+ *   2. the decode status of the first pk_j in j order that fails (BN254_FLAG_G2_SUBGROUP_CHECK / _REJECT_IDENTITY act as in verify);
+ *   3. the status of the first m_j that fails to hash: 1 (HashToPointError); in the _device form 5 for reversed or over-long offsets;
+ *   4. 0 if pairing_batch([(H(m_j), pk_j)..., (sigma_i, -G2::one())]) == Gt::one(), else 9.
+ * Consequences: k = 1 gives byte for byte the statuses of bn254_batch_verify on the same inputs; an EMPTY aggregate (k = 0) checks
+ * e(sigma, -G2) == 1, i.e. it is 0 iff sigma is the identity and the identity is accepted.
+ * Host form: agg_off[0] == 0, agg_off non-decreasing and agg_off[n] == m, msg_off non-decreasing, m, n < 2^32; anything else returns
+ * BN254_E_BAD_ARGUMENT.  _device form: an aggregate whose range is reversed, runs past m or starts before an earlier offset (the ranges of
+ * the accepted aggregates are disjoint) gets status 2 (IndexOutOfBounds) before anything else and no pairs — the convention of
+ * bn254_batch_aggregate_verify_device for tuple_off; bn254_ctx_expect_msgs_len applies.
+ * The check is exact (no random scalars).  Security: like the reference (src/lib.rs:34-38) it assumes a proof of possession of every key, and
+ * NO distinct-message check is made — a caller who needs the draft's basic-scheme rule must enforce it.
+ * Cost: one Miller loop per pair (two pairs of an aggregate share the squarings on a lane pair), one Miller loop of sigma and one final
+ * exponentiation per aggregate.  One call reserves workspace for m pairs + m / 64 partial products + n aggregates (792 B each; no automatic
+ * slicing): m is bounded by the device memory only (2^20 pairs in one aggregate take ~0.85 GB). */
+int bn254_batch_aggregate_verify_distinct(bn254_ctx *ctx, const uint8_t *msgs, const uint64_t *msg_off /* m+1 */, const uint8_t *pks /* m*128 */,
+                                          size_t m, const uint8_t *agg_sigs /* n*64 */, const uint64_t *agg_off /* n+1 */, size_t n, uint32_t flags,
+                                          uint8_t *status /* n */);
+int bn254_batch_aggregate_verify_distinct_device(bn254_ctx *ctx, const uint8_t *d_msgs, const uint64_t *d_msg_off, const uint8_t *d_pks, size_t m,
+                                                 const uint8_t *d_agg_sigs, const uint64_t *d_agg_off, size_t n, uint32_t flags, uint8_t *d_status,
+                                                 void *stream);
+
 /* compressed wire formats (src/utils.rs:84-104, :130-158): out = uncompressed point, status as
  * bn::G1::from_compressed / bn::G2::from_compressed report through src/types.rs:91-93, :233-237, checked in the order
  * those decoders work (an input with several faults reports the first):

@@ -147,6 +147,19 @@ __global__ void __launch_bounds__(256) k_issue_probe(uint32_t* out, uint32_t see
 extern "C" {
 
 // the routing table of the context (bn254_ws.h: bn_route_table) — tests iterate its boundaries
+// what the key deduplication of the last bn254_batch_verify_device decided on the device (bn254_keydedup.hip): out = {ran, distinct keys D,
+// flags (1 probe overflow, 2 degenerate line), items of the keyed Miller kernel, items of the generic one}; ran = 0: the call did not take
+// the dedup at all (other route, option off, no room), the other words are then 0.  Synchronises the device.
+int bn254_debug_key_dedup_last(bn254_ctx* c, uint32_t out[5]) {
+  if (!c || !out) return BN254_E_BAD_ARGUMENT;
+  for (int i = 0; i < 5; ++i) out[i] = 0;
+  if (!c->kd_last_run || !c->kd_ctl) return 0;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(out + 1, c->kd_ctl, KD_CTL_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  out[0] = 1;
+  return 0;
+}
 int bn254_debug_route_table(bn254_ctx* c, uint64_t* max_n, int* miller, int* fe, int cap) {
   if (!c || !max_n || !miller || !fe || cap < 5) return BN254_E_BAD_ARGUMENT;
   size_t m[5];

@@ -392,6 +392,7 @@ KERNEL_SMALL void k_encode_g1(size_t n, Ws ws, int px, int inf_plane, uint8_t* o
 int ctx_quiesce(bn254_ctx* c) {
   HIP_TRY(hipStreamSynchronize(c->stream));
   HIP_TRY(hipStreamSynchronize(c->copy_stream));
+  HIP_TRY(hipStreamSynchronize(c->kd_stream));
   if (c->last_done_armed) {                         // the last *_device call ran on a caller's stream: wait for the event recorded behind it
     c->last_done_armed = false;
     HIP_TRY(hipEventSynchronize(c->last_done));
@@ -419,22 +420,68 @@ int ws_reserve(bn254_ctx* c, size_t n) {
   return 0;
 }
 #define WS_BYTES_PER_ITEM ((size_t)N_PLANES * BN_LIMBS * sizeof(int32_t) + N_BYTE_PLANES + sizeof(uint32_t) + 1 + 2 * sizeof(uint32_t))
-size_t ws_chunk_for(bn254_ctx* c, size_t n) {
+size_t ws_chunk_for(bn254_ctx* c, size_t n, size_t ws_per_item, bool key_dedup) {
   if (c->max_chunk > 0) return n > (size_t)c->max_chunk ? (size_t)c->max_chunk : 0;
-  if (n <= c->ws.stride) return 0;                   // already reserved
+  if (n * ws_per_item <= c->ws.stride && (!key_dedup || (n <= c->kd_items_cap && (size_t)c->kd_max_keys <= c->kd_keys_cap))) return 0;   // already reserved
+  // per item: its workspace entries (two with BN254_OPT_SPLIT_MILLER) and the key-dedup words; per call: the dedup's key tables
+  const size_t per_item = ws_per_item * WS_BYTES_PER_ITEM + (key_dedup ? KD_BYTES_PER_ITEM : 0);
+  const size_t fixed = key_dedup ? (size_t)c->kd_max_keys * KD_BYTES_PER_KEY : 0;
   size_t avail;
   if (c->assume_free_mb > 0) avail = (size_t)c->assume_free_mb << 20;
   else {
     size_t fr = 0, total = 0;
     if (hipSetDevice(c->device) != hipSuccess || hipMemGetInfo(&fr, &total) != hipSuccess) { (void)hipGetLastError(); return 0; }
-    avail = fr + c->ws.stride * WS_BYTES_PER_ITEM;   // growing frees the present workspace first
+    avail = fr + c->ws.stride * WS_BYTES_PER_ITEM + c->kd_items_cap * KD_BYTES_PER_ITEM + c->kd_keys_cap * KD_BYTES_PER_KEY;   // growing frees the present buffers first
   }
-  const size_t need = ((n + 255) & ~(size_t)255) * WS_BYTES_PER_ITEM;
+  const size_t need = ((n + 255) & ~(size_t)255) * per_item + fixed;
   if (need <= avail / 10 * 9) return 0;
-  size_t chunk = (avail / 10 * 8) / WS_BYTES_PER_ITEM;
+  const size_t room = avail / 10 * 8 > fixed ? avail / 10 * 8 - fixed : 0;
+  size_t chunk = room / per_item;
   chunk &= ~(size_t)65535;
-  if (chunk == 0) chunk = (avail / 10 * 8) / WS_BYTES_PER_ITEM & ~(size_t)255;   // a very small device share: whatever fits (a failure to allocate is then reported as before)
+  if (chunk == 0) chunk = room / per_item & ~(size_t)255;   // a very small device share: whatever fits (a failure to allocate is then reported as before)
   return chunk && chunk < n ? chunk : 0;
+}
+// the key-dedup buffers (bn254_ws.h: KeyDedup) for n items and the context's max_keys, grown on demand
+#define KD_NO_ROOM 1
+static int kd_reserve(bn254_ctx* c, size_t n, KeyDedup& kd) {
+  size_t slots = 1;
+  while (slots < 2 * n) slots <<= 1;
+  const size_t keys = (size_t)c->kd_max_keys;
+  if (n > c->kd_items_cap || keys > c->kd_keys_cap) {
+    const size_t items_cap = n > c->kd_items_cap ? ((n + 255) & ~(size_t)255) : c->kd_items_cap;
+    const size_t keys_cap = keys > c->kd_keys_cap ? keys : c->kd_keys_cap;
+    { int rc_ = ctx_quiesce(c); if (rc_) return rc_; }
+    if (c->kd_buf) { HIP_TRY(hipFree(c->kd_buf)); c->kd_buf = nullptr; }
+    c->kd_items_cap = c->kd_keys_cap = 0;
+    c->kd_ctl = nullptr;
+    if (hipMalloc((void**)&c->kd_buf, items_cap * KD_BYTES_PER_ITEM + keys_cap * KD_BYTES_PER_KEY + 256) != hipSuccess) {
+      (void)hipGetLastError();                       // no room for the tables: this call takes the generic route (the caller sees no error)
+      c->kd_buf = nullptr;
+      return KD_NO_ROOM;
+    }
+    c->kd_items_cap = items_cap;
+    c->kd_keys_cap = keys_cap;
+  }
+  size_t slots_cap = 1;
+  while (slots_cap < 2 * c->kd_items_cap) slots_cap <<= 1;           // slot arrays sized for the capacity: <= 4 x items_cap words each
+  uint8_t* p = c->kd_buf;
+  auto take = [&](size_t bytes) { uint8_t* r = p; p += (bytes + 15) & ~(size_t)15; return r; };
+  kd.table = (uint32_t*)take(slots_cap * 4);
+  kd.slot_id = (uint32_t*)take(slots_cap * 4);
+  kd.slot_of = (uint32_t*)take(c->kd_items_cap * 4);
+  kd.key_idx = (uint32_t*)take(c->kd_items_cap * 4);
+  kd.lines = (int32_t*)take(c->kd_keys_cap * BN_N_FIXED_LINES * BN_KEY_LINE_WORDS * 4);
+  kd.c2 = (int32_t*)take(c->kd_keys_cap * BN_N_FIXED_LINES * 2 * BN_LIMBS * 4);
+  kd.rep = (uint32_t*)take(c->kd_keys_cap * 4);
+  kd.ctl = (uint32_t*)take(KD_CTL_WORDS * 4);
+  c->kd_ctl = kd.ctl;
+  kd.st = take(c->kd_keys_cap);
+  kd.inf = take(c->kd_keys_cap);
+  kd.slot_mask = (uint32_t)(slots - 1);
+  kd.hash_mask = c->kd_hash_bits > 0 && c->kd_hash_bits < 32 ? (1u << c->kd_hash_bits) - 1 : 0xFFFFFFFFu;
+  kd.max_keys = (uint32_t)keys;
+  kd.min_mult = (uint32_t)c->kd_min_mult;
+  return 0;
 }
 int stage_reserve(bn254_ctx* c, int slot, size_t bytes) {
   if (bytes <= c->stage_cap[slot]) return 0;
@@ -606,13 +653,22 @@ int bn254_ctx_create(int hip_device, bn254_ctx** out) {
   c->lm_max_batch = bn254_lm_fits_device() ? LM_MAX_BATCH_DEFAULT : 0;
   c->nonet_wide = 1;
   c->g2_fixed_base = 1;
+  c->key_dedup = 1;
+  c->kd_max_keys = KEY_DEDUP_MAX_KEYS_DEFAULT;
+  c->kd_min_mult = KEY_DEDUP_MIN_MULT_DEFAULT;
   c->device = hip_device;
   hipError_t err = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
   if (err == hipSuccess) err = hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking);
   if (err == hipSuccess) err = hipEventCreateWithFlags(&c->copy_done, hipEventDisableTiming);
   if (err == hipSuccess) err = hipEventCreateWithFlags(&c->last_done, hipEventDisableTiming);
+  if (err == hipSuccess) err = hipStreamCreateWithFlags(&c->kd_stream, hipStreamNonBlocking);
+  if (err == hipSuccess) err = hipEventCreateWithFlags(&c->kd_fork, hipEventDisableTiming);
+  if (err == hipSuccess) err = hipEventCreateWithFlags(&c->kd_join, hipEventDisableTiming);
   for (int i = 0; i < 5 && err == hipSuccess; ++i) err = hipEventCreate(&c->ev[i]);
   if (err != hipSuccess) {
+    if (c->kd_join) (void)hipEventDestroy(c->kd_join);
+    if (c->kd_fork) (void)hipEventDestroy(c->kd_fork);
+    if (c->kd_stream) (void)hipStreamDestroy(c->kd_stream);
     if (c->last_done) (void)hipEventDestroy(c->last_done);
     for (int i = 0; i < 5; ++i) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
     if (c->copy_done) (void)hipEventDestroy(c->copy_done);
@@ -647,7 +703,11 @@ void bn254_ctx_destroy(bn254_ctx* c) {
   if (c->key_st) (void)hipFree(c->key_st);
   if (c->key_inf) (void)hipFree(c->key_inf);
   if (c->aggd_buf) (void)hipFree(c->aggd_buf);
+  if (c->kd_buf) (void)hipFree(c->kd_buf);
   for (int i = 0; i < 5; ++i) (void)hipEventDestroy(c->ev[i]);
+  (void)hipEventDestroy(c->kd_fork);
+  (void)hipEventDestroy(c->kd_join);
+  (void)hipStreamDestroy(c->kd_stream);
   (void)hipEventDestroy(c->copy_done);
   (void)hipEventDestroy(c->last_done);
   (void)hipStreamSynchronize(c->copy_stream);
@@ -734,6 +794,11 @@ int bn254_ctx_set_option(bn254_ctx* c, int option, int value) {
   if (option == BN254_OPT_G2_FIXED_BASE) { c->g2_fixed_base = value != 0; return 0; }
   if (option == BN254_OPT_MAX_CHUNK) { if (value < 0) return BN254_E_BAD_ARGUMENT; c->max_chunk = value; return 0; }
   if (option == BN254_OPT_ASSUME_FREE_MB) { if (value < 0) return BN254_E_BAD_ARGUMENT; c->assume_free_mb = value; return 0; }
+  if (option == BN254_OPT_KEY_DEDUP) { if (value < 0 || value > 1) return BN254_E_BAD_ARGUMENT; c->key_dedup = value; return 0; }
+  if (option == BN254_OPT_KEY_DEDUP_MAX_KEYS) { if (value < 0 || value > KEY_DEDUP_MAX_KEYS_LIMIT) return BN254_E_BAD_ARGUMENT; c->kd_max_keys = value; return 0; }
+  if (option == BN254_OPT_KEY_DEDUP_MIN_MULT) { if (value < 1) return BN254_E_BAD_ARGUMENT; c->kd_min_mult = value; return 0; }
+  if (option == BN254_OPT_KEY_DEDUP_FORCE_GENERIC) { c->kd_force_generic = value != 0; return 0; }
+  if (option == BN254_OPT_KEY_DEDUP_HASH_BITS) { if (value < 0 || value > 32) return BN254_E_BAD_ARGUMENT; c->kd_hash_bits = value; return 0; }
   return BN254_E_BAD_ARGUMENT;
 }
 // clock probe (BN254_OPT_CLOCK_PROBE): the clock the chip ran the last Miller kernel [0], final exponentiation [1] and issue probe [2]
@@ -810,13 +875,24 @@ int launch_pair_or_trio(bn254_ctx* c, hipStream_t s, size_t n, int use_hash, uin
 
 extern "C" {
 // decode kernels have filled the P1 / Q planes and BY_ST_DECODE: hash, Miller loop, final exponentiation
-static int verify_after_decode(bn254_ctx* c, hipStream_t s, const uint8_t* d_msgs, const uint64_t* d_off, size_t n, uint8_t* d_status, bool split) {
+// kd: the key-dedup buffers when bn254_kd_enqueue runs beside decode and hash on c->kd_stream (joined by c->kd_join), else null
+static int verify_after_decode(bn254_ctx* c, hipStream_t s, const uint8_t* d_msgs, const uint64_t* d_off, size_t n, uint8_t* d_status, bool split,
+                               const KeyDedup* kd = nullptr) {
   int rc;
   unsigned g = grid_for(n);
   PROF_MARK(1);
   if ((rc = launch_hash_rounds(c, s, d_msgs, d_off, n, PL_P2X, BY_P2_INF, nullptr))) return rc;
   PROF_MARK(2);
-  if (split) {
+  if (kd) {
+    // both Miller kernels are enqueued; each reads its item count from the device-side decision (k_kd_decide) and one of them returns at
+    // once.  The wait for the builder counts in the Miller stage.
+    HIP_TRY(hipStreamWaitEvent(s, c->kd_join, 0));
+    const KeyTable kt = {kd->lines, kd->st, kd->inf, kd->max_keys};
+    if ((rc = bn254_pair_miller_verify_keyed(n, c->ws, kd->key_idx, kt, s, 0, nullptr, kd->ctl + KD_CTL_KEYED_N))) return rc;
+    if ((rc = bn254_pair_miller_verify(n, c->ws, nullptr, kd->ctl + KD_CTL_GENERIC_N, s))) return rc;
+    PROF_MARK(3);
+    if ((rc = bn254_pair_final_exp(n, c->ws, 1, d_status, nullptr, nullptr, s))) return rc;
+  } else if (split) {
     k_miller_verify_split<<<2 * g, BN_WAVE, 0, s>>>(n, c->ws.stride / 2, g, c->ws);
     PROF_MARK(3);
     k_final_exp<<<g, BN_WAVE, 0, s>>>(n, 2, 1, c->ws.stride / 2, c->ws, 1, nullptr, d_status, 0, 0, nullptr, nullptr);
@@ -844,7 +920,10 @@ int bn254_batch_verify_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_
   // loop; BN254_OPT_SPLIT_MILLER additionally runs one pairing per lane (two waves per verify) — both kept for A/B
   // runs, see profiles/r01_c_ab_occupancy.log and DESIGN.md section 4
   bool split = c->split_miller && n <= BN_SPLIT_MAX_N;
-  if (const size_t chunk = ws_chunk_for(c, n)) {
+  // key dedup (bn254_keydedup.hip): batches on the lane-pair Miller kernel look for repeated keys and take the keyed loop when they pay off
+  bool key_dedup = c->key_dedup && c->kd_max_keys > 0 && c->pair_lanes && !split && n <= 0xFFFFFFFFu &&
+                         route_for(c, n).miller == BN_ML_LANE_PAIRS && route_for(c, n).fe == BN_FE_LANE_PAIRS;
+  if (const size_t chunk = ws_chunk_for(c, n, split ? 2 : 1, key_dedup)) {
     // an oversized batch: slices of `chunk` items through this same entry point, one after the other on the caller's stream — the offsets are
     // absolute into d_msgs, so a slice is the same arrays further in; statuses land at the items' own positions (profiling: the last slice's)
     for (size_t lo = 0; lo < n; lo += chunk) {
@@ -856,12 +935,26 @@ int bn254_batch_verify_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_
   }
   int rc = ws_reserve(c, split ? 2 * n : n);
   if (rc) return rc;
+  KeyDedup kd;
+  if (key_dedup) {
+    rc = kd_reserve(c, n, kd);
+    if (rc == KD_NO_ROOM) key_dedup = false;
+    else if (rc) return rc;
+    rc = 0;
+  }
+  c->kd_last_run = key_dedup;
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   CallDone call_done(c, s);
   PROF_MARK(0);
+  if (key_dedup) {                                   // forked behind everything the caller's stream holds so far: d_pks is readable
+    HIP_TRY(hipEventRecord(c->kd_fork, s));
+    HIP_TRY(hipStreamWaitEvent(c->kd_stream, c->kd_fork, 0));
+    if ((rc = bn254_kd_enqueue(d_pks, n, flags, kd, c->kd_force_generic, c->kd_stream))) return rc;
+    HIP_TRY(hipEventRecord(c->kd_join, c->kd_stream));
+  }
   k_decode_g1<<<grid_for(n), BN_WAVE, 0, s>>>(d_sigs, n, flags, c->ws, PL_P1X, BY_P1_INF, 0);
   if ((rc = launch_decode_g2(c, s, d_pks, n, flags, 1))) return rc;
-  return verify_after_decode(c, s, d_msgs, d_off, n, d_status, split);
+  return verify_after_decode(c, s, d_msgs, d_off, n, d_status, split, key_dedup ? &kd : nullptr);
 }
 
 // the same from the COMPRESSED encodings callers store (serde, /root/reference/src/serde.rs:39, :54):

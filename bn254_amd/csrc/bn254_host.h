@@ -70,6 +70,17 @@ struct bn254_ctx {
   bool fits_w8, fits_quad, fits_trio;   // the device can hold a workgroup of the small-batch kernels (LDS), asked at creation
   uint8_t* aggd_buf;         // aggregate verify over distinct messages: the per-aggregate scans, the slot map and the partials' ids (bn254_aggdist.hip)
   size_t aggd_cap;
+  int key_dedup;             // BN254_OPT_KEY_DEDUP: verify on lane pairs finds the batch's distinct keys and runs the keyed Miller loop (bn254_keydedup.hip)
+  int kd_max_keys;           // BN254_OPT_KEY_DEDUP_MAX_KEYS
+  int kd_min_mult;           // BN254_OPT_KEY_DEDUP_MIN_MULT
+  int kd_force_generic;      // BN254_OPT_KEY_DEDUP_FORCE_GENERIC (developer hook): the device-side decision always says "generic"
+  int kd_hash_bits;          // BN254_OPT_KEY_DEDUP_HASH_BITS (test seam): bits of the key hash kept (0 = all), to force collisions
+  hipStream_t kd_stream;     // the dedup and the table builder run here, forked from and joined into the call's stream
+  hipEvent_t kd_fork, kd_join;
+  uint8_t* kd_buf;           // KeyDedup buffers (bn254_ws.h), grown on demand
+  size_t kd_items_cap, kd_keys_cap;
+  uint32_t* kd_ctl;          // the device-side decision of the last call that ran the dedup (bn254_debug_key_dedup_last)
+  int kd_last_run;           // ... and whether the last bn254_batch_verify_device ran it at all
 };
 
 struct ScopedEvents {
@@ -121,7 +132,9 @@ BN_HIDDEN int ws_reserve(bn254_ctx* c, size_t n);
 // Oversized batches: the slice length the verify-shaped entry points cut a batch of n items into, or 0 = one piece.  BN254_OPT_MAX_CHUNK when
 // set; otherwise only when the workspace of the whole batch (WS_BYTES_PER_ITEM each) would not fit what the device has free (+ what the
 // context's present workspace would give back): then the largest multiple of 65 536 items that fits in 80 % of it.
-BN_HIDDEN size_t ws_chunk_for(bn254_ctx* c, size_t n);
+// ws_per_item: workspace entries per item (2 with BN254_OPT_SPLIT_MILLER); key_dedup: the call also reserves the key-dedup buffers (bn254_ws.h:
+// KD_BYTES_PER_ITEM per item + KD_BYTES_PER_KEY per key of BN254_OPT_KEY_DEDUP_MAX_KEYS)
+BN_HIDDEN size_t ws_chunk_for(bn254_ctx* c, size_t n, size_t ws_per_item = 1, bool key_dedup = false);
 BN_HIDDEN int stage_reserve(bn254_ctx* c, int slot, size_t bytes);
 BN_HIDDEN int stage_in(bn254_ctx* c, int slot, const void* host, size_t bytes);
 BN_HIDDEN int stage_out(bn254_ctx* c, int slot, void* host, size_t bytes);

@@ -1,0 +1,75 @@
+// The arithmetic of the per-call key tables (bn254_keydedup.hip) in the PAIR layout, shared by the device kernels and their host emulation
+// (tests/test_keydedup_tables.py: word-for-word parity with g2_line_table + fp_canon, bound proof under -DBN_TRACK_BOUNDS).
+// g2_line_table (bn254_pairing.h) computes a key's 87 lines and scales each one by its own c2^-1 on the spot: 87 inversions in sequence.
+// Here the walk and the scaling are split — kd_walk_raw_lines emits the raw (c0, c1, c2) of every line, kd_scale_line turns one of them
+// into the c2 = 1 form with canonical limbs — so that the device runs the 87 scalings of a key side by side.  Same operations at the same
+// norm sites (290 .. 293) as g2_line_table: the same values and the same bounds.
+// Include after bn254_pairing.h (pair layout: BN_SPLIT_FP2).
+#pragma once
+
+namespace bn254 {
+
+// the twist-point walk of g2_line_table; emit(idx, c0, c1, c2) per line; returns true if some line has c2 = 0 (no table for this key)
+template <class Emit>
+BN_DEV bool kd_walk_raw_lines(const G2Affine& q, Emit&& emit) {
+  G2Proj t;
+  LineCoef l;
+  t.x = q.x; t.y = q.y; t.z = fp2_one();
+  const Fp2 q_yneg = fp2_neg(q.y);
+  bool degenerate = false;
+  int idx = 0;
+  auto line = [&]() {
+    const Fp2 c2 = NR(290, l.c2);
+    degenerate = fp2_is_zero(c2) || degenerate;
+    emit(idx++, NS(292, l.c0), NS(293, l.c1), c2);
+  };
+#if defined(__HIPCC__)
+#pragma clang loop unroll(disable)
+#endif
+  for (int d = 0; d < 64; ++d) {
+    dbl_step(t, l); line();
+    const int digit = C_ATE_NAF[d];
+    if (digit != 0) { add_step(t, l, q.x, fp2_select(digit > 0, q.y, q_yneg)); line(); }
+  }
+  add_step(t, l, fp2_mul(fp2_conj(q.x), fp2_load_const(C_TW_FROB_X1)), fp2_mul(fp2_conj(q.y), fp2_load_const(C_TW_FROB_Y1))); line();
+  add_step(t, l, fp2_mul(q.x, fp2_load_const(C_TW_FROB_X2)), q.y); line();
+  return degenerate;
+}
+// one raw line into the table form: (c0 / c2, c1 / c2), canonical limbs (what k_register_keys stores)
+BN_DEV void kd_scale_line(const Fp2& c0, const Fp2& c1, const Fp2& c2, Fp2& r0, Fp2& r1) {
+  const Fp2 inv = NS(291, fp2_inv(c2));
+  const Fp2 a = fp2_mul(c0, inv), b = fp2_mul(c1, inv);
+  BN_FOR_ROLES(k) { r0.c[k] = fp_canon(a.c[k]); r1.c[k] = fp_canon(b.c[k]); }
+}
+
+#if defined(__HIPCC__)
+// One uncompressed G2 point (/root/reference/src/utils.rs:107-116) on a lane pair: each lane reads, range-checks and converts the two
+// 32-byte words of its role; identity, range and curve rules combined over the pair.  The status of k_decode_g2_pair before its optional
+// subgroup ladder — the one decode both that kernel and the key-table builder run, so their statuses cannot drift apart.
+BN_DEV bool load_fp_be_checked(Fp& r, const uint8_t* p, uint32_t& any) {
+  const uint32_t* w = (const uint32_t*)p;
+  U256 t;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) { t.w[7 - k] = __builtin_bswap32(w[k]); any |= w[k]; }
+  bool ok = !u256_geq(t.w, C_Q);
+  r = fp_from_u256(t);
+  return ok;
+}
+BN_DEV uint8_t decode_g2_pair_role(G2Affine& q, const uint8_t* b, uint32_t flags) {
+  const unsigned role = threadIdx.x & 1u;
+  uint32_t any = 0;
+  bool ok = load_fp_be_checked(q.x.c[0], b + 32 * role, any);
+  ok = load_fp_be_checked(q.y.c[0], b + 64 + 32 * role, any) && ok;
+  any |= (uint32_t)bn_partner_word((int32_t)any);
+  ok = bn_pair_and(ok);
+  q.inf = any == 0;
+  uint8_t st = ST_OK;
+  if (q.inf) st = (flags & FLAG_REJECT_IDENTITY) ? (uint8_t)ST_INVALID_GROUP_POINT : (uint8_t)ST_OK;
+  else if (!ok) st = ST_NOT_MEMBER;
+  const bool on_curve = g2_on_curve(q);             // pair-combined; evaluated by every lane
+  if (st == ST_OK && !q.inf && !on_curve) st = ST_INVALID_GROUP_POINT;
+  return st;
+}
+#endif
+
+}  // namespace bn254

@@ -1,0 +1,155 @@
+// Translation unit of libbn254hip.so: KEY DEDUPLICATION of the exact verify (bn254_batch_verify_device on lane pairs).
+//
+// Pair A of a verify is e(H(m), pk); its twist-point walk (64 doublings, 23 additions: ~2.9 k of the 11.1 k Fq products of a verify's
+// Miller loop) depends on pk alone.  A validator-set batch uses few keys many times, so the call finds its distinct keys and tabulates
+// each one's 87 lines ONCE, in the exact format of bn254_ctx_register_keys (bn254_pairing.h: g2_line_table, c2 = 1, canonical limbs);
+// k_miller_verify_keyed_pair then runs the loop on the tables.  All of it is enqueued on a stream of the context beside the decode and
+// hash kernels of the call, and the route is decided ON THE DEVICE (no host sync):
+//   k_kd_insert   one lane per item: open addressing over 2n+ slots keyed by a hash of the 32 words of the key, atomicCAS; two items share
+//                 an entry only if all 128 bytes are equal (equal bytes decode equally, so grouping by bytes is exact).  The winner of a
+//                 slot takes the next dense key id (atomicAdd) and records itself as the key's representative.  A probe sequence longer
+//                 than KD_MAX_PROBES (an adversarial batch) sets KD_OVERFLOW: the call takes the generic route.
+//   k_kd_resolve  key_idx[i] = the id of item i's slot
+//   k_kd_lines    one key per lane pair: decode of the representative (the statuses of the items themselves stay what launch_decode_g2
+//                 writes), the twist-point walk of g2_line_table with the RAW lines (c0, c1, c2) stored; a line with c2 = 0 (not
+//                 reachable from the order-r subgroup, but keys are not subgroup-checked under flags = 0) sets KD_DEGENERATE
+//   k_kd_scale    one lane pair per (key, line): c0 / c2, c1 / c2, canonical — the arithmetic of g2_line_table's emit, so the tables
+//                 are word for word those of registration; the 87 inversions of a key run side by side instead of one after the other
+//   k_kd_decide   the route: keyed iff D <= max_keys, D * min_multiplicity <= n, no overflow, no degenerate line; written as the device-side
+//                 item counts the two Miller kernels read at entry (the unchosen one returns at once)
+#include <hip/hip_runtime.h>
+
+#define BN_SPLIT_FP2 1
+#define bn254 bn254_kd     // own namespace: the pair layout's types (bn254_fp2_pair.h)
+#include "bn254_pairing.h"
+#include "bn254_keydedup.h"
+
+using namespace bn254;
+
+#include "bn254_ws.h"
+
+#define KD_WG 256
+#define KERNEL_KD_PAIR __global__ __launch_bounds__(KD_WG) __attribute__((amdgpu_waves_per_eu(2, 2)))
+#define KERNEL_KD __global__ __launch_bounds__(KD_WG)
+#define KERNEL_KD_CHAIN __global__ __launch_bounds__(BN_WAVE) __attribute__((amdgpu_waves_per_eu(1, 1)))
+
+__device__ __forceinline__ uint32_t kd_hash(const uint32_t* w, uint32_t hash_mask) {
+  uint32_t h = 0x9E3779B9u;
+#pragma unroll
+  for (int k = 0; k < 32; ++k) {
+    h ^= w[k];
+    h *= 0x85EBCA6Bu;
+    h ^= h >> 13;
+  }
+  h ^= h >> 16; h *= 0xC2B2AE35u; h ^= h >> 16;
+  return h & hash_mask;
+}
+__device__ __forceinline__ bool kd_same_key(const uint32_t* pks, uint32_t other, const uint32_t* w) {
+  const uint32_t* o = pks + (size_t)other * 32;
+  bool eq = true;
+#pragma unroll
+  for (int k = 0; k < 32; ++k) eq = eq && o[k] == w[k];
+  return eq;
+}
+KERNEL_KD void k_kd_insert(const uint8_t* pks8, size_t n, KeyDedup kd) {
+  const size_t i = (size_t)blockIdx.x * KD_WG + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t* pks = (const uint32_t*)pks8;           // 4-byte aligned (the entry point checks)
+  uint32_t w[32];
+#pragma unroll
+  for (int k = 0; k < 32; ++k) w[k] = pks[i * 32 + k];
+  const uint32_t h = kd_hash(w, kd.hash_mask);
+  for (uint32_t probe = 0; probe < KD_MAX_PROBES; ++probe) {
+    const uint32_t s = (h + probe) & kd.slot_mask;
+    uint32_t cur = __atomic_load_n(&kd.table[s], __ATOMIC_RELAXED);
+    if (cur == KD_EMPTY) {
+      cur = atomicCAS(&kd.table[s], KD_EMPTY, (uint32_t)i);
+      if (cur == KD_EMPTY) {                                // this item represents a new key
+        const uint32_t id = atomicAdd(&kd.ctl[KD_CTL_D], 1u);
+        kd.slot_id[s] = id;
+        if (id < kd.max_keys) kd.rep[id] = (uint32_t)i;
+        kd.slot_of[i] = s;
+        return;
+      }
+    }
+    if (kd_same_key(pks, cur, w)) { kd.slot_of[i] = s; return; }   // full 128-byte compare: a hash match alone is not enough
+  }
+  kd.slot_of[i] = KD_EMPTY;
+  atomicOr(&kd.ctl[KD_CTL_FLAGS], (uint32_t)KD_OVERFLOW);
+}
+KERNEL_KD void k_kd_resolve(size_t n, KeyDedup kd) {
+  const size_t i = (size_t)blockIdx.x * KD_WG + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t s = kd.slot_of[i];
+  kd.key_idx[i] = s == KD_EMPTY ? 0u : kd.slot_id[s];
+}
+// the table route is possible at all (read by every lane of the builder kernels: wave-uniform)
+__device__ __forceinline__ bool kd_viable(const KeyDedup& kd, size_t n) {
+  const uint32_t d = kd.ctl[KD_CTL_D];
+  return d <= kd.max_keys && (size_t)d * kd.min_mult <= n && (kd.ctl[KD_CTL_FLAGS] & KD_OVERFLOW) == 0;
+}
+
+__device__ __forceinline__ void kd_store_own(int32_t* dst, const Fp2& x) {
+#pragma unroll
+  for (int k = 0; k < BN_LIMBS; ++k) dst[(threadIdx.x & 1u) * BN_LIMBS + k] = x.c[0].v[k];
+}
+__device__ __forceinline__ Fp2 kd_load_own(const int32_t* src) {
+  Fp2 r;
+#pragma unroll
+  for (int k = 0; k < BN_LIMBS; ++k) r.c[0].v[k] = src[(threadIdx.x & 1u) * BN_LIMBS + k];
+  return r;
+}
+// per key: the decode of its representative (bn254_keydedup.h: decode_g2_pair_role, the decode of k_decode_g2_pair; no subgroup ladder) and
+// the twist-point walk of g2_line_table with the RAW lines out: c0, c1 into the key's table rows (scaled in place by k_kd_scale), c2 into kd.c2.
+// One lane pair per key and a serial chain: one wave per workgroup, so that the chains spread over CUs (the 384 B of scratch per lane are
+// the call frames of the noinline step functions dbl_step / add_step, not spills)
+KERNEL_KD_CHAIN void k_kd_lines(const uint8_t* pks, size_t n, uint32_t flags, KeyDedup kd) {
+  if (!kd_viable(kd, n)) return;
+  const uint32_t j = (uint32_t)(((size_t)blockIdx.x * BN_WAVE + threadIdx.x) >> 1);
+  if (j >= kd.ctl[KD_CTL_D]) return;                     // both lanes of a pair leave together
+  __builtin_amdgcn_s_setprio(3);                         // a latency chain beside the hash rounds' throughput waves
+  G2Affine q;
+  const uint8_t st = decode_g2_pair_role(q, pks + 128 * (size_t)kd.rep[j], flags);
+  const bool real = st == ST_OK && !q.inf;               // a refused key or the identity: generator lines (its pair A is skipped)
+  if (!real) { q.x = fp2_load_const(C_G2_GEN[0]); q.y = fp2_load_const(C_G2_GEN[1]); }
+  if ((threadIdx.x & 1u) == 0) { kd.st[j] = st; kd.inf[j] = q.inf; }
+  int32_t* rows = kd.lines + (size_t)j * BN_N_FIXED_LINES * BN_KEY_LINE_WORDS;
+  int32_t* c2s = kd.c2 + (size_t)j * BN_N_FIXED_LINES * 2 * BN_LIMBS;
+  const bool degenerate = kd_walk_raw_lines(q, [&](int idx, const Fp2& c0, const Fp2& c1, const Fp2& c2) {
+    kd_store_own(c2s + (size_t)idx * 2 * BN_LIMBS, c2);
+    kd_store_own(rows + (size_t)idx * BN_KEY_LINE_WORDS, c0);
+    kd_store_own(rows + (size_t)idx * BN_KEY_LINE_WORDS + 2 * BN_LIMBS, c1);
+  });
+  if (real && degenerate && (threadIdx.x & 1u) == 0) atomicOr(&kd.ctl[KD_CTL_FLAGS], (uint32_t)KD_DEGENERATE);
+}
+// one lane pair per (key, line): (c0, c1) <- canonical (c0 / c2, c1 / c2)
+KERNEL_KD_PAIR void k_kd_scale(size_t n, KeyDedup kd) {
+  if (!kd_viable(kd, n)) return;
+  const size_t p = ((size_t)blockIdx.x * KD_WG + threadIdx.x) >> 1;
+  const uint32_t j = (uint32_t)(p / BN_N_FIXED_LINES), idx = (uint32_t)(p % BN_N_FIXED_LINES);
+  if (j >= kd.ctl[KD_CTL_D]) return;
+  int32_t* row = kd.lines + ((size_t)j * BN_N_FIXED_LINES + idx) * BN_KEY_LINE_WORDS;
+  Fp2 r0, r1;
+  kd_scale_line(kd_load_own(row), kd_load_own(row + 2 * BN_LIMBS), kd_load_own(kd.c2 + ((size_t)j * BN_N_FIXED_LINES + idx) * 2 * BN_LIMBS), r0, r1);
+  kd_store_own(row, r0);
+  kd_store_own(row + 2 * BN_LIMBS, r1);
+}
+KERNEL_KD void k_kd_decide(size_t n, KeyDedup kd, int force_generic) {
+  if (threadIdx.x != 0) return;
+  const bool keyed = !force_generic && kd_viable(kd, n) && (kd.ctl[KD_CTL_FLAGS] & KD_DEGENERATE) == 0;
+  kd.ctl[KD_CTL_KEYED_N] = keyed ? (uint32_t)n : 0u;
+  kd.ctl[KD_CTL_GENERIC_N] = keyed ? 0u : (uint32_t)n;
+}
+
+int bn254_kd_enqueue(const uint8_t* d_pks, size_t n, uint32_t flags, KeyDedup kd, int force_generic, hipStream_t s) {
+  HIP_TRY(hipMemsetAsync(kd.table, 0xFF, ((size_t)kd.slot_mask + 1) * sizeof(uint32_t), s));
+  HIP_TRY(hipMemsetAsync(kd.ctl, 0, KD_CTL_WORDS * sizeof(uint32_t), s));
+  const unsigned g = (unsigned)((n + KD_WG - 1) / KD_WG);
+  k_kd_insert<<<g, KD_WG, 0, s>>>(d_pks, n, kd);
+  k_kd_resolve<<<g, KD_WG, 0, s>>>(n, kd);
+  k_kd_lines<<<(unsigned)((2 * (size_t)kd.max_keys + BN_WAVE - 1) / BN_WAVE), BN_WAVE, 0, s>>>(d_pks, n, flags, kd);
+  k_kd_scale<<<(unsigned)((2 * (size_t)kd.max_keys * BN_N_FIXED_LINES + KD_WG - 1) / KD_WG), KD_WG, 0, s>>>(n, kd);
+  k_kd_decide<<<1, BN_WAVE, 0, s>>>(n, kd, force_generic);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}

@@ -213,6 +213,33 @@ __attribute__((visibility("hidden"))) int bn254_lm_miller_verify_keyed(size_t n,
 __attribute__((visibility("hidden"))) int bn254_pair_miller_verify_keyed(size_t n, Ws ws, const uint32_t* key_idx, KeyTable kt, hipStream_t s, size_t base = 0,
                                                                          const uint32_t* map = nullptr, const uint32_t* count = nullptr);
 
+// key deduplication of the exact verify (bn254_keydedup.hip): per call, the distinct keys of the batch and their line tables in the
+// KeyTable format above, built on a stream of the context beside decode and hash; the route (tables or the generic loop) is decided on the device
+#define KEY_DEDUP_MAX_KEYS_DEFAULT 1024            // tables for at most this many distinct keys per call (12.5 KB + 6.3 KB of raw c2 each)
+#define KEY_DEDUP_MIN_MULT_DEFAULT 16              // ... and only when every key serves this many items on average
+#define KEY_DEDUP_MAX_KEYS_LIMIT 16384             // BN254_OPT_KEY_DEDUP_MAX_KEYS at most (308 MB of tables)
+#define KD_MAX_PROBES 64u                          // open addressing: a longer probe sequence sends the call to the generic route
+#define KD_EMPTY 0xFFFFFFFFu
+enum { KD_OVERFLOW = 1, KD_DEGENERATE = 2 };
+enum { KD_CTL_D = 0, KD_CTL_FLAGS, KD_CTL_KEYED_N, KD_CTL_GENERIC_N, KD_CTL_WORDS = 4 };
+struct KeyDedup {
+  uint32_t* table;     // [slot_mask + 1] representative item of the slot, KD_EMPTY
+  uint32_t* slot_id;   // [slot_mask + 1] key id of the slot (written by its representative)
+  uint32_t* slot_of;   // [n] slot of the item (KD_EMPTY: probe overflow)
+  uint32_t* key_idx;   // [n] key id of the item
+  uint32_t* rep;       // [max_keys] representative item of the key
+  uint32_t* ctl;       // [KD_CTL_WORDS] distinct keys D, flags, item counts of the keyed / generic Miller kernel
+  int32_t* lines;      // [max_keys][87][c0, c1][re, im][9]
+  int32_t* c2;         // [max_keys][87][re, im][9] raw c2 of the lines
+  uint8_t* st;         // [max_keys] decode status of the representative
+  uint8_t* inf;        // [max_keys] identity flag
+  uint32_t slot_mask, hash_mask, max_keys, min_mult;
+};
+__attribute__((visibility("hidden"))) int bn254_kd_enqueue(const uint8_t* d_pks, size_t n, uint32_t flags, KeyDedup kd, int force_generic, hipStream_t s);
+// per-item and per-key bytes of the buffers above (slot arrays: at most 4n words each, the next power of two >= 2n)
+#define KD_BYTES_PER_ITEM ((size_t)(2 * 4 + 2) * sizeof(uint32_t))
+#define KD_BYTES_PER_KEY ((size_t)BN_N_FIXED_LINES * (BN_KEY_LINE_WORDS + 2 * BN_LIMBS) * sizeof(int32_t) + sizeof(uint32_t) + 2)
+
 // entry points of bn254_trio.hip (octet layout for small batches)
 __attribute__((visibility("hidden"))) int bn254_trio_miller_verify(size_t n, Ws ws, hipStream_t s, int mode = 0);
 // entry points of bn254_quad.hip (the same with the four lane pairs of a verify as four waves with roles)

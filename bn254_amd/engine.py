@@ -31,6 +31,11 @@ OPT_AGG_WIDE_MIN_TUPLES = 14
 OPT_MAX_CHUNK = 17          # verify-shaped batches above this size are processed in slices (0 = only when the workspace would not fit)
 OPT_ASSUME_FREE_MB = 18
 OPT_G2_FIXED_BASE = 19      # developer option: key derivation through the comb table of the generator (default 1)     # test knob of the automatic slicing rule
+OPT_KEY_DEDUP = 20           # verify on lane pairs: distinct keys found and tabulated per call, keyed Miller loop when it pays (default 1)
+OPT_KEY_DEDUP_MAX_KEYS = 21  # ... for at most this many distinct keys (default 1024)
+OPT_KEY_DEDUP_MIN_MULT = 22  # ... and at least this many items per key (default 16)
+OPT_KEY_DEDUP_FORCE_GENERIC = 23   # test hook: the device-side decision always takes the generic loop
+OPT_KEY_DEDUP_HASH_BITS = 24       # test seam: bits of the dedup hash kept (0 = all)
 
 
 class NativeError(RuntimeError):
@@ -117,6 +122,12 @@ class Engine:
         if rows < 0:
             _check("bn254_debug_route_table", rows)
         return [(int(m[i]), int(a[i]), int(b[i])) for i in range(rows)]
+
+    def debug_key_dedup_last(self):
+        """the key dedup's device-side decision of the last batch_verify_device: dict(ran, keys, flags, keyed_n, generic_n)"""
+        o = (ctypes.c_uint32 * 5)()
+        _check("bn254_debug_key_dedup_last", self._lib.bn254_debug_key_dedup_last(self._h, o))
+        return dict(zip(("ran", "keys", "flags", "keyed_n", "generic_n"), (int(x) for x in o)))
 
     def last_kernel_ms(self):
         ms = (ctypes.c_float * 4)()

@@ -343,6 +343,13 @@ int bn254_ctx_set_profiling(bn254_ctx *ctx, int enabled);
                                 is processed in slices of this size (the 792 B/item workspace of a slice is reused; statuses land at the items'
                                 own positions, so the result is that of one call).  0 (default) = automatic: slice only when the workspace of
                                 the whole batch does not fit the device's free memory */
+#define BN254_OPT_KEY_DEDUP 20 /* bn254_batch_verify_device on lane pairs (batches above the small-batch family): 1 (default) = find the batch's distinct
+                                public keys on the device and tabulate each one's 87 Miller-loop lines once per call (the format of
+                                bn254_ctx_register_keys), beside the decode and hash kernels on a stream of the context; the Miller loop then reads
+                                the tables (k_miller_verify_keyed_pair) when the thresholds below hold, decided on the device without a host sync.
+                                0 = always the generic loop.  Same status bytes either way */
+#define BN254_OPT_KEY_DEDUP_MAX_KEYS 21 /* ... tables for at most this many distinct keys per call (default 1024; 18.8 KB of device memory each) */
+#define BN254_OPT_KEY_DEDUP_MIN_MULT 22 /* ... and only when the batch has at least this many items per distinct key (default 16) */
 int bn254_ctx_set_option(bn254_ctx *ctx, int option, int value);
 /* per-kernel times of the last verify-shaped call with profiling on (HIP events on the call's stream):
  * ms[0] decode, ms[1] hash-to-G1, ms[2] Miller loop, ms[3] final exponentiation.  The host-pointer bn254_batch_verify runs
@@ -473,12 +480,20 @@ int bn254_mgpu_batch_hash_to_g1(bn254_mgpu *mg, const uint8_t *msgs, const uint6
 #define BN254_OPT_HASH_MAX_TRIES 2 /* test knob: counters tried before HashToPointError; 0 = 255 as in src/hash.rs:40 */
 #define BN254_OPT_G2_FIXED_BASE 19 /* key derivation (bn254_batch_g2_mul with points = NULL: sk * G2::one()): 1 (default) = 65 additions from a table of the
                                    generator's multiples, built once per context, on a lane pair; 0 = the general 256-step ladder on one lane.  Same bytes. */
+#define BN254_OPT_KEY_DEDUP_FORCE_GENERIC 23 /* test hook: the key-dedup route is prepared as usual but the device-side decision always takes the generic
+                                             Miller loop (the fallback path of an overflowing or degenerate batch); default 0 */
+#define BN254_OPT_KEY_DEDUP_HASH_BITS 24 /* test seam: keep only this many low bits of the key hash of the dedup table (0 = all, default), so that
+                                         distinct keys collide: the full 128-byte compare and the probe bound (overflow -> generic loop) */
 #define BN254_OPT_ASSUME_FREE_MB 18 /* test knob for the automatic slicing rule (BN254_OPT_MAX_CHUNK = 0): price the workspace of a batch against this many MB
                                     of free device memory instead of what hipMemGetInfo reports; 0 = ask the runtime */
 /* the routing table of this context as it stands (defaults + options): rows (max_n[i], miller[i], fe[i]) in ascending order of max_n, the last
  * row max_n = UINT64_MAX; miller: 0 lane machine, 1 wave roles, 2 lane pairs; fe: 0 eighteen lane pairs, 1 nine lane pairs, 2 octets, 3 lane
  * pairs.  Returns the number of rows (<= cap) or a negative error.  The parity tests generate every boundary +-1 from it. */
 int bn254_debug_route_table(bn254_ctx *ctx, uint64_t *max_n, int *miller, int *fe, int cap);
+/* the device-side decision of the key deduplication of the last bn254_batch_verify_device (BN254_OPT_KEY_DEDUP): out = {ran, distinct keys,
+ * flags (1 probe overflow, 2 degenerate line), items of the keyed Miller kernel, items of the generic one}; all 0 when the call did not run
+ * the dedup.  Synchronises the device. */
+int bn254_debug_key_dedup_last(bn254_ctx *ctx, uint32_t out[5]);
 /* test hooks: element-wise field/tower operations on byte-encoded operands, used by the parity
  * tests to compare each layer of the HIP arithmetic with the oracle.
  *   op: 0 mul, 1 add, 2 sub, 3 inverse(a), 4 square(a), 5 sqrt(a) (status 6 if none)   [Fq, 32 B]

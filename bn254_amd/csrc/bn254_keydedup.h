@@ -3,7 +3,9 @@
 // g2_line_table (bn254_pairing.h) computes a key's 87 lines and scales each one by its own c2^-1 on the spot: 87 inversions in sequence.
 // Here the walk and the scaling are split — kd_walk_raw_lines emits the raw (c0, c1, c2) of every line, kd_scale_line turns one of them
 // into the c2 = 1 form with canonical limbs — so that the device runs the 87 scalings of a key side by side.  Same operations at the same
-// norm sites (290 .. 293) as g2_line_table: the same values and the same bounds.
+// norm sites (290 .. 293) as g2_line_table: the same values and the same bounds.  kd_walk_raw_lines is the reference formulation of the
+// walk (one lane pair, one step after the other); the device builder runs the same walk as the lane machine's level program
+// (bn254_kdlines.h), whose raw lines tests/test_kd_builder.py checks against it.
 // Include after bn254_pairing.h (pair layout: BN_SPLIT_FP2).
 #pragma once
 

@@ -10,9 +10,10 @@
 //                 slot takes the next dense key id (atomicAdd) and records itself as the key's representative.  A probe sequence longer
 //                 than KD_MAX_PROBES (an adversarial batch) sets KD_OVERFLOW: the call takes the generic route.
 //   k_kd_resolve  key_idx[i] = the id of item i's slot
-//   k_kd_lines    one key per lane pair: decode of the representative (the statuses of the items themselves stay what launch_decode_g2
-//                 writes), the twist-point walk of g2_line_table with the RAW lines (c0, c1, c2) stored; a line with c2 = 0 (not
-//                 reachable from the order-r subgroup, but keys are not subgroup-checked under flags = 0) sets KD_DEGENERATE
+//   k_kd_lines    one key on nine lane pairs, three keys per wave (bn254_kdlines.h: the lane machine's wave-T program, 204 product levels):
+//                 decode of the representative (the statuses of the items themselves stay what launch_decode_g2 writes), the twist-point
+//                 walk of g2_line_table with the RAW lines (c0, c1, c2) stored; a line with c2 = 0 (not reachable from the order-r subgroup,
+//                 but keys are not subgroup-checked under flags = 0) sets KD_DEGENERATE
 //   k_kd_scale    one lane pair per (key, line): c0 / c2, c1 / c2, canonical — the arithmetic of g2_line_table's emit, so the tables
 //                 are word for word those of registration; the 87 inversions of a key run side by side instead of one after the other
 //   k_kd_decide   the route: keyed iff D <= max_keys, D * min_multiplicity <= n, no overflow, no degenerate line; written as the device-side
@@ -23,6 +24,8 @@
 #define bn254 bn254_kd     // own namespace: the pair layout's types (bn254_fp2_pair.h)
 #include "bn254_pairing.h"
 #include "bn254_keydedup.h"
+#include "bn254_lmachine.h"
+#include "bn254_kdlines.h"
 
 using namespace bn254;
 
@@ -31,7 +34,6 @@ using namespace bn254;
 #define KD_WG 256
 #define KERNEL_KD_PAIR __global__ __launch_bounds__(KD_WG) __attribute__((amdgpu_waves_per_eu(2, 2)))
 #define KERNEL_KD __global__ __launch_bounds__(KD_WG)
-#define KERNEL_KD_CHAIN __global__ __launch_bounds__(BN_WAVE) __attribute__((amdgpu_waves_per_eu(1, 1)))
 
 __device__ __forceinline__ uint32_t kd_hash(const uint32_t* w, uint32_t hash_mask) {
   uint32_t h = 0x9E3779B9u;
@@ -99,28 +101,106 @@ __device__ __forceinline__ Fp2 kd_load_own(const int32_t* src) {
   for (int k = 0; k < BN_LIMBS; ++k) r.c[0].v[k] = src[(threadIdx.x & 1u) * BN_LIMBS + k];
   return r;
 }
-// per key: the decode of its representative (bn254_keydedup.h: decode_g2_pair_role, the decode of k_decode_g2_pair; no subgroup ladder) and
-// the twist-point walk of g2_line_table with the RAW lines out: c0, c1 into the key's table rows (scaled in place by k_kd_scale), c2 into kd.c2.
-// One lane pair per key and a serial chain: one wave per workgroup, so that the chains spread over CUs (the 384 B of scratch per lane are
-// the call frames of the noinline step functions dbl_step / add_step, not spills)
-KERNEL_KD_CHAIN void k_kd_lines(const uint8_t* pks, size_t n, uint32_t flags, KeyDedup kd) {
+// The builder (bn254_kdlines.h): one key on nine lane pairs, three keys per wave, one wave per workgroup, so that the keys spread over CUs;
+// per key and lane role a register file in LDS.  Every lane of a key decodes its representative (bn254_keydedup.h: decode_g2_pair_role,
+// the decode of k_decode_g2_pair; no subgroup ladder); a refused key or the identity gets the generator's lines (its pair A is skipped).
+// Then the lane machine's wave-T program: after each step pairs 0 / 1 / 2 store the RAW line's c0, c1 into the key's table row (scaled in
+// place by k_kd_scale) and its c2 into kd.c2.  Lanes 54 .. 63 follow along on copies of the third key, without writing.
+#define KD_LM_PER_WAVE 3                           // keys per wave
+#define KD_LM_LANES 18                             // lanes per key: nine lane pairs
+#define KD_LM_ROLE_STRIDE (LS_KD_SLOTS * BN_LIMBS + 1)
+#define KD_LM_KEY_STRIDE (2 * KD_LM_ROLE_STRIDE)
+#define KD_LM_LDS_WORDS (KD_LM_PER_WAVE * KD_LM_KEY_STRIDE)
+static_assert(KD_LM_PER_WAVE * KD_LM_LANES <= BN_WAVE, "keys per wave");
+#define KERNEL_KD_LM __global__ __launch_bounds__(BN_WAVE) __attribute__((amdgpu_waves_per_eu(1, 1)))
+#define KD_LM_FENCE() do { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); } while (0)
+
+extern __shared__ int32_t kd_lds[];
+
+struct KdLdsBox {
+  typedef unsigned Ref;
+  unsigned base;                 // word offset of slot 0 of the lane's key and role
+  __device__ __forceinline__ Ref slot(uint32_t id) const { return base + id * BN_LIMBS; }
+  __device__ __forceinline__ Fp2 get(Ref off) const {
+    Fp2 r;
+#pragma unroll
+    for (int i = 0; i < BN_LIMBS; ++i) r.c[0].v[i] = kd_lds[off + i];
+    return r;
+  }
+  __device__ __forceinline__ void put(Ref off, const Fp2& x) const {
+#pragma unroll
+    for (int i = 0; i < BN_LIMBS; ++i) kd_lds[off + i] = x.c[0].v[i];
+  }
+};
+// the machine kd_builder_program drives, on the lanes of one key
+struct KdLmDev {
+  KdLdsBox bx;
+  LmEntry e[KD_LV_N];            // this pair's entry of every level
+  unsigned pair;
+  bool writer, live, degenerate;
+  int32_t* rows;
+  int32_t* c2s;
+  // products, publish, linear combinations, publish; a wave's LDS instructions execute in order, the fences keep the compiler's order
+  __device__ __forceinline__ void level(int lv) {
+    const LmEntry& en = e[lv];
+    {
+      const Fp2 pr = lm_stage_product(en, bx, 0);
+      KD_LM_FENCE();
+      if (writer && (en.w[1] & 255u) != (uint32_t)LS_DUMMY) bx.put(lm_product_out(en, bx, 0), pr);
+      KD_LM_FENCE();
+    }
+    const Fp2 li = lm_stage_linear(en, bx, 0, false, false);
+    KD_LM_FENCE();
+    if (writer && (en.w[4] & 255u) != (uint32_t)LS_DUMMY) bx.put(lm_linear_out(en, bx, 0), li);
+    KD_LM_FENCE();
+  }
+  __device__ __forceinline__ void add_point(int qx, int qy) {
+    const Fp2 x = bx.get(bx.slot((uint32_t)qx)), y = bx.get(bx.slot((uint32_t)qy));
+    if (writer) { bx.put(bx.slot(LS_TQX), x); bx.put(bx.slot(LS_TQY), y); }   // identical words from every pair of the key
+    KD_LM_FENCE();
+  }
+  __device__ __forceinline__ void line(int idx, int kind) {
+    degenerate = fp2_is_zero(bx.get(bx.slot((uint32_t)kd_line_slot(kind, 2)))) || degenerate;   // pair-combined: every lane
+    const int c = pair < 3 ? (int)pair : 2;
+    const Fp2 v = bx.get(bx.slot((uint32_t)kd_line_slot(kind, c)));
+    if (live && pair < 3) kd_store_own(c == 2 ? c2s + (size_t)idx * 2 * BN_LIMBS : rows + (size_t)idx * BN_KEY_LINE_WORDS + (size_t)c * 2 * BN_LIMBS, v);
+  }
+};
+KERNEL_KD_LM void k_kd_lines(const uint8_t* pks, size_t n, uint32_t flags, KeyDedup kd) {
   if (!kd_viable(kd, n)) return;
-  const uint32_t j = (uint32_t)(((size_t)blockIdx.x * BN_WAVE + threadIdx.x) >> 1);
-  if (j >= kd.ctl[KD_CTL_D]) return;                     // both lanes of a pair leave together
+  const uint32_t d = kd.ctl[KD_CTL_D];
+  if ((uint32_t)blockIdx.x * KD_LM_PER_WAVE >= d) return;                       // the whole wave leaves
   __builtin_amdgcn_s_setprio(3);                         // a latency chain beside the hash rounds' throughput waves
+  const unsigned l = threadIdx.x, v = l / KD_LM_LANES, role = l & 1u;
+  KdLmDev m;
+  m.writer = v < KD_LM_PER_WAVE;
+  const unsigned vslot = m.writer ? v : KD_LM_PER_WAVE - 1;
+  m.pair = (l % KD_LM_LANES) >> 1;
+  uint32_t j = (uint32_t)blockIdx.x * KD_LM_PER_WAVE + vslot;
+  m.live = m.writer && j < d;
+  if (j >= d) j = d - 1;                                 // lanes without a key of their own follow along on the last one
+  m.bx.base = vslot * KD_LM_KEY_STRIDE + role * KD_LM_ROLE_STRIDE;
   G2Affine q;
   const uint8_t st = decode_g2_pair_role(q, pks + 128 * (size_t)kd.rep[j], flags);
   const bool real = st == ST_OK && !q.inf;               // a refused key or the identity: generator lines (its pair A is skipped)
   if (!real) { q.x = fp2_load_const(C_G2_GEN[0]); q.y = fp2_load_const(C_G2_GEN[1]); }
-  if ((threadIdx.x & 1u) == 0) { kd.st[j] = st; kd.inf[j] = q.inf; }
-  int32_t* rows = kd.lines + (size_t)j * BN_N_FIXED_LINES * BN_KEY_LINE_WORDS;
-  int32_t* c2s = kd.c2 + (size_t)j * BN_N_FIXED_LINES * 2 * BN_LIMBS;
-  const bool degenerate = kd_walk_raw_lines(q, [&](int idx, const Fp2& c0, const Fp2& c1, const Fp2& c2) {
-    kd_store_own(c2s + (size_t)idx * 2 * BN_LIMBS, c2);
-    kd_store_own(rows + (size_t)idx * BN_KEY_LINE_WORDS, c0);
-    kd_store_own(rows + (size_t)idx * BN_KEY_LINE_WORDS + 2 * BN_LIMBS, c1);
-  });
-  if (real && degenerate && (threadIdx.x & 1u) == 0) atomicOr(&kd.ctl[KD_CTL_FLAGS], (uint32_t)KD_DEGENERATE);
+  if (m.live && m.pair == 0 && role == 0) { kd.st[j] = st; kd.inf[j] = q.inf; }
+  if (m.writer) {
+    m.bx.put(m.bx.slot(LS_ZERO), fp2_zero()); m.bx.put(m.bx.slot(LS_DUMMY), fp2_zero());
+    kd_builder_init(m.bx, q);
+  }
+#pragma unroll
+  for (int lv = 0; lv < KD_LV_N; ++lv) {
+    const LmEntry* t = kd_level_table(lv);
+#pragma unroll
+    for (int k = 0; k < 5; ++k) m.e[lv].w[k] = t[m.pair].w[k];
+  }
+  m.rows = kd.lines + (size_t)j * BN_N_FIXED_LINES * BN_KEY_LINE_WORDS;
+  m.c2s = kd.c2 + (size_t)j * BN_N_FIXED_LINES * 2 * BN_LIMBS;
+  m.degenerate = false;
+  KD_LM_FENCE();
+  kd_builder_program(m);
+  if (m.live && real && m.degenerate && m.pair == 0 && role == 0) atomicOr(&kd.ctl[KD_CTL_FLAGS], (uint32_t)KD_DEGENERATE);
 }
 // one lane pair per (key, line): (c0, c1) <- canonical (c0 / c2, c1 / c2)
 KERNEL_KD_PAIR void k_kd_scale(size_t n, KeyDedup kd) {
@@ -147,7 +227,7 @@ int bn254_kd_enqueue(const uint8_t* d_pks, size_t n, uint32_t flags, KeyDedup kd
   const unsigned g = (unsigned)((n + KD_WG - 1) / KD_WG);
   k_kd_insert<<<g, KD_WG, 0, s>>>(d_pks, n, kd);
   k_kd_resolve<<<g, KD_WG, 0, s>>>(n, kd);
-  k_kd_lines<<<(unsigned)((2 * (size_t)kd.max_keys + BN_WAVE - 1) / BN_WAVE), BN_WAVE, 0, s>>>(d_pks, n, flags, kd);
+  k_kd_lines<<<(unsigned)((kd.max_keys + KD_LM_PER_WAVE - 1) / KD_LM_PER_WAVE), BN_WAVE, KD_LM_LDS_WORDS * sizeof(int32_t), s>>>(d_pks, n, flags, kd);
   k_kd_scale<<<(unsigned)((2 * (size_t)kd.max_keys * BN_N_FIXED_LINES + KD_WG - 1) / KD_WG), KD_WG, 0, s>>>(n, kd);
   k_kd_decide<<<1, BN_WAVE, 0, s>>>(n, kd, force_generic);
   HIP_TRY(hipGetLastError());

@@ -439,6 +439,9 @@ size_t ws_chunk_for(bn254_ctx* c, size_t n, size_t ws_per_item, bool key_dedup) 
   size_t chunk = room / per_item;
   chunk &= ~(size_t)65535;
   if (chunk == 0) chunk = room / per_item & ~(size_t)255;   // a very small device share: whatever fits (a failure to allocate is then reported as before)
+  // the key tables leave no room for a slice that would still take the dedup route: price the generic route instead (its slices are then too
+  // small for the dedup, or kd_reserve finds no room for the tables and the slice takes the generic loop, KD_NO_ROOM) — never "do not slice"
+  if (key_dedup && (chunk == 0 || route_for(c, chunk).miller != BN_ML_LANE_PAIRS)) return ws_chunk_for(c, n, ws_per_item, false);
   return chunk && chunk < n ? chunk : 0;
 }
 // the key-dedup buffers (bn254_ws.h: KeyDedup) for n items and the context's max_keys, grown on demand

@@ -26,6 +26,73 @@ class SoakMismatch(AssertionError):
 R_ORDER = 0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001
 
 
+KD_MSG_LENS = (0, 1, 31, 55, 56, 64, 119, 120, 160)
+TWIST_SMALL_ORDER = 10069          # #E'(Fq2) = r * 10069 * (a 241-bit prime)
+
+
+def twist_small_order_key(rnd):
+    """the encoding of a point of the twist's subgroup of order 10 069: on the curve, outside G2"""
+    from oracle import bn254_model as M
+    cof = (2 * M.Q - M.R) // TWIST_SMALL_ORDER
+    while True:
+        x = (rnd.randrange(M.Q), rnd.randrange(M.Q))
+        y = M.f2_sqrt(M.f2_add(M.f2_mul(M.f2_mul(x, x), x), M.B2))
+        if y is None:
+            continue
+        p = M.g2_mul((x, y), M.R * cof)
+        if p is not None:
+            return M.g2_to_uncompressed(p)
+
+
+def dedup_batch(eng, rnd, n, sks, pk_pool, odd_keys, tag):
+    """n items over the len(sks) keys of pk_pool and 3 - 4 mutated variants of each — a bit flip at a random byte, a coordinate >= q in one of
+    the four 32-byte fields, 128 random bytes, or one of odd_keys (identity, outside G2, ...) —, so that a few hundred distinct keys serve the
+    batch, each many times: the key dedup's route of bn254_batch_verify_device.  Item i is signed with its base key's secret, on a message of
+    one of KD_MSG_LENS bytes; then the soak's signature defects (bit flip, x >= q, zeros, random bytes, another item's signature).
+    Returns msgs, sigs, pks and the field kinds used ("flip", "q0" .. "q3", "rand", "odd")"""
+    variants, kinds = [], set()
+    for j in range(len(sks)):
+        vs = []
+        for _ in range(rnd.choice((3, 4))):
+            kind = rnd.randrange(7)
+            p = bytearray(pk_pool[128 * j:128 * j + 128])
+            if kind == 0:
+                p[rnd.randrange(128)] ^= 1 << rnd.randrange(8)
+                kinds.add("flip")
+            elif kind <= 4:
+                f = 32 * (kind - 1)
+                p[f:f + 32] = (Q + rnd.randrange(1 << 200)).to_bytes(32, "big")
+                kinds.add("q%d" % (kind - 1))
+            elif kind == 5:
+                p[:] = rnd.randbytes(128)
+                kinds.add("rand")
+            else:
+                p[:] = rnd.choice(odd_keys)
+                kinds.add("odd")
+            vs.append(bytes(p))
+        variants.append(vs)
+    base = [rnd.randrange(len(sks)) for _ in range(n)]
+    msgs = [(hashlib.sha256(b"%s/%d" % (tag, i)).digest() * 5)[:rnd.choice(KD_MSG_LENS)] for i in range(n)]
+    sigs, st = eng.batch_sign(msgs, b"".join(sks[j] for j in base))
+    assert st == bytes(n)
+    sigs = bytearray(sigs)
+    pks = b"".join(rnd.choice(variants[j]) if rnd.randrange(3) == 0 else pk_pool[128 * j:128 * j + 128] for j in base)
+    for i in range(n):
+        kind = rnd.randrange(30)
+        s = memoryview(sigs)[64 * i:64 * i + 64]
+        if kind == 0:
+            s[rnd.randrange(64)] ^= 1 << rnd.randrange(8)
+        elif kind == 2:
+            s[:32] = (Q + rnd.randrange(1000)).to_bytes(32, "big")
+        elif kind == 4:
+            s[:] = bytes(64)
+        elif kind == 6:
+            s[:] = rnd.randbytes(64)
+        elif kind == 9 and i > 0:
+            s[:] = sigs[64 * (i - 1):64 * i]
+    return msgs, bytes(sigs), pks, kinds
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=120.0)
@@ -59,6 +126,7 @@ def soak(args):
     cores = len(os.sched_getaffinity(0))
     sks = [sk_bytes(j) for j in range(64)]
     pk_pool, _ = eng.batch_g2_mul(None, b"".join(sks), 64, reduce_scalar=True)
+    odd_keys = [bytes(128), off_sub, twist_small_order_key(random.Random(args.seed))]
     t0, rounds, items, codes, extra = time.time(), 0, 0, {}, {}
     last_note = t0
     while time.time() - t0 < args.seconds:
@@ -156,6 +224,25 @@ def soak(args):
                     raise SoakMismatch("MISMATCH %s round %d flags %d n %d %r %r" % (name, rounds, flags, n, bad[:5], [(g[i], want[i]) for i in bad[:5]]))
             for b in want:
                 codes[b] = codes.get(b, 0) + 1
+        if rounds % 8 == 1:
+            # the key dedup's route (the default of bn254_batch_verify_device on lane pairs): n >= 16 385 over a few hundred repeated, partly
+            # mutated keys, on the device-pointer entry point, against the oracle and the generic Miller loop (BN254_OPT_KEY_DEDUP = 0)
+            from tests.test_gpu_key_dedup import verify_device
+            kn = 16385 + rnd.randrange(4096)
+            kmsgs, ksigs, kpks, _ = dedup_batch(eng, rnd, kn, sks, pk_pool, odd_keys, b"soak-kd%d" % rounds)
+            kflags = rnd.randrange(4)
+            kwant, _ = c.batch_verify(kmsgs, ksigs, kpks, flags=kflags, nthreads=cores)
+            kgot = verify_device(eng, kmsgs, ksigs, kpks, kflags)
+            route = verify_device.route
+            if route["ran"] != 1 or route["keyed_n"] != kn:
+                raise SoakMismatch("dedup round %d n %d: the keyed route did not run %r" % (rounds, kn, route))
+            kgen = verify_device(eng, kmsgs, ksigs, kpks, kflags, KEY_DEDUP=0)
+            for name, g in (("key dedup", kgot), ("key dedup off", kgen)):
+                bad = [i for i in range(kn) if g[i] != kwant[i]]
+                if bad:
+                    raise SoakMismatch("MISMATCH %s round %d flags %d n %d %r %r" % (name, rounds, kflags, kn, bad[:5], [(g[i], kwant[i]) for i in bad[:5]]))
+            extra["dedup_tuples"] = extra.get("dedup_tuples", 0) + kn
+            extra["dedup_keys"] = extra.get("dedup_keys", 0) + route["keys"]
         if rounds % 8 == 0:
             # pairing API (canonical Gt bytes; both kernel families) and check_public_keys vs the oracle
             m = 24
@@ -274,7 +361,7 @@ def soak(args):
     lib_sha = hashlib.sha256(open(_native.LIB_PATH, "rb").read()).hexdigest()[:16]
     res = {"lib_sha256_16": lib_sha, "rounds": rounds, "tuples": items, "comparisons": items * 2 * 10, "seconds": round(time.time() - t0, 1), "oracle_threads": cores,
            "status_histogram": {str(k): v for k, v in sorted(codes.items())}, "mismatches": 0, "seed": args.seed, "also_compared": extra,
-           "modes": ["exact, the batch in three slices inside the library (BN254_OPT_MAX_CHUNK)", "aggregate verify on registered pools (every eighth round)", "keyed (registered keys, once per round with the subgroup check)", "keyed randomised 128-bit / 64-bit / GLV (once per round)", "exact, defaults (lane machine up to 1536, eight wave roles above; final exponentiation on nine lane pairs up to 3072)", "exact, Miller loop as the lane machine at every size", "exact, eight wave roles + final exponentiation on nine lane pairs", "... + octet final exponentiation", "... + nine lane pairs at every size", "exact, four wave roles", "exact, lane groups of one wave (octet)", "exact on lane pairs", "exact, one lane per verify", "randomised 128-bit", "randomised GLV", "randomised 64-bit"],
+           "modes": ["exact, key dedup route: n >= 16 385 on the device entry point over repeated mutated keys, and the same with it off (every eighth round)", "exact, the batch in three slices inside the library (BN254_OPT_MAX_CHUNK)", "aggregate verify on registered pools (every eighth round)", "keyed (registered keys, once per round with the subgroup check)", "keyed randomised 128-bit / 64-bit / GLV (once per round)", "exact, defaults (lane machine up to 1536, eight wave roles above; final exponentiation on nine lane pairs up to 3072)", "exact, Miller loop as the lane machine at every size", "exact, eight wave roles + final exponentiation on nine lane pairs", "... + octet final exponentiation", "... + nine lane pairs at every size", "exact, four wave roles", "exact, lane groups of one wave (octet)", "exact on lane pairs", "exact, one lane per verify", "randomised 128-bit", "randomised GLV", "randomised 64-bit"],
            "flags": [0, 1]}
     return res
 

@@ -53,27 +53,46 @@ def make_batch(eng, n, pool, derived=None):
     return msgs, bytes(sigs), pks
 
 
-def verify_device(eng, msgs, sigs, pks, flags, **opts):
+def verify_device(eng, msgs, sigs, pks, flags, stream=None, sync=True, **opts):
+    """bn254_batch_verify_device on the batch (messages of any length), with the options `opts` set for this call only; returns the status
+    bytes and leaves the key dedup's decision in verify_device.route.  stream: a torch.cuda.Stream or tests.hip_ctypes.Stream to enqueue on
+    (None: the context's own); sync=False: returns collect() instead, which waits for that stream, then reads the statuses and the route —
+    the inputs stay alive until then, and with a stream nothing waits on the host between the call and collect(), so calls can queue up"""
     import torch
     from bn254_amd import engine as E
     n = len(msgs)
     for k, v in opts.items():
         eng.set_option(getattr(E, "OPT_" + k), v)
     try:
-        d_msgs = torch.frombuffer(bytearray(b"".join(msgs)), dtype=torch.uint8).to("cuda:0")
-        d_off = torch.tensor([32 * i for i in range(n + 1)], dtype=torch.int64, device="cuda:0")
+        offs = [0]
+        for m in msgs:
+            offs.append(offs[-1] + len(m))
+        d_msgs = torch.frombuffer(bytearray(b"".join(msgs) or b"\0"), dtype=torch.uint8).to("cuda:0")
+        d_off = torch.tensor(offs, dtype=torch.int64, device="cuda:0")
         d_sigs = torch.frombuffer(bytearray(sigs), dtype=torch.uint8).to("cuda:0")
         d_pks = torch.frombuffer(bytearray(pks), dtype=torch.uint8).to("cuda:0")
         d_st = torch.full((n,), 0xEE, dtype=torch.uint8, device="cuda:0")
-        torch.cuda.synchronize()
-        eng.batch_verify_device(d_msgs.data_ptr(), d_off.data_ptr(), d_sigs.data_ptr(), d_pks.data_ptr(), n, d_st.data_ptr(), flags=flags)
-        eng.synchronize()
-        verify_device.route = eng.debug_key_dedup_last()
-        return bytes(d_st.cpu().numpy())
+        handle = None if stream is None else getattr(stream, "cuda_stream", None) or stream.handle
+        if stream is None:
+            torch.cuda.synchronize()
+        else:                                          # the uploads ordered before the call on the device: no host sync between calls
+            s = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(handle, device="cuda:0")
+            s.wait_stream(torch.cuda.current_stream())
+        eng.batch_verify_device(d_msgs.data_ptr(), d_off.data_ptr(), d_sigs.data_ptr(), d_pks.data_ptr(), n, d_st.data_ptr(), flags=flags,
+                                stream=handle)
+
+        def collect(keep=(d_msgs, d_off, d_sigs, d_pks)):
+            if stream is not None:
+                stream.synchronize()
+            eng.synchronize()
+            verify_device.route = eng.debug_key_dedup_last()
+            return bytes(d_st.cpu().numpy())
+        return collect() if sync else collect
     finally:
         from tests.conftest import ws_default
         defaults = {"KEY_DEDUP": 1, "KEY_DEDUP_FORCE_GENERIC": 0, "KEY_DEDUP_HASH_BITS": 0,
-                    "KEY_DEDUP_MAX_KEYS": ws_default("KEY_DEDUP_MAX_KEYS_DEFAULT"), "KEY_DEDUP_MIN_MULT": ws_default("KEY_DEDUP_MIN_MULT_DEFAULT")}
+                    "KEY_DEDUP_MAX_KEYS": ws_default("KEY_DEDUP_MAX_KEYS_DEFAULT"), "KEY_DEDUP_MIN_MULT": ws_default("KEY_DEDUP_MIN_MULT_DEFAULT"),
+                    "MAX_CHUNK": 0, "ASSUME_FREE_MB": 0, "SPLIT_MILLER": 0, "PAIR_LANES": 1}
         for k in opts:
             eng.set_option(getattr(E, "OPT_" + k), defaults[k])
 

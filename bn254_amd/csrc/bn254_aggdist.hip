@@ -273,20 +273,15 @@ int bn254_batch_aggregate_verify_distinct(bn254_ctx* c, const uint8_t* msgs, con
   if (agg_off[0] != 0 || agg_off[n] != m || !offsets_ok(agg_off, n) || !offsets_ok(msg_off, m)) return BN254_E_BAD_ARGUMENT;
   if (n == 0) return 0;
   HIP_TRY(hipSetDevice(c->device));
-  const size_t msg_bytes = (size_t)msg_off[m];
-  if (msg_bytes && !msgs) return BN254_E_BAD_ARGUMENT;
-  int rc;
-  if ((rc = stage_in(c, 0, msgs, msg_bytes))) return rc;
-  if ((rc = stage_in(c, 1, msg_off, (m + 1) * sizeof(uint64_t)))) return rc;
-  if ((rc = stage_in(c, 2, pks, m * 128))) return rc;
-  if ((rc = stage_in(c, 3, agg_sigs, n * 64))) return rc;
-  if ((rc = stage_in(c, 4, agg_off, (n + 1) * sizeof(uint64_t)))) return rc;
-  if ((rc = stage_reserve(c, 5, n))) return rc;
-  if ((rc = bn254_batch_aggregate_verify_distinct_device(c, c->stage[0], (const uint64_t*)c->stage[1], c->stage[2], m, c->stage[3],
-                                                         (const uint64_t*)c->stage[4], n, flags, c->stage[5], nullptr))) return rc;
-  if ((rc = stage_out(c, 5, status, n))) return rc;
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return 0;
+  if (!msgs_ok(msgs, msg_off, m)) return BN254_E_BAD_ARGUMENT;
+  HostStaging st(c);
+  const uint8_t *d_msgs = st.in(0, msgs, (size_t)msg_off[m]), *d_msg_off = st.in(1, msg_off, (m + 1) * sizeof(uint64_t));
+  const uint8_t *d_pks = st.in(2, pks, m * 128), *d_agg_sigs = st.in(3, agg_sigs, n * 64), *d_agg_off = st.in(4, agg_off, (n + 1) * sizeof(uint64_t));
+  uint8_t* d_status = st.out(5, n, status);
+  if (st.ok())
+    st.rc = bn254_batch_aggregate_verify_distinct_device(c, d_msgs, (const uint64_t*)d_msg_off, d_pks, m, d_agg_sigs, (const uint64_t*)d_agg_off, n, flags,
+                                                         d_status, nullptr);
+  return st.finish();
 }
 
 }  // extern "C"

@@ -262,32 +262,26 @@ int bn254_debug_fp_op(bn254_ctx* c, int op, const uint8_t* a, const uint8_t* b, 
   if (!c || (n && (!a || !out || !status))) return BN254_E_BAD_ARGUMENT;
   if (n == 0) return 0;
   HIP_TRY(hipSetDevice(c->device));
-  int rc;
-  if ((rc = stage_in(c, 0, a, n * 32))) return rc;
-  if (b && (rc = stage_in(c, 1, b, n * 32))) return rc;
-  if ((rc = stage_reserve(c, 2, n * 32))) return rc;
-  if ((rc = stage_reserve(c, 3, n))) return rc;
-  k_debug_fp_op<<<grid_for(n), BN_WAVE, 0, c->stream>>>(op, c->stage[0], b ? c->stage[1] : nullptr, n, c->stage[2], c->stage[3]);
+  HostStaging st(c);
+  const uint8_t* d_a = st.in(0, a, n * 32);
+  const uint8_t* d_b = b ? st.in(1, b, n * 32) : nullptr;
+  uint8_t *d_out = st.out(2, n * 32, out), *d_status = st.out(3, n, status);
+  if (!st.ok()) return st.rc;
+  k_debug_fp_op<<<grid_for(n), BN_WAVE, 0, c->stream>>>(op, d_a, d_b, n, d_out, d_status);
   HIP_TRY(hipGetLastError());
-  if ((rc = stage_out(c, 2, out, n * 32))) return rc;
-  if ((rc = stage_out(c, 3, status, n))) return rc;
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return 0;
+  return st.finish();
 }
 int bn254_debug_hash_candidate(bn254_ctx* c, const uint8_t* h, size_t n, uint8_t* out, uint8_t* status) {
   if (!c || (n && (!h || !out || !status))) return BN254_E_BAD_ARGUMENT;
   if (n == 0) return 0;
   HIP_TRY(hipSetDevice(c->device));
-  int rc;
-  if ((rc = stage_in(c, 0, h, n * 32))) return rc;
-  if ((rc = stage_reserve(c, 2, n * 64))) return rc;
-  if ((rc = stage_reserve(c, 3, n))) return rc;
-  k_debug_hash_candidate<<<grid_for(n), BN_WAVE, 0, c->stream>>>(c->stage[0], n, c->stage[2], c->stage[3]);
+  HostStaging st(c);
+  const uint8_t* d_h = st.in(0, h, n * 32);
+  uint8_t *d_out = st.out(2, n * 64, out), *d_status = st.out(3, n, status);
+  if (!st.ok()) return st.rc;
+  k_debug_hash_candidate<<<grid_for(n), BN_WAVE, 0, c->stream>>>(d_h, n, d_out, d_status);
   HIP_TRY(hipGetLastError());
-  if ((rc = stage_out(c, 2, out, n * 64))) return rc;
-  if ((rc = stage_out(c, 3, status, n))) return rc;
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return 0;
+  return st.finish();
 }
 // layout: 0 one lane per item, exact chain (Gt out) | 1 lane pairs, program C_FE_EXACT (Gt out) | 2 lane pairs, program C_FE_CHECK |
 // 3 octet (straight-line chains below 128 items, accumulator machine from 128 on) | 4 nonet | 5 one lane per item, check chain | 6 nonet, wide form (18 lane pairs)
@@ -298,41 +292,37 @@ int bn254_debug_final_exp_limbs(bn254_ctx* c, int layout, const int32_t* limbs, 
   HIP_TRY(hipSetDevice(c->device));
   int rc;
   if ((rc = ws_reserve(c, n))) return rc;
-  if ((rc = stage_in(c, 0, limbs, n * 12 * BN_LIMBS * sizeof(int32_t)))) return rc;
-  if ((rc = stage_reserve(c, 1, n * 384))) return rc;
-  if ((rc = stage_reserve(c, 2, n))) return rc;
+  HostStaging st(c);
+  const uint8_t* d_limbs = st.in(0, limbs, n * 12 * BN_LIMBS * sizeof(int32_t));
+  uint8_t *d_gt = st.out(1, n * 384, gt), *d_status = st.out(2, n, status);
+  if (!st.ok()) return st.rc;
   hipStream_t s = c->stream;
-  uint8_t* d_gt = gt ? c->stage[1] : nullptr;
-  k_debug_load_f<<<grid_for(n), BN_WAVE, 0, s>>>((const int32_t*)c->stage[0], n, c->ws);
+  k_debug_load_f<<<grid_for(n), BN_WAVE, 0, s>>>((const int32_t*)d_limbs, n, c->ws);
   switch (layout) {
-    case 0: { int rc_ = launch_final_exp_lane(c, s, n, 1, 1, 1, 0, d_gt ? d_gt : c->stage[1], c->stage[2], 0, 0, nullptr, nullptr); if (rc_) return rc_; } break;
-    case 1: rc = bn254_pair_final_exp_product(n, 1, c->ws, d_gt ? d_gt : c->stage[1], c->stage[2], 0, s); break;
-    case 2: rc = bn254_pair_final_exp(n, c->ws, 0, c->stage[2], nullptr, nullptr, s); break;
-    case 3: rc = bn254_trio_final_exp(n, c->ws, 0, c->stage[2], s); break;
-    case 4: rc = bn254_nonet_final_exp(n, c->ws, 0, c->stage[2], s); break;
-    case 6: rc = bn254_nonet_final_exp(n, c->ws, 0, c->stage[2], s, 1); break;
-    default: { int rc_ = launch_final_exp_lane(c, s, n, 1, 1, 1, 0, nullptr, c->stage[2], 0, 0, nullptr, nullptr); if (rc_) return rc_; } break;
+    case 0: rc = launch_final_exp_lane(c, s, n, 1, 1, 1, 0, d_gt, d_status, 0, 0, nullptr, nullptr); break;
+    case 1: rc = bn254_pair_final_exp_product(n, 1, c->ws, d_gt, d_status, 0, s); break;
+    case 2: rc = bn254_pair_final_exp(n, c->ws, 0, d_status, nullptr, nullptr, s); break;
+    case 3: rc = bn254_trio_final_exp(n, c->ws, 0, d_status, s); break;
+    case 4: rc = bn254_nonet_final_exp(n, c->ws, 0, d_status, s); break;
+    case 6: rc = bn254_nonet_final_exp(n, c->ws, 0, d_status, s, 1); break;
+    default: rc = launch_final_exp_lane(c, s, n, 1, 1, 1, 0, nullptr, d_status, 0, 0, nullptr, nullptr); break;
   }
   if (rc) return rc;
   HIP_TRY(hipGetLastError());
-  if (gt && (rc = stage_out(c, 1, gt, n * 384))) return rc;
-  if ((rc = stage_out(c, 2, status, n))) return rc;
-  HIP_TRY(hipStreamSynchronize(s));
-  return 0;
+  return st.finish();
 }
 int bn254_debug_fp12_op(bn254_ctx* c, int op, const uint8_t* a, const uint8_t* b, size_t n, uint8_t* out) {
   if (!c || (n && (!a || !out))) return BN254_E_BAD_ARGUMENT;
   if (n == 0) return 0;
   HIP_TRY(hipSetDevice(c->device));
-  int rc;
-  if ((rc = stage_in(c, 0, a, n * 384))) return rc;
-  if (b && (rc = stage_in(c, 1, b, n * 384))) return rc;
-  if ((rc = stage_reserve(c, 2, n * 384))) return rc;
-  k_debug_fp12_op<<<grid_for(n), BN_WAVE, 0, c->stream>>>(op, c->stage[0], b ? c->stage[1] : nullptr, n, c->stage[2]);
+  HostStaging st(c);
+  const uint8_t* d_a = st.in(0, a, n * 384);
+  const uint8_t* d_b = b ? st.in(1, b, n * 384) : nullptr;
+  uint8_t* d_out = st.out(2, n * 384, out);
+  if (!st.ok()) return st.rc;
+  k_debug_fp12_op<<<grid_for(n), BN_WAVE, 0, c->stream>>>(op, d_a, d_b, n, d_out);
   HIP_TRY(hipGetLastError());
-  if ((rc = stage_out(c, 2, out, n * 384))) return rc;
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return 0;
+  return st.finish();
 }
 
 

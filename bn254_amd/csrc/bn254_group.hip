@@ -462,18 +462,14 @@ static int binop_host(bn254_ctx* c, int g2, const uint8_t* a, const uint8_t* b, 
   if (n == 0) return 0;
   HIP_TRY(hipSetDevice(c->device));
   size_t sz = g2 ? 128 : 64;
-  int rc;
-  if ((rc = stage_in(c, 0, a, n * sz))) return rc;
-  if ((rc = stage_in(c, 1, b, n * sz))) return rc;
-  if ((rc = stage_reserve(c, 2, n * sz))) return rc;
-  if ((rc = stage_reserve(c, 3, n))) return rc;
-  if (g2) k_g2_add<<<grid_for(n), BN_WAVE, 0, c->stream>>>(c->stage[0], c->stage[1], n, c->stage[2], c->stage[3]);
-  else k_g1_add<<<grid_for(n), BN_WAVE, 0, c->stream>>>(c->stage[0], c->stage[1], n, c->stage[2], c->stage[3]);
+  HostStaging st(c);
+  const uint8_t *d_a = st.in(0, a, n * sz), *d_b = st.in(1, b, n * sz);
+  uint8_t *d_out = st.out(2, n * sz, out), *d_status = st.out(3, n, status);
+  if (!st.ok()) return st.rc;
+  if (g2) k_g2_add<<<grid_for(n), BN_WAVE, 0, c->stream>>>(d_a, d_b, n, d_out, d_status);
+  else k_g1_add<<<grid_for(n), BN_WAVE, 0, c->stream>>>(d_a, d_b, n, d_out, d_status);
   HIP_TRY(hipGetLastError());
-  if ((rc = stage_out(c, 2, out, n * sz))) return rc;
-  if ((rc = stage_out(c, 3, status, n))) return rc;
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return 0;
+  return st.finish();
 }
 int bn254_batch_g1_add(bn254_ctx* c, const uint8_t* a, const uint8_t* b, size_t n, uint8_t* out, uint8_t* status) { return binop_host(c, 0, a, b, n, out, status); }
 int bn254_batch_g2_add(bn254_ctx* c, const uint8_t* a, const uint8_t* b, size_t n, uint8_t* out, uint8_t* status) { return binop_host(c, 1, a, b, n, out, status); }
@@ -576,20 +572,23 @@ static int comb_build(bn254_ctx* c, int g2) {
   int rc;
   if ((rc = pool_reserve_one(c, g2 ? &c->g2_comb : &c->g1_comb, g2 ? 4 : 2, N))) { free(h); return rc; }
   // staging slots 5 .. 7: a host-pointer caller (mul_host) has ITS scalars in slots 0 .. 3 when this runs
-  if ((rc = stage_in(c, 5, h, N * 32))) { free(h); return rc; }
-  if ((rc = stage_reserve(c, 6, N * sz))) { free(h); return rc; }
-  if ((rc = stage_reserve(c, 7, N))) { free(h); return rc; }
-  if (g2) {
-    k_g2_mul<<<grid_for(N), BN_WAVE, 0, c->stream>>>(nullptr, c->stage[5], N, 0, c->stage[6], c->stage[7]);
-    k_pool_decode_g2<<<grid_for(N), BN_WAVE, 0, c->stream>>>(c->stage[6], N, 0, c->g2_comb);
-  } else {
-    k_g1_gen_mul<<<grid_for(N), BN_WAVE, 0, c->stream>>>(c->stage[5], N, c->stage[6]);
-    k_pool_decode_g1<<<grid_for(N), BN_WAVE, 0, c->stream>>>(c->stage[6], N, 0, c->g1_comb);
+  HostStaging st(c);
+  const uint8_t* d_k = st.in(5, h, N * 32);
+  uint8_t* d_pts = st.out(6, N * sz);
+  uint8_t* d_st = st.out(7, N);
+  if (st.ok()) {
+    if (g2) {
+      k_g2_mul<<<grid_for(N), BN_WAVE, 0, c->stream>>>(nullptr, d_k, N, 0, d_pts, d_st);
+      k_pool_decode_g2<<<grid_for(N), BN_WAVE, 0, c->stream>>>(d_pts, N, 0, c->g2_comb);
+    } else {
+      k_g1_gen_mul<<<grid_for(N), BN_WAVE, 0, c->stream>>>(d_k, N, d_pts);
+      k_pool_decode_g1<<<grid_for(N), BN_WAVE, 0, c->stream>>>(d_pts, N, 0, c->g1_comb);
+    }
+    st.check(hipGetLastError());
   }
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);      // the staged scalars are read from `h`; the table is complete before any stream uses it
+  rc = st.finish();                                      // the staged scalars are read from `h`; the table is complete before any stream uses it
   free(h);
-  if (e != hipSuccess) return -(int)e;
+  if (rc) return rc;
   if (g2) c->g2_comb_ready = 1; else c->g1_comb_ready = 1;
   return 0;
 }
@@ -616,18 +615,13 @@ static int mul_host(bn254_ctx* c, int g2, const uint8_t* p, const uint8_t* k, si
   if (n == 0) return 0;
   HIP_TRY(hipSetDevice(c->device));
   size_t sz = g2 ? 128 : 64;
-  int rc;
-  if (p && (rc = stage_in(c, 0, p, n * sz))) return rc;
-  if ((rc = stage_in(c, 1, k, n * 32))) return rc;
-  if ((rc = stage_reserve(c, 2, n * sz))) return rc;
-  if ((rc = stage_reserve(c, 3, n))) return rc;
-  rc = g2 ? bn254_batch_g2_mul_device(c, p ? c->stage[0] : nullptr, c->stage[1], n, reduce, c->stage[2], c->stage[3], nullptr)
-          : bn254_batch_g1_mul_device(c, p ? c->stage[0] : nullptr, c->stage[1], n, reduce, c->stage[2], c->stage[3], nullptr);
-  if (rc) return rc;
-  if ((rc = stage_out(c, 2, out, n * sz))) return rc;
-  if ((rc = stage_out(c, 3, status, n))) return rc;
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return 0;
+  HostStaging st(c);
+  const uint8_t* d_p = p ? st.in(0, p, n * sz) : nullptr;
+  const uint8_t* d_k = st.in(1, k, n * 32);
+  uint8_t *d_out = st.out(2, n * sz, out), *d_status = st.out(3, n, status);
+  if (st.ok()) st.rc = g2 ? bn254_batch_g2_mul_device(c, d_p, d_k, n, reduce, d_out, d_status, nullptr)
+                          : bn254_batch_g1_mul_device(c, d_p, d_k, n, reduce, d_out, d_status, nullptr);
+  return st.finish();
 }
 int bn254_batch_g1_mul(bn254_ctx* c, const uint8_t* p, const uint8_t* k, size_t n, int reduce, uint8_t* out, uint8_t* status) { return mul_host(c, 0, p, k, n, reduce, out, status); }
 int bn254_batch_g2_mul(bn254_ctx* c, const uint8_t* p, const uint8_t* k, size_t n, int reduce, uint8_t* out, uint8_t* status) { return mul_host(c, 1, p, k, n, reduce, out, status); }
@@ -653,18 +647,12 @@ int bn254_batch_sign(bn254_ctx* c, const uint8_t* msgs, const uint64_t* off, con
   if (!c || (n && (!off || !sks || !sigs || !status))) return BN254_E_BAD_ARGUMENT;
   if (n == 0) return 0;
   HIP_TRY(hipSetDevice(c->device));
-  int rc;
-  if (!offsets_ok(off, n)) return BN254_E_BAD_ARGUMENT;
-  if ((rc = stage_in(c, 0, msgs, (size_t)off[n]))) return rc;
-  if ((rc = stage_in(c, 1, off, (n + 1) * sizeof(uint64_t)))) return rc;
-  if ((rc = stage_in(c, 2, sks, n * 32))) return rc;
-  if ((rc = stage_reserve(c, 3, n * 64))) return rc;
-  if ((rc = stage_reserve(c, 4, n))) return rc;
-  if ((rc = bn254_batch_sign_device(c, c->stage[0], (const uint64_t*)c->stage[1], c->stage[2], n, c->stage[3], c->stage[4], nullptr))) return rc;
-  if ((rc = stage_out(c, 3, sigs, n * 64))) return rc;
-  if ((rc = stage_out(c, 4, status, n))) return rc;
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return 0;
+  if (!msgs_ok(msgs, off, n)) return BN254_E_BAD_ARGUMENT;
+  HostStaging st(c);
+  const uint8_t *d_msgs = st.in(0, msgs, (size_t)off[n]), *d_off = st.in(1, off, (n + 1) * sizeof(uint64_t)), *d_sks = st.in(2, sks, n * 32);
+  uint8_t *d_sigs = st.out(3, n * 64, sigs), *d_status = st.out(4, n, status);
+  if (st.ok()) st.rc = bn254_batch_sign_device(c, d_msgs, (const uint64_t*)d_off, d_sks, n, d_sigs, d_status, nullptr);
+  return st.finish();
 }
 
 static int sum_host(bn254_ctx* c, int g2, const uint8_t* pts, const uint64_t* seg, size_t n, uint8_t* out, uint8_t* status) {
@@ -674,18 +662,14 @@ static int sum_host(bn254_ctx* c, int g2, const uint8_t* pts, const uint64_t* se
   size_t sz = g2 ? 128 : 64;
   if (!offsets_ok(seg, n)) return BN254_E_BAD_ARGUMENT;
   size_t total = (size_t)seg[n];
-  int rc;
-  if ((rc = stage_in(c, 0, pts, total * sz))) return rc;
-  if ((rc = stage_in(c, 1, seg, (n + 1) * sizeof(uint64_t)))) return rc;
-  if ((rc = stage_reserve(c, 2, n * sz))) return rc;
-  if ((rc = stage_reserve(c, 3, n))) return rc;
-  if (g2) k_g2_sum<<<grid_for(n), BN_WAVE, 0, c->stream>>>(c->stage[0], (const uint64_t*)c->stage[1], n, c->stage[2], c->stage[3]);
-  else k_g1_sum<<<grid_for(n), BN_WAVE, 0, c->stream>>>(c->stage[0], (const uint64_t*)c->stage[1], n, c->stage[2], c->stage[3]);
+  HostStaging st(c);
+  const uint8_t *d_pts = st.in(0, pts, total * sz), *d_seg = st.in(1, seg, (n + 1) * sizeof(uint64_t));
+  uint8_t *d_out = st.out(2, n * sz, out), *d_status = st.out(3, n, status);
+  if (!st.ok()) return st.rc;
+  if (g2) k_g2_sum<<<grid_for(n), BN_WAVE, 0, c->stream>>>(d_pts, (const uint64_t*)d_seg, n, d_out, d_status);
+  else k_g1_sum<<<grid_for(n), BN_WAVE, 0, c->stream>>>(d_pts, (const uint64_t*)d_seg, n, d_out, d_status);
   HIP_TRY(hipGetLastError());
-  if ((rc = stage_out(c, 2, out, n * sz))) return rc;
-  if ((rc = stage_out(c, 3, status, n))) return rc;
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return 0;
+  return st.finish();
 }
 int bn254_batch_g1_sum(bn254_ctx* c, const uint8_t* pts, const uint64_t* seg, size_t n, uint8_t* out, uint8_t* status) { return sum_host(c, 0, pts, seg, n, out, status); }
 int bn254_batch_g2_sum(bn254_ctx* c, const uint8_t* pts, const uint64_t* seg, size_t n, uint8_t* out, uint8_t* status) { return sum_host(c, 1, pts, seg, n, out, status); }
@@ -846,16 +830,14 @@ int bn254_ctx_register_pools(bn254_ctx* c, const uint8_t* msgs, const uint64_t* 
                              const uint8_t* sig_pool, uint32_t flags, size_t expect_tuples) {
   MsgsLenScope msgs_len_scope(c);
   if (!c || !n_msgs || !n_signers || !msg_off || !pk_pool || !sig_pool) return BN254_E_BAD_ARGUMENT;
-  if (!offsets_ok(msg_off, n_msgs) || (msg_off[n_msgs] && !msgs)) return BN254_E_BAD_ARGUMENT;
+  if (!msgs_ok(msgs, msg_off, n_msgs)) return BN254_E_BAD_ARGUMENT;
   HIP_TRY(hipSetDevice(c->device));
-  int rc;
-  if ((rc = stage_in(c, 0, msgs, (size_t)msg_off[n_msgs]))) return rc;
-  if ((rc = stage_in(c, 1, msg_off, (n_msgs + 1) * sizeof(uint64_t)))) return rc;
-  if ((rc = stage_in(c, 2, pk_pool, n_signers * 128))) return rc;
-  if ((rc = stage_in(c, 3, sig_pool, n_msgs * n_signers * 64))) return rc;
-  rc = bn254_ctx_register_pools_device(c, c->stage[0], (const uint64_t*)c->stage[1], n_msgs, c->stage[2], n_signers, c->stage[3], flags, expect_tuples, nullptr);
-  hipError_t e = hipStreamSynchronize(c->stream);     // also on failure: the staged copies read the caller's buffers
-  return rc ? rc : -(int)e;
+  HostStaging st(c);
+  const uint8_t *d_msgs = st.in(0, msgs, (size_t)msg_off[n_msgs]), *d_msg_off = st.in(1, msg_off, (n_msgs + 1) * sizeof(uint64_t));
+  const uint8_t *d_pk_pool = st.in(2, pk_pool, n_signers * 128), *d_sig_pool = st.in(3, sig_pool, n_msgs * n_signers * 64);
+  if (st.ok())
+    st.rc = bn254_ctx_register_pools_device(c, d_msgs, (const uint64_t*)d_msg_off, n_msgs, d_pk_pool, n_signers, d_sig_pool, flags, expect_tuples, nullptr);
+  return st.finish();
 }
 int bn254_batch_aggregate_verify_registered_device(bn254_ctx* c, const uint32_t* d_tuple_msg, const uint64_t* d_tuple_off, const uint32_t* d_signer_idx, size_t n,
                                                    uint8_t* d_status, void* stream) {
@@ -877,15 +859,14 @@ int bn254_batch_aggregate_verify_registered(bn254_ctx* c, const uint32_t* tuple_
   if (n == 0) return 0;
   if (!offsets_ok(tuple_off, n)) return BN254_E_BAD_ARGUMENT;
   HIP_TRY(hipSetDevice(c->device));
-  int rc;
-  if ((rc = stage_in(c, 4, tuple_msg, n * sizeof(uint32_t)))) return rc;
-  if ((rc = stage_in(c, 5, tuple_off, (n + 1) * sizeof(uint64_t)))) return rc;
-  if ((rc = stage_in(c, 6, signer_idx, (size_t)tuple_off[n] * sizeof(uint32_t)))) return rc;
-  if ((rc = stage_reserve(c, 7, n))) return rc;
-  rc = bn254_batch_aggregate_verify_registered_device(c, (const uint32_t*)c->stage[4], (const uint64_t*)c->stage[5], (const uint32_t*)c->stage[6], n, c->stage[7], nullptr);
-  if (!rc) rc = stage_out(c, 7, status, n);
-  hipError_t e = hipStreamSynchronize(c->stream);
-  return rc ? rc : -(int)e;
+  HostStaging st(c);
+  const uint8_t *d_tuple_msg = st.in(4, tuple_msg, n * sizeof(uint32_t)), *d_tuple_off = st.in(5, tuple_off, (n + 1) * sizeof(uint64_t));
+  const uint8_t* d_signer_idx = st.in(6, signer_idx, (size_t)tuple_off[n] * sizeof(uint32_t));
+  uint8_t* d_status = st.out(7, n, status);
+  if (st.ok())
+    st.rc = bn254_batch_aggregate_verify_registered_device(c, (const uint32_t*)d_tuple_msg, (const uint64_t*)d_tuple_off, (const uint32_t*)d_signer_idx, n,
+                                                           d_status, nullptr);
+  return st.finish();
 }
 int bn254_batch_aggregate_verify(bn254_ctx* c, const uint8_t* msgs, const uint64_t* msg_off, size_t n_msgs, const uint8_t* pk_pool, size_t n_signers,
                                  const uint8_t* sig_pool, const uint32_t* tuple_msg, const uint64_t* tuple_off, const uint32_t* signer_idx, size_t n,
@@ -893,23 +874,18 @@ int bn254_batch_aggregate_verify(bn254_ctx* c, const uint8_t* msgs, const uint64
   MsgsLenScope msgs_len_scope(c);
   if (!c || !n_msgs || !n_signers || (n && (!msg_off || !pk_pool || !sig_pool || !tuple_msg || !tuple_off || !signer_idx || !status))) return BN254_E_BAD_ARGUMENT;
   if (n == 0) return 0;
-  if (!offsets_ok(tuple_off, n) || !offsets_ok(msg_off, n_msgs)) return BN254_E_BAD_ARGUMENT;
+  if (!offsets_ok(tuple_off, n) || !msgs_ok(msgs, msg_off, n_msgs)) return BN254_E_BAD_ARGUMENT;
   HIP_TRY(hipSetDevice(c->device));
-  int rc;
-  if ((rc = stage_in(c, 0, msgs, (size_t)msg_off[n_msgs]))) return rc;
-  if ((rc = stage_in(c, 1, msg_off, (n_msgs + 1) * sizeof(uint64_t)))) return rc;
-  if ((rc = stage_in(c, 2, pk_pool, n_signers * 128))) return rc;
-  if ((rc = stage_in(c, 3, sig_pool, n_msgs * n_signers * 64))) return rc;
-  if ((rc = stage_in(c, 4, tuple_msg, n * sizeof(uint32_t)))) return rc;
-  if ((rc = stage_in(c, 5, tuple_off, (n + 1) * sizeof(uint64_t)))) return rc;
-  if ((rc = stage_in(c, 6, signer_idx, (size_t)tuple_off[n] * sizeof(uint32_t)))) return rc;
-  if ((rc = stage_reserve(c, 7, n))) return rc;
-  if ((rc = bn254_batch_aggregate_verify_device(c, c->stage[0], (const uint64_t*)c->stage[1], n_msgs, c->stage[2], n_signers, c->stage[3],
-                                                (const uint32_t*)c->stage[4], (const uint64_t*)c->stage[5], (const uint32_t*)c->stage[6], n, flags,
-                                                c->stage[7], nullptr))) return rc;
-  if ((rc = stage_out(c, 7, status, n))) return rc;
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return 0;
+  HostStaging st(c);
+  const uint8_t *d_msgs = st.in(0, msgs, (size_t)msg_off[n_msgs]), *d_msg_off = st.in(1, msg_off, (n_msgs + 1) * sizeof(uint64_t));
+  const uint8_t *d_pk_pool = st.in(2, pk_pool, n_signers * 128), *d_sig_pool = st.in(3, sig_pool, n_msgs * n_signers * 64);
+  const uint8_t *d_tuple_msg = st.in(4, tuple_msg, n * sizeof(uint32_t)), *d_tuple_off = st.in(5, tuple_off, (n + 1) * sizeof(uint64_t));
+  const uint8_t* d_signer_idx = st.in(6, signer_idx, (size_t)tuple_off[n] * sizeof(uint32_t));
+  uint8_t* d_status = st.out(7, n, status);
+  if (st.ok())
+    st.rc = bn254_batch_aggregate_verify_device(c, d_msgs, (const uint64_t*)d_msg_off, n_msgs, d_pk_pool, n_signers, d_sig_pool, (const uint32_t*)d_tuple_msg,
+                                                (const uint64_t*)d_tuple_off, (const uint32_t*)d_signer_idx, n, flags, d_status, nullptr);
+  return st.finish();
 }
 
 static int decompress_host(bn254_ctx* c, int g2, const uint8_t* in, size_t n, uint8_t* out, uint8_t* status) {
@@ -917,17 +893,14 @@ static int decompress_host(bn254_ctx* c, int g2, const uint8_t* in, size_t n, ui
   if (n == 0) return 0;
   HIP_TRY(hipSetDevice(c->device));
   size_t isz = g2 ? 65 : 33, osz = g2 ? 128 : 64;
-  int rc;
-  if ((rc = stage_in(c, 0, in, n * isz))) return rc;
-  if ((rc = stage_reserve(c, 2, n * osz))) return rc;
-  if ((rc = stage_reserve(c, 3, n))) return rc;
-  if (g2) k_g2_decompress<<<grid_for(n), BN_WAVE, 0, c->stream>>>(c->stage[0], n, c->stage[2], c->stage[3]);
-  else k_g1_decompress<<<grid_for(n), BN_WAVE, 0, c->stream>>>(c->stage[0], n, c->stage[2], c->stage[3]);
+  HostStaging st(c);
+  const uint8_t* d_in = st.in(0, in, n * isz);
+  uint8_t *d_out = st.out(2, n * osz, out), *d_status = st.out(3, n, status);
+  if (!st.ok()) return st.rc;
+  if (g2) k_g2_decompress<<<grid_for(n), BN_WAVE, 0, c->stream>>>(d_in, n, d_out, d_status);
+  else k_g1_decompress<<<grid_for(n), BN_WAVE, 0, c->stream>>>(d_in, n, d_out, d_status);
   HIP_TRY(hipGetLastError());
-  if ((rc = stage_out(c, 2, out, n * osz))) return rc;
-  if ((rc = stage_out(c, 3, status, n))) return rc;
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return 0;
+  return st.finish();
 }
 int bn254_batch_g1_decompress(bn254_ctx* c, const uint8_t* in, size_t n, uint8_t* out, uint8_t* status) { return decompress_host(c, 0, in, n, out, status); }
 int bn254_batch_g2_decompress(bn254_ctx* c, const uint8_t* in, size_t n, uint8_t* out, uint8_t* status) { return decompress_host(c, 1, in, n, out, status); }

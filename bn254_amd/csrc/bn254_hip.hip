@@ -496,15 +496,32 @@ int stage_reserve(bn254_ctx* c, int slot, size_t bytes) {
   c->stage_cap[slot] = cap;
   return 0;
 }
-int stage_in(bn254_ctx* c, int slot, const void* host, size_t bytes) {
-  int rc = stage_reserve(c, slot, bytes ? bytes : 1);
-  if (rc) return rc;
-  if (bytes) HIP_TRY(hipMemcpyAsync(c->stage[slot], host, bytes, hipMemcpyHostToDevice, c->stream));
-  return 0;
+uint8_t* HostStaging::out(int slot, size_t bytes, void* host) {
+  if (!rc) rc = stage_reserve(c, slot, bytes);
+  if (rc) return nullptr;
+  if (host) copy_back(host, c->stage[slot], bytes);
+  return c->stage[slot];
 }
-int stage_out(bn254_ctx* c, int slot, void* host, size_t bytes) {
-  if (bytes) HIP_TRY(hipMemcpyAsync(host, c->stage[slot], bytes, hipMemcpyDeviceToHost, c->stream));
-  return 0;
+uint8_t* HostStaging::in(int slot, const void* host, size_t bytes) {
+  uint8_t* d = out(slot, bytes ? bytes : 1);
+  if (d && bytes) check(hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, c->stream));
+  return rc ? nullptr : d;
+}
+void HostStaging::copy_back(void* host, const void* dev, size_t bytes) {
+  if (!host || !bytes) return;
+  if (n_back == (int)(sizeof back / sizeof back[0])) { check(hipErrorInvalidValue); return; }   // more outputs than any entry point has
+  back[n_back++] = {host, dev, bytes};
+}
+hipError_t HostStaging::drain() {
+  finished = true;
+  const hipError_t e = hipStreamSynchronize(c->stream);
+  const hipError_t e_copy = hipStreamSynchronize(c->copy_stream);   // verify_host_overlapped's second stream (idle for every other call)
+  return e != hipSuccess ? e : e_copy;
+}
+int HostStaging::finish() {
+  for (int i = 0; i < n_back && !rc; ++i) check(hipMemcpyAsync(back[i].host, back[i].dev, back[i].bytes, hipMemcpyDeviceToHost, c->stream));
+  const hipError_t e = drain();
+  return rc ? rc : -(int)e;
 }
 // a pool outside the numbered slots (the comb table of the G2 generator): allocated once, never resized in practice
 int pool_reserve_one(bn254_ctx* c, Pool* p, size_t n_fp, size_t entries) {
@@ -991,35 +1008,38 @@ int bn254_batch_verify_compressed_device(bn254_ctx* c, const uint8_t* d_msgs, co
   else k_decompress_g2_ws<<<grid_for(n), BN_WAVE, 0, s>>>(d_pks65, n, c->ws);
   return verify_after_decode(c, s, d_msgs, d_off, n, d_status, false);
 }
+// An oversized host-pointer verify (bn254_batch_verify, _compressed): slices through the same entry point, each with its offsets rebased to
+// its own first message byte
+static int verify_host_sliced(bn254_ctx* c, const uint8_t* msgs, const uint64_t* off, const uint8_t* sigs, const uint8_t* pks, size_t n,
+                              uint32_t flags, uint8_t* status, size_t chunk, bool compressed) {
+  uint64_t* tmp = (uint64_t*)malloc((chunk + 1) * sizeof(uint64_t));
+  if (!tmp) return BN254_E_NO_MEMORY;
+  const size_t sig_sz = compressed ? 33 : 64, pk_sz = compressed ? 65 : 128;
+  int rc = 0;
+  for (size_t lo = 0; lo < n && !rc; lo += chunk) {
+    const size_t len = n - lo < chunk ? n - lo : chunk;
+    for (size_t i = 0; i <= len; ++i) tmp[i] = off[lo + i] - off[lo];
+    const uint8_t* m = msgs ? msgs + off[lo] : nullptr;
+    rc = compressed ? bn254_batch_verify_compressed(c, m, tmp, sigs + sig_sz * lo, pks + pk_sz * lo, len, status + lo)
+                    : bn254_batch_verify(c, m, tmp, sigs + sig_sz * lo, pks + pk_sz * lo, len, flags, status + lo);
+  }
+  free(tmp);
+  return rc;
+}
 int bn254_batch_verify_compressed(bn254_ctx* c, const uint8_t* msgs, const uint64_t* off, const uint8_t* sigs33, const uint8_t* pks65, size_t n,
                                   uint8_t* status) {
   MsgsLenScope msgs_len_scope(c);
   if (!c || (n && (!off || !sigs33 || !pks65 || !status))) return BN254_E_BAD_ARGUMENT;
   if (n == 0) return 0;
   HIP_TRY(hipSetDevice(c->device));
-  int rc;
-  if (!offsets_ok(off, n)) return BN254_E_BAD_ARGUMENT;
-  if (const size_t chunk = ws_chunk_for(c, n)) {       // an oversized batch in slices, offsets rebased per slice (see bn254_batch_verify)
-    uint64_t* tmp = (uint64_t*)malloc((chunk + 1) * sizeof(uint64_t));
-    if (!tmp) return BN254_E_NO_MEMORY;
-    rc = 0;
-    for (size_t lo = 0; lo < n && !rc; lo += chunk) {
-      const size_t len = n - lo < chunk ? n - lo : chunk;
-      for (size_t i = 0; i <= len; ++i) tmp[i] = off[lo + i] - off[lo];
-      rc = bn254_batch_verify_compressed(c, msgs ? msgs + off[lo] : nullptr, tmp, sigs33 + 33 * lo, pks65 + 65 * lo, len, status + lo);
-    }
-    free(tmp);
-    return rc;
-  }
-  if ((rc = stage_in(c, 0, msgs, (size_t)off[n]))) return rc;
-  if ((rc = stage_in(c, 1, off, (n + 1) * sizeof(uint64_t)))) return rc;
-  if ((rc = stage_in(c, 2, sigs33, n * 33))) return rc;
-  if ((rc = stage_in(c, 3, pks65, n * 65))) return rc;
-  if ((rc = stage_reserve(c, 4, n))) return rc;
-  if ((rc = bn254_batch_verify_compressed_device(c, c->stage[0], (const uint64_t*)c->stage[1], c->stage[2], c->stage[3], n, c->stage[4], nullptr))) return rc;
-  if ((rc = stage_out(c, 4, status, n))) return rc;
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return 0;
+  if (!msgs_ok(msgs, off, n)) return BN254_E_BAD_ARGUMENT;
+  if (const size_t chunk = ws_chunk_for(c, n)) return verify_host_sliced(c, msgs, off, sigs33, pks65, n, 0, status, chunk, true);
+  HostStaging st(c);
+  const uint8_t *d_msgs = st.in(0, msgs, (size_t)off[n]), *d_off = st.in(1, off, (n + 1) * sizeof(uint64_t));
+  const uint8_t *d_sigs = st.in(2, sigs33, n * 33), *d_pks = st.in(3, pks65, n * 65);
+  uint8_t* d_status = st.out(4, n, status);
+  if (st.ok()) st.rc = bn254_batch_verify_compressed_device(c, d_msgs, (const uint64_t*)d_off, d_sigs, d_pks, n, d_status, nullptr);
+  return st.finish();
 }
 
 // Pinned staging (BN254_OPT_PINNED_STAGING = T > 0): the caller's buffers are pageable, and a hipMemcpyAsync from pageable memory is
@@ -1070,13 +1090,15 @@ static int pinned_copy_in(bn254_ctx* c, uint8_t* d_dst, uint8_t* pin, const uint
   return 0;
 }
 static int verify_host_overlapped(bn254_ctx* c, const uint8_t* msgs, const uint64_t* off, const uint8_t* sigs, const uint8_t* pks, size_t n,
-                                  uint32_t flags, uint8_t* status, size_t msg_bytes) {
+                                  uint32_t flags, uint8_t* status) {
+  const size_t msg_bytes = (size_t)off[n];
   int rc;
   if ((rc = ws_reserve(c, n))) return rc;
-  for (int slot = 0; slot < 5; ++slot) {
-    const size_t need[5] = {msg_bytes ? msg_bytes : 1, (n + 1) * sizeof(uint64_t), n * 64, n * 128, n};
-    if ((rc = stage_reserve(c, slot, need[slot]))) return rc;
-  }
+  HostStaging st(c);               // the copies below go on two streams by hand; every return waits for both
+  const size_t need[4] = {msg_bytes ? msg_bytes : 1, (n + 1) * sizeof(uint64_t), n * 64, n * 128};
+  for (int slot = 0; slot < 4; ++slot) st.out(slot, need[slot]);
+  st.out(4, n, status);
+  if (!st.ok()) return st.rc;
   hipStream_t s = c->stream;
   const bool pinned = c->pinned_staging > 0 && n >= PINNED_STAGING_MIN_N;
   auto up = [](size_t x) { return (x + 4095) & ~(size_t)4095; };
@@ -1114,9 +1136,7 @@ static int verify_host_overlapped(bn254_ctx* c, const uint8_t* msgs, const uint6
   PROF_MARK(4);
   if (c->profiling) { c->ev_valid = 1; c->ev_hash_first = 1; }   // intervals: transfer + hash, decode, Miller, final exp.
   HIP_TRY(hipGetLastError());
-  if ((rc = stage_out(c, 4, status, n))) return rc;
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return 0;
+  return st.finish();
 }
 
 // Host-buffer entry point.  The hash-to-G1 rounds need only the messages, so those cross PCIe first and the hash
@@ -1129,43 +1149,17 @@ int bn254_batch_verify(bn254_ctx* c, const uint8_t* msgs, const uint64_t* off, c
   if (!c || (n && (!off || !sigs || !pks || !status))) return BN254_E_BAD_ARGUMENT;
   if (n == 0) return 0;
   HIP_TRY(hipSetDevice(c->device));
-  if (!offsets_ok(off, n)) return BN254_E_BAD_ARGUMENT;
-  size_t msg_bytes = (size_t)off[n];
-  if (msg_bytes && !msgs) return BN254_E_BAD_ARGUMENT;
-  int rc;
-  bool split = c->split_miller && n <= BN_SPLIT_MAX_N;
-  if (split) {                                       // A/B layout: plain staging, then the device entry point
-    if ((rc = stage_in(c, 0, msgs, msg_bytes))) return rc;
-    if ((rc = stage_in(c, 1, off, (n + 1) * sizeof(uint64_t)))) return rc;
-    if ((rc = stage_in(c, 2, sigs, n * 64))) return rc;
-    if ((rc = stage_in(c, 3, pks, n * 128))) return rc;
-    if ((rc = stage_reserve(c, 4, n))) return rc;
-    if ((rc = bn254_batch_verify_device(c, c->stage[0], (const uint64_t*)c->stage[1], c->stage[2], c->stage[3], n, flags, c->stage[4], nullptr))) return rc;
-    if ((rc = stage_out(c, 4, status, n))) return rc;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return 0;
+  if (!msgs_ok(msgs, off, n)) return BN254_E_BAD_ARGUMENT;
+  if (c->split_miller && n <= BN_SPLIT_MAX_N) {      // A/B layout: plain staging, then the device entry point
+    HostStaging st(c);
+    const uint8_t *d_msgs = st.in(0, msgs, (size_t)off[n]), *d_off = st.in(1, off, (n + 1) * sizeof(uint64_t));
+    const uint8_t *d_sigs = st.in(2, sigs, n * 64), *d_pks = st.in(3, pks, n * 128);
+    uint8_t* d_status = st.out(4, n, status);
+    if (st.ok()) st.rc = bn254_batch_verify_device(c, d_msgs, (const uint64_t*)d_off, d_sigs, d_pks, n, flags, d_status, nullptr);
+    return st.finish();
   }
-  if (const size_t chunk = ws_chunk_for(c, n)) {
-    // an oversized batch: slices through this same entry point, each with its offsets rebased to its own first message byte
-    uint64_t* tmp = (uint64_t*)malloc((chunk + 1) * sizeof(uint64_t));
-    if (!tmp) return BN254_E_NO_MEMORY;
-    rc = 0;
-    for (size_t lo = 0; lo < n && !rc; lo += chunk) {
-      const size_t len = n - lo < chunk ? n - lo : chunk;
-      for (size_t i = 0; i <= len; ++i) tmp[i] = off[lo + i] - off[lo];
-      rc = bn254_batch_verify(c, msgs ? msgs + off[lo] : nullptr, tmp, sigs + 64 * lo, pks + 128 * lo, len, flags, status + lo);
-    }
-    free(tmp);
-    return rc;
-  }
-  rc = verify_host_overlapped(c, msgs, off, sigs, pks, n, flags, status, msg_bytes);
-  if (rc) {
-    // a failure after the first asynchronous enqueue: the copies and kernels already in flight still read the caller's
-    // buffers — wait for both streams before handing them back
-    (void)hipStreamSynchronize(c->copy_stream);
-    (void)hipStreamSynchronize(c->stream);
-  }
-  return rc;
+  if (const size_t chunk = ws_chunk_for(c, n)) return verify_host_sliced(c, msgs, off, sigs, pks, n, flags, status, chunk, false);
+  return verify_host_overlapped(c, msgs, off, sigs, pks, n, flags, status);
 }
 
 int bn254_batch_hash_to_g1_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t* d_off, size_t n, uint8_t* d_points, uint8_t* d_status,
@@ -1195,19 +1189,12 @@ int bn254_batch_hash_to_g1(bn254_ctx* c, const uint8_t* msgs, const uint64_t* of
   if (!c || (n && (!off || !points || !status))) return BN254_E_BAD_ARGUMENT;
   if (n == 0) return 0;
   HIP_TRY(hipSetDevice(c->device));
-  int rc;
-  if (!offsets_ok(off, n)) return BN254_E_BAD_ARGUMENT;
-  if ((rc = stage_in(c, 0, msgs, (size_t)off[n]))) return rc;
-  if ((rc = stage_in(c, 1, off, (n + 1) * sizeof(uint64_t)))) return rc;
-  if ((rc = stage_reserve(c, 2, n * 64))) return rc;
-  if ((rc = stage_reserve(c, 3, n))) return rc;
-  if ((rc = stage_reserve(c, 4, n))) return rc;
-  if ((rc = bn254_batch_hash_to_g1_device(c, c->stage[0], (const uint64_t*)c->stage[1], n, c->stage[2], c->stage[3], c->stage[4], nullptr))) return rc;
-  if ((rc = stage_out(c, 2, points, n * 64))) return rc;
-  if ((rc = stage_out(c, 3, status, n))) return rc;
-  if (tries && (rc = stage_out(c, 4, tries, n))) return rc;
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return 0;
+  if (!msgs_ok(msgs, off, n)) return BN254_E_BAD_ARGUMENT;
+  HostStaging st(c);
+  const uint8_t *d_msgs = st.in(0, msgs, (size_t)off[n]), *d_off = st.in(1, off, (n + 1) * sizeof(uint64_t));
+  uint8_t *d_points = st.out(2, n * 64, points), *d_status = st.out(3, n, status), *d_tries = st.out(4, n, tries);
+  if (st.ok()) st.rc = bn254_batch_hash_to_g1_device(c, d_msgs, (const uint64_t*)d_off, n, d_points, d_status, d_tries, nullptr);
+  return st.finish();
 }
 
 // shared by pairing / pairing_check: mode 0 = reduced Gt + status, 1 = raw Miller value (debug)
@@ -1256,16 +1243,11 @@ static int pairing_host(bn254_ctx* c, const uint8_t* g1, const uint8_t* g2, size
   if (!c || k == 0 || (n && (!g1 || !g2))) return BN254_E_BAD_ARGUMENT;
   if (n == 0) return 0;
   HIP_TRY(hipSetDevice(c->device));
-  int rc;
-  if ((rc = stage_in(c, 0, g1, n * k * 64))) return rc;
-  if ((rc = stage_in(c, 1, g2, n * k * 128))) return rc;
-  if ((rc = stage_reserve(c, 2, n * 384))) return rc;
-  if ((rc = stage_reserve(c, 3, n))) return rc;
-  if ((rc = pairing_device(c, c->stage[0], c->stage[1], n, k, flags, gt ? c->stage[2] : nullptr, c->stage[3], nullptr, raw_only))) return rc;
-  if (gt && (rc = stage_out(c, 2, gt, n * 384))) return rc;
-  if (status && (rc = stage_out(c, 3, status, n))) return rc;
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return 0;
+  HostStaging st(c);
+  const uint8_t *d_g1 = st.in(0, g1, n * k * 64), *d_g2 = st.in(1, g2, n * k * 128);
+  uint8_t *d_gt = st.out(2, n * 384, gt), *d_status = st.out(3, n, status);
+  if (st.ok()) st.rc = pairing_device(c, d_g1, d_g2, n, k, flags, gt ? d_gt : nullptr, d_status, nullptr, raw_only);
+  return st.finish();
 }
 int bn254_batch_pairing_check(bn254_ctx* c, const uint8_t* g1, const uint8_t* g2, size_t n, size_t k, uint32_t flags, uint8_t* status) {
   if (!status && n) return BN254_E_BAD_ARGUMENT;
@@ -1286,23 +1268,22 @@ int bn254_batch_check_public_keys(bn254_ctx* c, const uint8_t* pk_g2, const uint
   HIP_TRY(hipSetDevice(c->device));
   int rc;
   if ((rc = ws_reserve(c, n))) return rc;
-  if ((rc = stage_in(c, 0, pk_g2, n * 128))) return rc;
-  if ((rc = stage_in(c, 1, pk_g1, n * 64))) return rc;
-  if ((rc = stage_reserve(c, 2, n))) return rc;
+  HostStaging st(c);
+  const uint8_t *d_g2 = st.in(0, pk_g2, n * 128), *d_g1 = st.in(1, pk_g1, n * 64);
+  uint8_t* d_status = st.out(2, n, status);
+  if (!st.ok()) return st.rc;
   hipStream_t s = c->stream;
   unsigned g = grid_for(n);
-  if ((rc = launch_decode_g2(c, s, c->stage[0], n, flags, 0))) return rc;       // ecdsa.rs:82: pk_g2 first
-  k_decode_g1<<<g, BN_WAVE, 0, s>>>(c->stage[1], n, flags, c->ws, PL_P1X, BY_P1_INF, 1);
+  if ((rc = launch_decode_g2(c, s, d_g2, n, flags, 0))) return rc;       // ecdsa.rs:82: pk_g2 first
+  k_decode_g1<<<g, BN_WAVE, 0, s>>>(d_g1, n, flags, c->ws, PL_P1X, BY_P1_INF, 1);
   if (c->pair_lanes) {
-    if ((rc = launch_pair_or_trio(c, s, n, 0, c->stage[2], 1, false))) return rc;
+    if ((rc = launch_pair_or_trio(c, s, n, 0, d_status, 1, false))) return rc;
   } else {
     k_miller_cpk<<<g, BN_WAVE, 0, s>>>(n, c->ws);
-    k_final_exp<<<g, BN_WAVE, 0, s>>>(n, 1, 1, 1, c->ws, 0, nullptr, c->stage[2], 0, 0, nullptr, nullptr);
+    k_final_exp<<<g, BN_WAVE, 0, s>>>(n, 1, 1, 1, c->ws, 0, nullptr, d_status, 0, 0, nullptr, nullptr);
   }
   HIP_TRY(hipGetLastError());
-  if ((rc = stage_out(c, 2, status, n))) return rc;
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return 0;
+  return st.finish();
 }
 
 }  // extern "C"

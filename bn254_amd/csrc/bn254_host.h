@@ -136,8 +136,6 @@ BN_HIDDEN int ws_reserve(bn254_ctx* c, size_t n);
 // KD_BYTES_PER_ITEM per item + KD_BYTES_PER_KEY per key of BN254_OPT_KEY_DEDUP_MAX_KEYS)
 BN_HIDDEN size_t ws_chunk_for(bn254_ctx* c, size_t n, size_t ws_per_item = 1, bool key_dedup = false);
 BN_HIDDEN int stage_reserve(bn254_ctx* c, int slot, size_t bytes);
-BN_HIDDEN int stage_in(bn254_ctx* c, int slot, const void* host, size_t bytes);
-BN_HIDDEN int stage_out(bn254_ctx* c, int slot, void* host, size_t bytes);
 BN_HIDDEN int pool_reserve(bn254_ctx* c, int which, size_t n_fp, size_t entries);
 BN_HIDDEN int pool_reserve_one(bn254_ctx* c, Pool* p, size_t n_fp, size_t entries);
 static inline bool misaligned(const void* p) { return ((uintptr_t)p & 3u) != 0; }
@@ -148,6 +146,8 @@ static inline bool offsets_ok(const uint64_t* off, size_t n) {
   for (size_t i = 0; i < n; ++i) if (off[i] > off[i + 1]) return false;
   return true;
 }
+// ... and the messages those offsets index: bytes to stage (off[n] > 0) need a buffer to stage them from
+static inline bool msgs_ok(const uint8_t* msgs, const uint64_t* off, size_t n) { return offsets_ok(off, n) && (off[n] == 0 || msgs); }
 // bn254_ctx_expect_msgs_len is consumed by the NEXT entry point that hashes messages — whatever that call goes on to do: every such
 // entry point opens with a MsgsLenScope, which takes the declaration and clears it before any argument check, staging step or
 // allocation can return early (a declaration left armed would bound-check an unrelated later call against the wrong length).
@@ -162,6 +162,31 @@ struct MsgsLenScope {
   ~MsgsLenScope() { if (c) --c->entry_depth; }
   MsgsLenScope(const MsgsLenScope&) = delete;
   MsgsLenScope& operator=(const MsgsLenScope&) = delete;
+};
+// The staging of a host-pointer entry point: the caller's buffers cross into the context's numbered slots (c->stage[slot]) on c->stream,
+// the outputs come back the same way.  Those copies read and write the caller's memory until the streams drain, so a HostStaging keeps
+// one rule on every path out: a call that has opened one returns only after c->stream and c->copy_stream are idle — finish() on the way
+// out, the destructor on an early return.  Errors are sticky: after the first one in() / out() do nothing, no copy goes back, and
+// finish() returns it.  The caller numbers the slots, because calls nest: mul_host -> *_mul_device -> comb_build stages into 5 .. 7
+// while mul_host holds 0 .. 3.
+struct BN_HIDDEN HostStaging {
+  bn254_ctx* c;
+  int rc = 0;                                              // the call's first error
+  explicit HostStaging(bn254_ctx* ctx) : c(ctx) {}
+  ~HostStaging() { if (!finished) (void)drain(); }
+  bool ok() const { return rc == 0; }
+  void check(hipError_t e) { if (!rc && e != hipSuccess) rc = -(int)e; }
+  uint8_t* in(int slot, const void* host, size_t bytes);   // reserve the slot and enqueue the H2D copy: the slot's device pointer
+  uint8_t* out(int slot, size_t bytes, void* host = nullptr);   // reserve the slot: its device pointer; finish() copies it to `host`
+  void copy_back(void* host, const void* dev, size_t bytes);      // ... the same for device memory outside the slots
+  int finish();      // unless the call has failed, enqueue the copies back; wait: the call's first error, else the wait's
+  HostStaging(const HostStaging&) = delete;
+  HostStaging& operator=(const HostStaging&) = delete;
+ private:
+  hipError_t drain();                                      // wait for c->stream and c->copy_stream
+  struct Back { void* host; const void* dev; size_t bytes; } back[4];
+  int n_back = 0;
+  bool finished = false;
 };
 
 // Enqueue the hash-to-G1 rounds for n messages; points land in planes (px, px+1), statuses in BY_ST_HASH.

@@ -354,12 +354,13 @@ int bn254_ctx_register_keys(bn254_ctx* c, const uint8_t* pks, size_t n_keys, uin
     HIP_TRY(hipMalloc((void**)&c->key_inf, n_keys));
     c->key_cap = n_keys;
   }
-  int rc;
-  if ((rc = stage_in(c, 3, pks, n_keys * 128))) return rc;
-  k_register_keys<<<grid_for(n_keys), BN_WAVE, 0, c->stream>>>(c->stage[3], n_keys, flags & FLAG_REJECT_IDENTITY, c->key_lines, c->key_st, c->key_inf, c->key_xy);
+  HostStaging st(c);
+  const uint8_t* d_pks = st.in(3, pks, n_keys * 128);
+  st.copy_back(key_status, c->key_st, n_keys);
+  if (!st.ok()) return st.rc;
+  k_register_keys<<<grid_for(n_keys), BN_WAVE, 0, c->stream>>>(d_pks, n_keys, flags & FLAG_REJECT_IDENTITY, c->key_lines, c->key_st, c->key_inf, c->key_xy);
   HIP_TRY(hipGetLastError());
-  if (key_status) HIP_TRY(hipMemcpyAsync(key_status, c->key_st, n_keys, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (const int rc = st.finish()) return rc;
   c->n_keys = n_keys;
   return 0;
 }
@@ -424,18 +425,13 @@ int bn254_batch_verify_keyed(bn254_ctx* c, const uint8_t* msgs, const uint64_t* 
   if (!c || (n && (!off || !sigs || !key_idx || !status))) return BN254_E_BAD_ARGUMENT;
   if (n == 0) return 0;
   HIP_TRY(hipSetDevice(c->device));
-  if (!offsets_ok(off, n)) return BN254_E_BAD_ARGUMENT;
-  if (off[n] && !msgs) return BN254_E_BAD_ARGUMENT;
-  int rc;
-  if ((rc = stage_in(c, 0, msgs, (size_t)off[n]))) return rc;
-  if ((rc = stage_in(c, 1, off, (n + 1) * sizeof(uint64_t)))) return rc;
-  if ((rc = stage_in(c, 2, sigs, n * 64))) return rc;
-  if ((rc = stage_in(c, 3, key_idx, n * sizeof(uint32_t)))) return rc;
-  if ((rc = stage_reserve(c, 4, n))) return rc;
-  rc = bn254_batch_verify_keyed_device(c, c->stage[0], (const uint64_t*)c->stage[1], c->stage[2], (const uint32_t*)c->stage[3], n, flags, c->stage[4], nullptr);
-  if (!rc) rc = stage_out(c, 4, status, n);
-  hipError_t e = hipStreamSynchronize(c->stream);     // also on failure: the staged copies read the caller's buffers
-  return rc ? rc : -(int)e;
+  if (!msgs_ok(msgs, off, n)) return BN254_E_BAD_ARGUMENT;
+  HostStaging st(c);
+  const uint8_t *d_msgs = st.in(0, msgs, (size_t)off[n]), *d_off = st.in(1, off, (n + 1) * sizeof(uint64_t));
+  const uint8_t *d_sigs = st.in(2, sigs, n * 64), *d_key_idx = st.in(3, key_idx, n * sizeof(uint32_t));
+  uint8_t* d_status = st.out(4, n, status);
+  if (st.ok()) st.rc = bn254_batch_verify_keyed_device(c, d_msgs, (const uint64_t*)d_off, d_sigs, (const uint32_t*)d_key_idx, n, flags, d_status, nullptr);
+  return st.finish();
 }
 
 int bn254_batch_verify_keyed_randomized_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t* d_off, const uint8_t* d_sigs,
@@ -497,19 +493,14 @@ int bn254_batch_verify_keyed_randomized(bn254_ctx* c, const uint8_t* msgs, const
   if (!c || !seed32 || (n && (!off || !sigs || !key_idx || !status))) return BN254_E_BAD_ARGUMENT;
   if (n == 0) return 0;
   HIP_TRY(hipSetDevice(c->device));
-  if (!offsets_ok(off, n)) return BN254_E_BAD_ARGUMENT;
-  if (off[n] && !msgs) return BN254_E_BAD_ARGUMENT;
-  int rc;
-  if ((rc = stage_in(c, 0, msgs, (size_t)off[n]))) return rc;
-  if ((rc = stage_in(c, 1, off, (n + 1) * sizeof(uint64_t)))) return rc;
-  if ((rc = stage_in(c, 2, sigs, n * 64))) return rc;
-  if ((rc = stage_in(c, 3, key_idx, n * sizeof(uint32_t)))) return rc;
-  if ((rc = stage_reserve(c, 4, n))) return rc;
-  rc = bn254_batch_verify_keyed_randomized_device(c, c->stage[0], (const uint64_t*)c->stage[1], c->stage[2], (const uint32_t*)c->stage[3], n, flags, seed32,
-                                                  c->stage[4], nullptr);
-  if (!rc) rc = stage_out(c, 4, status, n);
-  hipError_t e = hipStreamSynchronize(c->stream);
-  return rc ? rc : -(int)e;
+  if (!msgs_ok(msgs, off, n)) return BN254_E_BAD_ARGUMENT;
+  HostStaging st(c);
+  const uint8_t *d_msgs = st.in(0, msgs, (size_t)off[n]), *d_off = st.in(1, off, (n + 1) * sizeof(uint64_t));
+  const uint8_t *d_sigs = st.in(2, sigs, n * 64), *d_key_idx = st.in(3, key_idx, n * sizeof(uint32_t));
+  uint8_t* d_status = st.out(4, n, status);
+  if (st.ok())
+    st.rc = bn254_batch_verify_keyed_randomized_device(c, d_msgs, (const uint64_t*)d_off, d_sigs, (const uint32_t*)d_key_idx, n, flags, seed32, d_status, nullptr);
+  return st.finish();
 }
 
 int bn254_batch_verify_randomized_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t* d_off, const uint8_t* d_sigs,
@@ -587,21 +578,14 @@ int bn254_batch_verify_randomized(bn254_ctx* c, const uint8_t* msgs, const uint6
   if (!c || !seed32 || (n && (!off || !sigs || !pks || !status))) return BN254_E_BAD_ARGUMENT;
   if (n == 0) return 0;
   HIP_TRY(hipSetDevice(c->device));
-  if (!offsets_ok(off, n)) return BN254_E_BAD_ARGUMENT;
-  size_t msg_bytes = (size_t)off[n], n_groups = (n + BN_WAVE - 1) / BN_WAVE;
-  int rc;
-  if ((rc = stage_in(c, 0, msgs, msg_bytes))) return rc;
-  if ((rc = stage_in(c, 1, off, (n + 1) * sizeof(uint64_t)))) return rc;
-  if ((rc = stage_in(c, 2, sigs, n * 64))) return rc;
-  if ((rc = stage_in(c, 3, pks, n * 128))) return rc;
-  if ((rc = stage_reserve(c, 4, n))) return rc;
-  if ((rc = stage_reserve(c, 5, n_groups))) return rc;
-  if ((rc = bn254_batch_verify_randomized_device(c, c->stage[0], (const uint64_t*)c->stage[1], c->stage[2], c->stage[3], n, flags, seed32,
-                                                 c->stage[4], c->stage[5], nullptr))) return rc;
-  if ((rc = stage_out(c, 4, status, n))) return rc;
-  if (group_ok && (rc = stage_out(c, 5, group_ok, n_groups))) return rc;
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return 0;
+  if (!msgs_ok(msgs, off, n)) return BN254_E_BAD_ARGUMENT;
+  const size_t n_groups = (n + BN_WAVE - 1) / BN_WAVE;
+  HostStaging st(c);
+  const uint8_t *d_msgs = st.in(0, msgs, (size_t)off[n]), *d_off = st.in(1, off, (n + 1) * sizeof(uint64_t));
+  const uint8_t *d_sigs = st.in(2, sigs, n * 64), *d_pks = st.in(3, pks, n * 128);
+  uint8_t *d_status = st.out(4, n, status), *d_group_ok = st.out(5, n_groups, group_ok);
+  if (st.ok()) st.rc = bn254_batch_verify_randomized_device(c, d_msgs, (const uint64_t*)d_off, d_sigs, d_pks, n, flags, seed32, d_status, d_group_ok, nullptr);
+  return st.finish();
 }
 
 }  // extern "C"

@@ -27,7 +27,8 @@
  * -(hipError_t) for a HIP runtime failure, BN254_E_* for bad arguments.
  *
  * Ownership/threading: the caller owns every buffer; the library keeps no pointer after a
- * host-pointer call returns.  A bn254_ctx is used by one thread at a time; distinct contexts
+ * host-pointer call returns: such a call returns only after every copy from and to the caller's
+ * buffers has finished, also when it fails.  A bn254_ctx is used by one thread at a time; distinct contexts
  * (distinct devices) are fully concurrent.  There is NO CPU fallback: every entry point runs
  * HIP kernels on the context's device and fails if that is impossible.
  *

@@ -162,3 +162,19 @@ def test_generated_csqr_assembly_is_simulated_and_current():
     out = subprocess.check_output([sys.executable, gen, "selftest_mul"], text=True)
     assert "selftest mul ok" in out and "called 18 times" in out
     assert subprocess.check_output([sys.executable, gen, "header_mul"], text=True) == open(os.path.join(ROOT, "bn254_amd", "csrc", "bn254_mul_asm.h")).read()
+
+
+def test_host_pointer_staging_goes_through_one_helper():
+    """Every host-pointer entry point stages the caller's buffers through HostStaging (bn254_amd/csrc/bn254_host.h), which waits for the
+    context's streams on every path out, error returns included.  No source but the one that defines it enqueues a staging copy or waits
+    for the context's stream by hand: an entry point that did would be back to returning with copies still reading the caller's buffers."""
+    csrc = os.path.join(ROOT, "bn254_amd", "csrc")
+    by_hand = re.compile(r"\bstage_in\(|\bstage_out\(|hipStreamSynchronize\(\s*c->stream\s*\)")
+    offenders = {}
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith((".hip", ".h", ".inc")) and f != "bn254_hip.hip":
+            lines = [i + 1 for i, line in enumerate(open(os.path.join(csrc, f))) if by_hand.search(line)]
+            if lines:
+                offenders[f] = lines
+    assert not offenders, offenders
+    assert "HostStaging::finish()" in open(os.path.join(csrc, "bn254_hip.hip")).read()

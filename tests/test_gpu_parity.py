@@ -1271,6 +1271,19 @@ def test_argument_validation_and_empty_batches(eng):
     pts = ctypes.create_string_buffer(192)
     assert L.bn254_batch_hash_to_g1(h, bytes(64), bad_off, 3, pts, st, None) == -10001
     assert L.bn254_batch_g1_sum(h, bytes(64 * 48), bad_off, 3, pts, st) == -10001
+    # ... and messages passed as NULL while the offsets say there are message bytes to stage (every host form that takes messages)
+    off1, one = (ctypes.c_uint64 * 2)(0, 32), (ctypes.c_uint64 * 2)(0, 1)
+    idx = (ctypes.c_uint32 * 1)(0)
+    assert L.bn254_batch_verify(h, None, off1, bytes(64), bytes(128), 1, 0, st) == -10001
+    assert L.bn254_batch_verify_compressed(h, None, off1, bytes(33), bytes(65), 1, st) == -10001
+    assert L.bn254_batch_verify_keyed(h, None, off1, bytes(64), idx, 1, 0, st) == -10001
+    assert L.bn254_batch_verify_keyed_randomized(h, None, off1, bytes(64), idx, 1, 0, bytes(32), st) == -10001
+    assert L.bn254_batch_verify_randomized(h, None, off1, bytes(64), bytes(128), 1, 0, bytes(32), st, None) == -10001
+    assert L.bn254_batch_hash_to_g1(h, None, off1, 1, pts, st, None) == -10001
+    assert L.bn254_batch_sign(h, None, off1, bytes(32), 1, pts, st) == -10001
+    assert L.bn254_batch_aggregate_verify(h, None, off1, 1, bytes(128), 1, bytes(64), idx, one, idx, 1, 0, st) == -10001
+    assert L.bn254_ctx_register_pools(h, None, off1, 1, bytes(128), 1, bytes(64), 0, 1) == -10001
+    assert L.bn254_batch_aggregate_verify_distinct(h, None, off1, bytes(128), 1, bytes(64), one, 1, 0, st) == -10001
     # the context is still usable afterwards
     from tests.datagen import make_verify_batch
     msgs, sigs, pks, expected = make_verify_batch(eng, 130)

@@ -238,9 +238,7 @@ static int aggd_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t* d_ms
   if (c->pair_lanes) {
     // tail into index i (obase 0: everything below gbase is consumed by now), then the final exponentiation a verify of n items runs
     if ((rc = bn254_pair_aggd_tail(n, c->ws, gbase, 0, s))) return rc;
-    if (route_for(c, n).fe == BN_FE_LANE_PAIRS) rc = bn254_pair_final_exp(n, c->ws, 0, d_status, nullptr, nullptr, s, 0);
-    else rc = launch_small_final_exp(c, s, n, 0, d_status);
-    if (rc) return rc;
+    if ((rc = launch_final_exp_layout(c, s, n, 0, d_status, route_for(c, n).fe))) return rc;
   } else {
     if ((rc = launch_rand_tail_lane(c, s, n, gbase))) return rc;
     if ((rc = launch_final_exp_lane(c, s, n, 1, 1, 1, 0, nullptr, d_status, 0, gbase, nullptr, nullptr))) return rc;

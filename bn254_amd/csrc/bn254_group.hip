@@ -776,15 +776,9 @@ static int agg_run(bn254_ctx* c, hipStream_t s, const AggTables& t, const uint32
     k_aggregate<<<grid_for(n), BN_WAVE, 0, s>>>(d_tuple_msg, d_tuple_off, d_signer_idx, n, n_signers, n_msgs, c->pool[0], c->pool[1], c->pool[2], c->ws);
   }
   PROF_MARK(2);
-  if (c->pair_lanes) {
-    // the aggregated tuples are verify-shaped: batches that cannot fill the chip take the small-batch kernels (one aggregate verify: the
-    // pairing part 9.8 -> 1.0 ms)
-    if ((rc = launch_pair_or_trio(c, s, n, 1, d_status, 0, true))) return rc;
-  } else {
-    { int rc_ = launch_miller_verify_lane(c, s, n, nullptr, nullptr); if (rc_) return rc_; }
-    PROF_MARK(3);
-    { int rc_ = launch_final_exp_lane(c, s, n, 1, 1, 1, 1, nullptr, d_status, 0, 0, nullptr, nullptr); if (rc_) return rc_; }
-  }
+  // the aggregated tuples are verify-shaped: batches that cannot fill the chip take the small-batch kernels (one aggregate verify: the
+  // pairing part 9.8 -> 1.0 ms)
+  if ((rc = launch_verify_miller_fe(c, s, n, BN_PAIRS_VERIFY, 1, d_status, true))) return rc;
   PROF_MARK(4);
   if (c->profiling) { c->ev_valid = 1; c->ev_hash_first = 0; }
   HIP_TRY(hipGetLastError());

@@ -858,14 +858,10 @@ int bn254_ctx_last_kernel_ms(bn254_ctx* c, float ms[4]) {
 
 
 }  // extern "C"
-// Miller loop + final exponentiation of a verify-shaped batch on lane pairs, or — for batches that cannot fill the chip —
-// in the octet layout (three lane pairs share the Fq6 products of every Fq12 operation: fewer instructions per lane,
-// which is what latency is made of when a wave has its SIMD to itself).  Same status bytes either way.
-// final exponentiation of a small batch: the smallest on nine lane pairs per verify (bn254_nonet.hip; eighteen while one verify per wave
-// still covers the batch) — fewer instructions per lane again —, the others in the octet layout
-// (the layouts come from the routing table, bn254_ws.h: bn_route; a caller that has ALREADY chosen a small-batch Miller kernel — the keyed lane
-// machine — asks for the small-batch final exponentiation of the same row)
-static int launch_final_exp_layout(bn254_ctx* c, hipStream_t s, size_t n, int use_hash, uint8_t* d_status, int fe) {
+// final exponentiation of a verify-shaped batch in the layout of its routing-table row (bn254_ws.h: bn_route): lane pairs; small batches in
+// the octet layout; the smallest on nine lane pairs per verify (bn254_nonet.hip; eighteen while one verify per wave still covers the batch) —
+// fewer instructions per lane again.  Callers with a Miller kernel of their own (the keyed lane machine, aggd_device) pass route_for(c, n).fe.
+int launch_final_exp_layout(bn254_ctx* c, hipStream_t s, size_t n, int use_hash, uint8_t* d_status, int fe) {
   switch (fe) {
     case BN_FE_NONET_WIDE: return bn254_nonet_final_exp(n, c->ws, use_hash, d_status, s, 1);
     case BN_FE_NONET: return bn254_nonet_final_exp(n, c->ws, use_hash, d_status, s, 0);
@@ -873,20 +869,27 @@ static int launch_final_exp_layout(bn254_ctx* c, hipStream_t s, size_t n, int us
     default: return bn254_pair_final_exp(n, c->ws, use_hash, d_status, nullptr, nullptr, s);
   }
 }
-int launch_small_final_exp(bn254_ctx* c, hipStream_t s, size_t n, int use_hash, uint8_t* d_status) {
-  const BnRoute r = route_for(c, n);
-  return launch_final_exp_layout(c, s, n, use_hash, d_status, r.fe == BN_FE_LANE_PAIRS ? BN_FE_OCTET : r.fe);
-}
-int launch_pair_or_trio(bn254_ctx* c, hipStream_t s, size_t n, int use_hash, uint8_t* d_status, int mode, bool mark) {
+// Miller loop + final exponentiation of a verify-shaped batch on lane pairs, or — for batches that cannot fill the chip — in the octet layout
+// (three lane pairs share the Fq6 products of every Fq12 operation: fewer instructions per lane, which is what latency is made of when a wave
+// has its SIMD to itself).  Same status bytes either way.  BN254_OPT_PAIR_LANES = 0: one lane per item, the fused two-pair loop (A/B layout).
+int launch_verify_miller_fe(bn254_ctx* c, hipStream_t s, size_t n, int pairs, int use_hash, uint8_t* d_status, bool mark) {
+  if (!c->pair_lanes) {
+    const unsigned g = grid_for(n);
+    if (pairs == BN_PAIRS_CHECK_PKS) k_miller_cpk<<<g, BN_WAVE, 0, s>>>(n, c->ws);
+    else k_miller_verify<<<g, BN_WAVE, 0, s>>>(n, c->ws, nullptr, nullptr);
+    if (mark) PROF_MARK(3);
+    k_final_exp<<<g, BN_WAVE, 0, s>>>(n, 1, 1, 1, c->ws, use_hash, nullptr, d_status, 0, 0, nullptr, nullptr);
+    return 0;
+  }
   const BnRoute r = route_for(c, n);
   int rc;
   switch (r.miller) {
-    case BN_ML_LANE_MACHINE: rc = bn254_lm_miller_verify(n, c->ws, s, mode); break;
+    case BN_ML_LANE_MACHINE: rc = bn254_lm_miller_verify(n, c->ws, s, pairs); break;
     case BN_ML_WAVE_ROLES:         // BN254_OPT_TRIO_WAVE_ROLES (developer knob): eight waves (default), four, or the lane groups of one wave
-      rc = c->trio_wave_roles == 2 ? bn254_w8_miller_verify(n, c->ws, s, mode)
-           : c->trio_wave_roles ? bn254_quad_miller_verify(n, c->ws, s, mode) : bn254_trio_miller_verify(n, c->ws, s, mode);
+      rc = c->trio_wave_roles == 2 ? bn254_w8_miller_verify(n, c->ws, s, pairs)
+           : c->trio_wave_roles ? bn254_quad_miller_verify(n, c->ws, s, pairs) : bn254_trio_miller_verify(n, c->ws, s, pairs);
       break;
-    default: rc = bn254_pair_miller_verify(n, c->ws, nullptr, nullptr, s, mode); break;
+    default: rc = bn254_pair_miller_verify(n, c->ws, nullptr, nullptr, s, pairs); break;
   }
   if (rc) return rc;
   if (mark) PROF_MARK(3);
@@ -894,15 +897,11 @@ int launch_pair_or_trio(bn254_ctx* c, hipStream_t s, size_t n, int use_hash, uin
 }
 
 extern "C" {
-// decode kernels have filled the P1 / Q planes and BY_ST_DECODE: hash, Miller loop, final exponentiation
-// kd: the key-dedup buffers when bn254_kd_enqueue runs beside decode and hash on c->kd_stream (joined by c->kd_join), else null
-static int verify_after_decode(bn254_ctx* c, hipStream_t s, const uint8_t* d_msgs, const uint64_t* d_off, size_t n, uint8_t* d_status, bool split,
-                               const KeyDedup* kd = nullptr) {
+// the end of every verify (device and host-pointer): decode and hash have filled the P1 / P2 / Q planes — Miller loop, final exponentiation,
+// the last profiling event.  kd: the key-dedup buffers when bn254_kd_enqueue runs beside decode and hash on c->kd_stream (joined by
+// c->kd_join), else null; split: BN254_OPT_SPLIT_MILLER's layout; hash_first: the order of the intervals (bn254_ctx_last_kernel_ms)
+static int verify_tail(bn254_ctx* c, hipStream_t s, size_t n, uint8_t* d_status, bool split, const KeyDedup* kd, int hash_first) {
   int rc;
-  unsigned g = grid_for(n);
-  PROF_MARK(1);
-  if ((rc = launch_hash_rounds(c, s, d_msgs, d_off, n, PL_P2X, BY_P2_INF, nullptr))) return rc;
-  PROF_MARK(2);
   if (kd) {
     // both Miller kernels are enqueued; each reads its item count from the device-side decision (k_kd_decide) and one of them returns at
     // once.  The wait for the builder counts in the Miller stage.
@@ -913,20 +912,23 @@ static int verify_after_decode(bn254_ctx* c, hipStream_t s, const uint8_t* d_msg
     PROF_MARK(3);
     if ((rc = bn254_pair_final_exp(n, c->ws, 1, d_status, nullptr, nullptr, s))) return rc;
   } else if (split) {
+    const unsigned g = grid_for(n);
     k_miller_verify_split<<<2 * g, BN_WAVE, 0, s>>>(n, c->ws.stride / 2, g, c->ws);
     PROF_MARK(3);
     k_final_exp<<<g, BN_WAVE, 0, s>>>(n, 2, 1, c->ws.stride / 2, c->ws, 1, nullptr, d_status, 0, 0, nullptr, nullptr);
-  } else if (c->pair_lanes) {
-    if ((rc = launch_pair_or_trio(c, s, n, 1, d_status, 0, true))) return rc;
-  } else {
-    k_miller_verify<<<g, BN_WAVE, 0, s>>>(n, c->ws, nullptr, nullptr);
-    PROF_MARK(3);
-    k_final_exp<<<g, BN_WAVE, 0, s>>>(n, 1, 1, 1, c->ws, 1, nullptr, d_status, 0, 0, nullptr, nullptr);
-  }
+  } else if ((rc = launch_verify_miller_fe(c, s, n, BN_PAIRS_VERIFY, 1, d_status, true))) return rc;
   PROF_MARK(4);
-  if (c->profiling) { c->ev_valid = 1; c->ev_hash_first = 0; }
+  if (c->profiling) { c->ev_valid = 1; c->ev_hash_first = hash_first; }
   HIP_TRY(hipGetLastError());
   return 0;
+}
+// decode kernels have filled the P1 / Q planes and BY_ST_DECODE: hash, then the verify's tail
+static int verify_after_decode(bn254_ctx* c, hipStream_t s, const uint8_t* d_msgs, const uint64_t* d_off, size_t n, uint8_t* d_status, bool split,
+                               const KeyDedup* kd = nullptr) {
+  PROF_MARK(1);
+  if (const int rc = launch_hash_rounds(c, s, d_msgs, d_off, n, PL_P2X, BY_P2_INF, nullptr)) return rc;
+  PROF_MARK(2);
+  return verify_tail(c, s, n, d_status, split, kd, 0);
 }
 
 int bn254_batch_verify_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t* d_off, const uint8_t* d_sigs, const uint8_t* d_pks,
@@ -943,16 +945,10 @@ int bn254_batch_verify_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_
   // key dedup (bn254_keydedup.hip): batches on the lane-pair Miller kernel look for repeated keys and take the keyed loop when they pay off
   bool key_dedup = c->key_dedup && c->kd_max_keys > 0 && c->pair_lanes && !split && n <= 0xFFFFFFFFu &&
                          route_for(c, n).miller == BN_ML_LANE_PAIRS && route_for(c, n).fe == BN_FE_LANE_PAIRS;
-  if (const size_t chunk = ws_chunk_for(c, n, split ? 2 : 1, key_dedup)) {
-    // an oversized batch: slices of `chunk` items through this same entry point, one after the other on the caller's stream — the offsets are
-    // absolute into d_msgs, so a slice is the same arrays further in; statuses land at the items' own positions (profiling: the last slice's)
-    for (size_t lo = 0; lo < n; lo += chunk) {
-      const size_t len = n - lo < chunk ? n - lo : chunk;
-      const int rc_ = bn254_batch_verify_device(c, d_msgs, d_off + lo, d_sigs + 64 * lo, d_pks + 128 * lo, len, flags, d_status + lo, stream);
-      if (rc_) return rc_;
-    }
-    return 0;
-  }
+  if (const size_t chunk = ws_chunk_for(c, n, split ? 2 : 1, key_dedup))
+    return verify_device_sliced(n, chunk, [&](size_t lo, size_t len) {
+      return bn254_batch_verify_device(c, d_msgs, d_off + lo, d_sigs + 64 * lo, d_pks + 128 * lo, len, flags, d_status + lo, stream);
+    });
   int rc = ws_reserve(c, split ? 2 * n : n);
   if (rc) return rc;
   KeyDedup kd;
@@ -986,14 +982,10 @@ int bn254_batch_verify_compressed_device(bn254_ctx* c, const uint8_t* d_msgs, co
   if (n == 0) return 0;
   if ((uintptr_t)d_off & 7u) return BN254_E_MISALIGNED;
   HIP_TRY(hipSetDevice(c->device));
-  if (const size_t chunk = ws_chunk_for(c, n)) {       // an oversized batch in slices (see bn254_batch_verify_device)
-    for (size_t lo = 0; lo < n; lo += chunk) {
-      const size_t len = n - lo < chunk ? n - lo : chunk;
-      const int rc_ = bn254_batch_verify_compressed_device(c, d_msgs, d_off + lo, d_sigs33 + 33 * lo, d_pks65 + 65 * lo, len, d_status + lo, stream);
-      if (rc_) return rc_;
-    }
-    return 0;
-  }
+  if (const size_t chunk = ws_chunk_for(c, n))
+    return verify_device_sliced(n, chunk, [&](size_t lo, size_t len) {
+      return bn254_batch_verify_compressed_device(c, d_msgs, d_off + lo, d_sigs33 + 33 * lo, d_pks65 + 65 * lo, len, d_status + lo, stream);
+    });
   int rc = ws_reserve(c, n);
   if (rc) return rc;
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
@@ -1126,16 +1118,7 @@ static int verify_host_overlapped(bn254_ctx* c, const uint8_t* msgs, const uint6
   k_decode_g1<<<grid_for(n), BN_WAVE, 0, s>>>(c->stage[2], n, flags, c->ws, PL_P1X, BY_P1_INF, 0);
   if ((rc = launch_decode_g2(c, s, c->stage[3], n, flags, 1))) return rc;
   PROF_MARK(2);
-  if (c->pair_lanes) {
-    if ((rc = launch_pair_or_trio(c, s, n, 1, c->stage[4], 0, true))) return rc;
-  } else {
-    k_miller_verify<<<grid_for(n), BN_WAVE, 0, s>>>(n, c->ws, nullptr, nullptr);
-    PROF_MARK(3);
-    k_final_exp<<<grid_for(n), BN_WAVE, 0, s>>>(n, 1, 1, 1, c->ws, 1, nullptr, c->stage[4], 0, 0, nullptr, nullptr);
-  }
-  PROF_MARK(4);
-  if (c->profiling) { c->ev_valid = 1; c->ev_hash_first = 1; }   // intervals: transfer + hash, decode, Miller, final exp.
-  HIP_TRY(hipGetLastError());
+  if ((rc = verify_tail(c, s, n, c->stage[4], false, nullptr, 1))) return rc;   // intervals: transfer + hash, decode, Miller, final exp.
   return st.finish();
 }
 
@@ -1273,15 +1256,9 @@ int bn254_batch_check_public_keys(bn254_ctx* c, const uint8_t* pk_g2, const uint
   uint8_t* d_status = st.out(2, n, status);
   if (!st.ok()) return st.rc;
   hipStream_t s = c->stream;
-  unsigned g = grid_for(n);
   if ((rc = launch_decode_g2(c, s, d_g2, n, flags, 0))) return rc;       // ecdsa.rs:82: pk_g2 first
-  k_decode_g1<<<g, BN_WAVE, 0, s>>>(d_g1, n, flags, c->ws, PL_P1X, BY_P1_INF, 1);
-  if (c->pair_lanes) {
-    if ((rc = launch_pair_or_trio(c, s, n, 0, d_status, 1, false))) return rc;
-  } else {
-    k_miller_cpk<<<g, BN_WAVE, 0, s>>>(n, c->ws);
-    k_final_exp<<<g, BN_WAVE, 0, s>>>(n, 1, 1, 1, c->ws, 0, nullptr, d_status, 0, 0, nullptr, nullptr);
-  }
+  k_decode_g1<<<grid_for(n), BN_WAVE, 0, s>>>(d_g1, n, flags, c->ws, PL_P1X, BY_P1_INF, 1);
+  if ((rc = launch_verify_miller_fe(c, s, n, BN_PAIRS_CHECK_PKS, 0, d_status, false))) return rc;
   HIP_TRY(hipGetLastError());
   return st.finish();
 }

@@ -135,6 +135,14 @@ BN_HIDDEN int ws_reserve(bn254_ctx* c, size_t n);
 // ws_per_item: workspace entries per item (2 with BN254_OPT_SPLIT_MILLER); key_dedup: the call also reserves the key-dedup buffers (bn254_ws.h:
 // KD_BYTES_PER_ITEM per item + KD_BYTES_PER_KEY per key of BN254_OPT_KEY_DEDUP_MAX_KEYS)
 BN_HIDDEN size_t ws_chunk_for(bn254_ctx* c, size_t n, size_t ws_per_item = 1, bool key_dedup = false);
+// An oversized *_device verify: slice(lo, len) sends items [lo, lo + len) through the same entry point, one slice after the other on the
+// caller's stream — the offsets are absolute into d_msgs, so a slice is the same arrays further in; statuses land at the items' own positions
+// (profiling: the last slice's).  The host-pointer forms slice in bn254_hip.hip: verify_host_sliced.
+template <class Slice> static inline int verify_device_sliced(size_t n, size_t chunk, Slice slice) {
+  for (size_t lo = 0; lo < n; lo += chunk)
+    if (const int rc = slice(lo, n - lo < chunk ? n - lo : chunk)) return rc;
+  return 0;
+}
 BN_HIDDEN int stage_reserve(bn254_ctx* c, int slot, size_t bytes);
 BN_HIDDEN int pool_reserve(bn254_ctx* c, int which, size_t n_fp, size_t entries);
 BN_HIDDEN int pool_reserve_one(bn254_ctx* c, Pool* p, size_t n_fp, size_t entries);
@@ -198,8 +206,14 @@ BN_HIDDEN int launch_decode_g1(bn254_ctx* c, hipStream_t s, const uint8_t* d_pts
 BN_HIDDEN int launch_decode_g2(bn254_ctx* c, hipStream_t s, const uint8_t* d_pts, size_t n, uint32_t flags, int accumulate);
 BN_HIDDEN int launch_hash_rounds(bn254_ctx* c, hipStream_t s, const uint8_t* d_msgs, const uint64_t* d_off, size_t n, int px, int inf_plane,
                                  uint8_t* d_tries, int mark_finish = -1);
-BN_HIDDEN int launch_small_final_exp(bn254_ctx* c, hipStream_t s, size_t n, int use_hash, uint8_t* d_status);
-BN_HIDDEN int launch_pair_or_trio(bn254_ctx* c, hipStream_t s, size_t n, int use_hash, uint8_t* d_status, int mode, bool mark);
+// the final exponentiation of a verify-shaped batch in the layout `fe` (BnFeLayout) of its routing-table row
+BN_HIDDEN int launch_final_exp_layout(bn254_ctx* c, hipStream_t s, size_t n, int use_hash, uint8_t* d_status, int fe);
+// what the Miller loop of a verify-shaped batch computes (the `mode` of the Miller kernels): a verify's miller(H(m), pk) * miller(sig, -G2), or
+// check_public_keys' miller(G1::one(), pk_g2) * miller(pk_g1, -G2)
+enum BnVerifyPairs { BN_PAIRS_VERIFY = 0, BN_PAIRS_CHECK_PKS = 1 };
+// the Miller loop and final exponentiation of such a batch whose planes are filled, in the layouts BN254_OPT_PAIR_LANES, _TRIO_WAVE_ROLES and
+// the routing table choose; mark: profiling event 3 between the two
+BN_HIDDEN int launch_verify_miller_fe(bn254_ctx* c, hipStream_t s, size_t n, int pairs, int use_hash, uint8_t* d_status, bool mark);
 // one lane per item: k_miller_verify (map / count: a device-side queue of items, or null) and k_final_exp (the arguments of the kernel)
 // one lane per pairing: k_miller_var (f = miller(P1, Q) at every index below n), k_rand_tail (bn254_rand.hip: F_g * miller(S_g, -G2) at gbase + g)
 BN_HIDDEN int launch_miller_var_lane(bn254_ctx* c, hipStream_t s, size_t n);

@@ -371,14 +371,10 @@ int bn254_batch_verify_keyed_device(bn254_ctx* c, const uint8_t* d_msgs, const u
   if (n == 0) return 0;
   if (misaligned(d_sigs) || misaligned(d_key_idx) || ((uintptr_t)d_off & 7u)) return BN254_E_MISALIGNED;
   HIP_TRY(hipSetDevice(c->device));
-  if (const size_t chunk = ws_chunk_for(c, n)) {       // an oversized batch in slices (see bn254_batch_verify_device)
-    for (size_t lo = 0; lo < n; lo += chunk) {
-      const size_t len = n - lo < chunk ? n - lo : chunk;
-      const int rc_ = bn254_batch_verify_keyed_device(c, d_msgs, d_off + lo, d_sigs + 64 * lo, d_key_idx + lo, len, flags, d_status + lo, stream);
-      if (rc_) return rc_;
-    }
-    return 0;
-  }
+  if (const size_t chunk = ws_chunk_for(c, n))
+    return verify_device_sliced(n, chunk, [&](size_t lo, size_t len) {
+      return bn254_batch_verify_keyed_device(c, d_msgs, d_off + lo, d_sigs + 64 * lo, d_key_idx + lo, len, flags, d_status + lo, stream);
+    });
   int rc = ws_reserve(c, n);
   if (rc) return rc;
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
@@ -394,26 +390,22 @@ int bn254_batch_verify_keyed_device(bn254_ctx* c, const uint8_t* d_msgs, const u
   PROF_MARK(1);
   if ((rc = launch_hash_rounds(c, s, d_msgs, d_off, n, PL_P2X, BY_P2_INF, nullptr))) return rc;
   PROF_MARK(2);
-  if (route_for(c, n).miller != BN_ML_LANE_PAIRS) {
+  const BnRoute r = route_for(c, n);
+  if (r.miller == BN_ML_LANE_MACHINE) {
+    // the smallest batches: the lane machine's keyed form on the line tables themselves (no twist point to walk: 0.32 ms against 0.43)
+    if ((rc = bn254_lm_miller_verify_keyed(n, c->ws, d_key_idx, kt, s))) return rc;
+    PROF_MARK(3);
+    if ((rc = launch_final_exp_layout(c, s, n, 1, d_status, r.fe))) return rc;
+  } else if (r.miller != BN_ML_LANE_PAIRS) {
     // a batch that cannot fill the chip: latency counts — expand the keys and take the small-batch kernels (2.3 ms instead of the
     // 6 ms of the lane-pair layout; the line tables pay off only where throughput binds)
-    if (route_for(c, n).miller == BN_ML_LANE_MACHINE) {
-      // the smallest: the lane machine's keyed form on the line tables themselves (no twist point to walk: 0.32 ms against 0.43)
-      if ((rc = bn254_lm_miller_verify_keyed(n, c->ws, d_key_idx, kt, s))) return rc;
-      PROF_MARK(3);
-      if ((rc = launch_small_final_exp(c, s, n, 1, d_status))) return rc;
-    } else {
-      k_keyed_expand<<<grid_for(n), BN_WAVE, 0, s>>>(n, c->ws, d_key_idx, kt, c->key_xy);
-      if ((rc = launch_pair_or_trio(c, s, n, 1, d_status, 0, true))) return rc;
-    }
-    PROF_MARK(4);
-    if (c->profiling) { c->ev_valid = 1; c->ev_hash_first = 0; }
-    HIP_TRY(hipGetLastError());
-    return 0;
+    k_keyed_expand<<<grid_for(n), BN_WAVE, 0, s>>>(n, c->ws, d_key_idx, kt, c->key_xy);
+    if ((rc = launch_verify_miller_fe(c, s, n, BN_PAIRS_VERIFY, 1, d_status, true))) return rc;
+  } else {
+    if ((rc = bn254_pair_miller_verify_keyed(n, c->ws, d_key_idx, kt, s))) return rc;
+    PROF_MARK(3);
+    if ((rc = bn254_pair_final_exp(n, c->ws, 1, d_status, nullptr, nullptr, s))) return rc;
   }
-  if ((rc = bn254_pair_miller_verify_keyed(n, c->ws, d_key_idx, kt, s))) return rc;
-  PROF_MARK(3);
-  if ((rc = bn254_pair_final_exp(n, c->ws, 1, d_status, nullptr, nullptr, s))) return rc;
   PROF_MARK(4);
   if (c->profiling) { c->ev_valid = 1; c->ev_hash_first = 0; }
   HIP_TRY(hipGetLastError());

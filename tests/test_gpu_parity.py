@@ -459,19 +459,24 @@ def test_fused_and_split_miller_agree(eng, derived):
         eng.set_option(OPT_SPLIT_MILLER, 0)
 
 
-def test_pair_lanes_and_single_lane_agree(eng, derived):
-    """verify on lane pairs (default, bn254_pair.hip) and on one lane per verify give the same statuses"""
+def test_pair_lanes_and_single_lane_agree(eng, c, derived, kats):
+    """verify and check_public_keys on lane pairs (default, bn254_pair.hip) and on one lane per item give the same statuses"""
     from bn254_amd.engine import OPT_PAIR_LANES
     from tests.datagen import make_verify_batch
     cs = derived["verify_cases"]
     args = ([H(v["message_hex"]) for v in cs], b"".join(H(v["sig"]) for v in cs), b"".join(H(v["pk"]) for v in cs))
     want = [v["status"] for v in cs]
     big = make_verify_batch(eng, 2048 + 33)
+    cpk = kats["check_public_keys"]
+    g2s = b"".join(c.public_key_g2(H(v["sk_g2"])) for v in cpk)
+    g1s = b"".join(c.public_key_g1(H(v["sk_g1"])) for v in cpk)
+    cpk_want = bytes(v["status"] for v in cpk)
     for mode in (1, 0):
         eng.set_option(OPT_PAIR_LANES, mode)
         try:
             assert list(eng.batch_verify(*args, flags=1)) == want, mode
             assert eng.batch_verify(big[0], big[1], big[2]) == big[3], mode
+            assert eng.batch_check_public_keys(g2s, g1s, len(cpk)) == cpk_want, mode
         finally:
             eng.set_option(OPT_PAIR_LANES, 1)
 

@@ -353,6 +353,34 @@ class ECDSA:
         else the Error it would raise.  A length mismatch in any item raises Error(InvalidLength) before any device work."""
         return [None if s == 0 else Error(s) for s in ECDSA._distinct_status(aggregates, engine)]
 
+    @staticmethod
+    def aggregate_verify_keyed(messages, signature, key_indices, engine=None):
+        """aggregate_verify with public_keys[j] named by its index in the registered set (ECDSA.register_keys): Error(IndexOutOfBounds)
+        for an index outside the set, a refused key's registration Error, else what aggregate_verify raises
+        (include/bn254_hip.h: bn254_batch_aggregate_verify_distinct_keyed)."""
+        if len(messages) != len(key_indices):
+            raise Error(ErrorKind.InvalidLength)
+        _raise(ECDSA._distinct_keyed_status([(messages, signature, key_indices)], engine)[0])
+
+    @staticmethod
+    def _distinct_keyed_status(aggregates, engine):
+        msgs, idx, sigs, sizes = [], [], [], []
+        for messages, signature, key_indices in aggregates:
+            if len(messages) != len(key_indices):
+                raise Error(ErrorKind.InvalidLength)
+            msgs.extend(bytes(m) for m in messages)
+            idx.extend(int(k) for k in key_indices)
+            sigs.append(signature.raw)
+            sizes.append(len(messages))
+        eng = engine or _eng()
+        return eng.batch_aggregate_verify_distinct_keyed(msgs, idx, b"".join(sigs), sizes)
+
+    @staticmethod
+    def batch_aggregate_verify_distinct_keyed(aggregates, engine=None):
+        """aggregates: a list of (messages, signature, key_indices); result[i] is None iff ECDSA.aggregate_verify_keyed on item i succeeds,
+        else the Error it would raise.  A length mismatch in any item raises Error(InvalidLength) before any device work."""
+        return [None if s == 0 else Error(s) for s in ECDSA._distinct_keyed_status(aggregates, engine)]
+
 
 def check_public_keys(public_key_g2, public_key_g1):
     """/root/reference/src/ecdsa.rs:78-93."""

@@ -15,6 +15,9 @@
 //      (lane machine for the smallest m, lane pairs, or one lane with pair_lanes off) followed by the level kernel over the pairs;
 //   5. k_aggd_status, then per aggregate F_i * miller(sigma_i, -G2) (the randomised verify's tail) and the final exponentiation of a verify
 //      batch of n items, whose == one test gives 0 / 9 under the folded status.
+// Against registered keys (bn254_batch_aggregate_verify_distinct_keyed[_device]): step 2 writes each pair's key status instead of decoding
+// (k_aggd_keyed_keys), level 0 is the slot kernel of bn254_aggkeyed.hip over ALL k_i + 1 pairs of an aggregate, sigma's included (slots
+// from a second count and scan: k_aggd_keyed_count / _map), and step 5 has no tail: the products move from gbase + i to i.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -139,6 +142,46 @@ KERNEL_SMALL void k_aggd_status(size_t n, Ws ws, size_t gbase, const uint32_t* f
   ws_byte(ws, BY_ST_DECODE, gbase + i) = st;
 }
 
+// ---- registered keys (bn254_batch_aggregate_verify_distinct_keyed) -----------------------------------------------------------------------
+// pair j's key status in place of its decode status: 2 for an index >= n_keys, else what registration found (subgroup check included; the
+// REJECT_IDENTITY of the registration).  expand = 1: the key itself into the Q planes at j (the generator for a refused key: its status is
+// set, the arithmetic walks on), after which the pairs are those of the unkeyed call.  Never reads a table when nothing is registered.
+KERNEL_SMALL void k_aggd_keyed_keys(size_t m, const uint32_t* key_idx, KeyTable kt, const int32_t* key_xy, Ws ws, int expand) {
+  const size_t j = (size_t)blockIdx.x * BN_WAVE + threadIdx.x;
+  if (j >= m) return;
+  const uint32_t key = key_idx[j];
+  const bool in = key < kt.n_keys;
+  const uint8_t kst = in ? kt.st[key] : (uint8_t)ST_INDEX_OOB;
+  ws_byte(ws, BY_ST_DECODE, j) = kst;
+  if (!expand) return;
+  G2Affine q;
+  if (kst == ST_OK) {
+    const int32_t* w = key_xy + (size_t)key * 4 * BN_LIMBS;
+    q.x.c0 = fp_load_const(w); q.x.c1 = fp_load_const(w + BN_LIMBS); q.y.c0 = fp_load_const(w + 2 * BN_LIMBS); q.y.c1 = fp_load_const(w + 3 * BN_LIMBS);
+    q.inf = kt.inf[key] != 0;
+  } else {
+    g2_set_generator(q);
+  }
+  ws_store_g2(ws, j, q);
+}
+// slots of the slot kernel per aggregate: its k + 1 table pairs (sigma's included), `width` per slot
+KERNEL_SMALL void k_aggd_keyed_count(size_t n, const uint64_t* lo, const uint64_t* hi, uint64_t width, uint64_t* cnt) {
+  const size_t i = (size_t)blockIdx.x * BN_WAVE + threadIdx.x;
+  if (i >= n) return;
+  cnt[i] = (hi[i] - lo[i] + width) / width;
+}
+// slot e -> its aggregate: the first i whose inclusive slot count exceeds e (AGGD_SEG_NONE past the last slot)
+KERNEL_SMALL void k_aggd_keyed_map(size_t n_slots, size_t n, const uint64_t* incl, uint32_t* slot_agg) {
+  const size_t e = (size_t)blockIdx.x * BN_WAVE + threadIdx.x;
+  if (e >= n_slots) return;
+  size_t a = 0, b = n;
+  while (a < b) {
+    const size_t mid = (a + b) >> 1;
+    if (incl[mid] > e) b = mid; else a = mid + 1;
+  }
+  slot_agg[e] = a < n ? (uint32_t)a : AGGD_SEG_NONE;
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------------------------------
 static inline size_t round256(size_t x) { return (x + 255) & ~(size_t)255; }
 // entries of the partial array all levels need: a level of e elements runs ceil(e / 128) workgroups and, unless that is one, leaves two each
@@ -161,46 +204,69 @@ static int aggd_reserve(bn254_ctx* c, size_t bytes) {
   return 0;
 }
 
-static int aggd_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t* d_msg_off, const uint8_t* d_pks, size_t m, const uint8_t* d_sigs,
-                       const uint64_t* d_agg_off, size_t n, uint32_t flags, uint8_t* d_status, hipStream_t s) {
+// keyed: bn254_batch_aggregate_verify_distinct_keyed — pk_j = the registered key d_key_idx[j], d_pks unused
+static int aggd_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t* d_msg_off, const uint8_t* d_pks, bool keyed, const uint32_t* d_key_idx, size_t m,
+                       const uint8_t* d_sigs, const uint64_t* d_agg_off, size_t n, uint32_t flags, uint8_t* d_status, hipStream_t s) {
   const uint32_t dflags = flags & (BN254_FLAG_G2_SUBGROUP_CHECK | BN254_FLAG_REJECT_IDENTITY);
   // routes: small m -> one pairing per lane-machine verify (latency); pair_lanes off -> one pairing per lane; m below AGGD_TWO_PER_PAIR_MIN_M ->
   // one pair per lane pair (fills the chip); else two pairs of an aggregate per lane pair, the first product fused into the Miller kernel
   const bool lane_machine = c->pair_lanes && route_lane_machine_helpers(c, m);
-  const bool per_pair = lane_machine || !c->pair_lanes || m < AGGD_TWO_PER_PAIR_MIN_M;
+  // keyed: the slot kernel on the registered tables (sigma's pair in a slot like any other: no tail) at every size — it beats the expanded
+  // keys on the lane machine too, whose sigma tail is a whole Miller loop.  One table pair per lane pair while those fit
+  // one pass of two waves per SIMD, else two.  pair_lanes off and an empty key set expand the keys into the Q planes and run the unkeyed
+  // route from the map on.
+  const bool have_keys = c->n_keys > 0 && c->key_lines;
+  const int kr = c->aggd_keyed_route;
+  const bool slots = keyed && m && c->pair_lanes && have_keys && kr != 3;
+  const int width = !slots ? 0 : kr ? kr : m + n <= AGGD_KEYED_W1_MAX_SLOTS ? 1 : 2;
+  const bool per_pair = !slots && (lane_machine || !c->pair_lanes || m < AGGD_TWO_PER_PAIR_MIN_M);
   const size_t n_slots = (m + n + 1) / 2;             // sum of ceil(k_i / 2) over disjoint ranges
-  const size_t e0 = per_pair ? m : n_slots;
+  const size_t n_kslots = width == 1 ? m + n : m / 2 + n;   // sum of ceil((k_i + 1) / width)
+  const size_t e0 = slots ? n_kslots : per_pair ? m : n_slots;
   const size_t n_part = m ? aggd_partials(e0) : 0;
   const size_t pbase = round256(m), gbase = round256(pbase + n_part > n ? pbase + n_part : n);
   int rc = ws_reserve(c, gbase + n);
   if (rc) return rc;
   const size_t nb = (n + AGGD_SCAN_WG - 1) / AGGD_SCAN_WG;
-  const size_t n_seg0 = per_pair ? m : n_slots;
-  const size_t u64_words = 4 * n + nb, u32_words = 2 * n + n_seg0 + n_part;
+  const size_t n_seg0 = e0;
+  const size_t u64_words = (slots ? 5 : 4) * n + nb, u32_words = 2 * n + n_seg0 + n_part;
   if ((rc = aggd_reserve(c, 8 * u64_words + 4 * u32_words))) return rc;
   uint64_t* mx = (uint64_t*)c->aggd_buf;
   uint64_t* incl = mx + n;
   uint64_t* lo = incl + n;
   uint64_t* hi = lo + n;
   uint64_t* tot = hi + n;
-  uint32_t* first_pk = (uint32_t*)(tot + nb);
+  uint64_t* kincl = tot + nb;                                            // keyed slots: the inclusive scan of the slot counts
+  uint32_t* first_pk = (uint32_t*)(kincl + (slots ? n : 0));
   uint32_t* first_hash = first_pk + n;
   uint32_t* seg0 = first_hash + n;
   uint32_t* pseg = seg0 + n_seg0;
+  const KeyTable kt = {c->key_lines, c->key_st, c->key_inf, (uint32_t)(have_keys ? c->n_keys : 0)};
   CallDone call_done(c, s);
   PROF_MARK(0);
   if ((rc = launch_decode_g1(c, s, d_sigs, n, dflags, PL_P2X, BY_P2_INF, 0))) return rc;
   if ((rc = aggd_scan<AggdMax>(s, d_agg_off, n, mx, tot))) return rc;
   k_aggd_prep<<<grid_for(n), BN_WAVE, 0, s>>>(n, (uint64_t)m, d_agg_off, mx, incl, lo, hi, first_pk, first_hash, c->ws, gbase);
   if ((rc = aggd_scan<AggdAdd>(s, incl, n, incl, tot))) return rc;
+  if (slots) {
+    k_aggd_keyed_count<<<grid_for(n), BN_WAVE, 0, s>>>(n, lo, hi, (uint64_t)width, kincl);
+    if ((rc = aggd_scan<AggdAdd>(s, kincl, n, kincl, tot))) return rc;
+  }
   if (m) {
-    if ((rc = launch_decode_g2(c, s, d_pks, m, dflags, 0))) return rc;
+    if (keyed) {
+      k_aggd_keyed_keys<<<grid_for(m), BN_WAVE, 0, s>>>(m, d_key_idx, kt, c->key_xy, c->ws, slots ? 0 : 1);
+      HIP_TRY(hipGetLastError());
+    } else if ((rc = launch_decode_g2(c, s, d_pks, m, dflags, 0))) {
+      return rc;
+    }
     PROF_MARK(1);
     if ((rc = launch_hash_rounds(c, s, d_msgs, d_msg_off, m, PL_P1X, BY_P1_INF, nullptr))) return rc;
     PROF_MARK(2);
     if (per_pair) HIP_TRY(hipMemsetAsync(seg0, 0xFF, 4 * m, s));          // pairs outside every accepted range belong to nobody
-    k_aggd_map<<<grid_for(n_slots), BN_WAVE, 0, s>>>(n_slots, n, incl, lo, hi, per_pair ? nullptr : seg0, per_pair ? seg0 : nullptr, first_pk,
-                                                       first_hash, c->ws);
+    const bool two = !per_pair && !slots;                                  // the unkeyed segmented two-pair Miller kernel
+    k_aggd_map<<<grid_for(n_slots), BN_WAVE, 0, s>>>(n_slots, n, incl, lo, hi, two ? seg0 : nullptr, per_pair ? seg0 : nullptr, first_pk, first_hash,
+                                                       c->ws);
+    if (slots) k_aggd_keyed_map<<<grid_for(n_kslots), BN_WAVE, 0, s>>>(n_kslots, n, kincl, seg0);
     // level 0 (Miller loops, and on lane pairs the first product), then the levels over the partials until one workgroup holds them all
     size_t e = e0, ebase = 0, off = 0;
     const uint32_t* seg = seg0;
@@ -208,7 +274,11 @@ static int aggd_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t* d_ms
     for (;;) {
       const size_t g = (e + AGGD_WG_ELEMS - 1) / AGGD_WG_ELEMS;
       const int last = g <= 1;
-      if (level0 && !per_pair) {
+      if (level0 && slots) {
+        const AggdSlots sl = {seg0, kincl, lo, hi};
+        if ((rc = bn254_pair_aggd_keyed(e, width, c->ws, sl, d_key_idx, kt, gbase, pbase + off, pseg + off, last, s))) return rc;
+        PROF_MARK(3);
+      } else if (level0 && !per_pair) {
         const AggdSlots sl = {seg0, incl, lo, hi};
         if ((rc = bn254_pair_aggd_miller(e, c->ws, sl, gbase, pbase + off, pseg + off, last, s))) return rc;
         PROF_MARK(3);
@@ -235,7 +305,11 @@ static int aggd_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t* d_ms
     PROF_MARK(3);
   }
   k_aggd_status<<<grid_for(n), BN_WAVE, 0, s>>>(n, c->ws, gbase, first_pk, first_hash);
-  if (c->pair_lanes) {
+  if (slots) {
+    // sigma's pair is already in every product: move F and the status to index i, then the final exponentiation a verify of n items runs
+    if ((rc = bn254_pair_aggd_move(n, c->ws, gbase, s))) return rc;
+    if ((rc = launch_final_exp_layout(c, s, n, 0, d_status, route_for(c, n).fe))) return rc;
+  } else if (c->pair_lanes) {
     // tail into index i (obase 0: everything below gbase is consumed by now), then the final exponentiation a verify of n items runs
     if ((rc = bn254_pair_aggd_tail(n, c->ws, gbase, 0, s))) return rc;
     if ((rc = launch_final_exp_layout(c, s, n, 0, d_status, route_for(c, n).fe))) return rc;
@@ -260,7 +334,7 @@ int bn254_batch_aggregate_verify_distinct_device(bn254_ctx* c, const uint8_t* d_
   if (n == 0) return 0;
   if (misaligned(d_agg_sigs) || misaligned(d_pks) || ((uintptr_t)d_msg_off & 7u) || ((uintptr_t)d_agg_off & 7u)) return BN254_E_MISALIGNED;
   HIP_TRY(hipSetDevice(c->device));
-  return aggd_device(c, d_msgs, d_msg_off, d_pks, m, d_agg_sigs, d_agg_off, n, flags, d_status, stream ? (hipStream_t)stream : c->stream);
+  return aggd_device(c, d_msgs, d_msg_off, d_pks, false, nullptr, m, d_agg_sigs, d_agg_off, n, flags, d_status, stream ? (hipStream_t)stream : c->stream);
 }
 
 int bn254_batch_aggregate_verify_distinct(bn254_ctx* c, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* pks, size_t m, const uint8_t* agg_sigs,
@@ -279,6 +353,39 @@ int bn254_batch_aggregate_verify_distinct(bn254_ctx* c, const uint8_t* msgs, con
   if (st.ok())
     st.rc = bn254_batch_aggregate_verify_distinct_device(c, d_msgs, (const uint64_t*)d_msg_off, d_pks, m, d_agg_sigs, (const uint64_t*)d_agg_off, n, flags,
                                                          d_status, nullptr);
+  return st.finish();
+}
+
+// ---- registered keys: pk_j = registered[key_idx[j]] (include/bn254_hip.h) -------------------------------------------------------------------
+int bn254_batch_aggregate_verify_distinct_keyed_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t* d_msg_off, const uint32_t* d_key_idx, size_t m,
+                                                       const uint8_t* d_agg_sigs, const uint64_t* d_agg_off, size_t n, uint32_t flags, uint8_t* d_status,
+                                                       void* stream) {
+  MsgsLenScope msgs_len_scope(c);
+  if (!c || !d_agg_off || (n && (!d_agg_sigs || !d_status)) || (m && (!d_msgs || !d_msg_off || !d_key_idx))) return BN254_E_BAD_ARGUMENT;
+  if (m > 0xFFFFFFFFu || n > 0xFFFFFFFFu) return BN254_E_BAD_ARGUMENT;
+  if (n == 0) return 0;
+  if (misaligned(d_agg_sigs) || misaligned(d_key_idx) || ((uintptr_t)d_msg_off & 7u) || ((uintptr_t)d_agg_off & 7u)) return BN254_E_MISALIGNED;
+  HIP_TRY(hipSetDevice(c->device));
+  return aggd_device(c, d_msgs, d_msg_off, nullptr, true, d_key_idx, m, d_agg_sigs, d_agg_off, n, flags, d_status, stream ? (hipStream_t)stream : c->stream);
+}
+
+int bn254_batch_aggregate_verify_distinct_keyed(bn254_ctx* c, const uint8_t* msgs, const uint64_t* msg_off, const uint32_t* key_idx, size_t m,
+                                                const uint8_t* agg_sigs, const uint64_t* agg_off, size_t n, uint32_t flags, uint8_t* status) {
+  MsgsLenScope msgs_len_scope(c);
+  if (!c || !msg_off || !agg_off || (n && (!agg_sigs || !status)) || (m && !key_idx)) return BN254_E_BAD_ARGUMENT;
+  if (m > 0xFFFFFFFFu || n > 0xFFFFFFFFu) return BN254_E_BAD_ARGUMENT;
+  if (agg_off[0] != 0 || agg_off[n] != m || !offsets_ok(agg_off, n) || !offsets_ok(msg_off, m)) return BN254_E_BAD_ARGUMENT;
+  if (n == 0) return 0;
+  HIP_TRY(hipSetDevice(c->device));
+  if (!msgs_ok(msgs, msg_off, m)) return BN254_E_BAD_ARGUMENT;
+  HostStaging st(c);
+  const uint8_t *d_msgs = st.in(0, msgs, (size_t)msg_off[m]), *d_msg_off = st.in(1, msg_off, (m + 1) * sizeof(uint64_t));
+  const uint8_t *d_key_idx = st.in(2, key_idx, m * sizeof(uint32_t)), *d_agg_sigs = st.in(3, agg_sigs, n * 64);
+  const uint8_t* d_agg_off = st.in(4, agg_off, (n + 1) * sizeof(uint64_t));
+  uint8_t* d_status = st.out(5, n, status);
+  if (st.ok())
+    st.rc = bn254_batch_aggregate_verify_distinct_keyed_device(c, d_msgs, (const uint64_t*)d_msg_off, (const uint32_t*)d_key_idx, m, d_agg_sigs,
+                                                               (const uint64_t*)d_agg_off, n, flags, d_status, nullptr);
   return st.finish();
 }
 

@@ -819,6 +819,7 @@ int bn254_ctx_set_option(bn254_ctx* c, int option, int value) {
   if (option == BN254_OPT_KEY_DEDUP_MIN_MULT) { if (value < 1) return BN254_E_BAD_ARGUMENT; c->kd_min_mult = value; return 0; }
   if (option == BN254_OPT_KEY_DEDUP_FORCE_GENERIC) { c->kd_force_generic = value != 0; return 0; }
   if (option == BN254_OPT_KEY_DEDUP_HASH_BITS) { if (value < 0 || value > 32) return BN254_E_BAD_ARGUMENT; c->kd_hash_bits = value; return 0; }
+  if (option == BN254_OPT_AGGD_KEYED_ROUTE) { if (value < 0 || value > 3) return BN254_E_BAD_ARGUMENT; c->aggd_keyed_route = value; return 0; }
   return BN254_E_BAD_ARGUMENT;
 }
 // clock probe (BN254_OPT_CLOCK_PROBE): the clock the chip ran the last Miller kernel [0], final exponentiation [1] and issue probe [2]

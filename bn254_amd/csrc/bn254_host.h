@@ -81,6 +81,7 @@ struct bn254_ctx {
   size_t kd_items_cap, kd_keys_cap;
   uint32_t* kd_ctl;          // the device-side decision of the last call that ran the dedup (bn254_debug_key_dedup_last)
   int kd_last_run;           // ... and whether the last bn254_batch_verify_device ran it at all
+  int aggd_keyed_route;      // BN254_OPT_AGGD_KEYED_ROUTE (test and measurement knob): 0 by size, 1 / 2 the slot kernel of that width, 3 expanded keys
 };
 
 struct ScopedEvents {

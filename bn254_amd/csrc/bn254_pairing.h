@@ -248,6 +248,70 @@ BN_DEVM void miller_loop_keyed(Fp12& f, const G1Affine& pa, bool key_inf, const 
   step();
   step();
 }
+// mul_by_two_table_lines with lineB = (lb.c0, lb.c1, 1) from a per-lane table instead of the constant one.  A copy rather than a shared
+// body: sharing it moved the register allocation of the keyed verify kernel.  The operands are canonical in both, so the carry sites
+// are the same ones (280 .. 285).
+BN_DEV void mul_by_two_key_lines(Fp12& f, const KeyLine& la, const Fp& pax, const Fp& pay, bool skip_a, const KeyLine& lb, const Fp& pbx, const Fp& pby,
+                                 bool skip_b, bool any_skip) {
+  const Fp2 l0 = fp2_mul_fp(la.c0, pay), l1 = fp2_mul_fp(la.c1, pax);
+  const Fp2 m0 = fp2_mul_fp(lb.c0, pby), m1 = fp2_mul_fp(lb.c1, pbx);
+  const Fp2 v0 = fp2_mul(l0, m0), v1 = fp2_mul(l1, m1);
+  const Fp2 x01 = fp2_sub(fp2_sub(fp2_mul(NS(280, fp2_add(l0, l1)), NS(281, fp2_add(m0, m1))), v0), v1);
+  Fp6 b0;
+  b0.c0 = NS(282, fp2_add(v0, fp2_load_const(C_XI_MONT))); b0.c1 = v1; b0.c2 = NS(283, fp2_add(l1, m1));
+  Fp2 b10 = NS(284, x01), b11 = NS(285, fp2_add(l0, m0));
+  if (any_skip) {
+    const Fp2 one = fp2_one(), zero = fp2_zero();
+    const bool both = skip_a && skip_b, only_a = skip_a && !skip_b, only_b = skip_b && !skip_a;
+    b0.c0 = fp2_select(both, one, fp2_select(only_a, m0, fp2_select(only_b, l0, b0.c0)));
+    b0.c1 = fp2_select(skip_a || skip_b, zero, b0.c1);
+    b0.c2 = fp2_select(skip_a || skip_b, zero, b0.c2);
+    b10 = fp2_select(both, zero, fp2_select(only_a, m1, fp2_select(only_b, l1, b10)));
+    b11 = fp2_select(both, zero, fp2_select(skip_a || skip_b, one, b11));
+  }
+  fp12_mul_line2(f, f, b0, b10, b11);
+}
+// f = miller(pa, table A) * miller(pb, table B) with BOTH line sequences read through per-lane pointers (aggregates over distinct messages
+// against registered keys: any two of an aggregate's table pairs (H(m_j), pk_j) and (sigma, -G2) share a slot).  W = 1: pair A alone,
+// one sparse line product per step (pb / skip_b / tabb unused).  skip_a / skip_b: the pair contributes one (an identity point, a refused
+// or identity key, a padding pair); its table must still be readable.
+template <int W, bool F_LDS = false>
+BN_DEVM void miller_loop_tables(Fp12& f, const G1Affine& pa, bool skip_a, const int32_t (*taba)[2][2][BN_LIMBS], const G1Affine& pb, bool skip_b,
+                                const int32_t (*tabb)[2][2][BN_LIMBS]) {
+  static_assert(W == 1 || W == 2, "one or two table pairs per lane pair");
+  if constexpr (F_LDS) BN_ASSUME_LDS(&f);
+  fp12_set_one(f);
+#if defined(__HIPCC__)
+  const bool any_skip = __builtin_amdgcn_ballot_w64(skip_a || (W == 2 && skip_b)) != 0;   // wave-uniform
+#else
+  const bool any_skip = skip_a || (W == 2 && skip_b);
+#endif
+  int idx = 0;
+  auto step = [&]() {
+    if constexpr (W == 2) {
+      KeyLine la, lb;
+      la.c0 = fp2_load_const(taba[idx][0]); la.c1 = fp2_load_const(taba[idx][1]);
+      lb.c0 = fp2_load_const(tabb[idx][0]); lb.c1 = fp2_load_const(tabb[idx][1]);
+      mul_by_two_key_lines(f, la, pa.x, pa.y, skip_a, lb, pb.x, pb.y, skip_b, any_skip);
+    } else {
+      LineCoef l;
+      l.c0 = fp2_load_const(taba[idx][0]); l.c1 = fp2_load_const(taba[idx][1]); l.c2 = fp2_one();
+      mul_by_line(f, l, pa.x, pa.y, skip_a);
+    }
+    ++idx;
+  };
+  for (int d = 0; d < 64; ++d) {
+    BN_SET_STEP_PRIORITY(d);
+    fp12_sqr(f, f);
+    step();
+    if (C_ATE_NAF[d] != 0) step();      // wave-uniform
+  }
+  step();
+  step();
+}
+// the -G2 table in the key-table format: word w of line idx of [line][c0 / c1][re / im][limb] is C_NEG_G2_LINES[idx][0 / 1] (c2 = 1 is
+// implied in both).  Registration appends these 87 lines behind the registered keys (bn254_rand.hip: k_neg_g2_key_lines).
+BN_DEV int32_t neg_g2_key_line_word(int idx, int w) { return C_NEG_G2_LINES[idx][w / (2 * BN_LIMBS)][(w / BN_LIMBS) & 1][w % BN_LIMBS]; }
 
 #if defined(BN_TRIO_FORMULAS)
 // ---- ECDSA::verify's Miller loop in ROUNDS (octet layout, bn254_trio.hip) ------------------------------------------

@@ -332,6 +332,13 @@ KERNEL_SMALL void k_krand_collect(size_t n_slots_max, const uint32_t* perm, cons
   else ws.h_list[atomicAdd(&ws.h_cnt[0], 1u)] = item;
 }
 
+// registration, after the keys: -G2's 87 lines in the key-table format as the hidden entry n_keys behind them, for the aggregates over distinct
+// messages against registered keys (bn254_aggkeyed.hip), where sigma's pair reads its lines like any key's
+KERNEL_SMALL void k_neg_g2_key_lines(int32_t* out) {
+  const unsigned w = threadIdx.x;
+  if (w >= BN_KEY_LINE_WORDS) return;
+  for (int idx = 0; idx < BN_N_FIXED_LINES; ++idx) out[(size_t)idx * BN_KEY_LINE_WORDS + w] = neg_g2_key_line_word(idx, (int)w);
+}
 
 extern "C" {
 
@@ -348,7 +355,7 @@ int bn254_ctx_register_keys(bn254_ctx* c, const uint8_t* pks, size_t n_keys, uin
     if (c->key_st) { HIP_TRY(hipFree(c->key_st)); c->key_st = nullptr; }
     if (c->key_inf) { HIP_TRY(hipFree(c->key_inf)); c->key_inf = nullptr; }
     c->key_cap = 0;
-    HIP_TRY(hipMalloc((void**)&c->key_lines, n_keys * (size_t)BN_N_FIXED_LINES * BN_KEY_LINE_WORDS * sizeof(int32_t)));
+    HIP_TRY(hipMalloc((void**)&c->key_lines, (n_keys + 1) * (size_t)BN_N_FIXED_LINES * BN_KEY_LINE_WORDS * sizeof(int32_t)));   // + -G2's lines
     HIP_TRY(hipMalloc((void**)&c->key_xy, n_keys * 4 * BN_LIMBS * sizeof(int32_t)));
     HIP_TRY(hipMalloc((void**)&c->key_st, n_keys));
     HIP_TRY(hipMalloc((void**)&c->key_inf, n_keys));
@@ -359,6 +366,7 @@ int bn254_ctx_register_keys(bn254_ctx* c, const uint8_t* pks, size_t n_keys, uin
   st.copy_back(key_status, c->key_st, n_keys);
   if (!st.ok()) return st.rc;
   k_register_keys<<<grid_for(n_keys), BN_WAVE, 0, c->stream>>>(d_pks, n_keys, flags & FLAG_REJECT_IDENTITY, c->key_lines, c->key_st, c->key_inf, c->key_xy);
+  k_neg_g2_key_lines<<<1, BN_WAVE, 0, c->stream>>>(c->key_lines + n_keys * (size_t)BN_N_FIXED_LINES * BN_KEY_LINE_WORDS);
   HIP_TRY(hipGetLastError());
   if (const int rc = st.finish()) return rc;
   c->n_keys = n_keys;

@@ -212,6 +212,14 @@ struct KeyTable { const int32_t* lines; const uint8_t* st; const uint8_t* inf; u
 __attribute__((visibility("hidden"))) int bn254_lm_miller_verify_keyed(size_t n, Ws ws, const uint32_t* key_idx, KeyTable kt, hipStream_t s);   // bn254_lmiller.hip: the smallest batches
 __attribute__((visibility("hidden"))) int bn254_pair_miller_verify_keyed(size_t n, Ws ws, const uint32_t* key_idx, KeyTable kt, hipStream_t s, size_t base = 0,
                                                                          const uint32_t* map = nullptr, const uint32_t* count = nullptr);
+// aggregates over distinct messages against registered keys (bn254_aggdist.hip): level 0 over slots of `width` (1 or 2) table pairs whose
+// per-aggregate inclusive slot scan is sl.incl (ceil((hi - lo + 1) / width)); the registered table holds -G2's lines as entry kt.n_keys.
+// Then the aggregates' products from gbase + i to i for the final exponentiation.
+#define AGGD_KEYED_W1_MAX_SLOTS 65536             // one table pair per lane pair while that needs at most this many lane pairs (one pass at 2 waves
+                                                   // per SIMD: 16 384 x 4 takes 8.9 ms at width 1 against 6.9 at width 2, 1 024 x 4 3.2 against 3.8)
+__attribute__((visibility("hidden"))) int bn254_pair_aggd_keyed(size_t n_slots, int width, Ws ws, AggdSlots sl, const uint32_t* key_idx, KeyTable kt,
+                                                                size_t gbase, size_t pbase, uint32_t* pseg, int last, hipStream_t s);
+__attribute__((visibility("hidden"))) int bn254_pair_aggd_move(size_t n, Ws ws, size_t gbase, hipStream_t s);
 
 // key deduplication of the exact verify (bn254_keydedup.hip): per call, the distinct keys of the batch and their line tables in the
 // KeyTable format above, built on a stream of the context beside decode and hash; the route (tables or the generic loop) is decided on the device

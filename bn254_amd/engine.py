@@ -36,6 +36,7 @@ OPT_KEY_DEDUP_MAX_KEYS = 21  # ... for at most this many distinct keys (default 
 OPT_KEY_DEDUP_MIN_MULT = 22  # ... and at least this many items per key (default 16)
 OPT_KEY_DEDUP_FORCE_GENERIC = 23   # test hook: the device-side decision always takes the generic loop
 OPT_KEY_DEDUP_HASH_BITS = 24       # test seam: bits of the dedup hash kept (0 = all)
+OPT_AGGD_KEYED_ROUTE = 25          # keyed aggregates over distinct messages: 0 by size, 1 / 2 slot kernel width, 3 expanded keys
 
 
 class NativeError(RuntimeError):
@@ -299,6 +300,24 @@ class Engine:
                self._lib.bn254_batch_aggregate_verify_distinct(self._h, msgs, off, bytes(pks), m, bytes(agg_sigs), a_off, n, flags, status))
         return status.raw[:n]
 
+    def batch_aggregate_verify_distinct_keyed(self, messages, key_idx, agg_sigs, agg_sizes, flags=0):
+        """batch_aggregate_verify_distinct against the registered keys: pk_j = registered[key_idx[j]]
+        (include/bn254_hip.h: bn254_batch_aggregate_verify_distinct_keyed).  Returns n status bytes."""
+        m, n = len(messages), len(agg_sizes)
+        assert len(key_idx) == m and len(agg_sigs) == n * G1_BYTES and sum(agg_sizes) == m
+        msgs, off = pack_messages(messages)
+        idx = (ctypes.c_uint32 * max(m, 1))(*key_idx)
+        a_off = (ctypes.c_uint64 * (n + 1))()
+        pos = 0
+        for i, k in enumerate(agg_sizes):
+            a_off[i] = pos
+            pos += int(k)
+        a_off[n] = pos
+        status = ctypes.create_string_buffer(max(n, 1))
+        _check("bn254_batch_aggregate_verify_distinct_keyed",
+               self._lib.bn254_batch_aggregate_verify_distinct_keyed(self._h, msgs, off, idx, m, bytes(agg_sigs), a_off, n, flags, status))
+        return status.raw[:n]
+
     def register_pools(self, messages, pk_pool, sig_pool, expect_tuples, flags=0):
         """the pools of an aggregate verify decoded, hashed and tabulated ONCE (bn254_ctx_register_pools): for a fixed validator set / message
         set whose tuples keep arriving; `expect_tuples` = the batch size the subset-sum tables are chosen for"""
@@ -441,6 +460,11 @@ class Engine:
         _check("bn254_batch_aggregate_verify_distinct_device",
                self._lib.bn254_batch_aggregate_verify_distinct_device(self._h, d_msgs, d_msg_off, d_pks, m, d_agg_sigs, d_agg_off, n, flags, d_status,
                                                                       stream))
+
+    def batch_aggregate_verify_distinct_keyed_device(self, d_msgs, d_msg_off, d_key_idx, m, d_agg_sigs, d_agg_off, n, d_status, flags=0, stream=None):
+        _check("bn254_batch_aggregate_verify_distinct_keyed_device",
+               self._lib.bn254_batch_aggregate_verify_distinct_keyed_device(self._h, d_msgs, d_msg_off, d_key_idx, m, d_agg_sigs, d_agg_off, n, flags,
+                                                                            d_status, stream))
 
     def batch_sign_device(self, d_msgs, d_off, d_sks, n, d_sigs, d_status, stream=None):
         _check("bn254_batch_sign_device", self._lib.bn254_batch_sign_device(self._h, d_msgs, d_off, d_sks, n, d_sigs, d_status, stream))

@@ -3,6 +3,7 @@
 //
 //   bn254::ECDSA::sign / verify / batch_verify      /root/reference/src/ecdsa.rs:26-35, :49-64 (+ new batch entry)
 //   bn254::ECDSA::aggregate_verify / batch_aggregate_verify_distinct   (new: aggregates over distinct messages)
+//   bn254::ECDSA::aggregate_verify_keyed / batch_aggregate_verify_distinct_keyed   (... against registered keys)
 //   bn254::check_public_keys                        /root/reference/src/ecdsa.rs:78-93
 //   bn254::PrivateKey / PublicKey / PublicKeyG1 / Signature   /root/reference/src/types.rs:13,81,151,222
 //   bn254::Error                                    /root/reference/src/error.rs:6-29
@@ -243,6 +244,35 @@ struct ECDSA {
     }
     off[n] = msgs.size();
     check_rc("bn254_batch_verify_keyed", bn254_batch_verify_keyed(e.raw(), msgs.data(), off.data(), sigs.data(), key_indices.data(), n, 0, status.data()));
+    return status;
+  }
+  // aggregate_verify against the registered set: key_indices[j] names the key of messages[j]; 2 (IndexOutOfBounds) outside the set
+  // (include/bn254_hip.h: bn254_batch_aggregate_verify_distinct_keyed)
+  struct KeyedAggregate { std::vector<std::vector<uint8_t>> messages; Signature signature; std::vector<uint32_t> key_indices; };
+  static void aggregate_verify_keyed(const std::vector<std::vector<uint8_t>>& messages, const Signature& signature, const std::vector<uint32_t>& key_indices,
+                                     Engine& e = Engine::default_engine()) {
+    check_status(batch_aggregate_verify_distinct_keyed({KeyedAggregate{messages, signature, key_indices}}, e)[0]);
+  }
+  // result[i] == 0 iff aggregate_verify_keyed on aggregates[i] succeeds, else the ErrorKind it would throw
+  static std::vector<uint8_t> batch_aggregate_verify_distinct_keyed(const std::vector<KeyedAggregate>& aggregates, Engine& e = Engine::default_engine()) {
+    const size_t n = aggregates.size();
+    std::vector<uint64_t> msg_off(1, 0), agg_off(1, 0);
+    std::vector<uint32_t> idx;
+    std::vector<uint8_t> msgs, sigs(n * 64), status(n, 0);
+    for (size_t i = 0; i < n; ++i) {
+      const KeyedAggregate& a = aggregates[i];
+      if (a.messages.size() != a.key_indices.size()) throw Error(ErrorKind::InvalidLength);
+      for (size_t j = 0; j < a.messages.size(); ++j) {
+        msgs.insert(msgs.end(), a.messages[j].begin(), a.messages[j].end());
+        msg_off.push_back(msgs.size());
+      }
+      idx.insert(idx.end(), a.key_indices.begin(), a.key_indices.end());
+      agg_off.push_back(msg_off.size() - 1);
+      std::memcpy(&sigs[64 * i], a.signature.raw.data(), 64);
+    }
+    const size_t m = msg_off.size() - 1;
+    check_rc("bn254_batch_aggregate_verify_distinct_keyed",
+             bn254_batch_aggregate_verify_distinct_keyed(e.raw(), msgs.data(), msg_off.data(), idx.data(), m, sigs.data(), agg_off.data(), n, 0, status.data()));
     return status;
   }
   // opt-in randomised mode (include/bn254_hip.h: bn254_batch_verify_randomized): same result shape; non-zero entries

@@ -295,6 +295,25 @@ int bn254_batch_aggregate_verify_distinct_device(bn254_ctx *ctx, const uint8_t *
                                                  const uint8_t *d_agg_sigs, const uint64_t *d_agg_off, size_t n, uint32_t flags, uint8_t *d_status,
                                                  void *stream);
 
+/* bn254_batch_aggregate_verify_distinct_keyed[_device]: as bn254_batch_aggregate_verify_distinct with key_idx[j] (uint32) in place of the
+ * j-th public key: pk_j = the key registered at that index (bn254_ctx_register_keys).  Rule 2 takes, for the first failing key in j order,
+ * 2 (IndexOutOfBounds) if key_idx[j] >= n_keys, else the key's registration status; with no keys registered every non-empty aggregate whose
+ * sigma decodes gets 2.  An empty aggregate checks e(sigma, -G2) == 1 as before.  Same result bytes as
+ * bn254_batch_aggregate_verify_distinct(flags | BN254_FLAG_G2_SUBGROUP_CHECK) on the expanded keys; for the keys,
+ * BN254_FLAG_REJECT_IDENTITY is the one given at registration (the call's flags apply to sigma), as in bn254_batch_verify_keyed.  k = 1
+ * everywhere gives byte for byte the statuses of bn254_batch_verify_keyed.  The host-form argument checks, the _device range rule (2 for a
+ * reversed or overlapping agg_off), bn254_ctx_expect_msgs_len, BN254_E_MISALIGNED and the 2^32 limits are those of the unkeyed call.
+ * Cost: every G2 argument is a line table (the keys' from registration, -G2's kept behind them), so the whole product of an aggregate is
+ * ONE table-driven multi-Miller loop: its k + 1 pairs, sigma's included, take one or two per lane pair and no pair walks a twist point; no
+ * separate Miller loop of sigma.  Contexts with pair lanes off and an empty key set expand the keys and take the unkeyed route.
+ * Workspace: m pairs + partial products + n aggregates, nothing per key. */
+int bn254_batch_aggregate_verify_distinct_keyed(bn254_ctx *ctx, const uint8_t *msgs, const uint64_t *msg_off /* m+1 */, const uint32_t *key_idx /* m */,
+                                                size_t m, const uint8_t *agg_sigs /* n*64 */, const uint64_t *agg_off /* n+1 */, size_t n,
+                                                uint32_t flags, uint8_t *status /* n */);
+int bn254_batch_aggregate_verify_distinct_keyed_device(bn254_ctx *ctx, const uint8_t *d_msgs, const uint64_t *d_msg_off, const uint32_t *d_key_idx,
+                                                       size_t m, const uint8_t *d_agg_sigs, const uint64_t *d_agg_off, size_t n, uint32_t flags,
+                                                       uint8_t *d_status, void *stream);
+
 /* compressed wire formats (src/utils.rs:84-104, :130-158): out = uncompressed point, status as
  * bn::G1::from_compressed / bn::G2::from_compressed report through src/types.rs:91-93, :233-237, checked in the order
  * those decoders work (an input with several faults reports the first):
@@ -485,6 +504,9 @@ int bn254_mgpu_batch_hash_to_g1(bn254_mgpu *mg, const uint8_t *msgs, const uint6
                                              Miller loop (the fallback path of an overflowing or degenerate batch); default 0 */
 #define BN254_OPT_KEY_DEDUP_HASH_BITS 24 /* test seam: keep only this many low bits of the key hash of the dedup table (0 = all, default), so that
                                          distinct keys collide: the full 128-byte compare and the probe bound (overflow -> generic loop) */
+#define BN254_OPT_AGGD_KEYED_ROUTE 25 /* bn254_batch_aggregate_verify_distinct_keyed: 0 (default) = by size; 1 / 2 = the table-driven slot kernel with
+                                    one / two table pairs per lane pair; 3 = the keys expanded into the unkeyed route.  1 and 2 apply on lane pairs
+                                    with keys registered.  Same status bytes. */
 #define BN254_OPT_ASSUME_FREE_MB 18 /* test knob for the automatic slicing rule (BN254_OPT_MAX_CHUNK = 0): price the workspace of a batch against this many MB
                                     of free device memory instead of what hipMemGetInfo reports; 0 = ask the runtime */
 /* the routing table of this context as it stands (defaults + options): rows (max_n[i], miller[i], fe[i]) in ascending order of max_n, the last

@@ -363,7 +363,7 @@ class ECDSA:
         _raise(ECDSA._distinct_keyed_status([(messages, signature, key_indices)], engine)[0])
 
     @staticmethod
-    def _distinct_keyed_status(aggregates, engine):
+    def _distinct_keyed_status(aggregates, engine, seed=None, flags=0):
         msgs, idx, sigs, sizes = [], [], [], []
         for messages, signature, key_indices in aggregates:
             if len(messages) != len(key_indices):
@@ -373,6 +373,8 @@ class ECDSA:
             sigs.append(signature.raw)
             sizes.append(len(messages))
         eng = engine or _eng()
+        if seed is not None:
+            return eng.batch_aggregate_verify_distinct_keyed_randomized(msgs, idx, b"".join(sigs), sizes, seed, flags)
         return eng.batch_aggregate_verify_distinct_keyed(msgs, idx, b"".join(sigs), sizes)
 
     @staticmethod
@@ -380,6 +382,20 @@ class ECDSA:
         """aggregates: a list of (messages, signature, key_indices); result[i] is None iff ECDSA.aggregate_verify_keyed on item i succeeds,
         else the Error it would raise.  A length mismatch in any item raises Error(InvalidLength) before any device work."""
         return [None if s == 0 else Error(s) for s in ECDSA._distinct_keyed_status(aggregates, engine)]
+
+    @staticmethod
+    def batch_aggregate_verify_distinct_keyed_randomized(aggregates, seed=None, engine=None, rand64=False):
+        """batch_aggregate_verify_distinct_keyed with the pairing checks of whole groups of aggregates combined under random weights
+        (include/bn254_hip.h: bn254_batch_aggregate_verify_distinct_keyed_randomized): the same result shape and InvalidLength checks; an
+        Error is always the exact one, a None is wrong with probability <= 2^-128 per group (2^-64 with rand64) for a secret seed
+        (32 bytes, default os.urandom(32))."""
+        import os
+        if seed is None:
+            seed = os.urandom(32)
+        if len(seed) != 32:
+            raise ValueError("seed must be 32 bytes")
+        flags = _engine.FLAG_RAND64 if rand64 else 0
+        return [None if s == 0 else Error(s) for s in ECDSA._distinct_keyed_status(aggregates, engine, bytes(seed), flags)]
 
 
 def check_public_keys(public_key_g2, public_key_g1):

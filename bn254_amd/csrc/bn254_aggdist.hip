@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <algorithm>
 #include <cstring>
 
 #include "../../include/bn254_hip.h"
@@ -323,6 +324,154 @@ static int aggd_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t* d_ms
   return 0;
 }
 
+// ---- registered keys, randomised (bn254_batch_aggregate_verify_distinct_keyed_randomized[_device]; kernels: bn254_aggrand.hip) -------------
+// Steps 1-3 and the status fold are the exact keyed call's; then the G1 side (scaled entries, buckets by (group, key), their segmented sums),
+// ONE slot-kernel check per group over its table pairs (a bucket's sum and its key; S_g and -G2), the collect, and the exact slot kernel
+// for the aggregates of failed groups only.  Workspace: pairs at j (H(m_j) in the P1 planes throughout; scaled entries in P2 / HASHX),
+// the Fq12 partials of both checks from pbase, aggregates from gbase (sigma_i in P1, r_i sigma_i in P2 / HASHX), groups from cbase (S_g,
+// their products), the groups' table pairs from tbase.
+static size_t aggr_partials(size_t e) {
+  size_t p = 0;
+  for (;;) {
+    const size_t g = (e + AGGR_SUM_WG - 1) / AGGR_SUM_WG;
+    if (g <= 1) return p;
+    p += 2 * g;
+    e = 2 * g;
+  }
+}
+// level 0 of a segmented Fq12 product over e0 slot elements (level0(e, pbase, pseg, last)), then the level kernel until one workgroup is left
+template <class Level0>
+static int aggd_levels(bn254_ctx* c, hipStream_t s, size_t e0, size_t gbase, size_t pbase, uint32_t* pseg, Level0 level0) {
+  size_t e = e0, ebase = 0, off = 0;
+  const uint32_t* seg = nullptr;
+  for (bool first = true;; first = false) {
+    const size_t g = (e + AGGD_WG_ELEMS - 1) / AGGD_WG_ELEMS;
+    const int last = g <= 1;
+    if (const int rc = first ? level0(e, pbase + off, pseg + off, last) : bn254_pair_aggd_level(e, c->ws, seg, ebase, gbase, pbase + off, pseg + off, last, s))
+      return rc;
+    if (last) return 0;
+    e = 2 * g;
+    ebase = pbase + off;
+    seg = pseg + off;
+    off += 2 * g;
+  }
+}
+static int aggr_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t* d_msg_off, const uint32_t* d_key_idx, size_t m, const uint8_t* d_sigs,
+                       const uint64_t* d_agg_off, size_t n, uint32_t flags, const uint8_t* seed32, uint8_t* d_status, hipStream_t s) {
+  const uint32_t dflags = flags & (BN254_FLAG_G2_SUBGROUP_CHECK | BN254_FLAG_REJECT_IDENTITY);
+  const size_t K = c->n_keys, G = (size_t)c->agg_rand_group_pairs > K ? (size_t)c->agg_rand_group_pairs : K;
+  const size_t ng = m / G + 1, n_b = ng * (K + 1), n_e = m + n;
+  const size_t n_tp_max = m < ng * K ? m : ng * K;                          // table pairs: one per non-empty (group, key) bucket
+  const int kr = c->aggd_keyed_route;
+  const int wx = kr == 1 || kr == 2 ? kr : m + n <= AGGD_KEYED_W1_MAX_SLOTS ? 1 : 2;     // the re-check: the exact call's slots
+  const int wg = n_tp_max + ng <= AGGD_KEYED_W1_MAX_SLOTS ? 1 : 2;                       // the group checks: the same rule on their bound
+  const size_t n_xslots = wx == 1 ? m + n : m / 2 + n, n_gslots = wg == 1 ? n_tp_max + ng : n_tp_max / 2 + ng;
+  const size_t px = aggd_partials(n_xslots), pg = aggd_partials(n_gslots), n_part = px > pg ? px : pg, n_spart = aggr_partials(n_e);
+  const size_t pbase = round256(m + 1), gbase = round256(pbase + n_part > n ? pbase + n_part : n), cbase = round256(gbase + n);
+  const size_t tbase = round256(cbase + ng);
+  int rc = ws_reserve(c, tbase + n_tp_max);
+  if (rc) return rc;
+  const size_t nbmax = (std::max(std::max(n, n_b), ng) + AGGD_SCAN_WG - 1) / AGGD_SCAN_WG;
+  const size_t u64_words = 5 * n + nbmax + 2 * n_b + 3 * ng;
+  const size_t u32_words = 2 * n + m + n_xslots + n_part + ng + 3 * n_e + (tbase + n_tp_max) + n_gslots + n_spart;
+  const size_t bytes = 8 * u64_words + 4 * u32_words + 4 * AGGR_PART_WORDS * n_spart + ng + n;
+  if (bytes > c->aggr_cap) {
+    if ((rc = ctx_quiesce(c))) return rc;
+    if (c->aggr_buf) { HIP_TRY(hipFree(c->aggr_buf)); c->aggr_buf = nullptr; c->aggr_cap = 0; }
+    const size_t cap = (bytes + 4095) & ~(size_t)4095;
+    HIP_TRY(hipMalloc((void**)&c->aggr_buf, cap));
+    c->aggr_cap = cap;
+  }
+  if (!c->aggr_stats) HIP_TRY(hipMalloc((void**)&c->aggr_stats, 8 * sizeof(uint32_t)));
+  uint64_t* mx = (uint64_t*)c->aggr_buf;
+  uint64_t *incl = mx + n, *lo = incl + n, *hi = lo + n, *kincl = hi + n, *tot = kincl + n, *cnt = tot + nbmax, *tp = cnt + n_b, *glo = tp + n_b;
+  uint64_t *ghi = glo + ng, *gkincl = ghi + ng;
+  uint32_t* first_pk = (uint32_t*)(gkincl + ng);
+  uint32_t *first_hash = first_pk + n, *pair_agg = first_hash + n, *xseg0 = pair_agg + m, *pseg = xseg0 + n_xslots, *nagg = pseg + n_part;
+  uint32_t *ebkt = nagg + ng, *perm = ebkt + n_e, *eseg = perm + n_e, *bkey = eseg + n_e, *gseg0 = bkey + tbase + n_tp_max, *spseg = gseg0 + n_gslots;
+  int32_t* part = (int32_t*)(spseg + n_spart);
+  uint8_t* gst = (uint8_t*)(part + AGGR_PART_WORDS * n_spart);
+  uint8_t* queued = gst + ng;
+  const KeyTable kt = {c->key_lines, c->key_st, c->key_inf, (uint32_t)K};
+  uint32_t seed_w[8];
+  for (int j = 0; j < 8; ++j)
+    seed_w[j] = ((uint32_t)seed32[4 * j] << 24) | ((uint32_t)seed32[4 * j + 1] << 16) | ((uint32_t)seed32[4 * j + 2] << 8) | seed32[4 * j + 3];
+  const int mode = (flags & BN254_FLAG_RAND64) ? 1 : (flags & BN254_FLAG_RAND_GLV) ? 2 : 0;
+  CallDone call_done(c, s);
+  c->aggr_last_ran = 1;
+  PROF_MARK(0);
+  // 1-3: as the exact keyed call (bn254_aggdist.hip: aggd_device), with each pair's aggregate for the G1 side
+  if ((rc = launch_decode_g1(c, s, d_sigs, n, dflags, PL_P2X, BY_P2_INF, 0))) return rc;
+  if ((rc = aggd_scan<AggdMax>(s, d_agg_off, n, mx, tot))) return rc;
+  k_aggd_prep<<<grid_for(n), BN_WAVE, 0, s>>>(n, (uint64_t)m, d_agg_off, mx, incl, lo, hi, first_pk, first_hash, c->ws, gbase);
+  if ((rc = aggd_scan<AggdAdd>(s, incl, n, incl, tot))) return rc;
+  k_aggd_keyed_count<<<grid_for(n), BN_WAVE, 0, s>>>(n, lo, hi, (uint64_t)wx, kincl);
+  if ((rc = aggd_scan<AggdAdd>(s, kincl, n, kincl, tot))) return rc;
+  k_aggd_keyed_keys<<<grid_for(m), BN_WAVE, 0, s>>>(m, d_key_idx, kt, c->key_xy, c->ws, 0);
+  HIP_TRY(hipGetLastError());
+  PROF_MARK(1);
+  if ((rc = launch_hash_rounds(c, s, d_msgs, d_msg_off, m, PL_P1X, BY_P1_INF, nullptr))) return rc;
+  PROF_MARK(2);
+  HIP_TRY(hipMemsetAsync(pair_agg, 0xFF, 4 * m, s));
+  const size_t n_slots = (m + n + 1) / 2;
+  k_aggd_map<<<grid_for(n_slots), BN_WAVE, 0, s>>>(n_slots, n, incl, lo, hi, nullptr, pair_agg, first_pk, first_hash, c->ws);
+  k_aggd_keyed_map<<<grid_for(n_xslots), BN_WAVE, 0, s>>>(n_xslots, n, kincl, xseg0);
+  k_aggd_status<<<grid_for(n), BN_WAVE, 0, s>>>(n, c->ws, gbase, first_pk, first_hash);
+  // the G1 side: scaled entries counted by bucket, sorted, summed into the groups' table pairs and S_g
+  HIP_TRY(hipMemsetAsync(nagg, 0, 4 * ng, s));
+  HIP_TRY(hipMemsetAsync(cnt, 0, 8 * n_b, s));
+  HIP_TRY(hipMemsetAsync(eseg, 0xFF, 4 * n_e, s));
+  const AggrScale sc = {pair_agg, d_key_idx, c->key_inf, lo, nagg, ebkt, cnt, (uint64_t)G, (uint32_t)K};
+  if ((rc = bn254_aggr_scale(m, n, c->ws, gbase, sc, seed_w, mode, s))) return rc;
+  if ((rc = aggd_scan<AggdAdd>(s, cnt, n_b, tp, tot))) return rc;
+  if ((rc = bn254_aggr_scatter(n_e, ebkt, tp, perm, eseg, n_b, (uint32_t)K, cnt, tp, s))) return rc;
+  if ((rc = aggd_scan<AggdAdd>(s, tp, n_b, tp, tot))) return rc;
+  if ((rc = bn254_aggr_glimits(ng, (uint32_t)K, tbase, cnt, tp, glo, ghi, c->ws, cbase, s))) return rc;
+  const AggrSum sm = {perm, tp, bkey, m, gbase, cbase, tbase, (uint32_t)K};
+  {
+    size_t e = n_e, off = 0;
+    const uint32_t* seg_in = eseg;
+    const int32_t* part_in = nullptr;
+    for (bool first = true;; first = false) {
+      const size_t g = (e + AGGR_SUM_WG - 1) / AGGR_SUM_WG;
+      const int last = g <= 1;
+      if ((rc = bn254_aggr_sum(e, first, c->ws, sm, seg_in, part_in, spseg + off, part + AGGR_PART_WORDS * off, last, s))) return rc;
+      if (last) break;
+      seg_in = spseg + off;
+      part_in = part + AGGR_PART_WORDS * off;
+      e = 2 * g;
+      off += 2 * g;
+    }
+  }
+  PROF_MARK(3);                                        // ms[2] = hash .. sums, ms[3] = group checks, collect and re-check
+  // one check per group: its table pairs and (S_g, -G2) through the slot kernel, the levels, the final exponentiation at index g
+  k_aggd_keyed_count<<<grid_for(ng), BN_WAVE, 0, s>>>(ng, glo, ghi, (uint64_t)wg, gkincl);
+  if ((rc = aggd_scan<AggdAdd>(s, gkincl, ng, gkincl, tot))) return rc;
+  k_aggd_keyed_map<<<grid_for(n_gslots), BN_WAVE, 0, s>>>(n_gslots, ng, gkincl, gseg0);
+  const AggdSlots gsl = {gseg0, gkincl, glo, ghi};
+  if ((rc = aggd_levels(c, s, n_gslots, cbase, pbase, pseg, [&](size_t e, size_t pb, uint32_t* ps, int last) {
+         return bn254_pair_aggd_keyed_queued(e, wg, c->ws, gsl, bkey, kt, cbase, pb, ps, last, nullptr, s);   // empty workgroups leave
+       })))
+    return rc;
+  if ((rc = bn254_pair_aggd_move(ng, c->ws, cbase, s))) return rc;
+  if ((rc = launch_final_exp_layout(c, s, ng, 0, gst, route_for(c, ng).fe))) return rc;
+  // statuses; the aggregates of failed groups (of two or more) queued and checked exactly — with none queued, launches that leave at once
+  HIP_TRY(hipMemsetAsync(c->ws.h_cnt, 0, sizeof(uint32_t), s));
+  HIP_TRY(hipMemsetAsync(c->aggr_stats, 0, 8 * sizeof(uint32_t), s));
+  if ((rc = bn254_aggr_collect(n, c->ws, gbase, lo, (uint64_t)G, nagg, gst, d_status, queued, ng, glo, ghi, c->aggr_stats, s))) return rc;
+  const AggdSlots xsl = {xseg0, kincl, lo, hi};
+  if ((rc = aggd_levels(c, s, n_xslots, gbase, pbase, pseg, [&](size_t e, size_t pb, uint32_t* ps, int last) {
+         return bn254_pair_aggd_keyed_queued(e, wx, c->ws, xsl, d_key_idx, kt, gbase, pb, ps, last, queued, s);
+       })))
+    return rc;
+  if ((rc = bn254_pair_aggd_move(n, c->ws, gbase, s))) return rc;
+  if ((rc = bn254_pair_final_exp(n, c->ws, 0, d_status, c->ws.h_list, c->ws.h_cnt, s))) return rc;
+  PROF_MARK(4);
+  if (c->profiling) { c->ev_valid = 1; c->ev_hash_first = 0; }
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 extern "C" {
 
 int bn254_batch_aggregate_verify_distinct_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t* d_msg_off, const uint8_t* d_pks, size_t m,
@@ -386,6 +535,45 @@ int bn254_batch_aggregate_verify_distinct_keyed(bn254_ctx* c, const uint8_t* msg
   if (st.ok())
     st.rc = bn254_batch_aggregate_verify_distinct_keyed_device(c, d_msgs, (const uint64_t*)d_msg_off, (const uint32_t*)d_key_idx, m, d_agg_sigs,
                                                                (const uint64_t*)d_agg_off, n, flags, d_status, nullptr);
+  return st.finish();
+}
+
+// ---- registered keys, randomised ----------------------------------------------------------------------------------------------------------
+int bn254_batch_aggregate_verify_distinct_keyed_randomized_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t* d_msg_off, const uint32_t* d_key_idx,
+                                                                  size_t m, const uint8_t* d_agg_sigs, const uint64_t* d_agg_off, size_t n, uint32_t flags,
+                                                                  const uint8_t* seed32, uint8_t* d_status, void* stream) {
+  MsgsLenScope msgs_len_scope(c);
+  if (!c || !seed32 || !d_agg_off || (n && (!d_agg_sigs || !d_status)) || (m && (!d_msgs || !d_msg_off || !d_key_idx))) return BN254_E_BAD_ARGUMENT;
+  if (m > 0xFFFFFFFFu || n > 0xFFFFFFFFu) return BN254_E_BAD_ARGUMENT;
+  c->aggr_last_ran = 0;
+  if (n == 0) return 0;
+  if (misaligned(d_agg_sigs) || misaligned(d_key_idx) || ((uintptr_t)d_msg_off & 7u) || ((uintptr_t)d_agg_off & 7u)) return BN254_E_MISALIGNED;
+  // no keys, pair lanes off, too few messages (or none): the exact keyed call, same bytes; entries are numbered in 32 bits
+  if (c->n_keys == 0 || !c->key_lines || !c->pair_lanes || m == 0 || m < (size_t)c->agg_rand_min_pairs || m + n > 0xFFFFFFFFu)
+    return bn254_batch_aggregate_verify_distinct_keyed_device(c, d_msgs, d_msg_off, d_key_idx, m, d_agg_sigs, d_agg_off, n, flags, d_status, stream);
+  HIP_TRY(hipSetDevice(c->device));
+  return aggr_device(c, d_msgs, d_msg_off, d_key_idx, m, d_agg_sigs, d_agg_off, n, flags, seed32, d_status, stream ? (hipStream_t)stream : c->stream);
+}
+
+int bn254_batch_aggregate_verify_distinct_keyed_randomized(bn254_ctx* c, const uint8_t* msgs, const uint64_t* msg_off, const uint32_t* key_idx, size_t m,
+                                                           const uint8_t* agg_sigs, const uint64_t* agg_off, size_t n, uint32_t flags, const uint8_t* seed32,
+                                                           uint8_t* status) {
+  MsgsLenScope msgs_len_scope(c);
+  if (!c || !seed32 || !msg_off || !agg_off || (n && (!agg_sigs || !status)) || (m && !key_idx)) return BN254_E_BAD_ARGUMENT;
+  if (m > 0xFFFFFFFFu || n > 0xFFFFFFFFu) return BN254_E_BAD_ARGUMENT;
+  if (agg_off[0] != 0 || agg_off[n] != m || !offsets_ok(agg_off, n) || !offsets_ok(msg_off, m)) return BN254_E_BAD_ARGUMENT;
+  c->aggr_last_ran = 0;
+  if (n == 0) return 0;
+  HIP_TRY(hipSetDevice(c->device));
+  if (!msgs_ok(msgs, msg_off, m)) return BN254_E_BAD_ARGUMENT;
+  HostStaging st(c);
+  const uint8_t *d_msgs = st.in(0, msgs, (size_t)msg_off[m]), *d_msg_off = st.in(1, msg_off, (m + 1) * sizeof(uint64_t));
+  const uint8_t *d_key_idx = st.in(2, key_idx, m * sizeof(uint32_t)), *d_agg_sigs = st.in(3, agg_sigs, n * 64);
+  const uint8_t* d_agg_off = st.in(4, agg_off, (n + 1) * sizeof(uint64_t));
+  uint8_t* d_status = st.out(5, n, status);
+  if (st.ok())
+    st.rc = bn254_batch_aggregate_verify_distinct_keyed_randomized_device(c, d_msgs, (const uint64_t*)d_msg_off, (const uint32_t*)d_key_idx, m, d_agg_sigs,
+                                                                          (const uint64_t*)d_agg_off, n, flags, seed32, d_status, nullptr);
   return st.finish();
 }
 

@@ -160,6 +160,18 @@ int bn254_debug_key_dedup_last(bn254_ctx* c, uint32_t out[5]) {
   out[0] = 1;
   return 0;
 }
+int bn254_debug_agg_rand_last(bn254_ctx* c, uint64_t out[6]) {
+  if (!c || !out) return BN254_E_BAD_ARGUMENT;
+  for (int i = 0; i < 6; ++i) out[i] = 0;
+  if (!c->aggr_last_ran || !c->aggr_stats) return 0;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipDeviceSynchronize());
+  uint32_t st[5];
+  HIP_TRY(hipMemcpy(st, c->aggr_stats, sizeof st, hipMemcpyDeviceToHost));
+  out[0] = 1;
+  for (int i = 0; i < 5; ++i) out[i + 1] = st[i];
+  return 0;
+}
 int bn254_debug_route_table(bn254_ctx* c, uint64_t* max_n, int* miller, int* fe, int cap) {
   if (!c || !max_n || !miller || !fe || cap < 5) return BN254_E_BAD_ARGUMENT;
   size_t m[5];

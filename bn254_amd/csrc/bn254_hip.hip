@@ -656,6 +656,8 @@ int bn254_ctx_create(int hip_device, bn254_ctx** out) {
   memset(c, 0, sizeof *c);
   c->pair_lanes = 1;
   c->rand_min_batch = RAND_MIN_BATCH_DEFAULT;
+  c->agg_rand_min_pairs = AGG_RAND_MIN_PAIRS_DEFAULT;
+  c->agg_rand_group_pairs = AGG_RAND_GROUP_PAIRS_DEFAULT;
   c->trio_max_batch = TRIO_MAX_BATCH_DEFAULT;
   c->hash_direct_width = HASH_DIRECT_WIDTH_DEFAULT;
   c->trio_wave_roles = TRIO_WAVE_ROLES_DEFAULT;
@@ -723,6 +725,8 @@ void bn254_ctx_destroy(bn254_ctx* c) {
   if (c->key_st) (void)hipFree(c->key_st);
   if (c->key_inf) (void)hipFree(c->key_inf);
   if (c->aggd_buf) (void)hipFree(c->aggd_buf);
+  if (c->aggr_buf) (void)hipFree(c->aggr_buf);
+  if (c->aggr_stats) (void)hipFree(c->aggr_stats);
   if (c->kd_buf) (void)hipFree(c->kd_buf);
   for (int i = 0; i < 5; ++i) (void)hipEventDestroy(c->ev[i]);
   (void)hipEventDestroy(c->kd_fork);
@@ -820,6 +824,8 @@ int bn254_ctx_set_option(bn254_ctx* c, int option, int value) {
   if (option == BN254_OPT_KEY_DEDUP_FORCE_GENERIC) { c->kd_force_generic = value != 0; return 0; }
   if (option == BN254_OPT_KEY_DEDUP_HASH_BITS) { if (value < 0 || value > 32) return BN254_E_BAD_ARGUMENT; c->kd_hash_bits = value; return 0; }
   if (option == BN254_OPT_AGGD_KEYED_ROUTE) { if (value < 0 || value > 3) return BN254_E_BAD_ARGUMENT; c->aggd_keyed_route = value; return 0; }
+  if (option == BN254_OPT_AGG_RAND_MIN_PAIRS) { if (value < 0) return BN254_E_BAD_ARGUMENT; c->agg_rand_min_pairs = value; return 0; }
+  if (option == BN254_OPT_AGG_RAND_GROUP_PAIRS) { if (value < 1) return BN254_E_BAD_ARGUMENT; c->agg_rand_group_pairs = value; return 0; }
   return BN254_E_BAD_ARGUMENT;
 }
 // clock probe (BN254_OPT_CLOCK_PROBE): the clock the chip ran the last Miller kernel [0], final exponentiation [1] and issue probe [2]

@@ -82,6 +82,12 @@ struct bn254_ctx {
   uint32_t* kd_ctl;          // the device-side decision of the last call that ran the dedup (bn254_debug_key_dedup_last)
   int kd_last_run;           // ... and whether the last bn254_batch_verify_device ran it at all
   int aggd_keyed_route;      // BN254_OPT_AGGD_KEYED_ROUTE (test and measurement knob): 0 by size, 1 / 2 the slot kernel of that width, 3 expanded keys
+  int agg_rand_min_pairs;    // BN254_OPT_AGG_RAND_MIN_PAIRS: the randomised keyed aggregate verify from this many messages on
+  int agg_rand_group_pairs;  // BN254_OPT_AGG_RAND_GROUP_PAIRS: messages per group of its combined checks (at least the number of keys)
+  uint8_t* aggr_buf;         // ... its scratch (bn254_aggdist.hip: aggr_device), grown on demand
+  size_t aggr_cap;
+  uint32_t* aggr_stats;      // ... what its last run did on the device (bn254_debug_agg_rand_last)
+  int aggr_last_ran;         // ... and whether the last call took the randomised route at all
 };
 
 struct ScopedEvents {

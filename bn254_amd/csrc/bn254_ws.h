@@ -220,6 +220,29 @@ __attribute__((visibility("hidden"))) int bn254_pair_miller_verify_keyed(size_t 
 __attribute__((visibility("hidden"))) int bn254_pair_aggd_keyed(size_t n_slots, int width, Ws ws, AggdSlots sl, const uint32_t* key_idx, KeyTable kt,
                                                                 size_t gbase, size_t pbase, uint32_t* pseg, int last, hipStream_t s);
 __attribute__((visibility("hidden"))) int bn254_pair_aggd_move(size_t n, Ws ws, size_t gbase, hipStream_t s);
+// ... randomised (bn254_aggrand.hip; host side: bn254_aggdist.hip): the G1 side — groups, scaled entries, buckets, their segmented sums — and
+// the exact slot kernel restricted to the aggregates marked in `queued` (null: every aggregate; a workgroup with none leaves before its Miller loop)
+#define AGG_RAND_MIN_PAIRS_DEFAULT 65536           // BN254_OPT_AGG_RAND_MIN_PAIRS: the randomised call from this many messages on
+#define AGG_RAND_GROUP_PAIRS_DEFAULT 1024          // BN254_OPT_AGG_RAND_GROUP_PAIRS: messages per group (at least the number of keys)
+#define AGGR_SUM_WG 256                            // segmented G1 sums: elements (lanes) per workgroup
+#define AGGR_PART_WORDS (3 * BN_LIMBS)             // ... a partial sum: one Jacobian point
+struct AggrScale { const uint32_t* pair_agg; const uint32_t* key_idx; const uint8_t* key_inf; const uint64_t* lo; uint32_t* nagg; uint32_t* ebkt;
+                   uint64_t* cnt; uint64_t G; uint32_t n_keys; };
+struct AggrSum { const uint32_t* perm; const uint64_t* tp; uint32_t* bkey; size_t m, gbase, cbase, tbase; uint32_t n_keys; };
+__attribute__((visibility("hidden"))) int bn254_aggr_scale(size_t m, size_t n, Ws ws, size_t gbase, AggrScale a, const uint32_t* seed_be, int mode,
+                                                           hipStream_t s);
+__attribute__((visibility("hidden"))) int bn254_aggr_scatter(size_t n_entries, const uint32_t* ebkt, uint64_t* start, uint32_t* perm, uint32_t* eseg,
+                                                             size_t n_b, uint32_t n_keys, const uint64_t* cnt, uint64_t* tp, hipStream_t s);
+__attribute__((visibility("hidden"))) int bn254_aggr_glimits(size_t n_groups, uint32_t n_keys, size_t tbase, const uint64_t* cnt, const uint64_t* tp,
+                                                             uint64_t* glo, uint64_t* ghi, Ws ws, size_t cbase, hipStream_t s);
+__attribute__((visibility("hidden"))) int bn254_aggr_sum(size_t n_elems, int level0, Ws ws, AggrSum a, const uint32_t* seg_in, const int32_t* part_in,
+                                                         uint32_t* pseg_out, int32_t* part_out, int last, hipStream_t s);
+__attribute__((visibility("hidden"))) int bn254_aggr_collect(size_t n, Ws ws, size_t gbase, const uint64_t* lo, uint64_t G, const uint32_t* nagg,
+                                                             const uint8_t* gst, uint8_t* status, uint8_t* queued, size_t n_groups, const uint64_t* glo,
+                                                             const uint64_t* ghi, uint32_t* stats, hipStream_t s);
+__attribute__((visibility("hidden"))) int bn254_pair_aggd_keyed_queued(size_t n_slots, int width, Ws ws, AggdSlots sl, const uint32_t* key_idx, KeyTable kt,
+                                                                       size_t gbase, size_t pbase, uint32_t* pseg, int last, const uint8_t* queued,
+                                                                       hipStream_t s);
 
 // key deduplication of the exact verify (bn254_keydedup.hip): per call, the distinct keys of the batch and their line tables in the
 // KeyTable format above, built on a stream of the context beside decode and hash; the route (tables or the generic loop) is decided on the device

@@ -37,6 +37,8 @@ OPT_KEY_DEDUP_MIN_MULT = 22  # ... and at least this many items per key (default
 OPT_KEY_DEDUP_FORCE_GENERIC = 23   # test hook: the device-side decision always takes the generic loop
 OPT_KEY_DEDUP_HASH_BITS = 24       # test seam: bits of the dedup hash kept (0 = all)
 OPT_AGGD_KEYED_ROUTE = 25          # keyed aggregates over distinct messages: 0 by size, 1 / 2 slot kernel width, 3 expanded keys
+OPT_AGG_RAND_MIN_PAIRS = 26        # randomised keyed aggregates over distinct messages: the exact route below this many messages
+OPT_AGG_RAND_GROUP_PAIRS = 27      # ... messages per group of its combined checks (developer option; at least the number of keys)
 
 
 class NativeError(RuntimeError):
@@ -129,6 +131,13 @@ class Engine:
         o = (ctypes.c_uint32 * 5)()
         _check("bn254_debug_key_dedup_last", self._lib.bn254_debug_key_dedup_last(self._h, o))
         return dict(zip(("ran", "keys", "flags", "keyed_n", "generic_n"), (int(x) for x in o)))
+
+    def debug_agg_rand_last(self):
+        """what the last batch_aggregate_verify_distinct_keyed_randomized[_device] did: dict(ran, groups, table_pairs, failed_groups, rechecked,
+        single_groups)"""
+        o = (ctypes.c_uint64 * 6)()
+        _check("bn254_debug_agg_rand_last", self._lib.bn254_debug_agg_rand_last(self._h, o))
+        return dict(zip(("ran", "groups", "table_pairs", "failed_groups", "rechecked", "single_groups"), (int(x) for x in o)))
 
     def last_kernel_ms(self):
         ms = (ctypes.c_float * 4)()
@@ -318,6 +327,25 @@ class Engine:
                self._lib.bn254_batch_aggregate_verify_distinct_keyed(self._h, msgs, off, idx, m, bytes(agg_sigs), a_off, n, flags, status))
         return status.raw[:n]
 
+    def batch_aggregate_verify_distinct_keyed_randomized(self, messages, key_idx, agg_sigs, agg_sizes, seed32, flags=0):
+        """batch_aggregate_verify_distinct_keyed with the pairing checks of whole groups of aggregates combined under random weights from seed32
+        (include/bn254_hip.h: bn254_batch_aggregate_verify_distinct_keyed_randomized).  Returns n status bytes."""
+        m, n = len(messages), len(agg_sizes)
+        assert len(key_idx) == m and len(agg_sigs) == n * G1_BYTES and sum(agg_sizes) == m and len(seed32) == 32
+        msgs, off = pack_messages(messages)
+        idx = (ctypes.c_uint32 * max(m, 1))(*key_idx)
+        a_off = (ctypes.c_uint64 * (n + 1))()
+        pos = 0
+        for i, k in enumerate(agg_sizes):
+            a_off[i] = pos
+            pos += int(k)
+        a_off[n] = pos
+        status = ctypes.create_string_buffer(max(n, 1))
+        _check("bn254_batch_aggregate_verify_distinct_keyed_randomized",
+               self._lib.bn254_batch_aggregate_verify_distinct_keyed_randomized(self._h, msgs, off, idx, m, bytes(agg_sigs), a_off, n, flags, bytes(seed32),
+                                                                                status))
+        return status.raw[:n]
+
     def register_pools(self, messages, pk_pool, sig_pool, expect_tuples, flags=0):
         """the pools of an aggregate verify decoded, hashed and tabulated ONCE (bn254_ctx_register_pools): for a fixed validator set / message
         set whose tuples keep arriving; `expect_tuples` = the batch size the subset-sum tables are chosen for"""
@@ -460,6 +488,13 @@ class Engine:
         _check("bn254_batch_aggregate_verify_distinct_device",
                self._lib.bn254_batch_aggregate_verify_distinct_device(self._h, d_msgs, d_msg_off, d_pks, m, d_agg_sigs, d_agg_off, n, flags, d_status,
                                                                       stream))
+
+    def batch_aggregate_verify_distinct_keyed_randomized_device(self, d_msgs, d_msg_off, d_key_idx, m, d_agg_sigs, d_agg_off, n, seed32, d_status, flags=0,
+                                                                stream=None):
+        assert len(seed32) == 32
+        _check("bn254_batch_aggregate_verify_distinct_keyed_randomized_device",
+               self._lib.bn254_batch_aggregate_verify_distinct_keyed_randomized_device(self._h, d_msgs, d_msg_off, d_key_idx, m, d_agg_sigs, d_agg_off, n,
+                                                                                       flags, bytes(seed32), d_status, stream))
 
     def batch_aggregate_verify_distinct_keyed_device(self, d_msgs, d_msg_off, d_key_idx, m, d_agg_sigs, d_agg_off, n, d_status, flags=0, stream=None):
         _check("bn254_batch_aggregate_verify_distinct_keyed_device",

@@ -4,6 +4,7 @@
 //   bn254::ECDSA::sign / verify / batch_verify      /root/reference/src/ecdsa.rs:26-35, :49-64 (+ new batch entry)
 //   bn254::ECDSA::aggregate_verify / batch_aggregate_verify_distinct   (new: aggregates over distinct messages)
 //   bn254::ECDSA::aggregate_verify_keyed / batch_aggregate_verify_distinct_keyed   (... against registered keys)
+//   bn254::ECDSA::batch_aggregate_verify_distinct_keyed_randomized                  (... with the group checks combined)
 //   bn254::check_public_keys                        /root/reference/src/ecdsa.rs:78-93
 //   bn254::PrivateKey / PublicKey / PublicKeyG1 / Signature   /root/reference/src/types.rs:13,81,151,222
 //   bn254::Error                                    /root/reference/src/error.rs:6-29
@@ -255,6 +256,17 @@ struct ECDSA {
   }
   // result[i] == 0 iff aggregate_verify_keyed on aggregates[i] succeeds, else the ErrorKind it would throw
   static std::vector<uint8_t> batch_aggregate_verify_distinct_keyed(const std::vector<KeyedAggregate>& aggregates, Engine& e = Engine::default_engine()) {
+    return keyed_aggregates(aggregates, nullptr, 0, e);
+  }
+  // opt-in randomised mode (include/bn254_hip.h: bn254_batch_aggregate_verify_distinct_keyed_randomized): the same result shape; non-zero
+  // entries are exact, a zero is wrong with probability <= 2^-128 per group (2^-64 with rand64) for a fresh secret 32-byte seed
+  static std::vector<uint8_t> batch_aggregate_verify_distinct_keyed_randomized(const std::vector<KeyedAggregate>& aggregates,
+                                                                              const std::array<uint8_t, 32>& seed, Engine& e = Engine::default_engine(),
+                                                                              bool rand64 = false) {
+    return keyed_aggregates(aggregates, seed.data(), rand64 ? BN254_FLAG_RAND64 : 0, e);
+  }
+  // the two keyed aggregate calls: seed == nullptr the exact one, else the randomised one with these flags
+  static std::vector<uint8_t> keyed_aggregates(const std::vector<KeyedAggregate>& aggregates, const uint8_t* seed, uint32_t flags, Engine& e) {
     const size_t n = aggregates.size();
     std::vector<uint64_t> msg_off(1, 0), agg_off(1, 0);
     std::vector<uint32_t> idx;
@@ -271,8 +283,14 @@ struct ECDSA {
       std::memcpy(&sigs[64 * i], a.signature.raw.data(), 64);
     }
     const size_t m = msg_off.size() - 1;
-    check_rc("bn254_batch_aggregate_verify_distinct_keyed",
-             bn254_batch_aggregate_verify_distinct_keyed(e.raw(), msgs.data(), msg_off.data(), idx.data(), m, sigs.data(), agg_off.data(), n, 0, status.data()));
+    if (seed)
+      check_rc("bn254_batch_aggregate_verify_distinct_keyed_randomized",
+               bn254_batch_aggregate_verify_distinct_keyed_randomized(e.raw(), msgs.data(), msg_off.data(), idx.data(), m, sigs.data(), agg_off.data(), n,
+                                                                      flags, seed, status.data()));
+    else
+      check_rc("bn254_batch_aggregate_verify_distinct_keyed",
+               bn254_batch_aggregate_verify_distinct_keyed(e.raw(), msgs.data(), msg_off.data(), idx.data(), m, sigs.data(), agg_off.data(), n, 0,
+                                                           status.data()));
     return status;
   }
   // opt-in randomised mode (include/bn254_hip.h: bn254_batch_verify_randomized): same result shape; non-zero entries

@@ -314,6 +314,32 @@ int bn254_batch_aggregate_verify_distinct_keyed_device(bn254_ctx *ctx, const uin
                                                        size_t m, const uint8_t *d_agg_sigs, const uint64_t *d_agg_off, size_t n, uint32_t flags,
                                                        uint8_t *d_status, void *stream);
 
+/* bn254_batch_aggregate_verify_distinct_keyed_randomized[_device]: the same inputs and status bytes as bn254_batch_aggregate_verify_distinct_keyed,
+ * with the pairing checks of many aggregates combined.  Rules 1-3 (sigma's decode; the first bad key: 2 out of range, else its registration
+ * status; the first hash failure, or in the _device form a range error) are exact, and so are the host-form argument checks, the _device
+ * range rule, bn254_ctx_expect_msgs_len, BN254_E_MISALIGNED and the 2^32 limits, which are the keyed call's.  A non-zero status is always the
+ * exact one; a zero is wrong with probability <= 2^-128 per group (2^-64 with BN254_FLAG_RAND64) for a fresh secret seed32.
+ *   r_i = rand_scalar(seed32, i) as in the other randomised calls (SHA-256(seed32 || le64(i)), 0 -> 1) with i = the aggregate's index in the
+ *   call; BN254_FLAG_RAND64 and BN254_FLAG_RAND_GLV as documented there; the other flags apply to sigma, as in the keyed call.
+ *   Groups: aggregate i belongs to group agg_off[i] / G, G = max(BN254_OPT_AGG_RAND_GROUP_PAIRS, n_keys) — consecutive whole aggregates;
+ *   aggregates with a non-zero status from rules 1-3 take no part.  A group passes iff
+ *       prod_key e(sum_{i in g} r_i sum_{j in i, key_idx[j] = key} H(m_j), pk_key) * e(sum_{i in g} r_i sigma_i, -G2) == 1
+ *   — one table-driven multi-Miller loop over (distinct keys of the group + 1) pairs and one final exponentiation per group; messages that
+ *   share a key within a group cost G1 additions, not Miller loops.  A group with ONE aggregate at the check takes r = 1: its check is the
+ *   exact one with equal keys merged, and its status is that check's.  Every aggregate of a failed group of two or more is re-checked
+ *   exactly on the device, with no host synchronisation (the _device form only enqueues).
+ *   The exact keyed route, same bytes, when no keys are registered, pair lanes are off, or m < BN254_OPT_AGG_RAND_MIN_PAIRS.
+ * Security: as bn254_batch_aggregate_verify_distinct — proof of possession of the registered keys is assumed, and the messages are not
+ * checked for distinctness.  seed32 is host memory in both forms. */
+int bn254_batch_aggregate_verify_distinct_keyed_randomized(bn254_ctx *ctx, const uint8_t *msgs, const uint64_t *msg_off /* m+1 */,
+                                                           const uint32_t *key_idx /* m */, size_t m, const uint8_t *agg_sigs /* n*64 */,
+                                                           const uint64_t *agg_off /* n+1 */, size_t n, uint32_t flags, const uint8_t *seed32,
+                                                           uint8_t *status /* n */);
+int bn254_batch_aggregate_verify_distinct_keyed_randomized_device(bn254_ctx *ctx, const uint8_t *d_msgs, const uint64_t *d_msg_off,
+                                                                  const uint32_t *d_key_idx, size_t m, const uint8_t *d_agg_sigs,
+                                                                  const uint64_t *d_agg_off, size_t n, uint32_t flags,
+                                                                  const uint8_t *seed32 /* host memory */, uint8_t *d_status, void *stream);
+
 /* compressed wire formats (src/utils.rs:84-104, :130-158): out = uncompressed point, status as
  * bn::G1::from_compressed / bn::G2::from_compressed report through src/types.rs:91-93, :233-237, checked in the order
  * those decoders work (an input with several faults reports the first):
@@ -349,6 +375,8 @@ int bn254_ctx_set_profiling(bn254_ctx *ctx, int enabled);
                                    bytes.  0 = never (wave roles / octet layout) */
 #define BN254_OPT_RAND_MIN_BATCH 5 /* randomised verify: batches with fewer items run the exact kernels instead (same statuses; group_ok = no item of the
                                      group failed the pairing check).  Default 131072, the measured break-even on an MI355X; 0 = always randomised */
+#define BN254_OPT_AGG_RAND_MIN_PAIRS 26 /* bn254_batch_aggregate_verify_distinct_keyed_randomized: calls with fewer messages take the exact keyed route
+                                         (same statuses).  Default 65536, the measured break-even on an MI355X; 0 = always randomised */
 #define BN254_OPT_AGG_SUBSET_MIN_TUPLES 9 /* aggregate verify: from this many tuples on (default 4096) the sums of all subsets of every 8 consecutive
                                             keys of the pool are tabulated once per call and a tuple adds one table entry per group instead of one
                                             key per signer (pools of up to 2048 signers, lists longer than n_signers / 8); 0 = never.  Same statuses. */
@@ -507,6 +535,8 @@ int bn254_mgpu_batch_hash_to_g1(bn254_mgpu *mg, const uint8_t *msgs, const uint6
 #define BN254_OPT_AGGD_KEYED_ROUTE 25 /* bn254_batch_aggregate_verify_distinct_keyed: 0 (default) = by size; 1 / 2 = the table-driven slot kernel with
                                     one / two table pairs per lane pair; 3 = the keys expanded into the unkeyed route.  1 and 2 apply on lane pairs
                                     with keys registered.  Same status bytes. */
+#define BN254_OPT_AGG_RAND_GROUP_PAIRS 27 /* bn254_batch_aggregate_verify_distinct_keyed_randomized: messages per group of the combined checks (default
+                                           1024, at least 1; the number of keys when that is larger).  Same status bytes */
 #define BN254_OPT_ASSUME_FREE_MB 18 /* test knob for the automatic slicing rule (BN254_OPT_MAX_CHUNK = 0): price the workspace of a batch against this many MB
                                     of free device memory instead of what hipMemGetInfo reports; 0 = ask the runtime */
 /* the routing table of this context as it stands (defaults + options): rows (max_n[i], miller[i], fe[i]) in ascending order of max_n, the last
@@ -517,6 +547,10 @@ int bn254_debug_route_table(bn254_ctx *ctx, uint64_t *max_n, int *miller, int *f
  * flags (1 probe overflow, 2 degenerate line), items of the keyed Miller kernel, items of the generic one}; all 0 when the call did not run
  * the dedup.  Synchronises the device. */
 int bn254_debug_key_dedup_last(bn254_ctx *ctx, uint32_t out[5]);
+/* what the last bn254_batch_aggregate_verify_distinct_keyed_randomized[_device] did: out = {1 if it took the randomised route, groups that
+ * reached the check, table pairs of all group checks, failed groups, aggregates re-checked, groups of one aggregate (r = 1)}; all 0 when it
+ * took the exact route.  Synchronises the device. */
+int bn254_debug_agg_rand_last(bn254_ctx *ctx, uint64_t out[6]);
 /* test hooks: element-wise field/tower operations on byte-encoded operands, used by the parity
  * tests to compare each layer of the HIP arithmetic with the oracle.
  *   op: 0 mul, 1 add, 2 sub, 3 inverse(a), 4 square(a), 5 sqrt(a) (status 6 if none)   [Fq, 32 B]

@@ -398,7 +398,7 @@ static int aggr_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t* d_ms
     seed_w[j] = ((uint32_t)seed32[4 * j] << 24) | ((uint32_t)seed32[4 * j + 1] << 16) | ((uint32_t)seed32[4 * j + 2] << 8) | seed32[4 * j + 3];
   const int mode = (flags & BN254_FLAG_RAND64) ? 1 : (flags & BN254_FLAG_RAND_GLV) ? 2 : 0;
   CallDone call_done(c, s);
-  c->aggr_last_ran = 1;
+  c->aggr_last = {ng, cbase, tbase, nagg, bkey, glo, ghi, gst};   // nothing below rewrites these once the group checks are through
   PROF_MARK(0);
   // 1-3: as the exact keyed call (bn254_aggdist.hip: aggd_device), with each pair's aggregate for the G1 side
   if ((rc = launch_decode_g1(c, s, d_sigs, n, dflags, PL_P2X, BY_P2_INF, 0))) return rc;
@@ -469,6 +469,7 @@ static int aggr_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t* d_ms
   PROF_MARK(4);
   if (c->profiling) { c->ev_valid = 1; c->ev_hash_first = 0; }
   HIP_TRY(hipGetLastError());
+  c->aggr_last_ran = 1;                                // only a call that enqueued everything has something for the debug hooks to read
   return 0;
 }
 

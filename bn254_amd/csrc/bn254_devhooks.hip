@@ -102,6 +102,14 @@ KERNEL_SMALL void k_debug_load_f(const int32_t* limbs, size_t n, Ws ws) {
   ws_byte(ws, BY_ST_DECODE, i) = ST_OK;
   ws_byte(ws, BY_ST_HASH, i) = ST_OK;
 }
+// test hook: n affine G1 points of the P1 planes from `base` as 64-byte encodings (the identity: zeros)
+KERNEL_SMALL void k_debug_read_p1(Ws ws, size_t base, size_t n, uint8_t* out) {
+  size_t i = (size_t)blockIdx.x * BN_WAVE + threadIdx.x;
+  if (i >= n) return;
+  G1Affine p;
+  ws_load_g1(ws, PL_P1X, BY_P1_INF, base + i, p);
+  encode_g1(out + 64 * i, p);
+}
 
 // ---- in-process issue-rate probe (bench.py's roofline calibration) --------------------------------------------
 // 16 independent chains of one instruction, 4096 trips, on every SIMD of the device with `waves_per_simd` waves each
@@ -170,6 +178,43 @@ int bn254_debug_agg_rand_last(bn254_ctx* c, uint64_t out[6]) {
   HIP_TRY(hipMemcpy(st, c->aggr_stats, sizeof st, hipMemcpyDeviceToHost));
   out[0] = 1;
   for (int i = 0; i < 5; ++i) out[i + 1] = st[i];
+  return 0;
+}
+// The groups of the last randomised call, read from where it left them (bn254_host.h: aggr_last): the call itself launches and copies
+// nothing for this.  dims = {groups, table pairs}; with group_cap / pair_cap too small only dims is written.
+int bn254_debug_agg_rand_sums(bn254_ctx* c, uint64_t dims[2], size_t group_cap, size_t pair_cap, uint32_t* nagg, uint8_t* verdict, uint8_t* s_g,
+                              uint64_t* first_pair, uint32_t* pair_key, uint8_t* pair_point) {
+  if (!c || !dims) return BN254_E_BAD_ARGUMENT;
+  dims[0] = dims[1] = 0;
+  if (!c->aggr_last_ran || !c->aggr_buf) return 0;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipDeviceSynchronize());
+  const size_t ng = c->aggr_last.ng, tbase = c->aggr_last.tbase;
+  uint64_t end = 0;
+  HIP_TRY(hipMemcpy(&end, c->aggr_last.ghi + (ng - 1), sizeof end, hipMemcpyDeviceToHost));
+  const size_t n_tp = (size_t)(end - tbase);
+  dims[0] = ng;
+  dims[1] = n_tp;
+  if (group_cap < ng || pair_cap < n_tp) return 0;
+  if (!nagg || !verdict || !s_g || !first_pair || (n_tp && (!pair_key || !pair_point))) return BN254_E_BAD_ARGUMENT;
+  HIP_TRY(hipMemcpy(nagg, c->aggr_last.nagg, ng * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(verdict, c->aggr_last.gst, ng, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(first_pair, c->aggr_last.glo, ng * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  for (size_t g = 0; g < ng; ++g) first_pair[g] -= tbase;
+  first_pair[ng] = n_tp;
+  if (n_tp) HIP_TRY(hipMemcpy(pair_key, c->aggr_last.bkey + tbase, n_tp * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  int rc;
+  if ((rc = stage_reserve(c, 0, 64 * (ng > n_tp ? ng : n_tp)))) return rc;
+  k_debug_read_p1<<<grid_for(ng), BN_WAVE, 0, c->stream>>>(c->ws, c->aggr_last.cbase, ng, c->stage[0]);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(s_g, c->stage[0], 64 * ng, hipMemcpyDeviceToHost));
+  if (n_tp) {
+    k_debug_read_p1<<<grid_for(n_tp), BN_WAVE, 0, c->stream>>>(c->ws, tbase, n_tp, c->stage[0]);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(pair_point, c->stage[0], 64 * n_tp, hipMemcpyDeviceToHost));
+  }
   return 0;
 }
 int bn254_debug_route_table(bn254_ctx* c, uint64_t* max_n, int* miller, int* fe, int cap) {

@@ -88,6 +88,8 @@ struct bn254_ctx {
   size_t aggr_cap;
   uint32_t* aggr_stats;      // ... what its last run did on the device (bn254_debug_agg_rand_last)
   int aggr_last_ran;         // ... and whether the last call took the randomised route at all
+  // ... and where that call left its groups (bn254_debug_agg_rand_sums): S_g in the P1 planes from cbase, the table pairs from tbase, the rest in aggr_buf
+  struct { size_t ng, cbase, tbase; const uint32_t *nagg, *bkey; const uint64_t *glo, *ghi; const uint8_t* gst; } aggr_last;
 };
 
 struct ScopedEvents {

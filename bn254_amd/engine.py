@@ -139,6 +139,24 @@ class Engine:
         _check("bn254_debug_agg_rand_last", self._lib.bn254_debug_agg_rand_last(self._h, o))
         return dict(zip(("ran", "groups", "table_pairs", "failed_groups", "rechecked", "single_groups"), (int(x) for x in o)))
 
+    def debug_agg_rand_sums(self):
+        """the G1 side of that call's group checks as it left them (include/bn254_hip.h: bn254_debug_agg_rand_sums): a list with one
+        dict(nagg, verdict, s, pairs=[(key index, 64-byte bucket sum), ...]) per group, the groups without an aggregate included; [] when
+        the call took the exact route.  Read it directly after that call: ANY later call on the engine (a sign, a sum, a registration)
+        may reuse the workspace, and the hook then returns whatever lies there"""
+        name, f = "bn254_debug_agg_rand_sums", self._lib.bn254_debug_agg_rand_sums
+        dims = (ctypes.c_uint64 * 2)()
+        _check(name, f(self._h, dims, 0, 0, None, None, None, None, None, None))
+        ng, ntp = int(dims[0]), int(dims[1])
+        if ng == 0:
+            return []
+        nagg, verdict, s = (ctypes.c_uint32 * ng)(), ctypes.create_string_buffer(ng), ctypes.create_string_buffer(64 * ng)
+        first, keys, pts = (ctypes.c_uint64 * (ng + 1))(), (ctypes.c_uint32 * max(ntp, 1))(), ctypes.create_string_buffer(64 * max(ntp, 1))
+        _check(name, f(self._h, dims, ng, ntp, nagg, verdict, s, first, keys, pts))
+        assert (int(dims[0]), int(dims[1])) == (ng, ntp)
+        return [dict(nagg=int(nagg[g]), verdict=verdict.raw[g], s=s.raw[64 * g:64 * g + 64],
+                     pairs=[(int(keys[t]), pts.raw[64 * t:64 * t + 64]) for t in range(int(first[g]), int(first[g + 1]))]) for g in range(ng)]
+
     def last_kernel_ms(self):
         ms = (ctypes.c_float * 4)()
         _check("bn254_ctx_last_kernel_ms", self._lib.bn254_ctx_last_kernel_ms(self._h, ms))

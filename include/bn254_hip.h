@@ -551,6 +551,14 @@ int bn254_debug_key_dedup_last(bn254_ctx *ctx, uint32_t out[5]);
  * reached the check, table pairs of all group checks, failed groups, aggregates re-checked, groups of one aggregate (r = 1)}; all 0 when it
  * took the exact route.  Synchronises the device. */
 int bn254_debug_agg_rand_last(bn254_ctx *ctx, uint64_t out[6]);
+/* the G1 side of the group checks of that call, read from where it left them (valid until the next call on the context; the call itself
+ * does nothing extra for this).  dims = {groups = m / G + 1 (those with no aggregate included), table pairs of all groups}; dims = {0, 0}
+ * when the call took the exact route.  With group_cap >= groups and pair_cap >= table pairs also, per group g: nagg[g] = its aggregates
+ * at the check, verdict[g] = the status byte of its check (0 / 9; meaningful where nagg[g] != 0), s_g = S_g = sum r_i sigma_i (64 bytes
+ * affine, zeros = the identity), first_pair[g] .. first_pair[g + 1] = its table pairs (groups + 1 entries), and per table pair its key index
+ * and its point sum r_i H(m_j) over the group's entries of that key (64 bytes).  Otherwise only dims is written.  Synchronises the device. */
+int bn254_debug_agg_rand_sums(bn254_ctx *ctx, uint64_t dims[2], size_t group_cap, size_t pair_cap, uint32_t *nagg, uint8_t *verdict,
+                              uint8_t *s_g /* groups*64 */, uint64_t *first_pair /* groups+1 */, uint32_t *pair_key, uint8_t *pair_point /* pairs*64 */);
 /* test hooks: element-wise field/tower operations on byte-encoded operands, used by the parity
  * tests to compare each layer of the HIP arithmetic with the oracle.
  *   op: 0 mul, 1 add, 2 sub, 3 inverse(a), 4 square(a), 5 sqrt(a) (status 6 if none)   [Fq, 32 B]

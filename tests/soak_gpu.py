@@ -243,6 +243,74 @@ def soak(args):
                     raise SoakMismatch("MISMATCH %s round %d flags %d n %d %r %r" % (name, rounds, kflags, kn, bad[:5], [(g[i], kwant[i]) for i in bad[:5]]))
             extra["dedup_tuples"] = extra.get("dedup_tuples", 0) + kn
             extra["dedup_keys"] = extra.get("dedup_keys", 0) + route["keys"]
+        if rounds % 8 == 2:
+            # aggregates over distinct messages against registered keys: a ragged batch with random corruptions; the unkeyed call with the
+            # subgroup check == the keyed call == the randomised keyed call (random seed, scalar mode and group size), and what the randomised
+            # call did on the device (bn254_debug_agg_rand_last) == the model of tests/aggr_model.py
+            import ctypes
+            from bn254_amd.engine import OPT_AGG_RAND_GROUP_PAIRS, OPT_AGG_RAND_MIN_PAIRS
+            from tests.aggr_model import HOOK_FIELDS, grouping_from_statuses
+            reg_keys = [pk_pool[128 * j:128 * j + 128] for j in range(64)] + [bytes(128), off_sub]
+            key_inf = [False] * 64 + [True, False]
+            eng.register_keys(b"".join(reg_keys))
+            sizes = [rnd.choice([0, 1, 2, 3, 5, 8, 13, 21, 34, 55, 70, 130]) for _ in range(rnd.randrange(20, 61))] + [1]
+            amsgs, akidx, signed, soff = [], [], [], [0]
+            for a, k in enumerate(sizes):
+                for j in range(k):
+                    amsgs.append(hashlib.sha256(b"soak-aggd%d/%d/%d" % (rounds, a, j)).digest()[:rnd.choice([1, 31, 32])] + b"%d.%d" % (a, j))
+                    akidx.append(64 if rnd.randrange(25) == 0 else rnd.randrange(64))     # now and then the identity key: its pair is one
+                    if akidx[-1] < 64:
+                        signed.append(len(amsgs) - 1)
+                soff.append(len(signed))
+            ssig, st = eng.batch_sign([amsgs[j] for j in signed], b"".join(sks[akidx[j]] for j in signed))
+            assert st == bytes(len(signed))
+            full = [a for a in range(len(sizes)) if soff[a + 1] > soff[a]]
+            ssum, st = eng.batch_g1_sum(ssig, (ctypes.c_uint64 * (len(full) + 1))(*([soff[a] for a in full] + [len(signed)])))
+            assert st == bytes(len(full))
+            sigma = [bytes(64)] * len(sizes)
+            for x, a in enumerate(full):
+                sigma[a] = ssum[64 * x:64 * x + 64]
+            pos, oob_agg = 0, set()
+            for a, k in enumerate(sizes):
+                kind = rnd.randrange(12)
+                if kind == 0:
+                    sg = bytearray(sigma[a]); sg[rnd.randrange(64)] ^= 1 << rnd.randrange(8); sigma[a] = bytes(sg)
+                elif kind == 1:
+                    sigma[a] = c.g1_add(sigma[a], c.g1_generator())
+                elif kind == 2:
+                    sigma[a] = (Q + rnd.randrange(1000)).to_bytes(32, "big") + sigma[a][32:]
+                elif kind == 3 and k >= 2:
+                    amsgs[pos], amsgs[pos + k - 1] = amsgs[pos + k - 1], amsgs[pos]
+                elif kind == 4 and k:
+                    akidx[pos + rnd.randrange(k)] = rnd.randrange(64)
+                elif kind == 5 and k:
+                    akidx[pos + rnd.randrange(k)] = 65                                    # the key outside the subgroup: 4
+                elif kind == 6 and k:
+                    akidx[pos + rnd.randrange(k)] = rnd.choice([len(reg_keys), len(reg_keys) + 7, 0xFFFFFFFF])
+                    oob_agg.add(a)
+                pos += k
+            asig = b"".join(sigma)
+            got_k = eng.batch_aggregate_verify_distinct_keyed(amsgs, akidx, asig, sizes)
+            got_u = eng.batch_aggregate_verify_distinct(amsgs, b"".join(reg_keys[x] if x < len(reg_keys) else reg_keys[0] for x in akidx), asig, sizes, flags=1)
+            for a in range(len(sizes)):
+                if (got_k[a] in (0, 9) if a in oob_agg else got_k[a] != got_u[a]):
+                    raise SoakMismatch("MISMATCH keyed / unkeyed aggregates over distinct messages round %d aggregate %d got %d unkeyed %d" % (rounds, a, got_k[a], got_u[a]))
+            gp, mfl = rnd.choice([1, 100, 200, 1024, 4096]), rnd.choice([0, 0x100, 0x200])
+            eng.set_option(OPT_AGG_RAND_MIN_PAIRS, 0)
+            eng.set_option(OPT_AGG_RAND_GROUP_PAIRS, gp)
+            got_r = eng.batch_aggregate_verify_distinct_keyed_randomized(amsgs, akidx, asig, sizes, rnd.randbytes(32), flags=mfl)
+            hook = eng.debug_agg_rand_last()
+            eng.set_option(OPT_AGG_RAND_MIN_PAIRS, ws_default("AGG_RAND_MIN_PAIRS_DEFAULT"))
+            eng.set_option(OPT_AGG_RAND_GROUP_PAIRS, ws_default("AGG_RAND_GROUP_PAIRS_DEFAULT"))
+            if got_r != got_k:
+                bad = [a for a in range(len(sizes)) if got_r[a] != got_k[a]]
+                raise SoakMismatch("MISMATCH randomised keyed aggregates round %d group pairs %d flags %x %r %r" % (rounds, gp, mfl, bad[:5], [(got_r[a], got_k[a]) for a in bad[:5]]))
+            model = grouping_from_statuses([(amsgs[o:o + k], None, akidx[o:o + k]) for o, k in zip([sum(sizes[:a]) for a in range(len(sizes))], sizes)], got_k, key_inf, gp)
+            if hook["ran"] != 1 or {f: hook[f] for f in HOOK_FIELDS} != model:
+                raise SoakMismatch("MISMATCH randomised keyed aggregates round %d group pairs %d flags %x: the device did %r, the model says %r" % (rounds, gp, mfl, hook, model))
+            extra["aggd_keyed_aggregates"] = extra.get("aggd_keyed_aggregates", 0) + len(sizes)
+            extra["aggd_keyed_groups"] = extra.get("aggd_keyed_groups", 0) + model["groups"]
+            extra["aggd_keyed_failed_groups"] = extra.get("aggd_keyed_failed_groups", 0) + model["failed_groups"]
         if rounds % 8 == 0:
             # pairing API (canonical Gt bytes; both kernel families) and check_public_keys vs the oracle
             m = 24
@@ -361,7 +429,7 @@ def soak(args):
     lib_sha = hashlib.sha256(open(_native.LIB_PATH, "rb").read()).hexdigest()[:16]
     res = {"lib_sha256_16": lib_sha, "rounds": rounds, "tuples": items, "comparisons": items * 2 * 10, "seconds": round(time.time() - t0, 1), "oracle_threads": cores,
            "status_histogram": {str(k): v for k, v in sorted(codes.items())}, "mismatches": 0, "seed": args.seed, "also_compared": extra,
-           "modes": ["exact, key dedup route: n >= 16 385 on the device entry point over repeated mutated keys, and the same with it off (every eighth round)", "exact, the batch in three slices inside the library (BN254_OPT_MAX_CHUNK)", "aggregate verify on registered pools (every eighth round)", "keyed (registered keys, once per round with the subgroup check)", "keyed randomised 128-bit / 64-bit / GLV (once per round)", "exact, defaults (lane machine up to 1536, eight wave roles above; final exponentiation on nine lane pairs up to 3072)", "exact, Miller loop as the lane machine at every size", "exact, eight wave roles + final exponentiation on nine lane pairs", "... + octet final exponentiation", "... + nine lane pairs at every size", "exact, four wave roles", "exact, lane groups of one wave (octet)", "exact on lane pairs", "exact, one lane per verify", "randomised 128-bit", "randomised GLV", "randomised 64-bit"],
+           "modes": ["exact, key dedup route: n >= 16 385 on the device entry point over repeated mutated keys, and the same with it off (every eighth round)", "exact, the batch in three slices inside the library (BN254_OPT_MAX_CHUNK)", "aggregate verify on registered pools (every eighth round)", "aggregates over distinct messages: unkeyed with the subgroup check, keyed, randomised keyed with the device counters against the model (every eighth round)", "keyed (registered keys, once per round with the subgroup check)", "keyed randomised 128-bit / 64-bit / GLV (once per round)", "exact, defaults (lane machine up to 1536, eight wave roles above; final exponentiation on nine lane pairs up to 3072)", "exact, Miller loop as the lane machine at every size", "exact, eight wave roles + final exponentiation on nine lane pairs", "... + octet final exponentiation", "... + nine lane pairs at every size", "exact, four wave roles", "exact, lane groups of one wave (octet)", "exact on lane pairs", "exact, one lane per verify", "randomised 128-bit", "randomised GLV", "randomised 64-bit"],
            "flags": [0, 1]}
     return res
 

@@ -15,10 +15,10 @@ import re
 import pytest
 
 from bn254_amd import _native
+from tests import aggr_model as AM
+from tests.aggr_model import LAMBDA, R, model, r_model  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-R = 0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001
-LAMBDA = 0xb3c4d79d41a917585bfc41088d8daaa78b17ea66b99c90dd        # BN254_FLAG_RAND_GLV's eigenvalue (include/bn254_hip.h)
 SRC = os.path.join(ROOT, "tests", "hostsim", "hostsim_aggd_rand.cpp")
 NAMES = ["bn254_batch_aggregate_verify_distinct_keyed_randomized", "bn254_batch_aggregate_verify_distinct_keyed_randomized_device"]
 
@@ -36,19 +36,20 @@ def _decl(name):
 
 
 def test_declared_and_registered():
-    for name in NAMES + ["bn254_debug_agg_rand_last"]:
+    for name in NAMES + ["bn254_debug_agg_rand_last", "bn254_debug_agg_rand_sums"]:
         assert _decl(name), name
         assert name in _native.EXPORTED_SYMBOLS, name
     host, dev = _decl(NAMES[0]).group(1), _decl(NAMES[1]).group(1)
     assert _arity(host) == 11 and _arity(dev) == 12
     assert "const uint8_t *seed32" in host and "const uint8_t *seed32" in dev and "const uint32_t *d_key_idx" in dev
     assert _arity(_decl("bn254_debug_agg_rand_last").group(1)) == 2
+    assert _arity(_decl("bn254_debug_agg_rand_sums").group(1)) == 10
 
 
 def test_exported_by_the_library():
     _native.build()
     lib = _native.load()
-    for name in NAMES + ["bn254_debug_agg_rand_last"]:
+    for name in NAMES + ["bn254_debug_agg_rand_last", "bn254_debug_agg_rand_sums"]:
         assert hasattr(lib, name), name
         assert len(getattr(lib, name).argtypes) == _arity(_decl(name).group(1)), name
 
@@ -88,17 +89,6 @@ def test_api_rejects_bad_input_before_the_device(monkeypatch):
 
 # ---- the G1 side and the group checks against the oracle ---------------------------------------------------------------------------------
 MODES = [(0, "rand128"), (1, "rand64"), (2, "glv")]
-
-
-def r_model(seed, i, mode):
-    """the header's r_i: SHA-256(seed32 || le64(i)) read little-endian, 16 bytes (RAND64: 8), 0 -> 1; GLV: k1 + k2 lambda mod r with k1, k2
-    the two 64-bit halves"""
-    d = hashlib.sha256(seed + i.to_bytes(8, "little")).digest()
-    if mode == 2:
-        k1, k2 = int.from_bytes(d[:8], "little"), int.from_bytes(d[8:16], "little")
-        return (k1 or (0 if k2 else 1)) + k2 * LAMBDA
-    r = int.from_bytes(d[:8 if mode == 1 else 16], "little")
-    return r or 1
 
 
 @pytest.fixture(scope="module")
@@ -173,40 +163,6 @@ def batch():
     return pks, hs, kidx, sigs, off
 
 
-def model(c, pks, hs, kidx, sigs, off, seed, mode, group_pairs):
-    """the header's group rule from the oracle: per group the bucket sums of r_i H(m_j) by key, S_g = sum r_i sigma_i, and
-    pairing_check over (non-empty key buckets, S_g) against (their keys, -G2)"""
-    K, m, n = len(pks), len(hs), len(sigs)
-    G = max(group_pairs, K)
-    ng = m // G + 1
-    neg_g2 = c.g2_mul(c.g2_generator(), (R - 1).to_bytes(32, "big"))
-    nagg = [0] * ng
-    for i in range(n):
-        nagg[off[i] // G] += 1
-    sums, cnt = [bytes(64)] * (ng * (K + 1)), [0] * (ng * (K + 1))
-    for i in range(n):
-        g = off[i] // G
-        r = 1 if nagg[g] == 1 else r_model(seed, i, mode) % R
-        for j in range(off[i], off[i + 1]):
-            if pks[kidx[j]] != bytes(128):
-                b = g * (K + 1) + kidx[j]
-                sums[b] = c.g1_add(sums[b], c.g1_mul(hs[j], r.to_bytes(32, "big")))
-                cnt[b] += 1
-        b = g * (K + 1) + K
-        sums[b] = c.g1_add(sums[b], c.g1_mul(sigs[i], r.to_bytes(32, "big")))
-    verdict, pairs = [], 0
-    for g in range(ng):
-        if not nagg[g]:
-            verdict.append(255)
-            continue
-        keys = [k for k in range(K) if cnt[g * (K + 1) + k]]
-        pairs += len(keys) + 1
-        g1s = b"".join(sums[g * (K + 1) + k] for k in keys) + sums[g * (K + 1) + K]
-        g2s = b"".join(pks[k] for k in keys) + neg_g2
-        verdict.append(c.pairing_check(g1s, g2s, len(keys) + 1))
-    return sums, verdict, pairs
-
-
 @pytest.mark.parametrize("build", ["plain", "bounds"])
 @pytest.mark.parametrize("mode,name", MODES)
 def test_buckets_and_group_verdicts_against_the_oracle(libs, batch, build, mode, name):
@@ -233,3 +189,61 @@ def test_buckets_and_group_verdicts_against_the_oracle(libs, batch, build, mode,
             assert off[8] // G == 3 and off[7] // G == 2 and off[9] - off[8] == 300
         else:
             assert want == [9], want                                    # one group: the wrong sigma fails it
+
+
+def test_grouping_model_against_the_harness(libs, batch):
+    """tests/aggr_model.py: grouping() — what bn254_debug_agg_rand_last must report — against the harness' table pairs and group verdicts
+    on the batch above (aggregate 2 is the only wrong one), two group sizes; and with aggregates taken off the check, against model()"""
+    from oracle import c_oracle as c
+    lib = libs["plain"]
+    pks, hs, kidx, sigs, off = batch
+    K, m, n = len(pks), len(hs), len(sigs)
+    sizes = [off[i + 1] - off[i] for i in range(n)]
+    key_inf = [p == bytes(128) for p in pks]
+    seed = hashlib.sha256(b"aggdr/grouping").digest()
+    for gp, want in ((16, dict(groups=3, failed_groups=1, rechecked=5, single_groups=1)), (1024, dict(groups=1, failed_groups=1, rechecked=9, single_groups=0))):
+        ng = m // max(gp, K) + 1
+        buckets, verdict, tp = ctypes.create_string_buffer(64 * ng * (K + 1)), ctypes.create_string_buffer(ng), ctypes.c_uint64()
+        rc = lib.har_groups(ctypes.c_size_t(K), b"".join(pks), ctypes.c_size_t(m), b"".join(hs), (ctypes.c_uint32 * m)(*kidx), ctypes.c_size_t(n),
+                            (ctypes.c_uint64 * (n + 1))(*off), b"".join(sigs), seed, 0, ctypes.c_uint64(gp), buckets, verdict, ctypes.byref(tp))
+        assert rc == 0
+        got = AM.grouping(sizes, [True] * n, [i == 2 for i in range(n)], kidx, key_inf, K, gp)
+        members = AM.groups_of(sizes, [True] * n, K, gp)
+        assert got["table_pairs"] == tp.value and got["groups"] == len([v for v in verdict.raw if v != 255]), (gp, got)
+        assert got["failed_groups"] == len([g for g, a in members.items() if len(a) >= 2 and verdict.raw[g] == 9]), (gp, got)
+        assert got["rechecked"] == sum(len(a) for g, a in members.items() if len(a) >= 2 and verdict.raw[g] == 9), (gp, got)
+        assert {k: got[k] for k in want} == want, (gp, got)
+    # aggregates 1 and 6 off the check: group 0 loses key 3's bucket, group 2 keeps 5 and 7; model() with at_check counts the same pairs
+    at = [i not in (1, 6) for i in range(n)]
+    got = AM.grouping(sizes, at, [i == 2 for i in range(n)], kidx, key_inf, K, 16)
+    sums, verdict, pairs = model(c, pks, hs, kidx, sigs, off, seed, 0, 16, at_check=at)
+    assert got == dict(groups=3, table_pairs=pairs, failed_groups=1, rechecked=4, single_groups=1), (got, pairs)
+    assert verdict[:4] == [9, 255, 0, 0] and sums[0 * (K + 1) + 3] == bytes(64) and sums[2 * (K + 1) + 4] == bytes(64)
+
+
+def test_gpu_batch_plans_meet_their_conditions():
+    """the batches of tests/test_gpu_aggregate_distinct_keyed_randomized_groups.py: in every 'passing' one at least half of the counted
+    groups hold two or more aggregates at the check; in the interleaved one a quarter of the aggregates are off the check and a quarter of
+    the passing groups contain one; the localised failures fail some groups and not all; the run lengths meet every edge of a workgroup"""
+    from tests.conftest import ws_default
+    AM.check_runs(ws_default("AGGR_SUM_WG"))
+    assert sorted(set(len([k for k in a.kidx if k != AM.KIDX_IDENT]) for a in AM.ragged_plan())) == AM.SIZES
+    for gp in AM.GROUP_PAIRS:
+        AM.check_passing(AM.ragged_plan(), gp)
+        AM.check_passing(AM.runs_plan(), gp)
+        AM.check_passing(AM.interleaved_plan(), gp, interleaved=True)
+        AM.check_passing(AM.interleaved_plan(), gp, interleaved=True, reject_identity=True)
+        for plan in (AM.failing_plan(gp),) + ((AM.cancelling_plan(gp),) if gp != 4096 else ()):   # 4 096: one group
+            w = AM.plan_grouping(plan, gp)
+            assert 1 <= w["failed_groups"] and (gp == 4096 or w["failed_groups"] < w["groups"] - w["single_groups"]), (gp, w)
+    assert AM.plan_grouping(AM.cancelling_plan(1), 1)["failed_groups"] == 2
+    for G in (AM.N_KEYS, 200):
+        plan = AM.edges_plan(G)
+        sizes = [len(a.msgs) for a in plan]
+        assert sum(sizes) == 6 * G and sizes[-3:] == [0, 0, 0]
+        assert sorted(AM.groups_of(sizes, [True] * len(plan), AM.N_KEYS, G)) == [0, 1, 3, 4, 5, 6]
+        AM.check_passing(plan, G)
+    for nb in (False, True):
+        plan = AM.repeated_plan([2, 3, 4, 255, 256, 257, 513], nb)
+        w = AM.plan_grouping(plan, 1)
+        assert w["groups"] == 7 and w["single_groups"] == (0 if nb else 7), w

@@ -8,6 +8,7 @@ import os
 import pytest
 
 from bn254_amd import engine as E
+from tests.aggr_model import HOOK_FIELDS, KEY_INF, grouping, grouping_from_statuses
 from tests.conftest import ws_default
 from tests.datagen import D
 from tests.test_gpu_aggregate_distinct import g1_sum, sign_all
@@ -55,7 +56,10 @@ def test_ragged_same_bytes_as_the_exact_call(eng, c, keyset, ragged70):  # noqa:
                 for name, mf in MODES:
                     got = rand(eng, ragged70, seed, f | mf)
                     assert got == want, (f, gp, name, diff(got, want))
-                    assert eng.debug_agg_rand_last()["ran"] == 1
+                    h = eng.debug_agg_rand_last()
+                    assert h["ran"] == 1
+                    model = grouping_from_statuses(ragged70, want, KEY_INF, gp)      # the counters from the header's rule
+                    assert {k: h[k] for k in HOOK_FIELDS} == model, (f, gp, name, h, model)
 
 
 def test_reject_identity_and_hash_failures(eng, c, keyset, ragged70):  # noqa: F811
@@ -196,6 +200,9 @@ def test_k1_equals_batch_verify_keyed(eng):
         eng.set_option(E.OPT_AGG_RAND_GROUP_PAIRS, gp)
         got = eng.batch_aggregate_verify_distinct_keyed_randomized(msgs, kidx, sig, [1] * n, SEEDS[0])
         assert got == want, (gp, diff(got, want))
+        h = eng.debug_agg_rand_last()
+        model = grouping([1] * n, [s in (0, 9) for s in want], [s == 9 for s in want], kidx, [False] * 256 + [True], 257, gp)
+        assert h["ran"] == 1 and {k: h[k] for k in HOOK_FIELDS} == model, (gp, h, model)
 
 
 def test_device_form(eng, keyset):  # noqa: F811

@@ -486,15 +486,19 @@ static int kd_reserve(bn254_ctx* c, size_t n, KeyDedup& kd) {
   kd.min_mult = (uint32_t)c->kd_min_mult;
   return 0;
 }
+int scratch_reserve(bn254_ctx* c, uint8_t** buf, size_t* cap, size_t bytes) {
+  if (bytes <= *cap) return 0;
+  { int rc_ = ctx_quiesce(c); if (rc_) return rc_; }
+  if (*buf) { HIP_TRY(hipFree(*buf)); *buf = nullptr; *cap = 0; }
+  const size_t grown = (bytes + 4095) & ~(size_t)4095;
+  HIP_TRY(hipMalloc((void**)buf, grown));
+  *cap = grown;
+  return 0;
+}
 int stage_reserve(bn254_ctx* c, int slot, size_t bytes) {
   if (bytes <= c->stage_cap[slot]) return 0;
   HIP_TRY(hipSetDevice(c->device));
-  { int rc_ = ctx_quiesce(c); if (rc_) return rc_; }
-  if (c->stage[slot]) { HIP_TRY(hipFree(c->stage[slot])); c->stage[slot] = nullptr; c->stage_cap[slot] = 0; }
-  size_t cap = (bytes + 4095) & ~(size_t)4095;
-  HIP_TRY(hipMalloc((void**)&c->stage[slot], cap));
-  c->stage_cap[slot] = cap;
-  return 0;
+  return scratch_reserve(c, &c->stage[slot], &c->stage_cap[slot], bytes);
 }
 uint8_t* HostStaging::out(int slot, size_t bytes, void* host) {
   if (!rc) rc = stage_reserve(c, slot, bytes);

@@ -68,7 +68,7 @@ struct bn254_ctx {
   int max_chunk;             // BN254_OPT_MAX_CHUNK: verify-shaped batches above this size are processed in slices (0 = only when the workspace would not fit)
   int assume_free_mb;        // test knob (BN254_OPT_ASSUME_FREE_MB): the automatic rule prices the workspace against this much free memory instead of hipMemGetInfo
   bool fits_w8, fits_quad, fits_trio;   // the device can hold a workgroup of the small-batch kernels (LDS), asked at creation
-  uint8_t* aggd_buf;         // aggregate verify over distinct messages: the per-aggregate scans, the slot map and the partials' ids (bn254_aggdist.hip)
+  uint8_t* aggd_buf;         // aggregate verify over distinct messages: the per-aggregate scans, the slot map and the partials' ids (bn254_aggd_plan.h: AggdScratch)
   size_t aggd_cap;
   int key_dedup;             // BN254_OPT_KEY_DEDUP: verify on lane pairs finds the batch's distinct keys and runs the keyed Miller loop (bn254_keydedup.hip)
   int kd_max_keys;           // BN254_OPT_KEY_DEDUP_MAX_KEYS
@@ -84,7 +84,7 @@ struct bn254_ctx {
   int aggd_keyed_route;      // BN254_OPT_AGGD_KEYED_ROUTE (test and measurement knob): 0 by size, 1 / 2 the slot kernel of that width, 3 expanded keys
   int agg_rand_min_pairs;    // BN254_OPT_AGG_RAND_MIN_PAIRS: the randomised keyed aggregate verify from this many messages on
   int agg_rand_group_pairs;  // BN254_OPT_AGG_RAND_GROUP_PAIRS: messages per group of its combined checks (at least the number of keys)
-  uint8_t* aggr_buf;         // ... its scratch (bn254_aggdist.hip: aggr_device), grown on demand
+  uint8_t* aggr_buf;         // ... its scratch (bn254_aggd_plan.h: AggrScratch), grown on demand
   size_t aggr_cap;
   uint32_t* aggr_stats;      // ... what its last run did on the device (bn254_debug_agg_rand_last)
   int aggr_last_ran;         // ... and whether the last call took the randomised route at all
@@ -152,6 +152,9 @@ template <class Slice> static inline int verify_device_sliced(size_t n, size_t c
     if (const int rc = slice(lo, n - lo < chunk ? n - lo : chunk)) return rc;
   return 0;
 }
+// a device buffer of the context grown on demand to at least `bytes` (quiesce, free, allocate a multiple of 4 096): the staging slots,
+// and the scratch of the aggregate calls over distinct messages (aggd_buf, aggr_buf)
+BN_HIDDEN int scratch_reserve(bn254_ctx* c, uint8_t** buf, size_t* cap, size_t bytes);
 BN_HIDDEN int stage_reserve(bn254_ctx* c, int slot, size_t bytes);
 BN_HIDDEN int pool_reserve(bn254_ctx* c, int which, size_t n_fp, size_t entries);
 BN_HIDDEN int pool_reserve_one(bn254_ctx* c, Pool* p, size_t n_fp, size_t entries);

@@ -262,6 +262,38 @@ int hs_g2_add(const uint8_t* a, const uint8_t* b, uint8_t* out) {
   memcpy(out, tmp, 128);
   return st;
 }
+// jac_add on operands given in JACOBIAN coordinates (X, Y, Z big-endian; g2: each an Fq2, re || im): any Z = 0 triple is the identity and
+// a point has many representatives (l^2 x, l^3 y, l) — forms the byte decoders never produce but jac_add's contract covers
+int hs_jac_add_raw(int g2, const uint8_t* p, const uint8_t* q, uint8_t* out) {
+  alignas(4) uint8_t tp[192], tq[192], to[128];
+  const int len = g2 ? 192 : 96;
+  memcpy(tp, p, len); memcpy(tq, q, len);
+  uint32_t any = 0;
+  if (g2) {
+    G2Jac a, b, o;
+    Fp2* ca[3] = {&a.x, &a.y, &a.z};
+    Fp2* cb[3] = {&b.x, &b.y, &b.z};
+    for (int k = 0; k < 3; ++k) {
+      fp_from_be(ca[k]->c0, tp + 64 * k, any); fp_from_be(ca[k]->c1, tp + 64 * k + 32, any);
+      fp_from_be(cb[k]->c0, tq + 64 * k, any); fp_from_be(cb[k]->c1, tq + 64 * k + 32, any);
+    }
+    jac_add(o, a, b);
+    G2Affine r;
+    jac_to_affine(r, o);
+    encode_g2(to, r);
+  } else {
+    G1Jac a, b, o;
+    Fp* ca[3] = {&a.x, &a.y, &a.z};
+    Fp* cb[3] = {&b.x, &b.y, &b.z};
+    for (int k = 0; k < 3; ++k) { fp_from_be(*ca[k], tp + 32 * k, any); fp_from_be(*cb[k], tq + 32 * k, any); }
+    jac_add(o, a, b);
+    G1Affine r;
+    jac_to_affine(r, o);
+    encode_g1(to, r);
+  }
+  memcpy(out, to, g2 ? 128 : 64);
+  return 0;
+}
 // k * P with the 128-bit windowed ladder of the randomised batch verification (k: 16 bytes little-endian)
 int hs_g1_mul_u128(const uint8_t* p, const uint8_t* k16, uint8_t* out) {
   G1Affine a, o;
@@ -364,9 +396,15 @@ int hs_g1_msum(const uint8_t* pts, uint64_t k, uint8_t* out) {
   G1Jac acc;
   jac_set_identity(acc);
   uint8_t st = ST_OK;
-  for (uint64_t j = 0; j < k; ++j) { G1Affine p; uint8_t s = dec_g1(p, pts + 64 * j, 0); if (st == ST_OK) st = s; jac_accumulate(acc, p); }
+  for (uint64_t j = 0; j < k; ++j) {                 // as k_g1_sum: an invalid point is skipped, the first error is the segment's status
+    G1Affine p;
+    uint8_t s = dec_g1(p, pts + 64 * j, 0);
+    if (s != ST_OK) { if (st == ST_OK) st = s; continue; }
+    jac_accumulate(acc, p);
+  }
   G1Affine r;
   jac_to_affine(r, acc);
+  if (st != ST_OK) r.inf = true;
   alignas(4) uint8_t tmp[64];
   encode_g1(tmp, r);
   memcpy(out, tmp, 64);
@@ -376,13 +414,46 @@ int hs_g2_msum(const uint8_t* pts, uint64_t k, uint8_t* out) {
   G2Jac acc;
   jac_set_identity(acc);
   uint8_t st = ST_OK;
-  for (uint64_t j = 0; j < k; ++j) { G2Affine p; uint8_t s = dec_g2(p, pts + 128 * j, 0); if (st == ST_OK) st = s; jac_accumulate(acc, p); }
+  for (uint64_t j = 0; j < k; ++j) {                 // as k_g2_sum
+    G2Affine p;
+    uint8_t s = dec_g2(p, pts + 128 * j, 0);
+    if (s != ST_OK) { if (st == ST_OK) st = s; continue; }
+    jac_accumulate(acc, p);
+  }
   G2Affine r;
   jac_to_affine(r, acc);
+  if (st != ST_OK) r.inf = true;
   alignas(4) uint8_t tmp[128];
   encode_g2(tmp, r);
   memcpy(out, tmp, 128);
   return st;
+}
+// op codes as bn254_debug_fp12_op (k_debug_fp12_op, bn254_devhooks.hip); b == nullptr: the second operand is one
+int hs_fp12_op(int op, const uint8_t* a, const uint8_t* b, uint8_t* out) {
+  alignas(4) uint8_t ta[384], tb[384], to[384];
+  memcpy(ta, a, 384);
+  if (b) memcpy(tb, b, 384);
+  Fp12 x, y, r;
+  uint32_t any = 0;
+  Fp2* cx[6] = {&x.c0.c0, &x.c0.c1, &x.c0.c2, &x.c1.c0, &x.c1.c1, &x.c1.c2};
+  Fp2* cy[6] = {&y.c0.c0, &y.c0.c1, &y.c0.c2, &y.c1.c0, &y.c1.c1, &y.c1.c2};
+  for (int k = 0; k < 6; ++k) { fp_from_be(cx[k]->c0, ta + 64 * k, any); fp_from_be(cx[k]->c1, ta + 64 * k + 32, any); }
+  if (b) { for (int k = 0; k < 6; ++k) { fp_from_be(cy[k]->c0, tb + 64 * k, any); fp_from_be(cy[k]->c1, tb + 64 * k + 32, any); } }
+  else fp12_set_one(y);
+  switch (op) {
+    case 0: fp12_mul(r, x, y); break;
+    case 1: fp12_sqr(r, x); break;
+    case 2: fp12_inv(r, x); break;
+    case 3: fp12_conj(r, x); break;
+    case 4: fp12_frob(r, x, 1); break;
+    case 5: fp12_frob(r, x, 2); break;
+    case 6: fp12_frob(r, x, 3); break;
+    case 7: fp12_cyclotomic_sqr(r, x); break;
+    default: { Fp12 acc; final_exponentiation(r, x, acc); } break;
+  }
+  encode_fp12(to, r);
+  memcpy(out, to, 384);
+  return 0;
 }
 // deliberately unsafe sequences: the bound-tracking build must abort on them (tests/test_bounds.py)
 int hs_unsafe_sequence(int which) {

@@ -33,6 +33,8 @@ def lib():
             getattr(L, f).argtypes = [cp, cp, ctypes.c_int, cp]
         L.hs_sign.argtypes = [cp, ctypes.c_uint64, cp, cp]
         L.hs_fp_op.argtypes = [ctypes.c_int, cp, cp, cp]
+        L.hs_fp12_op.argtypes = [ctypes.c_int, cp, cp, cp]
+        L.hs_jac_add_raw.argtypes = [ctypes.c_int, cp, cp, cp]
         L.hs_g1_decompress.argtypes = [cp, cp]
         L.hs_g1_msum.argtypes = [cp, ctypes.c_uint64, cp]
         L.hs_g2_msum.argtypes = [cp, ctypes.c_uint64, cp]
@@ -75,6 +77,11 @@ def g2_add(a, b):
     o = _b(128); st = lib().hs_g2_add(bytes(a), bytes(b), o); return st, o.raw
 
 
+def jac_add_raw(g2, p, q):
+    """jac_add on Jacobian triples X || Y || Z (32 bytes per Fq, re || im per Fq2) -> the affine encoding of the sum"""
+    o = _b(128 if g2 else 64); lib().hs_jac_add_raw(int(g2), bytes(p), bytes(q), o); return o.raw
+
+
 def g1_mul(p, k, reduce=False):
     o = _b(64); st = lib().hs_g1_mul(bytes(p), bytes(k), int(reduce), o); return st, o.raw
 
@@ -103,6 +110,11 @@ def sign(msg, sk):
 
 def fp_op(op, a, b=None):
     o = _b(32); st = lib().hs_fp_op(op, bytes(a), None if b is None else bytes(b), o); return st, o.raw
+
+
+def fp12_op(op, a, b=None):
+    """op numbering of bn254_debug_fp12_op: 0 mul, 1 sqr, 2 inv, 3 conj, 4..6 frob^1..3, 7 cyclotomic sqr, 8 final exponentiation"""
+    o = _b(384); lib().hs_fp12_op(op, bytes(a), None if b is None else bytes(b), o); return o.raw
 
 
 def g1_decompress(c33):

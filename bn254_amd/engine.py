@@ -484,6 +484,11 @@ class Engine:
         _check("bn254_batch_verify_device",
                self._lib.bn254_batch_verify_device(self._h, d_msgs, d_off, d_sigs, d_pks, n, flags, d_status, stream))
 
+    def batch_verify_compressed_device(self, d_msgs, d_off, d_sigs33, d_pks65, n, d_status, stream=None):
+        """batch_verify_device from the compressed encodings (33-byte signatures, 65-byte public keys, any byte alignment)"""
+        _check("bn254_batch_verify_compressed_device",
+               self._lib.bn254_batch_verify_compressed_device(self._h, d_msgs, d_off, d_sigs33, d_pks65, n, d_status, stream))
+
     def batch_verify_randomized_device(self, d_msgs, d_off, d_sigs, d_pks, n, seed32, d_status, d_group_ok=None, flags=0, stream=None):
         assert len(seed32) == 32
         _check("bn254_batch_verify_randomized_device",

@@ -391,6 +391,17 @@ int hs_g2_decompress(const uint8_t* in65, uint8_t* out128) {
   memcpy(out128, tmp, 128);
   return st;
 }
+// decompress_g2's own status and point: BEFORE the subgroup test and before a failed item is replaced by the generator — the only place
+// where the root and the sign choice of an x outside the subgroup can be seen (tests/codec_cases.py: pre).  out = x || y as the decoder
+// holds them; y means something only where a root exists
+int hs_g2_decompress_raw(const uint8_t* in65, uint8_t* out128) {
+  G2Affine p;
+  uint8_t st = decompress_g2(p, in65);
+  alignas(4) uint8_t tmp[128];
+  encode_g2(tmp, p);
+  memcpy(out128, tmp, 128);
+  return st;
+}
 // sum of k points through the mixed-addition ladder used by k_aggregate
 int hs_g1_msum(const uint8_t* pts, uint64_t k, uint8_t* out) {
   G1Jac acc;

@@ -365,4 +365,11 @@ int hp_g2_decompress(const uint8_t* c65, uint8_t* out128) {
   if (st == ST_OK) { fp_to_be32(out128, q.x.c[0]); fp_to_be32(out128 + 32, q.x.c[1]); fp_to_be32(out128 + 64, q.y.c[0]); fp_to_be32(out128 + 96, q.y.c[1]); }
   return st;
 }
+// ... and the decoder's own status and point in this layout, before the subgroup test (hostsim.cpp: hs_g2_decompress_raw)
+int hp_g2_decompress_raw(const uint8_t* c65, uint8_t* out128) {
+  G2Affine q;
+  uint8_t st = decompress_g2(q, c65);
+  fp_to_be32(out128, q.x.c[0]); fp_to_be32(out128 + 32, q.x.c[1]); fp_to_be32(out128 + 64, q.y.c[0]); fp_to_be32(out128 + 96, q.y.c[1]);
+  return st;
+}
 }  // extern "C"

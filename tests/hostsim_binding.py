@@ -39,6 +39,7 @@ def lib():
         L.hs_g1_msum.argtypes = [cp, ctypes.c_uint64, cp]
         L.hs_g2_msum.argtypes = [cp, ctypes.c_uint64, cp]
         L.hs_g2_decompress.argtypes = [cp, cp]
+        L.hs_g2_decompress_raw.argtypes = [cp, cp]
         L.hs_g1_mul_u128.argtypes = [cp, cp, cp]
         L.hs_verify_randomized.argtypes = [cp, ctypes.POINTER(ctypes.c_uint64), cp, cp, ctypes.c_uint64, ctypes.c_uint32, cp, cp, cp]
         _lib = L
@@ -123,6 +124,30 @@ def g1_decompress(c33):
 
 def g2_decompress(c65):
     o = _b(128); st = lib().hs_g2_decompress(bytes(c65), o); return st, o.raw
+
+
+def g2_decompress_raw(c65):
+    """decompress_g2's own (status, x || y): before the subgroup test and the generator substitution"""
+    o = _b(128); st = lib().hs_g2_decompress_raw(bytes(c65), o); return st, o.raw
+
+
+_pair = None
+
+
+def pair_lib():
+    """the pair-layout host build (tests/hostsim/hostsim_pair.cpp)"""
+    global _pair
+    if _pair is None:
+        build_all()
+        _pair = ctypes.CDLL(os.path.join(_HERE, "libhostsim_pair.so"))
+        for f in ("hp_g2_decompress", "hp_g2_decompress_raw"):
+            getattr(_pair, f).argtypes = [ctypes.c_char_p, ctypes.c_char_p]
+    return _pair
+
+
+def pair_g2_decompress(c65, raw=False):
+    """(status, 128 bytes) of the pair layout's decoder; raw: before the subgroup test (hp_g2_decompress_raw)"""
+    o = _b(128); st = getattr(pair_lib(), "hp_g2_decompress_raw" if raw else "hp_g2_decompress")(bytes(c65), o); return st, o.raw
 
 
 def g1_msum(pts):

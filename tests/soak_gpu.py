@@ -311,6 +311,32 @@ def soak(args):
             extra["aggd_keyed_aggregates"] = extra.get("aggd_keyed_aggregates", 0) + len(sizes)
             extra["aggd_keyed_groups"] = extra.get("aggd_keyed_groups", 0) + model["groups"]
             extra["aggd_keyed_failed_groups"] = extra.get("aggd_keyed_failed_groups", 0) + model["failed_groups"]
+        if rounds % 8 == 3:
+            # the same batch from COMPRESSED encodings: what the oracle accepts as points is compressed by the byte rule, every other item gets
+            # a malformed encoding of tests/codec_cases.py in its place; statuses = that builder's, else the oracle's, on all three G2 decoders
+            from tests import codec_cases as cc
+            g1_bad = [cs for cs in cc.g1_cases() if cs.status]
+            g2_bad = [cs for cs in cc.g2_cases(derived["g2_not_in_subgroup"]) if cs.status]
+            s33, p65, cwant = [], [], bytearray(want1)
+            for i in range(n):
+                s, p = sigs[64 * i:64 * i + 64], pks[128 * i:128 * i + 128]
+                points = want1[i] in (0, 9) and s != bytes(64) and p != bytes(128)
+                bad = (rnd.choice(g1_bad) if not points or rnd.randrange(16) == 0 else None, rnd.choice(g2_bad) if not points or rnd.randrange(16) == 1 else None)
+                s33.append(bad[0].enc if bad[0] else cc.g1_compress(s))
+                p65.append(bad[1].enc if bad[1] else cc.g2_compress(p))
+                if bad[0] or bad[1]:
+                    cwant[i] = bad[0].status if bad[0] else bad[1].status
+            s33, p65 = b"".join(s33), b"".join(p65)
+            for name, opt, val, dflt in (("default", OPT_MAX_CHUNK, 0, 0), ("lane pairs", OPT_LM_MAX_BATCH, 0, ws_default("LM_MAX_BATCH_DEFAULT")), ("one lane", OPT_PAIR_LANES, 0, 1)):
+                eng.set_option(opt, val)
+                try:
+                    got_c = eng.batch_verify_compressed(msgs, s33, p65)
+                finally:
+                    eng.set_option(opt, dflt)
+                bad = [i for i in range(n) if got_c[i] != cwant[i]]
+                if bad:
+                    raise SoakMismatch("MISMATCH compressed %s round %d n %d %r %r" % (name, rounds, n, bad[:5], [(got_c[i], cwant[i]) for i in bad[:5]]))
+            extra["compressed_tuples"] = extra.get("compressed_tuples", 0) + n
         if rounds % 8 == 0:
             # pairing API (canonical Gt bytes; both kernel families) and check_public_keys vs the oracle
             m = 24
@@ -429,7 +455,7 @@ def soak(args):
     lib_sha = hashlib.sha256(open(_native.LIB_PATH, "rb").read()).hexdigest()[:16]
     res = {"lib_sha256_16": lib_sha, "rounds": rounds, "tuples": items, "comparisons": items * 2 * 10, "seconds": round(time.time() - t0, 1), "oracle_threads": cores,
            "status_histogram": {str(k): v for k, v in sorted(codes.items())}, "mismatches": 0, "seed": args.seed, "also_compared": extra,
-           "modes": ["exact, key dedup route: n >= 16 385 on the device entry point over repeated mutated keys, and the same with it off (every eighth round)", "exact, the batch in three slices inside the library (BN254_OPT_MAX_CHUNK)", "aggregate verify on registered pools (every eighth round)", "aggregates over distinct messages: unkeyed with the subgroup check, keyed, randomised keyed with the device counters against the model (every eighth round)", "keyed (registered keys, once per round with the subgroup check)", "keyed randomised 128-bit / 64-bit / GLV (once per round)", "exact, defaults (lane machine up to 1536, eight wave roles above; final exponentiation on nine lane pairs up to 3072)", "exact, Miller loop as the lane machine at every size", "exact, eight wave roles + final exponentiation on nine lane pairs", "... + octet final exponentiation", "... + nine lane pairs at every size", "exact, four wave roles", "exact, lane groups of one wave (octet)", "exact on lane pairs", "exact, one lane per verify", "randomised 128-bit", "randomised GLV", "randomised 64-bit"],
+           "modes": ["exact from compressed encodings with malformed ones of tests/codec_cases.py planted, on the three G2 decoders (every eighth round)", "exact, key dedup route: n >= 16 385 on the device entry point over repeated mutated keys, and the same with it off (every eighth round)", "exact, the batch in three slices inside the library (BN254_OPT_MAX_CHUNK)", "aggregate verify on registered pools (every eighth round)", "aggregates over distinct messages: unkeyed with the subgroup check, keyed, randomised keyed with the device counters against the model (every eighth round)", "keyed (registered keys, once per round with the subgroup check)", "keyed randomised 128-bit / 64-bit / GLV (once per round)", "exact, defaults (lane machine up to 1536, eight wave roles above; final exponentiation on nine lane pairs up to 3072)", "exact, Miller loop as the lane machine at every size", "exact, eight wave roles + final exponentiation on nine lane pairs", "... + octet final exponentiation", "... + nine lane pairs at every size", "exact, four wave roles", "exact, lane groups of one wave (octet)", "exact on lane pairs", "exact, one lane per verify", "randomised 128-bit", "randomised GLV", "randomised 64-bit"],
            "flags": [0, 1]}
     return res
 

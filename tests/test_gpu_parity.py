@@ -1586,6 +1586,20 @@ def test_batch_verify_from_compressed_encodings(eng, kats):
     base = eng.batch_verify(msgs, us, up)
     want = bytes(s1[i] or s2[i] or base[i] for i in range(n))
     assert got == want and got[3] == 3 and got[5] == 3 and got[7] == 6 and got[9] == 6 and got[11] in (6, 9)
+    # ... and the same bytes from the big-integer model's decoders, not from the device's: every untouched encoding is a valid point
+    # by construction, the five touched ones go through g1_from_compressed / g2_from_compressed
+    from oracle import bn254_model as m
+
+    def model_status(fn, enc):
+        try:
+            fn(bytes(enc))
+            return 0
+        except m.Bn254Error as e:
+            return e.code
+    m1 = {i: model_status(m.g1_from_compressed, sc[33 * i:33 * i + 33]) for i in (3, 7, 9)}
+    m2 = {i: model_status(m.g2_from_compressed, pc[65 * i:65 * i + 65]) for i in (5, 11)}
+    assert got == bytes(m1.get(i) or m2.get(i) or expected[i] for i in range(n))
+    assert all(s1[i] == m1.get(i, 0) and s2[i] == m2.get(i, 0) for i in range(n))
     # the reference's own compressed KAT decodes and verifies
     v = kats["sign"][0]
     pk = PublicKey.from_private_key(__import__("bn254_amd").PrivateKey.try_from(v["private_key"]))

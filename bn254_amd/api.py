@@ -283,6 +283,44 @@ class ECDSA:
         return [None if s == 0 else Error(s) for s in st]
 
     @staticmethod
+    def verify_keyed_signers(message, signature, signer_indices, engine=None):
+        """One message, one already aggregated signature, and the indices (in the registered set, ECDSA.register_keys) of the keys that
+        signed: None iff e(H(message), sum of those keys) * e(signature, -G2) == 1; raises Error(IndexOutOfBounds) for an index outside
+        the set, a refused key's registration Error, else what verify raises (include/bn254_hip.h: bn254_batch_verify_keyed_bitmap).
+        Assumes a proof of possession of every registered key."""
+        _raise(ECDSA._keyed_signers_status([(message, signature, signer_indices)], engine)[0])
+
+    @staticmethod
+    def _keyed_signers_status(items, engine):
+        rows = []
+        for item in items:
+            if len(item) != 3 or len(item[1].raw) != _engine.G1_BYTES:
+                raise Error(ErrorKind.InvalidLength)
+            message, signature, signer_indices = item
+            idx = [int(j) for j in signer_indices]
+            if any(j < 0 for j in idx):
+                raise Error(ErrorKind.IndexOutOfBounds)
+            rows.append((bytes(message), signature.raw, idx))
+        eng = engine or _eng()
+        # the bitmaps: as wide as the registered set plus ONE bit, on which every index outside the set lands (rule 2 reports the lowest bad
+        # bit, and every such index lies above the set); an engine that does not know its set: as wide as the largest index
+        n_keys = getattr(eng, "n_registered_keys", None)
+        top = n_keys if n_keys is not None else max([j for _, _, idx in rows for j in idx], default=-1)
+        bm_words = top // 32 + 1
+        bits = [0] * (len(rows) * bm_words)
+        for i, (_, _, idx) in enumerate(rows):
+            for j in idx:
+                j = min(j, top)
+                bits[i * bm_words + j // 32] |= 1 << (j % 32)
+        return eng.batch_verify_keyed_bitmap([r[0] for r in rows], b"".join(r[1] for r in rows), bits, bm_words)
+
+    @staticmethod
+    def batch_verify_keyed_signers(items, engine=None):
+        """items: a list of (message, signature, signer_indices); result[i] is None iff ECDSA.verify_keyed_signers on item i succeeds, else
+        the Error it would raise.  An item that is not such a triple raises Error(InvalidLength) before any device work."""
+        return [None if s == 0 else Error(s) for s in ECDSA._keyed_signers_status(items, engine)]
+
+    @staticmethod
     def batch_verify_keyed_randomized(messages, signatures, key_indices, seed=None, engine=None, rand64=False):
         """batch_verify_keyed through the combined check of items that share a key (64 per pairing product; include/bn254_hip.h:
         bn254_batch_verify_keyed_randomized).  Errors are exact; a None is wrong with probability <= 2^-128 per group."""

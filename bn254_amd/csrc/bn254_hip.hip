@@ -682,6 +682,7 @@ int bn254_ctx_create(int hip_device, bn254_ctx** out) {
   c->key_dedup = 1;
   c->kd_max_keys = KEY_DEDUP_MAX_KEYS_DEFAULT;
   c->kd_min_mult = KEY_DEDUP_MIN_MULT_DEFAULT;
+  c->bm_table_max_keys = BITMAP_TABLE_MAX_KEYS_DEFAULT;
   c->device = hip_device;
   hipError_t err = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
   if (err == hipSuccess) err = hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking);
@@ -732,6 +733,8 @@ void bn254_ctx_destroy(bn254_ctx* c) {
   if (c->aggr_buf) (void)hipFree(c->aggr_buf);
   if (c->aggr_stats) (void)hipFree(c->aggr_stats);
   if (c->kd_buf) (void)hipFree(c->kd_buf);
+  if (c->bm_bad) (void)hipFree(c->bm_bad);
+  if (c->bm_tab) (void)hipFree(c->bm_tab);
   for (int i = 0; i < 5; ++i) (void)hipEventDestroy(c->ev[i]);
   (void)hipEventDestroy(c->kd_fork);
   (void)hipEventDestroy(c->kd_join);
@@ -830,6 +833,8 @@ int bn254_ctx_set_option(bn254_ctx* c, int option, int value) {
   if (option == BN254_OPT_AGGD_KEYED_ROUTE) { if (value < 0 || value > 3) return BN254_E_BAD_ARGUMENT; c->aggd_keyed_route = value; return 0; }
   if (option == BN254_OPT_AGG_RAND_MIN_PAIRS) { if (value < 0) return BN254_E_BAD_ARGUMENT; c->agg_rand_min_pairs = value; return 0; }
   if (option == BN254_OPT_AGG_RAND_GROUP_PAIRS) { if (value < 1) return BN254_E_BAD_ARGUMENT; c->agg_rand_group_pairs = value; return 0; }
+  if (option == BN254_OPT_BITMAP_TABLE_MAX_KEYS) { if (value < 0) return BN254_E_BAD_ARGUMENT; c->bm_table_max_keys = value; return 0; }
+  if (option == BN254_OPT_BITMAP_ROUTE) { if (value < 0 || value > 2) return BN254_E_BAD_ARGUMENT; c->bm_route = value; return 0; }
   return BN254_E_BAD_ARGUMENT;
 }
 // clock probe (BN254_OPT_CLOCK_PROBE): the clock the chip ran the last Miller kernel [0], final exponentiation [1] and issue probe [2]

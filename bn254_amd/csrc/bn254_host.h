@@ -90,6 +90,15 @@ struct bn254_ctx {
   int aggr_last_ran;         // ... and whether the last call took the randomised route at all
   // ... and where that call left its groups (bn254_debug_agg_rand_sums): S_g in the P1 planes from cbase, the table pairs from tbase, the rest in aggr_buf
   struct { size_t ng, cbase, tbase; const uint32_t *nagg, *bkey; const uint64_t *glo, *ghi; const uint8_t* gst; } aggr_last;
+  // signer bitmaps over the registered keys (bn254_bitmap.hip): the bad-bit vector and the subset tables of the set, built by the first
+  // bitmap call after a registration (bn254_ctx_register_keys clears the two flags), grown on demand
+  uint8_t* bm_bad;           // uint32 words, one bit per key
+  size_t bm_bad_cap;
+  uint8_t* bm_tab;           // records (160 B per entry), then the identity flags (1 B per entry)
+  size_t bm_tab_cap;
+  bool bm_bad_valid, bm_tab_valid;
+  int bm_table_max_keys;     // BN254_OPT_BITMAP_TABLE_MAX_KEYS: tables while n_keys <= this (0 = never)
+  int bm_route;              // BN254_OPT_BITMAP_ROUTE (developer option): 0 by the rule above, 1 always tables, 2 never
 };
 
 struct ScopedEvents {

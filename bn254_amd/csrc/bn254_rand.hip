@@ -348,6 +348,7 @@ int bn254_ctx_register_keys(bn254_ctx* c, const uint8_t* pks, size_t n_keys, uin
   HIP_TRY(hipSetDevice(c->device));
   { int rc_ = ctx_quiesce(c); if (rc_) return rc_; }   // no keyed verify — on c->stream or on the caller's stream of the last call — may still be reading the previous tables
   c->n_keys = 0;
+  c->bm_bad_valid = c->bm_tab_valid = false;          // the bitmap call's bad-bit vector and subset tables belong to the previous set
   if (n_keys == 0) return 0;
   if (n_keys > c->key_cap) {
     if (c->key_lines) { HIP_TRY(hipFree(c->key_lines)); c->key_lines = nullptr; }

@@ -244,6 +244,14 @@ __attribute__((visibility("hidden"))) int bn254_pair_aggd_keyed_queued(size_t n_
                                                                        size_t gbase, size_t pbase, uint32_t* pseg, int last, const uint8_t* queued,
                                                                        hipStream_t s);
 
+// same-message aggregates given as signer bitmaps over the registered keys (bn254_bitmap.hip; lane pairs: bn254_bitmap_pair.hip; the walk:
+// bn254_bitmap.h): tuple i's aggregate key from its bm_words bitmap words into the Q planes at index i, rule 2's status behind the
+// signature's in BY_ST_DECODE.  rec / rec_inf = the subset tables of the registered set, or null: key by key from keys.xy
+#define BITMAP_TABLE_MAX_KEYS_DEFAULT 4096         // BN254_OPT_BITMAP_TABLE_MAX_KEYS: subset tables while the set has at most this many keys (5 152 B per key: 21 MB)
+struct BmKeysArg { const int32_t* xy; const uint8_t* st; const uint8_t* inf; const uint32_t* bad; uint32_t n_keys; };
+__attribute__((visibility("hidden"))) int bn254_pair_bitmap_sum(const uint32_t* d_bits, size_t bm_words, size_t n, BmKeysArg keys, const int32_t* rec,
+                                                                const uint8_t* rec_inf, Ws ws, hipStream_t s);
+
 // key deduplication of the exact verify (bn254_keydedup.hip): per call, the distinct keys of the batch and their line tables in the
 // KeyTable format above, built on a stream of the context beside decode and hash; the route (tables or the generic loop) is decided on the device
 #define KEY_DEDUP_MAX_KEYS_DEFAULT 1024            // tables for at most this many distinct keys per call (12.5 KB + 6.3 KB of raw c2 each)

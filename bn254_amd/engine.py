@@ -39,6 +39,8 @@ OPT_KEY_DEDUP_HASH_BITS = 24       # test seam: bits of the dedup hash kept (0 =
 OPT_AGGD_KEYED_ROUTE = 25          # keyed aggregates over distinct messages: 0 by size, 1 / 2 slot kernel width, 3 expanded keys
 OPT_AGG_RAND_MIN_PAIRS = 26        # randomised keyed aggregates over distinct messages: the exact route below this many messages
 OPT_AGG_RAND_GROUP_PAIRS = 27      # ... messages per group of its combined checks (developer option; at least the number of keys)
+OPT_BITMAP_TABLE_MAX_KEYS = 28     # signer bitmaps: subset tables of the registered set while it has at most this many keys (default 4096; 0 = never)
+OPT_BITMAP_ROUTE = 29              # ... test hook: 0 by that rule, 1 always tables, 2 always key by key
 
 
 class NativeError(RuntimeError):
@@ -450,6 +452,7 @@ class Engine:
         assert len(pks) == n * G2_BYTES
         st = ctypes.create_string_buffer(max(n, 1))
         _check("bn254_ctx_register_keys", self._lib.bn254_ctx_register_keys(self._h, bytes(pks), n, flags, st))
+        self.n_registered_keys = n
         return st.raw[:n]
 
     def batch_verify_keyed(self, messages, sigs, key_idx, flags=0):
@@ -460,6 +463,22 @@ class Engine:
         status = ctypes.create_string_buffer(max(n, 1))
         _check("bn254_batch_verify_keyed", self._lib.bn254_batch_verify_keyed(self._h, msgs, off, bytes(sigs), idx, n, flags, status))
         return status.raw[:n]
+
+    def batch_verify_keyed_bitmap(self, messages, sigs, bitmaps, bm_words, flags=0):
+        """same-message aggregates as signer bitmaps over the registered keys: bitmaps = n * bm_words uint32 words (signer j of tuple i = bit
+        j % 32 of bitmaps[i * bm_words + j // 32]); returns the status bytes (include/bn254_hip.h: bn254_batch_verify_keyed_bitmap)"""
+        n = len(messages)
+        assert len(sigs) == n * G1_BYTES and len(bitmaps) == n * bm_words
+        msgs, off = pack_messages(messages)
+        bits = (ctypes.c_uint32 * max(len(bitmaps), 1))(*bitmaps)
+        status = ctypes.create_string_buffer(max(n, 1))
+        _check("bn254_batch_verify_keyed_bitmap",
+               self._lib.bn254_batch_verify_keyed_bitmap(self._h, msgs, off, bytes(sigs), bits, bm_words, n, flags, status))
+        return status.raw[:n]
+
+    def batch_verify_keyed_bitmap_device(self, d_msgs, d_off, d_sigs, d_signer_bits, bm_words, n, d_status, flags=0, stream=None):
+        _check("bn254_batch_verify_keyed_bitmap_device",
+               self._lib.bn254_batch_verify_keyed_bitmap_device(self._h, d_msgs, d_off, d_sigs, d_signer_bits, bm_words, n, flags, d_status, stream))
 
     def batch_verify_keyed_randomized(self, messages, sigs, key_idx, seed32, flags=0):
         n = len(messages)

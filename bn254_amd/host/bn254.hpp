@@ -4,6 +4,7 @@
 //   bn254::ECDSA::sign / verify / batch_verify      /root/reference/src/ecdsa.rs:26-35, :49-64 (+ new batch entry)
 //   bn254::ECDSA::aggregate_verify / batch_aggregate_verify_distinct   (new: aggregates over distinct messages)
 //   bn254::ECDSA::aggregate_verify_keyed / batch_aggregate_verify_distinct_keyed   (... against registered keys)
+//   bn254::ECDSA::verify_keyed_signers / batch_verify_keyed_signers                 (one message, an aggregated signature, the signers' indices)
 //   bn254::ECDSA::batch_aggregate_verify_distinct_keyed_randomized                  (... with the group checks combined)
 //   bn254::check_public_keys                        /root/reference/src/ecdsa.rs:78-93
 //   bn254::PrivateKey / PublicKey / PublicKeyG1 / Signature   /root/reference/src/types.rs:13,81,151,222
@@ -246,6 +247,33 @@ struct ECDSA {
     off[n] = msgs.size();
     check_rc("bn254_batch_verify_keyed", bn254_batch_verify_keyed(e.raw(), msgs.data(), off.data(), sigs.data(), key_indices.data(), n, 0, status.data()));
     return status;
+  }
+  // One message, one already aggregated signature and the indices (in the registered set of n_keys keys) of the keys that signed
+  // (include/bn254_hip.h: bn254_batch_verify_keyed_bitmap): result[i] == 0 iff e(H(m_i), sum of the named keys) * e(sigma_i, -G2) == 1;
+  // 2 (IndexOutOfBounds) for an index outside the set — every such index lands on the one bit the bitmaps carry past the set.
+  struct SignerItem { std::vector<uint8_t> message; Signature signature; std::vector<uint32_t> signer_indices; };
+  static std::vector<uint8_t> batch_verify_keyed_signers(const std::vector<SignerItem>& items, size_t n_keys, Engine& e = Engine::default_engine()) {
+    const size_t n = items.size(), bm_words = n_keys / 32 + 1;
+    std::vector<uint64_t> off(n + 1, 0);
+    std::vector<uint8_t> msgs, sigs(n * 64), status(n, 0);
+    std::vector<uint32_t> bits(n * bm_words, 0);
+    for (size_t i = 0; i < n; ++i) {
+      off[i] = msgs.size();
+      msgs.insert(msgs.end(), items[i].message.begin(), items[i].message.end());
+      std::memcpy(&sigs[64 * i], items[i].signature.raw.data(), 64);
+      for (uint32_t j : items[i].signer_indices) {
+        const size_t b = j < n_keys ? j : n_keys;
+        bits[i * bm_words + b / 32] |= 1u << (b % 32);
+      }
+    }
+    off[n] = msgs.size();
+    check_rc("bn254_batch_verify_keyed_bitmap",
+             bn254_batch_verify_keyed_bitmap(e.raw(), msgs.data(), off.data(), sigs.data(), bits.data(), bm_words, n, 0, status.data()));
+    return status;
+  }
+  static void verify_keyed_signers(const std::vector<uint8_t>& message, const Signature& signature, const std::vector<uint32_t>& signer_indices,
+                                   size_t n_keys, Engine& e = Engine::default_engine()) {
+    check_status(batch_verify_keyed_signers({SignerItem{message, signature, signer_indices}}, n_keys, e)[0]);
   }
   // aggregate_verify against the registered set: key_indices[j] names the key of messages[j]; 2 (IndexOutOfBounds) outside the set
   // (include/bn254_hip.h: bn254_batch_aggregate_verify_distinct_keyed)

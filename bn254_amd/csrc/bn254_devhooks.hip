@@ -168,6 +168,31 @@ int bn254_debug_key_dedup_last(bn254_ctx* c, uint32_t out[5]) {
   out[0] = 1;
   return 0;
 }
+// the line tables as they stand on the device: which = 0 the per-call tables of the last key dedup (key ids as k_kd_insert gave them; rep = the
+// item that represents each key), 1 the registered tables of bn254_ctx_register_keys (rep is not written)
+int bn254_debug_key_tables(bn254_ctx* c, int which, size_t first, size_t count, int32_t* lines, uint32_t* rep, uint8_t* st, uint8_t* inf) {
+  if (!c || !lines || (which != 0 && which != 1)) return BN254_E_BAD_ARGUMENT;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipDeviceSynchronize());
+  const size_t per_key = (size_t)BN_N_FIXED_LINES * BN_KEY_LINE_WORDS;
+  const int32_t* src;
+  const uint8_t *src_st, *src_inf;
+  if (which == 0) {
+    uint32_t ctl[KD_CTL_WORDS];
+    if (!c->kd_last_run || !c->kd_ctl || !c->kd_lines_last) return BN254_E_BAD_ARGUMENT;
+    HIP_TRY(hipMemcpy(ctl, c->kd_ctl, sizeof ctl, hipMemcpyDeviceToHost));
+    if (first + count > ctl[KD_CTL_D] || first + count > c->kd_keys_cap) return BN254_E_BAD_ARGUMENT;
+    src = c->kd_lines_last; src_st = c->kd_st_last; src_inf = c->kd_inf_last;
+    if (rep) HIP_TRY(hipMemcpy(rep, c->kd_rep_last + first, count * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  } else {
+    if (!c->key_lines || first + count > c->n_keys) return BN254_E_BAD_ARGUMENT;
+    src = c->key_lines; src_st = c->key_st; src_inf = c->key_inf;
+  }
+  HIP_TRY(hipMemcpy(lines, src + first * per_key, count * per_key * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (st) HIP_TRY(hipMemcpy(st, src_st + first, count, hipMemcpyDeviceToHost));
+  if (inf) HIP_TRY(hipMemcpy(inf, src_inf + first, count, hipMemcpyDeviceToHost));
+  return 0;
+}
 int bn254_debug_agg_rand_last(bn254_ctx* c, uint64_t out[6]) {
   if (!c || !out) return BN254_E_BAD_ARGUMENT;
   for (int i = 0; i < 6; ++i) out[i] = 0;

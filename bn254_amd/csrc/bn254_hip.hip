@@ -106,7 +106,9 @@ KERNEL_SMALL void k_hash_round(const uint8_t* msgs, const uint64_t* off, uint64_
 // range, every survivor takes base + the waves before it + its rank in its own wave.
 // Rounds of up to HASH_RESOLVE_TILES_MIN slots keep one wave per 64 slots (k_hash_resolve: a few thousand atomics at most, and no
 // workgroup barriers on the latency path of the headline's 65 536-message hash).
-KERNEL_SMALL void k_hash_resolve(Ws ws, int round, uint32_t width, uint32_t max_ctr) {
+// `mark` (HASH_NONE = none): the value a survivor's h_best gets — HASH_TAIL in the wide schedule, whose survivors are finished by the tail
+// blocks of k_hash_finish_tail and by nobody else.
+KERNEL_SMALL void k_hash_resolve(Ws ws, int round, uint32_t width, uint32_t max_ctr, uint32_t mark) {
   const uint32_t n_act = ws.h_cnt[round];
   if (n_act == 0) return;
   const uint32_t* list = round == 0 ? nullptr : ws.h_list + (size_t)(round & 1) * ws.stride;
@@ -120,7 +122,10 @@ KERNEL_SMALL void k_hash_resolve(Ws ws, int round, uint32_t width, uint32_t max_
       i = list ? list[slot] : (uint32_t)slot;
       if (ws.h_best[i] == HASH_NONE) {
         const uint32_t next = (uint32_t)ws.h_next[i] + width;
-        if (next < max_ctr) { ws.h_next[i] = (uint8_t)next; survivor = true; }           // else hash.rs:62: HashToPointError (k_hash_finish)
+        if (next < max_ctr) {                                                             // else hash.rs:62: HashToPointError (k_hash_finish)
+          ws.h_next[i] = (uint8_t)next; survivor = true;
+          if (mark != HASH_NONE) ws.h_best[i] = mark;
+        }
       }
     }
     const uint64_t votes = __ballot(survivor);
@@ -133,7 +138,7 @@ KERNEL_SMALL void k_hash_resolve(Ws ws, int round, uint32_t width, uint32_t max_
 }
 #define HASH_RESOLVE_WG 1024
 #define HASH_RESOLVE_TILES_MIN ((size_t)1 << 20)
-__global__ void __launch_bounds__(HASH_RESOLVE_WG) k_hash_resolve_tiles(Ws ws, int round, uint32_t width, uint32_t max_ctr) {
+__global__ void __launch_bounds__(HASH_RESOLVE_WG) k_hash_resolve_tiles(Ws ws, int round, uint32_t width, uint32_t max_ctr, uint32_t mark) {
   const uint32_t n_act = ws.h_cnt[round];
   if (n_act == 0) return;
   const uint32_t* list = round == 0 ? nullptr : ws.h_list + (size_t)(round & 1) * ws.stride;
@@ -150,7 +155,10 @@ __global__ void __launch_bounds__(HASH_RESOLVE_WG) k_hash_resolve_tiles(Ws ws, i
       i = list ? list[slot] : (uint32_t)slot;
       if (ws.h_best[i] == HASH_NONE) {
         const uint32_t next = (uint32_t)ws.h_next[i] + width;
-        if (next < max_ctr) { ws.h_next[i] = (uint8_t)next; survivor = true; }           // else hash.rs:62: HashToPointError (k_hash_finish)
+        if (next < max_ctr) {                                                             // else hash.rs:62: HashToPointError (k_hash_finish)
+          ws.h_next[i] = (uint8_t)next; survivor = true;
+          if (mark != HASH_NONE) ws.h_best[i] = mark;
+        }
       }
     }
     const uint64_t votes = __ballot(survivor);
@@ -218,12 +226,10 @@ KERNEL_SMALL void k_hash_direct(const uint8_t* msgs, const uint64_t* off, uint64
   }
 }
 // the point of every message: the even root for its winning counter (or the error status)
-KERNEL_SMALL void k_hash_finish(const uint8_t* msgs, const uint64_t* off, uint64_t msgs_len, size_t n, Ws ws, uint32_t max_ctr, int px, int inf_plane,
-                                uint8_t* tries_out) {
-  size_t i = (size_t)blockIdx.x * BN_WAVE + threadIdx.x;
-  if (i >= n) return;
+__device__ __forceinline__ void hash_finish_item(const uint8_t* msgs, const uint64_t* off, uint64_t msgs_len, size_t i, const Ws& ws, uint32_t max_ctr, int px,
+                                                 int inf_plane, uint8_t* tries_out) {
   const uint32_t best = ws.h_best[i];
-  if (best == HASH_DONE) return;                                   // k_hash_direct
+  if (best == HASH_DONE || best == HASH_TAIL) return;              // k_hash_direct has written it / a tail block of k_hash_finish_tail does
   uint64_t lo, len;
   const bool span_ok = msg_span(off, i, msgs_len, lo, len);
   const uint8_t* msg = msgs + lo;
@@ -238,7 +244,72 @@ KERNEL_SMALL void k_hash_finish(const uint8_t* msgs, const uint64_t* off, uint64
   ws_byte(ws, BY_ST_HASH, i) = ok ? (uint8_t)ST_OK : !span_ok ? (uint8_t)ST_INVALID_LENGTH : (uint8_t)ST_HASH_TO_POINT;
   if (tries_out) tries_out[i] = ok ? (uint8_t)(best + 1) : !span_ok ? (uint8_t)0 : (uint8_t)max_ctr;
 }
-
+KERNEL_SMALL void k_hash_finish(const uint8_t* msgs, const uint64_t* off, uint64_t msgs_len, size_t n, Ws ws, uint32_t max_ctr, int px, int inf_plane,
+                                uint8_t* tries_out) {
+  size_t i = (size_t)blockIdx.x * BN_WAVE + threadIdx.x;
+  if (i >= n) return;
+  hash_finish_item(msgs, off, msgs_len, i, ws, max_ctr, px, inf_plane, tries_out);
+}
+// MID-SIZE batches (the wide schedule of launch_hash_rounds): ONE wide filter round leaves few messages without a counter; they must not
+// cost everyone else two more dependent rounds.  One launch, two block roles (wave-uniform, by blockIdx as in k_miller_verify_split):
+//   blocks [0, nblk_finish)   k_hash_finish for the messages the round decided
+//   the blocks behind them    the TAIL: a survivor of the round (list 1, marked HASH_TAIL by the resolve) gets `chunk` lanes of a wave in
+//                             k_hash_direct's counter-group form — the square root itself for `chunk` counters at once from h_next on,
+//                             the lowest passing counter writes the point; a group without one moves on by `chunk` counters (wave-uniform
+//                             loop) until max_ctr, where it reports HashToPointError as k_hash_finish does.
+// The tail's grid comes from the expected survivor count; the actual count is read from h_cnt[1] and the groups stride over the list.
+// (a function of its own: the tail blocks' square root does not share a register allocation with the finish blocks' inlined one)
+__device__ __noinline__ bool hash_try_msg(G1Affine& out, const uint8_t* msg, uint64_t len, uint32_t ctr) {
+  HashState hs;
+  hash_state_init(hs, msg, len);
+  return hash_try(out, hs, msg, len, ctr);
+}
+KERNEL_SMALL void k_hash_finish_tail(const uint8_t* msgs, const uint64_t* off, uint64_t msgs_len, size_t n, Ws ws, uint32_t max_ctr, int px, int inf_plane,
+                                     uint8_t* tries_out, unsigned nblk_finish, uint32_t chunk) {
+  if (blockIdx.x < nblk_finish) {
+    const size_t i = (size_t)blockIdx.x * BN_WAVE + threadIdx.x;
+    if (i < n) hash_finish_item(msgs, off, msgs_len, i, ws, max_ctr, px, inf_plane, tries_out);
+    return;
+  }
+  const uint32_t n_tail = ws.h_cnt[1];
+  const uint32_t* list = ws.h_list + ws.stride;
+  const uint32_t per_wave = BN_WAVE / chunk, sub = threadIdx.x / chunk, j = threadIdx.x % chunk;
+  const size_t span = (size_t)(gridDim.x - nblk_finish) * per_wave;
+  for (size_t base = (size_t)(blockIdx.x - nblk_finish) * per_wave; base < n_tail; base += span) {   // wave-uniform trip count: the votes need every lane
+    const size_t slot = base + sub;
+    const bool live = slot < n_tail;
+    uint32_t i = 0, first = 0;
+    uint64_t lo = 0, len = 0;
+    bool span_ok = true;
+    if (live) { i = list[slot]; first = ws.h_next[i]; span_ok = msg_span(off, i, msgs_len, lo, len); }
+    const uint8_t* msg = msgs + lo;
+    bool open = live && span_ok;                                    // this group still looks for its point
+    for (uint32_t k = 0;; k += chunk) {
+      const uint32_t ctr = first + k + j;
+      bool ok = false;
+      G1Affine p;
+      if (open && ctr < max_ctr) ok = hash_try_msg(p, msg, len, ctr);   // the hash state is rebuilt per pass (a second pass has p = 1.3e-9 at the default chunk)
+      const uint64_t pass = __ballot(ok);
+      const uint32_t group = (uint32_t)(pass >> (threadIdx.x & ~(chunk - 1u))) & (uint32_t)((1ull << chunk) - 1u);
+      if (group != 0) {
+        if (ok && j == (uint32_t)__builtin_ctz(group)) {            // hash.rs:40-59: the first counter that yields a point
+          ws_store_g1(ws, px, inf_plane, i, p);
+          ws_byte(ws, BY_ST_HASH, i) = (uint8_t)ST_OK;
+          if (tries_out) tries_out[i] = (uint8_t)(ctr + 1);
+        }
+        open = false;
+      }
+      if (__ballot(open && first + k + chunk < max_ctr) == 0) break;
+    }
+    if (live && j == 0 && (open || !span_ok)) {                      // counters exhausted (hash.rs:62), or a span that was never dereferenced
+      G1Affine p;
+      g1_set_generator(p);
+      ws_store_g1(ws, px, inf_plane, i, p);
+      ws_byte(ws, BY_ST_HASH, i) = span_ok ? (uint8_t)ST_HASH_TO_POINT : (uint8_t)ST_INVALID_LENGTH;
+      if (tries_out) tries_out[i] = span_ok ? (uint8_t)max_ctr : (uint8_t)0;
+    }
+  }
+}
 // ECDSA::verify Miller loop: f = miller(H(m), pk) * miller(sig, -G2)   (ecdsa.rs:53-57)
 // P1 planes hold sig, P2 planes hold H(m), Q planes hold pk.
 // With `map` (randomised batch verification, exact re-check of failed groups) lane j works on item
@@ -457,6 +528,7 @@ static int kd_reserve(bn254_ctx* c, size_t n, KeyDedup& kd) {
     if (c->kd_buf) { HIP_TRY(hipFree(c->kd_buf)); c->kd_buf = nullptr; }
     c->kd_items_cap = c->kd_keys_cap = 0;
     c->kd_ctl = nullptr;
+    c->kd_lines_last = nullptr;
     if (hipMalloc((void**)&c->kd_buf, items_cap * KD_BYTES_PER_ITEM + keys_cap * KD_BYTES_PER_KEY + 256) != hipSuccess) {
       (void)hipGetLastError();                       // no room for the tables: this call takes the generic route (the caller sees no error)
       c->kd_buf = nullptr;
@@ -480,6 +552,7 @@ static int kd_reserve(bn254_ctx* c, size_t n, KeyDedup& kd) {
   c->kd_ctl = kd.ctl;
   kd.st = take(c->kd_keys_cap);
   kd.inf = take(c->kd_keys_cap);
+  c->kd_lines_last = kd.lines; c->kd_rep_last = kd.rep; c->kd_st_last = kd.st; c->kd_inf_last = kd.inf;
   kd.slot_mask = (uint32_t)(slots - 1);
   kd.hash_mask = c->kd_hash_bits > 0 && c->kd_hash_bits < 32 ? (1u << c->kd_hash_bits) - 1 : 0xFFFFFFFFu;
   kd.max_keys = (uint32_t)keys;
@@ -573,6 +646,15 @@ int launch_decode_g2(bn254_ctx* c, hipStream_t s, const uint8_t* d_pts, size_t n
   return 0;
 }
 
+// width of the one round of the wide schedule: the smallest from 4 on (at most 8) with which the launch behind it — n / 64 finish waves and one
+// 32-lane group per expected survivor — stays within one wave per SIMD, so that every square root runs at a lone wave's rate in one pass.
+// Measured at 16 385 / 32 768 (profiles/hash_schedule_sweep.jsonl): widths 4 / 6 are the fastest, and they are what this rule gives.
+static uint32_t hash_wide_width(size_t n) {
+  double survivors = (double)n * 0.5274 * 0.5274 * 0.5274 * 0.5274;
+  uint32_t w = 4;
+  for (; w < 8 && (double)n / BN_WAVE + survivors * HASH_TAIL_CHUNK_DEFAULT / BN_WAVE > (double)HASH_WIDE_WAVES; ++w) survivors *= 0.5274;
+  return w;
+}
 // The schedule (widths, grid sizes) is fixed on the host from the EXPECTED survivor counts
 // (p_fail = 0.5274 per try); the kernels read the actual counts from device memory and use grid-stride
 // loops, so a wrong estimate costs time, never correctness.  No host synchronisation.
@@ -591,6 +673,33 @@ int launch_hash_rounds(bn254_ctx* c, hipStream_t s, const uint8_t* d_msgs, const
     HIP_TRY(hipGetLastError());
     return 0;
   }
+  if (n > HASH_DIRECT_MAX_N && (c->hash_schedule == 2 || (c->hash_schedule == 0 && n <= HASH_WIDE_MAX_N))) {
+    // the wide schedule: init, ONE round of width W0, resolve, finish + tail side by side (k_hash_finish_tail)
+    uint32_t w0 = c->hash_wide_width ? (uint32_t)c->hash_wide_width : hash_wide_width(n);
+    if (w0 > max_ctr) w0 = max_ctr;
+    size_t lanes = n * w0;
+    if (lanes > HASH_MAX_GRID_LANES) lanes = HASH_MAX_GRID_LANES;
+    k_hash_round<<<grid_for(lanes), BN_WAVE, 0, s>>>(d_msgs, d_off, msgs_len, c->ws, 0, w0, max_ctr);
+    if (n > HASH_RESOLVE_TILES_MIN) {
+      size_t tiles = (n + HASH_RESOLVE_WG - 1) / HASH_RESOLVE_WG;
+      if (tiles > 16384) tiles = 16384;
+      k_hash_resolve_tiles<<<(unsigned)tiles, HASH_RESOLVE_WG, 0, s>>>(c->ws, 0, w0, max_ctr, HASH_TAIL);
+    } else {
+      k_hash_resolve<<<grid_for(n), BN_WAVE, 0, s>>>(c->ws, 0, w0, max_ctr, HASH_TAIL);
+    }
+    double pf = 1.0;
+    for (uint32_t t = 0; t < w0 && pf > 1e-12; ++t) pf *= 0.5274;
+    double bound = (double)n * pf * 1.25 + 256.0;           // generous estimate of the survivors, as for the rounds below
+    if (bound > (double)n) bound = (double)n;
+    const uint32_t chunk = (uint32_t)c->hash_tail_chunk;
+    size_t tail_blocks = ((size_t)bound * chunk + BN_WAVE - 1) / BN_WAVE;
+    if (tail_blocks > HASH_TAIL_MAX_BLOCKS) tail_blocks = HASH_TAIL_MAX_BLOCKS;   // the groups stride over the list beyond
+    if (mark_finish >= 0 && c->profiling) HIP_TRY(hipEventRecord(c->ev[mark_finish], s));
+    const unsigned nblk = grid_for(n);
+    k_hash_finish_tail<<<nblk + (unsigned)tail_blocks, BN_WAVE, 0, s>>>(d_msgs, d_off, msgs_len, n, c->ws, max_ctr, px, inf_plane, d_tries, nblk, chunk);
+    HIP_TRY(hipGetLastError());
+    return 0;
+  }
   double expect = (double)n;
   uint32_t consumed = 0;
   for (int round = 0; round < HASH_MAX_ROUNDS && consumed < max_ctr; ++round) {
@@ -606,9 +715,9 @@ int launch_hash_rounds(bn254_ctx* c, hipStream_t s, const uint8_t* d_msgs, const
     if ((size_t)bound > HASH_RESOLVE_TILES_MIN) {
       size_t tiles = ((size_t)bound + HASH_RESOLVE_WG - 1) / HASH_RESOLVE_WG;
       if (tiles > 16384) tiles = 16384;                     // grid-stride beyond
-      k_hash_resolve_tiles<<<(unsigned)tiles, HASH_RESOLVE_WG, 0, s>>>(c->ws, round, width, max_ctr);
+      k_hash_resolve_tiles<<<(unsigned)tiles, HASH_RESOLVE_WG, 0, s>>>(c->ws, round, width, max_ctr, HASH_NONE);
     } else {
-      k_hash_resolve<<<grid_for((size_t)bound), BN_WAVE, 0, s>>>(c->ws, round, width, max_ctr);
+      k_hash_resolve<<<grid_for((size_t)bound), BN_WAVE, 0, s>>>(c->ws, round, width, max_ctr, HASH_NONE);
     }
     consumed += width;
     double pf = 1.0;
@@ -664,6 +773,7 @@ int bn254_ctx_create(int hip_device, bn254_ctx** out) {
   c->agg_rand_group_pairs = AGG_RAND_GROUP_PAIRS_DEFAULT;
   c->trio_max_batch = TRIO_MAX_BATCH_DEFAULT;
   c->hash_direct_width = HASH_DIRECT_WIDTH_DEFAULT;
+  c->hash_tail_chunk = HASH_TAIL_CHUNK_DEFAULT;
   c->trio_wave_roles = TRIO_WAVE_ROLES_DEFAULT;
   c->agg_subset_min_tuples = AGG_SUBSET_MIN_TUPLES_DEFAULT;
   c->agg_sort_by_msg = 1;
@@ -791,6 +901,13 @@ int bn254_ctx_set_option(bn254_ctx* c, int option, int value) {
   if (option == BN254_OPT_HASH_DIRECT_WIDTH) {
     if (value < 0 || value > 32 || (value & (value - 1))) return BN254_E_BAD_ARGUMENT;
     c->hash_direct_width = value;
+    return 0;
+  }
+  if (option == BN254_OPT_HASH_SCHEDULE) { if (value < 0 || value > 2) return BN254_E_BAD_ARGUMENT; c->hash_schedule = value; return 0; }
+  if (option == BN254_OPT_HASH_WIDE_WIDTH) { if (value < 0 || value > 64) return BN254_E_BAD_ARGUMENT; c->hash_wide_width = value; return 0; }
+  if (option == BN254_OPT_HASH_TAIL_CHUNK) {
+    if (value < 2 || value > 32 || (value & (value - 1))) return BN254_E_BAD_ARGUMENT;
+    c->hash_tail_chunk = value;
     return 0;
   }
   if (option == BN254_OPT_NONET_MAX_BATCH) {

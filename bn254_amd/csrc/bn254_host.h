@@ -36,6 +36,9 @@ struct bn254_ctx {
   int hash_max_tries; // test knob: counters tried before HashToPointError (0 = the reference's 255)
   int trio_wave_roles; // octet layout: the Miller loop's four lane pairs as the four waves of a workgroup (k_miller_verify_quad) instead of one wave
   int hash_direct_width; // small batches: counters tried at once with the square root itself (k_hash_direct); 0 = rounds only
+  int hash_schedule;     // BN254_OPT_HASH_SCHEDULE: 0 = by size, 1 = always the multi-round schedule, 2 = the wide round and tail above HASH_DIRECT_MAX_N
+  int hash_wide_width;   // BN254_OPT_HASH_WIDE_WIDTH (measurement knob): counters per message in the wide schedule's round; 0 = by size
+  int hash_tail_chunk;   // BN254_OPT_HASH_TAIL_CHUNK (test seam): counters a survivor's lane group tries at once in the tail (default 32)
   int trio_max_batch; // verify / check_public_keys batches up to this size run in the octet layout (bn254_trio.hip); 0 = never
   int lm_max_batch;    // ... and up to this size their Miller loop runs as the lane machine (bn254_lmiller.hip); 0 = never
   int nonet_wide;      // ... on eighteen lane pairs (one verify per wave) while the batch is at most one verify per SIMD (BN254_OPT_NONET_WIDE)
@@ -80,6 +83,9 @@ struct bn254_ctx {
   uint8_t* kd_buf;           // KeyDedup buffers (bn254_ws.h), grown on demand
   size_t kd_items_cap, kd_keys_cap;
   uint32_t* kd_ctl;          // the device-side decision of the last call that ran the dedup (bn254_debug_key_dedup_last)
+  const int32_t* kd_lines_last;   // ... and its tables, representatives, statuses and identity flags (bn254_debug_key_tables; into kd_buf)
+  const uint32_t* kd_rep_last;
+  const uint8_t *kd_st_last, *kd_inf_last;
   int kd_last_run;           // ... and whether the last bn254_batch_verify_device ran it at all
   int aggd_keyed_route;      // BN254_OPT_AGGD_KEYED_ROUTE (test and measurement knob): 0 by size, 1 / 2 the slot kernel of that width, 3 expanded keys
   int agg_rand_min_pairs;    // BN254_OPT_AGG_RAND_MIN_PAIRS: the randomised keyed aggregate verify from this many messages on

@@ -2,7 +2,8 @@
 // (tests/test_keydedup_tables.py: word-for-word parity with g2_line_table + fp_canon, bound proof under -DBN_TRACK_BOUNDS).
 // g2_line_table (bn254_pairing.h) computes a key's 87 lines and scales each one by its own c2^-1 on the spot: 87 inversions in sequence.
 // Here the walk and the scaling are split — kd_walk_raw_lines emits the raw (c0, c1, c2) of every line, kd_scale_line turns one of them
-// into the c2 = 1 form with canonical limbs — so that the device runs the 87 scalings of a key side by side.  Same operations at the same
+// into the c2 = 1 form with canonical limbs.  The device scales the 87 lines of a key with ONE inversion (k_kd_scale: Montgomery's trick as a
+// product tree over the key's c2 values); kd_scale_tree below is that tree's host form, equal to kd_scale_line line by line.  Same operations at the same
 // norm sites (290 .. 293) as g2_line_table: the same values and the same bounds.  kd_walk_raw_lines is the reference formulation of the
 // walk (one lane pair, one step after the other); the device builder runs the same walk as the lane machine's level program
 // (bn254_kdlines.h), whose raw lines tests/test_kd_builder.py checks against it.
@@ -43,6 +44,30 @@ BN_DEV void kd_scale_line(const Fp2& c0, const Fp2& c1, const Fp2& c2, Fp2& r0, 
   const Fp2 a = fp2_mul(c0, inv), b = fp2_mul(c1, inv);
   BN_FOR_ROLES(k) { r0.c[k] = fp_canon(a.c[k]); r1.c[k] = fp_canon(b.c[k]); }
 }
+
+// The tree of k_kd_scale (bn254_keydedup.hip), operation for operation: heap order, node 1 = the root, leaves KD_TREE_LEAVES + line (ones
+// beyond the 87 lines); leaf = the weakly reduced raw c2 (site 290's default); KD_TREE_LEVELS product levels up; fp2_inv of the root; the same
+// number of levels down (inverse of a node = inverse of its parent x its sibling); then kd_scale_line's two products and fp_canon.  Exact
+// field arithmetic and canonical results: the words are kd_scale_line's.  A zero c2 makes the root zero; the results of such a key are not
+// used (KD_DEGENERATE) and the work stays finite.
+#define KD_TREE_LEAVES 128
+#define KD_TREE_LEVELS 7
+#if !defined(__HIPCC__)
+static inline void kd_scale_tree(const Fp2* c0, const Fp2* c1, const Fp2* c2, Fp2* r0, Fp2* r1) {   // BN_N_FIXED_LINES entries each
+  static_assert(BN_N_FIXED_LINES <= KD_TREE_LEAVES && (1 << KD_TREE_LEVELS) == KD_TREE_LEAVES, "tree shape");
+  Fp2 prod[2 * KD_TREE_LEAVES], inv[2 * KD_TREE_LEAVES];
+  for (int p = 0; p < KD_TREE_LEAVES; ++p) prod[KD_TREE_LEAVES + p] = p < BN_N_FIXED_LINES ? fp2_reduce_weak(c2[p]) : fp2_one();
+  for (int w = KD_TREE_LEAVES / 2; w >= 1; w >>= 1)
+    for (int node = w; node < 2 * w; ++node) prod[node] = fp2_mul(prod[2 * node], prod[2 * node + 1]);
+  inv[1] = fp2_inv(prod[1]);
+  for (int w = 2; w <= KD_TREE_LEAVES; w <<= 1)
+    for (int node = w; node < 2 * w; ++node) inv[node] = fp2_mul(inv[node >> 1], prod[node ^ 1]);
+  for (int p = 0; p < BN_N_FIXED_LINES; ++p) {
+    const Fp2 a = fp2_mul(c0[p], inv[KD_TREE_LEAVES + p]), b = fp2_mul(c1[p], inv[KD_TREE_LEAVES + p]);
+    BN_FOR_ROLES(k) { r0[p].c[k] = fp_canon(a.c[k]); r1[p].c[k] = fp_canon(b.c[k]); }
+  }
+}
+#endif
 
 #if defined(__HIPCC__)
 // One uncompressed G2 point (/root/reference/src/utils.rs:107-116) on a lane pair: each lane reads, range-checks and converts the two

@@ -14,8 +14,8 @@
 //                 decode of the representative (the statuses of the items themselves stay what launch_decode_g2 writes), the twist-point
 //                 walk of g2_line_table with the RAW lines (c0, c1, c2) stored; a line with c2 = 0 (not reachable from the order-r subgroup,
 //                 but keys are not subgroup-checked under flags = 0) sets KD_DEGENERATE
-//   k_kd_scale    one lane pair per (key, line): c0 / c2, c1 / c2, canonical — the arithmetic of g2_line_table's emit, so the tables
-//                 are word for word those of registration; the 87 inversions of a key run side by side instead of one after the other
+//   k_kd_scale    one workgroup per key, one lane pair per line: c0 / c2, c1 / c2, canonical — the values of g2_line_table's emit, so the
+//                 tables are word for word those of registration; ONE inversion per key (a product tree over its 87 c2 in LDS)
 //   k_kd_decide   the route: keyed iff D <= max_keys, D * min_multiplicity <= n, no overflow, no degenerate line; written as the device-side
 //                 item counts the two Miller kernels read at entry (the unchosen one returns at once)
 #include <hip/hip_runtime.h>
@@ -202,15 +202,53 @@ KERNEL_KD_LM void k_kd_lines(const uint8_t* pks, size_t n, uint32_t flags, KeyDe
   kd_builder_program(m);
   if (m.live && real && m.degenerate && m.pair == 0 && role == 0) atomicOr(&kd.ctl[KD_CTL_FLAGS], (uint32_t)KD_DEGENERATE);
 }
-// one lane pair per (key, line): (c0, c1) <- canonical (c0 / c2, c1 / c2)
+// one workgroup per key, one lane pair per line: (c0, c1) <- canonical (c0 / c2, c1 / c2) with ONE inversion per key.  Montgomery's trick as a
+// tree over the key's 87 c2 values (padded with ones to KD_TREE_LEAVES) in LDS — bn254_keydedup.h: kd_scale_tree is its host form —, heap order (node 1 = the root, leaves from KD_TREE_LEAVES on):
+// seven product levels up, fp2_inv of the root, seven levels down (inverse of a node = inverse of its parent x its sibling), then the two
+// products of kd_scale_line.  Field arithmetic is exact and the results are canonical, so the table words are those of kd_scale_line line by
+// line.  A key with a line c2 = 0 has a zero root: every "inverse" is then what fp2_inv gives for zero times other values — finite work, no
+// table anyone reads (k_kd_lines has set KD_DEGENERATE).
+static_assert(BN_N_FIXED_LINES <= KD_TREE_LEAVES && 2 * KD_TREE_LEAVES == KD_WG, "one lane pair per leaf");
+#define KD_NODE_WORDS (2 * BN_LIMBS)
 KERNEL_KD_PAIR void k_kd_scale(size_t n, KeyDedup kd) {
   if (!kd_viable(kd, n)) return;
-  const size_t p = ((size_t)blockIdx.x * KD_WG + threadIdx.x) >> 1;
-  const uint32_t j = (uint32_t)(p / BN_N_FIXED_LINES), idx = (uint32_t)(p % BN_N_FIXED_LINES);
-  if (j >= kd.ctl[KD_CTL_D]) return;
-  int32_t* row = kd.lines + ((size_t)j * BN_N_FIXED_LINES + idx) * BN_KEY_LINE_WORDS;
+  const uint32_t j = blockIdx.x;
+  if (j >= kd.ctl[KD_CTL_D]) return;                               // the whole workgroup leaves
+  __shared__ int32_t prod[2 * KD_TREE_LEAVES * KD_NODE_WORDS];     // products of the subtrees
+  __shared__ int32_t inv[2 * KD_TREE_LEAVES * KD_NODE_WORDS];      // ... and their inverses
+  const uint32_t p = threadIdx.x >> 1;
+  const bool line = p < BN_N_FIXED_LINES;
+  int32_t* row = kd.lines + ((size_t)j * BN_N_FIXED_LINES + (line ? p : 0u)) * BN_KEY_LINE_WORDS;
+  {
+    Fp2 leaf = fp2_one();
+    if (line) leaf = fp2_reduce_weak(kd_load_own(kd.c2 + ((size_t)j * BN_N_FIXED_LINES + p) * KD_NODE_WORDS));   // site 290's default, for the raw slot value
+    kd_store_own(prod + (KD_TREE_LEAVES + p) * KD_NODE_WORDS, leaf);
+  }
+  __syncthreads();
+  for (uint32_t w = KD_TREE_LEAVES / 2; w >= 1; w >>= 1) {          // nodes w .. 2w - 1
+    if (p < w) {
+      const uint32_t node = w + p;
+      kd_store_own(prod + node * KD_NODE_WORDS, fp2_mul(kd_load_own(prod + 2 * node * KD_NODE_WORDS), kd_load_own(prod + (2 * node + 1) * KD_NODE_WORDS)));
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x < BN_WAVE) {                                      // one wave inverts the root (every pair the same value; pair 0 publishes it)
+    const Fp2 r = fp2_inv(kd_load_own(prod + KD_NODE_WORDS));
+    if (p == 0) kd_store_own(inv + KD_NODE_WORDS, r);
+  }
+  __syncthreads();
+  for (uint32_t w = 2; w <= KD_TREE_LEAVES; w <<= 1) {              // nodes w .. 2w - 1
+    if (p < w) {
+      const uint32_t node = w + p;
+      kd_store_own(inv + node * KD_NODE_WORDS, fp2_mul(kd_load_own(inv + (node >> 1) * KD_NODE_WORDS), kd_load_own(prod + (node ^ 1u) * KD_NODE_WORDS)));
+    }
+    __syncthreads();
+  }
+  if (!line) return;
+  const Fp2 c2inv = kd_load_own(inv + (KD_TREE_LEAVES + p) * KD_NODE_WORDS);
+  const Fp2 a = fp2_mul(kd_load_own(row), c2inv), b = fp2_mul(kd_load_own(row + 2 * BN_LIMBS), c2inv);
   Fp2 r0, r1;
-  kd_scale_line(kd_load_own(row), kd_load_own(row + 2 * BN_LIMBS), kd_load_own(kd.c2 + ((size_t)j * BN_N_FIXED_LINES + idx) * 2 * BN_LIMBS), r0, r1);
+  BN_FOR_ROLES(k) { r0.c[k] = fp_canon(a.c[k]); r1.c[k] = fp_canon(b.c[k]); }
   kd_store_own(row, r0);
   kd_store_own(row + 2 * BN_LIMBS, r1);
 }
@@ -228,7 +266,7 @@ int bn254_kd_enqueue(const uint8_t* d_pks, size_t n, uint32_t flags, KeyDedup kd
   k_kd_insert<<<g, KD_WG, 0, s>>>(d_pks, n, kd);
   k_kd_resolve<<<g, KD_WG, 0, s>>>(n, kd);
   k_kd_lines<<<(unsigned)((kd.max_keys + KD_LM_PER_WAVE - 1) / KD_LM_PER_WAVE), BN_WAVE, KD_LM_LDS_WORDS * sizeof(int32_t), s>>>(d_pks, n, flags, kd);
-  k_kd_scale<<<(unsigned)((2 * (size_t)kd.max_keys * BN_N_FIXED_LINES + KD_WG - 1) / KD_WG), KD_WG, 0, s>>>(n, kd);
+  k_kd_scale<<<kd.max_keys, KD_WG, 0, s>>>(n, kd);
   k_kd_decide<<<1, BN_WAVE, 0, s>>>(n, kd, force_generic);
   HIP_TRY(hipGetLastError());
   return 0;

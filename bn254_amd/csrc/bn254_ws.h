@@ -111,6 +111,7 @@ struct Ws {
   } while (0)
 #define HASH_NONE 0xFFFFFFFFu
 #define HASH_DONE 0xFFFFFFFEu                    // k_hash_direct has already written the point of this message
+#define HASH_TAIL 0xFFFFFFFDu                    // a survivor of the wide schedule's round: a tail block of k_hash_finish_tail writes its point
 #define HASH_DIRECT_WIDTH_DEFAULT 32             // counters tried at once per message by k_hash_direct (lanes of one wave; 1, 2, .. 32)
 #define HASH_DIRECT_MAX_N ((size_t)4096)         // ... for batches that leave the chip mostly idle: 32 n lanes <= two waves per SIMD
 #define HASH_MAX_ROUNDS 64
@@ -118,6 +119,14 @@ struct Ws {
 #ifndef HASH_TARGET_LANES
 #define HASH_TARGET_LANES ((size_t)1 << 17)    // ~2 waves per SIMD
 #endif
+// the wide schedule (launch_hash_rounds: one wide filter round, then finish and tail in one launch) from above HASH_DIRECT_MAX_N up to here;
+// above, the multi-round schedule, which is throughput-bound there
+#ifndef HASH_WIDE_MAX_N
+#define HASH_WIDE_MAX_N ((size_t)32768)
+#endif
+#define HASH_WIDE_WAVES 1024                    // ... whose round is as wide as keeps finish and tail waves together below this (one wave per SIMD)
+#define HASH_TAIL_CHUNK_DEFAULT 32              // counters a survivor's lane group tries at once in the tail (a power of two, 2 .. 32)
+#define HASH_TAIL_MAX_BLOCKS ((size_t)16384)    // tail waves launched at most (the groups stride over the survivor list beyond)
 enum { PL_P1X = 0, PL_P1Y, PL_QX0, PL_QX1, PL_QY0, PL_QY1, PL_P2X, PL_P2Y, PL_HASHX, PL_HASHY, PL_F0, N_PLANES = PL_F0 + 12 };
 enum { BY_ST_DECODE = 0, BY_ST_HASH, BY_P1_INF, BY_Q_INF, BY_P2_INF, BY_A_INF, N_BYTE_PLANES };
 

@@ -41,6 +41,9 @@ OPT_AGG_RAND_MIN_PAIRS = 26        # randomised keyed aggregates over distinct m
 OPT_AGG_RAND_GROUP_PAIRS = 27      # ... messages per group of its combined checks (developer option; at least the number of keys)
 OPT_BITMAP_TABLE_MAX_KEYS = 28     # signer bitmaps: subset tables of the registered set while it has at most this many keys (default 4096; 0 = never)
 OPT_BITMAP_ROUTE = 29              # ... test hook: 0 by that rule, 1 always tables, 2 always key by key
+OPT_HASH_SCHEDULE = 30             # hash-to-G1 above 4096 messages: 0 by size, 1 multi-round schedule, 2 one wide round + finish and tail in one launch
+OPT_HASH_WIDE_WIDTH = 31           # ... measurement knob: counters per message in the wide round (0 = by size)
+OPT_HASH_TAIL_CHUNK = 32           # ... test seam: counters per lane group and pass in the tail (power of two, 2 .. 32; default 32)
 
 
 class NativeError(RuntimeError):
@@ -133,6 +136,15 @@ class Engine:
         o = (ctypes.c_uint32 * 5)()
         _check("bn254_debug_key_dedup_last", self._lib.bn254_debug_key_dedup_last(self._h, o))
         return dict(zip(("ran", "keys", "flags", "keyed_n", "generic_n"), (int(x) for x in o)))
+
+    def debug_key_tables(self, which, first, count):
+        """developer hook: the line tables on the device (which = 0: of the last key dedup, 1: registered) of keys first .. first + count - 1
+        -> (words: count * 87 * 36 ints, rep or None, statuses, identity flags)"""
+        words = (ctypes.c_int32 * (count * 87 * 36))()
+        rep = (ctypes.c_uint32 * max(count, 1))()
+        st, inf = ctypes.create_string_buffer(max(count, 1)), ctypes.create_string_buffer(max(count, 1))
+        _check("bn254_debug_key_tables", self._lib.bn254_debug_key_tables(self._h, which, first, count, words, rep, st, inf))
+        return list(words), (list(rep)[:count] if which == 0 else None), st.raw[:count], inf.raw[:count]
 
     def debug_agg_rand_last(self):
         """what the last batch_aggregate_verify_distinct_keyed_randomized[_device] did: dict(ran, groups, table_pairs, failed_groups, rechecked,

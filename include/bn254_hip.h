@@ -551,6 +551,13 @@ int bn254_mgpu_batch_hash_to_g1(bn254_mgpu *mg, const uint8_t *msgs, const uint6
 #define BN254_OPT_HASH_DIRECT_WIDTH 7 /* hash-to-G1 of batches of up to 4096 messages: this many counters of every message are tried at once, in
                                        lanes of one wave, with the square root itself (latency 0.17 ms instead of 0.25); a power of two <= 32,
                                        default 32; 0 = always the filter rounds.  Same points and try counts either way. */
+#define BN254_OPT_HASH_SCHEDULE 30 /* hash-to-G1 of batches above 4096 messages: 0 (default) = by size, 1 = always the multi-round filter schedule,
+                                    2 = always one wide filter round, then the square roots and the round's few survivors (all their remaining
+                                    counters, in lane groups) in one launch.  Same points, statuses and try counts either way. */
+#define BN254_OPT_HASH_WIDE_WIDTH 31 /* measurement knob of that schedule (tools/hash_schedule_sweep.py): counters per message in the wide round,
+                                      1 .. 64; 0 (default) = chosen by size, 4 .. 8 */
+#define BN254_OPT_HASH_TAIL_CHUNK 32 /* test seam: counters a survivor's lane group tries at once in that launch; a power of two, 2 .. 32 (default
+                                      32: a second pass of a group has p = 1.3e-9).  Small values let real messages reach the group's loop. */
 #define BN254_OPT_NONET_WIDE 16 /* ... and, while the batch is at most one item per SIMD (1 024), on EIGHTEEN lane pairs, one item per wave: the 18
                                  products of a multiplication in one round (default 1; 0 = nine lane pairs at every size) */
 #define BN254_OPT_AGG_SORT_BY_MSG 11 /* aggregate verify, batches that use the per-message signature tables: bucket the tuples by message on the
@@ -584,6 +591,11 @@ int bn254_debug_route_table(bn254_ctx *ctx, uint64_t *max_n, int *miller, int *f
  * flags (1 probe overflow, 2 degenerate line), items of the keyed Miller kernel, items of the generic one}; all 0 when the call did not run
  * the dedup.  Synchronises the device. */
 int bn254_debug_key_dedup_last(bn254_ctx *ctx, uint32_t out[5]);
+/* the Miller-loop line tables as they stand on the device, keys first .. first + count - 1: which = 0 the per-call tables of the key
+ * deduplication of the last bn254_batch_verify_device (key ids in the order the device handed them out; rep[k] = the item that represents key
+ * k), which = 1 the tables of bn254_ctx_register_keys (rep is not written).  lines: count x 87 x 36 words ([line][c0, c1][re, im][9 limbs],
+ * canonical); st / inf (optional): decode status and identity flag per key.  Synchronises the device. */
+int bn254_debug_key_tables(bn254_ctx *ctx, int which, size_t first, size_t count, int32_t *lines, uint32_t *rep, uint8_t *st, uint8_t *inf);
 /* what the last bn254_batch_aggregate_verify_distinct_keyed_randomized[_device] did: out = {1 if it took the randomised route, groups that
  * reached the check, table pairs of all group checks, failed groups, aggregates re-checked, groups of one aggregate (r = 1)}; all 0 when it
  * took the exact route.  Synchronises the device. */

@@ -291,7 +291,7 @@ class ECDSA:
         _raise(ECDSA._keyed_signers_status([(message, signature, signer_indices)], engine)[0])
 
     @staticmethod
-    def _keyed_signers_status(items, engine):
+    def _keyed_signers_status(items, engine, seed=None, flags=0):
         rows = []
         for item in items:
             if len(item) != 3 or len(item[1].raw) != _engine.G1_BYTES:
@@ -312,6 +312,8 @@ class ECDSA:
             for j in idx:
                 j = min(j, top)
                 bits[i * bm_words + j // 32] |= 1 << (j % 32)
+        if seed is not None:
+            return eng.batch_verify_keyed_bitmap_randomized([r[0] for r in rows], b"".join(r[1] for r in rows), bits, bm_words, seed, flags)
         return eng.batch_verify_keyed_bitmap([r[0] for r in rows], b"".join(r[1] for r in rows), bits, bm_words)
 
     @staticmethod
@@ -319,6 +321,19 @@ class ECDSA:
         """items: a list of (message, signature, signer_indices); result[i] is None iff ECDSA.verify_keyed_signers on item i succeeds, else
         the Error it would raise.  An item that is not such a triple raises Error(InvalidLength) before any device work."""
         return [None if s == 0 else Error(s) for s in ECDSA._keyed_signers_status(items, engine)]
+
+    @staticmethod
+    def batch_verify_keyed_signers_randomized(items, seed=None, engine=None, rand64=False):
+        """batch_verify_keyed_signers with the pairing checks of whole groups of items combined (include/bn254_hip.h:
+        bn254_batch_verify_keyed_bitmap_randomized): the same result list; an Error is always the exact one, a None is wrong with probability
+        <= 2^-128 per group (2^-64 with rand64) for a secret seed (32 bytes; default os.urandom)."""
+        import os
+        if seed is None:
+            seed = os.urandom(32)
+        if len(seed) != 32:
+            raise ValueError("seed must be 32 bytes")
+        flags = _engine.FLAG_RAND64 if rand64 else 0
+        return [None if s == 0 else Error(s) for s in ECDSA._keyed_signers_status(items, engine, bytes(seed), flags)]
 
     @staticmethod
     def batch_verify_keyed_randomized(messages, signatures, key_indices, seed=None, engine=None, rand64=False):

@@ -426,3 +426,14 @@ int bn254_batch_aggregate_verify_distinct_keyed_randomized(bn254_ctx* c, const u
   return aggd_call_host(c, AGGD_RANDOMIZED, msgs, msg_off, key_idx, sizeof(uint32_t), m, agg_sigs, agg_off, n, flags, seed32, status);
 }
 }  // extern "C"
+
+// for the other unit that runs group checks (bn254_bitmap_rand.hip): the prefix sum, and the slot kernel's slots of n groups of table pairs
+int bn254_aggd_scan_add(hipStream_t s, const uint64_t* in, size_t n, uint64_t* out, uint64_t* tot) { return aggd_scan<AggdAdd>(s, in, n, out, tot); }
+int bn254_aggd_keyed_slot_map(hipStream_t s, size_t n, const uint64_t* lo, const uint64_t* hi, int width, uint64_t* kincl, uint64_t* tot, size_t n_slots,
+                              uint32_t* slot_agg) {
+  k_aggd_keyed_count<<<grid_for(n), BN_WAVE, 0, s>>>(n, lo, hi, (uint64_t)width, kincl);
+  if (const int rc = aggd_scan<AggdAdd>(s, kincl, n, kincl, tot)) return rc;
+  k_aggd_keyed_map<<<grid_for(n_slots), BN_WAVE, 0, s>>>(n_slots, n, kincl, slot_agg);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}

@@ -56,14 +56,14 @@ KERNEL void k_bm_sum(const uint32_t* bits, size_t bm_words, size_t n, BmKeys K, 
 }
 
 // does this call read tables?  BN254_OPT_BITMAP_ROUTE forces either answer (tests); otherwise the size rule of BN254_OPT_BITMAP_TABLE_MAX_KEYS
-static bool bm_wants_tables(const bn254_ctx* c) {
+bool bm_wants_tables(const bn254_ctx* c) {
   if (c->n_keys == 0 || c->bm_route == 2) return false;
   return c->bm_route == 1 || (c->bm_table_max_keys > 0 && c->n_keys <= (size_t)c->bm_table_max_keys);
 }
 // Built lazily, on the call's stream, by the first bitmap call after a registration: the bad-bit vector always, the subset tables when the
 // call reads them.  The context carries one call in flight, so every later call — on this stream, or on another one after this call has
 // finished — is ordered behind the build.
-static int bm_prepare(bn254_ctx* c, hipStream_t s, bool tables) {
+int bm_prepare(bn254_ctx* c, hipStream_t s, bool tables) {
   if (c->n_keys == 0) return 0;
   if (!c->bm_bad_valid) {
     const uint32_t n_words = (uint32_t)((c->n_keys + 31) / 32);

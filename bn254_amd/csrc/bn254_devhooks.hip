@@ -193,44 +193,46 @@ int bn254_debug_key_tables(bn254_ctx* c, int which, size_t first, size_t count, 
   if (inf) HIP_TRY(hipMemcpy(inf, src_inf + first, count, hipMemcpyDeviceToHost));
   return 0;
 }
-int bn254_debug_agg_rand_last(bn254_ctx* c, uint64_t out[6]) {
+static int debug_rand_last(bn254_ctx* c, int ran, const uint32_t* stats, uint64_t out[6]) {
   if (!c || !out) return BN254_E_BAD_ARGUMENT;
   for (int i = 0; i < 6; ++i) out[i] = 0;
-  if (!c->aggr_last_ran || !c->aggr_stats) return 0;
+  if (!ran || !stats) return 0;
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipDeviceSynchronize());
   uint32_t st[5];
-  HIP_TRY(hipMemcpy(st, c->aggr_stats, sizeof st, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(st, stats, sizeof st, hipMemcpyDeviceToHost));
   out[0] = 1;
   for (int i = 0; i < 5; ++i) out[i + 1] = st[i];
   return 0;
 }
+int bn254_debug_agg_rand_last(bn254_ctx* c, uint64_t out[6]) { return debug_rand_last(c, c ? c->aggr_last_ran : 0, c ? c->aggr_stats : nullptr, out); }
+int bn254_debug_bitmap_rand_last(bn254_ctx* c, uint64_t out[6]) { return debug_rand_last(c, c ? c->bmr_last_ran : 0, c ? c->bmr_stats : nullptr, out); }
 // The groups of the last randomised call, read from where it left them (bn254_host.h: aggr_last): the call itself launches and copies
 // nothing for this.  dims = {groups, table pairs}; with group_cap / pair_cap too small only dims is written.
-int bn254_debug_agg_rand_sums(bn254_ctx* c, uint64_t dims[2], size_t group_cap, size_t pair_cap, uint32_t* nagg, uint8_t* verdict, uint8_t* s_g,
-                              uint64_t* first_pair, uint32_t* pair_key, uint8_t* pair_point) {
+static int debug_rand_sums(bn254_ctx* c, int ran, const AggrLast& L, uint64_t dims[2], size_t group_cap, size_t pair_cap, uint32_t* nagg, uint8_t* verdict,
+                           uint8_t* s_g, uint64_t* first_pair, uint32_t* pair_key, uint8_t* pair_point) {
   if (!c || !dims) return BN254_E_BAD_ARGUMENT;
   dims[0] = dims[1] = 0;
-  if (!c->aggr_last_ran || !c->aggr_buf) return 0;
+  if (!ran) return 0;
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipDeviceSynchronize());
-  const size_t ng = c->aggr_last.ng, tbase = c->aggr_last.tbase;
+  const size_t ng = L.ng, tbase = L.tbase;
   uint64_t end = 0;
-  HIP_TRY(hipMemcpy(&end, c->aggr_last.ghi + (ng - 1), sizeof end, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&end, L.ghi + (ng - 1), sizeof end, hipMemcpyDeviceToHost));
   const size_t n_tp = (size_t)(end - tbase);
   dims[0] = ng;
   dims[1] = n_tp;
   if (group_cap < ng || pair_cap < n_tp) return 0;
   if (!nagg || !verdict || !s_g || !first_pair || (n_tp && (!pair_key || !pair_point))) return BN254_E_BAD_ARGUMENT;
-  HIP_TRY(hipMemcpy(nagg, c->aggr_last.nagg, ng * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(verdict, c->aggr_last.gst, ng, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(first_pair, c->aggr_last.glo, ng * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(nagg, L.nagg, ng * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(verdict, L.gst, ng, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(first_pair, L.glo, ng * sizeof(uint64_t), hipMemcpyDeviceToHost));
   for (size_t g = 0; g < ng; ++g) first_pair[g] -= tbase;
   first_pair[ng] = n_tp;
-  if (n_tp) HIP_TRY(hipMemcpy(pair_key, c->aggr_last.bkey + tbase, n_tp * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (n_tp) HIP_TRY(hipMemcpy(pair_key, L.bkey + tbase, n_tp * sizeof(uint32_t), hipMemcpyDeviceToHost));
   int rc;
   if ((rc = stage_reserve(c, 0, 64 * (ng > n_tp ? ng : n_tp)))) return rc;
-  k_debug_read_p1<<<grid_for(ng), BN_WAVE, 0, c->stream>>>(c->ws, c->aggr_last.cbase, ng, c->stage[0]);
+  k_debug_read_p1<<<grid_for(ng), BN_WAVE, 0, c->stream>>>(c->ws, L.cbase, ng, c->stage[0]);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(s_g, c->stage[0], 64 * ng, hipMemcpyDeviceToHost));
@@ -241,6 +243,16 @@ int bn254_debug_agg_rand_sums(bn254_ctx* c, uint64_t dims[2], size_t group_cap, 
     HIP_TRY(hipMemcpy(pair_point, c->stage[0], 64 * n_tp, hipMemcpyDeviceToHost));
   }
   return 0;
+}
+int bn254_debug_agg_rand_sums(bn254_ctx* c, uint64_t dims[2], size_t group_cap, size_t pair_cap, uint32_t* nagg, uint8_t* verdict, uint8_t* s_g,
+                              uint64_t* first_pair, uint32_t* pair_key, uint8_t* pair_point) {
+  if (!c) return BN254_E_BAD_ARGUMENT;
+  return debug_rand_sums(c, c->aggr_last_ran && c->aggr_buf, c->aggr_last, dims, group_cap, pair_cap, nagg, verdict, s_g, first_pair, pair_key, pair_point);
+}
+int bn254_debug_bitmap_rand_sums(bn254_ctx* c, uint64_t dims[2], size_t group_cap, size_t pair_cap, uint32_t* nagg, uint8_t* verdict, uint8_t* s_g,
+                                 uint64_t* first_pair, uint32_t* pair_key, uint8_t* pair_point) {
+  if (!c) return BN254_E_BAD_ARGUMENT;
+  return debug_rand_sums(c, c->bmr_last_ran && c->bmr_buf, c->bmr_last, dims, group_cap, pair_cap, nagg, verdict, s_g, first_pair, pair_key, pair_point);
 }
 int bn254_debug_route_table(bn254_ctx* c, uint64_t* max_n, int* miller, int* fe, int cap) {
   if (!c || !max_n || !miller || !fe || cap < 5) return BN254_E_BAD_ARGUMENT;

@@ -771,6 +771,9 @@ int bn254_ctx_create(int hip_device, bn254_ctx** out) {
   c->rand_min_batch = RAND_MIN_BATCH_DEFAULT;
   c->agg_rand_min_pairs = AGG_RAND_MIN_PAIRS_DEFAULT;
   c->agg_rand_group_pairs = AGG_RAND_GROUP_PAIRS_DEFAULT;
+  c->bmr_min_tuples = BITMAP_RAND_MIN_TUPLES_DEFAULT;
+  c->bmr_group_tuples = BITMAP_RAND_GROUP_TUPLES_DEFAULT;
+  c->bmr_max_keys = BITMAP_RAND_MAX_KEYS_DEFAULT;
   c->trio_max_batch = TRIO_MAX_BATCH_DEFAULT;
   c->hash_direct_width = HASH_DIRECT_WIDTH_DEFAULT;
   c->hash_tail_chunk = HASH_TAIL_CHUNK_DEFAULT;
@@ -842,6 +845,7 @@ void bn254_ctx_destroy(bn254_ctx* c) {
   if (c->aggd_buf) (void)hipFree(c->aggd_buf);
   if (c->aggr_buf) (void)hipFree(c->aggr_buf);
   if (c->aggr_stats) (void)hipFree(c->aggr_stats);
+  if (c->bmr_buf) (void)hipFree(c->bmr_buf);
   if (c->kd_buf) (void)hipFree(c->kd_buf);
   if (c->bm_bad) (void)hipFree(c->bm_bad);
   if (c->bm_tab) (void)hipFree(c->bm_tab);
@@ -951,6 +955,9 @@ int bn254_ctx_set_option(bn254_ctx* c, int option, int value) {
   if (option == BN254_OPT_AGG_RAND_MIN_PAIRS) { if (value < 0) return BN254_E_BAD_ARGUMENT; c->agg_rand_min_pairs = value; return 0; }
   if (option == BN254_OPT_AGG_RAND_GROUP_PAIRS) { if (value < 1) return BN254_E_BAD_ARGUMENT; c->agg_rand_group_pairs = value; return 0; }
   if (option == BN254_OPT_BITMAP_TABLE_MAX_KEYS) { if (value < 0) return BN254_E_BAD_ARGUMENT; c->bm_table_max_keys = value; return 0; }
+  if (option == BN254_OPT_BITMAP_RAND_MIN_TUPLES) { if (value < 0) return BN254_E_BAD_ARGUMENT; c->bmr_min_tuples = value; return 0; }
+  if (option == BN254_OPT_BITMAP_RAND_MAX_KEYS) { if (value < 0) return BN254_E_BAD_ARGUMENT; c->bmr_max_keys = value; return 0; }
+  if (option == BN254_OPT_BITMAP_RAND_GROUP_TUPLES) { if (value < 1) return BN254_E_BAD_ARGUMENT; c->bmr_group_tuples = value; return 0; }
   if (option == BN254_OPT_BITMAP_ROUTE) { if (value < 0 || value > 2) return BN254_E_BAD_ARGUMENT; c->bm_route = value; return 0; }
   return BN254_E_BAD_ARGUMENT;
 }

@@ -15,6 +15,10 @@
 // aggregate verify: which of the context's pool buffers hold valid tables, and for which pools (bn254_group.hip: agg_build_tables)
 struct AggTables { int valid; size_t n_msgs, n_signers, n_groups, groups4, built_for; int wide2, wide1; };
 
+// where a randomised call over groups left them for its debug hook: S_g in the P1 planes from cbase, the table pairs from tbase, the rest in
+// the call's scratch buffer
+struct AggrLast { size_t ng, cbase, tbase; const uint32_t *nagg, *bkey; const uint64_t *glo, *ghi; const uint8_t* gst; };
+
 struct bn254_ctx {
   int device;
   hipStream_t stream;
@@ -95,7 +99,7 @@ struct bn254_ctx {
   uint32_t* aggr_stats;      // ... what its last run did on the device (bn254_debug_agg_rand_last)
   int aggr_last_ran;         // ... and whether the last call took the randomised route at all
   // ... and where that call left its groups (bn254_debug_agg_rand_sums): S_g in the P1 planes from cbase, the table pairs from tbase, the rest in aggr_buf
-  struct { size_t ng, cbase, tbase; const uint32_t *nagg, *bkey; const uint64_t *glo, *ghi; const uint8_t* gst; } aggr_last;
+  AggrLast aggr_last;
   // signer bitmaps over the registered keys (bn254_bitmap.hip): the bad-bit vector and the subset tables of the set, built by the first
   // bitmap call after a registration (bn254_ctx_register_keys clears the two flags), grown on demand
   uint8_t* bm_bad;           // uint32 words, one bit per key
@@ -105,6 +109,15 @@ struct bn254_ctx {
   bool bm_bad_valid, bm_tab_valid;
   int bm_table_max_keys;     // BN254_OPT_BITMAP_TABLE_MAX_KEYS: tables while n_keys <= this (0 = never)
   int bm_route;              // BN254_OPT_BITMAP_ROUTE (developer option): 0 by the rule above, 1 always tables, 2 never
+  // ... randomised (bn254_bitmap_rand.hip), as the aggr_* members above
+  int bmr_min_tuples;        // BN254_OPT_BITMAP_RAND_MIN_TUPLES: the randomised bitmap call from this many tuples on
+  int bmr_group_tuples;      // BN254_OPT_BITMAP_RAND_GROUP_TUPLES: tuples per group of its combined checks
+  int bmr_max_keys;          // BN254_OPT_BITMAP_RAND_MAX_KEYS: ... and only while the registered set has at most this many keys
+  uint8_t* bmr_buf;          // its scratch, grown on demand
+  size_t bmr_cap;
+  uint32_t* bmr_stats;       // what its last run did on the device (bn254_debug_bitmap_rand_last); inside bmr_buf
+  int bmr_last_ran;          // ... and whether the last call took the randomised route at all
+  AggrLast bmr_last;         // ... and where it left its groups (bn254_debug_bitmap_rand_sums)
 };
 
 struct ScopedEvents {
@@ -248,4 +261,7 @@ BN_HIDDEN int launch_rand_tail_lane(bn254_ctx* c, hipStream_t s, size_t n_groups
 BN_HIDDEN int launch_miller_verify_lane(bn254_ctx* c, hipStream_t s, size_t n, const uint32_t* map, const uint32_t* count);
 BN_HIDDEN int launch_final_exp_lane(bn254_ctx* c, hipStream_t s, size_t n, size_t k, size_t item_stride, size_t pair_stride, int use_hash, uint8_t* gt_out,
                                     uint8_t* status_out, int raw_only, size_t base, const uint32_t* map, const uint32_t* count);
+// signer bitmaps (bn254_bitmap.hip): does a call read the subset tables; the bad-bit vector and, when read, the tables built on the call's stream
+BN_HIDDEN bool bm_wants_tables(const bn254_ctx* c);
+BN_HIDDEN int bm_prepare(bn254_ctx* c, hipStream_t s, bool tables);
 BN_HIDDEN int launch_encode_g1(bn254_ctx* c, hipStream_t s, size_t n, int px, int inf_plane, uint8_t* out, uint8_t* status_out);

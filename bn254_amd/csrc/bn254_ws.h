@@ -261,6 +261,16 @@ struct BmKeysArg { const int32_t* xy; const uint8_t* st; const uint8_t* inf; con
 __attribute__((visibility("hidden"))) int bn254_pair_bitmap_sum(const uint32_t* d_bits, size_t bm_words, size_t n, BmKeysArg keys, const int32_t* rec,
                                                                 const uint8_t* rec_inf, Ws ws, hipStream_t s);
 
+// ... randomised (bn254_bitmap_rand.hip), with two host helpers of bn254_aggdist.hip: the device-side prefix sum, and the slots
+// of the slot kernel over n groups of table pairs [lo, hi) (count, scan, map)
+#define BITMAP_RAND_MIN_TUPLES_DEFAULT 81920       // BN254_OPT_BITMAP_RAND_MIN_TUPLES: the randomised route from this many tuples on (measured: DESIGN.md §10d)
+#define BITMAP_RAND_MAX_KEYS_DEFAULT 256           // BN254_OPT_BITMAP_RAND_MAX_KEYS: ... while the set has at most this many keys (its sums grow with n_keys / 8 per
+                                                   //     tuple: at 1 024 keys it loses at every size measured)
+#define BITMAP_RAND_GROUP_TUPLES_DEFAULT 4096      // BN254_OPT_BITMAP_RAND_GROUP_TUPLES: tuples per group of its combined checks (the sweeps at 65 536 and 2^20 x 256)
+__attribute__((visibility("hidden"))) int bn254_aggd_scan_add(hipStream_t s, const uint64_t* in, size_t n, uint64_t* out, uint64_t* tot);
+__attribute__((visibility("hidden"))) int bn254_aggd_keyed_slot_map(hipStream_t s, size_t n, const uint64_t* lo, const uint64_t* hi, int width,
+                                                                    uint64_t* kincl, uint64_t* tot, size_t n_slots, uint32_t* slot_agg);
+
 // key deduplication of the exact verify (bn254_keydedup.hip): per call, the distinct keys of the batch and their line tables in the
 // KeyTable format above, built on a stream of the context beside decode and hash; the route (tables or the generic loop) is decided on the device
 #define KEY_DEDUP_MAX_KEYS_DEFAULT 1024            // tables for at most this many distinct keys per call (12.5 KB + 6.3 KB of raw c2 each)

@@ -44,6 +44,9 @@ OPT_BITMAP_ROUTE = 29              # ... test hook: 0 by that rule, 1 always tab
 OPT_HASH_SCHEDULE = 30             # hash-to-G1 above 4096 messages: 0 by size, 1 multi-round schedule, 2 one wide round + finish and tail in one launch
 OPT_HASH_WIDE_WIDTH = 31           # ... measurement knob: counters per message in the wide round (0 = by size)
 OPT_HASH_TAIL_CHUNK = 32           # ... test seam: counters per lane group and pass in the tail (power of two, 2 .. 32; default 32)
+OPT_BITMAP_RAND_MIN_TUPLES = 33    # randomised signer bitmaps: the exact bitmap call below this many tuples
+OPT_BITMAP_RAND_GROUP_TUPLES = 34  # ... tuples per group of its combined checks (developer option)
+OPT_BITMAP_RAND_MAX_KEYS = 35      # ... the exact bitmap call when more keys than this are registered
 
 
 class NativeError(RuntimeError):
@@ -158,7 +161,10 @@ class Engine:
         dict(nagg, verdict, s, pairs=[(key index, 64-byte bucket sum), ...]) per group, the groups without an aggregate included; [] when
         the call took the exact route.  Read it directly after that call: ANY later call on the engine (a sign, a sum, a registration)
         may reuse the workspace, and the hook then returns whatever lies there"""
-        name, f = "bn254_debug_agg_rand_sums", self._lib.bn254_debug_agg_rand_sums
+        return self._debug_rand_sums("bn254_debug_agg_rand_sums")
+
+    def _debug_rand_sums(self, name):
+        f = getattr(self._lib, name)
         dims = (ctypes.c_uint64 * 2)()
         _check(name, f(self._h, dims, 0, 0, None, None, None, None, None, None))
         ng, ntp = int(dims[0]), int(dims[1])
@@ -170,6 +176,18 @@ class Engine:
         assert (int(dims[0]), int(dims[1])) == (ng, ntp)
         return [dict(nagg=int(nagg[g]), verdict=verdict.raw[g], s=s.raw[64 * g:64 * g + 64],
                      pairs=[(int(keys[t]), pts.raw[64 * t:64 * t + 64]) for t in range(int(first[g]), int(first[g + 1]))]) for g in range(ng)]
+
+    def debug_bitmap_rand_last(self):
+        """what the last batch_verify_keyed_bitmap_randomized[_device] did: dict(ran, groups, table_pairs, failed_groups, rechecked, single_groups)"""
+        o = (ctypes.c_uint64 * 6)()
+        _check("bn254_debug_bitmap_rand_last", self._lib.bn254_debug_bitmap_rand_last(self._h, o))
+        return dict(zip(("ran", "groups", "table_pairs", "failed_groups", "rechecked", "single_groups"), (int(x) for x in o)))
+
+    def debug_bitmap_rand_sums(self):
+        """the G1 side of that call's group checks as it left them (include/bn254_hip.h: bn254_debug_bitmap_rand_sums), in the format of
+        debug_agg_rand_sums: one dict(nagg, verdict, s, pairs=[(key index, 64-byte T_{g,j}), ...]) per group; [] when the call took the exact
+        route.  Read it directly after that call"""
+        return self._debug_rand_sums("bn254_debug_bitmap_rand_sums")
 
     def last_kernel_ms(self):
         ms = (ctypes.c_float * 4)()
@@ -491,6 +509,24 @@ class Engine:
     def batch_verify_keyed_bitmap_device(self, d_msgs, d_off, d_sigs, d_signer_bits, bm_words, n, d_status, flags=0, stream=None):
         _check("bn254_batch_verify_keyed_bitmap_device",
                self._lib.bn254_batch_verify_keyed_bitmap_device(self._h, d_msgs, d_off, d_sigs, d_signer_bits, bm_words, n, flags, d_status, stream))
+
+    def batch_verify_keyed_bitmap_randomized(self, messages, sigs, bitmaps, bm_words, seed32, flags=0):
+        """batch_verify_keyed_bitmap with the pairing checks of whole groups of tuples combined under random weights from seed32
+        (include/bn254_hip.h: bn254_batch_verify_keyed_bitmap_randomized).  Returns the status bytes."""
+        n = len(messages)
+        assert len(sigs) == n * G1_BYTES and len(bitmaps) == n * bm_words and len(seed32) == 32
+        msgs, off = pack_messages(messages)
+        bits = (ctypes.c_uint32 * max(len(bitmaps), 1))(*bitmaps)
+        status = ctypes.create_string_buffer(max(n, 1))
+        _check("bn254_batch_verify_keyed_bitmap_randomized",
+               self._lib.bn254_batch_verify_keyed_bitmap_randomized(self._h, msgs, off, bytes(sigs), bits, bm_words, n, flags, bytes(seed32), status))
+        return status.raw[:n]
+
+    def batch_verify_keyed_bitmap_randomized_device(self, d_msgs, d_off, d_sigs, d_signer_bits, bm_words, n, seed32, d_status, flags=0, stream=None):
+        assert len(seed32) == 32
+        _check("bn254_batch_verify_keyed_bitmap_randomized_device",
+               self._lib.bn254_batch_verify_keyed_bitmap_randomized_device(self._h, d_msgs, d_off, d_sigs, d_signer_bits, bm_words, n, flags,
+                                                                           bytes(seed32), d_status, stream))
 
     def batch_verify_keyed_randomized(self, messages, sigs, key_idx, seed32, flags=0):
         n = len(messages)

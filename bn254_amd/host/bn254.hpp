@@ -252,23 +252,40 @@ struct ECDSA {
   // (include/bn254_hip.h: bn254_batch_verify_keyed_bitmap): result[i] == 0 iff e(H(m_i), sum of the named keys) * e(sigma_i, -G2) == 1;
   // 2 (IndexOutOfBounds) for an index outside the set — every such index lands on the one bit the bitmaps carry past the set.
   struct SignerItem { std::vector<uint8_t> message; Signature signature; std::vector<uint32_t> signer_indices; };
-  static std::vector<uint8_t> batch_verify_keyed_signers(const std::vector<SignerItem>& items, size_t n_keys, Engine& e = Engine::default_engine()) {
-    const size_t n = items.size(), bm_words = n_keys / 32 + 1;
-    std::vector<uint64_t> off(n + 1, 0);
-    std::vector<uint8_t> msgs, sigs(n * 64), status(n, 0);
-    std::vector<uint32_t> bits(n * bm_words, 0);
+  // the items packed as the bitmap calls take them
+  struct PackedSigners { size_t bm_words; std::vector<uint64_t> off; std::vector<uint8_t> msgs, sigs; std::vector<uint32_t> bits; };
+  static PackedSigners pack_signers(const std::vector<SignerItem>& items, size_t n_keys) {
+    const size_t n = items.size();
+    PackedSigners p{n_keys / 32 + 1, std::vector<uint64_t>(n + 1, 0), {}, std::vector<uint8_t>(n * 64), {}};
+    p.bits.assign(n * p.bm_words, 0);
     for (size_t i = 0; i < n; ++i) {
-      off[i] = msgs.size();
-      msgs.insert(msgs.end(), items[i].message.begin(), items[i].message.end());
-      std::memcpy(&sigs[64 * i], items[i].signature.raw.data(), 64);
+      p.off[i] = p.msgs.size();
+      p.msgs.insert(p.msgs.end(), items[i].message.begin(), items[i].message.end());
+      std::memcpy(&p.sigs[64 * i], items[i].signature.raw.data(), 64);
       for (uint32_t j : items[i].signer_indices) {
         const size_t b = j < n_keys ? j : n_keys;
-        bits[i * bm_words + b / 32] |= 1u << (b % 32);
+        p.bits[i * p.bm_words + b / 32] |= 1u << (b % 32);
       }
     }
-    off[n] = msgs.size();
-    check_rc("bn254_batch_verify_keyed_bitmap",
-             bn254_batch_verify_keyed_bitmap(e.raw(), msgs.data(), off.data(), sigs.data(), bits.data(), bm_words, n, 0, status.data()));
+    p.off[n] = p.msgs.size();
+    return p;
+  }
+  static std::vector<uint8_t> batch_verify_keyed_signers(const std::vector<SignerItem>& items, size_t n_keys, Engine& e = Engine::default_engine()) {
+    const PackedSigners p = pack_signers(items, n_keys);
+    std::vector<uint8_t> status(items.size(), 0);
+    check_rc("bn254_batch_verify_keyed_bitmap", bn254_batch_verify_keyed_bitmap(e.raw(), p.msgs.data(), p.off.data(), p.sigs.data(), p.bits.data(), p.bm_words,
+                                                                                items.size(), 0, status.data()));
+    return status;
+  }
+  // the same through the combined checks of whole groups of items (include/bn254_hip.h: bn254_batch_verify_keyed_bitmap_randomized): a non-zero
+  // status is exact, a zero is wrong with probability <= 2^-128 per group (2^-64 with rand64) for a fresh secret seed
+  static std::vector<uint8_t> batch_verify_keyed_signers_randomized(const std::vector<SignerItem>& items, size_t n_keys, const std::array<uint8_t, 32>& seed,
+                                                                    bool rand64 = false, Engine& e = Engine::default_engine()) {
+    const PackedSigners p = pack_signers(items, n_keys);
+    std::vector<uint8_t> status(items.size(), 0);
+    check_rc("bn254_batch_verify_keyed_bitmap_randomized",
+             bn254_batch_verify_keyed_bitmap_randomized(e.raw(), p.msgs.data(), p.off.data(), p.sigs.data(), p.bits.data(), p.bm_words, items.size(),
+                                                        rand64 ? BN254_FLAG_RAND64 : 0, seed.data(), status.data()));
     return status;
   }
   static void verify_keyed_signers(const std::vector<uint8_t>& message, const Signature& signature, const std::vector<uint32_t>& signer_indices,

@@ -371,6 +371,39 @@ int bn254_batch_verify_keyed_bitmap(bn254_ctx *ctx, const uint8_t *msgs, const u
 int bn254_batch_verify_keyed_bitmap_device(bn254_ctx *ctx, const uint8_t *d_msgs, const uint64_t *d_msg_off, const uint8_t *d_sigs,
                                            const uint32_t *d_signer_bits, size_t bm_words, size_t n, uint32_t flags, uint8_t *d_status, void *stream);
 
+/* bn254_batch_verify_keyed_bitmap_randomized[_device]: the same inputs and status bytes as bn254_batch_verify_keyed_bitmap with the same flags,
+ * with the pairing checks of many tuples combined.  Rules 1-3 (sigma's decode, the lowest bad bit, the hash status) are exact, and so are the
+ * argument checks, BN254_E_MISALIGNED, the _device conventions and the BN254_OPT_MAX_CHUNK slicing, which are the bitmap call's.  A non-zero
+ * status is always the exact one; a zero is wrong with probability <= 2^-128 per group (2^-64 with BN254_FLAG_RAND64) for a fresh secret seed32.
+ *   r_i = rand_scalar(seed32, i) as in the other randomised calls (SHA-256(seed32 || le64(i)), 0 -> 1) with i = the tuple's index in the
+ *   caller's arrays, also under slicing; BN254_FLAG_RAND64 and BN254_FLAG_RAND_GLV as documented there; the other flags apply to sigma.
+ *   Groups: tuple i of a slice belongs to group (i - slice_lo) / G, G = BN254_OPT_BITMAP_RAND_GROUP_TUPLES; tuples with a non-zero status from
+ *   rules 1-3 take no part.  Every aggregate key is a sum over the registered set, so the combined check regroups by key: a group passes iff
+ *       prod_j e(T_j, pk_j) * e(S, -G2) == 1,   T_j = sum_{i in g, bit j of tuple i} r_i H(m_i),   S = sum_{i in g} r_i sigma_i
+ *   over the keys j with a contributor (registered identity keys take no part; a T_j that comes out as the identity contributes 1) — at most
+ *   n_keys + 1 table-driven Miller pairs and ONE final exponentiation per group, every G2 argument a registered line table.  Per tuple there
+ *   remain the hash, two scalar ladders and one G1 addition per non-zero bitmap BYTE (the byte buckets of a window are folded into its eight
+ *   key sums once per group), whatever the popcount.  A group with ONE tuple at the check takes r = 1 and its verdict is final.  Every tuple
+ *   of a failed group of two or more is verified exactly on the device (aggregate key by the bitmap call's summation, then a verify), with
+ *   no host synchronisation (the _device form only enqueues).
+ *   The exact bitmap call, same bytes, when no keys are registered, pair lanes are off, n < BN254_OPT_BITMAP_RAND_MIN_TUPLES, more keys are
+ *   registered than BN254_OPT_BITMAP_RAND_MAX_KEYS, or the call (a
+ *   slice of it) is so large that its buckets, sort elements or workspace entries would not be numbered in 32 bits.
+ * Security: as bn254_batch_verify_keyed_bitmap — a proof of possession of every registered key is assumed.  seed32 is host memory in both forms.
+ * Which call when (measured on an MI355X, every tuple valid, two thirds of the keys signing, 128-bit weights): over
+ * 256 keys this call from 81 920 tuples on — 13.2 ms against the exact call's 16.9 there, 17.8 against 20.7 at 131 072, 104 against 165 ms at
+ * 2^20 (1.58 x; 1.79 x with BN254_FLAG_RAND64) — and the exact call below: at 65 536 tuples it takes 11.1 ms against 10.6, at 16 384 6.7
+ * against 4.9.  Over 1 024 keys the exact call at every size measured (65 536 tuples: 22.8 ms against 12.5): the G1 side costs one addition
+ * per bitmap byte and tuple.  The defaults follow that: below BN254_OPT_BITMAP_RAND_MIN_TUPLES (81 920) tuples or above
+ * BN254_OPT_BITMAP_RAND_MAX_KEYS (256) keys this call IS the exact call.  Key sets between 256 and 1 024 keys were not measured.  Where many
+ * groups are expected to fail, the exact call: a failed group pays the exact price on top. */
+int bn254_batch_verify_keyed_bitmap_randomized(bn254_ctx *ctx, const uint8_t *msgs, const uint64_t *msg_off /* n+1 */, const uint8_t *sigs /* n*64 */,
+                                               const uint32_t *signer_bits /* n*bm_words */, size_t bm_words, size_t n, uint32_t flags,
+                                               const uint8_t *seed32, uint8_t *status /* n */);
+int bn254_batch_verify_keyed_bitmap_randomized_device(bn254_ctx *ctx, const uint8_t *d_msgs, const uint64_t *d_msg_off, const uint8_t *d_sigs,
+                                                      const uint32_t *d_signer_bits, size_t bm_words, size_t n, uint32_t flags,
+                                                      const uint8_t *seed32 /* host memory */, uint8_t *d_status, void *stream);
+
 /* compressed wire formats (src/utils.rs:84-104, :130-158): out = uncompressed point, status as
  * bn::G1::from_compressed / bn::G2::from_compressed report through src/types.rs:91-93, :233-237, checked in the order
  * those decoders work (an input with several faults reports the first):
@@ -432,6 +465,12 @@ int bn254_ctx_set_profiling(bn254_ctx *ctx, int enabled);
 #define BN254_OPT_BITMAP_TABLE_MAX_KEYS 28 /* bn254_batch_verify_keyed_bitmap: subset tables of the registered set while it has at most this many keys
                                              (default 4096: 5 152 B per key, 21 MB); above, or with 0, the selected keys are added one by one.
                                              Same status bytes */
+#define BN254_OPT_BITMAP_RAND_MIN_TUPLES 33 /* bn254_batch_verify_keyed_bitmap_randomized: calls (slices) with fewer tuples take the exact bitmap call
+                                             (same statuses).  Default 81920, the smallest measured size from which the 128-bit variant wins at
+                                             256 keys; 0 = always randomised */
+#define BN254_OPT_BITMAP_RAND_MAX_KEYS 35 /* ... and when more keys than this are registered (same statuses): the G1 side costs one addition per
+                                           bitmap byte and tuple, which at 1 024 keys outweighs what the route saves at every size measured.
+                                           Default 256 */
 int bn254_ctx_set_option(bn254_ctx *ctx, int option, int value);
 /* per-kernel times of the last verify-shaped call with profiling on (HIP events on the call's stream):
  * ms[0] decode, ms[1] hash-to-G1, ms[2] Miller loop, ms[3] final exponentiation.  The host-pointer bn254_batch_verify runs
@@ -579,6 +618,8 @@ int bn254_mgpu_batch_hash_to_g1(bn254_mgpu *mg, const uint8_t *msgs, const uint6
                                     with keys registered.  Same status bytes. */
 #define BN254_OPT_AGG_RAND_GROUP_PAIRS 27 /* bn254_batch_aggregate_verify_distinct_keyed_randomized: messages per group of the combined checks (default
                                            1024, at least 1; the number of keys when that is larger).  Same status bytes */
+#define BN254_OPT_BITMAP_RAND_GROUP_TUPLES 34 /* bn254_batch_verify_keyed_bitmap_randomized: tuples per group of the combined checks (default 4096, from
+                                               the sweeps at 65 536 and 2^20 x 256; at least 1).  Same status bytes */
 #define BN254_OPT_BITMAP_ROUTE 29 /* bn254_batch_verify_keyed_bitmap, test hook: 0 (default) = by BN254_OPT_BITMAP_TABLE_MAX_KEYS, 1 = always the subset
                                     tables, 2 = always key by key.  Same status bytes */
 #define BN254_OPT_ASSUME_FREE_MB 18 /* test knob for the automatic slicing rule (BN254_OPT_MAX_CHUNK = 0): price the workspace of a batch against this many MB
@@ -608,6 +649,16 @@ int bn254_debug_agg_rand_last(bn254_ctx *ctx, uint64_t out[6]);
  * and its point sum r_i H(m_j) over the group's entries of that key (64 bytes).  Otherwise only dims is written.  Synchronises the device. */
 int bn254_debug_agg_rand_sums(bn254_ctx *ctx, uint64_t dims[2], size_t group_cap, size_t pair_cap, uint32_t *nagg, uint8_t *verdict,
                               uint8_t *s_g /* groups*64 */, uint64_t *first_pair /* groups+1 */, uint32_t *pair_key, uint8_t *pair_point /* pairs*64 */);
+/* what the last bn254_batch_verify_keyed_bitmap_randomized[_device] did (its last slice): out = {1 if it took the randomised route, groups that
+ * reached the check, table pairs of all group checks (S_g's included), failed groups, tuples re-checked, groups of one tuple (r = 1)}; all 0
+ * when it took the exact route.  Synchronises the device. */
+int bn254_debug_bitmap_rand_last(bn254_ctx *ctx, uint64_t out[6]);
+/* the G1 side of the group checks of that call, read from where it left them, in the format of bn254_debug_agg_rand_sums: dims = {groups =
+ * ceil(n / G), table pairs of all groups}; per group its tuples at the check, the status byte of its check, S_g, and its (key index, T_{g,j})
+ * pairs in key order — one per key with a contributor, zeros = a sum that came out as the identity.  The call itself launches nothing for
+ * this.  Synchronises the device. */
+int bn254_debug_bitmap_rand_sums(bn254_ctx *ctx, uint64_t dims[2], size_t group_cap, size_t pair_cap, uint32_t *nagg, uint8_t *verdict,
+                                 uint8_t *s_g /* groups*64 */, uint64_t *first_pair /* groups+1 */, uint32_t *pair_key, uint8_t *pair_point /* pairs*64 */);
 /* test hooks: element-wise field/tower operations on byte-encoded operands, used by the parity
  * tests to compare each layer of the HIP arithmetic with the oracle.
  *   op: 0 mul, 1 add, 2 sub, 3 inverse(a), 4 square(a), 5 sqrt(a) (status 6 if none)   [Fq, 32 B]

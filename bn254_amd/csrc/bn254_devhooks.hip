@@ -164,12 +164,28 @@ int bn254_debug_key_dedup_last(bn254_ctx* c, uint32_t out[5]) {
   if (!c->kd_last_run || !c->kd_ctl) return 0;
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(out + 1, c->kd_ctl, KD_CTL_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out + 1, c->kd_ctl, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost));
   out[0] = 1;
   return 0;
 }
-// the line tables as they stand on the device: which = 0 the per-call tables of the last key dedup (key ids as k_kd_insert gave them; rep = the
-// item that represents each key), 1 the registered tables of bn254_ctx_register_keys (rep is not written)
+// what that call did with the key cache (BN254_OPT_KEY_CACHE; k_kd_match): out = {ran, distinct keys D, keys found in the cache, keys built,
+// dropped (1 the misses did not fit the free rows, 2 the cache was emptied before the call: other flags or options, moved buffers, the
+// option at 0)}; a call the thresholds refuse looks nothing up: hits = built = 0.  Synchronises the device.
+int bn254_debug_key_cache_last(bn254_ctx* c, uint32_t out[5]) {
+  if (!c || !out) return BN254_E_BAD_ARGUMENT;
+  for (int i = 0; i < 5; ++i) out[i] = 0;
+  if (!c->kd_last_run || !c->kd_ctl) return 0;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipDeviceSynchronize());
+  uint32_t ctl[KD_CTL_WORDS];
+  HIP_TRY(hipMemcpy(ctl, c->kd_ctl, sizeof ctl, hipMemcpyDeviceToHost));
+  out[0] = 1; out[1] = ctl[KD_CTL_D]; out[2] = ctl[KD_CTL_HITS]; out[3] = ctl[KD_CTL_BUILD]; out[4] = ctl[KD_CTL_DROPPED];
+  return 0;
+}
+// the line tables as they stand on the device: which = 0 the tables of the keys of the last key dedup (key ids as k_kd_insert gave them; rep = the
+// item that represents each key; each key's table is read from the row the cache keeps it in; a call the thresholds refused has none:
+// BN254_E_BAD_ARGUMENT, nothing written), 1 the registered tables of
+// bn254_ctx_register_keys (rep is not written)
 int bn254_debug_key_tables(bn254_ctx* c, int which, size_t first, size_t count, int32_t* lines, uint32_t* rep, uint8_t* st, uint8_t* inf) {
   if (!c || !lines || (which != 0 && which != 1)) return BN254_E_BAD_ARGUMENT;
   HIP_TRY(hipSetDevice(c->device));
@@ -182,8 +198,28 @@ int bn254_debug_key_tables(bn254_ctx* c, int which, size_t first, size_t count, 
     if (!c->kd_last_run || !c->kd_ctl || !c->kd_lines_last) return BN254_E_BAD_ARGUMENT;
     HIP_TRY(hipMemcpy(ctl, c->kd_ctl, sizeof ctl, hipMemcpyDeviceToHost));
     if (first + count > ctl[KD_CTL_D] || first + count > c->kd_keys_cap) return BN254_E_BAD_ARGUMENT;
-    src = c->kd_lines_last; src_st = c->kd_st_last; src_inf = c->kd_inf_last;
+    if (ctl[KD_CTL_BUILD] + ctl[KD_CTL_HITS] != ctl[KD_CTL_D]) return BN254_E_BAD_ARGUMENT;   // a call the thresholds refused: it has no tables (nothing written)
     if (rep) HIP_TRY(hipMemcpy(rep, c->kd_rep_last + first, count * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    // rows, statuses and identity flags in one host block: [count] u32 | [kd_keys_cap] st | [kd_keys_cap] inf
+    const size_t cap = c->kd_keys_cap;
+    uint8_t* h = (uint8_t*)malloc(count * sizeof(uint32_t) + 2 * cap + 1);
+    if (!h) return BN254_E_NO_MEMORY;
+    const uint32_t* rows = (const uint32_t*)h;
+    uint8_t *h_st = h + count * sizeof(uint32_t), *h_inf = h_st + cap;
+    hipError_t e = count ? hipMemcpy(h, c->kd_row_of_last + first, count * sizeof(uint32_t), hipMemcpyDeviceToHost) : hipSuccess;
+    if (e == hipSuccess) e = hipMemcpy(h_st, c->kd_st_last, cap, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(h_inf, c->kd_inf_last, cap, hipMemcpyDeviceToHost);
+    int rc = e == hipSuccess ? 0 : -(int)e;
+    for (size_t k = 0; k < count && !rc; ++k) {
+      const size_t r = rows[k];
+      if (r >= cap) { rc = BN254_E_BAD_ARGUMENT; break; }
+      e = hipMemcpy(lines + k * per_key, c->kd_lines_last + r * per_key, per_key * sizeof(int32_t), hipMemcpyDeviceToHost);
+      if (e != hipSuccess) rc = -(int)e;
+      if (st) st[k] = h_st[r];
+      if (inf) inf[k] = h_inf[r];
+    }
+    free(h);
+    return rc;
   } else {
     if (!c->key_lines || first + count > c->n_keys) return BN254_E_BAD_ARGUMENT;
     src = c->key_lines; src_st = c->key_st; src_inf = c->key_inf;

@@ -529,7 +529,8 @@ static int kd_reserve(bn254_ctx* c, size_t n, KeyDedup& kd) {
     c->kd_items_cap = c->kd_keys_cap = 0;
     c->kd_ctl = nullptr;
     c->kd_lines_last = nullptr;
-    if (hipMalloc((void**)&c->kd_buf, items_cap * KD_BYTES_PER_ITEM + keys_cap * KD_BYTES_PER_KEY + 256) != hipSuccess) {
+    c->kd_cache_valid = false;                         // the cache lived in the freed buffer: the next call starts from an empty one
+    if (hipMalloc((void**)&c->kd_buf, items_cap * KD_BYTES_PER_ITEM + keys_cap * KD_BYTES_PER_KEY + 512) != hipSuccess) {
       (void)hipGetLastError();                       // no room for the tables: this call takes the generic route (the caller sees no error)
       c->kd_buf = nullptr;
       return KD_NO_ROOM;
@@ -552,7 +553,16 @@ static int kd_reserve(bn254_ctx* c, size_t n, KeyDedup& kd) {
   c->kd_ctl = kd.ctl;
   kd.st = take(c->kd_keys_cap);
   kd.inf = take(c->kd_keys_cap);
-  c->kd_lines_last = kd.lines; c->kd_rep_last = kd.rep; c->kd_st_last = kd.st; c->kd_inf_last = kd.inf;
+  kd.row_of = (uint32_t*)take(c->kd_keys_cap * 4);
+  kd.build_row = (uint32_t*)take(c->kd_keys_cap * 4);
+  kd.build_rep = (uint32_t*)take(c->kd_keys_cap * 4);
+  kd.c_keys = (uint32_t*)take(c->kd_keys_cap * 128);
+  size_t index_slots = 1;
+  while (index_slots < 2 * keys) index_slots <<= 1;                  // at most half full: < 4 x keys_cap words
+  kd.c_index = (uint32_t*)take(4 * c->kd_keys_cap * 4);
+  kd.c_state = (uint32_t*)take(4);
+  kd.index_mask = (uint32_t)(index_slots - 1);
+  c->kd_lines_last = kd.lines; c->kd_rep_last = kd.rep; c->kd_st_last = kd.st; c->kd_inf_last = kd.inf; c->kd_row_of_last = kd.row_of;
   kd.slot_mask = (uint32_t)(slots - 1);
   kd.hash_mask = c->kd_hash_bits > 0 && c->kd_hash_bits < 32 ? (1u << c->kd_hash_bits) - 1 : 0xFFFFFFFFu;
   kd.max_keys = (uint32_t)keys;
@@ -795,6 +805,7 @@ int bn254_ctx_create(int hip_device, bn254_ctx** out) {
   c->key_dedup = 1;
   c->kd_max_keys = KEY_DEDUP_MAX_KEYS_DEFAULT;
   c->kd_min_mult = KEY_DEDUP_MIN_MULT_DEFAULT;
+  c->kd_cache = 1;
   c->bm_table_max_keys = BITMAP_TABLE_MAX_KEYS_DEFAULT;
   c->device = hip_device;
   hipError_t err = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
@@ -804,8 +815,10 @@ int bn254_ctx_create(int hip_device, bn254_ctx** out) {
   if (err == hipSuccess) err = hipStreamCreateWithFlags(&c->kd_stream, hipStreamNonBlocking);
   if (err == hipSuccess) err = hipEventCreateWithFlags(&c->kd_fork, hipEventDisableTiming);
   if (err == hipSuccess) err = hipEventCreateWithFlags(&c->kd_join, hipEventDisableTiming);
+  if (err == hipSuccess) err = hipEventCreateWithFlags(&c->kd_done, hipEventDisableTiming);
   for (int i = 0; i < 5 && err == hipSuccess; ++i) err = hipEventCreate(&c->ev[i]);
   if (err != hipSuccess) {
+    if (c->kd_done) (void)hipEventDestroy(c->kd_done);
     if (c->kd_join) (void)hipEventDestroy(c->kd_join);
     if (c->kd_fork) (void)hipEventDestroy(c->kd_fork);
     if (c->kd_stream) (void)hipStreamDestroy(c->kd_stream);
@@ -852,6 +865,7 @@ void bn254_ctx_destroy(bn254_ctx* c) {
   for (int i = 0; i < 5; ++i) (void)hipEventDestroy(c->ev[i]);
   (void)hipEventDestroy(c->kd_fork);
   (void)hipEventDestroy(c->kd_join);
+  (void)hipEventDestroy(c->kd_done);
   (void)hipStreamDestroy(c->kd_stream);
   (void)hipEventDestroy(c->copy_done);
   (void)hipEventDestroy(c->last_done);
@@ -949,7 +963,8 @@ int bn254_ctx_set_option(bn254_ctx* c, int option, int value) {
   if (option == BN254_OPT_KEY_DEDUP) { if (value < 0 || value > 1) return BN254_E_BAD_ARGUMENT; c->key_dedup = value; return 0; }
   if (option == BN254_OPT_KEY_DEDUP_MAX_KEYS) { if (value < 0 || value > KEY_DEDUP_MAX_KEYS_LIMIT) return BN254_E_BAD_ARGUMENT; c->kd_max_keys = value; return 0; }
   if (option == BN254_OPT_KEY_DEDUP_MIN_MULT) { if (value < 1) return BN254_E_BAD_ARGUMENT; c->kd_min_mult = value; return 0; }
-  if (option == BN254_OPT_KEY_DEDUP_FORCE_GENERIC) { c->kd_force_generic = value != 0; return 0; }
+  if (option == BN254_OPT_KEY_DEDUP_FORCE_GENERIC) { c->kd_force_generic = value == 2 ? 2 : value != 0; return 0; }
+  if (option == BN254_OPT_KEY_CACHE) { if (value < 0 || value > 1) return BN254_E_BAD_ARGUMENT; c->kd_cache = value; c->kd_cache_valid = false; return 0; }
   if (option == BN254_OPT_KEY_DEDUP_HASH_BITS) { if (value < 0 || value > 32) return BN254_E_BAD_ARGUMENT; c->kd_hash_bits = value; return 0; }
   if (option == BN254_OPT_AGGD_KEYED_ROUTE) { if (value < 0 || value > 3) return BN254_E_BAD_ARGUMENT; c->aggd_keyed_route = value; return 0; }
   if (option == BN254_OPT_AGG_RAND_MIN_PAIRS) { if (value < 0) return BN254_E_BAD_ARGUMENT; c->agg_rand_min_pairs = value; return 0; }
@@ -1051,6 +1066,7 @@ static int verify_tail(bn254_ctx* c, hipStream_t s, size_t n, uint8_t* d_status,
     if ((rc = bn254_pair_miller_verify(n, c->ws, nullptr, kd->ctl + KD_CTL_GENERIC_N, s))) return rc;
     PROF_MARK(3);
     if ((rc = bn254_pair_final_exp(n, c->ws, 1, d_status, nullptr, nullptr, s))) return rc;
+    HIP_TRY(hipEventRecord(c->kd_done, s));          // the next call of this route waits for it, whatever its stream (bn254_batch_verify_device)
   } else if (split) {
     const unsigned g = grid_for(n);
     k_miller_verify_split<<<2 * g, BN_WAVE, 0, s>>>(n, c->ws.stride / 2, g, c->ws);
@@ -1103,10 +1119,22 @@ int bn254_batch_verify_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_
   CallDone call_done(c, s);
   PROF_MARK(0);
   if (key_dedup) {                                   // forked behind everything the caller's stream holds so far: d_pks is readable
+    // The key cache outlives the call: its rows are written on kd_stream and read by this call's Miller kernel and by the next call's match
+    // pass, and the dedup buffers beside it are rewritten by every call.  The next call may come on ANOTHER caller stream with no host sync in
+    // between, so the context orders it itself: this call — its side-stream work through kd_fork — starts behind kd_done, recorded at the
+    // end of the previous call of this route (never recorded yet: no wait).
+    HIP_TRY(hipStreamWaitEvent(s, c->kd_done, 0));
+    // a cached row depends on the key's bytes and on what the builder ran under: the decode flags, the hash seam of the index and the row
+    // capacity.  When one of them differs from the last call's (or the buffers moved, or the option was set) the cache starts empty.
+    const bool cache_reset = !c->kd_cache || !c->kd_cache_valid || c->kd_cache_flags != flags || c->kd_cache_max_keys != c->kd_max_keys ||
+                             c->kd_cache_hash_bits != c->kd_hash_bits;
+    c->kd_cache_valid = false;                       // until the call's dedup work is enqueued: a launch that fails leaves the cache to be emptied
     HIP_TRY(hipEventRecord(c->kd_fork, s));
     HIP_TRY(hipStreamWaitEvent(c->kd_stream, c->kd_fork, 0));
-    if ((rc = bn254_kd_enqueue(d_pks, n, flags, kd, c->kd_force_generic, c->kd_stream))) return rc;
+    if ((rc = bn254_kd_enqueue(d_pks, n, flags, kd, c->kd_force_generic, cache_reset, c->kd_cache, c->kd_stream))) return rc;
     HIP_TRY(hipEventRecord(c->kd_join, c->kd_stream));
+    c->kd_cache_valid = c->kd_cache != 0;
+    c->kd_cache_flags = flags; c->kd_cache_max_keys = c->kd_max_keys; c->kd_cache_hash_bits = c->kd_hash_bits;
   }
   k_decode_g1<<<grid_for(n), BN_WAVE, 0, s>>>(d_sigs, n, flags, c->ws, PL_P1X, BY_P1_INF, 0);
   if ((rc = launch_decode_g2(c, s, d_pks, n, flags, 1))) return rc;

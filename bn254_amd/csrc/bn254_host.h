@@ -80,15 +80,21 @@ struct bn254_ctx {
   int key_dedup;             // BN254_OPT_KEY_DEDUP: verify on lane pairs finds the batch's distinct keys and runs the keyed Miller loop (bn254_keydedup.hip)
   int kd_max_keys;           // BN254_OPT_KEY_DEDUP_MAX_KEYS
   int kd_min_mult;           // BN254_OPT_KEY_DEDUP_MIN_MULT
-  int kd_force_generic;      // BN254_OPT_KEY_DEDUP_FORCE_GENERIC (developer hook): the device-side decision always says "generic"
+  int kd_force_generic;      // BN254_OPT_KEY_DEDUP_FORCE_GENERIC (developer hook): 1 = the device-side decision always says "generic", 2 = the builder reports a degenerate line
   int kd_hash_bits;          // BN254_OPT_KEY_DEDUP_HASH_BITS (test seam): bits of the key hash kept (0 = all), to force collisions
   hipStream_t kd_stream;     // the dedup and the table builder run here, forked from and joined into the call's stream
   hipEvent_t kd_fork, kd_join;
+  hipEvent_t kd_done;        // recorded behind a dedup call on ITS stream; the next dedup call waits for it on the device before it touches the dedup buffers
+  int kd_cache;              // BN254_OPT_KEY_CACHE: the line tables stay between calls, a call builds only the keys it has not seen (default 1)
+  bool kd_cache_valid;       // ... the device-side cache holds what the last dedup call left (false: the next call empties it first)
+  uint32_t kd_cache_flags;   // ... and what its rows were built under: decode flags, KEY_DEDUP_MAX_KEYS, KEY_DEDUP_HASH_BITS
+  int kd_cache_max_keys, kd_cache_hash_bits;
   uint8_t* kd_buf;           // KeyDedup buffers (bn254_ws.h), grown on demand
   size_t kd_items_cap, kd_keys_cap;
   uint32_t* kd_ctl;          // the device-side decision of the last call that ran the dedup (bn254_debug_key_dedup_last)
   const int32_t* kd_lines_last;   // ... and its tables, representatives, statuses and identity flags (bn254_debug_key_tables; into kd_buf)
   const uint32_t* kd_rep_last;
+  const uint32_t* kd_row_of_last;   // ... key id of that call -> row of the tables
   const uint8_t *kd_st_last, *kd_inf_last;
   int kd_last_run;           // ... and whether the last bn254_batch_verify_device ran it at all
   int aggd_keyed_route;      // BN254_OPT_AGGD_KEYED_ROUTE (test and measurement knob): 0 by size, 1 / 2 the slot kernel of that width, 3 expanded keys

@@ -9,15 +9,25 @@
 //                 an entry only if all 128 bytes are equal (equal bytes decode equally, so grouping by bytes is exact).  The winner of a
 //                 slot takes the next dense key id (atomicAdd) and records itself as the key's representative.  A probe sequence longer
 //                 than KD_MAX_PROBES (an adversarial batch) sets KD_OVERFLOW: the call takes the generic route.
-//   k_kd_resolve  key_idx[i] = the id of item i's slot
+//   k_kd_match    THE KEY CACHE (BN254_OPT_KEY_CACHE): the tables are a pure function of a key's 128 bytes (and of the decode flags), and a validator
+//                 set's keys are the same from call to call, so the rows of kd.lines / st / inf stay between calls.  One workgroup looks each
+//                 of the call's D keys up in an index over the cached keys' bytes (kd.c_keys: the context's own copy; full 128-byte compare
+//                 again); a hit takes its row, a miss the next free row, in the order of the ids, and goes on the build list.  Misses that do
+//                 not fit the free rows drop the cache: the call builds all its keys into rows 0 .. D - 1, as a call without a cache does.
+//                 A batch the thresholds refuse looks nothing up and leaves the cache alone.
+//   k_kd_resolve  key_idx[i] = the ROW of the key of item i's slot
+//   (the two builder kernels run over the build list only and leave at entry when it is empty)
 //   k_kd_lines    one key on nine lane pairs, three keys per wave (bn254_kdlines.h: the lane machine's wave-T program, 204 product levels):
 //                 decode of the representative (the statuses of the items themselves stay what launch_decode_g2 writes), the twist-point
 //                 walk of g2_line_table with the RAW lines (c0, c1, c2) stored; a line with c2 = 0 (not reachable from the order-r subgroup,
-//                 but keys are not subgroup-checked under flags = 0) sets KD_DEGENERATE
+//                 but keys are not subgroup-checked under flags = 0) sets KD_DEGENERATE.  No key bytes that reach such a line are known (the
+//                 twist's order-10 069 points do not), so BN254_OPT_KEY_DEDUP_FORCE_GENERIC = 2 makes the builder report one for every key it builds
 //   k_kd_scale    one workgroup per key, one lane pair per line: c0 / c2, c1 / c2, canonical — the values of g2_line_table's emit, so the
 //                 tables are word for word those of registration; ONE inversion per key (a product tree over its 87 c2 in LDS)
 //   k_kd_decide   the route: keyed iff D <= max_keys, D * min_multiplicity <= n, no overflow, no degenerate line; written as the device-side
-//                 item counts the two Miller kernels read at entry (the unchosen one returns at once)
+//                 item counts the two Miller kernels read at entry (the unchosen one returns at once).  A keyed call COMMITS its build list to
+//                 the cache here (index entries, rows in use); a generic one — forced, or a degenerate line among the keys it built —
+//                 commits nothing, so a key with a degenerate line is never cached and the rows it wrote stay free.
 #include <hip/hip_runtime.h>
 
 #define BN_SPLIT_FP2 1
@@ -79,16 +89,92 @@ KERNEL_KD void k_kd_insert(const uint8_t* pks8, size_t n, KeyDedup kd) {
   kd.slot_of[i] = KD_EMPTY;
   atomicOr(&kd.ctl[KD_CTL_FLAGS], (uint32_t)KD_OVERFLOW);
 }
+// the table route is possible at all
+__device__ __forceinline__ bool kd_viable(const KeyDedup& kd, size_t n) {
+  const uint32_t d = kd.ctl[KD_CTL_D];
+  return d <= kd.max_keys && (size_t)d * kd.min_mult <= n && (kd.ctl[KD_CTL_FLAGS] & KD_OVERFLOW) == 0;
+}
+// One workgroup: the call's keys against the cache.  The index holds COMMITTED rows only (k_kd_decide), c_state[0] of them; the rows from there
+// on are free.  Rows are handed out by a prefix sum in the order of the ids, so a call into an empty cache gets row = id, the layout of a
+// call without a cache.
+#define KD_MATCH_WG 1024
+__global__ __launch_bounds__(KD_MATCH_WG) void k_kd_match(const uint8_t* pks8, size_t n, KeyDedup kd, int reset) {
+  __shared__ uint32_t scan[KD_MATCH_WG];
+  __shared__ uint32_t s_misses;
+  const uint32_t t = threadIdx.x;
+  const uint32_t* pks = (const uint32_t*)pks8;
+  if (reset) {
+    for (uint32_t s = t; s <= kd.index_mask; s += KD_MATCH_WG) kd.c_index[s] = KD_EMPTY;
+    if (t == 0) kd.c_state[0] = 0;
+  }
+  if (t == 0) s_misses = 0;
+  __syncthreads();
+  if (!kd_viable(kd, n)) {                                  // the generic route: nothing looked up, nothing built (KD_CTL_BUILD = KD_CTL_HITS = 0)
+    if (t == 0) kd.ctl[KD_CTL_DROPPED] = reset ? (uint32_t)KD_DROP_RESET : 0u;
+    return;
+  }
+  const uint32_t d = kd.ctl[KD_CTL_D];
+  uint32_t used = reset ? 0u : kd.c_state[0];
+  for (uint32_t id = t; id < d; id += KD_MATCH_WG) {
+    uint32_t row = KD_EMPTY;
+    if (used) {
+      uint32_t w[32];
+#pragma unroll
+      for (int k = 0; k < 32; ++k) w[k] = pks[(size_t)kd.rep[id] * 32 + k];
+      const uint32_t h = kd_hash(w, kd.hash_mask);
+      for (uint32_t probe = 0; probe <= kd.index_mask; ++probe) {     // the index is at most half full: an empty slot ends every probe sequence
+        const uint32_t r = kd.c_index[(h + probe) & kd.index_mask];
+        if (r == KD_EMPTY) break;
+        if (kd_same_key(kd.c_keys, r, w)) { row = r; break; }          // full 128-byte compare, as in k_kd_insert
+      }
+    }
+    kd.row_of[id] = row;
+    if (row == KD_EMPTY) atomicAdd(&s_misses, 1u);
+  }
+  __syncthreads();
+  const bool drop = used + s_misses > kd.max_keys;          // the misses do not fit: drop the cache, build every key of the call (D <= max_keys)
+  if (drop) {
+    for (uint32_t s = t; s <= kd.index_mask; s += KD_MATCH_WG) kd.c_index[s] = KD_EMPTY;
+    for (uint32_t id = t; id < d; id += KD_MATCH_WG) kd.row_of[id] = KD_EMPTY;
+    if (t == 0) kd.c_state[0] = 0;
+    used = 0;
+  }
+  uint32_t built = 0;                                       // misses among the ids below the current chunk (workgroup-uniform)
+  for (uint32_t id0 = 0; id0 < d; id0 += KD_MATCH_WG) {
+    const uint32_t id = id0 + t;
+    const bool miss = id < d && kd.row_of[id] == KD_EMPTY;   // written by this very thread above
+    scan[t] = miss ? 1u : 0u;
+    __syncthreads();
+    for (uint32_t o = 1; o < KD_MATCH_WG; o <<= 1) {         // inclusive prefix sum
+      const uint32_t v = t >= o ? scan[t - o] : 0u;
+      __syncthreads();
+      scan[t] += v;
+      __syncthreads();
+    }
+    if (miss) {
+      const uint32_t rank = built + scan[t] - 1, row = used + rank, item = kd.rep[id];
+      kd.row_of[id] = row;
+      kd.build_row[rank] = row;
+      kd.build_rep[rank] = item;
+#pragma unroll
+      for (int k = 0; k < 32; ++k) kd.c_keys[(size_t)row * 32 + k] = pks[(size_t)item * 32 + k];   // the caller's buffer may be gone by the next call
+    }
+    built += scan[KD_MATCH_WG - 1];
+    __syncthreads();
+  }
+  if (t == 0) {
+    kd.ctl[KD_CTL_BUILD] = built;
+    kd.ctl[KD_CTL_HITS] = d - built;
+    kd.ctl[KD_CTL_DROPPED] = (drop ? (uint32_t)KD_DROP_CAPACITY : 0u) | (reset ? (uint32_t)KD_DROP_RESET : 0u);
+  }
+}
 KERNEL_KD void k_kd_resolve(size_t n, KeyDedup kd) {
   const size_t i = (size_t)blockIdx.x * KD_WG + threadIdx.x;
   if (i >= n) return;
   const uint32_t s = kd.slot_of[i];
-  kd.key_idx[i] = s == KD_EMPTY ? 0u : kd.slot_id[s];
-}
-// the table route is possible at all (read by every lane of the builder kernels: wave-uniform)
-__device__ __forceinline__ bool kd_viable(const KeyDedup& kd, size_t n) {
-  const uint32_t d = kd.ctl[KD_CTL_D];
-  return d <= kd.max_keys && (size_t)d * kd.min_mult <= n && (kd.ctl[KD_CTL_FLAGS] & KD_OVERFLOW) == 0;
+  const uint32_t id = s == KD_EMPTY ? KD_EMPTY : kd.slot_id[s];
+  const bool looked_up = kd.ctl[KD_CTL_BUILD] + kd.ctl[KD_CTL_HITS] != 0;   // k_kd_match wrote row_of (a batch the thresholds refuse: it did not)
+  kd.key_idx[i] = looked_up && id < kd.max_keys ? kd.row_of[id] : 0u;        // (otherwise the call takes the generic route: nothing reads this)
 }
 
 __device__ __forceinline__ void kd_store_own(int32_t* dst, const Fp2& x) {
@@ -166,9 +252,8 @@ struct KdLmDev {
     if (live && pair < 3) kd_store_own(c == 2 ? c2s + (size_t)idx * 2 * BN_LIMBS : rows + (size_t)idx * BN_KEY_LINE_WORDS + (size_t)c * 2 * BN_LIMBS, v);
   }
 };
-KERNEL_KD_LM void k_kd_lines(const uint8_t* pks, size_t n, uint32_t flags, KeyDedup kd) {
-  if (!kd_viable(kd, n)) return;
-  const uint32_t d = kd.ctl[KD_CTL_D];
+KERNEL_KD_LM void k_kd_lines(const uint8_t* pks, uint32_t flags, KeyDedup kd, int report_degenerate) {
+  const uint32_t d = kd.ctl[KD_CTL_BUILD];                                      // the build list (k_kd_match); 0 on the generic route
   if ((uint32_t)blockIdx.x * KD_LM_PER_WAVE >= d) return;                       // the whole wave leaves
   __builtin_amdgcn_s_setprio(3);                         // a latency chain beside the hash rounds' throughput waves
   const unsigned l = threadIdx.x, v = l / KD_LM_LANES, role = l & 1u;
@@ -179,12 +264,13 @@ KERNEL_KD_LM void k_kd_lines(const uint8_t* pks, size_t n, uint32_t flags, KeyDe
   uint32_t j = (uint32_t)blockIdx.x * KD_LM_PER_WAVE + vslot;
   m.live = m.writer && j < d;
   if (j >= d) j = d - 1;                                 // lanes without a key of their own follow along on the last one
+  const uint32_t row = kd.build_row[j];
   m.bx.base = vslot * KD_LM_KEY_STRIDE + role * KD_LM_ROLE_STRIDE;
   G2Affine q;
-  const uint8_t st = decode_g2_pair_role(q, pks + 128 * (size_t)kd.rep[j], flags);
+  const uint8_t st = decode_g2_pair_role(q, pks + 128 * (size_t)kd.build_rep[j], flags);
   const bool real = st == ST_OK && !q.inf;               // a refused key or the identity: generator lines (its pair A is skipped)
   if (!real) { q.x = fp2_load_const(C_G2_GEN[0]); q.y = fp2_load_const(C_G2_GEN[1]); }
-  if (m.live && m.pair == 0 && role == 0) { kd.st[j] = st; kd.inf[j] = q.inf; }
+  if (m.live && m.pair == 0 && role == 0) { kd.st[row] = st; kd.inf[row] = q.inf; }
   if (m.writer) {
     m.bx.put(m.bx.slot(LS_ZERO), fp2_zero()); m.bx.put(m.bx.slot(LS_DUMMY), fp2_zero());
     kd_builder_init(m.bx, q);
@@ -195,12 +281,12 @@ KERNEL_KD_LM void k_kd_lines(const uint8_t* pks, size_t n, uint32_t flags, KeyDe
 #pragma unroll
     for (int k = 0; k < 5; ++k) m.e[lv].w[k] = t[m.pair].w[k];
   }
-  m.rows = kd.lines + (size_t)j * BN_N_FIXED_LINES * BN_KEY_LINE_WORDS;
-  m.c2s = kd.c2 + (size_t)j * BN_N_FIXED_LINES * 2 * BN_LIMBS;
+  m.rows = kd.lines + (size_t)row * BN_N_FIXED_LINES * BN_KEY_LINE_WORDS;
+  m.c2s = kd.c2 + (size_t)row * BN_N_FIXED_LINES * 2 * BN_LIMBS;
   m.degenerate = false;
   KD_LM_FENCE();
   kd_builder_program(m);
-  if (m.live && real && m.degenerate && m.pair == 0 && role == 0) atomicOr(&kd.ctl[KD_CTL_FLAGS], (uint32_t)KD_DEGENERATE);
+  if (m.live && ((real && m.degenerate) || report_degenerate) && m.pair == 0 && role == 0) atomicOr(&kd.ctl[KD_CTL_FLAGS], (uint32_t)KD_DEGENERATE);
 }
 // one workgroup per key, one lane pair per line: (c0, c1) <- canonical (c0 / c2, c1 / c2) with ONE inversion per key.  Montgomery's trick as a
 // tree over the key's 87 c2 values (padded with ones to KD_TREE_LEAVES) in LDS — bn254_keydedup.h: kd_scale_tree is its host form —, heap order (node 1 = the root, leaves from KD_TREE_LEAVES on):
@@ -210,10 +296,9 @@ KERNEL_KD_LM void k_kd_lines(const uint8_t* pks, size_t n, uint32_t flags, KeyDe
 // table anyone reads (k_kd_lines has set KD_DEGENERATE).
 static_assert(BN_N_FIXED_LINES <= KD_TREE_LEAVES && 2 * KD_TREE_LEAVES == KD_WG, "one lane pair per leaf");
 #define KD_NODE_WORDS (2 * BN_LIMBS)
-KERNEL_KD_PAIR void k_kd_scale(size_t n, KeyDedup kd) {
-  if (!kd_viable(kd, n)) return;
-  const uint32_t j = blockIdx.x;
-  if (j >= kd.ctl[KD_CTL_D]) return;                               // the whole workgroup leaves
+KERNEL_KD_PAIR void k_kd_scale(KeyDedup kd) {
+  if (blockIdx.x >= kd.ctl[KD_CTL_BUILD]) return;                  // the whole workgroup leaves
+  const uint32_t j = kd.build_row[blockIdx.x];                     // the row of this key's table
   __shared__ int32_t prod[2 * KD_TREE_LEAVES * KD_NODE_WORDS];     // products of the subtrees
   __shared__ int32_t inv[2 * KD_TREE_LEAVES * KD_NODE_WORDS];      // ... and their inverses
   const uint32_t p = threadIdx.x >> 1;
@@ -252,22 +337,37 @@ KERNEL_KD_PAIR void k_kd_scale(size_t n, KeyDedup kd) {
   kd_store_own(row, r0);
   kd_store_own(row + 2 * BN_LIMBS, r1);
 }
-KERNEL_KD void k_kd_decide(size_t n, KeyDedup kd, int force_generic) {
-  if (threadIdx.x != 0) return;
-  const bool keyed = !force_generic && kd_viable(kd, n) && (kd.ctl[KD_CTL_FLAGS] & KD_DEGENERATE) == 0;
-  kd.ctl[KD_CTL_KEYED_N] = keyed ? (uint32_t)n : 0u;
-  kd.ctl[KD_CTL_GENERIC_N] = keyed ? 0u : (uint32_t)n;
+KERNEL_KD void k_kd_decide(size_t n, KeyDedup kd, int force_generic, int cache_on) {
+  const bool keyed = force_generic != 1 && kd_viable(kd, n) && (kd.ctl[KD_CTL_FLAGS] & KD_DEGENERATE) == 0;   // every lane the same
+  if (threadIdx.x == 0) {
+    kd.ctl[KD_CTL_KEYED_N] = keyed ? (uint32_t)n : 0u;
+    kd.ctl[KD_CTL_GENERIC_N] = keyed ? 0u : (uint32_t)n;
+  }
+  if (!keyed || !cache_on) return;
+  // commit: the keys this call built become findable; their rows follow the rows in use (k_kd_match handed them out from there)
+  const uint32_t built = kd.ctl[KD_CTL_BUILD];
+  for (uint32_t m = threadIdx.x; m < built; m += KD_WG) {
+    const uint32_t row = kd.build_row[m];
+    uint32_t w[32];
+#pragma unroll
+    for (int k = 0; k < 32; ++k) w[k] = kd.c_keys[(size_t)row * 32 + k];
+    const uint32_t h = kd_hash(w, kd.hash_mask);
+    for (uint32_t probe = 0; probe <= kd.index_mask; ++probe)      // distinct keys, at most max_keys of them in 2 x max_keys slots or more
+      if (atomicCAS(&kd.c_index[(h + probe) & kd.index_mask], KD_EMPTY, row) == KD_EMPTY) break;
+  }
+  if (threadIdx.x == 0) kd.c_state[0] += built;
 }
 
-int bn254_kd_enqueue(const uint8_t* d_pks, size_t n, uint32_t flags, KeyDedup kd, int force_generic, hipStream_t s) {
+int bn254_kd_enqueue(const uint8_t* d_pks, size_t n, uint32_t flags, KeyDedup kd, int force_generic, int cache_reset, int cache_on, hipStream_t s) {
   HIP_TRY(hipMemsetAsync(kd.table, 0xFF, ((size_t)kd.slot_mask + 1) * sizeof(uint32_t), s));
   HIP_TRY(hipMemsetAsync(kd.ctl, 0, KD_CTL_WORDS * sizeof(uint32_t), s));
   const unsigned g = (unsigned)((n + KD_WG - 1) / KD_WG);
   k_kd_insert<<<g, KD_WG, 0, s>>>(d_pks, n, kd);
+  k_kd_match<<<1, KD_MATCH_WG, 0, s>>>(d_pks, n, kd, cache_reset || !cache_on);
   k_kd_resolve<<<g, KD_WG, 0, s>>>(n, kd);
-  k_kd_lines<<<(unsigned)((kd.max_keys + KD_LM_PER_WAVE - 1) / KD_LM_PER_WAVE), BN_WAVE, KD_LM_LDS_WORDS * sizeof(int32_t), s>>>(d_pks, n, flags, kd);
-  k_kd_scale<<<kd.max_keys, KD_WG, 0, s>>>(n, kd);
-  k_kd_decide<<<1, BN_WAVE, 0, s>>>(n, kd, force_generic);
+  k_kd_lines<<<(unsigned)((kd.max_keys + KD_LM_PER_WAVE - 1) / KD_LM_PER_WAVE), BN_WAVE, KD_LM_LDS_WORDS * sizeof(int32_t), s>>>(d_pks, flags, kd, force_generic == 2);
+  k_kd_scale<<<kd.max_keys, KD_WG, 0, s>>>(kd);
+  k_kd_decide<<<1, KD_WG, 0, s>>>(n, kd, force_generic, cache_on);
   HIP_TRY(hipGetLastError());
   return 0;
 }

@@ -279,7 +279,8 @@ __attribute__((visibility("hidden"))) int bn254_aggd_keyed_slot_map(hipStream_t 
 #define KD_MAX_PROBES 64u                          // open addressing: a longer probe sequence sends the call to the generic route
 #define KD_EMPTY 0xFFFFFFFFu
 enum { KD_OVERFLOW = 1, KD_DEGENERATE = 2 };
-enum { KD_CTL_D = 0, KD_CTL_FLAGS, KD_CTL_KEYED_N, KD_CTL_GENERIC_N, KD_CTL_WORDS = 4 };
+enum { KD_CTL_D = 0, KD_CTL_FLAGS, KD_CTL_KEYED_N, KD_CTL_GENERIC_N, KD_CTL_BUILD, KD_CTL_HITS, KD_CTL_DROPPED, KD_CTL_WORDS = 8 };
+enum { KD_DROP_CAPACITY = 1, KD_DROP_RESET = 2 };  // KD_CTL_DROPPED: the call's misses did not fit the free rows / the host asked for an empty cache
 struct KeyDedup {
   uint32_t* table;     // [slot_mask + 1] representative item of the slot, KD_EMPTY
   uint32_t* slot_id;   // [slot_mask + 1] key id of the slot (written by its representative)
@@ -291,12 +292,22 @@ struct KeyDedup {
   int32_t* c2;         // [max_keys][87][re, im][9] raw c2 of the lines
   uint8_t* st;         // [max_keys] decode status of the representative
   uint8_t* inf;        // [max_keys] identity flag
-  uint32_t slot_mask, hash_mask, max_keys, min_mult;
+  uint32_t* row_of;    // [max_keys] table row of the call's key id (k_kd_match)
+  uint32_t* build_row; // [max_keys] rows of the keys this call builds, in the order of their ids: KD_CTL_BUILD entries
+  uint32_t* build_rep; // [max_keys] ... and the item that represents each of them
+  // the key cache (BN254_OPT_KEY_CACHE): the rows of lines / st / inf below c_state[0] persist between calls, found again by the key's bytes
+  uint32_t* c_keys;    // [max_keys][32] the 128 bytes of the key of each row (the context's own copy)
+  uint32_t* c_index;   // [index_mask + 1] open addressing over the rows' keys: row, KD_EMPTY
+  uint32_t* c_state;   // [1] rows in use
+  uint32_t slot_mask, hash_mask, max_keys, min_mult, index_mask;
 };
-__attribute__((visibility("hidden"))) int bn254_kd_enqueue(const uint8_t* d_pks, size_t n, uint32_t flags, KeyDedup kd, int force_generic, hipStream_t s);
+// cache_reset: the cache is emptied before this call looks its keys up; cache_on = 0: ... and stays empty (every call builds all its keys)
+__attribute__((visibility("hidden"))) int bn254_kd_enqueue(const uint8_t* d_pks, size_t n, uint32_t flags, KeyDedup kd, int force_generic, int cache_reset,
+                                                           int cache_on, hipStream_t s);
 // per-item and per-key bytes of the buffers above (slot arrays: at most 4n words each, the next power of two >= 2n)
 #define KD_BYTES_PER_ITEM ((size_t)(2 * 4 + 2) * sizeof(uint32_t))
-#define KD_BYTES_PER_KEY ((size_t)BN_N_FIXED_LINES * (BN_KEY_LINE_WORDS + 2 * BN_LIMBS) * sizeof(int32_t) + sizeof(uint32_t) + 2)
+// (per key besides lines and raw c2: rep, row_of, build_row, build_rep, the cache's copy of the key and four index slots, st, inf)
+#define KD_BYTES_PER_KEY ((size_t)BN_N_FIXED_LINES * (BN_KEY_LINE_WORDS + 2 * BN_LIMBS) * sizeof(int32_t) + (4 + 32 + 4) * sizeof(uint32_t) + 2)
 
 // entry points of bn254_trio.hip (octet layout for small batches)
 __attribute__((visibility("hidden"))) int bn254_trio_miller_verify(size_t n, Ws ws, hipStream_t s, int mode = 0);

@@ -47,6 +47,7 @@ OPT_HASH_TAIL_CHUNK = 32           # ... test seam: counters per lane group and 
 OPT_BITMAP_RAND_MIN_TUPLES = 33    # randomised signer bitmaps: the exact bitmap call below this many tuples
 OPT_BITMAP_RAND_GROUP_TUPLES = 34  # ... tuples per group of its combined checks (developer option)
 OPT_BITMAP_RAND_MAX_KEYS = 35      # ... the exact bitmap call when more keys than this are registered
+OPT_KEY_CACHE = 36                 # key dedup: the line tables stay between calls, a call builds only unseen keys (default 1; 0 = build all, drops the cache)
 
 
 class NativeError(RuntimeError):
@@ -139,6 +140,12 @@ class Engine:
         o = (ctypes.c_uint32 * 5)()
         _check("bn254_debug_key_dedup_last", self._lib.bn254_debug_key_dedup_last(self._h, o))
         return dict(zip(("ran", "keys", "flags", "keyed_n", "generic_n"), (int(x) for x in o)))
+
+    def debug_key_cache_last(self):
+        """what the last batch_verify_device did with the key cache: dict(ran, keys, hits, built, dropped)"""
+        o = (ctypes.c_uint32 * 5)()
+        _check("bn254_debug_key_cache_last", self._lib.bn254_debug_key_cache_last(self._h, o))
+        return dict(zip(("ran", "keys", "hits", "built", "dropped"), (int(x) for x in o)))
 
     def debug_key_tables(self, which, first, count):
         """developer hook: the line tables on the device (which = 0: of the last key dedup, 1: registered) of keys first .. first + count - 1

@@ -462,6 +462,18 @@ int bn254_ctx_set_profiling(bn254_ctx *ctx, int enabled);
                                 0 = always the generic loop.  Same status bytes either way */
 #define BN254_OPT_KEY_DEDUP_MAX_KEYS 21 /* ... tables for at most this many distinct keys per call (default 1024; 18.8 KB of device memory each) */
 #define BN254_OPT_KEY_DEDUP_MIN_MULT 22 /* ... and only when the batch has at least this many items per distinct key (default 16) */
+#define BN254_OPT_KEY_CACHE 36 /* ... 1 (default) = the line tables stay in the context between calls, found again by the key's 128 bytes (the
+                                context keeps its own copy; the caller's buffer may be freed or rewritten): a call builds only the keys no
+                                earlier call has built, and a service with a stable key set builds none from its second call on.  Held within
+                                the memory of BN254_OPT_KEY_DEDUP_MAX_KEYS rows; when a call's new keys do not fit the free rows the cache
+                                is dropped and the call builds all its keys.  Also dropped: by other decode flags than the last call's, a
+                                change of the KEY_DEDUP options above, a growth of the dedup buffers, and by setting this option (0 = every
+                                call builds all its keys).  A call that takes the generic loop leaves it as it was; a key with a degenerate
+                                line is never kept.  ORDERING: the cache is written on a stream of the context during one call and read by
+                                the next.  A call of this route therefore waits ON THE DEVICE, through an event the context owns, for the end
+                                of the previous call of this route before it touches the dedup buffers — also when the two are enqueued on
+                                different caller streams with no host synchronisation in between.  (The rule above for everything else a
+                                context shares stands: one call in flight.)  Same status bytes, same table words */
 #define BN254_OPT_BITMAP_TABLE_MAX_KEYS 28 /* bn254_batch_verify_keyed_bitmap: subset tables of the registered set while it has at most this many keys
                                              (default 4096: 5 152 B per key, 21 MB); above, or with 0, the selected keys are added one by one.
                                              Same status bytes */
@@ -610,7 +622,9 @@ int bn254_mgpu_batch_hash_to_g1(bn254_mgpu *mg, const uint8_t *msgs, const uint6
 #define BN254_OPT_G2_FIXED_BASE 19 /* key derivation (bn254_batch_g2_mul with points = NULL: sk * G2::one()): 1 (default) = 65 additions from a table of the
                                    generator's multiples, built once per context, on a lane pair; 0 = the general 256-step ladder on one lane.  Same bytes. */
 #define BN254_OPT_KEY_DEDUP_FORCE_GENERIC 23 /* test hook: the key-dedup route is prepared as usual but the device-side decision always takes the generic
-                                             Miller loop (the fallback path of an overflowing or degenerate batch); default 0 */
+                                             Miller loop (the fallback path of an overflowing or degenerate batch); 2 = the table builder reports a
+                                             degenerate line (flags bit 1) for every key it builds — no key bytes that reach one are known —, so the
+                                             device takes the decision it takes for such a key: generic loop, nothing cached; default 0 */
 #define BN254_OPT_KEY_DEDUP_HASH_BITS 24 /* test seam: keep only this many low bits of the key hash of the dedup table (0 = all, default), so that
                                          distinct keys collide: the full 128-byte compare and the probe bound (overflow -> generic loop) */
 #define BN254_OPT_AGGD_KEYED_ROUTE 25 /* bn254_batch_aggregate_verify_distinct_keyed: 0 (default) = by size; 1 / 2 = the table-driven slot kernel with
@@ -632,10 +646,16 @@ int bn254_debug_route_table(bn254_ctx *ctx, uint64_t *max_n, int *miller, int *f
  * flags (1 probe overflow, 2 degenerate line), items of the keyed Miller kernel, items of the generic one}; all 0 when the call did not run
  * the dedup.  Synchronises the device. */
 int bn254_debug_key_dedup_last(bn254_ctx *ctx, uint32_t out[5]);
+/* ... and what that call did with the key cache (BN254_OPT_KEY_CACHE): out = {ran, distinct keys, keys found in the cache, keys built, dropped
+ * (bit 0: the new keys did not fit the free rows; bit 1: the cache was emptied before the call — other flags or options, moved buffers, the
+ * option at 0)}; a call whose batch the thresholds refuse looks nothing up (hits = built = 0).  Synchronises the device. */
+int bn254_debug_key_cache_last(bn254_ctx *ctx, uint32_t out[5]);
 /* the Miller-loop line tables as they stand on the device, keys first .. first + count - 1: which = 0 the per-call tables of the key
  * deduplication of the last bn254_batch_verify_device (key ids in the order the device handed them out; rep[k] = the item that represents key
- * k), which = 1 the tables of bn254_ctx_register_keys (rep is not written).  lines: count x 87 x 36 words ([line][c0, c1][re, im][9 limbs],
- * canonical); st / inf (optional): decode status and identity flag per key.  Synchronises the device. */
+ * k; a key's table is read from the cache row that holds it, so a key that call found cached reads the same as one it built), which = 1 the tables of bn254_ctx_register_keys (rep is not written).  lines: count x 87 x 36 words ([line][c0, c1][re, im][9 limbs],
+ * canonical); st / inf (optional): decode status and identity flag per key.  which = 0 after a call whose batch the thresholds refused
+ * (more keys than BN254_OPT_KEY_DEDUP_MAX_KEYS, too few items per key, a probe overflow) returns BN254_E_BAD_ARGUMENT and writes nothing: such
+ * a call looks no key up and builds no table.  Synchronises the device. */
 int bn254_debug_key_tables(bn254_ctx *ctx, int which, size_t first, size_t count, int32_t *lines, uint32_t *rep, uint8_t *st, uint8_t *inf);
 /* what the last bn254_batch_aggregate_verify_distinct_keyed_randomized[_device] did: out = {1 if it took the randomised route, groups that
  * reached the check, table pairs of all group checks, failed groups, aggregates re-checked, groups of one aggregate (r = 1)}; all 0 when it

@@ -323,6 +323,54 @@ class ECDSA:
         return [None if s == 0 else Error(s) for s in ECDSA._keyed_signers_status(items, engine)]
 
     @staticmethod
+    def aggregate_keyed_signers(message, signatures, key_indices, engine=None, n_keys=None):
+        """One message and the individual signatures of some registered keys (signatures[k] said to be by key key_indices[k] of the set,
+        ECDSA.register_keys): every signature is verified against its key, those that pass are added — one per key, however many valid
+        ones a key sent — and the result is (aggregate Signature, sorted indices of the keys that signed, statuses), statuses[k] None or
+        the Error ECDSA.batch_verify_keyed would give signature k.  The pair feeds ECDSA.verify_keyed_signers.  Raises the message's
+        Error(HashToPointError) (include/bn254_hip.h: bn254_batch_collect_keyed_bitmap)."""
+        r = ECDSA.batch_aggregate_keyed_signers([(message, signatures, key_indices)], engine, n_keys)[0]
+        if isinstance(r, Error):
+            raise r
+        return r
+
+    @staticmethod
+    def batch_aggregate_keyed_signers(items, engine=None, n_keys=None):
+        """items: a list of (message, signatures, key_indices); result[i] is what ECDSA.aggregate_keyed_signers returns for item i, or the
+        Error it would raise.  A malformed item (not such a triple, lengths that differ, an index that is negative or >= 2^32) raises
+        before any device work.  n_keys: the size of the registered set, for an engine that did not register it itself."""
+        rows = []
+        for item in items:
+            if len(item) != 3:
+                raise Error(ErrorKind.InvalidLength)
+            message, signatures, key_indices = item
+            sigs, idx = list(signatures), [int(j) for j in key_indices]
+            if len(sigs) != len(idx) or any(len(s.raw) != _engine.G1_BYTES for s in sigs):
+                raise Error(ErrorKind.InvalidLength)
+            if any(j < 0 or j >= 1 << 32 for j in idx):
+                raise Error(ErrorKind.IndexOutOfBounds)
+            rows.append((bytes(message), sigs, idx))
+        eng = engine or _eng()
+        if n_keys is None:
+            n_keys = getattr(eng, "n_registered_keys", None)
+        if n_keys is None:             # the bitmaps are as wide as the registered set, which the items cannot tell
+            raise ValueError("the engine does not know its registered key count: pass n_keys")
+        bm_words = max((int(n_keys) + 31) // 32, 1)
+        share_st, tuple_st, agg, bits = eng.batch_collect_keyed_bitmap(
+            [r[0] for r in rows], b"".join(s.raw for r in rows for s in r[1]), [j for r in rows for j in r[2]], [len(r[2]) for r in rows], bm_words)
+        out, at = [], 0
+        for i, (_, _, idx) in enumerate(rows):
+            st = share_st[at:at + len(idx)]
+            at += len(idx)
+            if tuple_st[i]:
+                out.append(Error(tuple_st[i]))
+                continue
+            row = bits[i * bm_words:(i + 1) * bm_words]
+            signers = [j for j in range(32 * bm_words) if (row[j // 32] >> (j % 32)) & 1]
+            out.append((Signature(agg[64 * i:64 * i + 64]), signers, [None if b == 0 else Error(b) for b in st]))
+        return out
+
+    @staticmethod
     def batch_verify_keyed_signers_randomized(items, seed=None, engine=None, rand64=False):
         """batch_verify_keyed_signers with the pairing checks of whole groups of items combined (include/bn254_hip.h:
         bn254_batch_verify_keyed_bitmap_randomized): the same result list; an Error is always the exact one, a None is wrong with probability

@@ -276,7 +276,7 @@ static int aggd_device(bn254_ctx* c, const AggdArgs& a, hipStream_t s) {
     if ((rc = launch_final_exp_lane(c, s, n, 1, 1, 1, 0, nullptr, a.d_status, 0, p.gbase, nullptr, nullptr))) return rc;
   }
   PROF_MARK(4);
-  if (c->profiling) { c->ev_valid = 1; c->ev_hash_first = 0; }
+  prof_done(c, EV_DECODE_FIRST);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -348,7 +348,7 @@ static int aggr_device(bn254_ctx* c, const AggdArgs& a, const uint8_t* seed32, h
   if ((rc = bn254_pair_aggd_move(n, c->ws, p.gbase, s))) return rc;
   if ((rc = bn254_pair_final_exp(n, c->ws, 0, a.d_status, c->ws.h_list, c->ws.h_cnt, s))) return rc;
   PROF_MARK(4);
-  if (c->profiling) { c->ev_valid = 1; c->ev_hash_first = 0; }
+  prof_done(c, EV_DECODE_FIRST);
   HIP_TRY(hipGetLastError());
   c->aggr_last_ran = 1;                                // only a call that enqueued everything has something for the debug hooks to read
   return 0;
@@ -429,6 +429,7 @@ int bn254_batch_aggregate_verify_distinct_keyed_randomized(bn254_ctx* c, const u
 
 // for the other unit that runs group checks (bn254_bitmap_rand.hip): the prefix sum, and the slot kernel's slots of n groups of table pairs
 int bn254_aggd_scan_add(hipStream_t s, const uint64_t* in, size_t n, uint64_t* out, uint64_t* tot) { return aggd_scan<AggdAdd>(s, in, n, out, tot); }
+int bn254_aggd_scan_max(hipStream_t s, const uint64_t* in, size_t n, uint64_t* out, uint64_t* tot) { return aggd_scan<AggdMax>(s, in, n, out, tot); }
 int bn254_aggd_keyed_slot_map(hipStream_t s, size_t n, const uint64_t* lo, const uint64_t* hi, int width, uint64_t* kincl, uint64_t* tot, size_t n_slots,
                               uint32_t* slot_agg) {
   k_aggd_keyed_count<<<grid_for(n), BN_WAVE, 0, s>>>(n, lo, hi, (uint64_t)width, kincl);

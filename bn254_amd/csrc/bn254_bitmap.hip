@@ -121,7 +121,7 @@ int bn254_batch_verify_keyed_bitmap_device(bn254_ctx* c, const uint8_t* d_msgs, 
   // the tuples are verify-shaped now: the routing table serves small batches with the small-batch kernels, as after the aggregation kernel
   if ((rc = launch_verify_miller_fe(c, s, n, BN_PAIRS_VERIFY, 1, d_status, true))) return rc;
   PROF_MARK(4);
-  if (c->profiling) { c->ev_valid = 1; c->ev_hash_first = 0; }
+  prof_done(c, EV_DECODE_FIRST);
   HIP_TRY(hipGetLastError());
   return 0;
 }

@@ -336,7 +336,7 @@ static int bmr_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t* d_off
   if ((rc = bn254_pair_miller_verify(n, c->ws, c->ws.h_list, c->ws.h_cnt, s))) return rc;
   if ((rc = bn254_pair_final_exp(n, c->ws, 1, d_status, c->ws.h_list, c->ws.h_cnt, s))) return rc;
   PROF_MARK(4);
-  if (c->profiling) { c->ev_valid = 1; c->ev_hash_first = 0; }
+  prof_done(c, EV_DECODE_FIRST);
   HIP_TRY(hipGetLastError());
   c->bmr_last_ran = 1;                                 // only a call that enqueued everything has something for the debug hooks to read
   return 0;

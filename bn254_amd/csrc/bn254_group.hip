@@ -780,7 +780,7 @@ static int agg_run(bn254_ctx* c, hipStream_t s, const AggTables& t, const uint32
   // pairing part 9.8 -> 1.0 ms)
   if ((rc = launch_verify_miller_fe(c, s, n, BN_PAIRS_VERIFY, 1, d_status, true))) return rc;
   PROF_MARK(4);
-  if (c->profiling) { c->ev_valid = 1; c->ev_hash_first = 0; }
+  prof_done(c, EV_DECODE_FIRST);
   HIP_TRY(hipGetLastError());
   return 0;
 }

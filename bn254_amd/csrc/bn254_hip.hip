@@ -784,6 +784,7 @@ int bn254_ctx_create(int hip_device, bn254_ctx** out) {
   c->bmr_min_tuples = BITMAP_RAND_MIN_TUPLES_DEFAULT;
   c->bmr_group_tuples = BITMAP_RAND_GROUP_TUPLES_DEFAULT;
   c->bmr_max_keys = BITMAP_RAND_MAX_KEYS_DEFAULT;
+  c->collect_wave_min = COLLECT_WAVE_MIN_SHARES_DEFAULT;
   c->trio_max_batch = TRIO_MAX_BATCH_DEFAULT;
   c->hash_direct_width = HASH_DIRECT_WIDTH_DEFAULT;
   c->hash_tail_chunk = HASH_TAIL_CHUNK_DEFAULT;
@@ -859,6 +860,7 @@ void bn254_ctx_destroy(bn254_ctx* c) {
   if (c->aggr_buf) (void)hipFree(c->aggr_buf);
   if (c->aggr_stats) (void)hipFree(c->aggr_stats);
   if (c->bmr_buf) (void)hipFree(c->bmr_buf);
+  if (c->collect_buf) (void)hipFree(c->collect_buf);
   if (c->kd_buf) (void)hipFree(c->kd_buf);
   if (c->bm_bad) (void)hipFree(c->bm_bad);
   if (c->bm_tab) (void)hipFree(c->bm_tab);
@@ -972,6 +974,7 @@ int bn254_ctx_set_option(bn254_ctx* c, int option, int value) {
   if (option == BN254_OPT_BITMAP_TABLE_MAX_KEYS) { if (value < 0) return BN254_E_BAD_ARGUMENT; c->bm_table_max_keys = value; return 0; }
   if (option == BN254_OPT_BITMAP_RAND_MIN_TUPLES) { if (value < 0) return BN254_E_BAD_ARGUMENT; c->bmr_min_tuples = value; return 0; }
   if (option == BN254_OPT_BITMAP_RAND_MAX_KEYS) { if (value < 0) return BN254_E_BAD_ARGUMENT; c->bmr_max_keys = value; return 0; }
+  if (option == BN254_OPT_COLLECT_WAVE_MIN_SHARES) { if (value < 1) return BN254_E_BAD_ARGUMENT; c->collect_wave_min = value; return 0; }
   if (option == BN254_OPT_BITMAP_RAND_GROUP_TUPLES) { if (value < 1) return BN254_E_BAD_ARGUMENT; c->bmr_group_tuples = value; return 0; }
   if (option == BN254_OPT_BITMAP_ROUTE) { if (value < 0 || value > 2) return BN254_E_BAD_ARGUMENT; c->bm_route = value; return 0; }
   return BN254_E_BAD_ARGUMENT;
@@ -1003,11 +1006,17 @@ int bn254_ctx_last_clocks(bn254_ctx* c, double sclk_mhz[3]) {
 }
 int bn254_ctx_last_kernel_ms(bn254_ctx* c, float ms[4]) {
   if (!c || !ms || !c->ev_valid) return BN254_E_BAD_ARGUMENT;
+  if (c->ev_layout == EV_COLLECT) {                       // bn254_batch_collect_keyed_bitmap: its select-and-sum runs last and reports in ms[1]
+    static const int from[4] = {1, 4, 2, 3}, to[4] = {2, 0, 3, 4};
+    HIP_TRY(hipEventSynchronize(c->ev[0]));
+    for (int i = 0; i < 4; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], c->ev[from[i]], c->ev[to[i]]));
+    return 0;
+  }
   HIP_TRY(hipEventSynchronize(c->ev[4]));
   for (int i = 0; i < 4; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], c->ev[i], c->ev[i + 1]));
   // the host-pointer verify hashes FIRST (the messages cross PCIe first) and decodes second: keep the documented slots
   // (ms[0] decode, ms[1] hash-to-G1 — there including the transfer of the messages)
-  if (c->ev_hash_first) { float t = ms[0]; ms[0] = ms[1]; ms[1] = t; }
+  if (c->ev_layout == EV_HASH_FIRST) { float t = ms[0]; ms[0] = ms[1]; ms[1] = t; }
   return 0;
 }
 
@@ -1074,7 +1083,7 @@ static int verify_tail(bn254_ctx* c, hipStream_t s, size_t n, uint8_t* d_status,
     k_final_exp<<<g, BN_WAVE, 0, s>>>(n, 2, 1, c->ws.stride / 2, c->ws, 1, nullptr, d_status, 0, 0, nullptr, nullptr);
   } else if ((rc = launch_verify_miller_fe(c, s, n, BN_PAIRS_VERIFY, 1, d_status, true))) return rc;
   PROF_MARK(4);
-  if (c->profiling) { c->ev_valid = 1; c->ev_hash_first = hash_first; }
+  prof_done(c, hash_first ? EV_HASH_FIRST : EV_DECODE_FIRST);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -1331,7 +1340,7 @@ int bn254_batch_hash_to_g1_device(bn254_ctx* c, const uint8_t* d_msgs, const uin
   k_encode_g1<<<g, BN_WAVE, 0, s>>>(n, c->ws, PL_P1X, BY_P1_INF, d_points, d_status);
   PROF_MARK(3);
   PROF_MARK(4);
-  if (c->profiling) { c->ev_valid = 1; c->ev_hash_first = 0; }
+  prof_done(c, EV_DECODE_FIRST);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -1381,7 +1390,7 @@ static int pairing_device(bn254_ctx* c, const uint8_t* d_g1, const uint8_t* d_g2
     k_final_exp<<<grid_for(n), BN_WAVE, 0, s>>>(n, k, k, 1, c->ws, 0, d_gt, d_status, raw_only, 0, nullptr, nullptr);
   }
   PROF_MARK(4);
-  if (c->profiling) { c->ev_valid = 1; c->ev_hash_first = 0; }
+  prof_done(c, EV_DECODE_FIRST);
   HIP_TRY(hipGetLastError());
   return 0;
 }

@@ -19,6 +19,11 @@ struct AggTables { int valid; size_t n_msgs, n_signers, n_groups, groups4, built
 // the call's scratch buffer
 struct AggrLast { size_t ng, cbase, tbase; const uint32_t *nagg, *bkey; const uint64_t *glo, *ghi; const uint8_t* gst; };
 
+// the order in which a profiled call recorded its events: decode, hash, Miller loop, final exponentiation between ev[0] .. ev[4]; the
+// host-pointer verify's hash, decode, ...; or the collect call's (its select-and-sum runs last and reports in ms[1]): front end ev[1]..ev[2],
+// Miller loop ..ev[3], final exponentiation ..ev[4], select-and-sum ..ev[0]
+enum EvLayout { EV_DECODE_FIRST = 0, EV_HASH_FIRST = 1, EV_COLLECT = 2 };
+
 struct bn254_ctx {
   int device;
   hipStream_t stream;
@@ -49,7 +54,7 @@ struct bn254_ctx {
   int nonet_max_batch; // ... and up to this size their final exponentiation runs on nine lane pairs per verify (bn254_nonet.hip); 0 = never
   hipEvent_t ev[5];
   int ev_valid;
-  int ev_hash_first;   // the recorded intervals are hash, decode, ... (host-pointer verify) instead of decode, hash, ...
+  int ev_layout;       // EvLayout: which intervals the five events of the last profiled call bracket (bn254_ctx_last_kernel_ms); set with ev_valid, by prof_done
   hipStream_t copy_stream;   // host-pointer verify: signatures and keys cross PCIe here while the hash rounds run on `stream`
   uint8_t* pin;              // ... through this PINNED host buffer (hipHostMalloc, grown on demand): BN254_OPT_PINNED_STAGING
   size_t pin_cap;
@@ -124,6 +129,10 @@ struct bn254_ctx {
   uint32_t* bmr_stats;       // what its last run did on the device (bn254_debug_bitmap_rand_last); inside bmr_buf
   int bmr_last_ran;          // ... and whether the last call took the randomised route at all
   AggrLast bmr_last;         // ... and where it left its groups (bn254_debug_bitmap_rand_sums)
+  // building signer-bitmap aggregates from shares (bn254_collect.hip)
+  uint8_t* collect_buf;      // per tuple: H(m), its flags and the scans of the share ranges (ClScratch), grown on demand
+  size_t collect_cap;
+  int collect_wave_min;      // BN254_OPT_COLLECT_WAVE_MIN_SHARES: tuples with at least this many shares are summed by a wave each
 };
 
 struct ScopedEvents {
@@ -238,13 +247,15 @@ struct BN_HIDDEN HostStaging {
   HostStaging& operator=(const HostStaging&) = delete;
  private:
   hipError_t drain();                                      // wait for c->stream and c->copy_stream
-  struct Back { void* host; const void* dev; size_t bytes; } back[4];
+  struct Back { void* host; const void* dev; size_t bytes; } back[6];
   int n_back = 0;
   bool finished = false;
 };
 
 // Enqueue the hash-to-G1 rounds for n messages; points land in planes (px, px+1), statuses in BY_ST_HASH.
 
+// the end of every profiled call: the events are valid and this is their order — one assignment, so a call cannot leave the other's layout behind
+static inline void prof_done(bn254_ctx* c, int layout) { if (c->profiling) { c->ev_valid = 1; c->ev_layout = layout; } }
 #define PROF_MARK(idx) do { if (c->profiling) HIP_TRY(hipEventRecord(c->ev[idx], s)); } while (0)
 
 // launchers of kernels that live in bn254_hip.hip and are used by other units too (a kernel is launched from the unit that defines it)
@@ -260,6 +271,10 @@ enum BnVerifyPairs { BN_PAIRS_VERIFY = 0, BN_PAIRS_CHECK_PKS = 1 };
 // the Miller loop and final exponentiation of such a batch whose planes are filled, in the layouts BN254_OPT_PAIR_LANES, _TRIO_WAVE_ROLES and
 // the routing table choose; mark: profiling event 3 between the two
 BN_HIDDEN int launch_verify_miller_fe(bn254_ctx* c, hipStream_t s, size_t n, int pairs, int use_hash, uint8_t* d_status, bool mark);
+// the same for a KEYED batch (bn254_rand.hip): item i's key is the registered key d_key_idx[i] — rule 2 of bn254_batch_verify_keyed behind the
+// decode status, then the routing table's keyed kernels; and the statuses of such a batch when no key is registered
+BN_HIDDEN int launch_keyed_miller_fe(bn254_ctx* c, hipStream_t s, size_t n, const uint32_t* d_key_idx, uint8_t* d_status);
+BN_HIDDEN int launch_keyed_no_keys(bn254_ctx* c, hipStream_t s, size_t n, uint8_t* d_status);
 // one lane per item: k_miller_verify (map / count: a device-side queue of items, or null) and k_final_exp (the arguments of the kernel)
 // one lane per pairing: k_miller_var (f = miller(P1, Q) at every index below n), k_rand_tail (bn254_rand.hip: F_g * miller(S_g, -G2) at gbase + g)
 BN_HIDDEN int launch_miller_var_lane(bn254_ctx* c, hipStream_t s, size_t n);

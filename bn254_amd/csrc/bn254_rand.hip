@@ -340,6 +340,36 @@ KERNEL_SMALL void k_neg_g2_key_lines(int32_t* out) {
   for (int idx = 0; idx < BN_N_FIXED_LINES; ++idx) out[(size_t)idx * BN_KEY_LINE_WORDS + w] = neg_g2_key_line_word(idx, (int)w);
 }
 
+// the Miller loop and final exponentiation of a keyed batch whose P1 / P2 planes are filled (bn254_host.h): by the routing table the lane
+// machine's keyed form, the expanded keys and the small-batch kernels, or the line tables on lane pairs; profiling event 3 between the two
+int launch_keyed_miller_fe(bn254_ctx* c, hipStream_t s, size_t n, const uint32_t* d_key_idx, uint8_t* d_status) {
+  const KeyTable kt = {c->key_lines, c->key_st, c->key_inf, (uint32_t)c->n_keys};
+  int rc;
+  const BnRoute r = route_for(c, n);
+  if (r.miller == BN_ML_LANE_MACHINE) {
+    // the smallest batches: the lane machine's keyed form on the line tables themselves (no twist point to walk: 0.32 ms against 0.43)
+    if ((rc = bn254_lm_miller_verify_keyed(n, c->ws, d_key_idx, kt, s))) return rc;
+    PROF_MARK(3);
+    if ((rc = launch_final_exp_layout(c, s, n, 1, d_status, r.fe))) return rc;
+  } else if (r.miller != BN_ML_LANE_PAIRS) {
+    // a batch that cannot fill the chip: latency counts — expand the keys and take the small-batch kernels (2.3 ms instead of the
+    // 6 ms of the lane-pair layout; the line tables pay off only where throughput binds)
+    k_keyed_expand<<<grid_for(n), BN_WAVE, 0, s>>>(n, c->ws, d_key_idx, kt, c->key_xy);
+    if ((rc = launch_verify_miller_fe(c, s, n, BN_PAIRS_VERIFY, 1, d_status, true))) return rc;
+  } else {
+    if ((rc = bn254_pair_miller_verify_keyed(n, c->ws, d_key_idx, kt, s))) return rc;
+    PROF_MARK(3);
+    if ((rc = bn254_pair_final_exp(n, c->ws, 1, d_status, nullptr, nullptr, s))) return rc;
+  }
+  return 0;
+}
+// ... and of one against an empty key set: the statuses straight from the decode
+int launch_keyed_no_keys(bn254_ctx* c, hipStream_t s, size_t n, uint8_t* d_status) {
+  k_keyed_no_keys<<<grid_for(n), BN_WAVE, 0, s>>>(n, c->ws, d_status);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 extern "C" {
 
 // ---- keyed verify (include/bn254_hip.h) ---------------------------------------------------------------------------------
@@ -388,7 +418,6 @@ int bn254_batch_verify_keyed_device(bn254_ctx* c, const uint8_t* d_msgs, const u
   if (rc) return rc;
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   CallDone call_done(c, s);
-  KeyTable kt = {c->key_lines, c->key_st, c->key_inf, (uint32_t)c->n_keys};
   PROF_MARK(0);
   { int rc_ = launch_decode_g1(c, s, d_sigs, n, flags, PL_P1X, BY_P1_INF, 0); if (rc_) return rc_; }
   if (c->n_keys == 0 || !c->key_lines) {             // nothing registered: no table to read — every item is out of range
@@ -399,24 +428,9 @@ int bn254_batch_verify_keyed_device(bn254_ctx* c, const uint8_t* d_msgs, const u
   PROF_MARK(1);
   if ((rc = launch_hash_rounds(c, s, d_msgs, d_off, n, PL_P2X, BY_P2_INF, nullptr))) return rc;
   PROF_MARK(2);
-  const BnRoute r = route_for(c, n);
-  if (r.miller == BN_ML_LANE_MACHINE) {
-    // the smallest batches: the lane machine's keyed form on the line tables themselves (no twist point to walk: 0.32 ms against 0.43)
-    if ((rc = bn254_lm_miller_verify_keyed(n, c->ws, d_key_idx, kt, s))) return rc;
-    PROF_MARK(3);
-    if ((rc = launch_final_exp_layout(c, s, n, 1, d_status, r.fe))) return rc;
-  } else if (r.miller != BN_ML_LANE_PAIRS) {
-    // a batch that cannot fill the chip: latency counts — expand the keys and take the small-batch kernels (2.3 ms instead of the
-    // 6 ms of the lane-pair layout; the line tables pay off only where throughput binds)
-    k_keyed_expand<<<grid_for(n), BN_WAVE, 0, s>>>(n, c->ws, d_key_idx, kt, c->key_xy);
-    if ((rc = launch_verify_miller_fe(c, s, n, BN_PAIRS_VERIFY, 1, d_status, true))) return rc;
-  } else {
-    if ((rc = bn254_pair_miller_verify_keyed(n, c->ws, d_key_idx, kt, s))) return rc;
-    PROF_MARK(3);
-    if ((rc = bn254_pair_final_exp(n, c->ws, 1, d_status, nullptr, nullptr, s))) return rc;
-  }
+  if ((rc = launch_keyed_miller_fe(c, s, n, d_key_idx, d_status))) return rc;
   PROF_MARK(4);
-  if (c->profiling) { c->ev_valid = 1; c->ev_hash_first = 0; }
+  prof_done(c, EV_DECODE_FIRST);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -484,7 +498,7 @@ int bn254_batch_verify_keyed_randomized_device(bn254_ctx* c, const uint8_t* d_ms
   if ((rc = bn254_pair_miller_verify_keyed(n, c->ws, d_key_idx, kt, s, 0, c->ws.h_list, c->ws.h_cnt))) return rc;
   if ((rc = bn254_pair_final_exp(n, c->ws, 1, d_status, c->ws.h_list, c->ws.h_cnt, s))) return rc;
   PROF_MARK(4);
-  if (c->profiling) { c->ev_valid = 1; c->ev_hash_first = 0; }
+  prof_done(c, EV_DECODE_FIRST);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -568,7 +582,7 @@ int bn254_batch_verify_randomized_device(bn254_ctx* c, const uint8_t* d_msgs, co
     { int rc_ = launch_final_exp_lane(c, s, n, 1, 1, 1, 1, nullptr, d_status, 0, 0, c->ws.h_list, c->ws.h_cnt); if (rc_) return rc_; }
   }
   PROF_MARK(4);
-  if (c->profiling) { c->ev_valid = 1; c->ev_hash_first = 0; }
+  prof_done(c, EV_DECODE_FIRST);
   HIP_TRY(hipGetLastError());
   return 0;
 }

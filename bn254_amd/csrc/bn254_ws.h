@@ -267,7 +267,10 @@ __attribute__((visibility("hidden"))) int bn254_pair_bitmap_sum(const uint32_t* 
 #define BITMAP_RAND_MAX_KEYS_DEFAULT 256           // BN254_OPT_BITMAP_RAND_MAX_KEYS: ... while the set has at most this many keys (its sums grow with n_keys / 8 per
                                                    //     tuple: at 1 024 keys it loses at every size measured)
 #define BITMAP_RAND_GROUP_TUPLES_DEFAULT 4096      // BN254_OPT_BITMAP_RAND_GROUP_TUPLES: tuples per group of its combined checks (the sweeps at 65 536 and 2^20 x 256)
+#define COLLECT_WAVE_MIN_SHARES_DEFAULT 16         // BN254_OPT_COLLECT_WAVE_MIN_SHARES (bn254_collect.hip): tuples with at least this many shares are summed by a
+                                                   //     wave each, the shorter ones by a lane each — swept at three shapes only
 __attribute__((visibility("hidden"))) int bn254_aggd_scan_add(hipStream_t s, const uint64_t* in, size_t n, uint64_t* out, uint64_t* tot);
+__attribute__((visibility("hidden"))) int bn254_aggd_scan_max(hipStream_t s, const uint64_t* in, size_t n, uint64_t* out, uint64_t* tot);   // ... the prefix maximum
 __attribute__((visibility("hidden"))) int bn254_aggd_keyed_slot_map(hipStream_t s, size_t n, const uint64_t* lo, const uint64_t* hi, int width,
                                                                     uint64_t* kincl, uint64_t* tot, size_t n_slots, uint32_t* slot_agg);
 

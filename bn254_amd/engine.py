@@ -48,6 +48,7 @@ OPT_BITMAP_RAND_MIN_TUPLES = 33    # randomised signer bitmaps: the exact bitmap
 OPT_BITMAP_RAND_GROUP_TUPLES = 34  # ... tuples per group of its combined checks (developer option)
 OPT_BITMAP_RAND_MAX_KEYS = 35      # ... the exact bitmap call when more keys than this are registered
 OPT_KEY_CACHE = 36                 # key dedup: the line tables stay between calls, a call builds only unseen keys (default 1; 0 = build all, drops the cache)
+OPT_COLLECT_WAVE_MIN_SHARES = 37   # collect_keyed_bitmap: tuples with at least this many shares are summed by a wave each (default 16; swept at three shapes only)
 
 
 class NativeError(RuntimeError):
@@ -516,6 +517,35 @@ class Engine:
     def batch_verify_keyed_bitmap_device(self, d_msgs, d_off, d_sigs, d_signer_bits, bm_words, n, d_status, flags=0, stream=None):
         _check("bn254_batch_verify_keyed_bitmap_device",
                self._lib.bn254_batch_verify_keyed_bitmap_device(self._h, d_msgs, d_off, d_sigs, d_signer_bits, bm_words, n, flags, d_status, stream))
+
+    def batch_collect_keyed_bitmap(self, messages, shares, share_keys, sizes, bm_words, flags=0, want_counts=False):
+        """build signer-bitmap aggregates from individual signatures (include/bn254_hip.h: bn254_batch_collect_keyed_bitmap): tuple i is
+        messages[i] with the next sizes[i] shares (64 B each, share s said to be by registered key share_keys[s]).  Returns (share status
+        bytes, tuple status bytes, the n aggregates, the n * bm_words bitmap words) — and the signer counts with want_counts."""
+        n, n_shares = len(messages), len(share_keys)
+        assert len(sizes) == n and all(k >= 0 for k in sizes) and sum(sizes) == n_shares and len(shares) == n_shares * G1_BYTES
+        msgs, off = pack_messages(messages)
+        ends = [0]
+        for k in sizes:
+            ends.append(ends[-1] + int(k))
+        share_off = (ctypes.c_uint64 * (n + 1))(*ends)
+        keys = (ctypes.c_uint32 * max(n_shares, 1))(*share_keys)
+        share_st = ctypes.create_string_buffer(max(n_shares, 1))
+        tuple_st = ctypes.create_string_buffer(max(n, 1))
+        agg = ctypes.create_string_buffer(max(n, 1) * G1_BYTES)
+        bits = (ctypes.c_uint32 * max(n * bm_words, 1))()
+        counts = (ctypes.c_uint32 * max(n, 1))()
+        _check("bn254_batch_collect_keyed_bitmap",
+               self._lib.bn254_batch_collect_keyed_bitmap(self._h, msgs, off, bytes(shares), keys, share_off, n_shares, n, bm_words, flags,
+                                                          share_st, tuple_st, agg, bits, counts if want_counts else None))
+        out = (share_st.raw[:n_shares], tuple_st.raw[:n], agg.raw[:n * G1_BYTES], list(bits)[:n * bm_words])
+        return out + (list(counts)[:n],) if want_counts else out
+
+    def batch_collect_keyed_bitmap_device(self, d_msgs, d_msg_off, d_shares, d_share_key, d_share_off, n_shares, n, bm_words, d_share_status,
+                                          d_tuple_status, d_agg_sigs, d_signer_bits, d_n_signers=None, flags=0, stream=None):
+        _check("bn254_batch_collect_keyed_bitmap_device",
+               self._lib.bn254_batch_collect_keyed_bitmap_device(self._h, d_msgs, d_msg_off, d_shares, d_share_key, d_share_off, n_shares, n, bm_words,
+                                                                 flags, d_share_status, d_tuple_status, d_agg_sigs, d_signer_bits, d_n_signers, stream))
 
     def batch_verify_keyed_bitmap_randomized(self, messages, sigs, bitmaps, bm_words, seed32, flags=0):
         """batch_verify_keyed_bitmap with the pairing checks of whole groups of tuples combined under random weights from seed32

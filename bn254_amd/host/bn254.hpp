@@ -292,6 +292,49 @@ struct ECDSA {
                                    size_t n_keys, Engine& e = Engine::default_engine()) {
     check_status(batch_verify_keyed_signers({SignerItem{message, signature, signer_indices}}, n_keys, e)[0]);
   }
+  // The producer of such an item (include/bn254_hip.h: bn254_batch_collect_keyed_bitmap): one message and individual signatures, signatures[k]
+  // said to be by registered key key_indices[k].  Every signature is verified against its key; those that pass are added, one per key.
+  // status: 0, or the message's hash ErrorKind (then nothing was added); statuses[k]: what batch_verify_keyed gives signature k.
+  struct ShareItem { std::vector<uint8_t> message; std::vector<Signature> signatures; std::vector<uint32_t> key_indices; };
+  struct KeyedAggregateResult { uint8_t status; Signature signature; std::vector<uint32_t> signer_indices; std::vector<uint8_t> statuses; };
+  static std::vector<KeyedAggregateResult> batch_aggregate_keyed_signers(const std::vector<ShareItem>& items, size_t n_keys, Engine& e = Engine::default_engine()) {
+    const size_t n = items.size(), bm_words = (n_keys + 31) / 32 ? (n_keys + 31) / 32 : 1;
+    std::vector<uint64_t> off(n + 1, 0), share_off(n + 1, 0);
+    std::vector<uint8_t> msgs, shares;
+    std::vector<uint32_t> keys;
+    for (size_t i = 0; i < n; ++i) {
+      if (items[i].signatures.size() != items[i].key_indices.size()) throw Error(ErrorKind::InvalidLength);
+      off[i] = msgs.size();
+      share_off[i] = keys.size();
+      msgs.insert(msgs.end(), items[i].message.begin(), items[i].message.end());
+      for (const Signature& s : items[i].signatures) shares.insert(shares.end(), s.raw.begin(), s.raw.end());
+      keys.insert(keys.end(), items[i].key_indices.begin(), items[i].key_indices.end());
+    }
+    off[n] = msgs.size();
+    share_off[n] = keys.size();
+    std::vector<uint8_t> share_st(keys.size() + 1, 0), tuple_st(n + 1, 0), agg(n * 64 + 1, 0);
+    std::vector<uint32_t> bits(n * bm_words + 1, 0);
+    shares.resize(shares.size() + 1);
+    keys.resize(keys.size() + 1);
+    check_rc("bn254_batch_collect_keyed_bitmap",
+             bn254_batch_collect_keyed_bitmap(e.raw(), msgs.data(), off.data(), shares.data(), keys.data(), share_off.data(), share_off[n], n, bm_words, 0,
+                                              share_st.data(), tuple_st.data(), agg.data(), bits.data(), nullptr));
+    std::vector<KeyedAggregateResult> out(n);
+    for (size_t i = 0; i < n; ++i) {
+      out[i].status = tuple_st[i];
+      std::memcpy(out[i].signature.raw.data(), &agg[64 * i], 64);
+      for (size_t j = 0; j < 32 * bm_words; ++j)
+        if ((bits[i * bm_words + j / 32] >> (j % 32)) & 1u) out[i].signer_indices.push_back((uint32_t)j);
+      out[i].statuses.assign(share_st.begin() + share_off[i], share_st.begin() + share_off[i + 1]);
+    }
+    return out;
+  }
+  static KeyedAggregateResult aggregate_keyed_signers(const std::vector<uint8_t>& message, const std::vector<Signature>& signatures,
+                                                      const std::vector<uint32_t>& key_indices, size_t n_keys, Engine& e = Engine::default_engine()) {
+    KeyedAggregateResult r = batch_aggregate_keyed_signers({ShareItem{message, signatures, key_indices}}, n_keys, e)[0];
+    check_status(r.status);
+    return r;
+  }
   // aggregate_verify against the registered set: key_indices[j] names the key of messages[j]; 2 (IndexOutOfBounds) outside the set
   // (include/bn254_hip.h: bn254_batch_aggregate_verify_distinct_keyed)
   struct KeyedAggregate { std::vector<std::vector<uint8_t>> messages; Signature signature; std::vector<uint32_t> key_indices; };

@@ -404,6 +404,61 @@ int bn254_batch_verify_keyed_bitmap_randomized_device(bn254_ctx *ctx, const uint
                                                       const uint32_t *d_signer_bits, size_t bm_words, size_t n, uint32_t flags,
                                                       const uint8_t *seed32 /* host memory */, uint8_t *d_status, void *stream);
 
+/* BUILDING a signer-bitmap aggregate — the producer half of bn254_batch_verify_keyed_bitmap: per message the node holds individual signatures
+ * ("shares"), each said to be by one registered key, and needs every share checked against its key (one bad share poisons the sum, and the
+ * sum cannot say which), the sum of those that passed, and the bitmap of who they were.  Tuple i is the message msgs[msg_off[i] ..
+ * msg_off[i+1]) and the shares s in [share_off[i], share_off[i+1]); share s is the signature shares[64 s] said to be by registered key
+ * share_key[s].  share_status[s] is the first of:
+ *   1. the share's decode status, exactly as bn254_batch_verify_keyed decodes a signature (the call's flags apply);
+ *   2. 2 (IndexOutOfBounds) if share_key[s] >= n_keys, else the key's non-zero registration status; with no keys registered every share
+ *      that decodes gets 2;
+ *   3. the hash status of the tuple's message: 1 (HashToPointError); in the _device form 5 for reversed or over-long message offsets
+ *      (bn254_ctx_expect_msgs_len applies);
+ *   4. 0 if e(H(m_i), pk_key) * e(share, -G2::one()) == 1, else 9.
+ * DEFINING IDENTITY 1: share_status is byte for byte what bn254_batch_verify_keyed returns, with the same flags, for n_shares items whose
+ * message is their tuple's message repeated.
+ * tuple_status[i] is 0, the hash status of m_i (1 or 5), or — in the _device form, and ahead of the hash status — 2 for a share range that
+ * is reversed, runs past n_shares, or starts before an earlier offset (the range rule of bn254_batch_aggregate_verify_distinct_device).
+ * Such a tuple gets an empty bitmap, the identity as its aggregate and no shares; share_status is first filled with 2, so a share that
+ * belongs to no accepted tuple reads 2.
+ * Outputs of an accepted tuple:
+ *   - signer_bits row i, in the bitmap call's numbering (signer j = bit j % 32 of word i * bm_words + j / 32): bit j is set iff some share of
+ *     the tuple with share_key == j has status 0; words past the key set are zero;
+ *   - agg_sigs[i]: the sum of ONE status-0 share per set bit, uncompressed, the identity as 64 zero bytes;
+ *   - n_signers[i] (the array may be NULL): the popcount of row i.
+ * A key that sent several valid shares counts once.  G1 has prime order, so the valid signature of (m, pk) is unique: the duplicates are the
+ * same point, the result does not depend on which of them is taken, and the sum may be formed in parallel in any order — the bytes are the
+ * same.  Two different indices that hold the same key both count, as the bitmap verify sums both.
+ * Argument checks: bm_words >= ceil(n_keys / 32) — a bitmap that cannot hold a registered key cannot describe the result — and bm_words <=
+ * 0xFFFFFFFF, else BN254_E_BAD_ARGUMENT; n and n_shares < 2^32; host form: share_off[0] == 0, non-decreasing, share_off[n] == n_shares.
+ * BN254_E_MISALIGNED as in the bitmap call: shares, share_key, agg_sigs, signer_bits and n_signers 4-byte aligned, the offsets 8-byte
+ * aligned.  n == 0 returns 0.  BN254_OPT_MAX_CHUNK slices the SHARES (and the tuples' hashing) freely; the outputs are the same.
+ * DEFINING IDENTITY 2 (closed loop, flags = 0): bn254_batch_verify_keyed_bitmap(msgs, agg_sigs, signer_bits, bm_words) on the call's own
+ * outputs returns 0 for every tuple with tuple_status == 0 — the tuple with no valid share (empty bitmap, identity signature) and a key and
+ * its negation both signing (two bits set, the aggregate is the identity) included.
+ * Cost: ONE hash-to-G1 per tuple (not per share), one keyed verify per share (the routing table and the line tables of
+ * bn254_batch_verify_keyed, unchanged), and one G1 addition per counted share in a select-and-sum launched once behind the last slice: a
+ * tuple of fewer than BN254_OPT_COLLECT_WAVE_MIN_SHARES shares is walked by one lane, a longer one by the 64 lanes of a wave (bits claimed
+ * with atomic ORs on the zeroed row, 64 partial sums folded by six levels of additions in LDS).  The _device form only enqueues: no host
+ * synchronisation, the range rule included.  Measured on an MI355X (tools/collect_throughput.py, profiles/collect_throughput.jsonl; 256 keys,
+ * every share valid; per-stage times from bn254_ctx_last_kernel_ms): 256 tuples x 171 shares — front end 0.19 ms, select-and-sum 0.24, Miller
+ * loop 4.03, final exponentiation 3.61, against the keyed verify's 0.03 + 0.32 (hash) + 4.05 + 3.60 on the 43 776 repeated messages;
+ * 4 096 x 11 — 0.32, 0.18, 3.99, 3.58 against 0.01 + 0.33 + 4.01 + 3.59; one tuple of 4 096 shares — 0.22, 0.27 (one wave), 1.06, 1.14:
+ * the sum is an eighth of its verify (one lane: 4.6 ms).  So the device work exceeds the keyed verify's by about 0.1 ms: hashing once saves
+ * less than the spread and the sum cost.  What the call spares a caller of bn254_batch_verify_keyed_device is what followed that verify: the
+ * copy of the statuses to the host, the filter there, and bn254_batch_g1_sum, whose host-pointer form stages every share again and walks each
+ * segment in one lane.  Whole-call intervals of both routes, as far as they were measured: DESIGN.md section 10e.
+ * Out of scope: a randomised form (the shares of a tuple share H(m), not the key: a different grouping), the multi-GPU layer, compressed shares. */
+int bn254_batch_collect_keyed_bitmap(bn254_ctx *ctx, const uint8_t *msgs, const uint64_t *msg_off /* n+1 */,
+                                     const uint8_t *shares /* n_shares*64 */, const uint32_t *share_key /* n_shares */,
+                                     const uint64_t *share_off /* n+1 */, size_t n_shares, size_t n, size_t bm_words, uint32_t flags,
+                                     uint8_t *share_status /* n_shares */, uint8_t *tuple_status /* n */, uint8_t *agg_sigs /* n*64 */,
+                                     uint32_t *signer_bits /* n*bm_words */, uint32_t *n_signers /* n, or NULL */);
+int bn254_batch_collect_keyed_bitmap_device(bn254_ctx *ctx, const uint8_t *d_msgs, const uint64_t *d_msg_off, const uint8_t *d_shares,
+                                            const uint32_t *d_share_key, const uint64_t *d_share_off, size_t n_shares, size_t n, size_t bm_words,
+                                            uint32_t flags, uint8_t *d_share_status, uint8_t *d_tuple_status, uint8_t *d_agg_sigs,
+                                            uint32_t *d_signer_bits, uint32_t *d_n_signers, void *stream);
+
 /* compressed wire formats (src/utils.rs:84-104, :130-158): out = uncompressed point, status as
  * bn::G1::from_compressed / bn::G2::from_compressed report through src/types.rs:91-93, :233-237, checked in the order
  * those decoders work (an input with several faults reports the first):
@@ -483,6 +538,10 @@ int bn254_ctx_set_profiling(bn254_ctx *ctx, int enabled);
 #define BN254_OPT_BITMAP_RAND_MAX_KEYS 35 /* ... and when more keys than this are registered (same statuses): the G1 side costs one addition per
                                            bitmap byte and tuple, which at 1 024 keys outweighs what the route saves at every size measured.
                                            Default 256 */
+#define BN254_OPT_COLLECT_WAVE_MIN_SHARES 37 /* bn254_batch_collect_keyed_bitmap, developer option: tuples with at least this many shares are summed by
+                                               one wave each (64 partial sums and a tree), shorter ones by one lane each; >= 1.  Default 16 — a
+                                               figure NOBODY HAS MEASURED beyond three shapes (tools/collect_throughput.py --wave-min: tuples of 11 shares sum in 0.18 ms by lanes
+                                               against 0.62 by waves, tuples of 171 in 0.24 by waves against 1.86 by lanes; nothing in between).  Same bytes either way */
 int bn254_ctx_set_option(bn254_ctx *ctx, int option, int value);
 /* per-kernel times of the last verify-shaped call with profiling on (HIP events on the call's stream):
  * ms[0] decode, ms[1] hash-to-G1, ms[2] Miller loop, ms[3] final exponentiation.  The host-pointer bn254_batch_verify runs
@@ -490,7 +549,9 @@ int bn254_ctx_set_option(bn254_ctx *ctx, int option, int value);
  * hash_to_g1 ms[0] = the filter rounds (SHA-256 + Jacobi symbol per tested counter), ms[1] = the square roots (one per message), ms[2] = encoding the
  * points, ms[3] = 0; aggregate_verify ms[0] = the pools
  * (decoding, hashing the messages, the subset-sum table), ms[1] = the aggregation kernel; verify_keyed_bitmap ms[0] = sigma's decode + hash-to-G1,
- * ms[1] = the aggregate keys (the summation kernel; the lazy table build runs ahead of ms[0]), ms[2] Miller loop, ms[3] final exponentiation. */
+ * ms[1] = the aggregate keys (the summation kernel; the lazy table build runs ahead of ms[0]), ms[2] Miller loop, ms[3] final exponentiation;
+ * collect_keyed_bitmap ms[0] = decode + hash-to-G1 (once per tuple) + spread, ms[1] = select-and-sum (it runs last), ms[2] Miller loop,
+ * ms[3] final exponentiation (the last slice's; the hash counts in ms[0] only when the call ran in one piece). */
 int bn254_ctx_last_kernel_ms(bn254_ctx *ctx, float ms[4]);
 /* with BN254_OPT_CLOCK_PROBE on: achieved shader clock in MHz of the lane-pair Miller kernels [0], final exponentiations [1] and probe
  * kernels (bn254_probe_issue_rate, bn254_probe_leaf_floor) [2] launched on this context SINCE THE PREVIOUS CALL of this function (or

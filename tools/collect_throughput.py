@@ -1,0 +1,152 @@
+#!/usr/bin/env python3
+"""bn254_batch_collect_keyed_bitmap_device against what a caller did without it, inputs resident in HBM, 256 registered keys, every share
+valid.  Per shape n tuples x k shares (the signers of a tuple: k distinct keys drawn at random; a tuple with more shares than keys repeats
+them):
+  (a) the new call;
+  (b) bn254_batch_verify_keyed_device on the tuple's message repeated once per share, a copy of the statuses to the host, the filter there,
+      and bn254_batch_g1_sum (host pointers) over the shares that passed, one segment per tuple.  The bitmap, which the caller would also
+      assemble by hand, is not counted.
+Both are timed with HIP events on the caller's stream around whole calls, alternating, `--reps` calls each after two warm-up calls: the
+median, with the min and max beside it.  (b)'s interval contains its host work — that is the route.  Per-stage times of one profiled call
+of (a) and of the keyed verify: bn254_ctx_last_kernel_ms ((a): ms[0] decode + hash + spread, ms[1] select-and-sum, ms[2] Miller loop,
+ms[3] final exponentiation).  --wave-min sweeps BN254_OPT_COLLECT_WAVE_MIN_SHARES for (a).  One JSON line per shape (default stdout).
+    python tools/collect_throughput.py [out.jsonl] [--reps R] [--wave-min W ...] [shape ...]      shape = n:k"""
+import argparse
+import ctypes
+import hashlib
+import json
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402  (first: one HIP runtime per process)
+import bn254_amd  # noqa: E402
+from bn254_amd import _native  # noqa: E402
+from bn254_amd.engine import OPT_COLLECT_WAVE_MIN_SHARES  # noqa: E402
+from tests.datagen import sk_bytes  # noqa: E402
+
+R = 0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001
+N_KEYS = 256
+SHAPES = [(256, 171), (4096, 11), (1, 4096)]
+MSG_LEN = 32
+
+
+def dev(data):
+    t = torch.empty(max(len(data), 8), dtype=torch.uint8, device="cuda")
+    if len(data):
+        t[:len(data)].copy_(torch.frombuffer(bytearray(data), dtype=torch.uint8))
+    return t
+
+
+def _check(rc):
+    if rc != 0:
+        raise RuntimeError("library call failed: %d" % rc)
+
+
+def timed(fn, ts):
+    """ms between two HIP events on the stream the calls are enqueued on"""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record(ts)
+    fn()
+    e1.record(ts)
+    e1.synchronize()
+    return e0.elapsed_time(e1)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("out", nargs="?")
+    ap.add_argument("shapes", nargs="*")
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--wave-min", type=int, nargs="*", default=[])
+    a = ap.parse_intermixed_args()
+    out = open(a.out, "a") if a.out else sys.stdout
+    shapes = [tuple(int(x) for x in s.split(":")) for s in a.shapes] or SHAPES
+    eng = bn254_amd.Engine(0)
+    lib, h = eng._lib, eng._h
+    ts = torch.cuda.Stream()                        # a stream of the caller's own: a null handle would send the calls to the context's stream
+    stream = ctypes.c_void_p(ts.cuda_stream)
+    box = {"device": torch.cuda.get_device_name(0), "lib_sha256": hashlib.sha256(open(_native.LIB_PATH, "rb").read()).hexdigest()[:16],
+           "n_keys": N_KEYS, "reps": a.reps}
+    rng = np.random.default_rng(20261018)
+    sks = [int.from_bytes(sk_bytes(9000 + j), "big") % R for j in range(N_KEYS)]
+    pool, st = eng.batch_g2_mul(None, b"".join(s.to_bytes(32, "big") for s in sks), N_KEYS, reduce_scalar=True)
+    assert st == bytes(N_KEYS) and eng.register_keys(pool) == bytes(N_KEYS)
+    bm_words = N_KEYS // 32
+
+    for n, k in shapes:
+        n_shares = n * k
+        keys = np.concatenate([np.resize(rng.permutation(N_KEYS), k) for _ in range(n)]).astype(np.uint32)
+        msgs = [hashlib.sha256(b"collect/tp/%d/%d/%d" % (n, k, i)).digest() for i in range(n)]
+        rep = [msgs[s // k] for s in range(n_shares)]
+        shares, st = eng.batch_sign(rep, b"".join(sks[j].to_bytes(32, "big") for j in keys))
+        assert st == bytes(n_shares)
+        share_off = np.arange(n + 1, dtype=np.uint64) * k
+        d_msgs, d_moff = dev(b"".join(msgs)), dev((np.arange(n + 1, dtype=np.uint64) * MSG_LEN).tobytes())
+        d_rep, d_roff = dev(b"".join(rep)), dev((np.arange(n_shares + 1, dtype=np.uint64) * MSG_LEN).tobytes())
+        d_shares, d_keys, d_soff = dev(shares), dev(keys.tobytes()), dev(share_off.tobytes())
+        d_sst, d_tst, d_agg, d_bits, d_cnt = dev(bytes(n_shares)), dev(bytes(n)), dev(bytes(64 * n)), dev(bytes(4 * bm_words * n)), dev(bytes(4 * n))
+        d_kst = dev(bytes(n_shares))
+        sum_out, sum_st = ctypes.create_string_buffer(64 * n), ctypes.create_string_buffer(n)
+        seg = (ctypes.c_uint64 * (n + 1))(*[int(x) for x in share_off])
+
+        def collect():
+            _check(lib.bn254_batch_collect_keyed_bitmap_device(h, d_msgs.data_ptr(), d_moff.data_ptr(), d_shares.data_ptr(), d_keys.data_ptr(),
+                                                               d_soff.data_ptr(), n_shares, n, bm_words, 0, d_sst.data_ptr(), d_tst.data_ptr(),
+                                                               d_agg.data_ptr(), d_bits.data_ptr(), d_cnt.data_ptr(), stream))
+
+        def keyed():
+            _check(lib.bn254_batch_verify_keyed_device(h, d_rep.data_ptr(), d_roff.data_ptr(), d_shares.data_ptr(), d_keys.data_ptr(), n_shares, 0,
+                                                       d_kst.data_ptr(), stream))
+
+        def parent_route():
+            keyed()
+            with torch.cuda.stream(ts):
+                status = d_kst[:n_shares].cpu().numpy()
+            assert not status.any()                                   # the filter: every share passed, so the sum takes them all
+            _check(lib.bn254_batch_g1_sum(h, shares, seg, n, sum_out, sum_st))
+
+        for fn in (collect, parent_route, collect, parent_route):
+            fn()
+        torch.cuda.synchronize()
+        # with more shares than keys a tuple repeats its signers: (a) takes one share per key, (b)'s plain sum takes them all — no comparison there
+        same = not d_sst[:n_shares].cpu().numpy().any() and (k > N_KEYS or bytes(d_agg.cpu().numpy().tobytes()[:64 * n]) == sum_out.raw)
+        counts = np.frombuffer(d_cnt.cpu().numpy().tobytes()[:4 * n], dtype=np.uint32)
+        ms = {"a": [], "b": [], "keyed": []}
+        for _ in range(a.reps):
+            ms["a"].append(timed(collect, ts))
+            ms["b"].append(timed(parent_route, ts))
+            ms["keyed"].append(timed(keyed, ts))
+        stages = {}
+        for name, fn in (("a_collect", collect), ("keyed_verify", keyed)):
+            eng.set_profiling(True)
+            fn()
+            kms = eng.last_kernel_ms()
+            eng.set_profiling(False)
+            stages[name] = [round(kms[x], 3) for x in ("decode", "hash_to_g1", "miller_loop", "final_exp")]
+        sweep = {}
+        for w in a.wave_min:
+            eng.set_option(OPT_COLLECT_WAVE_MIN_SHARES, w)
+            collect()
+            sweep[str(w)] = round(statistics.median([timed(collect, ts) for _ in range(a.reps)]), 3)
+            eng.set_profiling(True)
+            collect()
+            sweep[str(w) + "_sum_ms"] = round(eng.last_kernel_ms()["hash_to_g1"], 3)
+            eng.set_profiling(False)
+        eng.set_option(OPT_COLLECT_WAVE_MIN_SHARES, 16)
+        med = {x: statistics.median(v) for x, v in ms.items()}
+        row = {"shape": "%dx%d" % (n, k), "n": n, "shares_per_tuple": k, "n_shares": n_shares, "mean_signers": round(float(counts.mean()), 1),
+               "a_ms": round(med["a"], 3), "a_min_ms": round(min(ms["a"]), 3), "a_max_ms": round(max(ms["a"]), 3),
+               "b_ms": round(med["b"], 3), "b_min_ms": round(min(ms["b"]), 3), "b_max_ms": round(max(ms["b"]), 3),
+               "keyed_verify_alone_ms": round(med["keyed"], 3), "b_over_a": round(med["b"] / med["a"], 2),
+               "a_not_slower_beyond_spread": max(ms["a"]) <= min(ms["b"]),
+               "stages_ms": stages, "stage_slots": {"a_collect": "decode+hash+spread, select-and-sum, miller, final_exp", "keyed_verify": "decode, hash, miller, final_exp"},
+               "wave_min_sweep_ms": sweep, "same_aggregates_all_valid": bool(same), **box}
+        print(json.dumps(row), file=out, flush=True)
+        del d_msgs, d_moff, d_rep, d_roff, d_shares, d_keys, d_soff, d_sst, d_tst, d_agg, d_bits, d_cnt, d_kst
+
+
+if __name__ == "__main__":
+    main()

@@ -339,6 +339,10 @@ class ECDSA:
         """items: a list of (message, signatures, key_indices); result[i] is what ECDSA.aggregate_keyed_signers returns for item i, or the
         Error it would raise.  A malformed item (not such a triple, lengths that differ, an index that is negative or >= 2^32) raises
         before any device work.  n_keys: the size of the registered set, for an engine that did not register it itself."""
+        return ECDSA._aggregate_keyed_signers(items, engine, n_keys)
+
+    @staticmethod
+    def _aggregate_keyed_signers(items, engine, n_keys, seed=None, flags=0):
         rows = []
         for item in items:
             if len(item) != 3:
@@ -356,8 +360,11 @@ class ECDSA:
         if n_keys is None:             # the bitmaps are as wide as the registered set, which the items cannot tell
             raise ValueError("the engine does not know its registered key count: pass n_keys")
         bm_words = max((int(n_keys) + 31) // 32, 1)
-        share_st, tuple_st, agg, bits = eng.batch_collect_keyed_bitmap(
-            [r[0] for r in rows], b"".join(s.raw for r in rows for s in r[1]), [j for r in rows for j in r[2]], [len(r[2]) for r in rows], bm_words)
+        args = ([r[0] for r in rows], b"".join(s.raw for r in rows for s in r[1]), [j for r in rows for j in r[2]], [len(r[2]) for r in rows], bm_words)
+        if seed is not None:
+            share_st, tuple_st, agg, bits = eng.batch_collect_keyed_bitmap_randomized(*args, seed, flags)
+        else:
+            share_st, tuple_st, agg, bits = eng.batch_collect_keyed_bitmap(*args)
         out, at = [], 0
         for i, (_, _, idx) in enumerate(rows):
             st = share_st[at:at + len(idx)]
@@ -369,6 +376,28 @@ class ECDSA:
             signers = [j for j in range(32 * bm_words) if (row[j // 32] >> (j % 32)) & 1]
             out.append((Signature(agg[64 * i:64 * i + 64]), signers, [None if b == 0 else Error(b) for b in st]))
         return out
+
+    @staticmethod
+    def batch_aggregate_keyed_signers_randomized(items, seed=None, engine=None, n_keys=None, rand64=False):
+        """batch_aggregate_keyed_signers with the pairing checks of the signatures combined, 64 signatures of one key at a time across the
+        items of the call (include/bn254_hip.h: bn254_batch_collect_keyed_bitmap_randomized): the same result list and the same refusals
+        before any device work.  An Error among the statuses is always the exact one; a None is wrong with probability <= 2^-128 per group
+        (2^-64 with rand64) for a fresh SECRET seed (32 bytes; default os.urandom): who knows the seed can make two bad signatures of one
+        key pass together."""
+        import os
+        if seed is None:
+            seed = os.urandom(32)
+        if len(seed) != 32:
+            raise ValueError("seed must be 32 bytes")
+        return ECDSA._aggregate_keyed_signers(items, engine, n_keys, bytes(seed), _engine.FLAG_RAND64 if rand64 else 0)
+
+    @staticmethod
+    def aggregate_keyed_signers_randomized(message, signatures, key_indices, seed=None, engine=None, n_keys=None, rand64=False):
+        """aggregate_keyed_signers through batch_aggregate_keyed_signers_randomized: the same triple, the same Errors raised."""
+        r = ECDSA.batch_aggregate_keyed_signers_randomized([(message, signatures, key_indices)], seed, engine, n_keys, rand64)[0]
+        if isinstance(r, Error):
+            raise r
+        return r
 
     @staticmethod
     def batch_verify_keyed_signers_randomized(items, seed=None, engine=None, rand64=False):

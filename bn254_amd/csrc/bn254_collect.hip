@@ -2,6 +2,8 @@
 // bn254_batch_collect_keyed_bitmap[_device]) — the producer half of the bitmap verify.  Hash once per tuple, spread H(m)
 // over the tuple's share slots, the keyed verify of the slots unchanged, then select-and-sum in two layouts.  The bookkeeping and the
 // arithmetic of the kernels are bn254_collect.h, shared with the CPU suite's host compilation.
+// bn254_batch_collect_keyed_bitmap_randomized[_device] is the same call with the slots verified by the grouped checks of the
+// randomised keyed verify (bn254_rand.hip: launch_keyed_rand_checks): the shares of a slice grouped by key across its tuples.
 // Per-share semantics: ECDSA::verify (/root/reference/src/ecdsa.rs:49-64); the sum: `Add for Signature` (src/types.rs:264-270).
 #include <hip/hip_runtime.h>
 
@@ -25,9 +27,12 @@ using namespace bn254;
 
 // per tuple, outside the (sliced) workspace: the scans of the range rule, H(m) with its identity flag and hash status
 #define CL_HASH_WORDS (2 * BN_LIMBS)
-struct ClScratch { uint64_t *mx, *hi, *end, *tot; int32_t* hpt; uint8_t *hinf, *hst; };
+// ... and, in front, what the randomised slices of the call did: {slices, groups checked, groups failed, shares re-checked exactly}
+#define CL_STAT_WORDS 4
+struct ClScratch { uint32_t* stats; uint64_t *mx, *hi, *end, *tot; int32_t* hpt; uint8_t *hinf, *hst; };
 static ClScratch cl_scratch(Carve& c, size_t n) {
   ClScratch b;
+  b.stats = c.take<uint32_t>(CL_STAT_WORDS);
   b.mx = c.take<uint64_t>(n), b.hi = c.take<uint64_t>(n), b.end = c.take<uint64_t>(n);
   b.tot = c.take<uint64_t>((n + AGGD_SCAN_WG - 1) / AGGD_SCAN_WG);
   b.hpt = c.take<int32_t>(n * CL_HASH_WORDS);
@@ -140,13 +145,58 @@ static int cl_verify_slice(bn254_ctx* c, hipStream_t s, const uint8_t* d_shares,
   return 0;
 }
 
-extern "C" {
+// ---- the randomised route -------------------------------------------------------------------------------------------------------------------
+// what a slice's grouped checks did, added to the call's counters: one wave behind launch_keyed_rand_checks, which left {groups, slots} in
+// meta, the groups' verdicts in group_st and the length of the exact re-check's queue in h_cnt[0]
+KERNEL_SMALL void k_cl_rand_count(const uint32_t* meta, const uint8_t* group_st, const uint32_t* h_cnt, uint32_t* stats) {
+  const unsigned t = threadIdx.x;
+  uint32_t failed = 0;
+  for (uint32_t g = t; g < meta[0]; g += BN_WAVE) failed += group_st[g] != ST_OK ? 1u : 0u;
+  if (failed) atomicAdd(&stats[2], failed);
+  if (t == 0) { atomicAdd(&stats[0], 1u); atomicAdd(&stats[1], meta[0]); atomicAdd(&stats[3], h_cnt[0]); }
+}
+// The shares per slice of the randomised route.  A slice of len shares needs keyed_rand_need(c, len).ws_entries workspace entries — the
+// slots and, behind them, one entry per group — so the length is chosen for the ENTRIES that fit, never reserved as len alone:
+//   * BN254_OPT_MAX_CHUNK set: that many shares, as the caller asked, and the entries that go with them;
+//   * else everything in one slice when the entries of the whole call fit (ws_chunk_for prices entries, whatever they hold);
+//   * else the largest multiple of 256 shares whose entries fit in what ws_chunk_for allows: len + len / 64 + n_keys + 1 <= entries.
+// 0 = the allowance holds no slice with its groups: the caller takes the exact route (same bytes).
+static size_t cl_rand_slice_len(bn254_ctx* c, size_t n_shares) {
+  if (c->max_chunk > 0) return n_shares < (size_t)c->max_chunk ? n_shares : (size_t)c->max_chunk;
+  const size_t entries = ws_chunk_for(c, keyed_rand_need(c, n_shares).ws_entries);
+  if (entries == 0) return n_shares;
+  const size_t fixed = c->n_keys + 1 + 256;
+  if (entries <= fixed + 256) return 0;
+  const size_t len = ((entries - fixed) / 65 * 64) & ~(size_t)255;
+  return len < n_shares ? len : n_shares;
+}
+// ... and a slice whose padded runs (64 slots per group) would not be numbered in 32 bits is not grouped at all
+static bool cl_rand_slots_fit(const bn254_ctx* c, size_t len) { return keyed_rand_need(c, len).groups_max <= (size_t)0x03FFFFFF; }
+// one slice of the shares on that route: decode and spread as cl_verify_slice, then the grouped checks of the slots with the weights of the
+// shares' own indices (index_base = lo).  The spread has put H(m) and the hash status of its tuple into every slot, which is the layout
+// k_krand_prepare and the exact re-check read.  ms[2] = grouping + scalar ladders, ms[3] = group checks + exact re-checks.
+static int cl_verify_slice_rand(bn254_ctx* c, hipStream_t s, const uint8_t* d_shares, const uint32_t* d_share_key, const uint64_t* d_share_off, size_t n,
+                                size_t lo, size_t len, uint32_t dflags, const RandSeed& seed, int mode, const ClScratch& S, uint8_t* d_share_status) {
+  int rc;
+  if (lo) PROF_MARK(1);
+  if ((rc = launch_decode_g1(c, s, d_shares + 64 * lo, len, dflags, PL_P1X, BY_P1_INF, 0))) return rc;
+  k_cl_spread<<<grid_for(len), BN_WAVE, 0, s>>>(len, (uint64_t)lo, n, d_share_off, S, c->ws);
+  HIP_TRY(hipGetLastError());
+  PROF_MARK(2);
+  if ((rc = launch_keyed_rand_checks(c, s, len, d_share_key + lo, seed, mode, (uint64_t)lo, d_share_status + lo))) return rc;
+  k_cl_rand_count<<<1, BN_WAVE, 0, s>>>(keyed_rand_meta(c), keyed_rand_group_st(c), c->ws.h_cnt, S.stats);
+  HIP_TRY(hipGetLastError());
+  PROF_MARK(4);
+  return 0;
+}
 
-int bn254_batch_collect_keyed_bitmap_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t* d_msg_off, const uint8_t* d_shares,
-                                            const uint32_t* d_share_key, const uint64_t* d_share_off, size_t n_shares, size_t n, size_t bm_words,
-                                            uint32_t flags, uint8_t* d_share_status, uint8_t* d_tuple_status, uint8_t* d_agg_sigs,
-                                            uint32_t* d_signer_bits, uint32_t* d_n_signers, void* stream) {
+// both calls: seed32 == nullptr is the exact one
+static int cl_collect_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t* d_msg_off, const uint8_t* d_shares,
+                             const uint32_t* d_share_key, const uint64_t* d_share_off, size_t n_shares, size_t n, size_t bm_words,
+                             uint32_t flags, const uint8_t* seed32, uint8_t* d_share_status, uint8_t* d_tuple_status, uint8_t* d_agg_sigs,
+                             uint32_t* d_signer_bits, uint32_t* d_n_signers, void* stream) {
   MsgsLenScope msgs_len_scope(c);
+  if (c) c->clr_last_ran = 0;
   if (!c || bm_words > 0xFFFFFFFFu || n > 0xFFFFFFFFu || n_shares > 0xFFFFFFFFu) return BN254_E_BAD_ARGUMENT;
   if (bm_words < (c->n_keys + 31) / 32) return BN254_E_BAD_ARGUMENT;       // a bitmap that cannot hold a registered key cannot describe the result
   if (n && (!d_msgs || !d_msg_off || !d_share_off || !d_tuple_status || !d_agg_sigs || (bm_words && !d_signer_bits))) return BN254_E_BAD_ARGUMENT;
@@ -158,17 +208,40 @@ int bn254_batch_collect_keyed_bitmap_device(bn254_ctx* c, const uint8_t* d_msgs,
   HIP_TRY(hipSetDevice(c->device));
   // every buffer before the first kernel: growing one waits for the context's streams, which must not happen between the steps.  The
   // tuples are hashed, and the shares verified, in pieces of the slicing rule's size; the scratch holds the whole call.
-  const size_t t_chunk = ws_chunk_for(c, n), s_chunk = n_shares ? ws_chunk_for(c, n_shares) : 0;
-  const size_t t_piece = t_chunk ? t_chunk : n, s_piece = s_chunk ? s_chunk : n_shares;
-  int rc = ws_reserve(c, t_piece > s_piece ? t_piece : s_piece);
+  // The randomised route when the host can tell that it pays: keys to group by, enough shares, enough of them per key (groups are per key: a
+  // call whose keys have one or two shares each buys padding, not speed) — and a slice with its groups fits.  Else the exact route, same bytes.
+  size_t r_piece = 0;
+  if (seed32 && c->n_keys && c->key_lines && n_shares && n_shares >= (size_t)c->collect_rand_min_shares &&
+      n_shares / c->n_keys >= (size_t)c->collect_rand_min_per_key)
+    r_piece = cl_rand_slice_len(c, n_shares);
+  if (r_piece && !cl_rand_slots_fit(c, r_piece)) r_piece = 0;
+  const bool rand = r_piece != 0;
+  // the randomised call's own flags choose the weights; the remaining ones apply to the shares' decode on either route
+  const int mode = rand_mode_of(flags);
+  if (seed32) flags &= BN254_FLAG_G2_SUBGROUP_CHECK | BN254_FLAG_REJECT_IDENTITY;
+  const size_t t_chunk = ws_chunk_for(c, n), s_chunk = n_shares && !rand ? ws_chunk_for(c, n_shares) : 0;
+  const size_t t_piece = t_chunk ? t_chunk : n, s_piece = rand ? r_piece : s_chunk ? s_chunk : n_shares;
+  const size_t s_entries = rand ? keyed_rand_need(c, s_piece).ws_entries : s_piece;
+  int rc = ws_reserve(c, t_piece > s_entries ? t_piece : s_entries);
   if (rc) return rc;
+  if (rand) {                                          // the grouping scratch of the longest slice (stage slots 5 and 7) covers every slice
+    const KeyedRandNeed need = keyed_rand_need(c, s_piece);
+    if ((rc = stage_reserve(c, 5, need.words * sizeof(uint32_t)))) return rc;
+    if ((rc = stage_reserve(c, 7, need.groups_max))) return rc;
+  }
   Carve size(nullptr);
   cl_scratch(size, n);
   if ((rc = scratch_reserve(c, &c->collect_buf, &c->collect_cap, size.used))) return rc;
   Carve carve(c->collect_buf);
   const ClScratch S = cl_scratch(carve, n);
+  c->clr_stats = S.stats;
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   CallDone call_done(c, s);
+  RandSeed seed = {};
+  if (rand) {
+    seed = rand_seed_from(seed32);
+    HIP_TRY(hipMemsetAsync(S.stats, 0, CL_STAT_WORDS * sizeof(uint32_t), s));
+  }
   PROF_MARK(1);
   // 1. hash once per tuple
   for (size_t lo = 0; lo < n; lo += t_piece) {
@@ -185,9 +258,12 @@ int bn254_batch_collect_keyed_bitmap_device(bn254_ctx* c, const uint8_t* d_msgs,
   if (bm_words) HIP_TRY(hipMemsetAsync(d_signer_bits, 0, n * bm_words * sizeof(uint32_t), s));
   if (n_shares) HIP_TRY(hipMemsetAsync(d_share_status, ST_INDEX_OOB, n_shares, s));
   // 3. the keyed verify of the share slots
-  for (size_t lo = 0; lo < n_shares; lo += s_piece)
-    if ((rc = cl_verify_slice(c, s, d_shares, d_share_key, d_share_off, n, lo, n_shares - lo < s_piece ? n_shares - lo : s_piece, flags, S, d_share_status)))
+  for (size_t lo = 0; lo < n_shares; lo += s_piece) {
+    const size_t len = n_shares - lo < s_piece ? n_shares - lo : s_piece;
+    if ((rc = rand ? cl_verify_slice_rand(c, s, d_shares, d_share_key, d_share_off, n, lo, len, flags, seed, mode, S, d_share_status)
+                   : cl_verify_slice(c, s, d_shares, d_share_key, d_share_off, n, lo, len, flags, S, d_share_status)))
       return rc;
+  }
   if (!n_shares) { PROF_MARK(2); PROF_MARK(3); PROF_MARK(4); }
   // 4. select-and-sum, once, behind the last slice
   const ClShares in = {d_shares, d_share_key, d_share_off, d_share_status, d_tuple_status};
@@ -198,13 +274,16 @@ int bn254_batch_collect_keyed_bitmap_device(bn254_ctx* c, const uint8_t* d_msgs,
   PROF_MARK(0);
   prof_done(c, EV_COLLECT);
   HIP_TRY(hipGetLastError());
+  c->clr_last_ran = rand ? 1 : 0;                      // only a call that enqueued everything has something for the debug hook to read
   return 0;
 }
 
-int bn254_batch_collect_keyed_bitmap(bn254_ctx* c, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* shares, const uint32_t* share_key,
-                                     const uint64_t* share_off, size_t n_shares, size_t n, size_t bm_words, uint32_t flags, uint8_t* share_status,
-                                     uint8_t* tuple_status, uint8_t* agg_sigs, uint32_t* signer_bits, uint32_t* n_signers) {
+// the host-pointer form of both.  The randomised call's grouping scratch lives in stage slots 5 and 7, so its outputs take slot 6.
+static int cl_collect_host(bn254_ctx* c, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* shares, const uint32_t* share_key,
+                           const uint64_t* share_off, size_t n_shares, size_t n, size_t bm_words, uint32_t flags, const uint8_t* seed32,
+                           uint8_t* share_status, uint8_t* tuple_status, uint8_t* agg_sigs, uint32_t* signer_bits, uint32_t* n_signers) {
   MsgsLenScope msgs_len_scope(c);
+  if (c) c->clr_last_ran = 0;
   if (!c || bm_words > 0xFFFFFFFFu || n > 0xFFFFFFFFu || n_shares > 0xFFFFFFFFu) return BN254_E_BAD_ARGUMENT;
   if (bm_words < (c->n_keys + 31) / 32) return BN254_E_BAD_ARGUMENT;
   if (n && (!msg_off || !share_off || !tuple_status || !agg_sigs || (bm_words && !signer_bits))) return BN254_E_BAD_ARGUMENT;
@@ -219,7 +298,7 @@ int bn254_batch_collect_keyed_bitmap(bn254_ctx* c, const uint8_t* msgs, const ui
   const uint8_t* d_share_off = st.in(4, share_off, (n + 1) * sizeof(uint64_t));
   // the five outputs share one slot: the aligned ones first
   const size_t o_bits = n * 64, o_cnt = o_bits + n * bm_words * sizeof(uint32_t), o_sst = o_cnt + n * sizeof(uint32_t), o_tst = o_sst + n_shares;
-  uint8_t* d_out = st.out(5, o_tst + n);
+  uint8_t* d_out = st.out(seed32 ? 6 : 5, o_tst + n);
   if (st.ok()) {
     st.copy_back(agg_sigs, d_out, n * 64);
     st.copy_back(signer_bits, d_out + o_bits, n * bm_words * sizeof(uint32_t));
@@ -228,10 +307,43 @@ int bn254_batch_collect_keyed_bitmap(bn254_ctx* c, const uint8_t* msgs, const ui
     st.copy_back(tuple_status, d_out + o_tst, n);
   }
   if (st.ok())
-    st.rc = bn254_batch_collect_keyed_bitmap_device(c, d_msgs, (const uint64_t*)d_msg_off, d_shares, (const uint32_t*)d_key, (const uint64_t*)d_share_off,
-                                                    n_shares, n, bm_words, flags, d_out + o_sst, d_out + o_tst, d_out, (uint32_t*)(d_out + o_bits),
-                                                    n_signers ? (uint32_t*)(d_out + o_cnt) : nullptr, nullptr);
+    st.rc = cl_collect_device(c, d_msgs, (const uint64_t*)d_msg_off, d_shares, (const uint32_t*)d_key, (const uint64_t*)d_share_off, n_shares, n, bm_words,
+                              flags, seed32, d_out + o_sst, d_out + o_tst, d_out, (uint32_t*)(d_out + o_bits),
+                              n_signers ? (uint32_t*)(d_out + o_cnt) : nullptr, nullptr);
   return st.finish();
+}
+
+extern "C" {
+
+int bn254_batch_collect_keyed_bitmap_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t* d_msg_off, const uint8_t* d_shares,
+                                            const uint32_t* d_share_key, const uint64_t* d_share_off, size_t n_shares, size_t n, size_t bm_words,
+                                            uint32_t flags, uint8_t* d_share_status, uint8_t* d_tuple_status, uint8_t* d_agg_sigs,
+                                            uint32_t* d_signer_bits, uint32_t* d_n_signers, void* stream) {
+  return cl_collect_device(c, d_msgs, d_msg_off, d_shares, d_share_key, d_share_off, n_shares, n, bm_words, flags, nullptr, d_share_status, d_tuple_status,
+                           d_agg_sigs, d_signer_bits, d_n_signers, stream);
+}
+int bn254_batch_collect_keyed_bitmap(bn254_ctx* c, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* shares, const uint32_t* share_key,
+                                     const uint64_t* share_off, size_t n_shares, size_t n, size_t bm_words, uint32_t flags, uint8_t* share_status,
+                                     uint8_t* tuple_status, uint8_t* agg_sigs, uint32_t* signer_bits, uint32_t* n_signers) {
+  return cl_collect_host(c, msgs, msg_off, shares, share_key, share_off, n_shares, n, bm_words, flags, nullptr, share_status, tuple_status, agg_sigs,
+                         signer_bits, n_signers);
+}
+int bn254_batch_collect_keyed_bitmap_randomized_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t* d_msg_off, const uint8_t* d_shares,
+                                                       const uint32_t* d_share_key, const uint64_t* d_share_off, size_t n_shares, size_t n,
+                                                       size_t bm_words, uint32_t flags, const uint8_t* seed32, uint8_t* d_share_status,
+                                                       uint8_t* d_tuple_status, uint8_t* d_agg_sigs, uint32_t* d_signer_bits, uint32_t* d_n_signers,
+                                                       void* stream) {
+  if (!seed32) return BN254_E_BAD_ARGUMENT;
+  return cl_collect_device(c, d_msgs, d_msg_off, d_shares, d_share_key, d_share_off, n_shares, n, bm_words, flags, seed32, d_share_status, d_tuple_status,
+                           d_agg_sigs, d_signer_bits, d_n_signers, stream);
+}
+int bn254_batch_collect_keyed_bitmap_randomized(bn254_ctx* c, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* shares,
+                                                const uint32_t* share_key, const uint64_t* share_off, size_t n_shares, size_t n, size_t bm_words,
+                                                uint32_t flags, const uint8_t* seed32, uint8_t* share_status, uint8_t* tuple_status, uint8_t* agg_sigs,
+                                                uint32_t* signer_bits, uint32_t* n_signers) {
+  if (!seed32) return BN254_E_BAD_ARGUMENT;
+  return cl_collect_host(c, msgs, msg_off, shares, share_key, share_off, n_shares, n, bm_words, flags, seed32, share_status, tuple_status, agg_sigs,
+                         signer_bits, n_signers);
 }
 
 }  // extern "C"

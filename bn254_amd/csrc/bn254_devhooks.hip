@@ -243,6 +243,18 @@ static int debug_rand_last(bn254_ctx* c, int ran, const uint32_t* stats, uint64_
 }
 int bn254_debug_agg_rand_last(bn254_ctx* c, uint64_t out[6]) { return debug_rand_last(c, c ? c->aggr_last_ran : 0, c ? c->aggr_stats : nullptr, out); }
 int bn254_debug_bitmap_rand_last(bn254_ctx* c, uint64_t out[6]) { return debug_rand_last(c, c ? c->bmr_last_ran : 0, c ? c->bmr_stats : nullptr, out); }
+// bn254_batch_collect_keyed_bitmap_randomized: what the slices of the last call did, summed on the device by the call itself
+int bn254_debug_collect_rand_last(bn254_ctx* c, uint64_t out[4]) {
+  if (!c || !out) return BN254_E_BAD_ARGUMENT;
+  for (int i = 0; i < 4; ++i) out[i] = 0;
+  if (!c->clr_last_ran || !c->clr_stats) return 0;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipDeviceSynchronize());
+  uint32_t st[4];
+  HIP_TRY(hipMemcpy(st, c->clr_stats, sizeof st, hipMemcpyDeviceToHost));
+  for (int i = 0; i < 4; ++i) out[i] = st[i];
+  return 0;
+}
 // The groups of the last randomised call, read from where it left them (bn254_host.h: aggr_last): the call itself launches and copies
 // nothing for this.  dims = {groups, table pairs}; with group_cap / pair_cap too small only dims is written.
 static int debug_rand_sums(bn254_ctx* c, int ran, const AggrLast& L, uint64_t dims[2], size_t group_cap, size_t pair_cap, uint32_t* nagg, uint8_t* verdict,

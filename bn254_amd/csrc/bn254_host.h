@@ -133,6 +133,10 @@ struct bn254_ctx {
   uint8_t* collect_buf;      // per tuple: H(m), its flags and the scans of the share ranges (ClScratch), grown on demand
   size_t collect_cap;
   int collect_wave_min;      // BN254_OPT_COLLECT_WAVE_MIN_SHARES: tuples with at least this many shares are summed by a wave each
+  int collect_rand_min_shares;    // BN254_OPT_COLLECT_RAND_MIN_SHARES: the randomised collect from this many shares on
+  int collect_rand_min_per_key;   // BN254_OPT_COLLECT_RAND_MIN_PER_KEY: ... and from this many shares per registered key on
+  uint32_t* clr_stats;       // what the slices of its last call did on the device (bn254_debug_collect_rand_last); inside collect_buf
+  int clr_last_ran;          // ... and whether that call took the randomised route at all
 };
 
 struct ScopedEvents {
@@ -275,6 +279,43 @@ BN_HIDDEN int launch_verify_miller_fe(bn254_ctx* c, hipStream_t s, size_t n, int
 // decode status, then the routing table's keyed kernels; and the statuses of such a batch when no key is registered
 BN_HIDDEN int launch_keyed_miller_fe(bn254_ctx* c, hipStream_t s, size_t n, const uint32_t* d_key_idx, uint8_t* d_status);
 BN_HIDDEN int launch_keyed_no_keys(bn254_ctx* c, hipStream_t s, size_t n, uint8_t* d_status);
+// ... and its RANDOMISED form (bn254_rand.hip; the body of bn254_batch_verify_keyed_randomized behind decode and hash): the items that pass
+// rules 1-3 grouped by key in runs of 64, every group one combined check, the items of a failing group re-checked exactly through the
+// workspace's h_list / h_cnt queue.  Item i's weight is rand_scalar(seed, index_base + i).  mode: 0 = 128-bit weights, 1 = 64-bit, 2 = GLV.
+// Records profiling event 3 between the scalar ladders and the group checks.  The caller reserves, BEFORE its first kernel, what
+// keyed_rand_need names (keyed_rand_reserve does); the launcher refuses a call that did not.
+struct RandSeed { uint32_t w[8]; };
+static inline RandSeed rand_seed_from(const uint8_t* seed32) {
+  RandSeed seed;
+  for (int j = 0; j < 8; ++j)
+    seed.w[j] = ((uint32_t)seed32[4 * j] << 24) | ((uint32_t)seed32[4 * j + 1] << 16) | ((uint32_t)seed32[4 * j + 2] << 8) | seed32[4 * j + 3];
+  return seed;
+}
+static inline int rand_mode_of(uint32_t flags) { return (flags & BN254_FLAG_RAND64) ? 1 : (flags & BN254_FLAG_RAND_GLV) ? 2 : 0; }
+// n items over the registered set: the group slots start at workspace entry gbase, behind the items; at most groups_max groups (every key's
+// run is padded to whole groups of 64); ws_entries workspace entries, `words` uint32 of stage slot 5, groups_max bytes of stage slot 7
+struct KeyedRandNeed { size_t gbase, groups_max, ws_entries, words; };
+static inline KeyedRandNeed keyed_rand_need(const bn254_ctx* c, size_t n) {
+  KeyedRandNeed r;
+  const size_t K = c->n_keys;
+  r.groups_max = n / BN_WAVE + (K < n ? K : n) + 1;
+  r.gbase = (n + 255) & ~(size_t)255;
+  r.ws_entries = r.gbase + r.groups_max;
+  r.words = 2 * K + 2 + r.groups_max + r.groups_max * BN_WAVE;
+  return r;
+}
+static inline int keyed_rand_reserve(bn254_ctx* c, size_t n) {
+  const KeyedRandNeed need = keyed_rand_need(c, n);
+  int rc = ws_reserve(c, need.ws_entries);
+  if (!rc) rc = stage_reserve(c, 5, need.words * sizeof(uint32_t));
+  if (!rc) rc = stage_reserve(c, 7, need.groups_max);
+  return rc;
+}
+// where the last launch left {groups, slots in use} and the groups' verdicts (0 = passed)
+static inline uint32_t* keyed_rand_meta(const bn254_ctx* c) { return (uint32_t*)c->stage[5] + 2 * c->n_keys; }
+static inline uint8_t* keyed_rand_group_st(const bn254_ctx* c) { return c->stage[7]; }
+BN_HIDDEN int launch_keyed_rand_checks(bn254_ctx* c, hipStream_t s, size_t n, const uint32_t* d_key_idx, const RandSeed& seed, int mode,
+                                       uint64_t index_base, uint8_t* d_status);
 // one lane per item: k_miller_verify (map / count: a device-side queue of items, or null) and k_final_exp (the arguments of the kernel)
 // one lane per pairing: k_miller_var (f = miller(P1, Q) at every index below n), k_rand_tail (bn254_rand.hip: F_g * miller(S_g, -G2) at gbase + g)
 BN_HIDDEN int launch_miller_var_lane(bn254_ctx* c, hipStream_t s, size_t n);

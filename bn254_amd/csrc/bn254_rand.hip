@@ -106,7 +106,7 @@ KERNEL_SMALL void k_keyed_no_keys(size_t n, Ws ws, uint8_t* status_out) {
 //   k_rand_collect: statuses of passing groups; items of failing groups are queued for the exact kernels
 // Per-group values live at workspace index gbase + g, behind the per-item region.
 // ------------------------------------------------------------------------------------------
-struct Seed { uint32_t w[8]; };
+typedef RandSeed Seed;                       // bn254_host.h: the seed as the kernels take it
 struct G1JacSlot { G1Jac v; int32_t pad; };   // 31 words: odd stride, no LDS bank conflicts
 
 // mode: 0 = 128-bit scalar, 1 = 64-bit scalar, 2 = k1 + k2*lambda with 64-bit k1, k2 (BN254_FLAG_RAND_GLV)
@@ -286,7 +286,8 @@ KERNEL_SMALL void k_krand_scatter(size_t n, Ws ws, const uint32_t* key_idx, cons
   perm[start[key] + atomicAdd(&cursor[key], 1u)] = (uint32_t)i;
 }
 // group g = one wave: r_i H(m_i) and r_i sig_i of its items, both summed over the wave (LDS trees), as the tuple gbase + g
-KERNEL_SMALL void k_krand_scale(const uint32_t* perm, const uint32_t* meta, Ws ws, Seed seed, int mode, size_t gbase) {
+// (the weight of item i is rand_scalar(seed, index_base + i): a caller that checks a slice of its arrays passes the slice's first index)
+KERNEL_SMALL void k_krand_scale(const uint32_t* perm, const uint32_t* meta, Ws ws, Seed seed, int mode, size_t gbase, uint64_t index_base) {
   const unsigned t = threadIdx.x;
   const size_t g = blockIdx.x;
   if (g >= meta[0]) return;                              // the whole block together
@@ -297,7 +298,7 @@ KERNEL_SMALL void k_krand_scale(const uint32_t* perm, const uint32_t* meta, Ws w
   ws_load_g1(ws, PL_P1X, BY_P1_INF, ii, sig);
   ws_load_g1(ws, PL_P2X, BY_P2_INF, ii, h);
   uint32_t k[4];
-  rand_scalar(k, seed.w, (uint64_t)ii, mode == 1);
+  rand_scalar(k, seed.w, index_base + (uint64_t)ii, mode == 1);
   // both products are accumulated IN their LDS slots (jac_mul_window works in place through the reference): the 4 doublings + 1
   // addition of every window stay out of the private segment
   __shared__ G1JacSlot lds_a[BN_WAVE], lds_s[BN_WAVE];
@@ -367,6 +368,36 @@ int launch_keyed_miller_fe(bn254_ctx* c, hipStream_t s, size_t n, const uint32_t
 int launch_keyed_no_keys(bn254_ctx* c, hipStream_t s, size_t n, uint8_t* d_status) {
   k_keyed_no_keys<<<grid_for(n), BN_WAVE, 0, s>>>(n, c->ws, d_status);
   HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// the grouped checks of a keyed batch whose P1 / P2 planes, decode and hash statuses are filled (bn254_host.h): items grouped by key in runs of
+// 64, two table-driven Miller loops and one final exponentiation per group, the items of a failing group re-checked exactly.  The caller has
+// reserved what keyed_rand_need(c, n) names.  No profiling marks of its own except event 3 between the scalar ladders and the group checks.
+int launch_keyed_rand_checks(bn254_ctx* c, hipStream_t s, size_t n, const uint32_t* d_key_idx, const RandSeed& seed, int mode, uint64_t index_base,
+                             uint8_t* d_status) {
+  const KeyedRandNeed need = keyed_rand_need(c, n);
+  if (need.ws_entries > c->ws.stride || need.words * sizeof(uint32_t) > c->stage_cap[5] || need.groups_max > c->stage_cap[7]) return BN254_E_BAD_ARGUMENT;
+  const size_t K = c->n_keys, groups_max = need.groups_max, slots_max = groups_max * BN_WAVE, gbase = need.gbase;
+  // scratch of this mode: [cnt K | start K | meta 2 | gkey groups_max | perm slots_max] words, group statuses
+  uint32_t* cnt = (uint32_t*)c->stage[5];
+  uint32_t *start = cnt + K, *meta = keyed_rand_meta(c), *gkey = meta + 2, *perm = gkey + groups_max;
+  uint8_t* d_group_st = keyed_rand_group_st(c);
+  const KeyTable kt = {c->key_lines, c->key_st, c->key_inf, (uint32_t)c->n_keys};
+  int rc;
+  HIP_TRY(hipMemsetAsync(cnt, 0, K * sizeof(uint32_t), s));
+  HIP_TRY(hipMemsetAsync(perm, 0xFF, slots_max * sizeof(uint32_t), s));
+  k_krand_prepare<<<grid_for(n), BN_WAVE, 0, s>>>(n, c->ws, d_key_idx, kt, cnt, d_status);
+  k_krand_scan<<<1, BN_WAVE, 0, s>>>((uint32_t)K, cnt, start, gkey, meta);
+  k_krand_scatter<<<grid_for(n), BN_WAVE, 0, s>>>(n, c->ws, d_key_idx, start, cnt, perm);
+  k_krand_scale<<<(unsigned)groups_max, BN_WAVE, 0, s>>>(perm, meta, c->ws, seed, mode, gbase, index_base);
+  PROF_MARK(3);                                        // ms[2] = grouping + scalar multiplications, ms[3] = group checks + exact re-checks
+  if ((rc = bn254_pair_miller_verify_keyed(groups_max, c->ws, gkey, kt, s, gbase, nullptr, meta))) return rc;
+  if ((rc = bn254_pair_final_exp(groups_max, c->ws, 0, d_group_st, nullptr, meta, s, gbase))) return rc;
+  k_krand_collect<<<grid_for(slots_max), BN_WAVE, 0, s>>>(slots_max, perm, meta, d_group_st, d_status, c->ws);
+  // exact re-check of the items of failed groups (none queued: both kernels leave at once)
+  if ((rc = bn254_pair_miller_verify_keyed(n, c->ws, d_key_idx, kt, s, 0, c->ws.h_list, c->ws.h_cnt))) return rc;
+  if ((rc = bn254_pair_final_exp(n, c->ws, 1, d_status, c->ws.h_list, c->ws.h_cnt, s))) return rc;
   return 0;
 }
 
@@ -461,42 +492,17 @@ int bn254_batch_verify_keyed_randomized_device(bn254_ctx* c, const uint8_t* d_ms
   if (c->n_keys == 0 || !c->key_lines || n < (size_t)c->rand_min_batch)      // nothing to group by / too small to pay off: the exact keyed path
     return bn254_batch_verify_keyed_device(c, d_msgs, d_off, d_sigs, d_key_idx, n, dflags, d_status, stream);
   HIP_TRY(hipSetDevice(c->device));
-  const size_t K = c->n_keys;
-  const size_t groups_max = n / BN_WAVE + (K < n ? K : n) + 1, slots_max = groups_max * BN_WAVE;
-  const size_t gbase = (n + 255) & ~(size_t)255;
-  int rc = ws_reserve(c, gbase + groups_max);
+  int rc = keyed_rand_reserve(c, n);
   if (rc) return rc;
-  // scratch of this mode (device memory, grown on demand): [cnt K | start K | meta 2 | gkey groups_max | perm slots_max] words, group statuses
-  const size_t words = 2 * K + 2 + groups_max + slots_max;
-  if ((rc = stage_reserve(c, 5, words * sizeof(uint32_t)))) return rc;
-  if ((rc = stage_reserve(c, 7, groups_max))) return rc;
-  uint32_t* cnt = (uint32_t*)c->stage[5];
-  uint32_t *start = cnt + K, *meta = start + K, *gkey = meta + 2, *perm = gkey + groups_max;
-  uint8_t* d_group_st = c->stage[7];
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   CallDone call_done(c, s);
-  Seed seed;
-  for (int j = 0; j < 8; ++j)
-    seed.w[j] = ((uint32_t)seed32[4 * j] << 24) | ((uint32_t)seed32[4 * j + 1] << 16) | ((uint32_t)seed32[4 * j + 2] << 8) | seed32[4 * j + 3];
-  KeyTable kt = {c->key_lines, c->key_st, c->key_inf, (uint32_t)c->n_keys};
+  const RandSeed seed = rand_seed_from(seed32);
   PROF_MARK(0);
   { int rc_ = launch_decode_g1(c, s, d_sigs, n, dflags, PL_P1X, BY_P1_INF, 0); if (rc_) return rc_; }
   PROF_MARK(1);
   if ((rc = launch_hash_rounds(c, s, d_msgs, d_off, n, PL_P2X, BY_P2_INF, nullptr))) return rc;
   PROF_MARK(2);
-  HIP_TRY(hipMemsetAsync(cnt, 0, K * sizeof(uint32_t), s));
-  HIP_TRY(hipMemsetAsync(perm, 0xFF, slots_max * sizeof(uint32_t), s));
-  k_krand_prepare<<<grid_for(n), BN_WAVE, 0, s>>>(n, c->ws, d_key_idx, kt, cnt, d_status);
-  k_krand_scan<<<1, BN_WAVE, 0, s>>>((uint32_t)K, cnt, start, gkey, meta);
-  k_krand_scatter<<<grid_for(n), BN_WAVE, 0, s>>>(n, c->ws, d_key_idx, start, cnt, perm);
-  k_krand_scale<<<(unsigned)groups_max, BN_WAVE, 0, s>>>(perm, meta, c->ws, seed, (flags & BN254_FLAG_RAND64) ? 1 : (flags & BN254_FLAG_RAND_GLV) ? 2 : 0, gbase);
-  PROF_MARK(3);                                        // ms[2] = grouping + scalar multiplications, ms[3] = group checks + exact re-checks
-  if ((rc = bn254_pair_miller_verify_keyed(groups_max, c->ws, gkey, kt, s, gbase, nullptr, meta))) return rc;
-  if ((rc = bn254_pair_final_exp(groups_max, c->ws, 0, d_group_st, nullptr, meta, s, gbase))) return rc;
-  k_krand_collect<<<grid_for(slots_max), BN_WAVE, 0, s>>>(slots_max, perm, meta, d_group_st, d_status, c->ws);
-  // exact re-check of the items of failed groups (none queued: both kernels leave at once)
-  if ((rc = bn254_pair_miller_verify_keyed(n, c->ws, d_key_idx, kt, s, 0, c->ws.h_list, c->ws.h_cnt))) return rc;
-  if ((rc = bn254_pair_final_exp(n, c->ws, 1, d_status, c->ws.h_list, c->ws.h_cnt, s))) return rc;
+  if ((rc = launch_keyed_rand_checks(c, s, n, d_key_idx, seed, rand_mode_of(flags), 0, d_status))) return rc;
   PROF_MARK(4);
   prof_done(c, EV_DECODE_FIRST);
   HIP_TRY(hipGetLastError());

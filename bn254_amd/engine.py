@@ -48,6 +48,10 @@ OPT_BITMAP_RAND_MIN_TUPLES = 33    # randomised signer bitmaps: the exact bitmap
 OPT_BITMAP_RAND_GROUP_TUPLES = 34  # ... tuples per group of its combined checks (developer option)
 OPT_BITMAP_RAND_MAX_KEYS = 35      # ... the exact bitmap call when more keys than this are registered
 OPT_KEY_CACHE = 36                 # key dedup: the line tables stay between calls, a call builds only unseen keys (default 1; 0 = build all, drops the cache)
+OPT_COLLECT_RAND_MIN_SHARES = 38   # collect_keyed_bitmap_randomized: the exact collect below this many shares (default 65664)
+OPT_COLLECT_RAND_MIN_PER_KEY = 39  # ... and below this many shares per registered key, n_shares // n_keys (default 42); DESIGN.md §10f
+COLLECT_RAND_MIN_SHARES_DEFAULT = 65664  # the library's defaults of the two (bn254_amd/csrc/bn254_ws.h; measured: DESIGN.md §10f)
+COLLECT_RAND_MIN_PER_KEY_DEFAULT = 42
 OPT_COLLECT_WAVE_MIN_SHARES = 37   # collect_keyed_bitmap: tuples with at least this many shares are summed by a wave each (default 16; swept at three shapes only)
 
 
@@ -190,6 +194,13 @@ class Engine:
         o = (ctypes.c_uint64 * 6)()
         _check("bn254_debug_bitmap_rand_last", self._lib.bn254_debug_bitmap_rand_last(self._h, o))
         return dict(zip(("ran", "groups", "table_pairs", "failed_groups", "rechecked", "single_groups"), (int(x) for x in o)))
+
+    def debug_collect_rand_last(self):
+        """what the last batch_collect_keyed_bitmap_randomized[_device] did, summed over its slices: dict(slices, groups, failed_groups,
+        rechecked); all 0 when it took the exact route"""
+        o = (ctypes.c_uint64 * 4)()
+        _check("bn254_debug_collect_rand_last", self._lib.bn254_debug_collect_rand_last(self._h, o))
+        return dict(zip(("slices", "groups", "failed_groups", "rechecked"), (int(x) for x in o)))
 
     def debug_bitmap_rand_sums(self):
         """the G1 side of that call's group checks as it left them (include/bn254_hip.h: bn254_debug_bitmap_rand_sums), in the format of
@@ -518,10 +529,11 @@ class Engine:
         _check("bn254_batch_verify_keyed_bitmap_device",
                self._lib.bn254_batch_verify_keyed_bitmap_device(self._h, d_msgs, d_off, d_sigs, d_signer_bits, bm_words, n, flags, d_status, stream))
 
-    def batch_collect_keyed_bitmap(self, messages, shares, share_keys, sizes, bm_words, flags=0, want_counts=False):
+    def batch_collect_keyed_bitmap(self, messages, shares, share_keys, sizes, bm_words, flags=0, want_counts=False, seed32=None):
         """build signer-bitmap aggregates from individual signatures (include/bn254_hip.h: bn254_batch_collect_keyed_bitmap): tuple i is
         messages[i] with the next sizes[i] shares (64 B each, share s said to be by registered key share_keys[s]).  Returns (share status
-        bytes, tuple status bytes, the n aggregates, the n * bm_words bitmap words) — and the signer counts with want_counts."""
+        bytes, tuple status bytes, the n aggregates, the n * bm_words bitmap words) — and the signer counts with want_counts.
+        seed32: see batch_collect_keyed_bitmap_randomized."""
         n, n_shares = len(messages), len(share_keys)
         assert len(sizes) == n and all(k >= 0 for k in sizes) and sum(sizes) == n_shares and len(shares) == n_shares * G1_BYTES
         msgs, off = pack_messages(messages)
@@ -535,9 +547,12 @@ class Engine:
         agg = ctypes.create_string_buffer(max(n, 1) * G1_BYTES)
         bits = (ctypes.c_uint32 * max(n * bm_words, 1))()
         counts = (ctypes.c_uint32 * max(n, 1))()
-        _check("bn254_batch_collect_keyed_bitmap",
-               self._lib.bn254_batch_collect_keyed_bitmap(self._h, msgs, off, bytes(shares), keys, share_off, n_shares, n, bm_words, flags,
-                                                          share_st, tuple_st, agg, bits, counts if want_counts else None))
+        head = (self._h, msgs, off, bytes(shares), keys, share_off, n_shares, n, bm_words, flags)
+        tail = (share_st, tuple_st, agg, bits, counts if want_counts else None)
+        if seed32 is not None:
+            _check("bn254_batch_collect_keyed_bitmap_randomized", self._lib.bn254_batch_collect_keyed_bitmap_randomized(*head, bytes(seed32), *tail))
+        else:
+            _check("bn254_batch_collect_keyed_bitmap", self._lib.bn254_batch_collect_keyed_bitmap(*head, *tail))
         out = (share_st.raw[:n_shares], tuple_st.raw[:n], agg.raw[:n * G1_BYTES], list(bits)[:n * bm_words])
         return out + (list(counts)[:n],) if want_counts else out
 
@@ -546,6 +561,21 @@ class Engine:
         _check("bn254_batch_collect_keyed_bitmap_device",
                self._lib.bn254_batch_collect_keyed_bitmap_device(self._h, d_msgs, d_msg_off, d_shares, d_share_key, d_share_off, n_shares, n, bm_words,
                                                                  flags, d_share_status, d_tuple_status, d_agg_sigs, d_signer_bits, d_n_signers, stream))
+
+    def batch_collect_keyed_bitmap_randomized(self, messages, shares, share_keys, sizes, bm_words, seed32, flags=0, want_counts=False):
+        """batch_collect_keyed_bitmap with the pairing checks of the shares combined, 64 shares of one key at a time, under random weights
+        from seed32 (include/bn254_hip.h: bn254_batch_collect_keyed_bitmap_randomized; flags: FLAG_RAND64 / FLAG_RAND_GLV and the decode
+        flags).  The same outputs, byte for byte."""
+        assert len(seed32) == 32
+        return Engine.batch_collect_keyed_bitmap(self, messages, shares, share_keys, sizes, bm_words, flags, want_counts, seed32=seed32)
+
+    def batch_collect_keyed_bitmap_randomized_device(self, d_msgs, d_msg_off, d_shares, d_share_key, d_share_off, n_shares, n, bm_words, seed32,
+                                                     d_share_status, d_tuple_status, d_agg_sigs, d_signer_bits, d_n_signers=None, flags=0, stream=None):
+        assert len(seed32) == 32
+        _check("bn254_batch_collect_keyed_bitmap_randomized_device",
+               self._lib.bn254_batch_collect_keyed_bitmap_randomized_device(self._h, d_msgs, d_msg_off, d_shares, d_share_key, d_share_off, n_shares, n,
+                                                                            bm_words, flags, bytes(seed32), d_share_status, d_tuple_status, d_agg_sigs,
+                                                                            d_signer_bits, d_n_signers, stream))
 
     def batch_verify_keyed_bitmap_randomized(self, messages, sigs, bitmaps, bm_words, seed32, flags=0):
         """batch_verify_keyed_bitmap with the pairing checks of whole groups of tuples combined under random weights from seed32

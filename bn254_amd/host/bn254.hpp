@@ -298,6 +298,18 @@ struct ECDSA {
   struct ShareItem { std::vector<uint8_t> message; std::vector<Signature> signatures; std::vector<uint32_t> key_indices; };
   struct KeyedAggregateResult { uint8_t status; Signature signature; std::vector<uint32_t> signer_indices; std::vector<uint8_t> statuses; };
   static std::vector<KeyedAggregateResult> batch_aggregate_keyed_signers(const std::vector<ShareItem>& items, size_t n_keys, Engine& e = Engine::default_engine()) {
+    return aggregate_keyed_signers_impl(items, n_keys, nullptr, 0, e);
+  }
+  // the same through the combined checks of 64 signatures of one key at a time, across the items of the call (include/bn254_hip.h:
+  // bn254_batch_collect_keyed_bitmap_randomized): the same results; a non-zero status is exact, a zero is wrong with probability <= 2^-128 per
+  // group (2^-64 with rand64) for a fresh SECRET seed
+  static std::vector<KeyedAggregateResult> batch_aggregate_keyed_signers_randomized(const std::vector<ShareItem>& items, size_t n_keys,
+                                                                                    const std::array<uint8_t, 32>& seed, bool rand64 = false,
+                                                                                    Engine& e = Engine::default_engine()) {
+    return aggregate_keyed_signers_impl(items, n_keys, seed.data(), rand64 ? BN254_FLAG_RAND64 : 0, e);
+  }
+  static std::vector<KeyedAggregateResult> aggregate_keyed_signers_impl(const std::vector<ShareItem>& items, size_t n_keys, const uint8_t* seed32, uint32_t flags,
+                                                                        Engine& e) {
     const size_t n = items.size(), bm_words = (n_keys + 31) / 32 ? (n_keys + 31) / 32 : 1;
     std::vector<uint64_t> off(n + 1, 0), share_off(n + 1, 0);
     std::vector<uint8_t> msgs, shares;
@@ -316,9 +328,14 @@ struct ECDSA {
     std::vector<uint32_t> bits(n * bm_words + 1, 0);
     shares.resize(shares.size() + 1);
     keys.resize(keys.size() + 1);
-    check_rc("bn254_batch_collect_keyed_bitmap",
-             bn254_batch_collect_keyed_bitmap(e.raw(), msgs.data(), off.data(), shares.data(), keys.data(), share_off.data(), share_off[n], n, bm_words, 0,
-                                              share_st.data(), tuple_st.data(), agg.data(), bits.data(), nullptr));
+    if (seed32)
+      check_rc("bn254_batch_collect_keyed_bitmap_randomized",
+               bn254_batch_collect_keyed_bitmap_randomized(e.raw(), msgs.data(), off.data(), shares.data(), keys.data(), share_off.data(), share_off[n], n,
+                                                           bm_words, flags, seed32, share_st.data(), tuple_st.data(), agg.data(), bits.data(), nullptr));
+    else
+      check_rc("bn254_batch_collect_keyed_bitmap",
+               bn254_batch_collect_keyed_bitmap(e.raw(), msgs.data(), off.data(), shares.data(), keys.data(), share_off.data(), share_off[n], n, bm_words, 0,
+                                                share_st.data(), tuple_st.data(), agg.data(), bits.data(), nullptr));
     std::vector<KeyedAggregateResult> out(n);
     for (size_t i = 0; i < n; ++i) {
       out[i].status = tuple_st[i];
@@ -332,6 +349,13 @@ struct ECDSA {
   static KeyedAggregateResult aggregate_keyed_signers(const std::vector<uint8_t>& message, const std::vector<Signature>& signatures,
                                                       const std::vector<uint32_t>& key_indices, size_t n_keys, Engine& e = Engine::default_engine()) {
     KeyedAggregateResult r = batch_aggregate_keyed_signers({ShareItem{message, signatures, key_indices}}, n_keys, e)[0];
+    check_status(r.status);
+    return r;
+  }
+  static KeyedAggregateResult aggregate_keyed_signers_randomized(const std::vector<uint8_t>& message, const std::vector<Signature>& signatures,
+                                                                 const std::vector<uint32_t>& key_indices, size_t n_keys, const std::array<uint8_t, 32>& seed,
+                                                                 bool rand64 = false, Engine& e = Engine::default_engine()) {
+    KeyedAggregateResult r = batch_aggregate_keyed_signers_randomized({ShareItem{message, signatures, key_indices}}, n_keys, seed, rand64, e)[0];
     check_status(r.status);
     return r;
   }

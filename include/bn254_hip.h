@@ -448,7 +448,9 @@ int bn254_batch_verify_keyed_bitmap_randomized_device(bn254_ctx *ctx, const uint
  * less than the spread and the sum cost.  What the call spares a caller of bn254_batch_verify_keyed_device is what followed that verify: the
  * copy of the statuses to the host, the filter there, and bn254_batch_g1_sum, whose host-pointer form stages every share again and walks each
  * segment in one lane.  Whole-call intervals of both routes, as far as they were measured: DESIGN.md section 10e.
- * Out of scope: a randomised form (the shares of a tuple share H(m), not the key: a different grouping), the multi-GPU layer, compressed shares. */
+ * Which call when: this one for calls of few shares, or of few shares per registered key; bn254_batch_collect_keyed_bitmap_randomized below where
+ * the keys have many shares each across the tuples of the call.
+ * Out of scope: the multi-GPU layer, compressed shares. */
 int bn254_batch_collect_keyed_bitmap(bn254_ctx *ctx, const uint8_t *msgs, const uint64_t *msg_off /* n+1 */,
                                      const uint8_t *shares /* n_shares*64 */, const uint32_t *share_key /* n_shares */,
                                      const uint64_t *share_off /* n+1 */, size_t n_shares, size_t n, size_t bm_words, uint32_t flags,
@@ -458,6 +460,52 @@ int bn254_batch_collect_keyed_bitmap_device(bn254_ctx *ctx, const uint8_t *d_msg
                                             const uint32_t *d_share_key, const uint64_t *d_share_off, size_t n_shares, size_t n, size_t bm_words,
                                             uint32_t flags, uint8_t *d_share_status, uint8_t *d_tuple_status, uint8_t *d_agg_sigs,
                                             uint32_t *d_signer_bits, uint32_t *d_n_signers, void *stream);
+
+/* bn254_batch_collect_keyed_bitmap_randomized[_device]: the same inputs and, byte for byte, the same five outputs as
+ * bn254_batch_collect_keyed_bitmap[_device] with the same flags — share_status, tuple_status, agg_sigs, signer_bits and n_signers — with the
+ * pairing checks of the shares combined.  Rules 1-3 of share_status (decode, key index and registration status, the tuple's hash status) are
+ * exact; a non-zero share_status is always the exact one; a zero is wrong with probability <= 2^-128 per group (2^-64 with BN254_FLAG_RAND64)
+ * for a fresh secret seed32.  Defining identities 1 and 2 carry over.  The argument checks, BN254_E_MISALIGNED, the range rule, the fill of
+ * share_status with 2 and the _device conventions are the exact call's: no host synchronisation, every buffer reserved before the first kernel.
+ *   r_s = rand_scalar(seed32, s) as in the other randomised calls (the first 16 — 8 with BN254_FLAG_RAND64 — bytes of SHA-256(seed32 ||
+ *   le64(s)), little-endian, 0 -> 1) with s = the share's index in the caller's arrays, also under slicing.  BN254_FLAG_RAND64 and
+ *   BN254_FLAG_RAND_GLV mean what they mean in bn254_batch_verify_keyed_randomized; the other flags apply to the shares' decode.
+ *   Groups: the shares of a tuple share H(m), not the key — but across the TUPLES of a call every registered key has many shares.  Within a
+ *   slice of the shares, those that pass rules 1-3 are grouped by key in runs of 64, exactly as bn254_batch_verify_keyed_randomized groups its
+ *   items, and a group passes iff
+ *       e(sum_s r_s H(m_t(s)), pk) * e(sum_s r_s share_s, -G2) == 1      (t(s) = the tuple of share s)
+ *   — two table-driven Miller loops and one final exponentiation per 64 shares, and per share two scalar ladders.  The shares of a passing
+ *   group get 0; every share of a failing group is verified exactly on the device.  Select-and-sum runs once behind the last slice, unchanged.
+ *   A slice is as long as BN254_OPT_MAX_CHUNK says, or as its slots TOGETHER WITH its group entries (len / 64 + min(n_keys, len) + 1 of them,
+ *   behind the slots) fit the workspace.
+ *   The exact call, same bytes, when no keys are registered, n_shares < BN254_OPT_COLLECT_RAND_MIN_SHARES, n_shares / n_keys <
+ *   BN254_OPT_COLLECT_RAND_MIN_PER_KEY (groups are per key: a call whose keys have one or two shares each buys padding, not speed), or no
+ *   slice with its groups fits.  Both thresholds are the most the host can know without looking at share_key.
+ * The seed must be secret and fresh: who knows r can forge a pair of shares of one key whose errors cancel in the group's sum
+ * (share_1 + r_2 D, share_2 - r_1 D pass together), and both would then be summed into aggregates that do not verify.
+ * seed32 is host memory in both forms.  Profiling: bn254_ctx_last_kernel_ms keeps the exact call's four intervals; ms[2] and ms[3] mean
+ * "grouping + scalar ladders" and "group checks + exact re-checks" here.
+ * Which call when (measured on an MI355X, every share valid, tuples of 171 shares, whole-call medians on a caller's stream; DESIGN.md section
+ * 10f): over 256 keys this call from 65 664 shares on — 9.3 ms against the exact call's 13.4 there, 13.0 against 24.0 at 175 104, 18.3 against
+ * 42.9 at 350 208 (2.3 x; 13.3 ms, 3.2 x, with BN254_FLAG_RAND64) — and the exact call below: at 43 776 shares it takes 8.7 ms against 8.2
+ * (64-bit weights: 7.7), at 4 104 shares 7.4 against 2.6.  The group checks are ONE pass of the lane-pair keyed kernels over a few hundred to
+ * a few thousand groups, 4.7 ms whatever their number, which is what a small call cannot win back.  Over 4 096 keys: 175 104 shares (42 per
+ * key) 15.5 ms against 24.2, but 43 776 shares (10 per key) 13.5 against 8.3 — every key's run is padded to whole groups of 64, and the
+ * ladders are paid per slot.  The defaults follow that: below BN254_OPT_COLLECT_RAND_MIN_SHARES (65 664) shares, or below
+ * BN254_OPT_COLLECT_RAND_MIN_PER_KEY (42) shares per registered key, this call IS the exact call.  Not measured: between 45 056 and 65 664
+ * shares, and between 10 and 42 shares per key.  Where many shares are expected to be wrong, the exact call: 1 % wrong shares spread over the
+ * tuples fail 44 % of the groups of 256 x 171 and the call takes 13.4 ms against 8.0. */
+int bn254_batch_collect_keyed_bitmap_randomized(bn254_ctx *ctx, const uint8_t *msgs, const uint64_t *msg_off /* n+1 */,
+                                                const uint8_t *shares /* n_shares*64 */, const uint32_t *share_key /* n_shares */,
+                                                const uint64_t *share_off /* n+1 */, size_t n_shares, size_t n, size_t bm_words, uint32_t flags,
+                                                const uint8_t *seed32, uint8_t *share_status /* n_shares */, uint8_t *tuple_status /* n */,
+                                                uint8_t *agg_sigs /* n*64 */, uint32_t *signer_bits /* n*bm_words */,
+                                                uint32_t *n_signers /* n, or NULL */);
+int bn254_batch_collect_keyed_bitmap_randomized_device(bn254_ctx *ctx, const uint8_t *d_msgs, const uint64_t *d_msg_off, const uint8_t *d_shares,
+                                                       const uint32_t *d_share_key, const uint64_t *d_share_off, size_t n_shares, size_t n,
+                                                       size_t bm_words, uint32_t flags, const uint8_t *seed32 /* host memory */,
+                                                       uint8_t *d_share_status, uint8_t *d_tuple_status, uint8_t *d_agg_sigs,
+                                                       uint32_t *d_signer_bits, uint32_t *d_n_signers, void *stream);
 
 /* compressed wire formats (src/utils.rs:84-104, :130-158): out = uncompressed point, status as
  * bn::G1::from_compressed / bn::G2::from_compressed report through src/types.rs:91-93, :233-237, checked in the order
@@ -542,6 +590,13 @@ int bn254_ctx_set_profiling(bn254_ctx *ctx, int enabled);
                                                one wave each (64 partial sums and a tree), shorter ones by one lane each; >= 1.  Default 16 — a
                                                figure NOBODY HAS MEASURED beyond three shapes (tools/collect_throughput.py --wave-min: tuples of 11 shares sum in 0.18 ms by lanes
                                                against 0.62 by waves, tuples of 171 in 0.24 by waves against 1.86 by lanes; nothing in between).  Same bytes either way */
+#define BN254_OPT_COLLECT_RAND_MIN_SHARES 38 /* bn254_batch_collect_keyed_bitmap_randomized: calls with fewer shares take the exact collect (same
+                                               bytes).  Default 65664, the smallest measured size from which the call wins over 256 keys
+                                               (at 45 056 shares it ties or loses; nothing measured in between); 0 = no lower bound */
+#define BN254_OPT_COLLECT_RAND_MIN_PER_KEY 39 /* ... and calls with fewer than this many shares per registered key (n_shares / n_keys, rounded
+                                                down): groups are per key, so few shares per key mean padded groups.  Default 42, the smallest measured
+                                                ratio at which the call wins (175 104 shares over 4 096 keys; at 10 per key it loses;
+                                                nothing measured in between); 0 = no lower bound */
 int bn254_ctx_set_option(bn254_ctx *ctx, int option, int value);
 /* per-kernel times of the last verify-shaped call with profiling on (HIP events on the call's stream):
  * ms[0] decode, ms[1] hash-to-G1, ms[2] Miller loop, ms[3] final exponentiation.  The host-pointer bn254_batch_verify runs
@@ -551,7 +606,9 @@ int bn254_ctx_set_option(bn254_ctx *ctx, int option, int value);
  * (decoding, hashing the messages, the subset-sum table), ms[1] = the aggregation kernel; verify_keyed_bitmap ms[0] = sigma's decode + hash-to-G1,
  * ms[1] = the aggregate keys (the summation kernel; the lazy table build runs ahead of ms[0]), ms[2] Miller loop, ms[3] final exponentiation;
  * collect_keyed_bitmap ms[0] = decode + hash-to-G1 (once per tuple) + spread, ms[1] = select-and-sum (it runs last), ms[2] Miller loop,
- * ms[3] final exponentiation (the last slice's; the hash counts in ms[0] only when the call ran in one piece). */
+ * ms[3] final exponentiation (the last slice's; the hash counts in ms[0] only when the call ran in one piece);
+ * collect_keyed_bitmap_randomized on its randomised route the same four with ms[2] = grouping by key + scalar ladders, ms[3] = group checks +
+ * exact re-checks of failed groups. */
 int bn254_ctx_last_kernel_ms(bn254_ctx *ctx, float ms[4]);
 /* with BN254_OPT_CLOCK_PROBE on: achieved shader clock in MHz of the lane-pair Miller kernels [0], final exponentiations [1] and probe
  * kernels (bn254_probe_issue_rate, bn254_probe_leaf_floor) [2] launched on this context SINCE THE PREVIOUS CALL of this function (or
@@ -730,6 +787,10 @@ int bn254_debug_agg_rand_last(bn254_ctx *ctx, uint64_t out[6]);
  * and its point sum r_i H(m_j) over the group's entries of that key (64 bytes).  Otherwise only dims is written.  Synchronises the device. */
 int bn254_debug_agg_rand_sums(bn254_ctx *ctx, uint64_t dims[2], size_t group_cap, size_t pair_cap, uint32_t *nagg, uint8_t *verdict,
                               uint8_t *s_g /* groups*64 */, uint64_t *first_pair /* groups+1 */, uint32_t *pair_key, uint8_t *pair_point /* pairs*64 */);
+/* what the last bn254_batch_collect_keyed_bitmap_randomized[_device] did, summed over its slices (the kernels count): out = {slices that took
+ * the randomised route, groups checked, groups that failed, shares re-checked exactly}; all 0 when the call took the exact route.
+ * Synchronises the device. */
+int bn254_debug_collect_rand_last(bn254_ctx *ctx, uint64_t out[4]);
 /* what the last bn254_batch_verify_keyed_bitmap_randomized[_device] did (its last slice): out = {1 if it took the randomised route, groups that
  * reached the check, table pairs of all group checks (S_g's included), failed groups, tuples re-checked, groups of one tuple (r = 1)}; all 0
  * when it took the exact route.  Synchronises the device. */

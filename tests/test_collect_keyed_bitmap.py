@@ -6,7 +6,8 @@
   (tests/hostsim/hostsim_collect.cpp, plain and under -DBN_TRACK_BOUNDS), over GIVEN status arrays: both layouts (the wave layout as 64
   partial sums plus the tree) against tests/collect_model.py and the oracle's g1_add, tuples of 0 .. 130 shares, duplicates of a valid share,
   a valid and an invalid share of one key in both orders, a key and its negation, a registered identity key, all shares refused, statuses
-  2, 4, 6, 9 and 1 mixed in."""
+  2, 4, 6, 9 and 1 mixed in; and a key set that repeats keys (tests/collect_repeat_cases.py): equal and opposite partial sums at every level
+  of the tree and in a lane's own stride."""
 import ctypes
 import os
 import random
@@ -230,10 +231,67 @@ def test_select_and_sum_exceptional_cases(libs, c, build):
     assert agg3 == agg and all(bits3[3 * i + 1] == 0 and bits3[3 * i + 2] == 0 for i in range(len(tuples)))
 
 
+@pytest.fixture(scope="module")
+def repeated(c):
+    """tests/collect_repeat_cases.py as multiples of one base: sigma = a base, -sigma = (r - a) base, B_j's share b_j base, a wrong share
+    sigma + base.  -> (cases, (shares, keys, sizes, statuses), sigma, the B shares, the expectation by the model and the oracle's g1_add)"""
+    from tests import collect_repeat_cases as rc
+    rnd = random.Random(17)
+    st_h, base, _ = c.hash_to_g1(b"collect/repeated")
+    assert st_h == 0
+    a = rnd.randrange(1, R)
+    sigma, neg = c.g1_mul(base, a.to_bytes(32, "big")), c.g1_mul(base, (R - a).to_bytes(32, "big"))
+    assert c.g1_add(sigma, neg) == bytes(64) and sigma[:32] == neg[:32]
+    b = [c.g1_mul(base, rnd.randrange(1, R).to_bytes(32, "big")) for _ in range(rc.N_B)]
+    wrong = c.g1_add(sigma, base)
+    cases = rc.shapes()
+    flat = rc.plant(cases, lambda i, kind, key: {"A": sigma, "N": neg, "W": wrong}.get(kind) or b[key - rc.K_B])
+    shares, keys, sizes, status = flat
+    rows, counts, chosen = collect_model.select(keys, status, sizes, [0] * len(sizes), rc.BM)
+    want = ([w for r in rows for w in r], counts, b"".join(collect_model.aggregates(c, shares, chosen)))
+    return cases, flat, sigma, b, want
+
+
+@pytest.mark.parametrize("build", BUILDS)
+def test_select_and_sum_repeated_keys(libs, c, repeated, build):
+    """a key set that lists one key 128 times and its negation 64 times (tests/collect_repeat_cases.py), statuses given: a doubling and a
+    cancellation at every level of the tree with every other slot the identity, all 64 slots doubling at all six levels (the last one
+    32 sigma + 32 sigma), a cancellation at the first level only and at the last only, one level whose slots double, cancel, add ordinarily
+    and add identities, the same one position on, and a lane's own stride adding sigma to sigma and to -sigma.  Both layouts against the
+    model and the oracle's g1_add; every aggregate again as (the net multiple) sigma + the B shares, through g1_mul.  Under
+    -DBN_TRACK_BOUNDS the interval tracker aborts the process on a violated bound."""
+    from tests import collect_repeat_cases as rc
+    cases, (shares, keys, sizes, status), sigma, b, want = repeated
+    h = Harness(libs[build])
+    bits, counts, agg = want
+    for layout in (0, 1):
+        got = h.sum(shares, keys, sizes, status, [0] * len(sizes), rc.BM, layout)
+        assert got[0] == bits and got[1] == counts, layout
+        assert got[2] == agg, "layout %d: %s" % (layout, " ".join(cases[i][0] for i in range(len(cases)) if got[2][64 * i:64 * i + 64] != agg[64 * i:64 * i + 64]))
+    by_name = {}
+    for i, (name, sh) in enumerate(cases):
+        m, bs, count = rc.net(sh)
+        point = c.g1_mul(sigma, (m % R).to_bytes(32, "big")) if m % R else bytes(64)
+        for j in bs:
+            point = c.g1_add(point, b[j])
+        assert agg[64 * i:64 * i + 64] == point and counts[i] == count, name
+        assert sum(bin(w).count("1") for w in bits[rc.BM * i:rc.BM * i + rc.BM]) == count, name
+        by_name[name] = (m, bs, count)
+    assert by_name["double_every_level"] == (64, [], 64) and by_name["own_stride_128"] == (128, [], 128)
+    assert by_name["own_stride_sss"] == (128, [0, 1], 130) and by_name["own_stride_sns"] == (126, [], 130)
+    assert all(by_name["double_at_%d" % s] == (2, [], 2) and by_name["cancel_at_%d" % s] == (0, [], 2) for s in rc.STRIDES)
+    assert by_name["cancel_first_level"] == by_name["cancel_last_level"] == (0, [], 64) and by_name["mixed_vote"] == (16, list(range(16)), 48)
+    assert by_name["cancel_at_8+1"] == (0, [], 2) and by_name["double_every_level+2"] == (64, [62, 63], 66)
+
+
 def range_rule(off, n_shares):
-    """the range rule restated: accepted iff lo <= hi <= n_shares and no earlier offset exceeds lo; a share belongs to the accepted tuple that holds it"""
+    """the range rule restated: accepted iff lo <= hi <= n_shares and no earlier offset exceeds lo; a share belongs to the accepted tuple that holds it
+    (the earlier offsets as their running maximum, so that tests/test_gpu_collect_many_tuples.py can ask it about 65 900 tuples)"""
     n = len(off) - 1
-    ok = [int(off[i] <= off[i + 1] <= n_shares and all(o <= off[i] for o in off[:i])) for i in range(n)]
+    ok, before = [], 0
+    for i in range(n):
+        ok.append(int(off[i] <= off[i + 1] <= n_shares and before <= off[i]))
+        before = max(before, off[i])
     tuple_of = [n] * n_shares
     for i in range(n):
         if ok[i]:

@@ -342,7 +342,7 @@ class ECDSA:
         return ECDSA._aggregate_keyed_signers(items, engine, n_keys)
 
     @staticmethod
-    def _aggregate_keyed_signers(items, engine, n_keys, seed=None, flags=0):
+    def _aggregate_keyed_signers(items, engine, n_keys, seed=None, flags=0, optimistic=False):
         rows = []
         for item in items:
             if len(item) != 3:
@@ -361,7 +361,9 @@ class ECDSA:
             raise ValueError("the engine does not know its registered key count: pass n_keys")
         bm_words = max((int(n_keys) + 31) // 32, 1)
         args = ([r[0] for r in rows], b"".join(s.raw for r in rows for s in r[1]), [j for r in rows for j in r[2]], [len(r[2]) for r in rows], bm_words)
-        if seed is not None:
+        if optimistic:
+            share_st, tuple_st, agg, bits = eng.batch_collect_keyed_bitmap_optimistic(*args)
+        elif seed is not None:
             share_st, tuple_st, agg, bits = eng.batch_collect_keyed_bitmap_randomized(*args, seed, flags)
         else:
             share_st, tuple_st, agg, bits = eng.batch_collect_keyed_bitmap(*args)
@@ -376,6 +378,25 @@ class ECDSA:
             signers = [j for j in range(32 * bm_words) if (row[j // 32] >> (j % 32)) & 1]
             out.append((Signature(agg[64 * i:64 * i + 64]), signers, [None if b == 0 else Error(b) for b in st]))
         return out
+
+    @staticmethod
+    def batch_aggregate_keyed_signers_optimistic(items, engine=None, n_keys=None):
+        """batch_aggregate_keyed_signers with one verify per item — the sum of its signatures that pass every check short of the pairing,
+        against the sum of their keys — and the signatures verified one by one only in an item whose sum fails, that names a key twice, or
+        that is too short (include/bn254_hip.h: bn254_batch_collect_keyed_bitmap_optimistic).  The same result list and the same refusals
+        before any device work; no seed.  The aggregate and the indices are always a pair ECDSA.verify_keyed_signers accepts.  ONE
+        deviation: signatures whose errors cancel within an item that passes (sigma_a + D and sigma_b - D) read None and are counted — a
+        None there means "counted in a sum that verifies", not "individually valid".  Who needs per-signature verdicts takes
+        batch_aggregate_keyed_signers."""
+        return ECDSA._aggregate_keyed_signers(items, engine, n_keys, optimistic=True)
+
+    @staticmethod
+    def aggregate_keyed_signers_optimistic(message, signatures, key_indices, engine=None, n_keys=None):
+        """aggregate_keyed_signers through batch_aggregate_keyed_signers_optimistic: the same triple, the same Errors raised."""
+        r = ECDSA.batch_aggregate_keyed_signers_optimistic([(message, signatures, key_indices)], engine, n_keys)[0]
+        if isinstance(r, Error):
+            raise r
+        return r
 
     @staticmethod
     def batch_aggregate_keyed_signers_randomized(items, seed=None, engine=None, n_keys=None, rand64=False):

@@ -84,6 +84,21 @@ int bm_prepare(bn254_ctx* c, hipStream_t s, bool tables) {
   return 0;
 }
 
+// the aggregate keys of n tuples whose P1 / P2 planes and decode statuses are filled: row i of d_bits summed into the Q planes of entry i, rule 2
+// behind the decode status (bn254_host.h) — from the subset tables when `tables` (bm_prepare has built them), on lane pairs or one lane per tuple
+int launch_bitmap_sum(bn254_ctx* c, hipStream_t s, const uint32_t* d_bits, size_t bm_words, size_t n, bool tables) {
+  const int32_t* rec = tables ? (const int32_t*)c->bm_tab : nullptr;
+  const uint8_t* rec_inf = tables ? c->bm_tab + ((c->n_keys + 7) / 8) * 256 * BM_REC_WORDS * sizeof(int32_t) : nullptr;
+  if (c->pair_lanes) {
+    const BmKeysArg ka = {c->key_xy, c->key_st, c->key_inf, (const uint32_t*)c->bm_bad, (uint32_t)c->n_keys};
+    return bn254_pair_bitmap_sum(d_bits, bm_words, n, ka, rec, rec_inf, c->ws, s);
+  }
+  const BmKeys K = {c->key_xy, c->key_st, c->key_inf, (const uint32_t*)c->bm_bad, (uint32_t)c->n_keys};
+  k_bm_sum<<<grid_for(n), BN_WAVE, 0, s>>>(d_bits, bm_words, n, K, rec, rec_inf, c->ws);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 extern "C" {
 
 int bn254_batch_verify_keyed_bitmap_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t* d_off, const uint8_t* d_sigs, const uint32_t* d_bits,
@@ -108,15 +123,7 @@ int bn254_batch_verify_keyed_bitmap_device(bn254_ctx* c, const uint8_t* d_msgs, 
   if ((rc = launch_decode_g1(c, s, d_sigs, n, flags, PL_P1X, BY_P1_INF, 0))) return rc;
   if ((rc = launch_hash_rounds(c, s, d_msgs, d_off, n, PL_P2X, BY_P2_INF, nullptr))) return rc;
   PROF_MARK(1);
-  const int32_t* rec = tables ? (const int32_t*)c->bm_tab : nullptr;
-  const uint8_t* rec_inf = tables ? c->bm_tab + ((c->n_keys + 7) / 8) * 256 * BM_REC_WORDS * sizeof(int32_t) : nullptr;
-  if (c->pair_lanes) {
-    const BmKeysArg ka = {c->key_xy, c->key_st, c->key_inf, (const uint32_t*)c->bm_bad, (uint32_t)c->n_keys};
-    if ((rc = bn254_pair_bitmap_sum(d_bits, bm_words, n, ka, rec, rec_inf, c->ws, s))) return rc;
-  } else {
-    const BmKeys K = {c->key_xy, c->key_st, c->key_inf, (const uint32_t*)c->bm_bad, (uint32_t)c->n_keys};
-    k_bm_sum<<<grid_for(n), BN_WAVE, 0, s>>>(d_bits, bm_words, n, K, rec, rec_inf, c->ws);
-  }
+  if ((rc = launch_bitmap_sum(c, s, d_bits, bm_words, n, tables))) return rc;
   PROF_MARK(2);
   // the tuples are verify-shaped now: the routing table serves small batches with the small-batch kernels, as after the aggregation kernel
   if ((rc = launch_verify_miller_fe(c, s, n, BN_PAIRS_VERIFY, 1, d_status, true))) return rc;

@@ -1,4 +1,5 @@
-// Building signer-bitmap aggregates from the signers' individual signatures (include/bn254_hip.h: bn254_batch_collect_keyed_bitmap[_device]):
+// Building signer-bitmap aggregates from the signers' individual signatures (include/bn254_hip.h: bn254_batch_collect_keyed_bitmap[_device],
+// and at the end of the file the steps of bn254_batch_collect_keyed_bitmap_optimistic[_device]):
 // the bookkeeping and the arithmetic of the call's own kernels (bn254_collect.hip), shared with their host compilation for the CPU suite
 // (tests/hostsim, plain and under -DBN_TRACK_BOUNDS).  Written against the jac_* interface of bn254_curve.h and the
 // decoders of bn254_io.h; G1 only, so it is the same in both layouts of Fq2.
@@ -99,6 +100,77 @@ BN_DEV void cl_encode(uint8_t* out64, const G1Jac& acc) {
   G1Affine r;
   jac_to_affine(r, acc);
   encode_g1(out64, r);
+}
+
+// ---- the optimistic collect (bn254_batch_collect_keyed_bitmap_optimistic[_device]) ---------------------------------------------------------
+// The shares of a tuple share the message: if all of them are good, their sum is the aggregate of the tuple's bitmap, and ONE verify of the
+// sum against the sum of the keys proves it.  So: rules 1-3 per share without a pairing (clo_precheck: status 0 = a CANDIDATE), a
+// provisional select-and-sum of the candidates that reports a refused claim as a DUPLICATE (clo_step), one flag per tuple (clo_flag), the
+// tuple check by the bitmap verify's kernels, and — for the tuples that fail it, have a duplicate or too few candidates — the exact keyed
+// verify of their candidates through a queue (clo_queued) and the exact select-and-sum again on their zeroed rows (clo_goes_exact masks
+// it; the rows and aggregates of passing tuples are not touched).
+#define CLO_FINAL 0   // no candidate: empty row, identity, 0 — final as it stands
+#define CLO_CHECK 1   // eligible: the provisional outputs stand iff the tuple check says 0
+#define CLO_EXACT 2   // a duplicate, or fewer candidates than the per-tuple minimum: the exact way, whatever the check says
+
+// rules 1-3 of the exact collect for one share of an accepted tuple: decode (the call's flags), key index and registration status, the
+// tuple's hash status
+BN_DEV uint8_t clo_precheck(const uint8_t* share64, uint32_t flags, uint32_t key, const uint8_t* key_st, uint32_t n_keys, uint8_t hash_st) {
+  G1Affine p;
+  uint8_t st = decode_g1(p, share64, flags);
+  if (st == ST_OK) st = key >= n_keys ? (uint8_t)ST_INDEX_OOB : key_st[key];
+  if (st == ST_OK) st = hash_st;
+  return st;
+}
+// cl_step with the refused claim reported: a candidate whose bit another candidate of the tuple holds already.  (The tuple then goes the
+// exact way, so which of the two was taken never shows.)
+BN_DEV void clo_step(G1Jac& acc, uint32_t& count, uint32_t& dup, uint32_t* row, size_t bm_words, const ClShares& in, uint64_t lo, uint64_t len, uint64_t k) {
+  bool take = false;
+  const uint64_t s = lo + k;
+  if (k < len && in.share_st[s] == ST_OK) {
+    take = cl_claim(row, bm_words, in.key[s]);
+    if (!take) dup = 1u;
+  }
+  if (!BN_WAVE_ANY(take)) return;
+  G1Affine p;
+  cl_load_share(p, in.shares, s, take);
+  jac_accumulate(acc, p);
+  count += take ? 1u : 0u;
+}
+BN_DEV void clo_lane_sum(G1Jac& acc, uint32_t& count, uint32_t& dup, uint32_t* row, size_t bm_words, const ClShares& in, uint64_t lo, uint64_t len) {
+  jac_set_identity(acc);
+  count = 0;
+  dup = 0;
+  for (uint64_t k = 0; BN_WAVE_ANY(k < len); ++k) clo_step(acc, count, dup, row, bm_words, in, lo, len, k);
+}
+BN_DEV void clo_wave_partial(G1Jac& acc, uint32_t& count, uint32_t& dup, uint32_t* row, size_t bm_words, const ClShares& in, uint64_t lo, uint64_t len,
+                             unsigned lane) {
+  jac_set_identity(acc);
+  count = 0;
+  dup = 0;
+  for (uint64_t k = lane; BN_WAVE_ANY(k < len); k += BN_CL_WAVE) clo_step(acc, count, dup, row, bm_words, in, lo, len, k);
+}
+template <class Slot>
+BN_DEV void clo_tree_level(Slot* part, uint32_t* cnt, uint32_t* dup, unsigned t, unsigned stride) {
+  cl_tree_level(part, cnt, t, stride);
+  dup[t] |= dup[t + stride];
+}
+// the tuple's flag from what the provisional sum saw: `count` claims (= candidates, when none was refused), min_tuple = the per-tuple minimum
+BN_DEV uint8_t clo_flag(uint32_t count, uint32_t dup, uint32_t min_tuple) {
+  if (dup) return CLO_EXACT;
+  if (count == 0) return CLO_FINAL;
+  return count < min_tuple ? CLO_EXACT : CLO_CHECK;
+}
+// does tuple i go the exact way, given its flag and the tuple check's verdict (read for CLO_CHECK only)
+BN_DEV bool clo_goes_exact(uint8_t flag, uint8_t verdict) { return flag == CLO_EXACT || (flag == CLO_CHECK && verdict != ST_OK); }
+// is share s — status share_st behind the pre-check, of tuple t (n = of nobody) — queued for the exact verify
+BN_DEV bool clo_queued(uint8_t share_st, size_t t, size_t n, const uint8_t* flag, const uint8_t* verdict) {
+  return t < n && share_st == ST_OK && clo_goes_exact(flag[t], verdict[t]);
+}
+// the shares of tuple i as the masked re-sum walks them: those of a tuple that goes the exact way, none of any other
+BN_DEV uint64_t clo_resum_len(const ClShares& in, size_t i, bool live, const uint8_t* flag, const uint8_t* verdict) {
+  if (!live || !clo_goes_exact(flag[i], verdict[i])) return 0;
+  return cl_tuple_len(in, i, true);
 }
 
 }  // namespace bn254

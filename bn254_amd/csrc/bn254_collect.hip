@@ -4,6 +4,9 @@
 // arithmetic of the kernels are bn254_collect.h, shared with the CPU suite's host compilation.
 // bn254_batch_collect_keyed_bitmap_randomized[_device] is the same call with the slots verified by the grouped checks of the
 // randomised keyed verify (bn254_rand.hip: launch_keyed_rand_checks): the shares of a slice grouped by key across its tuples.
+// bn254_batch_collect_keyed_bitmap_optimistic[_device] verifies each tuple's SUM once, by the bitmap verify's kernels
+// (bn254_bitmap.hip: bm_prepare, launch_bitmap_sum; launch_verify_miller_fe), and sends only the candidates of the tuples that fail — or
+// have a duplicate, or too few candidates — through a device-side queue into the exact keyed kernels (cl_optimistic).
 // Per-share semantics: ECDSA::verify (/root/reference/src/ecdsa.rs:49-64); the sum: `Add for Signature` (src/types.rs:264-270).
 #include <hip/hip_runtime.h>
 
@@ -27,9 +30,12 @@ using namespace bn254;
 
 // per tuple, outside the (sliced) workspace: the scans of the range rule, H(m) with its identity flag and hash status
 #define CL_HASH_WORDS (2 * BN_LIMBS)
-// ... and, in front, what the randomised slices of the call did: {slices, groups checked, groups failed, shares re-checked exactly}
-#define CL_STAT_WORDS 4
-struct ClScratch { uint32_t* stats; uint64_t *mx, *hi, *end, *tot; int32_t* hpt; uint8_t *hinf, *hst; };
+// ... and, in front, what the randomised slices of the call did: {slices, groups checked, groups failed, shares re-checked exactly}, then what
+// the optimistic route did: {tuples checked, tuples passed, tuples sent the exact way, shares verified exactly}; behind, that route's flag
+// (bn254_collect.h: CLO_*) and tuple-check verdict per tuple
+#define CL_STAT_WORDS 8
+#define CLO_STAT_AT 4
+struct ClScratch { uint32_t* stats; uint64_t *mx, *hi, *end, *tot; int32_t* hpt; uint8_t *hinf, *hst, *flag, *verdict; };
 static ClScratch cl_scratch(Carve& c, size_t n) {
   ClScratch b;
   b.stats = c.take<uint32_t>(CL_STAT_WORDS);
@@ -37,6 +43,7 @@ static ClScratch cl_scratch(Carve& c, size_t n) {
   b.tot = c.take<uint64_t>((n + AGGD_SCAN_WG - 1) / AGGD_SCAN_WG);
   b.hpt = c.take<int32_t>(n * CL_HASH_WORDS);
   b.hinf = c.take<uint8_t>(n), b.hst = c.take<uint8_t>(n);
+  b.flag = c.take<uint8_t>(n), b.verdict = c.take<uint8_t>(n);
   return b;
 }
 
@@ -190,13 +197,163 @@ static int cl_verify_slice_rand(bn254_ctx* c, hipStream_t s, const uint8_t* d_sh
   return 0;
 }
 
-// both calls: seed32 == nullptr is the exact one
+// ---- the optimistic route (the steps are bn254_collect.h's clo_*) ------------------------------------------------------------
+// rules 1-3 of every share of an accepted tuple, straight from the caller's bytes: no workspace, no pairing.  A share of nobody keeps the 2
+// the status array was filled with.
+KERNEL_SMALL void k_clo_precheck(size_t n_shares, size_t n, const uint8_t* shares, const uint32_t* key, const uint64_t* off, uint32_t flags, ClScratch S,
+                                 const uint8_t* key_st, uint32_t n_keys, uint8_t* share_status) {
+  const size_t s = (size_t)blockIdx.x * BN_WAVE + threadIdx.x;
+  if (s >= n_shares) return;
+  const size_t t = cl_tuple_of(s, S.end, off, n);
+  if (t >= n) return;
+  share_status[s] = clo_precheck(shares + 64 * s, flags, key[s], key_st, n_keys, S.hst[t]);
+}
+// the select-and-sum of k_cl_sum_lane / k_cl_sum_wave with refused claims reported.  verdict == nullptr: the PROVISIONAL sum of every tuple's
+// candidates, which also writes the tuple's flag; else the RE-SUM of the tuples that go the exact way (their rows zeroed by k_clo_settle),
+// under the exact call's rule — the other tuples' outputs are not touched.
+KERNEL_SMALL void k_clo_sum_lane(ClShares in, size_t n, size_t bm_words, uint64_t wave_min, uint32_t min_tuple, const uint8_t* verdict, uint8_t* flag,
+                                 uint32_t* bits, uint8_t* agg, uint32_t* n_signers) {
+  const size_t i = (size_t)blockIdx.x * BN_WAVE + threadIdx.x;
+  const bool live = i < n;
+  uint64_t len = verdict ? clo_resum_len(in, live ? i : 0, live, flag, verdict) : cl_tuple_len(in, live ? i : 0, live);
+  const bool mine = live && len < wave_min && (!verdict || clo_goes_exact(flag[i], verdict[i]));
+  if (!mine) len = 0;
+  G1Jac acc;
+  uint32_t count, dup;
+  clo_lane_sum(acc, count, dup, bits + (mine ? i : 0) * bm_words, bm_words, in, mine ? in.off[i] : 0, len);
+  G1Affine r;
+  jac_to_affine(r, acc);
+  if (!mine) return;
+  encode_g1(agg + 64 * i, r);
+  if (n_signers) n_signers[i] = count;
+  if (!verdict) flag[i] = clo_flag(count, dup, min_tuple);
+}
+KERNEL_SMALL void k_clo_sum_wave(ClShares in, size_t n, size_t bm_words, uint64_t wave_min, uint32_t min_tuple, const uint8_t* verdict, uint8_t* flag,
+                                 uint32_t* bits, uint8_t* agg, uint32_t* n_signers) {
+  __shared__ ClJacSlot part[BN_WAVE];
+  __shared__ uint32_t cnt[BN_WAVE], dupf[BN_WAVE];
+  const unsigned t = threadIdx.x;
+  for (size_t i = blockIdx.x; i < n; i += gridDim.x) {
+    const uint64_t len = verdict ? clo_resum_len(in, i, true, flag, verdict) : cl_tuple_len(in, i, true);
+    if (len < wave_min) continue;                      // wave_min >= 1: also every tuple the re-sum masks out
+    clo_wave_partial(part[t].v, cnt[t], dupf[t], bits + i * bm_words, bm_words, in, in.off[i], len, t);
+    __syncthreads();
+    for (unsigned stride = BN_WAVE / 2; stride >= 1; stride >>= 1) {
+      if (t < stride) clo_tree_level(part, cnt, dupf, t, stride);
+      __syncthreads();
+    }
+    if (t == 0) {
+      cl_encode(agg + 64 * i, part[0].v);
+      if (n_signers) n_signers[i] = cnt[0];
+      if (!verdict) flag[i] = clo_flag(cnt[0], dupf[0], min_tuple);
+    }
+    __syncthreads();
+  }
+}
+// the tuple check's H(m): tuple base + j into slot j, as k_cl_spread gives a share its tuple's
+KERNEL_SMALL void k_clo_load_h(size_t len, size_t base, ClScratch S, Ws ws) {
+  const size_t j = (size_t)blockIdx.x * BN_WAVE + threadIdx.x;
+  if (j >= len) return;
+  const int32_t* w = S.hpt + (base + j) * CL_HASH_WORDS;
+  Fp x, y;
+#pragma unroll
+  for (int k = 0; k < BN_LIMBS; ++k) { x.v[k] = w[k]; y.v[k] = w[BN_LIMBS + k]; }
+  ws_store_fp(ws, PL_P2X, j, x);
+  ws_store_fp(ws, PL_P2Y, j, y);
+  ws_byte(ws, BY_P2_INF, j) = S.hinf[base + j];
+  ws_byte(ws, BY_ST_HASH, j) = S.hst[base + j];
+}
+// behind the tuple check: the rows of the tuples that go the exact way are zeroed for the re-sum, and the call's counters take what the
+// check did (one vector atomic per wave and counter)
+KERNEL_SMALL void k_clo_settle(size_t n, size_t bm_words, ClScratch S, uint32_t* bits) {
+  const size_t i = (size_t)blockIdx.x * BN_WAVE + threadIdx.x;
+  const bool live = i < n;
+  const uint8_t flag = live ? S.flag[i] : (uint8_t)CLO_FINAL, verdict = live ? S.verdict[i] : (uint8_t)ST_OK;
+  const bool checked = flag == CLO_CHECK, passed = checked && verdict == ST_OK, exact = clo_goes_exact(flag, verdict);
+  if (exact)
+    for (size_t w = 0; w < bm_words; ++w) bits[i * bm_words + w] = 0;
+  const uint32_t n_checked = (uint32_t)__popcll(__ballot(checked)), n_passed = (uint32_t)__popcll(__ballot(passed)), n_exact = (uint32_t)__popcll(__ballot(exact));
+  if (threadIdx.x == 0) {
+    uint32_t* stats = S.stats + CLO_STAT_AT;
+    if (n_checked) atomicAdd(&stats[0], n_checked);
+    if (n_passed) atomicAdd(&stats[1], n_passed);
+    if (n_exact) atomicAdd(&stats[2], n_exact);
+  }
+}
+// slot j of a slice = share base + j: queued for the exact keyed verify iff it is a candidate of a tuple that goes the exact way
+KERNEL_SMALL void k_clo_queue(size_t len, uint64_t base, size_t n, const uint64_t* off, ClScratch S, const uint8_t* share_status, Ws ws) {
+  const size_t j = (size_t)blockIdx.x * BN_WAVE + threadIdx.x;
+  if (j >= len) return;
+  const size_t t = cl_tuple_of(base + j, S.end, off, n);
+  if (clo_queued(share_status[base + j], t, n, S.flag, S.verdict)) ws.h_list[atomicAdd(&ws.h_cnt[0], 1u)] = (uint32_t)j;
+}
+// ... and the queue's length into the call's counters
+KERNEL_SMALL void k_clo_count(const uint32_t* h_cnt, uint32_t* stats) {
+  if (threadIdx.x == 0 && h_cnt[0]) atomicAdd(&stats[CLO_STAT_AT + 3], h_cnt[0]);
+}
+// The route behind the hash, the range rule and the fills (cl_collect_device): pre-check, provisional sum, the tuple check in pieces of
+// t_piece tuples, then the exact verify of the queued candidates in slices of s_piece shares and the re-sum.  Everything is enqueued whether
+// or not a tuple fails: the host never learns.  ms[0] = front end + provisional sum, ms[1] = aggregate keys, ms[2] = the tuples' Miller loop
+// and final exponentiation, ms[3] = exact fallback + re-sum (a call in several pieces: the last piece's ms[1] boundary).
+static int cl_optimistic(bn254_ctx* c, hipStream_t s, const ClShares& in, size_t n_shares, size_t n, size_t bm_words, uint32_t flags, size_t t_piece,
+                         size_t s_piece, const ClScratch& S, uint8_t* d_share_status, uint8_t* d_agg_sigs, uint32_t* d_signer_bits, uint32_t* d_n_signers) {
+  int rc;
+  const uint64_t wave_min = (uint64_t)c->collect_wave_min;
+  const uint32_t min_tuple = (uint32_t)c->collect_opt_min_tuple_shares;
+  const unsigned wave_grid = (unsigned)(n < CL_WAVE_MAX_BLOCKS ? n : CL_WAVE_MAX_BLOCKS);
+  const KeyTable kt = {c->key_lines, c->key_st, c->key_inf, (uint32_t)c->n_keys};
+  const bool tables = bm_wants_tables(c);
+  // 3. rules 1-3 of every share; 4. the provisional sum of the candidates and the tuples' flags
+  k_clo_precheck<<<grid_for(n_shares), BN_WAVE, 0, s>>>(n_shares, n, in.shares, in.key, in.off, flags, S, c->key_st, (uint32_t)c->n_keys, d_share_status);
+  HIP_TRY(hipGetLastError());
+  k_clo_sum_lane<<<grid_for(n), BN_WAVE, 0, s>>>(in, n, bm_words, wave_min, min_tuple, nullptr, S.flag, d_signer_bits, d_agg_sigs, d_n_signers);
+  HIP_TRY(hipGetLastError());
+  k_clo_sum_wave<<<wave_grid, BN_WAVE, 0, s>>>(in, n, bm_words, wave_min, min_tuple, nullptr, S.flag, d_signer_bits, d_agg_sigs, d_n_signers);
+  HIP_TRY(hipGetLastError());
+  PROF_MARK(1);
+  // 5. the tuple check: the call's own outputs through the bitmap verify's kernels, decode flags 0 (an identity aggregate is legitimate)
+  for (size_t lo = 0; lo < n; lo += t_piece) {
+    const size_t len = n - lo < t_piece ? n - lo : t_piece;
+    if ((rc = launch_decode_g1(c, s, d_agg_sigs + 64 * lo, len, 0, PL_P1X, BY_P1_INF, 0))) return rc;
+    k_clo_load_h<<<grid_for(len), BN_WAVE, 0, s>>>(len, lo, S, c->ws);
+    HIP_TRY(hipGetLastError());
+    if ((rc = launch_bitmap_sum(c, s, d_signer_bits + lo * bm_words, bm_words, len, tables))) return rc;
+    PROF_MARK(2);
+    if ((rc = launch_verify_miller_fe(c, s, len, BN_PAIRS_VERIFY, 1, S.verdict + lo, false))) return rc;
+  }
+  PROF_MARK(3);
+  k_clo_settle<<<grid_for(n), BN_WAVE, 0, s>>>(n, bm_words, S, d_signer_bits);
+  HIP_TRY(hipGetLastError());
+  // 6. the candidates of the tuples that go the exact way, verified by the keyed kernels over a queue; then those tuples summed again
+  for (size_t lo = 0; lo < n_shares; lo += s_piece) {
+    const size_t len = n_shares - lo < s_piece ? n_shares - lo : s_piece;
+    if ((rc = launch_decode_g1(c, s, in.shares + 64 * lo, len, flags, PL_P1X, BY_P1_INF, 0))) return rc;
+    k_cl_spread<<<grid_for(len), BN_WAVE, 0, s>>>(len, (uint64_t)lo, n, in.off, S, c->ws);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemsetAsync(c->ws.h_cnt, 0, sizeof(uint32_t), s));
+    k_clo_queue<<<grid_for(len), BN_WAVE, 0, s>>>(len, (uint64_t)lo, n, in.off, S, d_share_status, c->ws);
+    HIP_TRY(hipGetLastError());
+    k_clo_count<<<1, BN_WAVE, 0, s>>>(c->ws.h_cnt, S.stats);
+    HIP_TRY(hipGetLastError());
+    if ((rc = bn254_pair_miller_verify_keyed(len, c->ws, in.key + lo, kt, s, 0, c->ws.h_list, c->ws.h_cnt))) return rc;
+    if ((rc = bn254_pair_final_exp(len, c->ws, 1, d_share_status + lo, c->ws.h_list, c->ws.h_cnt, s))) return rc;
+  }
+  k_clo_sum_lane<<<grid_for(n), BN_WAVE, 0, s>>>(in, n, bm_words, wave_min, min_tuple, S.verdict, S.flag, d_signer_bits, d_agg_sigs, d_n_signers);
+  HIP_TRY(hipGetLastError());
+  k_clo_sum_wave<<<wave_grid, BN_WAVE, 0, s>>>(in, n, bm_words, wave_min, min_tuple, S.verdict, S.flag, d_signer_bits, d_agg_sigs, d_n_signers);
+  PROF_MARK(4);
+  prof_done(c, EV_DECODE_FIRST);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// all three calls: seed32 == nullptr and !optimistic is the exact one
 static int cl_collect_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t* d_msg_off, const uint8_t* d_shares,
                              const uint32_t* d_share_key, const uint64_t* d_share_off, size_t n_shares, size_t n, size_t bm_words,
-                             uint32_t flags, const uint8_t* seed32, uint8_t* d_share_status, uint8_t* d_tuple_status, uint8_t* d_agg_sigs,
-                             uint32_t* d_signer_bits, uint32_t* d_n_signers, void* stream) {
+                             uint32_t flags, const uint8_t* seed32, bool optimistic, uint8_t* d_share_status, uint8_t* d_tuple_status,
+                             uint8_t* d_agg_sigs, uint32_t* d_signer_bits, uint32_t* d_n_signers, void* stream) {
   MsgsLenScope msgs_len_scope(c);
-  if (c) c->clr_last_ran = 0;
+  if (c) c->clr_last_ran = c->clo_last_ran = 0;
   if (!c || bm_words > 0xFFFFFFFFu || n > 0xFFFFFFFFu || n_shares > 0xFFFFFFFFu) return BN254_E_BAD_ARGUMENT;
   if (bm_words < (c->n_keys + 31) / 32) return BN254_E_BAD_ARGUMENT;       // a bitmap that cannot hold a registered key cannot describe the result
   if (n && (!d_msgs || !d_msg_off || !d_share_off || !d_tuple_status || !d_agg_sigs || (bm_words && !d_signer_bits))) return BN254_E_BAD_ARGUMENT;
@@ -216,6 +373,8 @@ static int cl_collect_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t
     r_piece = cl_rand_slice_len(c, n_shares);
   if (r_piece && !cl_rand_slots_fit(c, r_piece)) r_piece = 0;
   const bool rand = r_piece != 0;
+  // the optimistic route: keys to sum, and enough shares for one more verify pass to pay.  Else the exact route, same bytes.
+  const bool opt = optimistic && c->n_keys && c->key_lines && n_shares && n_shares >= (size_t)c->collect_opt_min_shares;
   // the randomised call's own flags choose the weights; the remaining ones apply to the shares' decode on either route
   const int mode = rand_mode_of(flags);
   if (seed32) flags &= BN254_FLAG_G2_SUBGROUP_CHECK | BN254_FLAG_REJECT_IDENTITY;
@@ -235,14 +394,14 @@ static int cl_collect_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t
   Carve carve(c->collect_buf);
   const ClScratch S = cl_scratch(carve, n);
   c->clr_stats = S.stats;
+  c->clo_stats = S.stats + CLO_STAT_AT;
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   CallDone call_done(c, s);
+  if (opt && (rc = bm_prepare(c, s, bm_wants_tables(c)))) return rc;   // the first call after a registration builds here, ahead of the timed intervals
   RandSeed seed = {};
-  if (rand) {
-    seed = rand_seed_from(seed32);
-    HIP_TRY(hipMemsetAsync(S.stats, 0, CL_STAT_WORDS * sizeof(uint32_t), s));
-  }
-  PROF_MARK(1);
+  if (rand) seed = rand_seed_from(seed32);
+  if (rand || opt) HIP_TRY(hipMemsetAsync(S.stats, 0, CL_STAT_WORDS * sizeof(uint32_t), s));
+  PROF_MARK(opt ? 0 : 1);
   // 1. hash once per tuple
   for (size_t lo = 0; lo < n; lo += t_piece) {
     const size_t len = n - lo < t_piece ? n - lo : t_piece;
@@ -257,6 +416,12 @@ static int cl_collect_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t
   if ((rc = bn254_aggd_scan_max(s, S.hi, n, S.end, S.tot))) return rc;
   if (bm_words) HIP_TRY(hipMemsetAsync(d_signer_bits, 0, n * bm_words * sizeof(uint32_t), s));
   if (n_shares) HIP_TRY(hipMemsetAsync(d_share_status, ST_INDEX_OOB, n_shares, s));
+  if (opt) {
+    const ClShares in = {d_shares, d_share_key, d_share_off, d_share_status, d_tuple_status};
+    if ((rc = cl_optimistic(c, s, in, n_shares, n, bm_words, flags, t_piece, s_piece, S, d_share_status, d_agg_sigs, d_signer_bits, d_n_signers))) return rc;
+    c->clo_last_ran = 1;
+    return 0;
+  }
   // 3. the keyed verify of the share slots
   for (size_t lo = 0; lo < n_shares; lo += s_piece) {
     const size_t len = n_shares - lo < s_piece ? n_shares - lo : s_piece;
@@ -281,9 +446,10 @@ static int cl_collect_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t
 // the host-pointer form of both.  The randomised call's grouping scratch lives in stage slots 5 and 7, so its outputs take slot 6.
 static int cl_collect_host(bn254_ctx* c, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* shares, const uint32_t* share_key,
                            const uint64_t* share_off, size_t n_shares, size_t n, size_t bm_words, uint32_t flags, const uint8_t* seed32,
-                           uint8_t* share_status, uint8_t* tuple_status, uint8_t* agg_sigs, uint32_t* signer_bits, uint32_t* n_signers) {
+                           bool optimistic, uint8_t* share_status, uint8_t* tuple_status, uint8_t* agg_sigs, uint32_t* signer_bits,
+                           uint32_t* n_signers) {
   MsgsLenScope msgs_len_scope(c);
-  if (c) c->clr_last_ran = 0;
+  if (c) c->clr_last_ran = c->clo_last_ran = 0;
   if (!c || bm_words > 0xFFFFFFFFu || n > 0xFFFFFFFFu || n_shares > 0xFFFFFFFFu) return BN254_E_BAD_ARGUMENT;
   if (bm_words < (c->n_keys + 31) / 32) return BN254_E_BAD_ARGUMENT;
   if (n && (!msg_off || !share_off || !tuple_status || !agg_sigs || (bm_words && !signer_bits))) return BN254_E_BAD_ARGUMENT;
@@ -308,7 +474,7 @@ static int cl_collect_host(bn254_ctx* c, const uint8_t* msgs, const uint64_t* ms
   }
   if (st.ok())
     st.rc = cl_collect_device(c, d_msgs, (const uint64_t*)d_msg_off, d_shares, (const uint32_t*)d_key, (const uint64_t*)d_share_off, n_shares, n, bm_words,
-                              flags, seed32, d_out + o_sst, d_out + o_tst, d_out, (uint32_t*)(d_out + o_bits),
+                              flags, seed32, optimistic, d_out + o_sst, d_out + o_tst, d_out, (uint32_t*)(d_out + o_bits),
                               n_signers ? (uint32_t*)(d_out + o_cnt) : nullptr, nullptr);
   return st.finish();
 }
@@ -319,14 +485,14 @@ int bn254_batch_collect_keyed_bitmap_device(bn254_ctx* c, const uint8_t* d_msgs,
                                             const uint32_t* d_share_key, const uint64_t* d_share_off, size_t n_shares, size_t n, size_t bm_words,
                                             uint32_t flags, uint8_t* d_share_status, uint8_t* d_tuple_status, uint8_t* d_agg_sigs,
                                             uint32_t* d_signer_bits, uint32_t* d_n_signers, void* stream) {
-  return cl_collect_device(c, d_msgs, d_msg_off, d_shares, d_share_key, d_share_off, n_shares, n, bm_words, flags, nullptr, d_share_status, d_tuple_status,
-                           d_agg_sigs, d_signer_bits, d_n_signers, stream);
+  return cl_collect_device(c, d_msgs, d_msg_off, d_shares, d_share_key, d_share_off, n_shares, n, bm_words, flags, nullptr, false, d_share_status,
+                           d_tuple_status, d_agg_sigs, d_signer_bits, d_n_signers, stream);
 }
 int bn254_batch_collect_keyed_bitmap(bn254_ctx* c, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* shares, const uint32_t* share_key,
                                      const uint64_t* share_off, size_t n_shares, size_t n, size_t bm_words, uint32_t flags, uint8_t* share_status,
                                      uint8_t* tuple_status, uint8_t* agg_sigs, uint32_t* signer_bits, uint32_t* n_signers) {
-  return cl_collect_host(c, msgs, msg_off, shares, share_key, share_off, n_shares, n, bm_words, flags, nullptr, share_status, tuple_status, agg_sigs,
-                         signer_bits, n_signers);
+  return cl_collect_host(c, msgs, msg_off, shares, share_key, share_off, n_shares, n, bm_words, flags, nullptr, false, share_status, tuple_status,
+                         agg_sigs, signer_bits, n_signers);
 }
 int bn254_batch_collect_keyed_bitmap_randomized_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t* d_msg_off, const uint8_t* d_shares,
                                                        const uint32_t* d_share_key, const uint64_t* d_share_off, size_t n_shares, size_t n,
@@ -334,16 +500,30 @@ int bn254_batch_collect_keyed_bitmap_randomized_device(bn254_ctx* c, const uint8
                                                        uint8_t* d_tuple_status, uint8_t* d_agg_sigs, uint32_t* d_signer_bits, uint32_t* d_n_signers,
                                                        void* stream) {
   if (!seed32) return BN254_E_BAD_ARGUMENT;
-  return cl_collect_device(c, d_msgs, d_msg_off, d_shares, d_share_key, d_share_off, n_shares, n, bm_words, flags, seed32, d_share_status, d_tuple_status,
-                           d_agg_sigs, d_signer_bits, d_n_signers, stream);
+  return cl_collect_device(c, d_msgs, d_msg_off, d_shares, d_share_key, d_share_off, n_shares, n, bm_words, flags, seed32, false, d_share_status,
+                           d_tuple_status, d_agg_sigs, d_signer_bits, d_n_signers, stream);
 }
 int bn254_batch_collect_keyed_bitmap_randomized(bn254_ctx* c, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* shares,
                                                 const uint32_t* share_key, const uint64_t* share_off, size_t n_shares, size_t n, size_t bm_words,
                                                 uint32_t flags, const uint8_t* seed32, uint8_t* share_status, uint8_t* tuple_status, uint8_t* agg_sigs,
                                                 uint32_t* signer_bits, uint32_t* n_signers) {
   if (!seed32) return BN254_E_BAD_ARGUMENT;
-  return cl_collect_host(c, msgs, msg_off, shares, share_key, share_off, n_shares, n, bm_words, flags, seed32, share_status, tuple_status, agg_sigs,
-                         signer_bits, n_signers);
+  return cl_collect_host(c, msgs, msg_off, shares, share_key, share_off, n_shares, n, bm_words, flags, seed32, false, share_status, tuple_status,
+                         agg_sigs, signer_bits, n_signers);
+}
+int bn254_batch_collect_keyed_bitmap_optimistic_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t* d_msg_off, const uint8_t* d_shares,
+                                                       const uint32_t* d_share_key, const uint64_t* d_share_off, size_t n_shares, size_t n,
+                                                       size_t bm_words, uint32_t flags, uint8_t* d_share_status, uint8_t* d_tuple_status,
+                                                       uint8_t* d_agg_sigs, uint32_t* d_signer_bits, uint32_t* d_n_signers, void* stream) {
+  return cl_collect_device(c, d_msgs, d_msg_off, d_shares, d_share_key, d_share_off, n_shares, n, bm_words, flags, nullptr, true, d_share_status,
+                           d_tuple_status, d_agg_sigs, d_signer_bits, d_n_signers, stream);
+}
+int bn254_batch_collect_keyed_bitmap_optimistic(bn254_ctx* c, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* shares,
+                                                const uint32_t* share_key, const uint64_t* share_off, size_t n_shares, size_t n, size_t bm_words,
+                                                uint32_t flags, uint8_t* share_status, uint8_t* tuple_status, uint8_t* agg_sigs,
+                                                uint32_t* signer_bits, uint32_t* n_signers) {
+  return cl_collect_host(c, msgs, msg_off, shares, share_key, share_off, n_shares, n, bm_words, flags, nullptr, true, share_status, tuple_status,
+                         agg_sigs, signer_bits, n_signers);
 }
 
 }  // extern "C"

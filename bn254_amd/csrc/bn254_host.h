@@ -22,6 +22,7 @@ struct AggrLast { size_t ng, cbase, tbase; const uint32_t *nagg, *bkey; const ui
 // the order in which a profiled call recorded its events: decode, hash, Miller loop, final exponentiation between ev[0] .. ev[4]; the
 // host-pointer verify's hash, decode, ...; or the collect call's (its select-and-sum runs last and reports in ms[1]): front end ev[1]..ev[2],
 // Miller loop ..ev[3], final exponentiation ..ev[4], select-and-sum ..ev[0]
+// (the optimistic collect records its four intervals in order: EV_DECODE_FIRST)
 enum EvLayout { EV_DECODE_FIRST = 0, EV_HASH_FIRST = 1, EV_COLLECT = 2 };
 
 struct bn254_ctx {
@@ -137,6 +138,10 @@ struct bn254_ctx {
   int collect_rand_min_per_key;   // BN254_OPT_COLLECT_RAND_MIN_PER_KEY: ... and from this many shares per registered key on
   uint32_t* clr_stats;       // what the slices of its last call did on the device (bn254_debug_collect_rand_last); inside collect_buf
   int clr_last_ran;          // ... and whether that call took the randomised route at all
+  int collect_opt_min_shares;       // BN254_OPT_COLLECT_OPT_MIN_SHARES: the optimistic collect from this many shares on
+  int collect_opt_min_tuple_shares; // BN254_OPT_COLLECT_OPT_MIN_TUPLE_SHARES: ... and, per tuple, from this many candidates on
+  uint32_t* clo_stats;       // what its last call did on the device (bn254_debug_collect_opt_last); inside collect_buf
+  int clo_last_ran;          // ... and whether that call took the optimistic route at all
 };
 
 struct ScopedEvents {
@@ -326,4 +331,6 @@ BN_HIDDEN int launch_final_exp_lane(bn254_ctx* c, hipStream_t s, size_t n, size_
 // signer bitmaps (bn254_bitmap.hip): does a call read the subset tables; the bad-bit vector and, when read, the tables built on the call's stream
 BN_HIDDEN bool bm_wants_tables(const bn254_ctx* c);
 BN_HIDDEN int bm_prepare(bn254_ctx* c, hipStream_t s, bool tables);
+// ... and the aggregate keys of n tuples (row i of d_bits -> the Q planes of workspace entry i, rule 2 behind the entry's decode status)
+BN_HIDDEN int launch_bitmap_sum(bn254_ctx* c, hipStream_t s, const uint32_t* d_bits, size_t bm_words, size_t n, bool tables);
 BN_HIDDEN int launch_encode_g1(bn254_ctx* c, hipStream_t s, size_t n, int px, int inf_plane, uint8_t* out, uint8_t* status_out);

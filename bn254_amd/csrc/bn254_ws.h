@@ -273,6 +273,11 @@ __attribute__((visibility("hidden"))) int bn254_pair_bitmap_sum(const uint32_t* 
                                                    //     (the smallest measured size at which it wins; at 45 056 shares it ties or loses: DESIGN.md §10f)
 #define COLLECT_RAND_MIN_PER_KEY_DEFAULT 42        // BN254_OPT_COLLECT_RAND_MIN_PER_KEY: ... and from this many shares per registered key on (the smallest measured
                                                    //     ratio at which it wins; at 10 per key it loses, nothing measured in between)
+#define COLLECT_OPT_MIN_SHARES_DEFAULT 1539        // BN254_OPT_COLLECT_OPT_MIN_SHARES: bn254_batch_collect_keyed_bitmap_optimistic checks sums from this many shares
+                                                   //     on (the smallest measured size from which it wins, tuples of 171 shares: 1 026 ties, 513 loses)
+#define COLLECT_OPT_MIN_TUPLE_SHARES_DEFAULT 1     // BN254_OPT_COLLECT_OPT_MIN_TUPLE_SHARES: ... and only the tuples with at least this many candidates.  1 = every
+                                                   //     tuple: a tuple sent the exact way costs the call one pass of the queue's kernels, 4.9 ms measured whatever
+                                                   //     the queue's length, and the check of a short tuple's sum costs nothing measurable
 __attribute__((visibility("hidden"))) int bn254_aggd_scan_add(hipStream_t s, const uint64_t* in, size_t n, uint64_t* out, uint64_t* tot);
 __attribute__((visibility("hidden"))) int bn254_aggd_scan_max(hipStream_t s, const uint64_t* in, size_t n, uint64_t* out, uint64_t* tot);   // ... the prefix maximum
 __attribute__((visibility("hidden"))) int bn254_aggd_keyed_slot_map(hipStream_t s, size_t n, const uint64_t* lo, const uint64_t* hi, int width,

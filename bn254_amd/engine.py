@@ -52,6 +52,10 @@ OPT_COLLECT_RAND_MIN_SHARES = 38   # collect_keyed_bitmap_randomized: the exact 
 OPT_COLLECT_RAND_MIN_PER_KEY = 39  # ... and below this many shares per registered key, n_shares // n_keys (default 42); DESIGN.md §10f
 COLLECT_RAND_MIN_SHARES_DEFAULT = 65664  # the library's defaults of the two (bn254_amd/csrc/bn254_ws.h; measured: DESIGN.md §10f)
 COLLECT_RAND_MIN_PER_KEY_DEFAULT = 42
+OPT_COLLECT_OPT_MIN_SHARES = 40         # collect_keyed_bitmap_optimistic: the exact collect below this many shares (default 1539)
+OPT_COLLECT_OPT_MIN_TUPLE_SHARES = 41   # ... and, per tuple, the exact way below this many candidates (default 1 = every tuple is checked); DESIGN.md §10g
+COLLECT_OPT_MIN_SHARES_DEFAULT = 1539   # the library's defaults of the two (bn254_amd/csrc/bn254_ws.h; measured: DESIGN.md §10g)
+COLLECT_OPT_MIN_TUPLE_SHARES_DEFAULT = 1
 OPT_COLLECT_WAVE_MIN_SHARES = 37   # collect_keyed_bitmap: tuples with at least this many shares are summed by a wave each (default 16; swept at three shapes only)
 
 
@@ -201,6 +205,14 @@ class Engine:
         o = (ctypes.c_uint64 * 4)()
         _check("bn254_debug_collect_rand_last", self._lib.bn254_debug_collect_rand_last(self._h, o))
         return dict(zip(("slices", "groups", "failed_groups", "rechecked"), (int(x) for x in o)))
+
+    def debug_collect_opt_last(self):
+        """what the last batch_collect_keyed_bitmap_optimistic[_device] did, counted on the device: dict(checked, passed, exact_tuples,
+        exact_shares) — tuples whose sum was verified, those that passed, tuples sent the exact way (failed, a duplicate, below the
+        per-tuple minimum), shares verified one by one; all 0 when the call took the exact route as a whole"""
+        o = (ctypes.c_uint64 * 4)()
+        _check("bn254_debug_collect_opt_last", self._lib.bn254_debug_collect_opt_last(self._h, o))
+        return dict(zip(("checked", "passed", "exact_tuples", "exact_shares"), (int(x) for x in o)))
 
     def debug_bitmap_rand_sums(self):
         """the G1 side of that call's group checks as it left them (include/bn254_hip.h: bn254_debug_bitmap_rand_sums), in the format of
@@ -529,11 +541,11 @@ class Engine:
         _check("bn254_batch_verify_keyed_bitmap_device",
                self._lib.bn254_batch_verify_keyed_bitmap_device(self._h, d_msgs, d_off, d_sigs, d_signer_bits, bm_words, n, flags, d_status, stream))
 
-    def batch_collect_keyed_bitmap(self, messages, shares, share_keys, sizes, bm_words, flags=0, want_counts=False, seed32=None):
+    def batch_collect_keyed_bitmap(self, messages, shares, share_keys, sizes, bm_words, flags=0, want_counts=False, seed32=None, optimistic=False):
         """build signer-bitmap aggregates from individual signatures (include/bn254_hip.h: bn254_batch_collect_keyed_bitmap): tuple i is
         messages[i] with the next sizes[i] shares (64 B each, share s said to be by registered key share_keys[s]).  Returns (share status
         bytes, tuple status bytes, the n aggregates, the n * bm_words bitmap words) — and the signer counts with want_counts.
-        seed32: see batch_collect_keyed_bitmap_randomized."""
+        seed32: see batch_collect_keyed_bitmap_randomized; optimistic: see batch_collect_keyed_bitmap_optimistic."""
         n, n_shares = len(messages), len(share_keys)
         assert len(sizes) == n and all(k >= 0 for k in sizes) and sum(sizes) == n_shares and len(shares) == n_shares * G1_BYTES
         msgs, off = pack_messages(messages)
@@ -549,7 +561,9 @@ class Engine:
         counts = (ctypes.c_uint32 * max(n, 1))()
         head = (self._h, msgs, off, bytes(shares), keys, share_off, n_shares, n, bm_words, flags)
         tail = (share_st, tuple_st, agg, bits, counts if want_counts else None)
-        if seed32 is not None:
+        if optimistic:
+            _check("bn254_batch_collect_keyed_bitmap_optimistic", self._lib.bn254_batch_collect_keyed_bitmap_optimistic(*head, *tail))
+        elif seed32 is not None:
             _check("bn254_batch_collect_keyed_bitmap_randomized", self._lib.bn254_batch_collect_keyed_bitmap_randomized(*head, bytes(seed32), *tail))
         else:
             _check("bn254_batch_collect_keyed_bitmap", self._lib.bn254_batch_collect_keyed_bitmap(*head, *tail))
@@ -561,6 +575,19 @@ class Engine:
         _check("bn254_batch_collect_keyed_bitmap_device",
                self._lib.bn254_batch_collect_keyed_bitmap_device(self._h, d_msgs, d_msg_off, d_shares, d_share_key, d_share_off, n_shares, n, bm_words,
                                                                  flags, d_share_status, d_tuple_status, d_agg_sigs, d_signer_bits, d_n_signers, stream))
+
+    def batch_collect_keyed_bitmap_optimistic(self, messages, shares, share_keys, sizes, bm_words, flags=0, want_counts=False):
+        """batch_collect_keyed_bitmap with ONE verify per tuple — the sum of its candidate shares against the sum of their keys — and the
+        shares checked one by one only where that fails (include/bn254_hip.h: bn254_batch_collect_keyed_bitmap_optimistic).  The same five
+        outputs, except that shares whose errors cancel within a passing tuple read 0."""
+        return Engine.batch_collect_keyed_bitmap(self, messages, shares, share_keys, sizes, bm_words, flags, want_counts, optimistic=True)
+
+    def batch_collect_keyed_bitmap_optimistic_device(self, d_msgs, d_msg_off, d_shares, d_share_key, d_share_off, n_shares, n, bm_words, d_share_status,
+                                                     d_tuple_status, d_agg_sigs, d_signer_bits, d_n_signers=None, flags=0, stream=None):
+        _check("bn254_batch_collect_keyed_bitmap_optimistic_device",
+               self._lib.bn254_batch_collect_keyed_bitmap_optimistic_device(self._h, d_msgs, d_msg_off, d_shares, d_share_key, d_share_off, n_shares, n,
+                                                                            bm_words, flags, d_share_status, d_tuple_status, d_agg_sigs, d_signer_bits,
+                                                                            d_n_signers, stream))
 
     def batch_collect_keyed_bitmap_randomized(self, messages, shares, share_keys, sizes, bm_words, seed32, flags=0, want_counts=False):
         """batch_collect_keyed_bitmap with the pairing checks of the shares combined, 64 shares of one key at a time, under random weights

@@ -300,6 +300,13 @@ struct ECDSA {
   static std::vector<KeyedAggregateResult> batch_aggregate_keyed_signers(const std::vector<ShareItem>& items, size_t n_keys, Engine& e = Engine::default_engine()) {
     return aggregate_keyed_signers_impl(items, n_keys, nullptr, 0, e);
   }
+  // the same with ONE verify per item — the sum of its signatures that pass every check short of the pairing, against the sum of their keys —
+  // and the signatures verified one by one only where that fails (include/bn254_hip.h: bn254_batch_collect_keyed_bitmap_optimistic).  No
+  // seed.  Signatures whose errors cancel within a passing item read 0 and are counted: a 0 there means "counted in a sum that verifies".
+  static std::vector<KeyedAggregateResult> batch_aggregate_keyed_signers_optimistic(const std::vector<ShareItem>& items, size_t n_keys,
+                                                                                    Engine& e = Engine::default_engine()) {
+    return aggregate_keyed_signers_impl(items, n_keys, nullptr, 0, e, true);
+  }
   // the same through the combined checks of 64 signatures of one key at a time, across the items of the call (include/bn254_hip.h:
   // bn254_batch_collect_keyed_bitmap_randomized): the same results; a non-zero status is exact, a zero is wrong with probability <= 2^-128 per
   // group (2^-64 with rand64) for a fresh SECRET seed
@@ -309,7 +316,7 @@ struct ECDSA {
     return aggregate_keyed_signers_impl(items, n_keys, seed.data(), rand64 ? BN254_FLAG_RAND64 : 0, e);
   }
   static std::vector<KeyedAggregateResult> aggregate_keyed_signers_impl(const std::vector<ShareItem>& items, size_t n_keys, const uint8_t* seed32, uint32_t flags,
-                                                                        Engine& e) {
+                                                                        Engine& e, bool optimistic = false) {
     const size_t n = items.size(), bm_words = (n_keys + 31) / 32 ? (n_keys + 31) / 32 : 1;
     std::vector<uint64_t> off(n + 1, 0), share_off(n + 1, 0);
     std::vector<uint8_t> msgs, shares;
@@ -328,7 +335,11 @@ struct ECDSA {
     std::vector<uint32_t> bits(n * bm_words + 1, 0);
     shares.resize(shares.size() + 1);
     keys.resize(keys.size() + 1);
-    if (seed32)
+    if (optimistic)
+      check_rc("bn254_batch_collect_keyed_bitmap_optimistic",
+               bn254_batch_collect_keyed_bitmap_optimistic(e.raw(), msgs.data(), off.data(), shares.data(), keys.data(), share_off.data(), share_off[n], n,
+                                                           bm_words, 0, share_st.data(), tuple_st.data(), agg.data(), bits.data(), nullptr));
+    else if (seed32)
       check_rc("bn254_batch_collect_keyed_bitmap_randomized",
                bn254_batch_collect_keyed_bitmap_randomized(e.raw(), msgs.data(), off.data(), shares.data(), keys.data(), share_off.data(), share_off[n], n,
                                                            bm_words, flags, seed32, share_st.data(), tuple_st.data(), agg.data(), bits.data(), nullptr));
@@ -349,6 +360,13 @@ struct ECDSA {
   static KeyedAggregateResult aggregate_keyed_signers(const std::vector<uint8_t>& message, const std::vector<Signature>& signatures,
                                                       const std::vector<uint32_t>& key_indices, size_t n_keys, Engine& e = Engine::default_engine()) {
     KeyedAggregateResult r = batch_aggregate_keyed_signers({ShareItem{message, signatures, key_indices}}, n_keys, e)[0];
+    check_status(r.status);
+    return r;
+  }
+  static KeyedAggregateResult aggregate_keyed_signers_optimistic(const std::vector<uint8_t>& message, const std::vector<Signature>& signatures,
+                                                                 const std::vector<uint32_t>& key_indices, size_t n_keys,
+                                                                 Engine& e = Engine::default_engine()) {
+    KeyedAggregateResult r = batch_aggregate_keyed_signers_optimistic({ShareItem{message, signatures, key_indices}}, n_keys, e)[0];
     check_status(r.status);
     return r;
   }

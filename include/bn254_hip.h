@@ -507,6 +507,73 @@ int bn254_batch_collect_keyed_bitmap_randomized_device(bn254_ctx *ctx, const uin
                                                        uint8_t *d_share_status, uint8_t *d_tuple_status, uint8_t *d_agg_sigs,
                                                        uint32_t *d_signer_bits, uint32_t *d_n_signers, void *stream);
 
+/* bn254_batch_collect_keyed_bitmap_optimistic[_device]: the exact collect's arguments and five outputs, with ONE verify per tuple.  The
+ * shares of a tuple share the message: if every share is good, their sum is the aggregate of the tuple's bitmap, and
+ *     e(H(m_i), sum_{j in row} pk_j) * e(sum_j share_j, -G2) == 1
+ * proves it.  Only a tuple whose sum fails needs its shares checked one by one.  No randomness, no seed.  The argument checks,
+ * BN254_E_MISALIGNED, the range rule, the fill of share_status with 2 and the _device conventions are those of
+ * bn254_batch_collect_keyed_bitmap[_device]: no host synchronisation, every buffer reserved before the first kernel; BN254_OPT_MAX_CHUNK
+ * slices the shares (of the exact fallback) and the tuples (of the hash and of the tuple check) as it does there.
+ *   1. PRE-CHECK.  Every share of an accepted tuple gets its status from rules 1-3 of the exact collect, with the call's flags: the decode
+ *      status; 2 for share_key >= n_keys, or the key's non-zero registration status; the tuple's hash status.  No pairing is computed.  A
+ *      share with status 0 here is a CANDIDATE.
+ *   2. ELIGIBILITY, decided per tuple on the device: at least BN254_OPT_COLLECT_OPT_MIN_TUPLE_SHARES candidates, and no two candidates that
+ *      name the same key index.  Honest traffic has no duplicates; a tuple with one goes the exact way, so "which duplicate is taken" never
+ *      arises on this route and the outcome does not depend on the order in which racing lanes claim bits.
+ *   3. PROVISIONAL RESULT of an eligible tuple: the bitmap row is its candidates' keys, the aggregate their sum, the count the popcount.  A
+ *      tuple with no candidate is final as it stands: empty row, identity, 0.
+ *   4. TUPLE CHECK.  Each eligible tuple gets one verify, e(H(m_i), sum_{j in row} pk_j) * e(agg_i, -G2) == 1: H(m_i) was hashed once, the
+ *      aggregate key comes from the bitmap call's subset tables, and the decode flags are 0 for this step — an identity aggregate is
+ *      legitimate (a key and its negation both signing).  The kernels are those of bn254_batch_verify_keyed_bitmap, so a small n is served
+ *      by the small-batch kernels of the routing table.
+ *   5. PASS.  The provisional outputs of a passing tuple are final, and its candidates keep status 0.
+ *   6. FALLBACK.  The tuples that fail the check, that have a duplicate, or that have fewer candidates than the per-tuple minimum go into a
+ *      device-side queue with their candidates.  The queued candidates are verified exactly by the keyed kernels (rule 4 of the exact
+ *      collect: 0 or 9) — the Miller loop and the final exponentiation run over queued shares only, though every share of a slice is decoded
+ *      and spread again; the tuples' rows are zeroed and select-and-sum runs again for these tuples only, with the exact call's rule.  Their
+ *      outputs are byte for byte the exact call's.
+ *   7. WHOLE-CALL ROUTING.  The call IS the exact call (same bytes) when no keys are registered or n_shares < BN254_OPT_COLLECT_OPT_MIN_SHARES.
+ * IDENTITY 2 OF THE EXACT COLLECT HOLDS UNCONDITIONALLY: bn254_batch_verify_keyed_bitmap with flags 0 on the call's own outputs returns 0 for
+ * every tuple with tuple_status == 0 — a passing tuple has just been verified so, a fallback tuple is the exact call's.
+ * EQUALITY WITH THE EXACT CALL: all five outputs equal bn254_batch_collect_keyed_bitmap's whenever no passing tuple contains a candidate that
+ * the exact call would have given 9.
+ * THE ONE DEVIATION: candidates whose errors cancel — share_a + D and share_b - D from two cooperating signers — read 0 and are counted here;
+ * the exact call gives both 9.  What comes out is still the valid aggregate share_a + share_b for bits a and b.  A status 0 inside a passing
+ * tuple therefore means "counted in a sum that verifies", not "individually valid"; a caller who needs per-share verdicts, for slashing say,
+ * uses the exact call.  Defining identity 1 of the exact collect holds only up to this deviation.
+ * Proof of possession of the registered keys is assumed, as everywhere in this family.
+ * Cost: with every share valid the Miller loop and the final exponentiation run over n tuples instead of n_shares shares; per share remain
+ * the decode of the pre-check, one G1 addition, and the decode and spread of the fallback's front end, which runs whether or not anything
+ * is queued (the host never learns).  With every tuple failing the call costs the exact call plus one n-item verify pass.
+ * Which call when (measured on an MI355X, tools/collect_throughput.py --optimistic, whole-call medians on a caller's stream, inputs
+ * resident, 256 keys).  Every share valid: 256 tuples x 171 shares 1.87 ms against the exact call's 8.24 and the
+ * randomised call's 8.71; 1 024 x 171 2.54 against 24.4 and 12.6; 2 048 x 171 2.85 against 44.6 and 18.4 (15.7 x, 6.5 x); 4 096 x 11 3.25
+ * against 8.29; 24 x 171 1.85 against 2.56; 9 x 171 (1 539 shares) 1.86 against 2.09 — but 6 x 171 ties (1.83) and 3 x 171 loses (1.84
+ * against 1.38): the call is one verify pass of n items plus 0.9 ms whatever the shares.  Over 4 096 keys 256 x 171 takes 6.71 ms against
+ * 8.15: the aggregate keys cost 5.2 ms there (the bitmap verify's sum, unchanged).  ANY tuple that goes the exact way costs the call one pass
+ * of the queue's lane-pair kernels, 4.9 ms whether it queues 11 shares or 5 000: one failing tuple takes 256 x 171 to 6.73 ms (still below
+ * the exact call), 2 048 x 171 to 7.78 (against 44.6), but 24 x 171 to 6.70 against the exact call's 2.56.  1 % wrong shares spread over
+ * tuples of 171 fail every tuple: 10.0 ms against 8.07 at 256 x 171, 47.9 against 44.3 at 2 048 x 171 — the exact call plus the optimistic
+ * pass.  Tuples of ONE or TWO shares lose (4 096 x 1: 3.33 against 2.51; 4 096 x 2: 3.31 against 2.54; 16 384 x 1: 5.47 against 4.60 — a
+ * tuple check per share or two is no saving), tuples of four win (4 096 x 4: 3.31 against 4.66); three were not measured.  A tuple that
+ * lists a key twice sends itself the exact way (1 x 4 096 over 256 keys: 6.89 against 2.62).  So: this call where tuples have four or more
+ * shares, almost all valid, and the call has 1 539 shares or more (BN254_OPT_COLLECT_OPT_MIN_SHARES); the exact call for small calls, for
+ * per-share verdicts, where more than the odd tuple is expected to hold a wrong share and the call is one the exact route serves in under
+ * 5 ms, and for calls made of one- or two-share tuples (the host-side thresholds cannot see the shape).  Not measured: between 1 026 and
+ * 1 539 shares, tuples of 3 and of 12 .. 170 shares, key sets between 256 and 4 096 keys, wrong shares over 4 096 keys beyond 256 x 171.
+ * Profiling: ms[0] = front end (hash, range rule, pre-check) and provisional sum, ms[1] = aggregate keys, ms[2] = the tuples' Miller loop and
+ * final exponentiation, ms[3] = exact fallback and re-sum.
+ * Out of scope: a randomised fallback, the multi-GPU layer, compressed shares. */
+int bn254_batch_collect_keyed_bitmap_optimistic(bn254_ctx *ctx, const uint8_t *msgs, const uint64_t *msg_off /* n+1 */,
+                                                const uint8_t *shares /* n_shares*64 */, const uint32_t *share_key /* n_shares */,
+                                                const uint64_t *share_off /* n+1 */, size_t n_shares, size_t n, size_t bm_words, uint32_t flags,
+                                                uint8_t *share_status /* n_shares */, uint8_t *tuple_status /* n */, uint8_t *agg_sigs /* n*64 */,
+                                                uint32_t *signer_bits /* n*bm_words */, uint32_t *n_signers /* n, or NULL */);
+int bn254_batch_collect_keyed_bitmap_optimistic_device(bn254_ctx *ctx, const uint8_t *d_msgs, const uint64_t *d_msg_off, const uint8_t *d_shares,
+                                                       const uint32_t *d_share_key, const uint64_t *d_share_off, size_t n_shares, size_t n,
+                                                       size_t bm_words, uint32_t flags, uint8_t *d_share_status, uint8_t *d_tuple_status,
+                                                       uint8_t *d_agg_sigs, uint32_t *d_signer_bits, uint32_t *d_n_signers, void *stream);
+
 /* compressed wire formats (src/utils.rs:84-104, :130-158): out = uncompressed point, status as
  * bn::G1::from_compressed / bn::G2::from_compressed report through src/types.rs:91-93, :233-237, checked in the order
  * those decoders work (an input with several faults reports the first):
@@ -597,6 +664,18 @@ int bn254_ctx_set_profiling(bn254_ctx *ctx, int enabled);
                                                 down): groups are per key, so few shares per key mean padded groups.  Default 42, the smallest measured
                                                 ratio at which the call wins (175 104 shares over 4 096 keys; at 10 per key it loses;
                                                 nothing measured in between); 0 = no lower bound */
+#define BN254_OPT_COLLECT_OPT_MIN_SHARES 40 /* bn254_batch_collect_keyed_bitmap_optimistic: calls with fewer shares take the exact collect (same
+                                              bytes).  Default 1539, the smallest measured size from which the call wins with every share
+                                              valid (tuples of 171 shares over 256 keys: 1.86 ms against 2.09; at 1 026 shares it ties, at 513
+                                              it loses; nothing measured in between).  Calls made of one- or two-share tuples lose at every
+                                              size measured, which a count of shares cannot see; 0 = no lower bound */
+#define BN254_OPT_COLLECT_OPT_MIN_TUPLE_SHARES 41 /* ... and, per tuple, tuples with fewer candidates go the exact way.  Default 1: every tuple
+                                                    with a candidate is checked.  Measured: a tuple sent the exact way costs the call one pass
+                                                    of the queue's kernels, 4.9 ms whatever the queue's length, while the check of a short
+                                                    tuple's sum adds nothing measurable to the pass over the other tuples — so no measured
+                                                    size favours a higher value (calls of ONLY one- or two-share tuples lose 0.8 ms to the
+                                                    exact call as a whole; tuples of four win).  The option stays for callers who want short
+                                                    tuples verified share by share; 0 and 1 mean the same */
 int bn254_ctx_set_option(bn254_ctx *ctx, int option, int value);
 /* per-kernel times of the last verify-shaped call with profiling on (HIP events on the call's stream):
  * ms[0] decode, ms[1] hash-to-G1, ms[2] Miller loop, ms[3] final exponentiation.  The host-pointer bn254_batch_verify runs
@@ -608,7 +687,10 @@ int bn254_ctx_set_option(bn254_ctx *ctx, int option, int value);
  * collect_keyed_bitmap ms[0] = decode + hash-to-G1 (once per tuple) + spread, ms[1] = select-and-sum (it runs last), ms[2] Miller loop,
  * ms[3] final exponentiation (the last slice's; the hash counts in ms[0] only when the call ran in one piece);
  * collect_keyed_bitmap_randomized on its randomised route the same four with ms[2] = grouping by key + scalar ladders, ms[3] = group checks +
- * exact re-checks of failed groups. */
+ * exact re-checks of failed groups;
+ * collect_keyed_bitmap_optimistic on its optimistic route ms[0] = front end (hash, range rule, pre-check) + provisional sum, ms[1] = the
+ * aggregate keys, ms[2] = the tuples' Miller loop and final exponentiation, ms[3] = exact fallback + re-sum (a call whose tuples are checked
+ * in several pieces: ms[1] runs from the provisional sum to the last piece's keys). */
 int bn254_ctx_last_kernel_ms(bn254_ctx *ctx, float ms[4]);
 /* with BN254_OPT_CLOCK_PROBE on: achieved shader clock in MHz of the lane-pair Miller kernels [0], final exponentiations [1] and probe
  * kernels (bn254_probe_issue_rate, bn254_probe_leaf_floor) [2] launched on this context SINCE THE PREVIOUS CALL of this function (or
@@ -791,6 +873,10 @@ int bn254_debug_agg_rand_sums(bn254_ctx *ctx, uint64_t dims[2], size_t group_cap
  * the randomised route, groups checked, groups that failed, shares re-checked exactly}; all 0 when the call took the exact route.
  * Synchronises the device. */
 int bn254_debug_collect_rand_last(bn254_ctx *ctx, uint64_t out[4]);
+/* what the last bn254_batch_collect_keyed_bitmap_optimistic[_device] did, counted by the call's own kernels and summed over its slices: out =
+ * {tuples checked optimistically, tuples that passed, tuples sent to the exact route (failed, a duplicate, or below the per-tuple minimum),
+ * shares verified exactly}; all 0 when the call as a whole took the exact route.  Synchronises the device. */
+int bn254_debug_collect_opt_last(bn254_ctx *ctx, uint64_t out[4]);
 /* what the last bn254_batch_verify_keyed_bitmap_randomized[_device] did (its last slice): out = {1 if it took the randomised route, groups that
  * reached the check, table pairs of all group checks (S_g's included), failed groups, tuples re-checked, groups of one tuple (r = 1)}; all 0
  * when it took the exact route.  Synchronises the device. */

@@ -14,8 +14,14 @@ ms[3] final exponentiation).  --wave-min sweeps BN254_OPT_COLLECT_WAVE_MIN_SHARE
 whole-call median, per-stage times (ms[2] = grouping + scalar ladders, ms[3] = group checks + exact re-checks), the debug hook's counters, and
 whether all five outputs are the exact call's bytes.  --keys sets the size of the registered set; --bad-percent P corrupts every (100 / P)-th
 share (a valid point, the neighbour's signature), which prices failed groups — route (b) is then left out, its filter assumes valid shares.
-A library without the randomised call (BN254_LIB = an older build, the baseline of an A/B) runs the other legs.
-    python tools/collect_throughput.py [out.jsonl] [--reps R] [--wave-min W ...] [--rand] [--keys K] [--bad-percent P] [--note TEXT] [shape ...]   shape = n:k"""
+--optimistic adds bn254_batch_collect_keyed_bitmap_optimistic_device with its route forced (options 40 = 0, 41 = 0): whole-call median,
+per-stage times (ms[0] = front end + provisional sum, ms[1] = aggregate keys, ms[2] = the tuples' Miller loop and final exponentiation,
+ms[3] = exact fallback + re-sum), the debug hook's counters, and whether all five outputs are the exact call's bytes.  --bad-one-tuple puts
+the wrong shares of --bad-percent into tuple 0 alone (at most its k shares; each the share at its position in the NEXT tuple, so that the
+tuple's sum is wrong too).  --skip-b leaves route (b) out.
+A library without the randomised or the optimistic call (BN254_LIB = an older build, the baseline of an A/B) runs the other legs.
+    python tools/collect_throughput.py [out.jsonl] [--reps R] [--wave-min W ...] [--rand] [--optimistic] [--keys K] [--bad-percent P]
+                                       [--bad-one-tuple] [--skip-b] [--note TEXT] [shape ...]   shape = n:k"""
 import argparse
 import ctypes
 import hashlib
@@ -29,6 +35,8 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402  (first: one HIP runtime per process)
 import bn254_amd  # noqa: E402
 from bn254_amd import _native  # noqa: E402
+from bn254_amd.engine import (COLLECT_OPT_MIN_SHARES_DEFAULT, COLLECT_OPT_MIN_TUPLE_SHARES_DEFAULT, OPT_COLLECT_OPT_MIN_SHARES,  # noqa: E402
+                              OPT_COLLECT_OPT_MIN_TUPLE_SHARES)
 from bn254_amd.engine import (FLAG_RAND64, OPT_COLLECT_RAND_MIN_PER_KEY, OPT_COLLECT_RAND_MIN_SHARES, OPT_COLLECT_WAVE_MIN_SHARES,  # noqa: E402
                               COLLECT_RAND_MIN_PER_KEY_DEFAULT, COLLECT_RAND_MIN_SHARES_DEFAULT)
 from tests.datagen import sk_bytes  # noqa: E402
@@ -67,6 +75,9 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--wave-min", type=int, nargs="*", default=[])
     ap.add_argument("--rand", action="store_true")
+    ap.add_argument("--optimistic", action="store_true")
+    ap.add_argument("--bad-one-tuple", action="store_true")
+    ap.add_argument("--skip-b", action="store_true")
     ap.add_argument("--keys", type=int, default=256)
     ap.add_argument("--bad-percent", type=float, default=0.0)
     ap.add_argument("--note", default=None, help="recorded with every line, e.g. which build ran")
@@ -88,6 +99,7 @@ def main():
     assert st == bytes(N_KEYS) and eng.register_keys(pool) == bytes(N_KEYS)
     bm_words = (N_KEYS + 31) // 32
     have_rand = a.rand and hasattr(lib, "bn254_batch_collect_keyed_bitmap_randomized_device")
+    have_opt = a.optimistic and hasattr(lib, "bn254_batch_collect_keyed_bitmap_optimistic_device")
     seed = hashlib.sha256(b"collect/tp/seed").digest()
 
     for n, k in shapes:
@@ -101,8 +113,13 @@ def main():
         if a.bad_percent > 0:
             every = max(int(round(100.0 / a.bad_percent)), 2)
             sh = bytearray(shares)
-            for s in range(every // 2, n_shares, every):
+            where = range(every // 2, n_shares, every)
+            if a.bad_one_tuple:
+                where = range(min(len(where), k))
+            for s in where:
                 o = s + 1 if s + 1 < n_shares else s - 1
+                if a.bad_one_tuple and n > 1:
+                    o = s + k
                 sh[64 * s:64 * s + 64] = shares[64 * o:64 * o + 64]
                 n_bad += 1
             shares = bytes(sh)
@@ -136,11 +153,16 @@ def main():
                                                                           d_soff.data_ptr(), n_shares, n, bm_words, flags, seed, d_sst.data_ptr(),
                                                                           d_tst.data_ptr(), d_agg.data_ptr(), d_bits.data_ptr(), d_cnt.data_ptr(), stream))
 
+        def collect_opt():
+            _check(lib.bn254_batch_collect_keyed_bitmap_optimistic_device(h, d_msgs.data_ptr(), d_moff.data_ptr(), d_shares.data_ptr(), d_keys.data_ptr(),
+                                                                          d_soff.data_ptr(), n_shares, n, bm_words, 0, d_sst.data_ptr(), d_tst.data_ptr(),
+                                                                          d_agg.data_ptr(), d_bits.data_ptr(), d_cnt.data_ptr(), stream))
+
         def outputs():
             torch.cuda.synchronize()
             return tuple(t.cpu().numpy().tobytes()[:m] for t, m in ((d_sst, n_shares), (d_tst, n), (d_agg, 64 * n), (d_bits, 4 * bm_words * n), (d_cnt, 4 * n)))
 
-        if n_bad:
+        if n_bad or a.skip_b:
             def parent_route():   # noqa: F811  (its filter assumes that every share passes)
                 keyed()
         for fn in (collect, parent_route, collect, parent_route):
@@ -192,6 +214,24 @@ def main():
                               "hook": hook, "same_bytes_as_exact": bool(same_bytes)}
             eng.set_option(OPT_COLLECT_RAND_MIN_SHARES, COLLECT_RAND_MIN_SHARES_DEFAULT)
             eng.set_option(OPT_COLLECT_RAND_MIN_PER_KEY, COLLECT_RAND_MIN_PER_KEY_DEFAULT)
+        optimistic = {}
+        if have_opt:
+            eng.set_option(OPT_COLLECT_OPT_MIN_SHARES, 0)
+            eng.set_option(OPT_COLLECT_OPT_MIN_TUPLE_SHARES, 0)
+            collect_opt()
+            collect_opt()
+            same_bytes = outputs() == exact_out
+            hook = eng.debug_collect_opt_last()
+            t = [timed(collect_opt, ts) for _ in range(a.reps)]
+            eng.set_profiling(True)
+            collect_opt()
+            kms = eng.last_kernel_ms()
+            eng.set_profiling(False)
+            optimistic = {"ms": round(statistics.median(t), 3), "min_ms": round(min(t), 3), "max_ms": round(max(t), 3),
+                          "stages_ms": [round(kms[x], 3) for x in ("decode", "hash_to_g1", "miller_loop", "final_exp")],
+                          "hook": hook, "same_bytes_as_exact": bool(same_bytes)}
+            eng.set_option(OPT_COLLECT_OPT_MIN_SHARES, COLLECT_OPT_MIN_SHARES_DEFAULT)
+            eng.set_option(OPT_COLLECT_OPT_MIN_TUPLE_SHARES, COLLECT_OPT_MIN_TUPLE_SHARES_DEFAULT)
         med = {x: statistics.median(v) for x, v in ms.items()}
         row = {"shape": "%dx%d" % (n, k), "n": n, "shares_per_tuple": k, "n_shares": n_shares, "mean_signers": round(float(counts.mean()), 1),
                "a_ms": round(med["a"], 3), "a_min_ms": round(min(ms["a"]), 3), "a_max_ms": round(max(ms["a"]), 3),
@@ -200,11 +240,16 @@ def main():
                "a_not_slower_beyond_spread": max(ms["a"]) <= min(ms["b"]),
                "stages_ms": stages, "stage_slots": {"a_collect": "decode+hash+spread, select-and-sum, miller, final_exp", "keyed_verify": "decode, hash, miller, final_exp"},
                "wave_min_sweep_ms": sweep, "same_aggregates_all_valid": bool(same), **box}
+        if a.skip_b and not n_bad:
+            row.update({"b_ms": None, "b_min_ms": None, "b_max_ms": None, "b_over_a": None, "a_not_slower_beyond_spread": None, "same_aggregates_all_valid": None})
         if n_bad:
-            row.update({"bad_shares": n_bad, "b_ms": None, "b_min_ms": None, "b_max_ms": None, "b_over_a": None, "a_not_slower_beyond_spread": None})
+            row.update({"bad_shares": n_bad, "bad_in_one_tuple": bool(a.bad_one_tuple), "b_ms": None, "b_min_ms": None, "b_max_ms": None, "b_over_a": None, "a_not_slower_beyond_spread": None})
         if have_rand:
             row["randomized"] = rand
             row["rand_stage_slots"] = "decode+hash+spread, select-and-sum, grouping+ladders, group checks+re-checks"
+        if have_opt:
+            row["optimistic"] = optimistic
+            row["optimistic_stage_slots"] = "front end+provisional sum, aggregate keys, tuples' miller+final_exp, exact fallback+re-sum"
         print(json.dumps(row), file=out, flush=True)
         del d_msgs, d_moff, d_rep, d_roff, d_shares, d_keys, d_soff, d_sst, d_tst, d_agg, d_bits, d_cnt, d_kst
 

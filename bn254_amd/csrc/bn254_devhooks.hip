@@ -150,10 +150,59 @@ __global__ void __launch_bounds__(256) k_issue_probe(uint32_t* out, uint32_t see
     p[0] += clock64() - clk0; p[1] += wall_clock64() - wall0;
   }
 }
-
+// test hook: entries first .. first + n - 1 of a pool / table of the aggregate verify as canonical bytes (zeros under the identity flag) and
+// their raw status bytes.  The words are read under the stored-word contract of bn254_pooltab.h (|value| <= q), which fp_to_be accepts.
+KERNEL_SMALL void k_debug_read_pool(Pool pool, size_t first, size_t n, uint8_t* out, uint8_t* flags) {
+  size_t i = (size_t)blockIdx.x * BN_WAVE + threadIdx.x;
+  if (i >= n) return;
+  const size_t j = first + i;
+  const uint8_t st = pool.st[j];
+  if (pool.g2) {
+    G2Affine q;
+    q.x.c0 = pool_load_fp(pool, 0, j); q.x.c1 = pool_load_fp(pool, 1, j); q.y.c0 = pool_load_fp(pool, 2, j); q.y.c1 = pool_load_fp(pool, 3, j);
+    q.inf = (st & 0x80) != 0;
+    encode_g2(out + 128 * i, q);
+  } else {
+    G1Affine p;
+    p.x = pool_load_fp(pool, 0, j); p.y = pool_load_fp(pool, 1, j);
+    p.inf = (st & 0x80) != 0;
+    encode_g1(out + 64 * i, p);
+  }
+  flags[i] = st;
+}
 
 extern "C" {
 
+// the tables of the registered pools as they stand on the device (include/bn254_hip.h); which = -1: the query form
+int bn254_debug_agg_tables(bn254_ctx* c, int which, size_t first, size_t count, uint8_t* points, uint8_t* flags) {
+  if (!c || which < -1 || which > 7 || !points) return BN254_E_BAD_ARGUMENT;
+  const AggTables& t = c->reg_pools;
+  if (!t.valid) return BN254_E_BAD_ARGUMENT;          // nothing registered, or a call with raw pools has overwritten the buffers since
+  HIP_TRY(hipSetDevice(c->device));
+  { int rc_ = ctx_quiesce(c); if (rc_) return rc_; }
+  if (which < 0) {
+    const uint64_t q[5] = {(uint64_t)t.n_groups, (uint64_t)t.groups4, (uint64_t)t.wide2, (uint64_t)t.wide1, (uint64_t)t.t4_builder};
+    memcpy(points, q, sizeof q);
+    return 0;
+  }
+  if (!flags) return BN254_E_BAD_ARGUMENT;
+  // entries of each table; 0 = not built for this registration (the buffer may still hold an older registration's table)
+  const size_t entries[8] = {t.n_signers, t.n_msgs * t.n_signers, t.n_msgs, t.n_groups * 256, t.n_msgs * t.groups4 * 16,
+                             t.wide2 ? ((t.n_groups + 1) / 2) * 65536 : 0, t.wide1 ? t.n_msgs * t.n_groups * 256 : 0,
+                             t.t4_builder == 1 ? t.n_msgs * 2 * t.groups4 * 4 : 0};
+  const size_t total = entries[which];
+  const Pool& p = c->pool[which];
+  if (total == 0 || !p.planes || total > p.stride) return BN254_E_BAD_ARGUMENT;
+  if (first > total || count > total - first) return BN254_E_BAD_ARGUMENT;
+  if (count == 0) return 0;
+  const size_t sz = p.g2 ? 128 : 64;
+  HostStaging st(c);
+  uint8_t *d_out = st.out(0, count * sz, points), *d_flags = st.out(1, count, flags);
+  if (!st.ok()) return st.rc;
+  k_debug_read_pool<<<grid_for(count), BN_WAVE, 0, c->stream>>>(p, first, count, d_out, d_flags);
+  HIP_TRY(hipGetLastError());
+  return st.finish();
+}
 // the routing table of the context (bn254_ws.h: bn_route_table) — tests iterate its boundaries
 // what the key deduplication of the last bn254_batch_verify_device decided on the device (bn254_keydedup.hip): out = {ran, distinct keys D,
 // flags (1 probe overflow, 2 degenerate line), items of the keyed Miller kernel, items of the generic one}; ran = 0: the call did not take

@@ -16,6 +16,7 @@
 
 using namespace bn254;
 
+#include "bn254_pooltab.h"
 #include "bn254_ws.h"
 #include "bn254_lane.h"
 #include "bn254_host.h"
@@ -182,182 +183,44 @@ KERNEL void k_pool_decode_g2(const uint8_t* pts, size_t n, uint32_t flags, Pool 
 // x 256 affine points, 4.7 MB for 1024 signers; ~4 additions + one inversion per entry) and a tuple adds ONE table entry per
 // group — 128 additions instead of the ~512 of a dense list (k_aggregate_pair).  Entry j = group * 256 + mask; a pool entry
 // that failed to decode counts as the identity here (the tuples that name it carry its status anyway).
+// The arithmetic of every builder below — one lane's work — is bn254_pooltab.h's (compiled for the host by the CPU suite, with the
+// stored-word contract of the tables); the kernels only name their lane.
 KERNEL void k_pool_subsets_g2(Pool pk_pool, size_t n_signers, size_t n_groups, Pool sub) {
-  const size_t j = (size_t)blockIdx.x * BN_WAVE + threadIdx.x;
-  const bool live = j < n_groups * 256;
-  const size_t g = (live ? j : 0) >> 8;
-  const unsigned mask = (unsigned)(j & 255u);
-  G2Jac acc;
-  jac_set_identity(acc);
-  for (int b = 0; b < 8; ++b) {                      // wave-uniform: jac_accumulate votes across the wave
-    const size_t sgn = g * 8 + b;
-    const size_t ss = sgn < n_signers ? sgn : 0;
-    const uint8_t st = pk_pool.st[ss];
-    G2Affine p;
-    p.x.c0 = pool_load_fp(pk_pool, 0, ss); p.x.c1 = pool_load_fp(pk_pool, 1, ss);
-    p.y.c0 = pool_load_fp(pk_pool, 2, ss); p.y.c1 = pool_load_fp(pk_pool, 3, ss);
-    p.inf = !live || !((mask >> b) & 1u) || sgn >= n_signers || st != 0;       // st: 0x80 = identity entry, low bits = decode error
-    jac_accumulate(acc, p);
-  }
-  G2Affine a;
-  jac_to_affine(a, acc);
-  if (!live) return;
-  pool_store_fp(sub, 0, j, a.x.c0); pool_store_fp(sub, 1, j, a.x.c1);
-  pool_store_fp(sub, 2, j, a.y.c0); pool_store_fp(sub, 3, j, a.y.c1);
-  sub.st[j] = a.inf ? 0x80 : 0;
+  pt_subsets_g2_lane((size_t)blockIdx.x * BN_WAVE + threadIdx.x, pk_pool, n_signers, n_groups, sub);
 }
 // The same for the signatures, per message: the sums of the 15 non-empty subsets of every group of 4 consecutive signers of
 // message m (entry j = (m * groups4 + group) * 16 + mask; 302 MB for 1024 x 1024 — HBM is what this machine has), so that a
 // tuple adds one table entry per group of 4 signers (256 instead of ~512 additions; 4 bits, not 8: an entry costs two additions
 // and an inversion to build and is used by ~n / n_msgs tuples only).
 KERNEL_SMALL void k_pool_subsets_g1(Pool sig_pool, size_t n_signers, size_t groups4, size_t n_msgs, Pool sub) {
-  const size_t j = (size_t)blockIdx.x * BN_WAVE + threadIdx.x;
-  const bool live = j < n_msgs * groups4 * 16;
-  const size_t jj = live ? j : 0;
-  const unsigned mask = (unsigned)(jj & 15u);
-  const size_t g = (jj >> 4) % groups4, m = (jj >> 4) / groups4;
-  G1Jac acc;
-  jac_set_identity(acc);
-  for (int b = 0; b < 4; ++b) {                      // wave-uniform
-    const size_t sgn = g * 4 + b;
-    const size_t sj = m * n_signers + (sgn < n_signers ? sgn : 0);
-    const uint8_t st = sig_pool.st[sj];
-    G1Affine p;
-    p.x = pool_load_fp(sig_pool, 0, sj); p.y = pool_load_fp(sig_pool, 1, sj);
-    p.inf = !live || !((mask >> b) & 1u) || sgn >= n_signers || st != 0;
-    jac_accumulate(acc, p);
-  }
-  G1Affine a;
-  jac_to_affine(a, acc);
-  if (!live) return;
-  pool_store_fp(sub, 0, j, a.x); pool_store_fp(sub, 1, j, a.y);
-  sub.st[j] = a.inf ? 0x80 : 0;
+  pt_subsets_g1_lane((size_t)blockIdx.x * BN_WAVE + threadIdx.x, sig_pool, n_signers, groups4, n_msgs, sub);
 }
 // ---- WIDER subset tables for the largest aggregate batches (BN254_OPT_AGG_WIDE_MIN_TUPLES) ---------------------------------------------
 // k_aggregate_pair adds one table entry per window of signers; twice the window is half the additions.  From a table of windows of w
 // signers one of 2w signers is its "outer sum": T2w[hi * 2^w + lo] = Tw[group 2k][lo] + Tw[group 2k + 1][hi] — ONE affine addition per
 // entry, 2^(2w) entries per doubled group: keys 8 -> 16 signers per entry (n_signers / 16 x 65 536 entries, 671 MB for 1 024 signers:
 // HBM is what this machine has), signatures per message 4 -> 8.  An affine addition needs 1 / (x_B - x_A); a lane owns one `hi` and
-// walks its `lo` values in batches of 8 whose denominators share ONE inversion (Montgomery's trick: prefix products up, the inverse
-// peeled off on the way down; the B points are re-read from the source table, an L2 hit, instead of being kept in registers): 2
+// walks its `lo` values in batches of 8 whose denominators share ONE inversion (bn254_pooltab.h: pool_widen_lane): 2
 // products + 1 square for the chord, 3 products for the trick, an eighth of an inversion — ~16 products per entry where accumulate +
-// jac_to_affine costs ~100.  Entries with an identity operand are copies; the rare lo with x_B = x_A (B = +-A: a pool that holds a
-// point twice, or a point and its negative) takes the complete Jacobian formula and an inversion of its own.
-__device__ __forceinline__ void pool_load_aff(const Pool& p, size_t j, G1Affine& q) { q.x = pool_load_fp(p, 0, j); q.y = pool_load_fp(p, 1, j); q.inf = (p.st[j] & 0x80) != 0; }
-__device__ __forceinline__ void pool_load_aff(const Pool& p, size_t j, G2Affine& q) {
-  q.x.c0 = pool_load_fp(p, 0, j); q.x.c1 = pool_load_fp(p, 1, j); q.y.c0 = pool_load_fp(p, 2, j); q.y.c1 = pool_load_fp(p, 3, j);
-  q.inf = (p.st[j] & 0x80) != 0;
-}
-__device__ __forceinline__ void pool_store_aff(const Pool& p, size_t j, const G1Affine& q) { pool_store_fp(p, 0, j, q.x); pool_store_fp(p, 1, j, q.y); p.st[j] = q.inf ? 0x80 : 0; }
-__device__ __forceinline__ void pool_store_aff(const Pool& p, size_t j, const G2Affine& q) {
-  pool_store_fp(p, 0, j, q.x.c0); pool_store_fp(p, 1, j, q.x.c1); pool_store_fp(p, 2, j, q.y.c0); pool_store_fp(p, 3, j, q.y.c1);
-  p.st[j] = q.inf ? 0x80 : 0;
-}
-// one lane: dst[dst0 + lo] = src[b0 + lo] + A for NLO consecutive lo (an entry of src may be the identity: the empty subset, or a sum that
-// cancelled)
-template <class F> __device__ __forceinline__ void aff_select(Affine<F>& r, bool c, const Affine<F>& a, const Affine<F>& b) {
-  r.x = f_select(c, a.x, b.x); r.y = f_select(c, a.y, b.y); r.inf = c ? a.inf : b.inf;
-}
-template <class F, int NLO, int BATCH = 8> __device__ __forceinline__ void pool_widen_lane(bool live, const Pool& src, size_t b0, Affine<F> A, const Pool& dst, size_t dst0) {
-  static_assert(NLO % BATCH == 0, "whole batches");
-  for (int base = 0; base < NLO; base += BATCH) {
-    F d[BATCH], pre[BATCH];
-    bool exc[BATCH];
-#pragma unroll
-    for (int i = 0; i < BATCH; ++i) {
-      Affine<F> B;
-      pool_load_aff(src, b0 + base + i, B);
-      d[i] = f_norm(f_sub(B.x, A.x));
-      const bool zero = f_is_zero(d[i]);
-      exc[i] = zero && !A.inf && !B.inf;              // B = +-A
-      if (zero || A.inf || B.inf) f_set_one(d[i]);    // keeps the batch's product invertible; the chord of such an entry is not used
-      pre[i] = i ? f_mul(pre[i - 1], d[i]) : d[i];
-    }
-    F inv = f_inv(pre[BATCH - 1]);
-#pragma unroll
-    for (int i = BATCH - 1; i >= 0; --i) {
-      const F dinv = i ? f_mul(inv, pre[i - 1]) : inv;
-      if (i) inv = f_mul(inv, d[i]);
-      Affine<F> B, R;
-      pool_load_aff(src, b0 + base + i, B);
-      aff_add_given_inv(R, A, B, dinv);
-      aff_select(R, B.inf, A, R);                     // identity operands: copies
-      aff_select(R, A.inf, B, R);
-      if (BN_WAVE_ANY(exc[i])) {                      // rare: the complete formula (and an inversion of its own) for the lanes that met B = +-A
-        Jac<F> J;
-        Affine<F> Bc = B, C;
-        jac_from_affine(J, A);
-        Bc.inf = !exc[i];                             // the other lanes add nothing here
-        jac_madd(J, J, Bc);
-        jac_to_affine(C, J);
-        if (exc[i]) R = C;
-      }
-      if (live) pool_store_aff(dst, dst0 + base + i, R);
-    }
-  }
-}
-// keys: T16[k][hi * 256 + lo] = T8[2k][lo] + T8[2k + 1][hi]; lane = (k, hi, block of 32 lo values) — 2 048 waves for 1 024 signers.  A
-// chunk whose second group does not exist (an odd number of groups) only ever sees hi = 0.
-#define BN_WIDEN_G2_NLO 32
+// jac_to_affine costs ~100.
+// keys: T16[k][hi * 256 + lo] = T8[2k][lo] + T8[2k + 1][hi]; lane = (k, hi, block of 32 lo values) — 2 048 waves for 1 024 signers
 KERNEL void k_pool_widen_g2(Pool t8, size_t n_groups, size_t n_chunks, Pool t16) {
-  const size_t lane = (size_t)blockIdx.x * BN_WAVE + threadIdx.x;
-  constexpr size_t BLK = 256 / BN_WIDEN_G2_NLO;
-  const bool live = lane < n_chunks * 256 * BLK;
-  const size_t ll = live ? lane : 0, blk = ll % BLK, hi = (ll / BLK) & 255u, k = ll / (BLK * 256);
-  const bool has_hi = 2 * k + 1 < n_groups;
-  G2Affine A;
-  pool_load_aff(t8, (has_hi ? 2 * k + 1 : 2 * k) * 256 + hi, A);
-  A.inf = A.inf || !has_hi || hi == 0;
-  if (A.inf) g2_set_generator_keep_inf(A);
-  pool_widen_lane<Fp2, BN_WIDEN_G2_NLO>(live, t8, 2 * k * 256 + blk * BN_WIDEN_G2_NLO, A, t16, k * 65536 + hi * 256 + blk * BN_WIDEN_G2_NLO);
+  pt_widen_g2_lane((size_t)blockIdx.x * BN_WAVE + threadIdx.x, t8, n_groups, n_chunks, t16);
 }
 // signatures, per message: T8[m][g][hi * 16 + lo] = T4[m][2g][lo] + T4[m][2g + 1][hi]; lane = (m, g, hi)
 KERNEL_SMALL void k_pool_widen_g1(Pool t4, size_t groups4, size_t n_groups, size_t n_msgs, Pool t8) {
-  const size_t lane = (size_t)blockIdx.x * BN_WAVE + threadIdx.x;
-  const bool live = lane < n_msgs * n_groups * 16;
-  const size_t ll = live ? lane : 0, hi = ll & 15u, g = (ll >> 4) % n_groups, m = (ll >> 4) / n_groups;
-  G1Affine A;
-  pool_load_aff(t4, (m * groups4 + 2 * g + 1) * 16 + hi, A);
-  A.inf = A.inf || hi == 0;
-  if (A.inf) { A.x = fp_load_const(C_G1_GEN[0]); A.y = fp_load_const(C_G1_GEN[1]); }
-  pool_widen_lane<Fp, 16>(live, t4, (m * groups4 + 2 * g) * 16, A, t8, (m * n_groups + g) * 256 + hi * 16);
+  pt_widen_g1_lane((size_t)blockIdx.x * BN_WAVE + threadIdx.x, t4, groups4, n_groups, n_msgs, t8);
 }
 // The 4-signer signature tables themselves are built the same way, in two steps (round 5: 4.6 -> ~1.1 ms per 1 024 x 1 024 pool):
 //   k_pool_pairs_g1: T2[m][pair][mask] = {O, s0, s1, s0 + s1} for every pair of consecutive signers (one complete addition and one
 //                    inversion per PAIR), then  k_pool_quads_g1: T4[hi * 4 + lo] = T2[pair 2g][lo] + T2[pair 2g + 1][hi], batches of 4.
-// k_pool_subsets_g1 above (four accumulations and an inversion per ENTRY) stays as the fallback when the pair table cannot be allocated.
+// k_pool_subsets_g1 above (four accumulations and an inversion per ENTRY) stays as the fallback when the pair table cannot be allocated
+// (and as the route of BN254_OPT_AGG_T4_ROUTE = 1).
 KERNEL_SMALL void k_pool_pairs_g1(Pool sig_pool, size_t n_signers, size_t groups2, size_t n_msgs, Pool t2) {
-  const size_t lane = (size_t)blockIdx.x * BN_WAVE + threadIdx.x;
-  const bool live = lane < n_msgs * groups2;
-  const size_t ll = live ? lane : 0, g = ll % groups2, m = ll / groups2;
-  G1Affine s[2];
-#pragma unroll
-  for (int b = 0; b < 2; ++b) {
-    const size_t sgn = 2 * g + b, sj = m * n_signers + (sgn < n_signers ? sgn : 0);
-    s[b].x = pool_load_fp(sig_pool, 0, sj); s[b].y = pool_load_fp(sig_pool, 1, sj);
-    s[b].inf = sgn >= n_signers || sig_pool.st[sj] != 0;          // st: 0x80 = identity entry, low bits = decode error (counts as the identity here)
-    if (s[b].inf) { s[b].x = fp_load_const(C_G1_GEN[0]); s[b].y = fp_load_const(C_G1_GEN[1]); }
-  }
-  G1Jac J;
-  G1Affine sum, none;
-  jac_from_affine(J, s[0]);
-  jac_madd(J, J, s[1]);
-  jac_to_affine(sum, J);
-  none.x = fp_zero(); none.y = fp_zero(); none.inf = true;
-  if (!live) return;
-  pool_store_aff(t2, 4 * lane + 0, none);
-  pool_store_aff(t2, 4 * lane + 1, s[0]);
-  pool_store_aff(t2, 4 * lane + 2, s[1]);
-  pool_store_aff(t2, 4 * lane + 3, sum);
+  pt_pairs_g1_lane((size_t)blockIdx.x * BN_WAVE + threadIdx.x, sig_pool, n_signers, groups2, n_msgs, t2);
 }
 KERNEL_SMALL void k_pool_quads_g1(Pool t2, size_t groups2, size_t groups4, size_t n_msgs, Pool t4) {
-  const size_t lane = (size_t)blockIdx.x * BN_WAVE + threadIdx.x;
-  const bool live = lane < n_msgs * groups4 * 4;
-  const size_t ll = live ? lane : 0, hi = ll & 3u, g = (ll >> 2) % groups4, m = (ll >> 2) / groups4;
-  G1Affine A;
-  pool_load_aff(t2, (m * groups2 + 2 * g + 1) * 4 + hi, A);
-  if (A.inf) { A.x = fp_load_const(C_G1_GEN[0]); A.y = fp_load_const(C_G1_GEN[1]); }
-  pool_widen_lane<Fp, 4, 4>(live, t2, (m * groups2 + 2 * g) * 4, A, t4, (m * groups4 + g) * 16 + hi * 4);
+  pt_quads_g1_lane((size_t)blockIdx.x * BN_WAVE + threadIdx.x, t2, groups2, groups4, n_msgs, t4);
 }
 // tuple i: agg_sig = sum_s sig_pool[msg_i * S + s], agg_pk = sum_s pk_pool[s] over its signer list
 // (Add for Signature / PublicKey, types.rs:264-270, :126-132); results + H(msg_i) go to the verify planes.
@@ -683,6 +546,7 @@ static int agg_build_tables(bn254_ctx* c, hipStream_t s, const uint8_t* d_msgs, 
                             size_t n_signers, const uint8_t* d_sig_pool, uint32_t flags, size_t n, AggTables* t) {
   int rc;
   t->valid = 0; t->n_msgs = n_msgs; t->n_signers = n_signers; t->n_groups = 0; t->groups4 = 0; t->wide2 = 0; t->wide1 = 0; t->built_for = n;
+  t->t4_builder = 0;
   if ((rc = ws_reserve(c, n > n_msgs ? n : n_msgs))) return rc;
   if ((rc = pool_reserve(c, 0, 4, n_signers))) return rc;
   if ((rc = pool_reserve(c, 1, 2, n_msgs * n_signers))) return rc;
@@ -708,12 +572,15 @@ static int agg_build_tables(bn254_ctx* c, hipStream_t s, const uint8_t* d_msgs, 
         if (pool_reserve(c, 4, 2, entries) == 0) {
           groups4 = 2 * n_groups;
           const size_t groups2 = 2 * groups4;
-          if (pool_reserve(c, 7, 2, n_msgs * groups2 * 4) == 0) {          // pairs first, then quads by batched affine additions
+          // pairs first, then quads by batched affine additions (BN254_OPT_AGG_T4_ROUTE = 1, a developer option: always the fallback)
+          if (c->agg_t4_route == 0 && pool_reserve(c, 7, 2, n_msgs * groups2 * 4) == 0) {
             k_pool_pairs_g1<<<grid_for(n_msgs * groups2), BN_WAVE, 0, s>>>(c->pool[1], n_signers, groups2, n_msgs, c->pool[7]);
             k_pool_quads_g1<<<grid_for(n_msgs * groups4 * 4), BN_WAVE, 0, s>>>(c->pool[7], groups2, groups4, n_msgs, c->pool[4]);
+            t->t4_builder = 1;
           } else {
             (void)hipGetLastError();
             k_pool_subsets_g1<<<grid_for(entries), BN_WAVE, 0, s>>>(c->pool[1], n_signers, groups4, n_msgs, c->pool[4]);
+            t->t4_builder = 2;
           }
         } else {
           (void)hipGetLastError();     // no HBM for the table: the signatures are added one by one (groups4 = 0), same statuses

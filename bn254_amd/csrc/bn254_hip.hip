@@ -795,6 +795,7 @@ int bn254_ctx_create(int hip_device, bn254_ctx** out) {
   c->trio_wave_roles = TRIO_WAVE_ROLES_DEFAULT;
   c->agg_subset_min_tuples = AGG_SUBSET_MIN_TUPLES_DEFAULT;
   c->agg_sort_by_msg = 1;
+  c->agg_t4_route = 0;
   c->agg_wide_min_tuples = AGG_WIDE_MIN_TUPLES_DEFAULT;
   c->pinned_staging = PINNED_STAGING_DEFAULT;
   // the small-batch kernels ask for up to 156 KB of dynamic LDS per workgroup: on a part that cannot hold one, step down
@@ -949,6 +950,7 @@ int bn254_ctx_set_option(bn254_ctx* c, int option, int value) {
   }
   if (option == BN254_OPT_PINNED_STAGING) { if (value < 0 || value > 16) return BN254_E_BAD_ARGUMENT; c->pinned_staging = value; return 0; }
   if (option == BN254_OPT_AGG_SORT_BY_MSG) { c->agg_sort_by_msg = value != 0; return 0; }
+  if (option == BN254_OPT_AGG_T4_ROUTE) { if (value < 0 || value > 1) return BN254_E_BAD_ARGUMENT; c->agg_t4_route = value; return 0; }
   if (option == BN254_OPT_AGG_WIDE_MIN_TUPLES) { if (value < 0) return BN254_E_BAD_ARGUMENT; c->agg_wide_min_tuples = value; return 0; }
   if (option == BN254_OPT_CLOCK_PROBE) {
     HIP_TRY(hipSetDevice(c->device));

@@ -13,7 +13,8 @@
 #define BN_HIDDEN __attribute__((visibility("hidden")))
 
 // aggregate verify: which of the context's pool buffers hold valid tables, and for which pools (bn254_group.hip: agg_build_tables)
-struct AggTables { int valid; size_t n_msgs, n_signers, n_groups, groups4, built_for; int wide2, wide1; };
+// t4_builder: how the 4-signer signature tables were built — 0 not at all, 1 pairs + quads (the pair table is in pool[7]), 2 k_pool_subsets_g1
+struct AggTables { int valid; size_t n_msgs, n_signers, n_groups, groups4, built_for; int wide2, wide1, t4_builder; };
 
 // where a randomised call over groups left them for its debug hook: S_g in the P1 planes from cbase, the table pairs from tbase, the rest in
 // the call's scratch buffer
@@ -40,6 +41,7 @@ struct bn254_ctx {
   int agg_wide_min_tuples;    // aggregate verify: the widened tables from this many tuples on (0 = never)
   int agg_subset_min_tuples;  // aggregate verify: tabulate subset sums of the pk pool for batches of at least this many tuples (0 = never)
   int agg_sort_by_msg;        // aggregate verify: bucket the tuples by message before the aggregation kernel (default 1; A/B and test knob)
+  int agg_t4_route;           // BN254_OPT_AGG_T4_ROUTE (developer option): 0 = the 4-signer signature tables from pairs + quads, 1 = from k_pool_subsets_g1
   int pair_lanes;    // verify: Miller loop + final exponentiation on lane pairs (bn254_pair.hip); default on
   int rand_min_batch;      // randomised verify: batches below this size run the exact kernels (default RAND_MIN_BATCH_DEFAULT)
   int rand_items_per_lane; // randomised verify: 0 = by batch size, 1 or 2 forced (A/B and tests)

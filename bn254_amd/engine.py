@@ -53,6 +53,7 @@ OPT_COLLECT_RAND_MIN_PER_KEY = 39  # ... and below this many shares per register
 COLLECT_RAND_MIN_SHARES_DEFAULT = 65664  # the library's defaults of the two (bn254_amd/csrc/bn254_ws.h; measured: DESIGN.md §10f)
 COLLECT_RAND_MIN_PER_KEY_DEFAULT = 42
 OPT_COLLECT_OPT_MIN_SHARES = 40         # collect_keyed_bitmap_optimistic: the exact collect below this many shares (default 1539)
+OPT_AGG_T4_ROUTE = 42              # aggregate verify, test hook: 0 the 4-signer signature tables from pairs + quads, 1 from k_pool_subsets_g1
 OPT_COLLECT_OPT_MIN_TUPLE_SHARES = 41   # ... and, per tuple, the exact way below this many candidates (default 1 = every tuple is checked); DESIGN.md §10g
 COLLECT_OPT_MIN_SHARES_DEFAULT = 1539   # the library's defaults of the two (bn254_amd/csrc/bn254_ws.h; measured: DESIGN.md §10g)
 COLLECT_OPT_MIN_TUPLE_SHARES_DEFAULT = 1
@@ -164,6 +165,21 @@ class Engine:
         st, inf = ctypes.create_string_buffer(max(count, 1)), ctypes.create_string_buffer(max(count, 1))
         _check("bn254_debug_key_tables", self._lib.bn254_debug_key_tables(self._h, which, first, count, words, rep, st, inf))
         return list(words), (list(rep)[:count] if which == 0 else None), st.raw[:count], inf.raw[:count]
+
+    def debug_agg_tables_info(self):
+        """developer hook: which tables the registered pools have -> dict(n_groups, groups4, wide2, wide1, t4_builder: 0 none, 1 pairs + quads,
+        2 k_pool_subsets_g1)"""
+        o = (ctypes.c_uint64 * 5)()
+        _check("bn254_debug_agg_tables", self._lib.bn254_debug_agg_tables(self._h, -1, 0, 0, o, None))
+        return dict(zip(("n_groups", "groups4", "wide2", "wide1", "t4_builder"), (int(v) for v in o)))
+
+    def debug_agg_tables(self, which, first, count):
+        """developer hook: entries first .. first + count - 1 of table `which` (the context's pool index, 0 .. 7) of the registered pools ->
+        (points: canonical bytes, 128 per entry for which in (0, 3, 5) else 64, zeros under an identity flag; flags: the raw status bytes)"""
+        size = 128 if which in (0, 3, 5) else 64
+        pts, fl = ctypes.create_string_buffer(max(count * size, 1)), ctypes.create_string_buffer(max(count, 1))
+        _check("bn254_debug_agg_tables", self._lib.bn254_debug_agg_tables(self._h, which, first, count, pts, fl))
+        return pts.raw[:count * size], fl.raw[:count]
 
     def debug_agg_rand_last(self):
         """what the last batch_aggregate_verify_distinct_keyed_randomized[_device] did: dict(ran, groups, table_pairs, failed_groups, rechecked,

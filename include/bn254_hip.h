@@ -836,6 +836,10 @@ int bn254_mgpu_batch_hash_to_g1(bn254_mgpu *mg, const uint8_t *msgs, const uint6
                                                the sweeps at 65 536 and 2^20 x 256; at least 1).  Same status bytes */
 #define BN254_OPT_BITMAP_ROUTE 29 /* bn254_batch_verify_keyed_bitmap, test hook: 0 (default) = by BN254_OPT_BITMAP_TABLE_MAX_KEYS, 1 = always the subset
                                     tables, 2 = always key by key.  Same status bytes */
+#define BN254_OPT_AGG_T4_ROUTE 42 /* aggregate verify, test hook: how the per-message 4-signer signature tables are built: 0 (default) = pair tables, then
+                                     quads by batched affine additions (k_pool_pairs_g1 + k_pool_quads_g1); 1 = every entry from the pool
+                                     (k_pool_subsets_g1, otherwise only the fallback when the pair table cannot be allocated).  Same tables as
+                                     points, same status bytes */
 #define BN254_OPT_ASSUME_FREE_MB 18 /* test knob for the automatic slicing rule (BN254_OPT_MAX_CHUNK = 0): price the workspace of a batch against this many MB
                                     of free device memory instead of what hipMemGetInfo reports; 0 = ask the runtime */
 /* the routing table of this context as it stands (defaults + options): rows (max_n[i], miller[i], fe[i]) in ascending order of max_n, the last
@@ -857,6 +861,17 @@ int bn254_debug_key_cache_last(bn254_ctx *ctx, uint32_t out[5]);
  * (more keys than BN254_OPT_KEY_DEDUP_MAX_KEYS, too few items per key, a probe overflow) returns BN254_E_BAD_ARGUMENT and writes nothing: such
  * a call looks no key up and builds no table.  Synchronises the device. */
 int bn254_debug_key_tables(bn254_ctx *ctx, int which, size_t first, size_t count, int32_t *lines, uint32_t *rep, uint8_t *st, uint8_t *inf);
+/* the tables of the registered pools (bn254_ctx_register_pools) as they stand on the device: which = the context's pool index — 0 the decoded
+ * key pool (n_signers entries), 1 the decoded signature pool (n_msgs * n_signers), 2 H(m) (n_msgs), 3 T8 keys (entry g * 256 + mask), 4 T4
+ * signatures ((m * groups4 + g) * 16 + mask), 5 T16 keys (k * 65536 + mask), 6 T8 signatures ((m * n_groups + g) * 256 + mask), 7 T2 signatures
+ * ((m * 2 * groups4 + pair) * 4 + mask).  points: entries first .. first + count - 1 as canonical big-endian bytes, 64 per G1 entry, 128 per G2
+ * entry (which = 0, 3, 5), all-zero for an entry flagged as the identity (the tables store non-canonical words: the hook canonicalises);
+ * flags: the raw status bytes (0x80 = identity; in the decoded pools the low bits are the decode status, under which the coordinates are
+ * the generator's).  QUERY FORM, which = -1: points receives five uint64_t (40 bytes, 8-byte aligned) {n_groups, groups4, wide2, wide1, the
+ * builder of the T4 signatures: 0 none, 1 pairs + quads, 2 k_pool_subsets_g1}; first, count and flags are not used.
+ * BN254_E_BAD_ARGUMENT when no registration is valid (none yet, or a call with raw pools since), when the table was not built, and when
+ * first + count runs past the table.  Synchronises the context. */
+int bn254_debug_agg_tables(bn254_ctx *ctx, int which, size_t first, size_t count, uint8_t *points, uint8_t *flags);
 /* what the last bn254_batch_aggregate_verify_distinct_keyed_randomized[_device] did: out = {1 if it took the randomised route, groups that
  * reached the check, table pairs of all group checks, failed groups, aggregates re-checked, groups of one aggregate (r = 1)}; all 0 when it
  * took the exact route.  Synchronises the device. */

@@ -380,6 +380,70 @@ class ECDSA:
         return out
 
     @staticmethod
+    def merge_keyed_signers(message, parts, engine=None, n_keys=None):
+        """One message and some PARTIAL aggregates of it — parts[k] = (Signature, signer_indices), the sum of the signatures of those keys of
+        the registered set, as a child of an aggregation tree sends it: every partial is verified as ECDSA.verify_keyed_signers verifies it,
+        and, in the order given, the valid ones whose indices do not overlap what was taken before are added (first fit: sort by
+        descending number of signers for the largest cover).  Returns (aggregate Signature, sorted indices of the union, statuses, taken):
+        statuses[k] is None or the Error verify_keyed_signers would raise for partial k, taken[k] a bool.  The first two feed
+        ECDSA.verify_keyed_signers.  Raises the message's Error(HashToPointError) (include/bn254_hip.h: bn254_batch_merge_keyed_bitmap).
+        Assumes a proof of possession of every registered key."""
+        r = ECDSA.batch_merge_keyed_signers([(message, parts)], engine, n_keys)[0]
+        if isinstance(r, Error):
+            raise r
+        return r
+
+    @staticmethod
+    def batch_merge_keyed_signers(items, engine=None, n_keys=None):
+        """items: a list of (message, parts); result[i] is what ECDSA.merge_keyed_signers returns for item i, or the Error it would raise.
+        A malformed item (not such a pair, a part that is not a pair, a signature of the wrong length, an index that is negative or >= 2^32)
+        raises before any device work.  n_keys: the size of the registered set, for an engine that did not register it itself (without
+        either the bitmaps are as wide as the largest index)."""
+        rows = []
+        for item in items:
+            if not isinstance(item, (tuple, list)) or len(item) != 2:
+                raise Error(ErrorKind.InvalidLength)
+            message, parts = item
+            sigs, sets = [], []
+            for part in parts:
+                if not isinstance(part, (tuple, list)) or len(part) != 2 or len(part[0].raw) != _engine.G1_BYTES:
+                    raise Error(ErrorKind.InvalidLength)
+                idx = [int(j) for j in part[1]]
+                if any(j < 0 or j >= 1 << 32 for j in idx):
+                    raise Error(ErrorKind.IndexOutOfBounds)
+                sigs.append(part[0].raw)
+                sets.append(idx)
+            rows.append((bytes(message), sigs, sets))
+        eng = engine or _eng()
+        # the bitmaps as ECDSA.verify_keyed_signers builds them: as wide as the registered set plus ONE bit, on which every index outside
+        # the set lands (such a partial reads IndexOutOfBounds and is never taken, so the bit never reaches the union)
+        if n_keys is None:
+            n_keys = getattr(eng, "n_registered_keys", None)
+        top = int(n_keys) if n_keys is not None else max([j for _, _, sets in rows for idx in sets for j in idx], default=-1)
+        bm_words = top // 32 + 1
+        bits = []
+        for _, _, sets in rows:
+            for idx in sets:
+                row = [0] * bm_words
+                for j in idx:
+                    j = min(j, top)
+                    row[j // 32] |= 1 << (j % 32)
+                bits += row
+        part_st, taken, tuple_st, agg, union = eng.merge_keyed_bitmap([r[0] for r in rows], b"".join(s for r in rows for s in r[1]), bits,
+                                                                     [len(r[1]) for r in rows], bm_words)
+        out, at = [], 0
+        for i, (_, sigs, _) in enumerate(rows):
+            st, tk = part_st[at:at + len(sigs)], taken[at:at + len(sigs)]
+            at += len(sigs)
+            if tuple_st[i]:
+                out.append(Error(tuple_st[i]))
+                continue
+            row = union[i * bm_words:(i + 1) * bm_words]
+            signers = [j for j in range(32 * bm_words) if (row[j // 32] >> (j % 32)) & 1]
+            out.append((Signature(agg[64 * i:64 * i + 64]), signers, [None if b == 0 else Error(b) for b in st], [bool(b) for b in tk]))
+        return out
+
+    @staticmethod
     def batch_aggregate_keyed_signers_optimistic(items, engine=None, n_keys=None):
         """batch_aggregate_keyed_signers with one verify per item — the sum of its signatures that pass every check short of the pairing,
         against the sum of their keys — and the signatures verified one by one only in an item whose sum fails, that names a key twice, or

@@ -95,6 +95,10 @@ BN_DEV void cl_tree_level(Slot* part, uint32_t* cnt, unsigned t, unsigned stride
   jac_add(part[t].v, part[t].v, part[t + stride].v);
   cnt[t] += cnt[t + stride];
 }
+// the slot of a partial sum in LDS, padded like G1JacSlot of the randomised verify (bn254_rand.hip); and the block cap of the wave-per-tuple
+// kernels, which reach the tuples beyond the grid by stride (k_cl_sum_wave, k_clo_sum_wave; bn254_merge.hip: k_mg_wave)
+struct ClJacSlot { G1Jac v; int32_t pad; };
+#define CL_WAVE_MAX_BLOCKS ((size_t)65536)
 // the aggregate as the caller gets it: uncompressed, the identity as 64 zero bytes
 BN_DEV void cl_encode(uint8_t* out64, const G1Jac& acc) {
   G1Affine r;

@@ -35,7 +35,7 @@ using namespace bn254;
 // (bn254_collect.h: CLO_*) and tuple-check verdict per tuple
 #define CL_STAT_WORDS 8
 #define CLO_STAT_AT 4
-struct ClScratch { uint32_t* stats; uint64_t *mx, *hi, *end, *tot; int32_t* hpt; uint8_t *hinf, *hst, *flag, *verdict; };
+// (struct ClScratch: bn254_host.h — the merge of partial aggregates, bn254_merge.hip, shares the scratch and the front end)
 static ClScratch cl_scratch(Carve& c, size_t n) {
   ClScratch b;
   b.stats = c.take<uint32_t>(CL_STAT_WORDS);
@@ -90,6 +90,36 @@ KERNEL_SMALL void k_cl_spread(size_t len, uint64_t base, size_t n, const uint64_
   ws_byte(ws, BY_ST_HASH, j) = S.hst[t];
 }
 
+// ---- what bn254_merge.hip shares with this unit (bn254_host.h): the scratch, steps 1 and 2 of every call, and the spread -------------------
+int cl_scratch_reserve(bn254_ctx* c, size_t n, ClScratch* S) {
+  Carve size(nullptr);
+  cl_scratch(size, n);
+  if (const int rc = scratch_reserve(c, &c->collect_buf, &c->collect_cap, size.used)) return rc;
+  Carve carve(c->collect_buf);
+  *S = cl_scratch(carve, n);
+  return 0;
+}
+// 1. hash once per tuple, in pieces of t_piece tuples; 2. the range rule over d_off against n_items, the tuples' statuses, item -> tuple
+int cl_hash_and_plan(bn254_ctx* c, hipStream_t s, const uint8_t* d_msgs, const uint64_t* d_msg_off, const uint64_t* d_off, size_t n_items, size_t n,
+                     size_t t_piece, const ClScratch& S, uint8_t* d_tuple_status) {
+  int rc;
+  for (size_t lo = 0; lo < n; lo += t_piece) {
+    const size_t len = n - lo < t_piece ? n - lo : t_piece;
+    if ((rc = launch_hash_rounds(c, s, d_msgs, d_msg_off + lo, len, PL_P2X, BY_P2_INF, nullptr))) return rc;
+    k_cl_save<<<grid_for(len), BN_WAVE, 0, s>>>(len, lo, c->ws, S);
+    HIP_TRY(hipGetLastError());
+  }
+  if ((rc = bn254_aggd_scan_max(s, d_off, n, S.mx, S.tot))) return rc;
+  k_cl_plan<<<grid_for(n), BN_WAVE, 0, s>>>(n, (uint64_t)n_items, d_off, S, d_tuple_status);
+  HIP_TRY(hipGetLastError());
+  return bn254_aggd_scan_max(s, S.hi, n, S.end, S.tot);
+}
+int launch_cl_spread(bn254_ctx* c, hipStream_t s, size_t len, uint64_t base, size_t n, const uint64_t* d_off, const ClScratch& S) {
+  k_cl_spread<<<grid_for(len), BN_WAVE, 0, s>>>(len, base, n, d_off, S, c->ws);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 // ---- select-and-sum (both kernels run on the zeroed output rows; a tuple is taken by exactly one of them, by its own length) ---------------
 // lane per tuple, the tuples below wave_min shares.  No early return: the additions vote across the wave (see k_bm_sum); a lane whose
 // tuple is long, or past the end, walks identities.
@@ -111,7 +141,6 @@ KERNEL_SMALL void k_cl_sum_lane(ClShares in, size_t n, size_t bm_words, uint64_t
 // wave per tuple, the others: a wave leaves a short tuple at once (wave-uniformly); tuples beyond the grid by stride.  The partial sums are
 // accumulated in place in LDS, through generic references (as k_rand_scale keeps its accumulator): every limb is a flat access.  Measured,
 // the kernel sums one tuple of 4 096 shares in 0.27 ms beside a 2.2 ms verify, so the partial sums were not moved into registers.
-struct ClJacSlot { G1Jac v; int32_t pad; };   // padded like G1JacSlot of the randomised verify (bn254_rand.hip)
 KERNEL_SMALL void k_cl_sum_wave(ClShares in, size_t n, size_t bm_words, uint64_t wave_min, uint32_t* bits, uint8_t* agg, uint32_t* n_signers) {
   __shared__ ClJacSlot part[BN_WAVE];
   __shared__ uint32_t cnt[BN_WAVE];
@@ -132,7 +161,6 @@ KERNEL_SMALL void k_cl_sum_wave(ClShares in, size_t n, size_t bm_words, uint64_t
     __syncthreads();
   }
 }
-#define CL_WAVE_MAX_BLOCKS ((size_t)65536)
 
 // one slice of the shares: decode, spread, the keyed verify of the slots; statuses at the shares' own positions.  Profiling: every slice
 // records its intervals, so the last one's stay (a slice behind the first opens its own front end; the first one's began with the hash)
@@ -388,11 +416,8 @@ static int cl_collect_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t
     if ((rc = stage_reserve(c, 5, need.words * sizeof(uint32_t)))) return rc;
     if ((rc = stage_reserve(c, 7, need.groups_max))) return rc;
   }
-  Carve size(nullptr);
-  cl_scratch(size, n);
-  if ((rc = scratch_reserve(c, &c->collect_buf, &c->collect_cap, size.used))) return rc;
-  Carve carve(c->collect_buf);
-  const ClScratch S = cl_scratch(carve, n);
+  ClScratch S;
+  if ((rc = cl_scratch_reserve(c, n, &S))) return rc;
   c->clr_stats = S.stats;
   c->clo_stats = S.stats + CLO_STAT_AT;
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
@@ -402,18 +427,8 @@ static int cl_collect_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t
   if (rand) seed = rand_seed_from(seed32);
   if (rand || opt) HIP_TRY(hipMemsetAsync(S.stats, 0, CL_STAT_WORDS * sizeof(uint32_t), s));
   PROF_MARK(opt ? 0 : 1);
-  // 1. hash once per tuple
-  for (size_t lo = 0; lo < n; lo += t_piece) {
-    const size_t len = n - lo < t_piece ? n - lo : t_piece;
-    if ((rc = launch_hash_rounds(c, s, d_msgs, d_msg_off + lo, len, PL_P2X, BY_P2_INF, nullptr))) return rc;
-    k_cl_save<<<grid_for(len), BN_WAVE, 0, s>>>(len, lo, c->ws, S);
-    HIP_TRY(hipGetLastError());
-  }
-  // 2. the range rule, the tuples' statuses, share -> tuple
-  if ((rc = bn254_aggd_scan_max(s, d_share_off, n, S.mx, S.tot))) return rc;
-  k_cl_plan<<<grid_for(n), BN_WAVE, 0, s>>>(n, (uint64_t)n_shares, d_share_off, S, d_tuple_status);
-  HIP_TRY(hipGetLastError());
-  if ((rc = bn254_aggd_scan_max(s, S.hi, n, S.end, S.tot))) return rc;
+  // 1. hash once per tuple; 2. the range rule, the tuples' statuses, share -> tuple
+  if ((rc = cl_hash_and_plan(c, s, d_msgs, d_msg_off, d_share_off, n_shares, n, t_piece, S, d_tuple_status))) return rc;
   if (bm_words) HIP_TRY(hipMemsetAsync(d_signer_bits, 0, n * bm_words * sizeof(uint32_t), s));
   if (n_shares) HIP_TRY(hipMemsetAsync(d_share_status, ST_INDEX_OOB, n_shares, s));
   if (opt) {

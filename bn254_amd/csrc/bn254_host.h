@@ -144,6 +144,7 @@ struct bn254_ctx {
   int collect_opt_min_tuple_shares; // BN254_OPT_COLLECT_OPT_MIN_TUPLE_SHARES: ... and, per tuple, from this many candidates on
   uint32_t* clo_stats;       // what its last call did on the device (bn254_debug_collect_opt_last); inside collect_buf
   int clo_last_ran;          // ... and whether that call took the optimistic route at all
+  int merge_wave_min;        // BN254_OPT_MERGE_WAVE_MIN_PARTS (bn254_merge.hip): tuples with at least this many partials are merged by a wave each
 };
 
 struct ScopedEvents {
@@ -335,4 +336,17 @@ BN_HIDDEN bool bm_wants_tables(const bn254_ctx* c);
 BN_HIDDEN int bm_prepare(bn254_ctx* c, hipStream_t s, bool tables);
 // ... and the aggregate keys of n tuples (row i of d_bits -> the Q planes of workspace entry i, rule 2 behind the entry's decode status)
 BN_HIDDEN int launch_bitmap_sum(bn254_ctx* c, hipStream_t s, const uint32_t* d_bits, size_t bm_words, size_t n, bool tables);
+// the collect family (bn254_collect.hip), shared with the merge of partial aggregates (bn254_merge.hip).  Per tuple, outside the (sliced)
+// workspace: the scans of the range rule, H(m) with its identity flag and hash status; in front the counters of the randomised and the
+// optimistic collect, behind the optimistic route's flag and verdict
+struct ClScratch { uint32_t* stats; uint64_t *mx, *hi, *end, *tot; int32_t* hpt; uint8_t *hinf, *hst, *flag, *verdict; };
+// ... carved for n tuples from the context's collect_buf (grown on demand: before the call's first kernel)
+BN_HIDDEN int cl_scratch_reserve(bn254_ctx* c, size_t n, ClScratch* S);
+// ... the hash of the n messages, once per tuple in pieces of t_piece, and the range rule over the n + 1 offsets d_off into n_items items:
+// d_tuple_status, and S.end for the item -> tuple search
+BN_HIDDEN int cl_hash_and_plan(bn254_ctx* c, hipStream_t s, const uint8_t* d_msgs, const uint64_t* d_msg_off, const uint64_t* d_off, size_t n_items, size_t n,
+                               size_t t_piece, const ClScratch& S, uint8_t* d_tuple_status);
+// ... and H(m) and the hash status of its tuple into workspace entries 0 .. len for the items base .. base + len (an item of no accepted tuple:
+// the generator, decode status 2)
+BN_HIDDEN int launch_cl_spread(bn254_ctx* c, hipStream_t s, size_t len, uint64_t base, size_t n, const uint64_t* d_off, const ClScratch& S);
 BN_HIDDEN int launch_encode_g1(bn254_ctx* c, hipStream_t s, size_t n, int px, int inf_plane, uint8_t* out, uint8_t* status_out);

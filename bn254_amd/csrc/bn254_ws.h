@@ -278,6 +278,9 @@ __attribute__((visibility("hidden"))) int bn254_pair_bitmap_sum(const uint32_t* 
 #define COLLECT_OPT_MIN_TUPLE_SHARES_DEFAULT 1     // BN254_OPT_COLLECT_OPT_MIN_TUPLE_SHARES: ... and only the tuples with at least this many candidates.  1 = every
                                                    //     tuple: a tuple sent the exact way costs the call one pass of the queue's kernels, 4.9 ms measured whatever
                                                    //     the queue's length, and the check of a short tuple's sum costs nothing measurable
+#define MERGE_WAVE_MIN_PARTS_DEFAULT 16            // BN254_OPT_MERGE_WAVE_MIN_PARTS (bn254_merge.hip): tuples with at least this many partials are merged by a
+                                                   //     wave each.  Swept over 4 .. 256 partials at rows of 8 and of 128 words: the layouts
+                                                   //     cross between 16 and 32 partials at 8 words, at 8 at 128 words; 16 has the smallest worst loss (0.15 ms)
 __attribute__((visibility("hidden"))) int bn254_aggd_scan_add(hipStream_t s, const uint64_t* in, size_t n, uint64_t* out, uint64_t* tot);
 __attribute__((visibility("hidden"))) int bn254_aggd_scan_max(hipStream_t s, const uint64_t* in, size_t n, uint64_t* out, uint64_t* tot);   // ... the prefix maximum
 __attribute__((visibility("hidden"))) int bn254_aggd_keyed_slot_map(hipStream_t s, size_t n, const uint64_t* lo, const uint64_t* hi, int width,

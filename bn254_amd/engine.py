@@ -57,6 +57,8 @@ OPT_AGG_T4_ROUTE = 42              # aggregate verify, test hook: 0 the 4-signer
 OPT_COLLECT_OPT_MIN_TUPLE_SHARES = 41   # ... and, per tuple, the exact way below this many candidates (default 1 = every tuple is checked); DESIGN.md §10g
 COLLECT_OPT_MIN_SHARES_DEFAULT = 1539   # the library's defaults of the two (bn254_amd/csrc/bn254_ws.h; measured: DESIGN.md §10g)
 COLLECT_OPT_MIN_TUPLE_SHARES_DEFAULT = 1
+OPT_MERGE_WAVE_MIN_PARTS = 43       # merge_keyed_bitmap: tuples with at least this many partials are merged by a wave each (default 16, from the sweep of tools/merge_throughput.py)
+MERGE_WAVE_MIN_PARTS_DEFAULT = 16   # ... as bn254_ws.h has it
 OPT_COLLECT_WAVE_MIN_SHARES = 37   # collect_keyed_bitmap: tuples with at least this many shares are summed by a wave each (default 16; swept at three shapes only)
 
 
@@ -591,6 +593,40 @@ class Engine:
         _check("bn254_batch_collect_keyed_bitmap_device",
                self._lib.bn254_batch_collect_keyed_bitmap_device(self._h, d_msgs, d_msg_off, d_shares, d_share_key, d_share_off, n_shares, n, bm_words,
                                                                  flags, d_share_status, d_tuple_status, d_agg_sigs, d_signer_bits, d_n_signers, stream))
+
+    def merge_keyed_bitmap(self, messages, parts, part_bitmaps, sizes, bm_words, flags=0, want_counts=False):
+        """merge partial signer-bitmap aggregates into one aggregate per message (include/bn254_hip.h: bn254_batch_merge_keyed_bitmap):
+        tuple i is messages[i] with the next sizes[i] partials (64 B each; partial p has the bm_words bitmap words part_bitmaps[p * bm_words
+        ..]).  Returns (partial status bytes, taken bytes, tuple status bytes, the n aggregates, the n * bm_words bitmap words) — and the
+        signer counts with want_counts."""
+        n = len(messages)
+        assert len(sizes) == n and all(k >= 0 for k in sizes)
+        n_parts = sum(int(k) for k in sizes)
+        assert len(parts) == n_parts * G1_BYTES and len(part_bitmaps) == n_parts * bm_words
+        msgs, off = pack_messages(messages)
+        ends = [0]
+        for k in sizes:
+            ends.append(ends[-1] + int(k))
+        part_off = (ctypes.c_uint64 * (n + 1))(*ends)
+        rows = (ctypes.c_uint32 * max(n_parts * bm_words, 1))(*part_bitmaps)
+        part_st = ctypes.create_string_buffer(max(n_parts, 1))
+        taken = ctypes.create_string_buffer(max(n_parts, 1))
+        tuple_st = ctypes.create_string_buffer(max(n, 1))
+        agg = ctypes.create_string_buffer(max(n, 1) * G1_BYTES)
+        bits = (ctypes.c_uint32 * max(n * bm_words, 1))()
+        counts = (ctypes.c_uint32 * max(n, 1))()
+        _check("bn254_batch_merge_keyed_bitmap",
+               self._lib.bn254_batch_merge_keyed_bitmap(self._h, msgs, off, bytes(parts), rows, part_off, n_parts, n, bm_words, flags, part_st, taken, tuple_st,
+                                                        agg, bits, counts if want_counts else None))
+        out = (part_st.raw[:n_parts], taken.raw[:n_parts], tuple_st.raw[:n], agg.raw[:n * G1_BYTES], list(bits)[:n * bm_words])
+        return out + (list(counts)[:n],) if want_counts else out
+
+    def merge_keyed_bitmap_device(self, d_msgs, d_msg_off, d_parts, d_part_bits, d_part_off, n_parts, n, bm_words, d_part_status, d_part_taken,
+                                  d_tuple_status, d_agg_sigs, d_signer_bits, d_n_signers=None, flags=0, stream=None):
+        """the device-pointer form: enqueues only (include/bn254_hip.h: bn254_batch_merge_keyed_bitmap_device)"""
+        _check("bn254_batch_merge_keyed_bitmap_device",
+               self._lib.bn254_batch_merge_keyed_bitmap_device(self._h, d_msgs, d_msg_off, d_parts, d_part_bits, d_part_off, n_parts, n, bm_words, flags,
+                                                               d_part_status, d_part_taken, d_tuple_status, d_agg_sigs, d_signer_bits, d_n_signers, stream))
 
     def batch_collect_keyed_bitmap_optimistic(self, messages, shares, share_keys, sizes, bm_words, flags=0, want_counts=False):
         """batch_collect_keyed_bitmap with ONE verify per tuple — the sum of its candidate shares against the sum of their keys — and the

@@ -377,6 +377,58 @@ struct ECDSA {
     check_status(r.status);
     return r;
   }
+  // The inner node of an aggregation tree (include/bn254_hip.h: bn254_batch_merge_keyed_bitmap): one message and PARTIAL aggregates of it,
+  // parts[k] = a summed signature and the indices of the registered keys it is said to sum.  Every partial is verified as verify_keyed_signers
+  // verifies it; in the order given, the valid ones whose indices do not overlap what was taken before are added (first fit).
+  // status: 0, or the message's hash ErrorKind (then nothing was added); statuses[k]: what verify_keyed_signers gives partial k; taken[k]: 1 or 0.
+  struct PartialAggregate { Signature signature; std::vector<uint32_t> signer_indices; };
+  struct MergeItem { std::vector<uint8_t> message; std::vector<PartialAggregate> parts; };
+  struct KeyedMergeResult { uint8_t status; Signature signature; std::vector<uint32_t> signer_indices; std::vector<uint8_t> statuses, taken; };
+  static std::vector<KeyedMergeResult> batch_merge_keyed_signers(const std::vector<MergeItem>& items, size_t n_keys, Engine& e = Engine::default_engine()) {
+    const size_t n = items.size(), bm_words = n_keys / 32 + 1;   // one bit past the set: every index outside it lands there -> IndexOutOfBounds
+    std::vector<uint64_t> off(n + 1, 0), part_off(n + 1, 0);
+    std::vector<uint8_t> msgs, parts;
+    std::vector<uint32_t> rows;
+    for (size_t i = 0; i < n; ++i) {
+      off[i] = msgs.size();
+      part_off[i] = parts.size() / 64;
+      msgs.insert(msgs.end(), items[i].message.begin(), items[i].message.end());
+      for (const PartialAggregate& p : items[i].parts) {
+        parts.insert(parts.end(), p.signature.raw.begin(), p.signature.raw.end());
+        rows.resize(rows.size() + bm_words, 0);
+        for (uint32_t j : p.signer_indices) {
+          const size_t b = j < n_keys ? j : n_keys;
+          rows[rows.size() - bm_words + b / 32] |= 1u << (b % 32);
+        }
+      }
+    }
+    off[n] = msgs.size();
+    part_off[n] = parts.size() / 64;
+    const size_t n_parts = (size_t)part_off[n];
+    std::vector<uint8_t> part_st(n_parts + 1, 0), taken(n_parts + 1, 0), tuple_st(n + 1, 0), agg(n * 64 + 1, 0);
+    std::vector<uint32_t> bits(n * bm_words + 1, 0);
+    parts.resize(parts.size() + 1);
+    rows.resize(rows.size() + 1);
+    check_rc("bn254_batch_merge_keyed_bitmap",
+             bn254_batch_merge_keyed_bitmap(e.raw(), msgs.data(), off.data(), parts.data(), rows.data(), part_off.data(), n_parts, n, bm_words, 0, part_st.data(),
+                                            taken.data(), tuple_st.data(), agg.data(), bits.data(), nullptr));
+    std::vector<KeyedMergeResult> out(n);
+    for (size_t i = 0; i < n; ++i) {
+      out[i].status = tuple_st[i];
+      std::memcpy(out[i].signature.raw.data(), &agg[64 * i], 64);
+      for (size_t j = 0; j < 32 * bm_words; ++j)
+        if ((bits[i * bm_words + j / 32] >> (j % 32)) & 1u) out[i].signer_indices.push_back((uint32_t)j);
+      out[i].statuses.assign(part_st.begin() + part_off[i], part_st.begin() + part_off[i + 1]);
+      out[i].taken.assign(taken.begin() + part_off[i], taken.begin() + part_off[i + 1]);
+    }
+    return out;
+  }
+  static KeyedMergeResult merge_keyed_signers(const std::vector<uint8_t>& message, const std::vector<PartialAggregate>& parts, size_t n_keys,
+                                              Engine& e = Engine::default_engine()) {
+    KeyedMergeResult r = batch_merge_keyed_signers({MergeItem{message, parts}}, n_keys, e)[0];
+    check_status(r.status);
+    return r;
+  }
   // aggregate_verify against the registered set: key_indices[j] names the key of messages[j]; 2 (IndexOutOfBounds) outside the set
   // (include/bn254_hip.h: bn254_batch_aggregate_verify_distinct_keyed)
   struct KeyedAggregate { std::vector<std::vector<uint8_t>> messages; Signature signature; std::vector<uint32_t> key_indices; };

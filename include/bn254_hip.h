@@ -574,6 +574,73 @@ int bn254_batch_collect_keyed_bitmap_optimistic_device(bn254_ctx *ctx, const uin
                                                        size_t bm_words, uint32_t flags, uint8_t *d_share_status, uint8_t *d_tuple_status,
                                                        uint8_t *d_agg_sigs, uint32_t *d_signer_bits, uint32_t *d_n_signers, void *stream);
 
+/* MERGING partial signer-bitmap aggregates — the inner node of an aggregation tree.  A committee node receives, per message, a handful of
+ * PARTIAL aggregates from its children (a bitmap and one summed signature each) and has to pass one aggregate upward: every partial verified
+ * against its bitmap, the valid ones that do not overlap added, and the union bitmap written — on the device, with no host synchronisation,
+ * the outputs going straight into bn254_batch_verify_keyed_bitmap.  Tuple i is the message msgs[msg_off[i] .. msg_off[i+1]) and the partials
+ * p in [part_off[i], part_off[i+1]); partial p is the signature parts[64 p] with bitmap row p of part_bits (bm_words words, in the bitmap
+ * verify's numbering: signer j = bit j % 32 of word p * bm_words + j / 32).
+ * part_status[p], DEFINING IDENTITY 1: byte for byte what bn254_batch_verify_keyed_bitmap returns, with the same flags, for n_parts items whose
+ * message is their tuple's message repeated — rules 1-4 there: sigma's decode status, the lowest bad bit (2 if it is >= n_keys, else the key's
+ * registration status; with no keys registered any set bit gives 2), the hash status (1, or 5 in the _device form), then 0 or 9.  The
+ * message is hashed once per tuple, not once per partial.  An empty row is verified as the bitmap call verifies it (e(sigma, -G2) == 1: only
+ * the identity passes).  No new status code.
+ * tuple_status[i] and the RANGE RULE are the exact collect's: 0, the hash status of m_i, or — in the _device form, and ahead of it — 2 for a
+ * range that is reversed, runs past n_parts, or starts before an earlier offset.  part_status is filled with 2 first: a partial of no accepted
+ * tuple reads 2, and its part_taken 0.  A refused tuple gets an empty row, the identity as its aggregate and count 0.
+ * SELECT, part_taken[p] (1 or 0): within a tuple, IN THE CALLER'S ORDER, partial p is taken iff part_status[p] == 0 and its row is disjoint from
+ * the union of the rows taken earlier in that tuple (first fit).  A partial that overlaps only partials that were themselves refused or not
+ * taken is taken.  A status-0 partial with an empty row is taken and adds nothing: its signature is the identity.  A caller who wants the
+ * largest cover sorts a tuple's partials by descending popcount.  First fit is well defined here because the valid aggregate of (m, set of
+ * keys) is unique — G1 has prime order —, so the outputs depend only on WHICH rows are taken, never on which of two equal partials was, and the
+ * sum may be formed in parallel in any order: the bytes are the same.
+ * Outputs of an accepted tuple:
+ *   - signer_bits row i: the OR of the taken rows;
+ *   - agg_sigs[i]: the sum of the taken signatures, uncompressed, the identity as 64 zero bytes;
+ *   - n_signers[i] (the array may be NULL): the popcount of row i.
+ * DEFINING IDENTITY 2 (closed loop, flags = 0): bn254_batch_verify_keyed_bitmap(msgs, agg_sigs, signer_bits, bm_words) on the call's own
+ * outputs returns 0 for every tuple with tuple_status == 0.
+ * DEFINING IDENTITY 3 (the collect inside it): with bm_words >= ceil(n_keys / 32) and every partial's row holding exactly one bit, bit k_p,
+ * part_status, tuple_status, agg_sigs, signer_bits and n_signers equal bn254_batch_collect_keyed_bitmap's with share_key = k_p, and
+ * part_taken[p] is 1 exactly for the first status-0 share of its key in its tuple.
+ * Argument checks: bm_words follows the bitmap verify's rule — any value up to 0xFFFFFFFF, 0 included (part_bits and signer_bits may then be
+ * NULL); keys beyond the bitmap are absent, bits beyond the key set give 2; else BN254_E_BAD_ARGUMENT.  n and n_parts < 2^32.  Host form:
+ * part_off[0] == 0, non-decreasing, part_off[n] == n_parts.  BN254_E_MISALIGNED as in the collect: parts, part_bits, agg_sigs, signer_bits and
+ * n_signers 4-byte aligned, the offsets 8-byte aligned.  n == 0 returns 0.  BN254_OPT_MAX_CHUNK slices the PARTIALS (and the tuples' hashing),
+ * as the collect slices shares; the outputs are the same.
+ * Security: a proof of possession of every registered key is assumed, as in the rest of the family.
+ * Cost: ONE hash-to-G1 per tuple; per partial the bitmap verify's aggregate key (subset tables: n_keys / 8 additions) and one verify; then a
+ * select-and-sum launched once behind the last slice, in two layouts chosen per tuple by its number of partials: below
+ * BN254_OPT_MERGE_WAVE_MIN_PARTS one lane walks the tuple (all bm_words words of each partial's row, one addition per taken partial); from
+ * there on a wave does — lane l owns words l, l + 64, .. of the row, one wave vote per status-0 partial decides, then the 64 lanes add the
+ * taken partials l, l + 64, .. and six levels of additions in LDS fold the partial sums.  All additions are complete.  The _device form only
+ * enqueues: no host synchronisation, the range rule included.
+ * Profiling: bn254_ctx_last_kernel_ms keeps four intervals with the exact collect's meaning: ms[0] front end (hash once per tuple, decode,
+ * spread, aggregate keys), ms[1] select-and-sum (it runs last), ms[2] Miller loop, ms[3] final exponentiation — of the last slice.
+ * Which call when: this one wherever a node holds partial aggregates per message; the route without it is
+ * bn254_batch_verify_keyed_bitmap_device on the repeated messages, a copy of the statuses to the host, the first-fit filter there, and
+ * bn254_batch_g1_sum.  Measured on an MI355X (tools/merge_throughput.py, profiles/merge_throughput.jsonl; 256 keys, two thirds signing in
+ * disjoint committees, every partial valid, whole-call medians of 9 alternating calls on a caller's stream, inputs resident, min .. max in
+ * brackets): 256 tuples x 16 partials 3.07 ms [3.05 .. 3.09] against that route's 3.50 [3.49 .. 3.51]; 4 096 x 4 5.14 [5.09 .. 5.17] against
+ * 5.88 [5.83 .. 5.93]; 1 024 x 64 11.8 [11.6 .. 12.5] against 15.3 [15.0 .. 16.3]; one tuple of 4 096 one-bit partials 4.21 [4.19 .. 4.26]
+ * against 6.64 [6.28 .. 7.08] — the call is ahead beyond the spread at all four, by 1.14 x to 1.58 x.  The other route's interval holds its
+ * host filter (numpy: 0.22, 0.65, 2.9 and 0.73 ms of it); with the filter's time taken off entirely the call is still ahead at every shape
+ * (3.07 against 3.28, 5.14 against 5.23, 11.8 against 12.4, 4.21 against 5.91).  Per stage (front end, select-and-sum, Miller loop, final exponentiation): 256 x 16 0.71 + 0.23 + 1.04 + 1.13
+ * ms; 1 024 x 64 1.39 + 0.41 + 6.06 + 3.90; the lone tuple 0.36 + 1.59 + 1.07 + 1.14 — there the select, serial in 4 096 partials for one
+ * wave, costs 0.39 us per partial and is the largest stage; the collect sums the same shares in 0.27 ms, so a caller whose partials are all
+ * single shares takes the collect.  No shape at which the call loses was found; shapes with invalid partials were not measured.
+ * Out of scope: an optimistic form (one verify of the tuple's sum when its partials are pairwise disjoint — the obvious follow-up), a
+ * randomised form, the multi-GPU layer, compressed input. */
+int bn254_batch_merge_keyed_bitmap(bn254_ctx *ctx, const uint8_t *msgs, const uint64_t *msg_off /* n+1 */,
+                                   const uint8_t *parts /* n_parts*64 */, const uint32_t *part_bits /* n_parts*bm_words */,
+                                   const uint64_t *part_off /* n+1 */, size_t n_parts, size_t n, size_t bm_words, uint32_t flags,
+                                   uint8_t *part_status /* n_parts */, uint8_t *part_taken /* n_parts */, uint8_t *tuple_status /* n */,
+                                   uint8_t *agg_sigs /* n*64 */, uint32_t *signer_bits /* n*bm_words */, uint32_t *n_signers /* n, or NULL */);
+int bn254_batch_merge_keyed_bitmap_device(bn254_ctx *ctx, const uint8_t *d_msgs, const uint64_t *d_msg_off, const uint8_t *d_parts,
+                                          const uint32_t *d_part_bits, const uint64_t *d_part_off, size_t n_parts, size_t n, size_t bm_words,
+                                          uint32_t flags, uint8_t *d_part_status, uint8_t *d_part_taken, uint8_t *d_tuple_status,
+                                          uint8_t *d_agg_sigs, uint32_t *d_signer_bits, uint32_t *d_n_signers, void *stream);
+
 /* compressed wire formats (src/utils.rs:84-104, :130-158): out = uncompressed point, status as
  * bn::G1::from_compressed / bn::G2::from_compressed report through src/types.rs:91-93, :233-237, checked in the order
  * those decoders work (an input with several faults reports the first):
@@ -676,6 +743,15 @@ int bn254_ctx_set_profiling(bn254_ctx *ctx, int enabled);
                                                     size favours a higher value (calls of ONLY one- or two-share tuples lose 0.8 ms to the
                                                     exact call as a whole; tuples of four win).  The option stays for callers who want short
                                                     tuples verified share by share; 0 and 1 mean the same */
+#define BN254_OPT_MERGE_WAVE_MIN_PARTS 43 /* bn254_batch_merge_keyed_bitmap, developer option: tuples with at least this many partials are merged by
+                                            one wave each (select parallel in the words of the row, 64 partial sums and a tree), shorter
+                                            ones by one lane each; >= 1.  Default 16, from the sweep of tools/merge_throughput.py --sweep
+                                            (select-and-sum ms, lane / wave, 16 384 partials per call): rows of 8 words — 8 partials 0.15 /
+                                            0.41, 16 0.25 / 0.40, 32 0.44 / 0.30, 64 0.82 / 0.24, 256 3.10 / 0.36; rows of 128 words — 4 0.26
+                                            / 0.63, 8 0.45 / 0.42, 16 0.84 / 0.42, 32 1.60 / 0.32, 256 12.4 / 0.49.  The crossing lies
+                                            between 16 and 32 partials at 8 words and at 8 at 128 words; 16 loses 0.15 ms at (8 words, 16
+                                            partials) where 32 would lose 0.42 ms at (128 words, 16 partials).  Lengths between the
+                                            powers of two were not measured.  Same bytes either way */
 int bn254_ctx_set_option(bn254_ctx *ctx, int option, int value);
 /* per-kernel times of the last verify-shaped call with profiling on (HIP events on the call's stream):
  * ms[0] decode, ms[1] hash-to-G1, ms[2] Miller loop, ms[3] final exponentiation.  The host-pointer bn254_batch_verify runs
@@ -690,7 +766,9 @@ int bn254_ctx_set_option(bn254_ctx *ctx, int option, int value);
  * exact re-checks of failed groups;
  * collect_keyed_bitmap_optimistic on its optimistic route ms[0] = front end (hash, range rule, pre-check) + provisional sum, ms[1] = the
  * aggregate keys, ms[2] = the tuples' Miller loop and final exponentiation, ms[3] = exact fallback + re-sum (a call whose tuples are checked
- * in several pieces: ms[1] runs from the provisional sum to the last piece's keys). */
+ * in several pieces: ms[1] runs from the provisional sum to the last piece's keys);
+ * merge_keyed_bitmap the exact collect's four: ms[0] = front end (hash-to-G1 once per tuple, decode, spread, aggregate keys), ms[1] =
+ * select-and-sum (it runs last), ms[2] Miller loop, ms[3] final exponentiation (the last slice's). */
 int bn254_ctx_last_kernel_ms(bn254_ctx *ctx, float ms[4]);
 /* with BN254_OPT_CLOCK_PROBE on: achieved shader clock in MHz of the lane-pair Miller kernels [0], final exponentiations [1] and probe
  * kernels (bn254_probe_issue_rate, bn254_probe_leaf_floor) [2] launched on this context SINCE THE PREVIOUS CALL of this function (or

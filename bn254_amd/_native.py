@@ -111,6 +111,8 @@ def load():
         L.bn254_debug_key_cache_last.argtypes = [vp, ctypes.POINTER(ctypes.c_uint32)]
     if hasattr(L, "bn254_debug_key_tables"):         # absent from an older build loaded through BN254_LIB
         L.bn254_debug_key_tables.argtypes = [vp, i32, sz, sz, vp, vp, vp, vp]
+    if hasattr(L, "bn254_debug_key_fold_tables"):    # absent from an older build loaded through BN254_LIB
+        L.bn254_debug_key_fold_tables.argtypes = [vp, sz, sz, vp]
     if hasattr(L, "bn254_debug_agg_tables"):         # absent from an older build loaded through BN254_LIB
         L.bn254_debug_agg_tables.argtypes = [vp, i32, sz, sz, vp, vp]
     L.bn254_debug_agg_rand_last.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
@@ -224,7 +226,7 @@ EXPORTED_SYMBOLS = [
     "bn254_batch_g1_add", "bn254_batch_g2_add", "bn254_batch_g1_mul", "bn254_batch_g2_mul", "bn254_batch_g1_mul_device",
     "bn254_batch_g2_mul_device", "bn254_batch_sign", "bn254_batch_sign_device", "bn254_batch_g1_sum", "bn254_batch_g2_sum",
     "bn254_batch_aggregate_verify", "bn254_batch_aggregate_verify_device", "bn254_ctx_register_pools", "bn254_ctx_register_pools_device",
-    "bn254_batch_aggregate_verify_registered", "bn254_batch_aggregate_verify_registered_device", "bn254_batch_aggregate_verify_distinct", "bn254_batch_aggregate_verify_distinct_device", "bn254_batch_aggregate_verify_distinct_keyed", "bn254_batch_aggregate_verify_distinct_keyed_device", "bn254_batch_aggregate_verify_distinct_keyed_randomized", "bn254_batch_aggregate_verify_distinct_keyed_randomized_device", "bn254_batch_g1_decompress", "bn254_batch_g2_decompress", "bn254_debug_fp_op", "bn254_debug_fp12_op", "bn254_debug_final_exp_limbs", "bn254_debug_miller_loop", "bn254_debug_hash_candidate", "bn254_debug_route_table", "bn254_debug_key_dedup_last", "bn254_debug_key_cache_last", "bn254_debug_key_tables", "bn254_debug_agg_tables", "bn254_debug_agg_rand_last", "bn254_debug_agg_rand_sums", "bn254_probe_issue_rate", "bn254_probe_leaf_floor", "bn254_probe_fe_program", "bn254_ctx_set_profiling", "bn254_ctx_last_kernel_ms", "bn254_ctx_set_option", "bn254_ctx_last_clocks", "bn254_ctx_expect_msgs_len", "bn254_ctx_register_keys", "bn254_batch_verify_keyed", "bn254_batch_verify_keyed_device", "bn254_batch_verify_keyed_randomized", "bn254_batch_verify_keyed_randomized_device",
+    "bn254_batch_aggregate_verify_registered", "bn254_batch_aggregate_verify_registered_device", "bn254_batch_aggregate_verify_distinct", "bn254_batch_aggregate_verify_distinct_device", "bn254_batch_aggregate_verify_distinct_keyed", "bn254_batch_aggregate_verify_distinct_keyed_device", "bn254_batch_aggregate_verify_distinct_keyed_randomized", "bn254_batch_aggregate_verify_distinct_keyed_randomized_device", "bn254_batch_g1_decompress", "bn254_batch_g2_decompress", "bn254_debug_fp_op", "bn254_debug_fp12_op", "bn254_debug_final_exp_limbs", "bn254_debug_miller_loop", "bn254_debug_hash_candidate", "bn254_debug_route_table", "bn254_debug_key_dedup_last", "bn254_debug_key_cache_last", "bn254_debug_key_tables", "bn254_debug_key_fold_tables", "bn254_debug_agg_tables", "bn254_debug_agg_rand_last", "bn254_debug_agg_rand_sums", "bn254_probe_issue_rate", "bn254_probe_leaf_floor", "bn254_probe_fe_program", "bn254_ctx_set_profiling", "bn254_ctx_last_kernel_ms", "bn254_ctx_set_option", "bn254_ctx_last_clocks", "bn254_ctx_expect_msgs_len", "bn254_ctx_register_keys", "bn254_batch_verify_keyed", "bn254_batch_verify_keyed_device", "bn254_batch_verify_keyed_randomized", "bn254_batch_verify_keyed_randomized_device",
     "bn254_batch_verify_keyed_bitmap", "bn254_batch_verify_keyed_bitmap_device",
     "bn254_batch_verify_keyed_bitmap_randomized", "bn254_batch_verify_keyed_bitmap_randomized_device", "bn254_debug_bitmap_rand_last",
     "bn254_debug_bitmap_rand_sums", "bn254_batch_collect_keyed_bitmap", "bn254_batch_collect_keyed_bitmap_device",

@@ -278,6 +278,30 @@ int bn254_debug_key_tables(bn254_ctx* c, int which, size_t first, size_t count, 
   if (inf) HIP_TRY(hipMemcpy(inf, src_inf + first, count, hipMemcpyDeviceToHost));
   return 0;
 }
+// the folded rows (kd.fold) of the keys of the last key dedup, in the order and under the conditions of bn254_debug_key_tables(which = 0)
+int bn254_debug_key_fold_tables(bn254_ctx* c, size_t first, size_t count, int32_t* rows_out) {
+  if (!c || !rows_out) return BN254_E_BAD_ARGUMENT;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipDeviceSynchronize());
+  const size_t per_key = (size_t)BN_N_FOLD_ROWS * BN_KEY_FOLD_WORDS;
+  uint32_t ctl[KD_CTL_WORDS];
+  if (!c->kd_last_run || !c->kd_ctl || !c->kd_fold_last) return BN254_E_BAD_ARGUMENT;
+  HIP_TRY(hipMemcpy(ctl, c->kd_ctl, sizeof ctl, hipMemcpyDeviceToHost));
+  if (first + count > ctl[KD_CTL_D] || first + count > c->kd_keys_cap) return BN254_E_BAD_ARGUMENT;
+  if (ctl[KD_CTL_BUILD] + ctl[KD_CTL_HITS] != ctl[KD_CTL_D]) return BN254_E_BAD_ARGUMENT;   // a call the thresholds refused: it has no tables
+  if (count == 0) return 0;
+  uint32_t* rows = (uint32_t*)malloc(count * sizeof(uint32_t));
+  if (!rows) return BN254_E_NO_MEMORY;
+  hipError_t e = hipMemcpy(rows, c->kd_row_of_last + first, count * sizeof(uint32_t), hipMemcpyDeviceToHost);
+  int rc = e == hipSuccess ? 0 : -(int)e;
+  for (size_t k = 0; k < count && !rc; ++k) {
+    if (rows[k] >= c->kd_keys_cap) { rc = BN254_E_BAD_ARGUMENT; break; }
+    e = hipMemcpy(rows_out + k * per_key, c->kd_fold_last + (size_t)rows[k] * per_key, per_key * sizeof(int32_t), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) rc = -(int)e;
+  }
+  free(rows);
+  return rc;
+}
 static int debug_rand_last(bn254_ctx* c, int ran, const uint32_t* stats, uint64_t out[6]) {
   if (!c || !out) return BN254_E_BAD_ARGUMENT;
   for (int i = 0; i < 6; ++i) out[i] = 0;

@@ -529,6 +529,7 @@ static int kd_reserve(bn254_ctx* c, size_t n, KeyDedup& kd) {
     c->kd_items_cap = c->kd_keys_cap = 0;
     c->kd_ctl = nullptr;
     c->kd_lines_last = nullptr;
+    c->kd_fold_last = nullptr;
     c->kd_cache_valid = false;                         // the cache lived in the freed buffer: the next call starts from an empty one
     if (hipMalloc((void**)&c->kd_buf, items_cap * KD_BYTES_PER_ITEM + keys_cap * KD_BYTES_PER_KEY + 512) != hipSuccess) {
       (void)hipGetLastError();                       // no room for the tables: this call takes the generic route (the caller sees no error)
@@ -547,7 +548,8 @@ static int kd_reserve(bn254_ctx* c, size_t n, KeyDedup& kd) {
   kd.slot_of = (uint32_t*)take(c->kd_items_cap * 4);
   kd.key_idx = (uint32_t*)take(c->kd_items_cap * 4);
   kd.lines = (int32_t*)take(c->kd_keys_cap * BN_N_FIXED_LINES * BN_KEY_LINE_WORDS * 4);
-  kd.c2 = (int32_t*)take(c->kd_keys_cap * BN_N_FIXED_LINES * 2 * BN_LIMBS * 4);
+  kd.fold = (int32_t*)take(c->kd_keys_cap * KD_FOLD_KEY_WORDS * 4);
+  kd.c2 = kd.fold;                                                   // a key's raw c2 while it is built, its folded rows afterwards (bn254_ws.h)
   kd.rep = (uint32_t*)take(c->kd_keys_cap * 4);
   kd.ctl = (uint32_t*)take(KD_CTL_WORDS * 4);
   c->kd_ctl = kd.ctl;
@@ -562,7 +564,7 @@ static int kd_reserve(bn254_ctx* c, size_t n, KeyDedup& kd) {
   kd.c_index = (uint32_t*)take(4 * c->kd_keys_cap * 4);
   kd.c_state = (uint32_t*)take(4);
   kd.index_mask = (uint32_t)(index_slots - 1);
-  c->kd_lines_last = kd.lines; c->kd_rep_last = kd.rep; c->kd_st_last = kd.st; c->kd_inf_last = kd.inf; c->kd_row_of_last = kd.row_of;
+  c->kd_lines_last = kd.lines; c->kd_fold_last = kd.fold; c->kd_rep_last = kd.rep; c->kd_st_last = kd.st; c->kd_inf_last = kd.inf; c->kd_row_of_last = kd.row_of;
   kd.slot_mask = (uint32_t)(slots - 1);
   kd.hash_mask = c->kd_hash_bits > 0 && c->kd_hash_bits < 32 ? (1u << c->kd_hash_bits) - 1 : 0xFFFFFFFFu;
   kd.max_keys = (uint32_t)keys;
@@ -812,6 +814,7 @@ int bn254_ctx_create(int hip_device, bn254_ctx** out) {
   c->key_dedup = 1;
   c->kd_max_keys = KEY_DEDUP_MAX_KEYS_DEFAULT;
   c->kd_min_mult = KEY_DEDUP_MIN_MULT_DEFAULT;
+  c->kd_fold = KEY_DEDUP_FOLD_DEFAULT;
   c->kd_cache = 1;
   c->bm_table_max_keys = BITMAP_TABLE_MAX_KEYS_DEFAULT;
   c->device = hip_device;
@@ -972,6 +975,7 @@ int bn254_ctx_set_option(bn254_ctx* c, int option, int value) {
   if (option == BN254_OPT_KEY_DEDUP) { if (value < 0 || value > 1) return BN254_E_BAD_ARGUMENT; c->key_dedup = value; return 0; }
   if (option == BN254_OPT_KEY_DEDUP_MAX_KEYS) { if (value < 0 || value > KEY_DEDUP_MAX_KEYS_LIMIT) return BN254_E_BAD_ARGUMENT; c->kd_max_keys = value; return 0; }
   if (option == BN254_OPT_KEY_DEDUP_MIN_MULT) { if (value < 1) return BN254_E_BAD_ARGUMENT; c->kd_min_mult = value; return 0; }
+  if (option == BN254_OPT_KEY_DEDUP_FOLD) { if (value < 0 || value > 1) return BN254_E_BAD_ARGUMENT; c->kd_fold = value; return 0; }
   if (option == BN254_OPT_KEY_DEDUP_FORCE_GENERIC) { c->kd_force_generic = value == 2 ? 2 : value != 0; return 0; }
   if (option == BN254_OPT_KEY_CACHE) { if (value < 0 || value > 1) return BN254_E_BAD_ARGUMENT; c->kd_cache = value; c->kd_cache_valid = false; return 0; }
   if (option == BN254_OPT_KEY_DEDUP_HASH_BITS) { if (value < 0 || value > 32) return BN254_E_BAD_ARGUMENT; c->kd_hash_bits = value; return 0; }
@@ -1083,7 +1087,9 @@ static int verify_tail(bn254_ctx* c, hipStream_t s, size_t n, uint8_t* d_status,
     // once.  The wait for the builder counts in the Miller stage.
     HIP_TRY(hipStreamWaitEvent(s, c->kd_join, 0));
     const KeyTable kt = {kd->lines, kd->st, kd->inf, kd->max_keys};
-    if ((rc = bn254_pair_miller_verify_keyed(n, c->ws, kd->key_idx, kt, s, 0, nullptr, kd->ctl + KD_CTL_KEYED_N))) return rc;
+    if (c->kd_fold) rc = bn254_pair_miller_verify_keyed_fold(n, c->ws, kd->key_idx, kt, kd->fold, s, 0, nullptr, kd->ctl + KD_CTL_KEYED_N);
+    else rc = bn254_pair_miller_verify_keyed(n, c->ws, kd->key_idx, kt, s, 0, nullptr, kd->ctl + KD_CTL_KEYED_N);
+    if (rc) return rc;
     if ((rc = bn254_pair_miller_verify(n, c->ws, nullptr, kd->ctl + KD_CTL_GENERIC_N, s))) return rc;
     PROF_MARK(3);
     if ((rc = bn254_pair_final_exp(n, c->ws, 1, d_status, nullptr, nullptr, s))) return rc;

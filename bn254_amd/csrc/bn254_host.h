@@ -89,6 +89,7 @@ struct bn254_ctx {
   int kd_max_keys;           // BN254_OPT_KEY_DEDUP_MAX_KEYS
   int kd_min_mult;           // BN254_OPT_KEY_DEDUP_MIN_MULT
   int kd_force_generic;      // BN254_OPT_KEY_DEDUP_FORCE_GENERIC (developer hook): 1 = the device-side decision always says "generic", 2 = the builder reports a degenerate line
+  int kd_fold;               // BN254_OPT_KEY_DEDUP_FOLD (developer option): the keyed Miller kernel on the folded rows (k_miller_verify_keyed_fold_pair)
   int kd_hash_bits;          // BN254_OPT_KEY_DEDUP_HASH_BITS (test seam): bits of the key hash kept (0 = all), to force collisions
   hipStream_t kd_stream;     // the dedup and the table builder run here, forked from and joined into the call's stream
   hipEvent_t kd_fork, kd_join;
@@ -101,6 +102,7 @@ struct bn254_ctx {
   size_t kd_items_cap, kd_keys_cap;
   uint32_t* kd_ctl;          // the device-side decision of the last call that ran the dedup (bn254_debug_key_dedup_last)
   const int32_t* kd_lines_last;   // ... and its tables, representatives, statuses and identity flags (bn254_debug_key_tables; into kd_buf)
+  const int32_t* kd_fold_last;    // ... its folded rows (bn254_debug_key_fold_tables)
   const uint32_t* kd_rep_last;
   const uint32_t* kd_row_of_last;   // ... key id of that call -> row of the tables
   const uint8_t *kd_st_last, *kd_inf_last;

@@ -69,6 +69,30 @@ static inline void kd_scale_tree(const Fp2* c0, const Fp2* c1, const Fp2* c2, Fp
 }
 #endif
 
+// FOLDED ROWS.  At a nonzero digit of the loop (and at its end) two lines of the same key multiply f with no squaring between them, both
+// evaluated at the same G1 point (x, y) and both in the c2 = 1 form, so their product is a five-term element whose Fq2 coefficients
+// depend on the key alone (w^6 = xi):
+//   (c0 y + c1 x w + w^3)(c0' y + c1' x w + w^3) = (K0 y^2 + xi) + K1 xy w + K2 x^2 w^2 + K3 y w^3 + K4 x w^4
+//   K0 = c0 c0', K1 = c0 c1' + c1 c0' (Karatsuba: (c0 + c1)(c0' + c1') - K0 - K2), K2 = c1 c1', K3 = c0 + c0', K4 = c1 + c1'
+// kd_fold_pair is that one row from two canonical table lines, canonical again (sites 294 / 295: the two Karatsuba sums of canonical
+// limbs); the tail of k_kd_scale runs it on the lane pairs of a key's BN_N_FOLD_ROWS rows (bn254_constants.h: C_FOLD_FIRST), and
+// miller_loop_keyed_fold (bn254_pairing.h) reads the rows.
+BN_DEV void kd_fold_pair(const Fp2& c0, const Fp2& c1, const Fp2& d0, const Fp2& d1, Fp2 k[5]) {
+  const Fp2 k0 = fp2_mul(c0, d0), k2 = fp2_mul(c1, d1);
+  const Fp2 k1 = fp2_sub(fp2_sub(fp2_mul(NS(294, fp2_add(c0, c1)), NS(295, fp2_add(d0, d1))), k0), k2);
+  const Fp2 k3 = fp2_add(c0, d0), k4 = fp2_add(c1, d1);
+  BN_FOR_ROLES(r) { k[0].c[r] = fp_canon(k0.c[r]); k[1].c[r] = fp_canon(k1.c[r]); k[2].c[r] = fp_canon(k2.c[r]); k[3].c[r] = fp_canon(k3.c[r]); k[4].c[r] = fp_canon(k4.c[r]); }
+}
+#if !defined(__HIPCC__)
+// a key's BN_N_FOLD_ROWS folded rows from its BN_N_FIXED_LINES canonical (c0, c1) rows: the host form of k_kd_scale's tail
+static inline void kd_fold_lines(const Fp2* c0, const Fp2* c1, Fp2 (*fold)[5]) {
+  for (int r = 0; r < BN_N_FOLD_ROWS; ++r) {
+    const int i = C_FOLD_FIRST[r];
+    kd_fold_pair(c0[i], c1[i], c0[i + 1], c1[i + 1], fold[r]);
+  }
+}
+#endif
+
 #if defined(__HIPCC__)
 // One uncompressed G2 point (/root/reference/src/utils.rs:107-116) on a lane pair: each lane reads, range-checks and converts the two
 // 32-byte words of its role; identity, range and curve rules combined over the pair.  The status of k_decode_g2_pair before its optional

@@ -23,7 +23,9 @@
 //                 but keys are not subgroup-checked under flags = 0) sets KD_DEGENERATE.  No key bytes that reach such a line are known (the
 //                 twist's order-10 069 points do not), so BN254_OPT_KEY_DEDUP_FORCE_GENERIC = 2 makes the builder report one for every key it builds
 //   k_kd_scale    one workgroup per key, one lane pair per line: c0 / c2, c1 / c2, canonical — the values of g2_line_table's emit, so the
-//                 tables are word for word those of registration; ONE inversion per key (a product tree over its 87 c2 in LDS)
+//                 tables are word for word those of registration; ONE inversion per key (a product tree over its 87 c2 in LDS).  Its tail
+//                 folds the 22 places where two lines of the key meet with no squaring between them into rows of five coefficients
+//                 (kd.fold; bn254_keydedup.h: kd_fold_pair), which k_miller_verify_keyed_fold_pair reads (BN254_OPT_KEY_DEDUP_FOLD)
 //   k_kd_decide   the route: keyed iff D <= max_keys, D * min_multiplicity <= n, no overflow, no degenerate line; written as the device-side
 //                 item counts the two Miller kernels read at entry (the unchosen one returns at once).  A keyed call COMMITS its build list to
 //                 the cache here (index entries, rows in use); a generic one — forced, or a degenerate line among the keys it built —
@@ -191,7 +193,7 @@ __device__ __forceinline__ Fp2 kd_load_own(const int32_t* src) {
 // per key and lane role a register file in LDS.  Every lane of a key decodes its representative (bn254_keydedup.h: decode_g2_pair_role,
 // the decode of k_decode_g2_pair; no subgroup ladder); a refused key or the identity gets the generator's lines (its pair A is skipped).
 // Then the lane machine's wave-T program: after each step pairs 0 / 1 / 2 store the RAW line's c0, c1 into the key's table row (scaled in
-// place by k_kd_scale) and its c2 into kd.c2.  Lanes 54 .. 63 follow along on copies of the third key, without writing.
+// place by k_kd_scale) and its c2 into kd.c2 (the head of the key's folded rows, which k_kd_scale writes last).  Lanes 54 .. 63 follow along on copies of the third key, without writing.
 #define KD_LM_PER_WAVE 3                           // keys per wave
 #define KD_LM_LANES 18                             // lanes per key: nine lane pairs
 #define KD_LM_ROLE_STRIDE (LS_KD_SLOTS * BN_LIMBS + 1)
@@ -282,7 +284,7 @@ KERNEL_KD_LM void k_kd_lines(const uint8_t* pks, uint32_t flags, KeyDedup kd, in
     for (int k = 0; k < 5; ++k) m.e[lv].w[k] = t[m.pair].w[k];
   }
   m.rows = kd.lines + (size_t)row * BN_N_FIXED_LINES * BN_KEY_LINE_WORDS;
-  m.c2s = kd.c2 + (size_t)row * BN_N_FIXED_LINES * 2 * BN_LIMBS;
+  m.c2s = kd.c2 + (size_t)row * KD_FOLD_KEY_WORDS;
   m.degenerate = false;
   KD_LM_FENCE();
   kd_builder_program(m);
@@ -306,7 +308,7 @@ KERNEL_KD_PAIR void k_kd_scale(KeyDedup kd) {
   int32_t* row = kd.lines + ((size_t)j * BN_N_FIXED_LINES + (line ? p : 0u)) * BN_KEY_LINE_WORDS;
   {
     Fp2 leaf = fp2_one();
-    if (line) leaf = fp2_reduce_weak(kd_load_own(kd.c2 + ((size_t)j * BN_N_FIXED_LINES + p) * KD_NODE_WORDS));   // site 290's default, for the raw slot value
+    if (line) leaf = fp2_reduce_weak(kd_load_own(kd.c2 + (size_t)j * KD_FOLD_KEY_WORDS + p * KD_NODE_WORDS));   // site 290's default, for the raw slot value
     kd_store_own(prod + (KD_TREE_LEAVES + p) * KD_NODE_WORDS, leaf);
   }
   __syncthreads();
@@ -329,13 +331,28 @@ KERNEL_KD_PAIR void k_kd_scale(KeyDedup kd) {
     }
     __syncthreads();
   }
-  if (!line) return;
-  const Fp2 c2inv = kd_load_own(inv + (KD_TREE_LEAVES + p) * KD_NODE_WORDS);
-  const Fp2 a = fp2_mul(kd_load_own(row), c2inv), b = fp2_mul(kd_load_own(row + 2 * BN_LIMBS), c2inv);
-  Fp2 r0, r1;
-  BN_FOR_ROLES(k) { r0.c[k] = fp_canon(a.c[k]); r1.c[k] = fp_canon(b.c[k]); }
-  kd_store_own(row, r0);
-  kd_store_own(row + 2 * BN_LIMBS, r1);
+  if (line) {
+    const Fp2 c2inv = kd_load_own(inv + (KD_TREE_LEAVES + p) * KD_NODE_WORDS);
+    const Fp2 a = fp2_mul(kd_load_own(row), c2inv), b = fp2_mul(kd_load_own(row + 2 * BN_LIMBS), c2inv);
+    Fp2 r0, r1;
+    BN_FOR_ROLES(k) { r0.c[k] = fp_canon(a.c[k]); r1.c[k] = fp_canon(b.c[k]); }
+    kd_store_own(row, r0);
+    kd_store_own(row + 2 * BN_LIMBS, r1);
+    // ... and into the leaves of the two trees, which nobody reads any more (the last level down has passed its barrier; the leaf of `inv`
+    // was this pair's own): the folded rows below take both lines of a row from there
+    kd_store_own(prod + (KD_TREE_LEAVES + p) * KD_NODE_WORDS, r0);
+    kd_store_own(inv + (KD_TREE_LEAVES + p) * KD_NODE_WORDS, r1);
+  }
+  __syncthreads();
+  // THE FOLDED ROWS (bn254_keydedup.h: kd_fold_pair; host form kd_fold_lines): lane pair r < BN_N_FOLD_ROWS folds lines C_FOLD_FIRST[r] and the next
+  if (p >= BN_N_FOLD_ROWS) return;
+  const uint32_t first = C_FOLD_FIRST[p];
+  Fp2 k[5];
+  kd_fold_pair(kd_load_own(prod + (KD_TREE_LEAVES + first) * KD_NODE_WORDS), kd_load_own(inv + (KD_TREE_LEAVES + first) * KD_NODE_WORDS),
+               kd_load_own(prod + (KD_TREE_LEAVES + first + 1) * KD_NODE_WORDS), kd_load_own(inv + (KD_TREE_LEAVES + first + 1) * KD_NODE_WORDS), k);
+  int32_t* frow = kd.fold + (size_t)j * KD_FOLD_KEY_WORDS + p * BN_KEY_FOLD_WORDS;   // over the row's raw c2: every leaf was loaded before the first barrier
+#pragma unroll
+  for (int e = 0; e < 5; ++e) kd_store_own(frow + e * 2 * BN_LIMBS, k[e]);
 }
 KERNEL_KD void k_kd_decide(size_t n, KeyDedup kd, int force_generic, int cache_on) {
   const bool keyed = force_generic != 1 && kd_viable(kd, n) && (kd.ctl[KD_CTL_FLAGS] & KD_DEGENERATE) == 0;   // every lane the same

@@ -212,6 +212,63 @@ int bn254_pair_miller_verify_keyed(size_t n, Ws ws, const uint32_t* key_idx, Key
   HIP_TRY(hipGetLastError());
   return 0;
 }
+// the monomial store of miller_loop_keyed_fold: planes PL_F0 .. PL_F0 + 5 at the verify's own workspace index — where the kernel writes its
+// result at the very end, free until then.  Both lanes of a pair write the same words and each reads back what it wrote itself.
+struct WsMonomials {     // (handed to the loop by value; a reference would put it into the private segment)
+  int32_t* f0;           // plane PL_F0 (wave-uniform)
+  size_t stride;
+  uint32_t i;            // the verify's workspace index
+  __device__ __forceinline__ void uniform() {
+    f0 = (int32_t*)bn_wave_uniform(f0);
+    stride = ((size_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(stride >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)stride);
+  }
+  __device__ __forceinline__ void put(int pair, int j, const Fp& x) {
+#pragma unroll
+    for (int k = 0; k < BN_LIMBS; ++k) f0[((size_t)(3 * pair + j) * BN_LIMBS + k) * stride + i] = x.v[k];
+  }
+  __device__ __forceinline__ Fp get(int pair, int j) const {
+    Fp r;
+#pragma unroll
+    for (int k = 0; k < BN_LIMBS; ++k) r.v[k] = f0[((size_t)(3 * pair + j) * BN_LIMBS + k) * stride + i];
+    return r;
+  }
+};
+// The same verify on the key's FOLDED rows (key dedup: bn254_keydedup.hip builds them beside the plain rows; bn254_pairing.h:
+// miller_loop_keyed_fold): `fold` = [key][BN_N_FOLD_ROWS][K0 .. K4][re / im][limb].  Per verify 43 plain rows of 144 B and 22 folded rows of
+// 360 B per pair of lanes.  Same status merge and the same count / map / base contract as k_miller_verify_keyed_pair.
+KERNEL_PAIR void k_miller_verify_keyed_fold_pair(size_t n, Ws ws, const uint32_t* key_idx, KeyTable kt, const int32_t* fold, size_t base, const uint32_t* map,
+                                                 const uint32_t* count) {
+  size_t i = ((size_t)blockIdx.x * BN_PAIR_WG + threadIdx.x) >> 1;
+  if (i >= n) return;
+  if (count && i >= *count) return;
+  if (map) i = map[i];
+  uint32_t key = key_idx[i];
+  i += base;
+  uint8_t kst = ST_OK;
+  if (key >= kt.n_keys) { kst = ST_INDEX_OOB; key = 0; }
+  else kst = kt.st[key];
+  const bool key_inf = kst != ST_OK || kt.inf[key] != 0;      // a refused key walks the loop as a skipped pair
+  if ((threadIdx.x & 1u) == 0) {
+    const uint8_t prev = ws_byte(ws, BY_ST_DECODE, i);
+    ws_byte(ws, BY_ST_DECODE, i) = prev != ST_OK ? prev : kst;
+  }
+  G1Affine sig, h;
+  ws_load_g1(ws, PL_P1X, BY_P1_INF, i, sig);
+  ws_load_g1(ws, PL_P2X, BY_P2_INF, i, h);
+  __shared__ Fp12PairSlot lds_f[BN_PAIR_WG];
+  Fp12& f = lds_f[threadIdx.x].v;
+  const WsMonomials mono = {ws.planes + (size_t)PL_F0 * BN_LIMBS * ws.stride, ws.stride, (uint32_t)i};
+  BN_CLK_BEGIN(ws);
+  miller_loop_keyed_fold<true>(f, h, key_inf, kt.lines, fold, key, sig, mono);
+  BN_CLK_END(ws, 0);
+  ws_store_f12_own(ws, i, f);
+}
+int bn254_pair_miller_verify_keyed_fold(size_t n, Ws ws, const uint32_t* key_idx, KeyTable kt, const int32_t* fold, hipStream_t s, size_t base,
+                                        const uint32_t* map, const uint32_t* count) {
+  k_miller_verify_keyed_fold_pair<<<(unsigned)((2 * n + BN_PAIR_WG - 1) / BN_PAIR_WG), BN_PAIR_WG, 0, s>>>(n, ws, key_idx, kt, fold, base, map, count);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
 // generic single pair per lane pair: f = miller(P1, Q)   (bn254_batch_pairing*)
 KERNEL_PAIR void k_miller_var_pair(size_t n, Ws ws) {
   size_t i = ((size_t)blockIdx.x * BN_PAIR_WG + threadIdx.x) >> 1;

@@ -248,6 +248,109 @@ BN_DEVM void miller_loop_keyed(Fp12& f, const G1Affine& pa, bool key_inf, const 
   step();
   step();
 }
+#if defined(BN_SPLIT_FP2)      // (the pair layout only: bn254_pair.hip and its host emulation)
+// ---- the keyed loop on FOLDED rows (key dedup of the exact verify; bn254_keydedup.h: kd_fold_pair) ------------------------------------
+// Where two lines of one pair meet with no squaring between them — the doubling and the addition line of a nonzero digit (21 steps), the
+// two closing lines — miller_loop_keyed multiplies lineA lineB twice: (dbl_A dbl_B), then (add_A add_B).  Both lines of a pair are taken at
+// the same point (x, y) and have c2 = 1, so the product of the two lines OF ONE PAIR is
+//   G = (K0 y^2 + xi) + K1 xy w + K2 x^2 w^2 + K3 y w^3 + K4 x w^4
+// with K0 .. K4 functions of the key alone (tabulated: `fold`, and C_NEG_G2_FOLD for -G2): f <- f G_A, then f <- f G_B.  Five scalings per
+// G against the three Fq2 products and four scalings of each line pair: 46 dual + 10 single product slots at such a step instead of
+// 52 + 8.  G has the five-term shape fp12_mul_line2 takes; a skipped pair contributes G = 1.
+// The six monomials x^2, xy, y^2 of the two G1 points are computed once and kept OUTSIDE the registers, in a store the caller hands in
+// (`mono.put(pair, j, v)` / `mono.get(pair, j)`, pair 0 = A, 1 = B; j = 0 x^2, 1 xy, 2 y^2): the loop body is at the register limit of two waves
+// per SIMD without them, and six more live field elements (54 registers) went to the private segment — 130 stores and 329 reloads in the loop.
+// G1MonomialValues is the plain store (host builds); the kernel's store is a piece of the workspace (bn254_pair.hip: WsMonomials).
+#if defined(__HIPCC__)
+#define BN_MEMBER __device__ __forceinline__
+#else
+#define BN_MEMBER inline
+#endif
+struct G1MonomialValues {
+  Fp v[2][3];
+  BN_MEMBER void put(int pair, int j, const Fp& x) { v[pair][j] = x; }
+  BN_MEMBER Fp get(int pair, int j) const { return v[pair][j]; }
+  BN_MEMBER void uniform() {}
+};
+template <class Mono>
+BN_DEV void g1_monomials_put(Mono& mono, int pair, const G1Affine& p) {
+  BN_FOR_ROLES(k) {                       // every lane of the pair computes its own copy (the host emulation counts per role, as the device spends)
+    mono.put(pair, 0, fp_sqr(p.x)); mono.put(pair, 1, fp_mul(p.x, p.y)); mono.put(pair, 2, fp_sqr(p.y));
+  }
+}
+struct LineProduct { Fp6 b0; Fp2 b10, b11; };     // b0 + (b10 + b11 v) w: what fp12_mul_line2 takes
+template <int S, class Mono>
+BN_DEV void folded_row_product(LineProduct& L, const int32_t (*row)[2][BN_LIMBS], const G1Affine& p, const Mono& mono, int pair, bool skip, bool any_skip) {   // site S
+  L.b0.c0 = NS(S, fp2_add(fp2_mul_fp(fp2_load_const(row[0]), mono.get(pair, 2)), fp2_load_const(C_XI_MONT)));
+  L.b0.c1 = fp2_mul_fp(fp2_load_const(row[2]), mono.get(pair, 0));
+  L.b0.c2 = fp2_mul_fp(fp2_load_const(row[4]), p.x);
+  L.b10 = fp2_mul_fp(fp2_load_const(row[1]), mono.get(pair, 1));
+  L.b11 = fp2_mul_fp(fp2_load_const(row[3]), p.y);
+  if (any_skip) {
+    const Fp2 zero = fp2_zero();
+    L.b0.c0 = fp2_select(skip, fp2_one(), L.b0.c0);
+    L.b0.c1 = fp2_select(skip, zero, L.b0.c1);
+    L.b0.c2 = fp2_select(skip, zero, L.b0.c2);
+    L.b10 = fp2_select(skip, zero, L.b10);
+    L.b11 = fp2_select(skip, zero, L.b11);
+  }
+}
+// f = miller(pa, key) * miller(pb, -G2), the value of miller_loop_keyed: `lines` = per key 87 x (c0, c1), `folds` = per key BN_N_FOLD_ROWS x
+// (K0 .. K4) as [row][coefficient][re / im][limb].  The 43 steps with a zero digit are miller_loop_keyed's; folded row r stands for
+// table lines C_FOLD_FIRST[r] and the next (bn254_constants.h).
+// `lines` / `folds` are the tables of ALL keys (wave-uniform) and `key` the lane's row: the loop is a real function, whose pointer arguments
+// arrive in vector registers; the uniform ones go back into scalar registers here, and one word per lane names the two tables
+// (a second per-lane pointer, live through the Fq12 bodies, cost them 100 more spilled registers).
+template <class T> BN_DEV const T* bn_wave_uniform(const T* p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const uint64_t v = (uint64_t)p;
+  return (const T*)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v));
+#else
+  return p;
+#endif
+}
+template <bool F_LDS = false, class Mono>
+BN_DEVM void miller_loop_keyed_fold(Fp12& f, const G1Affine& pa, bool key_inf, const int32_t* lines, const int32_t* folds, uint32_t key, const G1Affine& pb,
+                                    Mono mono) {   // sites 286, 287
+  if constexpr (F_LDS) BN_ASSUME_LDS(&f);
+  fp12_set_one(f);
+  lines = bn_wave_uniform(lines); folds = bn_wave_uniform(folds);
+  mono.uniform();
+  typedef const int32_t (*LinePtr)[2][2][BN_LIMBS];
+  typedef const int32_t (*FoldPtr)[5][2][BN_LIMBS];
+  const bool skip_a = pa.inf || key_inf, skip_b = pb.inf;
+#if defined(__HIPCC__)
+  const bool any_skip = __builtin_amdgcn_ballot_w64(skip_a || skip_b) != 0;   // wave-uniform
+#else
+  const bool any_skip = skip_a || skip_b;
+#endif
+  g1_monomials_put(mono, 0, pa);
+  g1_monomials_put(mono, 1, pb);
+  const LinePtr tab = (LinePtr)(lines + (size_t)key * (BN_N_FIXED_LINES * 2 * 2 * BN_LIMBS));
+  const FoldPtr fold = (FoldPtr)(folds + (size_t)key * (BN_N_FOLD_ROWS * 5 * 2 * BN_LIMBS));
+  auto folded_a = [&](int r) { LineProduct L; folded_row_product<286>(L, fold[r], pa, mono, 0, skip_a, any_skip); fp12_mul_line2(f, f, L.b0, L.b10, L.b11); };
+  auto folded_b = [&](int r) { LineProduct L; folded_row_product<287>(L, C_NEG_G2_FOLD[r], pb, mono, 1, skip_b, any_skip); fp12_mul_line2(f, f, L.b0, L.b10, L.b11); };
+  // The order of the statements below is the one whose register allocation keeps every spill store outside the loop (G_B before G_A, two
+  // tests of the digit, the closing rows in the same order, rows and lines counted rather than looked up): every other form tried of the
+  // same multiplications — G_A first, one test, the closing rows as a 65th step, a table of positions, one shared copy of each Fq12 routine —
+  // put ~120 stores and as many reloads into an Fq12 body.  The factors commute.
+  int idx = 0, r = 0;
+  for (int d = 0; d < 64; ++d) {
+    BN_SET_STEP_PRIORITY(d);
+    fp12_sqr(f, f);
+    const bool digit = C_ATE_NAF[d] != 0;     // wave-uniform
+    if (digit) folded_b(r);
+    if (!digit) {
+      KeyLine la;
+      la.c0 = fp2_load_const(tab[idx][0]); la.c1 = fp2_load_const(tab[idx][1]);
+      mul_by_two_table_lines(f, la, pa.x, pa.y, skip_a, idx, pb.x, pb.y, skip_b, any_skip);
+      ++idx;
+    } else { folded_a(r); ++r; idx += 2; }
+  }
+  folded_b(r);                                // the two closing lines: row BN_N_FOLD_ROWS - 1
+  folded_a(r);
+}
+#endif  // BN_SPLIT_FP2
 // mul_by_two_table_lines with lineB = (lb.c0, lb.c1, 1) from a per-lane table instead of the constant one.  A copy rather than a shared
 // body: sharing it moved the register allocation of the keyed verify kernel.  The operands are canonical in both, so the carry sites
 // are the same ones (280 .. 285).

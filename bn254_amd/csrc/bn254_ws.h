@@ -221,6 +221,11 @@ struct KeyTable { const int32_t* lines; const uint8_t* st; const uint8_t* inf; u
 __attribute__((visibility("hidden"))) int bn254_lm_miller_verify_keyed(size_t n, Ws ws, const uint32_t* key_idx, KeyTable kt, hipStream_t s);   // bn254_lmiller.hip: the smallest batches
 __attribute__((visibility("hidden"))) int bn254_pair_miller_verify_keyed(size_t n, Ws ws, const uint32_t* key_idx, KeyTable kt, hipStream_t s, size_t base = 0,
                                                                          const uint32_t* map = nullptr, const uint32_t* count = nullptr);
+// ... on the folded rows of the key dedup (kd.fold: per key BN_N_FOLD_ROWS x (K0 .. K4) x (re, im) x limbs; bn254_pairing.h: miller_loop_keyed_fold)
+#define BN_KEY_FOLD_WORDS (5 * 2 * BN_LIMBS)
+__attribute__((visibility("hidden"))) int bn254_pair_miller_verify_keyed_fold(size_t n, Ws ws, const uint32_t* key_idx, KeyTable kt, const int32_t* fold,
+                                                                              hipStream_t s, size_t base = 0, const uint32_t* map = nullptr,
+                                                                              const uint32_t* count = nullptr);
 // aggregates over distinct messages against registered keys (bn254_aggdist.hip): level 0 over slots of `width` (1 or 2) table pairs whose
 // per-aggregate inclusive slot scan is sl.incl (ceil((hi - lo + 1) / width)); the registered table holds -G2's lines as entry kt.n_keys.
 // Then the aggregates' products from gbase + i to i for the final exponentiation.
@@ -288,9 +293,10 @@ __attribute__((visibility("hidden"))) int bn254_aggd_keyed_slot_map(hipStream_t 
 
 // key deduplication of the exact verify (bn254_keydedup.hip): per call, the distinct keys of the batch and their line tables in the
 // KeyTable format above, built on a stream of the context beside decode and hash; the route (tables or the generic loop) is decided on the device
-#define KEY_DEDUP_MAX_KEYS_DEFAULT 1024            // tables for at most this many distinct keys per call (12.5 KB + 6.3 KB of raw c2 each)
+#define KEY_DEDUP_MAX_KEYS_DEFAULT 1024            // tables for at most this many distinct keys per call (12.5 KB + 7.9 KB of folded rows, which a key's raw c2 shares while it is built)
 #define KEY_DEDUP_MIN_MULT_DEFAULT 16              // ... and only when every key serves this many items on average
-#define KEY_DEDUP_MAX_KEYS_LIMIT 16384             // BN254_OPT_KEY_DEDUP_MAX_KEYS at most (308 MB of tables)
+#define KEY_DEDUP_FOLD_DEFAULT 1                   // BN254_OPT_KEY_DEDUP_FOLD: the keyed Miller loop of the dedup reads the folded rows
+#define KEY_DEDUP_MAX_KEYS_LIMIT 16384             // BN254_OPT_KEY_DEDUP_MAX_KEYS at most (338 MB of tables)
 #define KD_MAX_PROBES 64u                          // open addressing: a longer probe sequence sends the call to the generic route
 #define KD_EMPTY 0xFFFFFFFFu
 enum { KD_OVERFLOW = 1, KD_DEGENERATE = 2 };
@@ -304,7 +310,10 @@ struct KeyDedup {
   uint32_t* rep;       // [max_keys] representative item of the key
   uint32_t* ctl;       // [KD_CTL_WORDS] distinct keys D, flags, item counts of the keyed / generic Miller kernel
   int32_t* lines;      // [max_keys][87][c0, c1][re, im][9]
-  int32_t* c2;         // [max_keys][87][re, im][9] raw c2 of the lines
+  int32_t* c2;         // [max_keys][KD_FOLD_KEY_WORDS] raw c2 of the lines of a key being built: [87][re, im][9] at the head of ...
+  int32_t* fold;       // ... [max_keys][22][K0 .. K4][re, im][9] the folded rows (bn254_keydedup.h: kd_fold_pair), cached and dropped with `lines`.
+                       // ONE buffer (fold == c2): a row's raw c2 is dead once k_kd_scale has loaded it into the leaves of its tree, and
+                       // the workgroup that did so writes the row's folded rows over it at its end
   uint8_t* st;         // [max_keys] decode status of the representative
   uint8_t* inf;        // [max_keys] identity flag
   uint32_t* row_of;    // [max_keys] table row of the call's key id (k_kd_match)
@@ -321,8 +330,10 @@ __attribute__((visibility("hidden"))) int bn254_kd_enqueue(const uint8_t* d_pks,
                                                            int cache_on, hipStream_t s);
 // per-item and per-key bytes of the buffers above (slot arrays: at most 4n words each, the next power of two >= 2n)
 #define KD_BYTES_PER_ITEM ((size_t)(2 * 4 + 2) * sizeof(uint32_t))
-// (per key besides lines and raw c2: rep, row_of, build_row, build_rep, the cache's copy of the key and four index slots, st, inf)
-#define KD_BYTES_PER_KEY ((size_t)BN_N_FIXED_LINES * (BN_KEY_LINE_WORDS + 2 * BN_LIMBS) * sizeof(int32_t) + (4 + 32 + 4) * sizeof(uint32_t) + 2)
+// (per key besides lines and folded rows / raw c2: rep, row_of, build_row, build_rep, the cache's copy of the key and four index slots, st, inf)
+#define KD_FOLD_KEY_WORDS (BN_N_FOLD_ROWS * BN_KEY_FOLD_WORDS)
+static_assert(KD_FOLD_KEY_WORDS >= BN_N_FIXED_LINES * 2 * BN_LIMBS, "a key's raw c2 fits where its folded rows go");
+#define KD_BYTES_PER_KEY ((size_t)(BN_N_FIXED_LINES * BN_KEY_LINE_WORDS + KD_FOLD_KEY_WORDS) * sizeof(int32_t) + (4 + 32 + 4) * sizeof(uint32_t) + 2)
 
 // entry points of bn254_trio.hip (octet layout for small batches)
 __attribute__((visibility("hidden"))) int bn254_trio_miller_verify(size_t n, Ws ws, hipStream_t s, int mode = 0);

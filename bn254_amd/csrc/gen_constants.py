@@ -493,6 +493,28 @@ def main():
     for ln in lines:
         o.append("  {%s, %s, %s}," % (c_fp2(ln[0]), c_fp2(ln[1]), c_fp2(ln[2])))
     o.append("};")
+    # Two consecutive table lines of one pair with no squaring between them (the doubling and the addition line of a nonzero digit; the two
+    # closing lines), both evaluated at P = (x, y), folded into ONE five-term element (w^6 = xi):
+    #   (c0 y + c1 x w + w^3)(c0' y + c1' x w + w^3) = (K0 y^2 + xi) + K1 xy w + K2 x^2 w^2 + K3 y w^3 + K4 x w^4
+    #   K0 = c0 c0', K1 = c0 c1' + c1 c0', K2 = c1 c1', K3 = c0 + c0', K4 = c1 + c1'   (bn254_pairing.h: miller_loop_keyed_fold)
+    fold_first = []
+    idx = 0
+    for d in naf:
+        if d:
+            fold_first.append(idx)
+        idx += 2 if d else 1
+    fold_first.append(idx)
+    assert idx + 2 == len(lines)
+    o.append("#define BN_N_FOLD_ROWS %d" % len(fold_first))
+    o.append("BN_CONST unsigned char C_FOLD_FIRST[BN_N_FOLD_ROWS] = {%s};  /* folded row -> its first table line (the second one follows it); the last row = the two closing lines */" %
+             ", ".join(str(i) for i in fold_first))
+    o.append("/* the folded rows (K0 .. K4) of Q = -G2::one() */")
+    o.append("BN_CONST int32_t C_NEG_G2_FOLD[BN_N_FOLD_ROWS][5][2][BN_LIMBS] = {")
+    for i in fold_first:
+        (a0, a1, _), (b0, b1, _) = lines[i], lines[i + 1]
+        ks = (mul(a0, b0), add(mul(a0, b1), mul(a1, b0)), mul(a1, b1), add(a0, b0), add(a1, b1))
+        o.append("  {%s}," % ", ".join(c_fp2(k) for k in ks))
+    o.append("};")
     o.append("")
     path = os.path.join(here, "bn254_constants.h")
     with open(path, "w") as f:

@@ -47,6 +47,7 @@ OPT_HASH_TAIL_CHUNK = 32           # ... test seam: counters per lane group and 
 OPT_BITMAP_RAND_MIN_TUPLES = 33    # randomised signer bitmaps: the exact bitmap call below this many tuples
 OPT_BITMAP_RAND_GROUP_TUPLES = 34  # ... tuples per group of its combined checks (developer option)
 OPT_BITMAP_RAND_MAX_KEYS = 35      # ... the exact bitmap call when more keys than this are registered
+OPT_KEY_DEDUP_FOLD = 44            # key dedup: the keyed Miller loop reads the keys' folded rows (default 1; 0 = line by line)
 OPT_KEY_CACHE = 36                 # key dedup: the line tables stay between calls, a call builds only unseen keys (default 1; 0 = build all, drops the cache)
 OPT_COLLECT_RAND_MIN_SHARES = 38   # collect_keyed_bitmap_randomized: the exact collect below this many shares (default 65664)
 OPT_COLLECT_RAND_MIN_PER_KEY = 39  # ... and below this many shares per registered key, n_shares // n_keys (default 42); DESIGN.md §10f
@@ -167,6 +168,13 @@ class Engine:
         st, inf = ctypes.create_string_buffer(max(count, 1)), ctypes.create_string_buffer(max(count, 1))
         _check("bn254_debug_key_tables", self._lib.bn254_debug_key_tables(self._h, which, first, count, words, rep, st, inf))
         return list(words), (list(rep)[:count] if which == 0 else None), st.raw[:count], inf.raw[:count]
+
+    def debug_key_fold_tables(self, first, count):
+        """developer hook: the folded rows of the keys first .. first + count - 1 of the last key dedup (OPT_KEY_DEDUP_FOLD)
+        -> count * 22 * 90 ints ([row][K0 .. K4][re, im][9 limbs])"""
+        words = (ctypes.c_int32 * (count * 22 * 90))()
+        _check("bn254_debug_key_fold_tables", self._lib.bn254_debug_key_fold_tables(self._h, first, count, words))
+        return list(words)
 
     def debug_agg_tables_info(self):
         """developer hook: which tables the registered pools have -> dict(n_groups, groups4, wide2, wide1, t4_builder: 0 none, 1 pairs + quads,

@@ -697,7 +697,7 @@ int bn254_ctx_set_profiling(bn254_ctx *ctx, int enabled);
                                 bn254_ctx_register_keys), beside the decode and hash kernels on a stream of the context; the Miller loop then reads
                                 the tables (k_miller_verify_keyed_pair) when the thresholds below hold, decided on the device without a host sync.
                                 0 = always the generic loop.  Same status bytes either way */
-#define BN254_OPT_KEY_DEDUP_MAX_KEYS 21 /* ... tables for at most this many distinct keys per call (default 1024; 18.8 KB of device memory each) */
+#define BN254_OPT_KEY_DEDUP_MAX_KEYS 21 /* ... tables for at most this many distinct keys per call (default 1024; 20.6 KB of device memory each) */
 #define BN254_OPT_KEY_DEDUP_MIN_MULT 22 /* ... and only when the batch has at least this many items per distinct key (default 16) */
 #define BN254_OPT_KEY_CACHE 36 /* ... 1 (default) = the line tables stay in the context between calls, found again by the key's 128 bytes (the
                                 context keeps its own copy; the caller's buffer may be freed or rewritten): a call builds only the keys no
@@ -903,6 +903,11 @@ int bn254_mgpu_batch_hash_to_g1(bn254_mgpu *mg, const uint8_t *msgs, const uint6
                                              Miller loop (the fallback path of an overflowing or degenerate batch); 2 = the table builder reports a
                                              degenerate line (flags bit 1) for every key it builds — no key bytes that reach one are known —, so the
                                              device takes the decision it takes for such a key: generic loop, nothing cached; default 0 */
+#define BN254_OPT_KEY_DEDUP_FOLD 44 /* key dedup: 1 (default) = the keyed Miller loop of the dedup reads each key's 22 FOLDED rows — the product of the two
+                                    lines of a key that meet with no squaring between them (a nonzero digit's doubling and addition line, the two
+                                    closing lines), five Fq2 coefficients per row, built with the key's plain rows and cached with them — and
+                                    multiplies one folded element per pair there (k_miller_verify_keyed_fold_pair); 0 = line by line
+                                    (k_miller_verify_keyed_pair).  The rows are built either way.  Same status bytes. */
 #define BN254_OPT_KEY_DEDUP_HASH_BITS 24 /* test seam: keep only this many low bits of the key hash of the dedup table (0 = all, default), so that
                                          distinct keys collide: the full 128-byte compare and the probe bound (overflow -> generic loop) */
 #define BN254_OPT_AGGD_KEYED_ROUTE 25 /* bn254_batch_aggregate_verify_distinct_keyed: 0 (default) = by size; 1 / 2 = the table-driven slot kernel with
@@ -939,6 +944,10 @@ int bn254_debug_key_cache_last(bn254_ctx *ctx, uint32_t out[5]);
  * (more keys than BN254_OPT_KEY_DEDUP_MAX_KEYS, too few items per key, a probe overflow) returns BN254_E_BAD_ARGUMENT and writes nothing: such
  * a call looks no key up and builds no table.  Synchronises the device. */
 int bn254_debug_key_tables(bn254_ctx *ctx, int which, size_t first, size_t count, int32_t *lines, uint32_t *rep, uint8_t *st, uint8_t *inf);
+/* ... and the FOLDED rows of the keys of the last key deduplication (BN254_OPT_KEY_DEDUP_FOLD), keys first .. first + count - 1 in the order of
+ * bn254_debug_key_tables(which = 0), each read from the cache row that holds it: rows = count x 22 x 90 words ([row][K0 .. K4][re, im][9
+ * limbs], canonical).  BN254_E_BAD_ARGUMENT, nothing written, where bn254_debug_key_tables(0, ..) returns it.  Synchronises the device. */
+int bn254_debug_key_fold_tables(bn254_ctx *ctx, size_t first, size_t count, int32_t *rows);
 /* the tables of the registered pools (bn254_ctx_register_pools) as they stand on the device: which = the context's pool index — 0 the decoded
  * key pool (n_signers entries), 1 the decoded signature pool (n_msgs * n_signers), 2 H(m) (n_msgs), 3 T8 keys (entry g * 256 + mask), 4 T4
  * signatures ((m * groups4 + g) * 16 + mask), 5 T16 keys (k * 65536 + mask), 6 T8 signatures ((m * n_groups + g) * 256 + mask), 7 T2 signatures

@@ -140,6 +140,10 @@ def load():
     if hasattr(L, "bn254_batch_merge_keyed_bitmap"):                  # absent from an older build loaded through BN254_LIB
         L.bn254_batch_merge_keyed_bitmap.argtypes = [vp, vp, vp, vp, vp, vp, sz, sz, sz, u32, vp, vp, vp, vp, vp, vp]
         L.bn254_batch_merge_keyed_bitmap_device.argtypes = [vp, vp, vp, vp, vp, vp, sz, sz, sz, u32, vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "bn254_batch_merge_keyed_bitmap_optimistic"):       # absent from an older build loaded through BN254_LIB
+        L.bn254_batch_merge_keyed_bitmap_optimistic.argtypes = [vp, vp, vp, vp, vp, vp, sz, sz, sz, u32, vp, vp, vp, vp, vp, vp]
+        L.bn254_batch_merge_keyed_bitmap_optimistic_device.argtypes = [vp, vp, vp, vp, vp, vp, sz, sz, sz, u32, vp, vp, vp, vp, vp, vp, vp]
+        L.bn254_debug_merge_opt_last.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     L.bn254_debug_bitmap_rand_last.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     L.bn254_debug_bitmap_rand_sums.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), sz, sz, vp, vp, vp, vp, vp, vp]
     L.bn254_batch_verify_keyed_randomized.argtypes = [vp, vp, vp, vp, vp, sz, u32, vp, vp]
@@ -233,6 +237,7 @@ EXPORTED_SYMBOLS = [
     "bn254_batch_collect_keyed_bitmap_randomized", "bn254_batch_collect_keyed_bitmap_randomized_device", "bn254_debug_collect_rand_last",
     "bn254_batch_collect_keyed_bitmap_optimistic", "bn254_batch_collect_keyed_bitmap_optimistic_device", "bn254_debug_collect_opt_last",
     "bn254_batch_merge_keyed_bitmap", "bn254_batch_merge_keyed_bitmap_device",
+    "bn254_batch_merge_keyed_bitmap_optimistic", "bn254_batch_merge_keyed_bitmap_optimistic_device", "bn254_debug_merge_opt_last",
     "bn254_mgpu_create", "bn254_mgpu_destroy", "bn254_mgpu_device_count", "bn254_mgpu_ctx", "bn254_mgpu_shard_len", "bn254_mgpu_shard_range",
     "bn254_mgpu_gathered_len", "bn254_mgpu_reserve", "bn254_mgpu_synchronize", "bn254_mgpu_set_option", "bn254_mgpu_last_timing",
     "bn254_mgpu_last_error", "bn254_mgpu_batch_verify", "bn254_mgpu_batch_verify_device", "bn254_mgpu_batch_pairing",

@@ -394,11 +394,11 @@ class ECDSA:
         return r
 
     @staticmethod
-    def batch_merge_keyed_signers(items, engine=None, n_keys=None):
+    def batch_merge_keyed_signers(items, engine=None, n_keys=None, optimistic=False):
         """items: a list of (message, parts); result[i] is what ECDSA.merge_keyed_signers returns for item i, or the Error it would raise.
         A malformed item (not such a pair, a part that is not a pair, a signature of the wrong length, an index that is negative or >= 2^32)
         raises before any device work.  n_keys: the size of the registered set, for an engine that did not register it itself (without
-        either the bitmaps are as wide as the largest index)."""
+        either the bitmaps are as wide as the largest index).  optimistic: see batch_merge_keyed_signers_optimistic."""
         rows = []
         for item in items:
             if not isinstance(item, (tuple, list)) or len(item) != 2:
@@ -429,8 +429,8 @@ class ECDSA:
                     j = min(j, top)
                     row[j // 32] |= 1 << (j % 32)
                 bits += row
-        part_st, taken, tuple_st, agg, union = eng.merge_keyed_bitmap([r[0] for r in rows], b"".join(s for r in rows for s in r[1]), bits,
-                                                                     [len(r[1]) for r in rows], bm_words)
+        merge = eng.merge_keyed_bitmap_optimistic if optimistic else eng.merge_keyed_bitmap
+        part_st, taken, tuple_st, agg, union = merge([r[0] for r in rows], b"".join(s for r in rows for s in r[1]), bits, [len(r[1]) for r in rows], bm_words)
         out, at = [], 0
         for i, (_, sigs, _) in enumerate(rows):
             st, tk = part_st[at:at + len(sigs)], taken[at:at + len(sigs)]
@@ -442,6 +442,26 @@ class ECDSA:
             signers = [j for j in range(32 * bm_words) if (row[j // 32] >> (j % 32)) & 1]
             out.append((Signature(agg[64 * i:64 * i + 64]), signers, [None if b == 0 else Error(b) for b in st], [bool(b) for b in tk]))
         return out
+
+    @staticmethod
+    def batch_merge_keyed_signers_optimistic(items, engine=None, n_keys=None):
+        """batch_merge_keyed_signers with one verify per item — the sum of its partials that pass every check short of the pairing, against
+        the keys of the union of their indices — and the partials verified one by one only in an item whose sum fails or in which two such
+        partials overlap (include/bn254_hip.h: bn254_batch_merge_keyed_bitmap_optimistic).  The same result list and the same refusals
+        before any device work.  The aggregate and the indices are always a pair ECDSA.verify_keyed_signers accepts.  ONE deviation:
+        partials whose errors cancel within an item that passes (sigma_a + D and sigma_b - D, also with no indices at all) read None and
+        are taken — a None there means "taken into a sum that verifies", not "individually valid".  Who needs per-partial verdicts takes
+        batch_merge_keyed_signers."""
+        return ECDSA.batch_merge_keyed_signers(items, engine, n_keys, optimistic=True)
+
+    @staticmethod
+    def merge_keyed_signers_optimistic(message, parts, engine=None, n_keys=None):
+        """merge_keyed_signers through batch_merge_keyed_signers_optimistic: the same quadruple, the same Errors raised, the same one
+        deviation (partials whose errors cancel within a sum that verifies read None and are taken)."""
+        r = ECDSA.batch_merge_keyed_signers_optimistic([(message, parts)], engine, n_keys)[0]
+        if isinstance(r, Error):
+            raise r
+        return r
 
     @staticmethod
     def batch_aggregate_keyed_signers_optimistic(items, engine=None, n_keys=None):

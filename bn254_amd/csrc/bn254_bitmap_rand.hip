@@ -190,6 +190,17 @@ KERNEL_PAIR void k_bmr_sum_pair_q(const uint32_t* bits, size_t bm_words, BmKeys 
   if (role == 0) ws_byte(ws, BY_Q_INF, i) = pk.inf;
 }
 
+// (bn254_host.h) — also what the optimistic merge's fallback launches (bn254_merge.hip)
+int launch_bitmap_sum_queued(bn254_ctx* c, hipStream_t s, const uint32_t* d_bits, size_t bm_words, size_t n, bool tables, const uint32_t* map,
+                             const uint32_t* count) {
+  const BmKeys Kb = {c->key_xy, c->key_st, c->key_inf, (const uint32_t*)c->bm_bad, (uint32_t)c->n_keys};
+  const int32_t* rec = tables ? (const int32_t*)c->bm_tab : nullptr;
+  const uint8_t* rec_inf = tables ? c->bm_tab + ((c->n_keys + 7) / 8) * 256 * BM_REC_WORDS * sizeof(int32_t) : nullptr;
+  k_bmr_sum_pair_q<<<(unsigned)((2 * n + BN_PAIR_WG - 1) / BN_PAIR_WG), BN_PAIR_WG, 0, s>>>(d_bits, bm_words, Kb, rec, rec_inf, c->ws, map, count);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 // ---- host side ----------------------------------------------------------------------------------------------------------------------------
 // The sizes of a call (one slice): groups, buckets, sort elements, and the places in the workspace — tuples from 0 (sigma: P1, H(m): P2, the
 // re-check's key: Q), the scaled points from ebase, the partial products of the group checks from pbase, the groups (S_g, their products)
@@ -329,10 +340,7 @@ static int bmr_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t* d_off
   HIP_TRY(hipMemsetAsync(c->ws.h_cnt, 0, sizeof(uint32_t), s));
   HIP_TRY(hipMemsetAsync(c->bmr_stats, 0, 8 * sizeof(uint32_t), s));
   if ((rc = bn254_aggr_collect(n, c->ws, 0, b.lo, (uint64_t)p.G, b.nagg, b.gst, d_status, b.queued, p.ng, b.glo, b.ghi, c->bmr_stats, s))) return rc;
-  const int32_t* rec = tables ? (const int32_t*)c->bm_tab : nullptr;
-  const uint8_t* rec_inf = tables ? c->bm_tab + ((K + 7) / 8) * 256 * BM_REC_WORDS * sizeof(int32_t) : nullptr;
-  k_bmr_sum_pair_q<<<(unsigned)((2 * n + BN_PAIR_WG - 1) / BN_PAIR_WG), BN_PAIR_WG, 0, s>>>(d_bits, bm_words, Kb, rec, rec_inf, c->ws, c->ws.h_list, c->ws.h_cnt);
-  HIP_TRY(hipGetLastError());
+  if ((rc = launch_bitmap_sum_queued(c, s, d_bits, bm_words, n, tables, c->ws.h_list, c->ws.h_cnt))) return rc;
   if ((rc = bn254_pair_miller_verify(n, c->ws, c->ws.h_list, c->ws.h_cnt, s))) return rc;
   if ((rc = bn254_pair_final_exp(n, c->ws, 1, d_status, c->ws.h_list, c->ws.h_cnt, s))) return rc;
   PROF_MARK(4);

@@ -31,10 +31,8 @@ using namespace bn254;
 // per tuple, outside the (sliced) workspace: the scans of the range rule, H(m) with its identity flag and hash status
 #define CL_HASH_WORDS (2 * BN_LIMBS)
 // ... and, in front, what the randomised slices of the call did: {slices, groups checked, groups failed, shares re-checked exactly}, then what
-// the optimistic route did: {tuples checked, tuples passed, tuples sent the exact way, shares verified exactly}; behind, that route's flag
-// (bn254_collect.h: CLO_*) and tuple-check verdict per tuple
-#define CL_STAT_WORDS 8
-#define CLO_STAT_AT 4
+// the optimistic route did: {tuples checked, tuples passed, tuples sent the exact way, shares verified exactly} (bn254_host.h: CL_STAT_WORDS,
+// CLO_STAT_AT); behind, that route's flag (bn254_collect.h: CLO_*) and tuple-check verdict per tuple
 // (struct ClScratch: bn254_host.h — the merge of partial aggregates, bn254_merge.hip, shares the scratch and the front end)
 static ClScratch cl_scratch(Carve& c, size_t n) {
   ClScratch b;
@@ -291,6 +289,11 @@ KERNEL_SMALL void k_clo_load_h(size_t len, size_t base, ClScratch S, Ws ws) {
   ws_byte(ws, BY_P2_INF, j) = S.hinf[base + j];
   ws_byte(ws, BY_ST_HASH, j) = S.hst[base + j];
 }
+int launch_clo_load_h(bn254_ctx* c, hipStream_t s, size_t len, size_t base, const ClScratch& S) {
+  k_clo_load_h<<<grid_for(len), BN_WAVE, 0, s>>>(len, base, S, c->ws);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
 // behind the tuple check: the rows of the tuples that go the exact way are zeroed for the re-sum, and the call's counters take what the
 // check did (one vector atomic per wave and counter)
 KERNEL_SMALL void k_clo_settle(size_t n, size_t bm_words, ClScratch S, uint32_t* bits) {
@@ -381,7 +384,7 @@ static int cl_collect_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t
                              uint32_t flags, const uint8_t* seed32, bool optimistic, uint8_t* d_share_status, uint8_t* d_tuple_status,
                              uint8_t* d_agg_sigs, uint32_t* d_signer_bits, uint32_t* d_n_signers, void* stream) {
   MsgsLenScope msgs_len_scope(c);
-  if (c) c->clr_last_ran = c->clo_last_ran = 0;
+  if (c) c->clr_last_ran = c->clo_last_ran = c->mgo_last_ran = 0;
   if (!c || bm_words > 0xFFFFFFFFu || n > 0xFFFFFFFFu || n_shares > 0xFFFFFFFFu) return BN254_E_BAD_ARGUMENT;
   if (bm_words < (c->n_keys + 31) / 32) return BN254_E_BAD_ARGUMENT;       // a bitmap that cannot hold a registered key cannot describe the result
   if (n && (!d_msgs || !d_msg_off || !d_share_off || !d_tuple_status || !d_agg_sigs || (bm_words && !d_signer_bits))) return BN254_E_BAD_ARGUMENT;
@@ -464,7 +467,7 @@ static int cl_collect_host(bn254_ctx* c, const uint8_t* msgs, const uint64_t* ms
                            bool optimistic, uint8_t* share_status, uint8_t* tuple_status, uint8_t* agg_sigs, uint32_t* signer_bits,
                            uint32_t* n_signers) {
   MsgsLenScope msgs_len_scope(c);
-  if (c) c->clr_last_ran = c->clo_last_ran = 0;
+  if (c) c->clr_last_ran = c->clo_last_ran = c->mgo_last_ran = 0;
   if (!c || bm_words > 0xFFFFFFFFu || n > 0xFFFFFFFFu || n_shares > 0xFFFFFFFFu) return BN254_E_BAD_ARGUMENT;
   if (bm_words < (c->n_keys + 31) / 32) return BN254_E_BAD_ARGUMENT;
   if (n && (!msg_off || !share_off || !tuple_status || !agg_sigs || (bm_words && !signer_bits))) return BN254_E_BAD_ARGUMENT;

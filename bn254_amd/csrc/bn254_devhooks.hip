@@ -340,6 +340,18 @@ int bn254_debug_collect_opt_last(bn254_ctx* c, uint64_t out[4]) {
   for (int i = 0; i < 4; ++i) out[i] = st[i];
   return 0;
 }
+// bn254_batch_merge_keyed_bitmap_optimistic: the same four of its last call, the fourth in partials
+int bn254_debug_merge_opt_last(bn254_ctx* c, uint64_t out[4]) {
+  if (!c || !out) return BN254_E_BAD_ARGUMENT;
+  for (int i = 0; i < 4; ++i) out[i] = 0;
+  if (!c->mgo_last_ran || !c->mgo_stats) return 0;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipDeviceSynchronize());
+  uint32_t st[4];
+  HIP_TRY(hipMemcpy(st, c->mgo_stats, sizeof st, hipMemcpyDeviceToHost));
+  for (int i = 0; i < 4; ++i) out[i] = st[i];
+  return 0;
+}
 // The groups of the last randomised call, read from where it left them (bn254_host.h: aggr_last): the call itself launches and copies
 // nothing for this.  dims = {groups, table pairs}; with group_cap / pair_cap too small only dims is written.
 static int debug_rand_sums(bn254_ctx* c, int ran, const AggrLast& L, uint64_t dims[2], size_t group_cap, size_t pair_cap, uint32_t* nagg, uint8_t* verdict,

@@ -792,6 +792,7 @@ int bn254_ctx_create(int hip_device, bn254_ctx** out) {
   c->collect_opt_min_shares = COLLECT_OPT_MIN_SHARES_DEFAULT;
   c->collect_opt_min_tuple_shares = COLLECT_OPT_MIN_TUPLE_SHARES_DEFAULT;
   c->merge_wave_min = MERGE_WAVE_MIN_PARTS_DEFAULT;
+  c->merge_opt_min_parts = MERGE_OPT_MIN_PARTS_DEFAULT;
   c->trio_max_batch = TRIO_MAX_BATCH_DEFAULT;
   c->hash_direct_width = HASH_DIRECT_WIDTH_DEFAULT;
   c->hash_tail_chunk = HASH_TAIL_CHUNK_DEFAULT;
@@ -990,6 +991,7 @@ int bn254_ctx_set_option(bn254_ctx* c, int option, int value) {
   if (option == BN254_OPT_COLLECT_RAND_MIN_PER_KEY) { if (value < 0) return BN254_E_BAD_ARGUMENT; c->collect_rand_min_per_key = value; return 0; }
   if (option == BN254_OPT_COLLECT_OPT_MIN_SHARES) { if (value < 0) return BN254_E_BAD_ARGUMENT; c->collect_opt_min_shares = value; return 0; }
   if (option == BN254_OPT_MERGE_WAVE_MIN_PARTS) { if (value < 1) return BN254_E_BAD_ARGUMENT; c->merge_wave_min = value; return 0; }
+  if (option == BN254_OPT_MERGE_OPT_MIN_PARTS) { if (value < 0) return BN254_E_BAD_ARGUMENT; c->merge_opt_min_parts = value; return 0; }
   if (option == BN254_OPT_COLLECT_OPT_MIN_TUPLE_SHARES) { if (value < 0) return BN254_E_BAD_ARGUMENT; c->collect_opt_min_tuple_shares = value; return 0; }
   if (option == BN254_OPT_BITMAP_RAND_GROUP_TUPLES) { if (value < 1) return BN254_E_BAD_ARGUMENT; c->bmr_group_tuples = value; return 0; }
   if (option == BN254_OPT_BITMAP_ROUTE) { if (value < 0 || value > 2) return BN254_E_BAD_ARGUMENT; c->bm_route = value; return 0; }

@@ -147,6 +147,9 @@ struct bn254_ctx {
   uint32_t* clo_stats;       // what its last call did on the device (bn254_debug_collect_opt_last); inside collect_buf
   int clo_last_ran;          // ... and whether that call took the optimistic route at all
   int merge_wave_min;        // BN254_OPT_MERGE_WAVE_MIN_PARTS (bn254_merge.hip): tuples with at least this many partials are merged by a wave each
+  int merge_opt_min_parts;   // BN254_OPT_MERGE_OPT_MIN_PARTS: the optimistic merge from this many partials on
+  uint32_t* mgo_stats;       // what its last call did on the device (bn254_debug_merge_opt_last); inside collect_buf
+  int mgo_last_ran;          // ... and whether that call took the optimistic route at all
 };
 
 struct ScopedEvents {
@@ -342,6 +345,10 @@ BN_HIDDEN int launch_bitmap_sum(bn254_ctx* c, hipStream_t s, const uint32_t* d_b
 // workspace: the scans of the range rule, H(m) with its identity flag and hash status; in front the counters of the randomised and the
 // optimistic collect, behind the optimistic route's flag and verdict
 struct ClScratch { uint32_t* stats; uint64_t *mx, *hi, *end, *tot; int32_t* hpt; uint8_t *hinf, *hst, *flag, *verdict; };
+// stats: {slices, groups checked, groups failed, shares re-checked exactly} of the randomised collect, then from CLO_STAT_AT what an optimistic
+// route did — the collect's or the merge's, whichever call owns the scratch: {tuples checked, passed, sent the exact way, items verified exactly}
+#define CL_STAT_WORDS 8
+#define CLO_STAT_AT 4
 // ... carved for n tuples from the context's collect_buf (grown on demand: before the call's first kernel)
 BN_HIDDEN int cl_scratch_reserve(bn254_ctx* c, size_t n, ClScratch* S);
 // ... the hash of the n messages, once per tuple in pieces of t_piece, and the range rule over the n + 1 offsets d_off into n_items items:
@@ -351,4 +358,10 @@ BN_HIDDEN int cl_hash_and_plan(bn254_ctx* c, hipStream_t s, const uint8_t* d_msg
 // ... and H(m) and the hash status of its tuple into workspace entries 0 .. len for the items base .. base + len (an item of no accepted tuple:
 // the generator, decode status 2)
 BN_HIDDEN int launch_cl_spread(bn254_ctx* c, hipStream_t s, size_t len, uint64_t base, size_t n, const uint64_t* d_off, const ClScratch& S);
+// ... and, for a check per TUPLE, H(m) and the hash status of the tuples base .. base + len into workspace entries 0 .. len (k_clo_load_h)
+BN_HIDDEN int launch_clo_load_h(bn254_ctx* c, hipStream_t s, size_t len, size_t base, const ClScratch& S);
+// the aggregate keys of a device-side QUEUE of tuples on lane pairs (bn254_bitmap_rand.hip: k_bmr_sum_pair_q): lane pair e < *count takes row
+// map[e] of d_bits into the Q planes of entry map[e]; rule 2 is the caller's.  n = the most the queue can hold
+BN_HIDDEN int launch_bitmap_sum_queued(bn254_ctx* c, hipStream_t s, const uint32_t* d_bits, size_t bm_words, size_t n, bool tables, const uint32_t* map,
+                                       const uint32_t* count);
 BN_HIDDEN int launch_encode_g1(bn254_ctx* c, hipStream_t s, size_t n, int px, int inf_plane, uint8_t* out, uint8_t* status_out);

@@ -11,7 +11,9 @@
 //     adds the taken partials l, l + 64, .. (mg_wave_partial, reading part_taken) and the collect's tree folds the 64 partial sums.
 //   * Both layouts take the same partials and end in the same affine point, so the bytes cannot depend on the layout.
 // A partial that is not taken is added as the identity under the generator's coordinates, as in the collect.  Include after bn254_collect.h.
+// At the end of the file: the steps of bn254_batch_merge_keyed_bitmap_optimistic[_device] (mgo_*), which read rule 2 of bn254_bitmap.h.
 #pragma once
+#include "bn254_bitmap.h"
 
 namespace bn254 {
 
@@ -98,6 +100,91 @@ BN_DEV void mg_wave_partial(G1Jac& acc, uint32_t& count, const uint32_t* row, co
     jac_accumulate(acc, pt);
   }
   count = mg_popcount(row, bm_words, lane, BN_CL_WAVE);
+}
+
+// ---- the optimistic merge (bn254_batch_merge_keyed_bitmap_optimistic[_device]) -----------------------------------------------
+// The partials of a tuple share the message: if all candidates are good and pairwise disjoint, their sum is the aggregate of the union row,
+// and ONE verify of the sum against the union row's keys proves it.  So: rules 1-3 per partial without a pairing or an aggregate key
+// (mgo_precheck: status 0 = a CANDIDATE), the first fit above over the candidates with a refused candidate reported as an OVERLAP and the
+// candidates counted (mgo_lane_step, mgo_wave_select), one flag per tuple (mgo_flag, the collect's CLO_* values), the tuple check by the
+// bitmap verify's kernels, and — for the tuples that fail it or have an overlap — the exact verify of their candidates through a queue
+// (clo_queued serves: it asks only for status 0 and the tuple's flag and verdict) and the exact first fit again on their zeroed rows
+// (mgo_resum_len masks it: a tuple that does not go the exact way has length 0, so nothing of it is written).
+
+// rules 1-3 of the bitmap verify for one partial of an accepted tuple, in that order: sigma's decode status (the call's flags), the lowest
+// bad bit of its row, the tuple's hash status
+BN_DEV uint8_t mgo_precheck(const uint8_t* part64, uint32_t flags, const uint32_t* row, size_t bm_words, const BmKeys& K, uint8_t hash_st) {
+  G1Affine p;
+  uint8_t st = decode_g1(p, part64, flags);
+  if (st == ST_OK) st = bm_rule2_status(row, bm_words, K);
+  if (st == ST_OK) st = hash_st;
+  return st;
+}
+// the tuple's flag from what the provisional select saw.  FINAL goes by the number of candidates, not by the row: a candidate with an empty
+// row leaves the row empty and still needs its check (only the identity passes it)
+BN_DEV uint8_t mgo_flag(uint32_t cand, uint32_t overlap) {
+  if (overlap) return CLO_EXACT;
+  return cand == 0 ? CLO_FINAL : CLO_CHECK;
+}
+// the partials of tuple i as the masked re-select walks them: those of a tuple that goes the exact way, none of any other
+BN_DEV uint64_t mgo_resum_len(const MgParts& in, size_t i, bool live, const uint8_t* flag, const uint8_t* verdict) {
+  if (!live || !clo_goes_exact(flag[i], verdict[i])) return 0;
+  return mg_tuple_len(in, i, true);
+}
+// mg_lane_step with the candidates counted and a refused candidate (ok && hit) reported
+BN_DEV void mgo_lane_step(G1Jac& acc, uint32_t& cand, uint32_t& overlap, uint32_t* row, uint8_t* part_taken, size_t bm_words, const MgParts& in, uint64_t lo,
+                          uint64_t len, uint64_t k) {
+  bool take = false;
+  const uint64_t p = lo + k;
+  if (k < len) {
+    const uint32_t* part = in.rows + p * bm_words;
+    const bool ok = in.part_st[p] == ST_OK;
+    const bool hit = ok && mg_overlap(row, part, bm_words, 0, 1);
+    take = ok && !hit;
+    if (take) mg_or_in(row, part, bm_words, 0, 1);
+    part_taken[p] = take ? 1 : 0;
+    cand += ok ? 1u : 0u;
+    overlap |= hit ? 1u : 0u;
+  }
+  if (!BN_WAVE_ANY(take)) return;                           // a step nobody in the wave takes
+  G1Affine pt;
+  cl_load_share(pt, in.parts, p, take);
+  jac_accumulate(acc, pt);
+}
+BN_DEV void mgo_lane_walk(G1Jac& acc, uint32_t& count, uint32_t& cand, uint32_t& overlap, uint32_t* row, uint8_t* part_taken, size_t bm_words, const MgParts& in,
+                          uint64_t lo, uint64_t len) {
+  jac_set_identity(acc);
+  cand = 0;
+  overlap = 0;
+  for (uint64_t k = 0; BN_WAVE_ANY(k < len); ++k) mgo_lane_step(acc, cand, overlap, row, part_taken, bm_words, in, lo, len, k);
+  count = len ? mg_popcount(row, bm_words, 0, 1) : 0;
+}
+// mg_wave_select with the same two reports; both are wave-uniform (the statuses are, and the overlap is the wave's vote).  The sum behind
+// it is mg_wave_partial, unchanged.
+BN_DEV void mgo_wave_select(uint32_t& cand, uint32_t& overlap, uint32_t* row, uint8_t* part_taken, size_t bm_words, const MgParts& in, uint64_t lo, uint64_t len,
+                            unsigned lane) {
+  cand = 0;
+  overlap = 0;
+  for (uint64_t k = 0; k < len; ++k) {
+    const uint64_t p = lo + k;
+    const uint32_t* part = in.rows + p * bm_words;
+    const bool ok = in.part_st[p] == ST_OK;
+#if defined(__HIPCC__)
+    const bool hit = BN_WAVE_ANY(ok && mg_overlap(row, part, bm_words, lane, BN_CL_WAVE));
+#else
+    bool hit = false;
+    for (unsigned l = 0; ok && l < BN_CL_WAVE; ++l) hit = mg_overlap(row, part, bm_words, l, BN_CL_WAVE) || hit;
+#endif
+    const bool take = ok && !hit;
+#if defined(__HIPCC__)
+    if (take) mg_or_in(row, part, bm_words, lane, BN_CL_WAVE);
+#else
+    for (unsigned l = 0; take && l < BN_CL_WAVE; ++l) mg_or_in(row, part, bm_words, l, BN_CL_WAVE);
+#endif
+    if (lane == 0) part_taken[p] = take ? 1 : 0;
+    cand += ok ? 1u : 0u;
+    overlap |= hit ? 1u : 0u;
+  }
 }
 
 }  // namespace bn254

@@ -60,6 +60,8 @@ COLLECT_OPT_MIN_SHARES_DEFAULT = 1539   # the library's defaults of the two (bn2
 COLLECT_OPT_MIN_TUPLE_SHARES_DEFAULT = 1
 OPT_MERGE_WAVE_MIN_PARTS = 43       # merge_keyed_bitmap: tuples with at least this many partials are merged by a wave each (default 16, from the sweep of tools/merge_throughput.py)
 MERGE_WAVE_MIN_PARTS_DEFAULT = 16   # ... as bn254_ws.h has it
+OPT_MERGE_OPT_MIN_PARTS = 45        # merge_keyed_bitmap_optimistic: the exact merge below this many partials (default 64, measured: DESIGN.md §10i); 0 = no lower bound
+MERGE_OPT_MIN_PARTS_DEFAULT = 64    # ... as bn254_ws.h has it
 OPT_COLLECT_WAVE_MIN_SHARES = 37   # collect_keyed_bitmap: tuples with at least this many shares are summed by a wave each (default 16; swept at three shapes only)
 
 
@@ -239,6 +241,14 @@ class Engine:
         o = (ctypes.c_uint64 * 4)()
         _check("bn254_debug_collect_opt_last", self._lib.bn254_debug_collect_opt_last(self._h, o))
         return dict(zip(("checked", "passed", "exact_tuples", "exact_shares"), (int(x) for x in o)))
+
+    def debug_merge_opt_last(self):
+        """what the last merge_keyed_bitmap_optimistic[_device] did, counted on the device: dict(checked, passed, exact_tuples, exact_parts) —
+        tuples whose sum was verified, those that passed, tuples sent the exact way (failed, or an overlap), partials verified one by one;
+        all 0 after any call that did not take the route"""
+        o = (ctypes.c_uint64 * 4)()
+        _check("bn254_debug_merge_opt_last", self._lib.bn254_debug_merge_opt_last(self._h, o))
+        return dict(zip(("checked", "passed", "exact_tuples", "exact_parts"), (int(x) for x in o)))
 
     def debug_bitmap_rand_sums(self):
         """the G1 side of that call's group checks as it left them (include/bn254_hip.h: bn254_debug_bitmap_rand_sums), in the format of
@@ -602,15 +612,16 @@ class Engine:
                self._lib.bn254_batch_collect_keyed_bitmap_device(self._h, d_msgs, d_msg_off, d_shares, d_share_key, d_share_off, n_shares, n, bm_words,
                                                                  flags, d_share_status, d_tuple_status, d_agg_sigs, d_signer_bits, d_n_signers, stream))
 
-    def merge_keyed_bitmap(self, messages, parts, part_bitmaps, sizes, bm_words, flags=0, want_counts=False):
+    def merge_keyed_bitmap(self, messages, parts, part_bitmaps, sizes, bm_words, flags=0, want_counts=False, optimistic=False):
         """merge partial signer-bitmap aggregates into one aggregate per message (include/bn254_hip.h: bn254_batch_merge_keyed_bitmap):
         tuple i is messages[i] with the next sizes[i] partials (64 B each; partial p has the bm_words bitmap words part_bitmaps[p * bm_words
         ..]).  Returns (partial status bytes, taken bytes, tuple status bytes, the n aggregates, the n * bm_words bitmap words) — and the
-        signer counts with want_counts."""
+        signer counts with want_counts.  optimistic: see merge_keyed_bitmap_optimistic."""
         n = len(messages)
         assert len(sizes) == n and all(k >= 0 for k in sizes)
         n_parts = sum(int(k) for k in sizes)
         assert len(parts) == n_parts * G1_BYTES and len(part_bitmaps) == n_parts * bm_words
+        name = "bn254_batch_merge_keyed_bitmap_optimistic" if optimistic else "bn254_batch_merge_keyed_bitmap"
         msgs, off = pack_messages(messages)
         ends = [0]
         for k in sizes:
@@ -623,9 +634,8 @@ class Engine:
         agg = ctypes.create_string_buffer(max(n, 1) * G1_BYTES)
         bits = (ctypes.c_uint32 * max(n * bm_words, 1))()
         counts = (ctypes.c_uint32 * max(n, 1))()
-        _check("bn254_batch_merge_keyed_bitmap",
-               self._lib.bn254_batch_merge_keyed_bitmap(self._h, msgs, off, bytes(parts), rows, part_off, n_parts, n, bm_words, flags, part_st, taken, tuple_st,
-                                                        agg, bits, counts if want_counts else None))
+        _check(name, getattr(self._lib, name)(self._h, msgs, off, bytes(parts), rows, part_off, n_parts, n, bm_words, flags, part_st, taken, tuple_st, agg, bits,
+                                              counts if want_counts else None))
         out = (part_st.raw[:n_parts], taken.raw[:n_parts], tuple_st.raw[:n], agg.raw[:n * G1_BYTES], list(bits)[:n * bm_words])
         return out + (list(counts)[:n],) if want_counts else out
 
@@ -635,6 +645,21 @@ class Engine:
         _check("bn254_batch_merge_keyed_bitmap_device",
                self._lib.bn254_batch_merge_keyed_bitmap_device(self._h, d_msgs, d_msg_off, d_parts, d_part_bits, d_part_off, n_parts, n, bm_words, flags,
                                                                d_part_status, d_part_taken, d_tuple_status, d_agg_sigs, d_signer_bits, d_n_signers, stream))
+
+    def merge_keyed_bitmap_optimistic(self, messages, parts, part_bitmaps, sizes, bm_words, flags=0, want_counts=False):
+        """merge_keyed_bitmap with ONE verify per tuple — the sum of its candidate partials against the keys of their union row — and the
+        partials checked one by one only where that fails or two candidates overlap (include/bn254_hip.h:
+        bn254_batch_merge_keyed_bitmap_optimistic).  The same six outputs, except that partials whose errors cancel within a passing tuple
+        read 0 and are taken."""
+        return Engine.merge_keyed_bitmap(self, messages, parts, part_bitmaps, sizes, bm_words, flags, want_counts, optimistic=True)
+
+    def merge_keyed_bitmap_optimistic_device(self, d_msgs, d_msg_off, d_parts, d_part_bits, d_part_off, n_parts, n, bm_words, d_part_status, d_part_taken,
+                                             d_tuple_status, d_agg_sigs, d_signer_bits, d_n_signers=None, flags=0, stream=None):
+        """the device-pointer form: enqueues only (include/bn254_hip.h: bn254_batch_merge_keyed_bitmap_optimistic_device)"""
+        _check("bn254_batch_merge_keyed_bitmap_optimistic_device",
+               self._lib.bn254_batch_merge_keyed_bitmap_optimistic_device(self._h, d_msgs, d_msg_off, d_parts, d_part_bits, d_part_off, n_parts, n, bm_words,
+                                                                          flags, d_part_status, d_part_taken, d_tuple_status, d_agg_sigs, d_signer_bits,
+                                                                          d_n_signers, stream))
 
     def batch_collect_keyed_bitmap_optimistic(self, messages, shares, share_keys, sizes, bm_words, flags=0, want_counts=False):
         """batch_collect_keyed_bitmap with ONE verify per tuple — the sum of its candidate shares against the sum of their keys — and the

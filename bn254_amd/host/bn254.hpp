@@ -49,6 +49,10 @@ class Engine {   // one per GPU; not thread-safe (one thread at a time per conte
   Engine(const Engine&) = delete;
   Engine& operator=(const Engine&) = delete;
   bn254_ctx* raw() const { return ctx_; }
+  // a BN254_OPT_* of include/bn254_hip.h, e.g. OPT_MERGE_OPT_MIN_PARTS below
+  void set_option(int option, int value) { check_rc("bn254_ctx_set_option", bn254_ctx_set_option(ctx_, option, value)); }
+  // merge_keyed_signers_optimistic: calls with fewer partials take the exact merge, same bytes; 0 = no lower bound
+  static constexpr int OPT_MERGE_OPT_MIN_PARTS = BN254_OPT_MERGE_OPT_MIN_PARTS;
   static Engine& default_engine() { static Engine e(0); return e; }
  private:
   bn254_ctx* ctx_ = nullptr;
@@ -384,7 +388,8 @@ struct ECDSA {
   struct PartialAggregate { Signature signature; std::vector<uint32_t> signer_indices; };
   struct MergeItem { std::vector<uint8_t> message; std::vector<PartialAggregate> parts; };
   struct KeyedMergeResult { uint8_t status; Signature signature; std::vector<uint32_t> signer_indices; std::vector<uint8_t> statuses, taken; };
-  static std::vector<KeyedMergeResult> batch_merge_keyed_signers(const std::vector<MergeItem>& items, size_t n_keys, Engine& e = Engine::default_engine()) {
+  static std::vector<KeyedMergeResult> batch_merge_keyed_signers(const std::vector<MergeItem>& items, size_t n_keys, Engine& e = Engine::default_engine(),
+                                                                 bool optimistic = false) {
     const size_t n = items.size(), bm_words = n_keys / 32 + 1;   // one bit past the set: every index outside it lands there -> IndexOutOfBounds
     std::vector<uint64_t> off(n + 1, 0), part_off(n + 1, 0);
     std::vector<uint8_t> msgs, parts;
@@ -409,9 +414,14 @@ struct ECDSA {
     std::vector<uint32_t> bits(n * bm_words + 1, 0);
     parts.resize(parts.size() + 1);
     rows.resize(rows.size() + 1);
-    check_rc("bn254_batch_merge_keyed_bitmap",
-             bn254_batch_merge_keyed_bitmap(e.raw(), msgs.data(), off.data(), parts.data(), rows.data(), part_off.data(), n_parts, n, bm_words, 0, part_st.data(),
-                                            taken.data(), tuple_st.data(), agg.data(), bits.data(), nullptr));
+    if (optimistic)
+      check_rc("bn254_batch_merge_keyed_bitmap_optimistic",
+               bn254_batch_merge_keyed_bitmap_optimistic(e.raw(), msgs.data(), off.data(), parts.data(), rows.data(), part_off.data(), n_parts, n, bm_words, 0,
+                                                         part_st.data(), taken.data(), tuple_st.data(), agg.data(), bits.data(), nullptr));
+    else
+      check_rc("bn254_batch_merge_keyed_bitmap",
+               bn254_batch_merge_keyed_bitmap(e.raw(), msgs.data(), off.data(), parts.data(), rows.data(), part_off.data(), n_parts, n, bm_words, 0, part_st.data(),
+                                              taken.data(), tuple_st.data(), agg.data(), bits.data(), nullptr));
     std::vector<KeyedMergeResult> out(n);
     for (size_t i = 0; i < n; ++i) {
       out[i].status = tuple_st[i];
@@ -426,6 +436,20 @@ struct ECDSA {
   static KeyedMergeResult merge_keyed_signers(const std::vector<uint8_t>& message, const std::vector<PartialAggregate>& parts, size_t n_keys,
                                               Engine& e = Engine::default_engine()) {
     KeyedMergeResult r = batch_merge_keyed_signers({MergeItem{message, parts}}, n_keys, e)[0];
+    check_status(r.status);
+    return r;
+  }
+  // ... with ONE verify per item — the sum of its partials that pass every check short of the pairing, against the keys of the union of their
+  // indices — and the partials verified one by one only where that fails or two of them overlap (include/bn254_hip.h:
+  // bn254_batch_merge_keyed_bitmap_optimistic).  The same results, with one deviation: partials whose errors cancel within an item that passes
+  // read 0 and are taken; the aggregate is still the valid one for the union.  Who needs per-partial verdicts takes batch_merge_keyed_signers.
+  static std::vector<KeyedMergeResult> batch_merge_keyed_signers_optimistic(const std::vector<MergeItem>& items, size_t n_keys,
+                                                                            Engine& e = Engine::default_engine()) {
+    return batch_merge_keyed_signers(items, n_keys, e, true);
+  }
+  static KeyedMergeResult merge_keyed_signers_optimistic(const std::vector<uint8_t>& message, const std::vector<PartialAggregate>& parts, size_t n_keys,
+                                                         Engine& e = Engine::default_engine()) {
+    KeyedMergeResult r = batch_merge_keyed_signers_optimistic({MergeItem{message, parts}}, n_keys, e)[0];
     check_status(r.status);
     return r;
   }

@@ -629,8 +629,8 @@ int bn254_batch_collect_keyed_bitmap_optimistic_device(bn254_ctx *ctx, const uin
  * ms; 1 024 x 64 1.39 + 0.41 + 6.06 + 3.90; the lone tuple 0.36 + 1.59 + 1.07 + 1.14 — there the select, serial in 4 096 partials for one
  * wave, costs 0.39 us per partial and is the largest stage; the collect sums the same shares in 0.27 ms, so a caller whose partials are all
  * single shares takes the collect.  No shape at which the call loses was found; shapes with invalid partials were not measured.
- * Out of scope: an optimistic form (one verify of the tuple's sum when its partials are pairwise disjoint — the obvious follow-up), a
- * randomised form, the multi-GPU layer, compressed input. */
+ * The optimistic form (one verify of the tuple's sum when its partials are pairwise disjoint) is bn254_batch_merge_keyed_bitmap_optimistic,
+ * below.  Out of scope: a randomised form, the multi-GPU layer, compressed input. */
 int bn254_batch_merge_keyed_bitmap(bn254_ctx *ctx, const uint8_t *msgs, const uint64_t *msg_off /* n+1 */,
                                    const uint8_t *parts /* n_parts*64 */, const uint32_t *part_bits /* n_parts*bm_words */,
                                    const uint64_t *part_off /* n+1 */, size_t n_parts, size_t n, size_t bm_words, uint32_t flags,
@@ -640,6 +640,81 @@ int bn254_batch_merge_keyed_bitmap_device(bn254_ctx *ctx, const uint8_t *d_msgs,
                                           const uint32_t *d_part_bits, const uint64_t *d_part_off, size_t n_parts, size_t n, size_t bm_words,
                                           uint32_t flags, uint8_t *d_part_status, uint8_t *d_part_taken, uint8_t *d_tuple_status,
                                           uint8_t *d_agg_sigs, uint32_t *d_signer_bits, uint32_t *d_n_signers, void *stream);
+
+/* bn254_batch_merge_keyed_bitmap_optimistic[_device]: the exact merge's arguments and six outputs, with ONE verify per tuple.  The partials
+ * of a tuple share the message: if every candidate is good and their rows are pairwise disjoint, their sum is the aggregate of the union row,
+ * and
+ *     e(H(m_i), sum_{j in union row} pk_j) * e(sum of the taken sigma, -G2) == 1
+ * proves it.  Only a tuple whose sum fails, or that holds an overlap, needs its partials checked one by one.  No randomness, no seed.  The
+ * argument checks, BN254_E_MISALIGNED, the range rule, the fills (part_status with 2, part_taken with 0) and the _device conventions are those
+ * of bn254_batch_merge_keyed_bitmap[_device]: no host synchronisation, every buffer reserved before the first kernel, everything enqueued
+ * whether or not a tuple fails; BN254_OPT_MAX_CHUNK slices the partials (of the fallback) and the tuples (of the hash and of the tuple check).
+ *   1. PRE-CHECK.  Every partial of an accepted tuple gets rules 1-3 of identity 1, in that order and with the call's flags: sigma's decode
+ *      status; the status of the lowest bad bit of its row; the tuple's hash status.  No pairing and no aggregate key is computed.  Status 0
+ *      means the partial is a CANDIDATE.  A candidate may have an empty row.
+ *   2. PROVISIONAL SELECT.  The exact call's first fit, run over the pre-check statuses in both layouts.  It additionally reports an
+ *      OVERLAP: a candidate refused because its row meets the union taken so far.
+ *   3. FLAG PER TUPLE, decided on the device.  FINAL: no candidate — by the number of candidates, not by the popcount of the row, because an
+ *      empty-row candidate still needs its check.  EXACT: an overlap was reported.  CHECK: everything else, i.e. every candidate was taken.
+ *   4. TUPLE CHECK.  For every CHECK tuple one verify e(H(m_i), sum_{j in union row} pk_j) * e(sum of the taken sigma, -G2) == 1, over the
+ *      call's own outputs through the bitmap verify's kernels, with decode flags 0 — an identity sum is legitimate.  It runs over all n tuples
+ *      in pieces of the slicing rule's size; the verdicts of tuples that are not CHECK are not read.
+ *   5. PASS.  The provisional row, aggregate, count, part_taken and statuses are final.
+ *   6. FALLBACK.  The candidates of the tuples that fail the check or are EXACT are queued on the device and verified exactly as the bitmap
+ *      verify would: the aggregate key per queued partial, the Miller loop and the final exponentiation over the queue only (every partial
+ *      of a slice is still decoded and spread).  The tuples' rows are zeroed and the exact first-fit select-and-sum runs again for these
+ *      tuples only; it rewrites part_taken for all of their partials.  Their six outputs are byte for byte the exact merge's.  A passing
+ *      tuple's outputs are not touched by the re-select.
+ *   7. WHOLE-CALL ROUTING.  The call IS the exact merge (same bytes) when no keys are registered, when BN254_OPT_PAIR_LANES is off (the
+ *      queue's kernels are lane-pair kernels), or when n_parts < BN254_OPT_MERGE_OPT_MIN_PARTS.  There is no per-tuple minimum: the collect's
+ *      measurements showed that such an option only pushes tuples through the queue, and a one-candidate tuple's check is the exact verify
+ *      anyway.
+ * IDENTITY 2 OF THE MERGE HOLDS UNCONDITIONALLY: bn254_batch_verify_keyed_bitmap with flags 0 on the call's own outputs returns 0 for every
+ * tuple with tuple_status == 0 — a passing tuple has just been verified so, a fallback tuple is the exact call's, a FINAL one is empty.
+ * EQUALITY WITH THE EXACT CALL: all six outputs equal bn254_batch_merge_keyed_bitmap's whenever no passing tuple holds a candidate that the
+ * exact call would have given 9.
+ * THE ONE DEVIATION: candidates whose errors cancel inside a passing tuple — sigma_a + D and sigma_b - D, also with empty rows — read 0 and
+ * are taken; the exact call gives both 9.  The aggregate is still the valid one for the union row.  A caller who needs per-partial verdicts
+ * uses the exact call.  Identity 1 holds only up to this deviation.
+ * With one-bit rows and distinct keys per tuple the outputs equal bn254_batch_collect_keyed_bitmap_optimistic's (part_status as its
+ * share_status).
+ * Cost: with every partial valid the aggregate keys, the Miller loop and the final exponentiation run over n tuples instead of n_parts
+ * partials; per partial remain the decode and rule 2 of the pre-check, one G1 addition, and the decode and spread of the fallback's front
+ * end, which runs whether or not anything is queued.  With every tuple failing the call costs the exact call plus one n-item verify pass.
+ * Which call when (measured on an MI355X, tools/merge_throughput.py --optimistic, profiles/merge_throughput.jsonl: whole-call medians of 9
+ * alternating calls after two warm-ups on a caller's stream, inputs resident, 256 keys, two thirds signing in disjoint committees, min .. max
+ * in brackets).  Every partial valid: 256 tuples x 16 partials 1.84 ms [1.84 .. 1.86] against the exact merge's 3.10
+ * [3.09 .. 3.16]; 4 096 x 4 2.95 [2.95 .. 2.96] against 5.10 [5.07 .. 5.15]; 1 024 x 64 2.53 [2.51 .. 2.54] against 11.9 [11.8 .. 12.0]
+ * (4.7 x); 64 x 16 1.84 against 2.43; 16 x 16 1.81 against 1.93; 8 x 16 1.82 against 1.92; 4 x 16 1.81 [1.79 .. 1.82] against 1.86 [1.86 ..
+ * 1.88] — ahead beyond the spread from 64 partials on; 2 x 16 (1.81 against 1.82) and 1 x 16 (1.82 against 1.80) tie.  The call is one verify
+ * pass of n items plus 0.9 ms whatever the partials: per stage 256 x 16 0.41 + 0.37 + 0.98 + 0.08 ms, 4 096 x 4 0.42 + 0.37 + 2.09 + 0.09,
+ * 1 024 x 64 0.61 + 0.38 + 1.46 + 0.09 — ms[2] is a bitmap verify's Miller loop and final exponentiation at n items (0.98 ms up to 256, 1.46 at
+ * 1 024, 2.09 at 4 096), as the optimistic collect found.  ANY tuple that goes the exact way costs the call one pass of the queue's lane-pair
+ * kernels (aggregate keys, Miller loop, final exponentiation), 6.3 - 7.6 ms here whether it queues 4 partials or 656: one failing tuple takes
+ * 256 x 16 to 8.62 ms [8.15 .. 9.47] against the exact merge's 3.18, 4 096 x 4 to 9.33 against 5.67, 16 x 16 to 9.05 against 1.91, and 1 024 x
+ * 64 to 8.92 against 12.8 (still ahead); 1 % wrong partials spread over the call: 256 x 16 (41 tuples fail) 8.72 against 3.18, 4 096 x 4 (164)
+ * 9.45 against 5.67, 1 024 x 64 (655 tuples, 41 920 partials queued) 13.3 against 12.1 — the exact call plus the optimistic pass.  A tuple whose
+ * candidates OVERLAP sends itself the exact way: one tuple of 4 096 one-bit partials over 256 keys takes 10.4 ms against 4.21 (both selects
+ * are serial in the partials: 1.7 ms each).  So: this call where partials are disjoint and almost all valid and the call has 64 partials or
+ * more (BN254_OPT_MERGE_OPT_MIN_PARTS); the exact call for per-partial verdicts, for overlapping partials (single shares belong to the
+ * collect), and where a failing tuple is expected in a call the exact route serves in under 8 ms.  The exact merge is unchanged by the
+ * route: against the parent commit's build in the same process, alternating, -1.8 % .. +0.1 % over the ten shapes (the parent's own calls
+ * spread -1.5 % .. +1.8 % about their median).  Not measured: between 32 and 64 partials, tuples of other lengths than 4, 16 and 64 below 256
+ * tuples, key sets other than 256 keys, wrong partials beyond the four shapes named.
+ * Profiling: ms[0] = front end (hash, range rule, pre-check) and provisional select-and-sum, ms[1] = aggregate keys of the union rows, ms[2] =
+ * the tuples' Miller loop and final exponentiation, ms[3] = fallback and re-select.
+ * Out of scope: a short queue served by the small-batch kernels, a randomised merge, the multi-GPU layer, compressed input. */
+int bn254_batch_merge_keyed_bitmap_optimistic(bn254_ctx *ctx, const uint8_t *msgs, const uint64_t *msg_off /* n+1 */,
+                                              const uint8_t *parts /* n_parts*64 */, const uint32_t *part_bits /* n_parts*bm_words */,
+                                              const uint64_t *part_off /* n+1 */, size_t n_parts, size_t n, size_t bm_words, uint32_t flags,
+                                              uint8_t *part_status /* n_parts */, uint8_t *part_taken /* n_parts */, uint8_t *tuple_status /* n */,
+                                              uint8_t *agg_sigs /* n*64 */, uint32_t *signer_bits /* n*bm_words */,
+                                              uint32_t *n_signers /* n, or NULL */);
+int bn254_batch_merge_keyed_bitmap_optimistic_device(bn254_ctx *ctx, const uint8_t *d_msgs, const uint64_t *d_msg_off, const uint8_t *d_parts,
+                                                     const uint32_t *d_part_bits, const uint64_t *d_part_off, size_t n_parts, size_t n,
+                                                     size_t bm_words, uint32_t flags, uint8_t *d_part_status, uint8_t *d_part_taken,
+                                                     uint8_t *d_tuple_status, uint8_t *d_agg_sigs, uint32_t *d_signer_bits, uint32_t *d_n_signers,
+                                                     void *stream);
 
 /* compressed wire formats (src/utils.rs:84-104, :130-158): out = uncompressed point, status as
  * bn::G1::from_compressed / bn::G2::from_compressed report through src/types.rs:91-93, :233-237, checked in the order
@@ -752,6 +827,11 @@ int bn254_ctx_set_profiling(bn254_ctx *ctx, int enabled);
                                             between 16 and 32 partials at 8 words and at 8 at 128 words; 16 loses 0.15 ms at (8 words, 16
                                             partials) where 32 would lose 0.42 ms at (128 words, 16 partials).  Lengths between the
                                             powers of two were not measured.  Same bytes either way */
+#define BN254_OPT_MERGE_OPT_MIN_PARTS 45 /* bn254_batch_merge_keyed_bitmap_optimistic: calls with fewer partials take the exact merge (same
+                                           bytes).  Default 64, the smallest measured size from which the call wins beyond the spread with every partial
+                                           valid (tuples of 16 partials over 256 keys: 4 x 16 1.81 ms against 1.86; 2 x 16 and 1 x 16 tie;
+                                           nothing measured between 32 and 64 partials).  A call whose tuples hold overlapping candidates
+                                           loses at any size, which a count of partials cannot see; 0 = no lower bound */
 int bn254_ctx_set_option(bn254_ctx *ctx, int option, int value);
 /* per-kernel times of the last verify-shaped call with profiling on (HIP events on the call's stream):
  * ms[0] decode, ms[1] hash-to-G1, ms[2] Miller loop, ms[3] final exponentiation.  The host-pointer bn254_batch_verify runs
@@ -768,7 +848,10 @@ int bn254_ctx_set_option(bn254_ctx *ctx, int option, int value);
  * aggregate keys, ms[2] = the tuples' Miller loop and final exponentiation, ms[3] = exact fallback + re-sum (a call whose tuples are checked
  * in several pieces: ms[1] runs from the provisional sum to the last piece's keys);
  * merge_keyed_bitmap the exact collect's four: ms[0] = front end (hash-to-G1 once per tuple, decode, spread, aggregate keys), ms[1] =
- * select-and-sum (it runs last), ms[2] Miller loop, ms[3] final exponentiation (the last slice's). */
+ * select-and-sum (it runs last), ms[2] Miller loop, ms[3] final exponentiation (the last slice's);
+ * merge_keyed_bitmap_optimistic on its optimistic route ms[0] = front end (hash, range rule, pre-check) + provisional select-and-sum, ms[1] =
+ * the aggregate keys of the union rows, ms[2] = the tuples' Miller loop and final exponentiation, ms[3] = fallback + re-select (a call whose
+ * tuples are checked in several pieces: ms[1] runs from the provisional select to the last piece's keys). */
 int bn254_ctx_last_kernel_ms(bn254_ctx *ctx, float ms[4]);
 /* with BN254_OPT_CLOCK_PROBE on: achieved shader clock in MHz of the lane-pair Miller kernels [0], final exponentiations [1] and probe
  * kernels (bn254_probe_issue_rate, bn254_probe_leaf_floor) [2] launched on this context SINCE THE PREVIOUS CALL of this function (or
@@ -979,6 +1062,10 @@ int bn254_debug_collect_rand_last(bn254_ctx *ctx, uint64_t out[4]);
  * {tuples checked optimistically, tuples that passed, tuples sent to the exact route (failed, a duplicate, or below the per-tuple minimum),
  * shares verified exactly}; all 0 when the call as a whole took the exact route.  Synchronises the device. */
 int bn254_debug_collect_opt_last(bn254_ctx *ctx, uint64_t out[4]);
+/* what the last bn254_batch_merge_keyed_bitmap_optimistic[_device] did, counted by the call's own kernels and summed over its slices: out =
+ * {tuples checked optimistically, tuples that passed, tuples sent the exact way (failed, or an overlap), partials verified exactly}; all 0
+ * ("did not run") after any call that did not take the route — the exact merge and the collect calls included.  Synchronises the device. */
+int bn254_debug_merge_opt_last(bn254_ctx *ctx, uint64_t out[4]);
 /* what the last bn254_batch_verify_keyed_bitmap_randomized[_device] did (its last slice): out = {1 if it took the randomised route, groups that
  * reached the check, table pairs of all group checks (S_g's included), failed groups, tuples re-checked, groups of one tuple (r = 1)}; all 0
  * when it took the exact route.  Synchronises the device. */

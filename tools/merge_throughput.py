@@ -17,7 +17,16 @@ select-and-sum, ms[2] Miller loop, ms[3] final exponentiation).
 2^31 - 1 = a lane per tuple) over tuple lengths 4 .. 256 at bm_words 8 and 128, about --sweep-parts partials per call, all 256 keys signing
 in k disjoint committees: the select-and-sum interval (median of --reps profiled calls) and the whole call.  One JSON line per shape or
 sweep point (default stdout).
-    python tools/merge_throughput.py [out.jsonl] [--reps R] [--keys K] [--sweep] [--sweep-parts P] [--note TEXT] [shape ...]   shape = n:k[:1]"""
+--optimistic: instead of (a) against (b), bn254_batch_merge_keyed_bitmap_optimistic_device — its route forced with
+BN254_OPT_MERGE_OPT_MIN_PARTS = 0 — against the exact merge of the same build, alternating, over the shapes above and n x 16 for n = 1, 2,
+4, 8, 16, 64: whole-call medians with min and max, the four intervals of one profiled optimistic call (ms[0] front end + provisional
+select-and-sum, ms[1] aggregate keys of the union rows, ms[2] the tuples' Miller loop and final exponentiation, ms[3] fallback + re-select),
+the debug hook's counters, and whether all six outputs are the exact call's bytes.  --bad-one-tuple replaces the first partial's signature by
+its neighbour's (one failing tuple); --bad-percent P does so for P % of the partials, spread evenly.  --other-lib PATH loads a second build
+of the library (the parent commit's, say) into the same process, with a context of its own over the same keys, and times ITS exact merge in
+the same alternation: what the new route costs the old one.
+    python tools/merge_throughput.py [out.jsonl] [--reps R] [--keys K] [--sweep] [--sweep-parts P] [--optimistic] [--bad-one-tuple]
+                                     [--bad-percent P] [--other-lib PATH] [--note TEXT] [shape ...]   shape = n:k[:1]"""
 import argparse
 import ctypes
 import hashlib
@@ -32,6 +41,7 @@ import numpy as np  # noqa: E402
 
 R = 0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001
 SHAPES = [(256, 16, 0), (4096, 4, 0), (1024, 64, 0), (1, 4096, 1)]
+OPT_SHAPES = SHAPES + [(n, 16, 0) for n in (1, 2, 4, 8, 16, 64)]
 SWEEP_LENGTHS = [4, 8, 16, 32, 64, 128, 256]
 SWEEP_WIDTHS = [8, 128]
 MSG_LEN = 32
@@ -89,9 +99,13 @@ def main():
     ap.add_argument("--keys", type=int, default=256)
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--sweep-parts", type=int, default=16384)
+    ap.add_argument("--optimistic", action="store_true")
+    ap.add_argument("--bad-one-tuple", action="store_true")
+    ap.add_argument("--bad-percent", type=float, default=0.0)
+    ap.add_argument("--other-lib", default=None, help="a second build whose exact merge is timed in the same alternation")
     ap.add_argument("--note", default=None, help="recorded with every line, e.g. which build ran")
     a = ap.parse_intermixed_args()
-    shapes = [tuple(int(x) for x in (s + ":0").split(":")[:3]) for s in a.shapes] or SHAPES
+    shapes = [tuple(int(x) for x in (s + ":0").split(":")[:3]) for s in a.shapes] or (OPT_SHAPES if a.optimistic else SHAPES)
 
     import torch  # (first: one HIP runtime per process)
     import bn254_amd
@@ -134,14 +148,20 @@ def main():
     assert st == bytes(n_keys) and eng.register_keys(pool) == bytes(n_keys)
     stage_names = ("decode", "hash_to_g1", "miller_loop", "final_exp")
 
-    def setup(n, k, bm_words, n_signing, one_bit, tag):
-        """the inputs of one shape, resident; -> dict"""
+    def setup(n, k, bm_words, n_signing, one_bit, tag, bad=()):
+        """the inputs of one shape, resident; -> dict.  bad: the partials whose signature is replaced by the next partial's"""
         n_parts = n * k
         sets = [c for t in committees(rng, n, k, n_keys, n_signing, one_bit) for c in t]
         msgs = [hashlib.sha256(b"merge/tp/%s/%d/%d/%d" % (tag.encode(), n, k, i)).digest() for i in range(n)]
         rep = [msgs[p // k] for p in range(n_parts)]
         parts, st = eng.batch_sign(rep, b"".join((sum(sks[j] for j in c) % R).to_bytes(32, "big") for c in sets))
         assert st == bytes(n_parts)
+        if bad:
+            honest, parts = parts, bytearray(parts)
+            for p in bad:
+                q = (p + 1) % n_parts
+                parts[64 * p:64 * p + 64] = honest[64 * q:64 * q + 64]
+            parts = bytes(parts)
         rows = rows_of(sets, bm_words)
         d = dict(n=n, k=k, n_parts=n_parts, bm_words=bm_words, parts=parts, rows=rows, sets=sets)
         d["d_msgs"], d["d_moff"] = dev(b"".join(msgs)), dev((np.arange(n + 1, dtype=np.uint64) * MSG_LEN).tobytes())
@@ -188,6 +208,79 @@ def main():
                 row.update(box)
                 print(json.dumps(row), file=out, flush=True)
                 del d
+        return
+
+    if a.optimistic:
+        from bn254_amd.engine import MERGE_OPT_MIN_PARTS_DEFAULT, OPT_MERGE_OPT_MIN_PARTS
+        other = None
+        if a.other_lib:                                    # a second build in the same process: its own context over the same keys
+            vp, sz, u32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32
+            other = ctypes.CDLL(os.path.abspath(a.other_lib))
+            other.bn254_ctx_create.argtypes = [ctypes.c_int32, ctypes.POINTER(vp)]
+            other.bn254_ctx_register_keys.argtypes = [vp, vp, sz, u32, vp]
+            other.bn254_batch_merge_keyed_bitmap_device.argtypes = [vp, vp, vp, vp, vp, vp, sz, sz, sz, u32, vp, vp, vp, vp, vp, vp, vp]
+            other.bn254_ctx_destroy.argtypes = [vp]
+            other.bn254_ctx_destroy.restype = None
+            h2 = vp()
+            check(other.bn254_ctx_create(0, ctypes.byref(h2)))
+            reg = ctypes.create_string_buffer(n_keys)
+            check(other.bn254_ctx_register_keys(h2, pool, n_keys, 0, reg))
+            assert reg.raw == bytes(n_keys)
+            box["other_lib_sha256"] = hashlib.sha256(open(a.other_lib, "rb").read()).hexdigest()[:16]
+        names = ("d_pst", "d_tkn", "d_tst", "d_agg", "d_bits", "d_cnt")
+        for n, k, one_bit in shapes:
+            bm_words = (n_keys + 31) // 32
+            n_parts = n * k
+            bad = [0] if a.bad_one_tuple else []
+            if a.bad_percent > 0:
+                step = max(int(round(100.0 / a.bad_percent)), 1)
+                bad = list(range(step // 2, n_parts, step))
+            d = setup(n, k, bm_words, (2 * n_keys) // 3, bool(one_bit), "opt", bad)
+
+            def device_call(fn, ctx):
+                check(fn(ctx, d["d_msgs"].data_ptr(), d["d_moff"].data_ptr(), d["d_parts"].data_ptr(), d["d_rows"].data_ptr(), d["d_poff"].data_ptr(), n_parts, n,
+                         bm_words, 0, d["d_pst"].data_ptr(), d["d_tkn"].data_ptr(), d["d_tst"].data_ptr(), d["d_agg"].data_ptr(), d["d_bits"].data_ptr(),
+                         d["d_cnt"].data_ptr(), stream))
+            legs = {"exact": lambda: merge_call(d), "opt": lambda: device_call(lib.bn254_batch_merge_keyed_bitmap_optimistic_device, h)}
+            if other is not None:
+                legs["other_exact"] = lambda: device_call(other.bn254_batch_merge_keyed_bitmap_device, h2)
+            eng.set_option(OPT_MERGE_OPT_MIN_PARTS, 0)
+            try:
+                outs = {}
+                for _ in range(2):                             # two warm-up calls each; the second one's outputs are compared
+                    for name, fn in legs.items():
+                        fn()
+                        torch.cuda.synchronize()
+                        outs[name] = tuple(d[x].cpu().numpy().tobytes() for x in names)
+                        if name == "opt":
+                            hook = eng.debug_merge_opt_last()
+                ms = {name: [] for name in legs}
+                for _ in range(a.reps):
+                    for name, fn in legs.items():
+                        ms[name].append(timed(fn, ts))
+                stages = [round(x, 3) for x in profiled(legs["opt"])]
+                exact_stages = [round(x, 3) for x in profiled(legs["exact"])]
+            finally:
+                eng.set_option(OPT_MERGE_OPT_MIN_PARTS, MERGE_OPT_MIN_PARTS_DEFAULT)
+            med = {name: statistics.median(v) for name, v in ms.items()}
+            row = {"optimistic": True, "shape": "%dx%d%s" % (n, k, " one-bit" if one_bit else ""), "n": n, "partials_per_tuple": k, "n_parts": n_parts,
+                   "bm_words": bm_words, "bad_parts": len(bad), "bad_in_one_tuple": bool(a.bad_one_tuple)}
+            for name in legs:
+                row.update({name + "_ms": round(med[name], 3), name + "_min_ms": round(min(ms[name]), 3), name + "_max_ms": round(max(ms[name]), 3)})
+            row.update({"exact_over_opt": round(med["exact"] / med["opt"], 2), "opt_wins_beyond_spread": max(ms["opt"]) < min(ms["exact"]),
+                        "opt_loses_beyond_spread": min(ms["opt"]) > max(ms["exact"]),
+                        "opt_stages_ms": stages, "opt_stage_slots": "front end + provisional select-and-sum, aggregate keys, tuples' miller + final_exp, fallback + re-select",
+                        "exact_stages_ms": exact_stages, "hook": hook, "same_outputs_as_exact": outs["opt"] == outs["exact"]})
+            if other is not None:
+                row.update({"same_outputs_other_exact": outs["other_exact"] == outs["exact"],
+                            "exact_vs_other_percent": round(100.0 * (med["exact"] / med["other_exact"] - 1.0), 2),
+                            "other_spread_percent": [round(100.0 * (min(ms["other_exact"]) / med["other_exact"] - 1.0), 2),
+                                                     round(100.0 * (max(ms["other_exact"]) / med["other_exact"] - 1.0), 2)]})
+            row.update(box)
+            print(json.dumps(row), file=out, flush=True)
+            del d
+        if other is not None:
+            other.bn254_ctx_destroy(h2)
         return
 
     for n, k, one_bit in shapes:

@@ -572,8 +572,9 @@ def test_octet_and_pair_layouts_agree_with_oracle(eng, c, derived, kats):
 def test_every_boundary_of_the_routing_table_vs_expected(eng, c):
     """The batch size -> layout routing is ONE table (bn254_amd/csrc/bn254_ws.h: bn_route; bn254_debug_route_table hands out the rows of this
     context): every boundary of it, on both sides, is generated FROM the table — for the defaults and for three other settings of the
-    thresholds — and must give the expected status bytes (one batch, checked once against the oracle, cut at every size needed); the keyed
-    verify and check_public_keys take the same table and are cut at the same sizes."""
+    thresholds — and must give batch_verify's expected status bytes (one batch, checked once against the oracle, cut at every size needed).
+    This body calls batch_verify only: check_public_keys takes the same table and is cut at its boundaries in
+    tests/test_gpu_check_public_keys.py (test_routing_table_boundaries_at_the_defaults), the keyed verify in its own test files."""
     from bn254_amd.engine import OPT_LM_MAX_BATCH, OPT_NONET_MAX_BATCH, OPT_NONET_WIDE, OPT_TRIO_MAX_BATCH
     from tests.datagen import make_verify_batch
     big = make_verify_batch(eng, 16386, corrupt_every=13)

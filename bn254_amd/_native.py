@@ -144,6 +144,13 @@ def load():
         L.bn254_batch_merge_keyed_bitmap_optimistic.argtypes = [vp, vp, vp, vp, vp, vp, sz, sz, sz, u32, vp, vp, vp, vp, vp, vp]
         L.bn254_batch_merge_keyed_bitmap_optimistic_device.argtypes = [vp, vp, vp, vp, vp, vp, sz, sz, sz, u32, vp, vp, vp, vp, vp, vp, vp]
         L.bn254_debug_merge_opt_last.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
+    if hasattr(L, "bn254_batch_pop_verify"):                          # absent from an older build loaded through BN254_LIB
+        L.bn254_batch_pop_prove.argtypes = [vp, vp, sz, vp, vp, vp]
+        L.bn254_batch_pop_prove_device.argtypes = [vp, vp, sz, vp, vp, vp, vp]
+        L.bn254_batch_pop_verify.argtypes = [vp, vp, vp, sz, u32, vp]
+        L.bn254_batch_pop_verify_device.argtypes = [vp, vp, vp, sz, u32, vp, vp]
+        L.bn254_ctx_register_keys_pop.argtypes = [vp, vp, vp, sz, u32, vp]
+        L.bn254_mgpu_register_keys_pop.argtypes = [vp, vp, vp, sz, u32, vp]
     L.bn254_debug_bitmap_rand_last.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     L.bn254_debug_bitmap_rand_sums.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), sz, sz, vp, vp, vp, vp, vp, vp]
     L.bn254_batch_verify_keyed_randomized.argtypes = [vp, vp, vp, vp, vp, sz, u32, vp, vp]
@@ -243,4 +250,6 @@ EXPORTED_SYMBOLS = [
     "bn254_mgpu_last_error", "bn254_mgpu_batch_verify", "bn254_mgpu_batch_verify_device", "bn254_mgpu_batch_pairing",
     "bn254_mgpu_batch_pairing_device", "bn254_mgpu_batch_hash_to_g1", "bn254_mgpu_batch_verify_compressed", "bn254_mgpu_register_keys",
     "bn254_mgpu_batch_verify_keyed", "bn254_mgpu_batch_aggregate_verify",
+    "bn254_batch_pop_prove", "bn254_batch_pop_prove_device", "bn254_batch_pop_verify", "bn254_batch_pop_verify_device",
+    "bn254_ctx_register_keys_pop", "bn254_mgpu_register_keys_pop",
 ]

@@ -9,6 +9,8 @@ bn254_amd/host/bn254.hpp (C++); INTEGRATION.md holds the Rust shim a maintainer 
     ECDSA.batch_verify_randomized(messages, signatures, public_keys, seed) -> same    (new, opt-in, probabilistic)
     ECDSA.aggregate_verify(messages, signature, public_keys) -> None/raise              (new: distinct messages, one sum)
     ECDSA.batch_aggregate_verify_distinct([(messages, signature, public_keys), ...]) -> [None | Error, ...]   (new)
+    PrivateKey.prove_possession() / PublicKey.verify_possession(proof) / ECDSA.batch_verify_possession / ECDSA.register_keys_proven
+                                                                 (new: proofs of possession, the remedy of src/lib.rs:34-38)
     check_public_keys(public_key_g2, public_key_g1)              src/ecdsa.rs:78-93
     PrivateKey / PublicKey / PublicKeyG1 / Signature             src/types.rs:13,81,151,222
 
@@ -91,6 +93,13 @@ class PrivateKey:
 
     def to_hex(self):
         return self.to_bytes().hex()
+
+    def prove_possession(self):
+        """The proof of possession of this key's PublicKey: the signature on POP_TAG + pk, pk the key's 128 uncompressed bytes
+        (include/bn254_hip.h: bn254_batch_pop_prove).  A signer must refuse application messages that begin with POP_TAG."""
+        _, pops, st = _eng().batch_pop_prove(self.to_bytes())
+        _raise(st[0])
+        return Signature(pops)
 
     def __eq__(self, other):
         return isinstance(other, PrivateKey) and other.value == self.value
@@ -201,6 +210,12 @@ class PublicKey:
         _raise(st[0])
         return cls(out)
 
+    def verify_possession(self, proof):
+        """None iff `proof` (a Signature) is this key's proof of possession — ECDSA.verify of POP_TAG + the key's bytes with the key
+        validated as from_uncompressed does (subgroup check, identity refused); raises the Error otherwise.  The proof is bound to
+        the key's encoding bytes (include/bn254_hip.h: bn254_batch_pop_verify)."""
+        _raise(ECDSA._possession_status([self], [proof], None)[0])
+
     def to_uncompressed(self):
         if self.raw == bytes(128):
             raise Error(ErrorKind.PointInJacobian)          # utils.rs:163
@@ -271,6 +286,30 @@ class ECDSA:
         return [None if s == 0 else Error(s) for s in st]
 
     @staticmethod
+    def _possession_status(public_keys, proofs, engine):
+        if len(public_keys) != len(proofs):
+            raise Error(ErrorKind.InvalidLength)
+        eng = engine or _eng()
+        return eng.batch_pop_verify(b"".join(p.raw for p in public_keys), b"".join(s.raw for s in proofs), flags=_engine.FLAG_REJECT_IDENTITY)
+
+    @staticmethod
+    def batch_verify_possession(public_keys, proofs, engine=None):
+        """result[j] is None iff public_keys[j].verify_possession(proofs[j]) succeeds, else the Error it would raise."""
+        return [None if s == 0 else Error(s) for s in ECDSA._possession_status(public_keys, proofs, engine)]
+
+    @staticmethod
+    def register_keys_proven(public_keys, proofs, engine=None):
+        """register_keys with every key's proof of possession checked on the device (include/bn254_hip.h: bn254_ctx_register_keys_pop):
+        result[j] is None, the Error register_keys gives for key j, or the Error verify_possession raises — and that result is the key's
+        registration status: every keyed call (batch_verify_keyed, the keyed-signers calls, the keyed aggregates) refuses a key whose
+        proof failed with Error(VerificationFailed).  The identity is refused, as a key and as a proof."""
+        if len(public_keys) != len(proofs):
+            raise Error(ErrorKind.InvalidLength)
+        eng = engine or _eng()
+        st = eng.register_keys_pop(b"".join(p.raw for p in public_keys), b"".join(s.raw for s in proofs), flags=_engine.FLAG_REJECT_IDENTITY)
+        return [None if s == 0 else Error(s) for s in st]
+
+    @staticmethod
     def batch_verify_keyed(messages, signatures, key_indices, engine=None):
         """batch_verify with public_keys[i] named by its index in the registered set: result[i] is None iff
         ECDSA.verify(messages[i], signatures[i], registered[key_indices[i]]) succeeds, Error(IndexOutOfBounds) for an index
@@ -287,7 +326,7 @@ class ECDSA:
         """One message, one already aggregated signature, and the indices (in the registered set, ECDSA.register_keys) of the keys that
         signed: None iff e(H(message), sum of those keys) * e(signature, -G2) == 1; raises Error(IndexOutOfBounds) for an index outside
         the set, a refused key's registration Error, else what verify raises (include/bn254_hip.h: bn254_batch_verify_keyed_bitmap).
-        Assumes a proof of possession of every registered key."""
+        Assumes a proof of possession of every registered key (ECDSA.register_keys_proven registers a set with its proofs checked)."""
         _raise(ECDSA._keyed_signers_status([(message, signature, signer_indices)], engine)[0])
 
     @staticmethod
@@ -387,7 +426,7 @@ class ECDSA:
         descending number of signers for the largest cover).  Returns (aggregate Signature, sorted indices of the union, statuses, taken):
         statuses[k] is None or the Error verify_keyed_signers would raise for partial k, taken[k] a bool.  The first two feed
         ECDSA.verify_keyed_signers.  Raises the message's Error(HashToPointError) (include/bn254_hip.h: bn254_batch_merge_keyed_bitmap).
-        Assumes a proof of possession of every registered key."""
+        Assumes a proof of possession of every registered key (ECDSA.register_keys_proven registers a set with its proofs checked)."""
         r = ECDSA.batch_merge_keyed_signers([(message, parts)], engine, n_keys)[0]
         if isinstance(r, Error):
             raise r
@@ -564,7 +603,8 @@ class ECDSA:
         """Aggregate signature over DISTINCT messages (the IRTF BLS draft's AggregateVerify): signature = the sum of the signatures of
         public_keys[j] on messages[j] (`Add for Signature`, src/types.rs:264-270).  Returns None, or raises the Error of the first failing
         check: signature, keys, messages, then VerificationFailed (include/bn254_hip.h: bn254_batch_aggregate_verify_distinct).
-        Assumes a proof of possession of every key; distinct messages are NOT enforced here."""
+        Assumes a proof of possession of every key (PublicKey.verify_possession, ECDSA.batch_verify_possession; for registered keys
+        ECDSA.register_keys_proven); distinct messages are NOT enforced here."""
         if len(messages) != len(public_keys):
             raise Error(ErrorKind.InvalidLength)
         _raise(ECDSA._distinct_status([(messages, signature, public_keys)], engine)[0])

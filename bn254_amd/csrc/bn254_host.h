@@ -150,6 +150,9 @@ struct bn254_ctx {
   int merge_opt_min_parts;   // BN254_OPT_MERGE_OPT_MIN_PARTS: the optimistic merge from this many partials on
   uint32_t* mgo_stats;       // what its last call did on the device (bn254_debug_merge_opt_last); inside collect_buf
   int mgo_last_ran;          // ... and whether that call took the optimistic route at all
+  // proofs of possession (bn254_pop.hip): the composed messages TAG || pk, their offsets, and the second status array of a fold, grown on demand
+  uint8_t* pop_buf;
+  size_t pop_cap;
 };
 
 struct ScopedEvents {
@@ -292,6 +295,11 @@ BN_HIDDEN int launch_verify_miller_fe(bn254_ctx* c, hipStream_t s, size_t n, int
 // decode status, then the routing table's keyed kernels; and the statuses of such a batch when no key is registered
 BN_HIDDEN int launch_keyed_miller_fe(bn254_ctx* c, hipStream_t s, size_t n, const uint32_t* d_key_idx, uint8_t* d_status);
 BN_HIDDEN int launch_keyed_no_keys(bn254_ctx* c, hipStream_t s, size_t n, uint8_t* d_status);
+// a registration in two steps (bn254_rand.hip), shared by bn254_ctx_register_keys and bn254_ctx_register_keys_pop: quiesce, drop the previous set
+// (n_keys = 0, the bitmap call's vector and tables invalid) and make room for n_keys keys; then decode and tabulate the staged keys on c->stream.
+// The caller sets c->n_keys once the new set stands.
+BN_HIDDEN int register_keys_begin(bn254_ctx* c, size_t n_keys);
+BN_HIDDEN int launch_register_keys(bn254_ctx* c, const uint8_t* d_pks, size_t n_keys, uint32_t flags);
 // ... and its RANDOMISED form (bn254_rand.hip; the body of bn254_batch_verify_keyed_randomized behind decode and hash): the items that pass
 // rules 1-3 grouped by key in runs of 64, every group one combined check, the items of a failing group re-checked exactly through the
 // workspace's h_list / h_cnt queue.  Item i's weight is rand_scalar(seed, index_base + i).  mode: 0 = 128-bit weights, 1 = 64-bit, 2 = GLV.

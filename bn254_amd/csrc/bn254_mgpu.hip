@@ -350,6 +350,11 @@ int job_register_keys(bn254_mgpu*, Dev* d, void* p) {                   // the w
   const RegisterKeysArgs& a = *(const RegisterKeysArgs*)p;
   return bn254_ctx_register_keys(d->ctx, a.pks, a.n_keys, a.flags, d->index == 0 ? a.key_status : nullptr);
 }
+struct RegisterKeysPopArgs { const uint8_t* pks; const uint8_t* pops; size_t n_keys; uint32_t flags; uint8_t* key_status; };
+int job_register_keys_pop(bn254_mgpu*, Dev* d, void* p) {               // ... and the same with every key's proof of possession checked on every device
+  const RegisterKeysPopArgs& a = *(const RegisterKeysPopArgs*)p;
+  return bn254_ctx_register_keys_pop(d->ctx, a.pks, a.pops, a.n_keys, a.flags, d->index == 0 ? a.key_status : nullptr);
+}
 struct KeyedHostArgs { const uint8_t* msgs; const uint64_t* off; const uint8_t* sigs; const uint32_t* key_idx; size_t n; uint32_t flags; uint8_t* status; };
 int job_verify_keyed_host(bn254_mgpu* mg, Dev* d, void* p) {
   const KeyedHostArgs& a = *(const KeyedHostArgs*)p;
@@ -648,6 +653,13 @@ int bn254_mgpu_register_keys(bn254_mgpu* mg, const uint8_t* pks, size_t n_keys, 
   mg->err[0] = 0;
   RegisterKeysArgs a = {pks, n_keys, flags, key_status};
   return run_all(mg, job_register_keys, &a);
+}
+int bn254_mgpu_register_keys_pop(bn254_mgpu* mg, const uint8_t* pks, const uint8_t* pops, size_t n_keys, uint32_t flags, uint8_t* key_status) {
+  if (!mg || (n_keys && (!pks || !pops))) return BN254_E_BAD_ARGUMENT;
+  DeviceGuard guard;
+  mg->err[0] = 0;
+  RegisterKeysPopArgs a = {pks, pops, n_keys, flags, key_status};
+  return run_all(mg, job_register_keys_pop, &a);
 }
 
 int bn254_mgpu_batch_verify_keyed(bn254_mgpu* mg, const uint8_t* msgs, const uint64_t* off, const uint8_t* sigs, const uint32_t* key_idx, size_t n,

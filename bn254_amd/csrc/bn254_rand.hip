@@ -401,12 +401,9 @@ int launch_keyed_rand_checks(bn254_ctx* c, hipStream_t s, size_t n, const uint32
   return 0;
 }
 
-extern "C" {
-
-// ---- keyed verify (include/bn254_hip.h) ---------------------------------------------------------------------------------
-int bn254_ctx_register_keys(bn254_ctx* c, const uint8_t* pks, size_t n_keys, uint32_t flags, uint8_t* key_status) {
-  if (!c || (n_keys && !pks) || n_keys > 0xFFFFFFFFu) return BN254_E_BAD_ARGUMENT;
-  HIP_TRY(hipSetDevice(c->device));
+// a registration's first steps (bn254_host.h), shared by bn254_ctx_register_keys and bn254_ctx_register_keys_pop (bn254_pop.hip): the previous
+// set is dropped and the tables hold n_keys keys ...
+int register_keys_begin(bn254_ctx* c, size_t n_keys) {
   { int rc_ = ctx_quiesce(c); if (rc_) return rc_; }   // no keyed verify — on c->stream or on the caller's stream of the last call — may still be reading the previous tables
   c->n_keys = 0;
   c->bm_bad_valid = c->bm_tab_valid = false;          // the bitmap call's bad-bit vector and subset tables belong to the previous set
@@ -423,13 +420,29 @@ int bn254_ctx_register_keys(bn254_ctx* c, const uint8_t* pks, size_t n_keys, uin
     HIP_TRY(hipMalloc((void**)&c->key_inf, n_keys));
     c->key_cap = n_keys;
   }
+  return 0;
+}
+// ... and the keys staged at d_pks are decoded and tabulated on the context's stream
+int launch_register_keys(bn254_ctx* c, const uint8_t* d_pks, size_t n_keys, uint32_t flags) {
+  k_register_keys<<<grid_for(n_keys), BN_WAVE, 0, c->stream>>>(d_pks, n_keys, flags & FLAG_REJECT_IDENTITY, c->key_lines, c->key_st, c->key_inf, c->key_xy);
+  k_neg_g2_key_lines<<<1, BN_WAVE, 0, c->stream>>>(c->key_lines + n_keys * (size_t)BN_N_FIXED_LINES * BN_KEY_LINE_WORDS);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+extern "C" {
+
+// ---- keyed verify (include/bn254_hip.h) ---------------------------------------------------------------------------------
+int bn254_ctx_register_keys(bn254_ctx* c, const uint8_t* pks, size_t n_keys, uint32_t flags, uint8_t* key_status) {
+  if (!c || (n_keys && !pks) || n_keys > 0xFFFFFFFFu) return BN254_E_BAD_ARGUMENT;
+  HIP_TRY(hipSetDevice(c->device));
+  { int rc_ = register_keys_begin(c, n_keys); if (rc_) return rc_; }
+  if (n_keys == 0) return 0;
   HostStaging st(c);
   const uint8_t* d_pks = st.in(3, pks, n_keys * 128);
   st.copy_back(key_status, c->key_st, n_keys);
   if (!st.ok()) return st.rc;
-  k_register_keys<<<grid_for(n_keys), BN_WAVE, 0, c->stream>>>(d_pks, n_keys, flags & FLAG_REJECT_IDENTITY, c->key_lines, c->key_st, c->key_inf, c->key_xy);
-  k_neg_g2_key_lines<<<1, BN_WAVE, 0, c->stream>>>(c->key_lines + n_keys * (size_t)BN_N_FIXED_LINES * BN_KEY_LINE_WORDS);
-  HIP_TRY(hipGetLastError());
+  { int rc_ = launch_register_keys(c, d_pks, n_keys, flags); if (rc_) return rc_; }
   if (const int rc = st.finish()) return rc;
   c->n_keys = n_keys;
   return 0;

@@ -12,6 +12,7 @@ FLAG_G2_SUBGROUP_CHECK = 1
 FLAG_REJECT_IDENTITY = 2
 FLAG_RAND64 = 0x100
 FLAG_RAND_GLV = 0x200
+POP_TAG = b"BN254G2_POP_V01:"   # BN254_POP_TAG (include/bn254_hip.h): the proof of possession of a key is its holder's signature on POP_TAG + pk
 OPT_SPLIT_MILLER = 1
 OPT_HASH_MAX_TRIES = 2
 OPT_RAND_ITEMS_PER_LANE = 3
@@ -552,6 +553,45 @@ class Engine:
         self.n_registered_keys = n
         return st.raw[:n]
 
+    def register_keys_pop(self, pks, pops, flags=0):
+        """register_keys with every key's proof of possession checked (include/bn254_hip.h: bn254_ctx_register_keys_pop): pops = one 64-byte
+        proof per key.  Returns the per-key status bytes — the plain registration's if non-zero, else the proof's under
+        flags & FLAG_REJECT_IDENTITY — which ARE the keys' registration statuses: every keyed call refuses an unproven key with 9.
+        If the call fails the context is left without keys."""
+        n = len(pks) // G2_BYTES
+        assert len(pks) == n * G2_BYTES and len(pops) == n * G1_BYTES
+        st = ctypes.create_string_buffer(max(n, 1))
+        self.n_registered_keys = 0
+        _check("bn254_ctx_register_keys_pop", self._lib.bn254_ctx_register_keys_pop(self._h, bytes(pks), bytes(pops), n, flags, st))
+        self.n_registered_keys = n
+        return st.raw[:n]
+
+    def batch_pop_prove(self, sks):
+        """n private keys (32 B each) -> (public keys, proofs of possession, status bytes): pk = sk * G2 as batch_g2_mul(None, sks,
+        reduce_scalar=True) gives it, pop = sk * H(POP_TAG || pk) as batch_sign gives it"""
+        n = len(sks) // SCALAR_BYTES
+        assert len(sks) == n * SCALAR_BYTES
+        pks = ctypes.create_string_buffer(max(n, 1) * G2_BYTES)
+        pops = ctypes.create_string_buffer(max(n, 1) * G1_BYTES)
+        status = ctypes.create_string_buffer(max(n, 1))
+        _check("bn254_batch_pop_prove", self._lib.bn254_batch_pop_prove(self._h, bytes(sks), n, pks, pops, status))
+        return pks.raw[:n * G2_BYTES], pops.raw[:n * G1_BYTES], status.raw[:n]
+
+    def batch_pop_verify(self, pks, pops, flags=0):
+        """status bytes of the proofs: batch_verify of message POP_TAG || pk_i, signature pop_i, key pk_i under
+        flags | FLAG_G2_SUBGROUP_CHECK.  Pass FLAG_REJECT_IDENTITY: the identity key with the identity proof verifies without it."""
+        n = len(pks) // G2_BYTES
+        assert len(pks) == n * G2_BYTES and len(pops) == n * G1_BYTES
+        status = ctypes.create_string_buffer(max(n, 1))
+        _check("bn254_batch_pop_verify", self._lib.bn254_batch_pop_verify(self._h, bytes(pks), bytes(pops), n, flags, status))
+        return status.raw[:n]
+
+    def batch_pop_prove_device(self, d_sks, n, d_pks, d_pops, d_status, stream=None):
+        _check("bn254_batch_pop_prove_device", self._lib.bn254_batch_pop_prove_device(self._h, d_sks, n, d_pks, d_pops, d_status, stream))
+
+    def batch_pop_verify_device(self, d_pks, d_pops, n, d_status, flags=0, stream=None):
+        _check("bn254_batch_pop_verify_device", self._lib.bn254_batch_pop_verify_device(self._h, d_pks, d_pops, n, flags, d_status, stream))
+
     def batch_verify_keyed(self, messages, sigs, key_idx, flags=0):
         n = len(messages)
         assert len(sigs) == n * G1_BYTES and len(key_idx) == n
@@ -896,6 +936,14 @@ class MultiEngine:
         n = len(pks) // G2_BYTES
         st = ctypes.create_string_buffer(max(n, 1))
         self._check("bn254_mgpu_register_keys", self._lib.bn254_mgpu_register_keys(self._h, bytes(pks), n, flags, st))
+        return st.raw[:n]
+
+    def register_keys_pop(self, pks, pops, flags=0):
+        """... with every key's proof of possession (64 B each) checked on every device -> per-key status bytes (Engine.register_keys_pop)"""
+        n = len(pks) // G2_BYTES
+        assert len(pks) == n * G2_BYTES and len(pops) == n * G1_BYTES
+        st = ctypes.create_string_buffer(max(n, 1))
+        self._check("bn254_mgpu_register_keys_pop", self._lib.bn254_mgpu_register_keys_pop(self._h, bytes(pks), bytes(pops), n, flags, st))
         return st.raw[:n]
 
     def batch_verify_keyed(self, messages, sigs, key_idx, flags=0):

@@ -184,7 +184,8 @@ struct ECDSA {
   }
   // Aggregate signature over DISTINCT messages (the IRTF BLS draft's AggregateVerify): signature = the sum of the signatures of
   // public_keys[j] on messages[j].  Throws the Error of the first failing check (signature, keys, messages, then VerificationFailed);
-  // include/bn254_hip.h: bn254_batch_aggregate_verify_distinct.  Assumes a proof of possession of every key; distinct messages are not enforced.
+  // include/bn254_hip.h: bn254_batch_aggregate_verify_distinct.  Assumes a proof of possession of every key (verify_possession,
+  // register_keys_proven below); distinct messages are not enforced.
   struct Aggregate { std::vector<std::vector<uint8_t>> messages; Signature signature; std::vector<PublicKey> public_keys; };
   static void aggregate_verify(const std::vector<std::vector<uint8_t>>& messages, const Signature& signature, const std::vector<PublicKey>& public_keys,
                                Engine& e = Engine::default_engine()) {
@@ -234,6 +235,41 @@ struct ECDSA {
     std::vector<uint8_t> pks(keys.size() * 128), status(keys.size(), 0);
     for (size_t j = 0; j < keys.size(); ++j) std::memcpy(&pks[128 * j], keys[j].raw.data(), 128);
     check_rc("bn254_ctx_register_keys", bn254_ctx_register_keys(e.raw(), pks.data(), keys.size(), 0, status.data()));
+    return status;
+  }
+  // PROOFS OF POSSESSION (include/bn254_hip.h: BN254_POP_TAG, bn254_batch_pop_prove / _verify, bn254_ctx_register_keys_pop) — what the
+  // same-message aggregate calls below assume of the registered keys.  The proof of a key is its holder's signature on BN254_POP_TAG || pk,
+  // pk the key's 128 uncompressed bytes.  Two caller rules: a signer must refuse application messages that begin with BN254_POP_TAG, and a
+  // proof is bound to the key's encoding bytes.  The identity is refused, as a key and as a proof (BN254_FLAG_REJECT_IDENTITY).
+  static Signature prove_possession(const PrivateKey& k, Engine& e = Engine::default_engine()) {
+    uint8_t pk[128], st = 0;
+    Signature pop;
+    check_rc("bn254_batch_pop_prove", bn254_batch_pop_prove(e.raw(), k.bytes.data(), 1, pk, pop.raw.data(), &st));
+    check_status(st);
+    return pop;
+  }
+  // result[j] == 0 iff proofs[j] is the proof of possession of keys[j], else the ErrorKind verify_possession would throw
+  static std::vector<uint8_t> batch_verify_possession(const std::vector<PublicKey>& keys, const std::vector<Signature>& proofs,
+                                                      Engine& e = Engine::default_engine()) {
+    const size_t n = keys.size();
+    if (proofs.size() != n) throw Error(ErrorKind::InvalidLength);
+    std::vector<uint8_t> pks(n * 128), pops(n * 64), status(n, 0);
+    for (size_t j = 0; j < n; ++j) { std::memcpy(&pks[128 * j], keys[j].raw.data(), 128); std::memcpy(&pops[64 * j], proofs[j].raw.data(), 64); }
+    check_rc("bn254_batch_pop_verify", bn254_batch_pop_verify(e.raw(), pks.data(), pops.data(), n, BN254_FLAG_REJECT_IDENTITY, status.data()));
+    return status;
+  }
+  static void verify_possession(const PublicKey& key, const Signature& proof, Engine& e = Engine::default_engine()) {
+    check_status(batch_verify_possession({key}, {proof}, e)[0]);
+  }
+  // register_keys with every proof checked on the device: result[j] == 0, the ErrorKind of key j, or that of its proof (9 for a wrong one) —
+  // and that byte is the key's registration status: every keyed call below refuses an unproven key with it
+  static std::vector<uint8_t> register_keys_proven(const std::vector<PublicKey>& keys, const std::vector<Signature>& proofs,
+                                                   Engine& e = Engine::default_engine()) {
+    const size_t n = keys.size();
+    if (proofs.size() != n) throw Error(ErrorKind::InvalidLength);
+    std::vector<uint8_t> pks(n * 128), pops(n * 64), status(n, 0);
+    for (size_t j = 0; j < n; ++j) { std::memcpy(&pks[128 * j], keys[j].raw.data(), 128); std::memcpy(&pops[64 * j], proofs[j].raw.data(), 64); }
+    check_rc("bn254_ctx_register_keys_pop", bn254_ctx_register_keys_pop(e.raw(), pks.data(), pops.data(), n, BN254_FLAG_REJECT_IDENTITY, status.data()));
     return status;
   }
   // result[i] == 0 iff verify(messages[i], signatures[i], registered[key_indices[i]]) succeeds; 2 (IndexOutOfBounds) outside the set

@@ -353,7 +353,8 @@ int bn254_batch_aggregate_verify_distinct_keyed_randomized_device(bn254_ctx *ctx
  * m_i once per set bit, with key_idx = the set bits in ascending order — e(H(m), sum pk_j) = prod e(H(m), pk_j).  Consequences: an EMPTY
  * bitmap checks e(sigma, -G2) == 1; a registered identity key contributes nothing; a selection whose keys sum to the identity (a key and its
  * negation) behaves like the empty bitmap — the aggregate key is never "rejected as identity".  Security, as for the distinct-message calls:
- * a proof of possession of every registered key is assumed (src/lib.rs:34-38) — without one, rogue keys forge aggregates.
+ * a proof of possession of every registered key is assumed (src/lib.rs:34-38) — without one, rogue keys forge aggregates;
+ * bn254_ctx_register_keys_pop registers a set with its proofs checked.
  * Argument checks, BN254_E_MISALIGNED (d_signer_bits is a 4-byte-aligned uint32 array) and the _device conventions are those of
  * bn254_batch_verify_keyed; BN254_OPT_MAX_CHUNK slices the tuples as there.
  * Cost: the aggregate key of a tuple is summed on the device from SUBSET TABLES of the registered set — the 256 subset sums of every 8
@@ -716,6 +717,59 @@ int bn254_batch_merge_keyed_bitmap_optimistic_device(bn254_ctx *ctx, const uint8
                                                      uint8_t *d_tuple_status, uint8_t *d_agg_sigs, uint32_t *d_signer_bits, uint32_t *d_n_signers,
                                                      void *stream);
 
+/* PROOFS OF POSSESSION — what every same-message aggregate call above assumes of the registered keys (the bitmap verify and its randomised
+ * form, the three collect calls, the two merge calls, the distinct-message keyed calls).  Without one, an attacker who registers
+ * pk* = a G2 - pk_v makes the aggregate key of {victim, attacker} equal a G2 and forges "both signed m" as a H(m) without the victim's
+ * secret.  The reference names the remedy (src/lib.rs:34-38): each key holder proves possession "by signing a message".
+ * THE SCHEME.  BN254_POP_TAG is 16 ASCII bytes.  The proof message of a key is TAG || pk: the tag, then the 128 bytes of the key's
+ * uncompressed G2 encoding EXACTLY as the caller passes them — 144 bytes.  It is hashed by the library's one hash-to-G1 (try-and-increment,
+ * src/hash.rs:29-63).  The proof is pop = sk * H(TAG || pk), a 64-byte uncompressed G1 point — ECDSA::sign (src/ecdsa.rs:26-35) on that
+ * message — and it is checked as e(H(TAG || pk), pk) * e(pop, -G2::one()) == 1 — ECDSA::verify (src/ecdsa.rs:49-64).
+ * TWO CALLER RULES.  The reference's hash has no domain separation (src/hash.rs:30-33), so the tag separates proofs from signatures only
+ * if the caller keeps them apart:
+ *   1. a signer must REFUSE application messages that begin with BN254_POP_TAG — a signature on TAG || pk' is a proof for pk';
+ *   2. a proof is bound to the key's ENCODING BYTES: the bytes hashed are the bytes passed, so a key must be presented to the verifier in
+ *      the encoding it was proven in (the uncompressed encoding of a curve point is unique; an encoding with a coordinate >= q is refused).
+ * DEFINING IDENTITIES, byte for byte.
+ *   bn254_batch_pop_prove[_device]: pks = what bn254_batch_g2_mul(NULL, sks, reduce_scalar = 1) gives; pops[i] = what bn254_batch_sign
+ *     gives for the message TAG || pks[i] and sks[i]; status[i] = the first non-zero status of the two (the key derivation's, then the
+ *     signature's: 1 HashToPointError is the only one either can give).  Pinned: a scalar >= r is reduced mod r by both steps (Fr::from_slice),
+ *     so sk and sk mod r give the same bytes; sk == 0 (mod r) gives the identity twice — pk and pop all-zero bytes, status 0.  That pair
+ *     verifies under flags = 0 (e(H, O) * e(O, -G2) == 1) and reports 4 under BN254_FLAG_REJECT_IDENTITY: a verifier of proofs passes that flag.
+ *   bn254_batch_pop_verify[_device]: status[i] = the status of bn254_batch_verify on message TAG || pk_i, signature pop_i, key pk_i under
+ *     flags | BN254_FLAG_G2_SUBGROUP_CHECK (a proof for a key outside the order-r subgroup means nothing).  Status order as there: the
+ *     proof's decode status, the key's, the hash status, then 0 or 9.
+ *   bn254_ctx_register_keys_pop: key_status[j] (may be NULL) = what bn254_ctx_register_keys reports for key j if that is non-zero, else what
+ *     bn254_batch_pop_verify reports for (pk_j, pop_j) under flags & BN254_FLAG_REJECT_IDENTITY.  THAT BYTE BECOMES THE KEY'S REGISTRATION
+ *     STATUS: every keyed call reads it where it read the plain registration's, so a key whose proof failed is refused with 9 by
+ *     bn254_batch_verify_keyed, by rule 2 of the bitmap verify (the lowest bad bit) and its randomised form, by the collect, merge and
+ *     distinct-message keyed calls — while the proven keys verify.  Otherwise the call is bn254_ctx_register_keys: it replaces the key set,
+ *     waits as that call does, invalidates the bitmap call's bad-bit vector and subset tables, is synchronous (statuses and tables are final
+ *     when it returns), and bn254_ctx_register_keys afterwards registers plainly again.
+ *     FAIL CLOSED: if anything after the keys' own registration step fails (a HIP error, an allocation), the context is left with NO keys
+ *     registered — never with keys in place whose proofs were not checked.  Argument errors (pops == NULL with n_keys > 0 included) return
+ *     BN254_E_BAD_ARGUMENT before anything is touched: the previous set stays.
+ *     Cost: the plain registration, then on the same stream a composer kernel (TAG || pk_j from the staged keys: no second copy of the
+ *     keys crosses the bus), the decode of the proofs, the hash of the messages and ONE keyed verify per key against the key's own freshly
+ *     built line table, on the routing-table row of n_keys items; a fold kernel writes the statuses.
+ * These calls take no message buffer: a pending bn254_ctx_expect_msgs_len is neither consumed nor applied (the composed buffer is bounded by
+ * its true length) and stays armed for the caller's next hashing call.  _device forms: d_sks, d_pks, d_pops 4-byte aligned, else
+ * BN254_E_MISALIGNED; they only enqueue (the first key derivation of a context builds its fixed-base table synchronously, as
+ * bn254_batch_g2_mul_device does); BN254_OPT_MAX_CHUNK and the workspace rule slice them as they slice a verify.  n < 2^32.
+ * bn254_ctx_register_pools takes raw pools, not registered keys: proofs for pooled keys are out of scope (check them with
+ * bn254_batch_pop_verify first).  Measured cost of the three calls: DESIGN.md section 10j. */
+#define BN254_POP_TAG "BN254G2_POP_V01:"
+#define BN254_POP_TAG_LEN 16
+int bn254_batch_pop_prove(bn254_ctx *ctx, const uint8_t *sks /* n*32 */, size_t n, uint8_t *pks /* n*128 */, uint8_t *pops /* n*64 */,
+                          uint8_t *status /* n */);
+int bn254_batch_pop_prove_device(bn254_ctx *ctx, const uint8_t *d_sks, size_t n, uint8_t *d_pks, uint8_t *d_pops, uint8_t *d_status, void *stream);
+int bn254_batch_pop_verify(bn254_ctx *ctx, const uint8_t *pks /* n*128 */, const uint8_t *pops /* n*64 */, size_t n, uint32_t flags,
+                           uint8_t *status /* n */);
+int bn254_batch_pop_verify_device(bn254_ctx *ctx, const uint8_t *d_pks, const uint8_t *d_pops, size_t n, uint32_t flags, uint8_t *d_status,
+                                  void *stream);
+int bn254_ctx_register_keys_pop(bn254_ctx *ctx, const uint8_t *pks /* n_keys*128 */, const uint8_t *pops /* n_keys*64 */, size_t n_keys,
+                                uint32_t flags, uint8_t *key_status /* n_keys or NULL */);
+
 /* compressed wire formats (src/utils.rs:84-104, :130-158): out = uncompressed point, status as
  * bn::G1::from_compressed / bn::G2::from_compressed report through src/types.rs:91-93, :233-237, checked in the order
  * those decoders work (an input with several faults reports the first):
@@ -925,6 +979,10 @@ int bn254_mgpu_batch_verify_device(bn254_mgpu *mg, const uint8_t *const *d_msgs,
 int bn254_mgpu_batch_verify_compressed(bn254_mgpu *mg, const uint8_t *msgs, const uint64_t *msg_off, const uint8_t *sigs33, const uint8_t *pks65,
                                        size_t n, uint8_t *status);
 int bn254_mgpu_register_keys(bn254_mgpu *mg, const uint8_t *pks /* n_keys*128 */, size_t n_keys, uint32_t flags, uint8_t *key_status /* or NULL */);
+/* ... and with every key's proof of possession checked: bn254_ctx_register_keys_pop on every device (each checks the whole set, so no
+ * device holds an unproven key as registered); device 0 reports key_status */
+int bn254_mgpu_register_keys_pop(bn254_mgpu *mg, const uint8_t *pks /* n_keys*128 */, const uint8_t *pops /* n_keys*64 */, size_t n_keys,
+                                 uint32_t flags, uint8_t *key_status /* or NULL */);
 int bn254_mgpu_batch_verify_keyed(bn254_mgpu *mg, const uint8_t *msgs, const uint64_t *msg_off, const uint8_t *sigs, const uint32_t *key_idx, size_t n,
                                   uint32_t flags, uint8_t *status);
 int bn254_mgpu_batch_aggregate_verify(bn254_mgpu *mg, const uint8_t *msgs, const uint64_t *msg_off, size_t n_msgs, const uint8_t *pk_pool,

@@ -193,7 +193,19 @@ int bn254_batch_hash_to_g1_device(bn254_ctx *ctx, const uint8_t *d_msgs, const u
                                   uint8_t *d_status, uint8_t *d_tries, void *stream);
 
 /* status[i] = (bn::pairing_batch(&[(g1[i*k+j], g2[i*k+j]); k]) == Gt::one()) ? 0 : 9 — the kernel
- * shared by ECDSA::verify and check_public_keys (src/ecdsa.rs:57-63, :86-92). */
+ * shared by ECDSA::verify and check_public_keys (src/ecdsa.rs:57-63, :86-92).
+ *
+ * The contract of the three pairing calls (tests/pairing_cases.py, tests/test_gpu_pairing.py):
+ *   - Operands: all-zero bytes are the identity; a pair with an identity operand contributes one.  An item is decoded in the order
+ *     g1[i*k], g2[i*k], g1[i*k+1], g2[i*k+1], ...: inside a pair G1 comes before G2, across the pairs of an item the lowest index comes
+ *     first, and status[i] is the code of the FIRST operand in that order that does not decode (6 = a coordinate >= q; 4 = not on the
+ *     curve / the twist, outside the subgroup under BN254_FLAG_G2_SUBGROUP_CHECK, an identity under BN254_FLAG_REJECT_IDENTITY).  Only
+ *     when every operand decodes is it 0 / 9 by the product.  This is the order of the oracle's bn254o_batch_pairing.
+ *   - k >= 1 has no upper bound of its own: a call needs workspace for n*k pairs (bn254_ctx_reserve's size, grown on demand; the
+ *     call fails with the allocation's error when it cannot be had), and every route takes any k.  k == 0 is BN254_E_BAD_ARGUMENT.
+ *   - gt[i] of an item whose status is a decode error is defined, and the same on every route: the product with the GENERATOR of its
+ *     group (G1::one(), G2::one()) in place of every operand of the item that did not decode — all of them, not only the first — and
+ *     the other operands as given.  It says nothing about the input; a caller reads status[i] first. */
 int bn254_batch_pairing_check(bn254_ctx *ctx, const uint8_t *g1 /* n*k*64 */, const uint8_t *g2 /* n*k*128 */, size_t n, size_t k,
                               uint32_t flags, uint8_t *status /* n */);
 /* gt[i] = prod_j e(g1[i*k+j], g2[i*k+j]) = Miller product ^ ((q^12-1)/r), 384 bytes each.  Batches that cannot fill the chip (n*k <=

@@ -103,6 +103,14 @@ int bn254_ctx_synchronize(bn254_ctx *ctx);
  * reversed offset pairs can be detected.  No counterpart in the reference: a Rust slice (src/ecdsa.rs:49) carries its length. */
 int bn254_ctx_expect_msgs_len(bn254_ctx *ctx, uint64_t msgs_len);
 
+/* Message arrays, in every call that takes msgs / msg_off: message i is the bytes msgs[msg_off[i] .. msg_off[i+1]), of any length
+ * (an empty message is msg_off[i] == msg_off[i+1]); msg_off has n + 1 non-decreasing entries.  msg_off[0] need NOT be 0: the bytes
+ * in front of it belong to no message and are never hashed.  The HOST forms nevertheless stage msgs[0 .. msg_off[n]) as a whole
+ * (a call that slices its batch: each slice's own bytes) — so msgs must be readable from its first byte, and a large msg_off[0]
+ * costs staging memory and copy time; pass msgs + msg_off[0] with rebased offsets to avoid both.  The *_device forms read message bytes only.
+ * (tests/hash_cases.py, tests/test_gpu_hash_cases.py: every length 0 .. 200, the block edges of the SHA-256 padding, up to
+ * 2^20 + 1 bytes, offsets behind a junk prefix.) */
+
 /* status[i] = what ECDSA::verify(msg_i, sig_i, pk_i) returns (src/ecdsa.rs:49-64):
  * e(H(m), pk) * e(sig, -G2::one()) == 1.  Decoding errors of sig (first) or pk are reported with
  * the code from_uncompressed would give (src/utils.rs:107-127). */

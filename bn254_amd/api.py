@@ -61,6 +61,31 @@ def _eng():
     return _engine.default_engine()
 
 
+def _lagrange_at_zero(xs):
+    """the Lagrange coefficients at zero of the distinct points xs, mod r: prod x_k / prod (x_k - x_j) over k != j"""
+    out = []
+    for j, xj in enumerate(xs):
+        num = den = 1
+        for k, xk in enumerate(xs):
+            if k != j:
+                num, den = num * xk % _R, den * (xk - xj) % _R
+        out.append(num * pow(den, -1, _R) % _R)
+    return out
+
+
+def threshold_deal(secret, t, n, seed):
+    """Shamir-share `secret` (an integer, taken mod r) among n key indices with threshold t: a polynomial f of degree t - 1 with f(0) = secret
+    and the other coefficients drawn from random.Random(seed); returns the n share secrets [PrivateKey(f(1)), .., PrivateKey(f(n))] — key
+    index j holds f(j + 1), the numbering of ECDSA.threshold_combine_keyed.  For tests and examples: pure Python integers, NOT constant-time,
+    and a seeded generator is no source of key material; a deployment deals with a DKG or a trusted dealer of its own."""
+    import random
+    if not 1 <= int(t) <= int(n):
+        raise ValueError("need 1 <= t <= n")
+    rnd = random.Random(seed)
+    coeffs = [int(secret) % _R] + [rnd.randrange(_R) for _ in range(int(t) - 1)]
+    return [PrivateKey(sum(c * pow(x, e, _R) for e, c in enumerate(coeffs)) % _R) for x in range(1, int(n) + 1)]
+
+
 def _neg_fq_bytes(b):
     v = int.from_bytes(b, "big")
     return (0 if v == 0 else _Q - v).to_bytes(32, "big")
@@ -417,6 +442,92 @@ class ECDSA:
             signers = [j for j in range(32 * bm_words) if (row[j // 32] >> (j % 32)) & 1]
             out.append((Signature(agg[64 * i:64 * i + 64]), signers, [None if b == 0 else Error(b) for b in st]))
         return out
+
+    @staticmethod
+    def threshold_combine_keyed(message, signatures, key_indices, threshold, engine=None, n_keys=None):
+        """t-of-n threshold BLS over the registered keys (ECDSA.register_keys; key j is the share key f(j + 1) * G2 of a dealing, so index 0
+        is a legal signer): every share signatures[k], said to be by key key_indices[k], is verified against its key; if at least
+        `threshold` keys have a valid share, the shares of the `threshold` LOWEST such keys are interpolated at zero.  Returns (the group
+        Signature — which ECDSA.verify accepts under the group key, ECDSA.threshold_group_key —, the sorted indices used, statuses) with
+        statuses[k] None or the Error ECDSA.batch_verify_keyed would give share k.  Raises Error(VerificationFailed) with fewer valid
+        keys — the error's .signers lists who was there, .statuses the shares' — and the message's Error(HashToPointError).  The library
+        checks every share against its registered key; it does NOT check that the registered keys lie on one polynomial of degree
+        threshold - 1: that is the dealer's or the DKG's job (include/bn254_hip.h: bn254_batch_threshold_combine_keyed)."""
+        r = ECDSA.batch_threshold_combine_keyed([(message, signatures, key_indices)], threshold, engine, n_keys)[0]
+        if isinstance(r, Error):
+            raise r
+        return r
+
+    @staticmethod
+    def batch_threshold_combine_keyed(items, threshold, engine=None, n_keys=None):
+        """items: a list of (message, signatures, key_indices), one threshold for all; result[i] is what ECDSA.threshold_combine_keyed returns
+        for item i, or the Error it would raise.  A malformed item raises Error(InvalidLength) / Error(IndexOutOfBounds), a threshold below
+        1 ValueError, before any device work."""
+        if int(threshold) < 1 or int(threshold) >= 1 << 32:
+            raise ValueError("threshold must be between 1 and 2^32 - 1")
+        rows = []
+        for item in items:
+            if len(item) != 3:
+                raise Error(ErrorKind.InvalidLength)
+            message, signatures, key_indices = item
+            sigs, idx = list(signatures), [int(j) for j in key_indices]
+            if len(sigs) != len(idx) or any(len(s.raw) != _engine.G1_BYTES for s in sigs):
+                raise Error(ErrorKind.InvalidLength)
+            if any(j < 0 or j >= 1 << 32 for j in idx):
+                raise Error(ErrorKind.IndexOutOfBounds)
+            rows.append((bytes(message), sigs, idx))
+        eng = engine or _eng()
+        if n_keys is None:
+            n_keys = getattr(eng, "n_registered_keys", None)
+        if n_keys is None:
+            raise ValueError("the engine does not know its registered key count: pass n_keys")
+        bm_words = max((int(n_keys) + 31) // 32, 1)
+        share_st, tuple_st, group, bits, _ = eng.batch_threshold_combine_keyed(
+            [r[0] for r in rows], b"".join(s.raw for r in rows for s in r[1]), [j for r in rows for j in r[2]], [len(r[2]) for r in rows], bm_words,
+            int(threshold))
+        out, at = [], 0
+        for i, (_, _, idx) in enumerate(rows):
+            st = [None if b == 0 else Error(b) for b in share_st[at:at + len(idx)]]
+            at += len(idx)
+            row = bits[i * bm_words:(i + 1) * bm_words]
+            signers = [j for j in range(32 * bm_words) if (row[j // 32] >> (j % 32)) & 1]
+            if tuple_st[i]:
+                err = Error(tuple_st[i])
+                err.signers, err.statuses = signers, st
+                out.append(err)
+            else:
+                out.append((Signature(group[64 * i:64 * i + 64]), signers, st))
+        return out
+
+    @staticmethod
+    def threshold_group_key(indices, public_keys, engine=None):
+        """The group key f(0) * G2 interpolated from the share keys of `indices` (distinct key indices; public_keys[k] is the key of
+        indices[k] = f(indices[k] + 1) * G2): sum lambda_k pk_k, the coefficients from Python integers, the points through
+        bn254_batch_g2_mul and bn254_batch_g2_sum.  Any `threshold` keys of one dealing give the same key."""
+        idx, pks = [int(j) for j in indices], list(public_keys)
+        if len(idx) != len(pks) or not idx or len(set(idx)) != len(idx):
+            raise Error(ErrorKind.InvalidLength)
+        if any(j < 0 or j >= 1 << 32 for j in idx):
+            raise Error(ErrorKind.IndexOutOfBounds)
+        lam = _lagrange_at_zero([j + 1 for j in idx])
+        eng = engine or _eng()
+        prod, st = eng.batch_g2_mul(b"".join(p.raw for p in pks), b"".join(k.to_bytes(32, "big") for k in lam), len(idx))
+        for b in st:
+            _raise(b)
+        out, st = eng.batch_g2_sum(prod, [0, len(idx)])
+        _raise(st[0])
+        return PublicKey(out)
+
+    @staticmethod
+    def g1_msm(points, scalars, engine=None):
+        """sum scalars[k] * points[k] in G1 (points: Signature / PublicKeyG1, scalars: integers, taken mod r) as a Signature
+        (include/bn254_hip.h: bn254_batch_g1_msm); raises the first point's decode Error"""
+        pts, ks = list(points), [int(k) % _R for k in scalars]
+        if len(pts) != len(ks) or any(len(p.raw) != _engine.G1_BYTES for p in pts):
+            raise Error(ErrorKind.InvalidLength)
+        out, st = (engine or _eng()).batch_g1_msm(b"".join(p.raw for p in pts), b"".join(k.to_bytes(32, "big") for k in ks), [0, len(pts)])
+        _raise(st[0])
+        return Signature(out)
 
     @staticmethod
     def merge_keyed_signers(message, parts, engine=None, n_keys=None):

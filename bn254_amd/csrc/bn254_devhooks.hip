@@ -12,6 +12,9 @@
 #include "bn254_hash.h"
 #include "bn254_io.h"
 #include "bn254_pairing.h"
+#include "bn254_collect.h"
+#include "bn254_fr.h"
+#include "bn254_threshold.h"
 
 using namespace bn254;
 
@@ -109,6 +112,38 @@ KERNEL_SMALL void k_debug_read_p1(Ws ws, size_t base, size_t n, uint8_t* out) {
   G1Affine p;
   ws_load_g1(ws, PL_P1X, BY_P1_INF, base + i, p);
   encode_g1(out + 64 * i, p);
+}
+
+// Fr, element-wise (bn254_fr.h): operands as 32 big-endian bytes, reduced on load.  op 0 mul, 1 add, 2 sub, 3 neg, 4 inv (0 -> 0),
+// 5 the round trip into Montgomery form and back, 6 the low 32 bits of a (its last four bytes) loaded as a uint32_t
+KERNEL_SMALL void k_debug_fr_op(int op, const uint8_t* a, const uint8_t* b, size_t n, uint8_t* out) {
+  size_t i = (size_t)blockIdx.x * BN_WAVE + threadIdx.x;
+  if (i >= n) return;
+  const Fr x = fr_from_be(a + 32 * i), y = b ? fr_from_be(b + 32 * i) : fr_zero();
+  Fr r;
+  switch (op) {
+    case 0: r = fr_mul(x, y); break;
+    case 1: r = fr_add(x, y); break;
+    case 2: r = fr_sub(x, y); break;
+    case 3: r = fr_neg(x); break;
+    case 4: r = fr_inv(x); break;
+    case 6: r = fr_from_u32(__builtin_bswap32(((const uint32_t*)(a + 32 * i))[7])); break;
+    default: r = x; break;
+  }
+  fr_to_be(out + 32 * i, r);
+}
+// the Lagrange coefficient at zero of every point within its segment (bn254_threshold.h: th_lagrange_points): one lane per point, which
+// finds its segment by a search of the (host-checked, non-decreasing) offsets
+KERNEL_SMALL void k_debug_lagrange(const uint32_t* x, const uint64_t* seg, size_t m, size_t n, uint8_t* out) {
+  size_t j = (size_t)blockIdx.x * BN_WAVE + threadIdx.x;
+  if (j >= m) return;
+  size_t a = 0, b = n;                                 // the first segment that ends behind j
+  while (a < b) {
+    const size_t mid = (a + b) >> 1;
+    if (seg[mid + 1] > j) b = mid; else a = mid + 1;
+  }
+  const uint64_t lo = seg[a], len = seg[a + 1] - lo;
+  fr_to_be(out + 32 * j, th_lagrange_points(x + lo, len, j - lo));
 }
 
 // ---- in-process issue-rate probe (bench.py's roofline calibration) --------------------------------------------
@@ -507,6 +542,35 @@ int bn254_debug_fp_op(bn254_ctx* c, int op, const uint8_t* a, const uint8_t* b, 
   uint8_t *d_out = st.out(2, n * 32, out), *d_status = st.out(3, n, status);
   if (!st.ok()) return st.rc;
   k_debug_fp_op<<<grid_for(n), BN_WAVE, 0, c->stream>>>(op, d_a, d_b, n, d_out, d_status);
+  HIP_TRY(hipGetLastError());
+  return st.finish();
+}
+int bn254_debug_fr_op(bn254_ctx* c, int op, const uint8_t* a, const uint8_t* b, size_t n, uint8_t* out) {
+  if (!c || op < 0 || op > 6 || (n && (!a || !out)) || (n && op <= 2 && !b)) return BN254_E_BAD_ARGUMENT;
+  if (n == 0) return 0;
+  HIP_TRY(hipSetDevice(c->device));
+  HostStaging st(c);
+  const uint8_t* d_a = st.in(0, a, n * 32);
+  const uint8_t* d_b = b ? st.in(1, b, n * 32) : nullptr;
+  uint8_t* d_out = st.out(2, n * 32, out);
+  if (!st.ok()) return st.rc;
+  k_debug_fr_op<<<grid_for(n), BN_WAVE, 0, c->stream>>>(op, d_a, d_b, n, d_out);
+  HIP_TRY(hipGetLastError());
+  return st.finish();
+}
+int bn254_debug_lagrange_at_zero(bn254_ctx* c, const uint32_t* x, const uint64_t* seg_off, size_t n, uint8_t* out) {
+  if (!c || (n && !seg_off)) return BN254_E_BAD_ARGUMENT;
+  if (n == 0) return 0;
+  if (seg_off[0] != 0 || !offsets_ok(seg_off, n) || seg_off[n] > 0xFFFFFFFFu) return BN254_E_BAD_ARGUMENT;
+  const size_t m = (size_t)seg_off[n];
+  if (m == 0) return 0;
+  if (!x || !out) return BN254_E_BAD_ARGUMENT;
+  HIP_TRY(hipSetDevice(c->device));
+  HostStaging st(c);
+  const uint8_t *d_x = st.in(0, x, m * sizeof(uint32_t)), *d_seg = st.in(1, seg_off, (n + 1) * sizeof(uint64_t));
+  uint8_t* d_out = st.out(2, m * 32, out);
+  if (!st.ok()) return st.rc;
+  k_debug_lagrange<<<grid_for(m), BN_WAVE, 0, c->stream>>>((const uint32_t*)d_x, (const uint64_t*)d_seg, m, n, d_out);
   HIP_TRY(hipGetLastError());
   return st.finish();
 }

@@ -875,6 +875,7 @@ void bn254_ctx_destroy(bn254_ctx* c) {
   if (c->bm_bad) (void)hipFree(c->bm_bad);
   if (c->bm_tab) (void)hipFree(c->bm_tab);
   if (c->pop_buf) (void)hipFree(c->pop_buf);
+  if (c->th_buf) (void)hipFree(c->th_buf);
   for (int i = 0; i < 5; ++i) (void)hipEventDestroy(c->ev[i]);
   (void)hipEventDestroy(c->kd_fork);
   (void)hipEventDestroy(c->kd_join);

@@ -153,6 +153,10 @@ struct bn254_ctx {
   // proofs of possession (bn254_pop.hip): the composed messages TAG || pk, their offsets, and the second status array of a fold, grown on demand
   uint8_t* pop_buf;
   size_t pop_cap;
+  // threshold signatures and the scalar-weighted sum (bn254_threshold.hip): a Jacobian term and its status per share / term, and for the
+  // threshold call the coefficients, the take flags and the second claim rows, grown on demand
+  uint8_t* th_buf;
+  size_t th_cap;
 };
 
 struct ScopedEvents {

@@ -413,6 +413,13 @@ def main():
     o.append("BN_CONST uint32_t C_GLV_A1[2] = %s, C_GLV_B1N[4] = %s, C_GLV_A2[4] = %s;   /* reduced basis (a1, -b1n), (a2, a1) of the GLV lattice */" %
              (c_words(glv_a1, 2), c_words(glv_b1n, 4), c_words(glv_a2, 4)))
     o.append("BN_CONST uint32_t C_GLV_G1[3] = %s, C_GLV_G2[5] = %s;   /* floor(2^256 a1 / r), floor(2^256 b1n / r) */" % (c_words(glv_g1, 3), c_words(glv_g2, 5)))
+    # Fr, the scalar field (bn254_fr.h): Montgomery form with R = 2^256 on 8 x 32-bit words — Lagrange coefficients of threshold signatures
+    fr_mont = 1 << 256
+    fr_n0 = (-pow(R_ORDER, -1, 1 << 32)) % (1 << 32)
+    assert (R_ORDER * fr_n0 + 1) % (1 << 32) == 0 and 4 * R_ORDER < fr_mont          # a + b of two reduced values fits 256 bits with room
+    o.append("#define BN_FR_N0 0x%08xu   /* -r^-1 mod 2^32 */" % fr_n0)
+    o.append("BN_CONST uint32_t C_FR_R2[8] = %s;        /* (2^256)^2 mod r, plain U256: fr_to_mont(x) = fr_mul(x, R2) */" % c_u256(fr_mont * fr_mont % R_ORDER))
+    o.append("BN_CONST uint32_t C_FR_ONE[8] = %s;       /* 2^256 mod r: one in Montgomery form */" % c_u256(fr_mont % R_ORDER))
     o.append("/* width-4 sliding-window schedules for the fixed exponents: {squarings, odd multiplier} steps, MSB first;")
     o.append("   the first step only selects its multiplier, a multiplier of 0 means squarings only */")
     for name, e in (("QM2", Q - 2), ("QP1D4", (Q + 1) // 4), ("QM3D4", (Q - 3) // 4), ("QM1D2", (Q - 1) // 2)):

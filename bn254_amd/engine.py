@@ -390,6 +390,22 @@ class Engine:
     def batch_g2_sum(self, points, seg_off):
         return self._sum("bn254_batch_g2_sum", points, seg_off, G2_BYTES)
 
+    def batch_g1_msm(self, points, scalars, seg_off, reduce_scalar=False):
+        """segmented scalar-weighted sums in G1 (include/bn254_hip.h: bn254_batch_g1_msm): out[i] = sum of scalars[s] * points[s] over the
+        terms seg_off[i] .. seg_off[i+1]; returns (the n sums, the n status bytes)"""
+        n = len(seg_off) - 1
+        m = int(seg_off[n]) if n >= 0 else 0
+        assert len(points) == m * G1_BYTES and len(scalars) == m * SCALAR_BYTES
+        off = (ctypes.c_uint64 * (n + 1))(*seg_off)
+        out = ctypes.create_string_buffer(max(n, 1) * G1_BYTES)
+        status = ctypes.create_string_buffer(max(n, 1))
+        _check("bn254_batch_g1_msm", self._lib.bn254_batch_g1_msm(self._h, bytes(points), bytes(scalars), off, n, int(reduce_scalar), out, status))
+        return out.raw[:n * G1_BYTES], status.raw[:n]
+
+    def batch_g1_msm_device(self, d_points, d_scalars, d_seg_off, n, d_out, d_status, reduce_scalar=False, stream=None):
+        _check("bn254_batch_g1_msm_device",
+               self._lib.bn254_batch_g1_msm_device(self._h, d_points, d_scalars, d_seg_off, n, int(reduce_scalar), d_out, d_status, stream))
+
     def batch_aggregate_verify(self, messages, pk_pool, sig_pool, tuple_msg, signer_lists, flags=0):
         """messages: M byte strings; pk_pool: S*128 B; sig_pool: M*S*64 B (signer s on message m at m*S+s);
         tuple i verifies messages[tuple_msg[i]] against the aggregate of signer_lists[i]."""
@@ -516,6 +532,22 @@ class Engine:
         status = ctypes.create_string_buffer(max(n, 1))
         _check("bn254_debug_fp_op", self._lib.bn254_debug_fp_op(self._h, op, bytes(a), None if b is None else bytes(b), n, out, status))
         return out.raw[:n * 32], status.raw[:n]
+
+    def debug_fr_op(self, op, a, b, n):
+        """Fr on n 32-byte big-endian operands (include/bn254_hip.h: bn254_debug_fr_op) -> n * 32 bytes"""
+        out = ctypes.create_string_buffer(max(n, 1) * 32)
+        _check("bn254_debug_fr_op", self._lib.bn254_debug_fr_op(self._h, op, bytes(a), None if b is None else bytes(b), n, out))
+        return out.raw[:n * 32]
+
+    def debug_lagrange_at_zero(self, xs, seg_off):
+        """the Lagrange coefficients at zero of the points xs (uint32) within their segments -> len(xs) * 32 bytes"""
+        n, m = len(seg_off) - 1, len(xs)
+        assert seg_off[n] == m
+        x = (ctypes.c_uint32 * max(m, 1))(*xs)
+        off = (ctypes.c_uint64 * (n + 1))(*seg_off)
+        out = ctypes.create_string_buffer(max(m, 1) * 32)
+        _check("bn254_debug_lagrange_at_zero", self._lib.bn254_debug_lagrange_at_zero(self._h, x, off, n, out))
+        return out.raw[:m * 32]
 
     def debug_fp12_op(self, op, a, b, n):
         out = ctypes.create_string_buffer(max(n, 1) * GT_BYTES)
@@ -645,6 +677,36 @@ class Engine:
             _check("bn254_batch_collect_keyed_bitmap", self._lib.bn254_batch_collect_keyed_bitmap(*head, *tail))
         out = (share_st.raw[:n_shares], tuple_st.raw[:n], agg.raw[:n * G1_BYTES], list(bits)[:n * bm_words])
         return out + (list(counts)[:n],) if want_counts else out
+
+    def batch_threshold_combine_keyed(self, messages, shares, share_keys, sizes, bm_words, threshold, flags=0):
+        """t-of-n threshold signatures over the registered keys (include/bn254_hip.h: bn254_batch_threshold_combine_keyed): the arguments of
+        batch_collect_keyed_bitmap and the threshold.  Returns (share status bytes, tuple status bytes, the n group signatures, the
+        n * bm_words words of the rows — the keys used, or of a failed tuple the keys that were there —, the counts of keys with a valid share)."""
+        n, n_shares = len(messages), len(share_keys)
+        assert len(sizes) == n and all(k >= 0 for k in sizes) and sum(sizes) == n_shares and len(shares) == n_shares * G1_BYTES
+        assert 0 < int(threshold) < 1 << 32, "threshold must be at least 1"
+        msgs, off = pack_messages(messages)
+        ends = [0]
+        for k in sizes:
+            ends.append(ends[-1] + int(k))
+        share_off = (ctypes.c_uint64 * (n + 1))(*ends)
+        keys = (ctypes.c_uint32 * max(n_shares, 1))(*share_keys)
+        share_st = ctypes.create_string_buffer(max(n_shares, 1))
+        tuple_st = ctypes.create_string_buffer(max(n, 1))
+        sigs = ctypes.create_string_buffer(max(n, 1) * G1_BYTES)
+        bits = (ctypes.c_uint32 * max(n * bm_words, 1))()
+        counts = (ctypes.c_uint32 * max(n, 1))()
+        _check("bn254_batch_threshold_combine_keyed",
+               self._lib.bn254_batch_threshold_combine_keyed(self._h, msgs, off, bytes(shares), keys, share_off, n_shares, n, bm_words, int(threshold), flags,
+                                                             share_st, tuple_st, sigs, bits, counts))
+        return share_st.raw[:n_shares], tuple_st.raw[:n], sigs.raw[:n * G1_BYTES], list(bits)[:n * bm_words], list(counts)[:n]
+
+    def batch_threshold_combine_keyed_device(self, d_msgs, d_msg_off, d_shares, d_share_key, d_share_off, n_shares, n, bm_words, threshold,
+                                             d_share_status, d_tuple_status, d_group_sigs, d_used_bits, d_n_valid=None, flags=0, stream=None):
+        _check("bn254_batch_threshold_combine_keyed_device",
+               self._lib.bn254_batch_threshold_combine_keyed_device(self._h, d_msgs, d_msg_off, d_shares, d_share_key, d_share_off, n_shares, n, bm_words,
+                                                                    threshold, flags, d_share_status, d_tuple_status, d_group_sigs, d_used_bits, d_n_valid,
+                                                                    stream))
 
     def batch_collect_keyed_bitmap_device(self, d_msgs, d_msg_off, d_shares, d_share_key, d_share_off, n_shares, n, bm_words, d_share_status,
                                           d_tuple_status, d_agg_sigs, d_signer_bits, d_n_signers=None, flags=0, stream=None):

@@ -417,6 +417,68 @@ struct ECDSA {
     check_status(r.status);
     return r;
   }
+  // t-of-n threshold signatures over the registered keys (include/bn254_hip.h: bn254_batch_threshold_combine_keyed): registered key j is the
+  // share key f(j + 1) * G2 of a dealing, an item's signatures are the validators' shares.  Every share is verified against its key; with at
+  // least `threshold` keys holding a valid share, the shares of the `threshold` lowest such keys are interpolated at zero: `signature` is the
+  // group signature (verify accepts it under f(0) * G2) and signer_indices the keys used.  status 9 (VerificationFailed): too few valid keys —
+  // signer_indices then lists who was there and the signature is the identity; else the message's hash ErrorKind.  The library does NOT check
+  // that the registered keys lie on one polynomial of degree threshold - 1: that is the dealer's or the DKG's job.
+  static std::vector<KeyedAggregateResult> batch_threshold_combine_keyed(const std::vector<ShareItem>& items, size_t n_keys, uint32_t threshold,
+                                                                         Engine& e = Engine::default_engine()) {
+    if (threshold == 0) throw Error(ErrorKind::InvalidLength);
+    const size_t n = items.size(), bm_words = (n_keys + 31) / 32 ? (n_keys + 31) / 32 : 1;
+    std::vector<uint64_t> off(n + 1, 0), share_off(n + 1, 0);
+    std::vector<uint8_t> msgs, shares;
+    std::vector<uint32_t> keys;
+    for (size_t i = 0; i < n; ++i) {
+      if (items[i].signatures.size() != items[i].key_indices.size()) throw Error(ErrorKind::InvalidLength);
+      off[i] = msgs.size();
+      share_off[i] = keys.size();
+      msgs.insert(msgs.end(), items[i].message.begin(), items[i].message.end());
+      for (const Signature& s : items[i].signatures) shares.insert(shares.end(), s.raw.begin(), s.raw.end());
+      keys.insert(keys.end(), items[i].key_indices.begin(), items[i].key_indices.end());
+    }
+    off[n] = msgs.size();
+    share_off[n] = keys.size();
+    std::vector<uint8_t> share_st(keys.size() + 1, 0), tuple_st(n + 1, 0), group(n * 64 + 1, 0);
+    std::vector<uint32_t> bits(n * bm_words + 1, 0);
+    shares.resize(shares.size() + 1);
+    keys.resize(keys.size() + 1);
+    check_rc("bn254_batch_threshold_combine_keyed",
+             bn254_batch_threshold_combine_keyed(e.raw(), msgs.data(), off.data(), shares.data(), keys.data(), share_off.data(), share_off[n], n, bm_words,
+                                                 threshold, 0, share_st.data(), tuple_st.data(), group.data(), bits.data(), nullptr));
+    std::vector<KeyedAggregateResult> out(n);
+    for (size_t i = 0; i < n; ++i) {
+      out[i].status = tuple_st[i];
+      std::memcpy(out[i].signature.raw.data(), &group[64 * i], 64);
+      for (size_t j = 0; j < 32 * bm_words; ++j)
+        if ((bits[i * bm_words + j / 32] >> (j % 32)) & 1u) out[i].signer_indices.push_back((uint32_t)j);
+      out[i].statuses.assign(share_st.begin() + share_off[i], share_st.begin() + share_off[i + 1]);
+    }
+    return out;
+  }
+  static KeyedAggregateResult threshold_combine_keyed(const std::vector<uint8_t>& message, const std::vector<Signature>& signatures,
+                                                      const std::vector<uint32_t>& key_indices, size_t n_keys, uint32_t threshold,
+                                                      Engine& e = Engine::default_engine()) {
+    KeyedAggregateResult r = batch_threshold_combine_keyed({ShareItem{message, signatures, key_indices}}, n_keys, threshold, e)[0];
+    check_status(r.status);
+    return r;
+  }
+  // sum scalars[k] * points[k] in G1 (include/bn254_hip.h: bn254_batch_g1_msm), scalars as 32 big-endian bytes each, taken mod r
+  static Signature g1_msm(const std::vector<Signature>& points, const std::vector<std::array<uint8_t, 32>>& scalars, Engine& e = Engine::default_engine()) {
+    if (points.size() != scalars.size()) throw Error(ErrorKind::InvalidLength);
+    std::vector<uint8_t> p(points.size() * 64 + 4, 0), k(points.size() * 32 + 4, 0);
+    for (size_t i = 0; i < points.size(); ++i) {
+      std::memcpy(&p[64 * i], points[i].raw.data(), 64);
+      std::memcpy(&k[32 * i], scalars[i].data(), 32);
+    }
+    const uint64_t seg[2] = {0, points.size()};
+    Signature out;
+    uint8_t st = 0;
+    check_rc("bn254_batch_g1_msm", bn254_batch_g1_msm(e.raw(), p.data(), k.data(), seg, 1, 1, out.raw.data(), &st));
+    check_status(st);
+    return out;
+  }
   // The inner node of an aggregation tree (include/bn254_hip.h: bn254_batch_merge_keyed_bitmap): one message and PARTIAL aggregates of it,
   // parts[k] = a summed signature and the indices of the registered keys it is said to sum.  Every partial is verified as verify_keyed_signers
   // verifies it; in the order given, the valid ones whose indices do not overlap what was taken before are added (first fit).

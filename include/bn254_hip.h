@@ -256,6 +256,30 @@ int bn254_batch_sign_device(bn254_ctx *ctx, const uint8_t *d_msgs, const uint64_
  * (unit-scalar "MSM" of config 3: aggregate public key / aggregate signature) */
 int bn254_batch_g1_sum(bn254_ctx *ctx, const uint8_t *points, const uint64_t *seg_off /* n+1 */, size_t n, uint8_t *out /* n*64 */, uint8_t *status);
 int bn254_batch_g2_sum(bn254_ctx *ctx, const uint8_t *points, const uint64_t *seg_off /* n+1 */, size_t n, uint8_t *out /* n*128 */, uint8_t *status);
+/* segmented SCALAR-WEIGHTED sum in G1: out[i] = sum over the terms s in [seg_off[i], seg_off[i+1]) of scalars[s] * points[s] — the sum of
+ * bn254_batch_g1_sum with a scalar per point (interpolating threshold signatures, linear combinations of commitments).
+ * DEFINING IDENTITY: byte for byte bn254_batch_g1_mul(points, scalars, reduce_scalar) followed by bn254_batch_g1_sum of the products over
+ * the same segments.  reduce_scalar as in bn254_batch_g1_mul (a raw 256-bit scalar acts mod r on G1 either way).  Statuses follow
+ * bn254_batch_g1_sum: the first non-zero decode status of a point in segment order wins, and the output is then the identity as 64 zero
+ * bytes; an empty segment gives the identity with status 0; the identity (64 zero bytes) is a legal point.
+ * Argument checks: n < 2^32, at most 2^32 - 1 terms; host form: seg_off non-decreasing (else BN254_E_BAD_ARGUMENT), points and scalars hold
+ * seg_off[n] entries.  _device form: d_points, d_scalars and d_out 4-byte aligned, d_seg_off 8-byte aligned, else BN254_E_MISALIGNED; a
+ * segment that is reversed or runs past d_seg_off[n] terms reads status 2 with the identity, never a read outside the buffers.  The number
+ * of terms sizes the call's scratch (108 B per term), and the _device form learns it from d_seg_off[n]: ONE 8-byte copy to the host and a
+ * wait for the stream before anything is enqueued — unlike the other _device forms it cannot be captured into a graph.  One call per
+ * context in flight, as everywhere.
+ * Cost: a term kernel, one lane per term (decode, the 128-step endomorphism ladder of bn254_batch_g1_mul, the Jacobian result to scratch —
+ * no inversion per term), then one sum per segment in the two layouts of the collect: a lane per segment of fewer than
+ * BN254_OPT_COLLECT_WAVE_MIN_SHARES terms, the 64 lanes of a wave with a six-level tree in LDS per longer one; one inversion per segment.
+ * Measured on an MI355X (tools/threshold_throughput.py --msm, profiles/threshold_throughput.jsonl; 65 536 terms, host forms, median [min,
+ * max] of 7): in 4 096 segments of 16 — the first length the wave layout takes — 3.48 ms [3.47, 3.53] against 3.23 [3.21, 3.26] for
+ * bn254_batch_g1_mul + bn254_batch_g1_sum: 0.25 ms SLOWER; in one segment 14.8 ms [14.76, 14.87] against 766 [709, 865], where g1_sum walks
+ * the segment in one lane.  The _device form: 3.30 and 14.70 ms.  Which call when: this one for long segments, or where the products are
+ * not wanted; the two old calls for many segments of about 16.  The lane/wave split was not swept for this call.  DESIGN.md section 10k. */
+int bn254_batch_g1_msm(bn254_ctx *ctx, const uint8_t *points /* m*64 */, const uint8_t *scalars /* m*32, big-endian */,
+                       const uint64_t *seg_off /* n+1 */, size_t n, int reduce_scalar, uint8_t *out /* n*64 */, uint8_t *status /* n */);
+int bn254_batch_g1_msm_device(bn254_ctx *ctx, const uint8_t *d_points, const uint8_t *d_scalars, const uint64_t *d_seg_off, size_t n,
+                              int reduce_scalar, uint8_t *d_out, uint8_t *d_status, void *stream);
 
 /* aggregate verify over shared pools (BASELINE config 3): tuple i names a message tuple_msg[i] and a
  * list of signers signer_idx[tuple_off[i] .. tuple_off[i+1]); status[i] = ECDSA::verify(msg, sum of the
@@ -790,6 +814,61 @@ int bn254_batch_pop_verify_device(bn254_ctx *ctx, const uint8_t *d_pks, const ui
 int bn254_ctx_register_keys_pop(bn254_ctx *ctx, const uint8_t *pks /* n_keys*128 */, const uint8_t *pops /* n_keys*64 */, size_t n_keys,
                                 uint32_t flags, uint8_t *key_status /* n_keys or NULL */);
 
+/* THRESHOLD SIGNATURES over the registered keys: t-of-n BLS.  The group key is Shamir-shared by a polynomial f of degree t - 1; registered
+ * key j is pk_j = f(j + 1) * G2::one() — key index j stands for the evaluation point x_j = j + 1, so index 0 is a legal signer — and validator
+ * j's share of a message is the ordinary signature under pk_j.  Any t valid shares interpolate to THE signature under f(0) * G2::one(), which
+ * bn254_batch_verify (or one pairing check on chain) accepts under the group key.  This call checks the shares and interpolates.
+ * Inputs, argument checks, alignment rules, the range rule of the _device form, the fill of share_status with 2, BN254_OPT_MAX_CHUNK slicing
+ * and bn254_ctx_expect_msgs_len are exactly those of bn254_batch_collect_keyed_bitmap[_device] above; in addition threshold == 0 is
+ * BN254_E_BAD_ARGUMENT.  A threshold above n_keys is legal: every accepted tuple then fails as described below.
+ * share_status[s], DEFINING IDENTITY 1: the collect's — byte for byte what bn254_batch_verify_keyed returns, with the same flags, for
+ * n_shares items whose message is their tuple's message repeated (the call runs the collect's front end and verify slices as they stand).
+ * Let V_i be the set of key indices with at least one status-0 share in accepted tuple i (the collect's bitmap row); n_valid[i] = |V_i| (the
+ * array may be NULL).
+ *   |V_i| >= threshold: S_i = the `threshold` LOWEST indices of V_i — a choice that depends on nothing but V_i, so the bytes do not depend on
+ *     the order of the shares, on slicing or on the layout of the sum.  used_bits row i = S_i (exactly `threshold` bits, in the bitmap call's
+ *     numbering), group_sigs[i] = sum over j in S_i of lambda_j(S_i) * sigma_j, where sigma_j is a status-0 share of key j (several are the
+ *     same point: bn254_batch_collect_keyed_bitmap) and lambda_j(S) = prod x_k / prod (x_k - x_j) over the k != j of S, mod r.  Uncompressed,
+ *     the identity as 64 zero bytes.  tuple_status[i] = 0.
+ *   |V_i| < threshold: tuple_status[i] = 9 (VerificationFailed), group_sigs[i] = 64 zero bytes, used_bits row i = V_i — who is there.
+ *   A tuple the range rule refuses reads 2, one whose hash status is non-zero reads that status (in the collect's order); both get the empty
+ *     row, 64 zero bytes and n_valid 0.
+ * DEFINING IDENTITY 2: group_sigs[i] is byte for byte bn254_batch_g1_msm of the chosen shares with the coefficients above.
+ * DEFINING IDENTITY 3 (closed loop, flags = 0): for registered keys pk_j = f(j + 1) * G2::one() of ONE polynomial of degree threshold - 1,
+ * bn254_batch_verify of (m_i, group_sigs[i], f(0) * G2::one()) returns 0 for every tuple with tuple_status 0, whatever subset signed, and
+ * group_sigs[i] is the same point for every subset.
+ * WHAT IS CHECKED: every share against its registered key.  WHAT IS NOT: that the registered keys lie on one polynomial of degree
+ * threshold - 1 — that is the dealer's or the DKG's job.  For a key set that does not, the output is still well defined (the rule for S_i)
+ * but is the signature of no key in particular.  Registration statuses apply as in every keyed call (a key registered with a failed proof
+ * of possession has no valid share).
+ * Cost: the collect's — one hash per tuple, one keyed verify per share, its select-and-sum — then a lane per tuple for rank and select (the
+ * `threshold` lowest bits of the row, counted across its words), a lane per share that claims its kept key and writes the key's
+ * coefficient (2 (t - 1) products and one inversion in Fr: about 2t + 400 products), and bn254_batch_g1_msm's term and sum kernels over
+ * ALL the shares, masked: a lane whose share is not kept walks the identity, and every wave that holds at least one kept share walks the
+ * full 128-step ladder.  Scratch beyond the collect's: 142 B per share and a second bitmap row per tuple.  The _device form only
+ * enqueues: no host synchronisation.  Under bn254_ctx_set_profiling the intervals are the collect's, with the interpolation inside ms[1] (select-and-sum).
+ * Measured on an MI355X (tools/threshold_throughput.py, profiles/threshold_throughput.jsonl; 256 keys, every share valid, threshold = two
+ * thirds of a tuple's keys; _device forms under HIP events, median [min, max] of 7): 256 tuples x 171 shares 11.42 ms [11.31, 11.52] against
+ * 8.28 [8.23, 8.36] for bn254_batch_collect_keyed_bitmap_device on the same inputs; 4 096 x 11: 11.10 against 8.32; one tuple of 4 096
+ * shares: 6.13 against 2.74.  So the interpolation costs 2.8 - 3.4 ms — a ladder per kept share is what bn254_batch_g1_mul costs, and one
+ * ladder is about 3 ms of latency however few lanes walk one; it is a third on top of the verification, not a small addition.  The route
+ * without the call (keyed verify, statuses to the host, coefficients in Python integers, g1_mul, g1_sum): 654.5, 76.4 and 11.8 ms, the
+ * same signature bytes.  Unmeasured: other thresholds, invalid shares, more than 256 keys, the host form.
+ * Which call when: this one whenever the shares are in hand and the share keys registered; bn254_batch_collect_keyed_bitmap for
+ * multi-signatures (no interpolation); bn254_batch_g1_msm for weighted sums of the caller's own points.  DESIGN.md section 10k.
+ * Out of scope: an optimistic form that interpolates first and verifies the result once, a randomised form, the multi-GPU layer,
+ * compressed shares, key dealing (Shamir sharing, DKG) in the C ABI. */
+int bn254_batch_threshold_combine_keyed(bn254_ctx *ctx, const uint8_t *msgs, const uint64_t *msg_off /* n+1 */,
+                                        const uint8_t *shares /* n_shares*64 */, const uint32_t *share_key /* n_shares */,
+                                        const uint64_t *share_off /* n+1 */, size_t n_shares, size_t n, size_t bm_words, uint32_t threshold,
+                                        uint32_t flags, uint8_t *share_status /* n_shares */, uint8_t *tuple_status /* n */,
+                                        uint8_t *group_sigs /* n*64 */, uint32_t *used_bits /* n*bm_words */, uint32_t *n_valid /* n, or NULL */);
+int bn254_batch_threshold_combine_keyed_device(bn254_ctx *ctx, const uint8_t *d_msgs, const uint64_t *d_msg_off, const uint8_t *d_shares,
+                                               const uint32_t *d_share_key, const uint64_t *d_share_off, size_t n_shares, size_t n,
+                                               size_t bm_words, uint32_t threshold, uint32_t flags, uint8_t *d_share_status,
+                                               uint8_t *d_tuple_status, uint8_t *d_group_sigs, uint32_t *d_used_bits, uint32_t *d_n_valid,
+                                               void *stream);
+
 /* compressed wire formats (src/utils.rs:84-104, :130-158): out = uncompressed point, status as
  * bn::G1::from_compressed / bn::G2::from_compressed report through src/types.rs:91-93, :233-237, checked in the order
  * those decoders work (an input with several faults reports the first):
@@ -1161,6 +1240,16 @@ int bn254_debug_bitmap_rand_sums(bn254_ctx *ctx, uint64_t dims[2], size_t group_
  *            8 final exponentiation                                                    [384 B] */
 int bn254_debug_fp_op(bn254_ctx *ctx, int op, const uint8_t *a, const uint8_t *b, size_t n, uint8_t *out, uint8_t *status);
 int bn254_debug_fp12_op(bn254_ctx *ctx, int op, const uint8_t *a, const uint8_t *b, size_t n, uint8_t *out);
+/* ... and in Fr, arithmetic mod the group order (bn254_fr.h), on 32-byte big-endian operands, reduced mod r on load as
+ * bn254_batch_g1_mul(reduce_scalar = 1) reduces a scalar; out = 32 B big-endian, in [0, r).
+ *   op: 0 mul, 1 add, 2 sub (b required), 3 neg(a), 4 inverse(a) (0 gives 0), 5 a itself through Montgomery form and back,
+ *       6 the low 32 bits of a (its last four bytes) through the uint32_t load */
+int bn254_debug_fr_op(bn254_ctx *ctx, int op, const uint8_t *a, const uint8_t *b, size_t n, uint8_t *out /* n*32 */);
+/* the Lagrange coefficients at zero of bn254_batch_threshold_combine_keyed, the evaluation points given directly (so a test can use points up
+ * to 2^32 - 1 without registering that many keys): segment i holds the points x[seg_off[i] .. seg_off[i+1]), and out[32 j] is the
+ * coefficient of point j within its segment, prod x_k / prod (x_k - x_j) mod r over the segment's other points.  The points of a segment
+ * must be distinct and non-zero (a repeated point gives 0).  seg_off[0] == 0, non-decreasing. */
+int bn254_debug_lagrange_at_zero(bn254_ctx *ctx, const uint32_t *x /* m */, const uint64_t *seg_off /* n+1 */, size_t n, uint8_t *out /* m*32 */);
 /* the final exponentiation of ECDSA::verify / bn::pairing_batch (src/ecdsa.rs:57-59) on caller-supplied LIMB vectors — n x 12 coefficients
  * (Gt order) x 9 int32 limbs, value = sum limb_k 2^(29 k) in Montgomery form (R = 2^261) — in the layout named: 0 one lane per item, exact
  * exponent, gt = canonical Gt bytes | 1 lane pairs, exact, gt | 2 lane pairs, the == one chain | 3 lane octets (straight-line chains below

@@ -7,6 +7,9 @@
 // bn254_batch_collect_keyed_bitmap_optimistic[_device] verifies each tuple's SUM once, by the bitmap verify's kernels
 // (bn254_bitmap.hip: bm_prepare, launch_bitmap_sum; launch_verify_miller_fe), and sends only the candidates of the tuples that fail — or
 // have a duplicate, or too few candidates — through a device-side queue into the exact keyed kernels (cl_optimistic).
+// The unit also holds what the whole family shares (bn254_host.h): every extern "C" function fills one record of its arguments (ClCall), and
+// the checks, the staging of a host form, the front end, the head of a slice and the optimistic route's tuple check and queue take that
+// record — for the merge of partial aggregates (bn254_merge.hip) and the threshold call (bn254_threshold.hip: cl_collect_run) as for the collect.
 // Per-share semantics: ECDSA::verify (/root/reference/src/ecdsa.rs:49-64); the sum: `Add for Signature` (src/types.rs:264-270).
 #include <hip/hip_runtime.h>
 
@@ -88,7 +91,50 @@ KERNEL_SMALL void k_cl_spread(size_t len, uint64_t base, size_t n, const uint64_
   ws_byte(ws, BY_ST_HASH, j) = S.hst[t];
 }
 
-// ---- what bn254_merge.hip shares with this unit (bn254_host.h): the scratch, steps 1 and 2 of every call, and the spread -------------------
+// ---- what bn254_merge.hip and bn254_threshold.hip share with this unit (bn254_host.h): the checks and the staging of a call, the scratch,
+// steps 1 and 2 of every call, and the head of a slice ------------------------------------------------------------------------------------------
+static int cl_checks_head(const bn254_ctx* c, const ClCall& a, bool device) {
+  if (!c || a.bm_words > 0xFFFFFFFFu || a.n > 0xFFFFFFFFu || a.n_items > 0xFFFFFFFFu) return BN254_E_BAD_ARGUMENT;
+  if (a.n && ((device && !a.msgs) || !a.msg_off || !a.off || !a.tuple_status || !a.agg_sigs || (a.bm_words && !a.signer_bits))) return BN254_E_BAD_ARGUMENT;
+  if (a.n && a.n_items && (!a.items || !a.item_status)) return BN254_E_BAD_ARGUMENT;
+  return 0;
+}
+bool cl_checks_host(bn254_ctx* c, const ClCall& a, int* rc) {
+  if ((*rc = cl_checks_head(c, a, false)) || a.n == 0) return false;
+  if (const hipError_t e = hipSetDevice(c->device)) *rc = -(int)e;
+  else if (!msgs_ok(a.msgs, a.msg_off, a.n) || a.off[0] != 0 || !offsets_ok(a.off, a.n) || a.off[a.n] != a.n_items) *rc = BN254_E_BAD_ARGUMENT;
+  return *rc == 0;
+}
+bool cl_checks_device(bn254_ctx* c, const ClCall& a, int* rc) {
+  if ((*rc = cl_checks_head(c, a, true)) || a.n == 0) return false;
+  if (misaligned(a.items) || misaligned(a.aux) || misaligned(a.agg_sigs) || misaligned(a.signer_bits) || misaligned(a.n_signers) ||
+      ((uintptr_t)a.msg_off & 7u) || ((uintptr_t)a.off & 7u))
+    *rc = BN254_E_MISALIGNED;
+  else if (const hipError_t e = hipSetDevice(c->device)) *rc = -(int)e;
+  return *rc == 0;
+}
+void cl_stage(HostStaging& st, const ClCall& a, size_t aux_words, int out_slot, ClCall* d) {
+  const size_t n = a.n, m = a.n_items, row = a.bm_words * sizeof(uint32_t), taken = a.item_taken ? m : 0;
+  *d = a;
+  d->msgs = st.in(0, a.msgs, (size_t)a.msg_off[n]);
+  d->msg_off = (const uint64_t*)st.in(1, a.msg_off, (n + 1) * sizeof(uint64_t));
+  d->items = st.in(2, a.items, m * 64);
+  const uint8_t* d_aux = st.in(3, a.aux, m * aux_words * sizeof(uint32_t));
+  d->aux = aux_words ? (const uint32_t*)d_aux : nullptr;
+  d->off = (const uint64_t*)st.in(4, a.off, (n + 1) * sizeof(uint64_t));
+  // the outputs share one slot: the aligned ones first
+  const size_t o_bits = n * 64, o_cnt = o_bits + n * row, o_ist = o_cnt + n * sizeof(uint32_t), o_tkn = o_ist + m, o_tst = o_tkn + taken;
+  uint8_t* d_out = st.out(out_slot, o_tst + n);
+  if (!st.ok()) return;
+  d->agg_sigs = d_out, d->signer_bits = (uint32_t*)(d_out + o_bits), d->n_signers = a.n_signers ? (uint32_t*)(d_out + o_cnt) : nullptr;
+  d->item_status = d_out + o_ist, d->item_taken = a.item_taken ? d_out + o_tkn : nullptr, d->tuple_status = d_out + o_tst;
+  st.copy_back(a.agg_sigs, d->agg_sigs, n * 64);
+  st.copy_back(a.signer_bits, d->signer_bits, n * row);
+  st.copy_back(a.n_signers, d_out + o_cnt, n * sizeof(uint32_t));
+  st.copy_back(a.item_status, d->item_status, m);
+  st.copy_back(a.item_taken, d->item_taken, taken);
+  st.copy_back(a.tuple_status, d->tuple_status, n);
+}
 int cl_scratch_reserve(bn254_ctx* c, size_t n, ClScratch* S) {
   Carve size(nullptr);
   cl_scratch(size, n);
@@ -97,23 +143,26 @@ int cl_scratch_reserve(bn254_ctx* c, size_t n, ClScratch* S) {
   *S = cl_scratch(carve, n);
   return 0;
 }
-// 1. hash once per tuple, in pieces of t_piece tuples; 2. the range rule over d_off against n_items, the tuples' statuses, item -> tuple
-int cl_hash_and_plan(bn254_ctx* c, hipStream_t s, const uint8_t* d_msgs, const uint64_t* d_msg_off, const uint64_t* d_off, size_t n_items, size_t n,
-                     size_t t_piece, const ClScratch& S, uint8_t* d_tuple_status) {
+// 1. hash once per tuple, in pieces of t_piece tuples; 2. the range rule over a.off against n_items, the tuples' statuses, item -> tuple
+int cl_hash_and_plan(bn254_ctx* c, hipStream_t s, const ClCall& a, size_t t_piece, const ClScratch& S) {
   int rc;
-  for (size_t lo = 0; lo < n; lo += t_piece) {
-    const size_t len = n - lo < t_piece ? n - lo : t_piece;
-    if ((rc = launch_hash_rounds(c, s, d_msgs, d_msg_off + lo, len, PL_P2X, BY_P2_INF, nullptr))) return rc;
+  for (size_t lo = 0; lo < a.n; lo += t_piece) {
+    const size_t len = a.n - lo < t_piece ? a.n - lo : t_piece;
+    if ((rc = launch_hash_rounds(c, s, a.msgs, a.msg_off + lo, len, PL_P2X, BY_P2_INF, nullptr))) return rc;
     k_cl_save<<<grid_for(len), BN_WAVE, 0, s>>>(len, lo, c->ws, S);
     HIP_TRY(hipGetLastError());
   }
-  if ((rc = bn254_aggd_scan_max(s, d_off, n, S.mx, S.tot))) return rc;
-  k_cl_plan<<<grid_for(n), BN_WAVE, 0, s>>>(n, (uint64_t)n_items, d_off, S, d_tuple_status);
+  if ((rc = bn254_aggd_scan_max(s, a.off, a.n, S.mx, S.tot))) return rc;
+  k_cl_plan<<<grid_for(a.n), BN_WAVE, 0, s>>>(a.n, (uint64_t)a.n_items, a.off, S, a.tuple_status);
   HIP_TRY(hipGetLastError());
-  return bn254_aggd_scan_max(s, S.hi, n, S.end, S.tot);
+  return bn254_aggd_scan_max(s, S.hi, a.n, S.end, S.tot);
 }
-int launch_cl_spread(bn254_ctx* c, hipStream_t s, size_t len, uint64_t base, size_t n, const uint64_t* d_off, const ClScratch& S) {
-  k_cl_spread<<<grid_for(len), BN_WAVE, 0, s>>>(len, base, n, d_off, S, c->ws);
+// Profiling: every slice records its intervals, so the last one's stay (a slice behind the first opens its own front end; the first one's
+// began with the hash)
+int cl_slice_head(bn254_ctx* c, hipStream_t s, const ClCall& a, size_t lo, size_t len, const ClScratch& S) {
+  if (lo) PROF_MARK(1);
+  if (const int rc = launch_decode_g1(c, s, a.items + 64 * lo, len, a.flags, PL_P1X, BY_P1_INF, 0)) return rc;
+  k_cl_spread<<<grid_for(len), BN_WAVE, 0, s>>>(len, (uint64_t)lo, a.n, a.off, S, c->ws);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -160,20 +209,15 @@ KERNEL_SMALL void k_cl_sum_wave(ClShares in, size_t n, size_t bm_words, uint64_t
   }
 }
 
-// one slice of the shares: decode, spread, the keyed verify of the slots; statuses at the shares' own positions.  Profiling: every slice
-// records its intervals, so the last one's stay (a slice behind the first opens its own front end; the first one's began with the hash)
-static int cl_verify_slice(bn254_ctx* c, hipStream_t s, const uint8_t* d_shares, const uint32_t* d_share_key, const uint64_t* d_share_off, size_t n,
-                           size_t lo, size_t len, uint32_t flags, const ClScratch& S, uint8_t* d_share_status) {
+// one slice of the shares: decode, spread, the keyed verify of the slots; statuses at the shares' own positions
+static int cl_verify_slice(bn254_ctx* c, hipStream_t s, const ClCall& a, size_t lo, size_t len, const ClScratch& S) {
   int rc;
-  if (lo) PROF_MARK(1);
-  if ((rc = launch_decode_g1(c, s, d_shares + 64 * lo, len, flags, PL_P1X, BY_P1_INF, 0))) return rc;
-  k_cl_spread<<<grid_for(len), BN_WAVE, 0, s>>>(len, (uint64_t)lo, n, d_share_off, S, c->ws);
-  HIP_TRY(hipGetLastError());
+  if ((rc = cl_slice_head(c, s, a, lo, len, S))) return rc;
   PROF_MARK(2);
   if (c->n_keys == 0 || !c->key_lines) {               // nothing registered: every share that decodes is out of range
-    if ((rc = launch_keyed_no_keys(c, s, len, d_share_status + lo))) return rc;
+    if ((rc = launch_keyed_no_keys(c, s, len, a.item_status + lo))) return rc;
     PROF_MARK(3);
-  } else if ((rc = launch_keyed_miller_fe(c, s, len, d_share_key + lo, d_share_status + lo))) return rc;
+  } else if ((rc = launch_keyed_miller_fe(c, s, len, a.aux + lo, a.item_status + lo))) return rc;
   PROF_MARK(4);
   return 0;
 }
@@ -208,15 +252,11 @@ static bool cl_rand_slots_fit(const bn254_ctx* c, size_t len) { return keyed_ran
 // one slice of the shares on that route: decode and spread as cl_verify_slice, then the grouped checks of the slots with the weights of the
 // shares' own indices (index_base = lo).  The spread has put H(m) and the hash status of its tuple into every slot, which is the layout
 // k_krand_prepare and the exact re-check read.  ms[2] = grouping + scalar ladders, ms[3] = group checks + exact re-checks.
-static int cl_verify_slice_rand(bn254_ctx* c, hipStream_t s, const uint8_t* d_shares, const uint32_t* d_share_key, const uint64_t* d_share_off, size_t n,
-                                size_t lo, size_t len, uint32_t dflags, const RandSeed& seed, int mode, const ClScratch& S, uint8_t* d_share_status) {
+static int cl_verify_slice_rand(bn254_ctx* c, hipStream_t s, const ClCall& a, size_t lo, size_t len, const RandSeed& seed, int mode, const ClScratch& S) {
   int rc;
-  if (lo) PROF_MARK(1);
-  if ((rc = launch_decode_g1(c, s, d_shares + 64 * lo, len, dflags, PL_P1X, BY_P1_INF, 0))) return rc;
-  k_cl_spread<<<grid_for(len), BN_WAVE, 0, s>>>(len, (uint64_t)lo, n, d_share_off, S, c->ws);
-  HIP_TRY(hipGetLastError());
+  if ((rc = cl_slice_head(c, s, a, lo, len, S))) return rc;
   PROF_MARK(2);
-  if ((rc = launch_keyed_rand_checks(c, s, len, d_share_key + lo, seed, mode, (uint64_t)lo, d_share_status + lo))) return rc;
+  if ((rc = launch_keyed_rand_checks(c, s, len, a.aux + lo, seed, mode, (uint64_t)lo, a.item_status + lo))) return rc;
   k_cl_rand_count<<<1, BN_WAVE, 0, s>>>(keyed_rand_meta(c), keyed_rand_group_st(c), c->ws.h_cnt, S.stats);
   HIP_TRY(hipGetLastError());
   PROF_MARK(4);
@@ -289,11 +329,6 @@ KERNEL_SMALL void k_clo_load_h(size_t len, size_t base, ClScratch S, Ws ws) {
   ws_byte(ws, BY_P2_INF, j) = S.hinf[base + j];
   ws_byte(ws, BY_ST_HASH, j) = S.hst[base + j];
 }
-int launch_clo_load_h(bn254_ctx* c, hipStream_t s, size_t len, size_t base, const ClScratch& S) {
-  k_clo_load_h<<<grid_for(len), BN_WAVE, 0, s>>>(len, base, S, c->ws);
-  HIP_TRY(hipGetLastError());
-  return 0;
-}
 // behind the tuple check: the rows of the tuples that go the exact way are zeroed for the re-sum, and the call's counters take what the
 // check did (one vector atomic per wave and counter)
 KERNEL_SMALL void k_clo_settle(size_t n, size_t bm_words, ClScratch S, uint32_t* bits) {
@@ -322,78 +357,79 @@ KERNEL_SMALL void k_clo_queue(size_t len, uint64_t base, size_t n, const uint64_
 KERNEL_SMALL void k_clo_count(const uint32_t* h_cnt, uint32_t* stats) {
   if (threadIdx.x == 0 && h_cnt[0]) atomicAdd(&stats[CLO_STAT_AT + 3], h_cnt[0]);
 }
-// The route behind the hash, the range rule and the fills (cl_collect_device): pre-check, provisional sum, the tuple check in pieces of
-// t_piece tuples, then the exact verify of the queued candidates in slices of s_piece shares and the re-sum.  Everything is enqueued whether
-// or not a tuple fails: the host never learns.  ms[0] = front end + provisional sum, ms[1] = aggregate keys, ms[2] = the tuples' Miller loop
-// and final exponentiation, ms[3] = exact fallback + re-sum (a call in several pieces: the last piece's ms[1] boundary).
-static int cl_optimistic(bn254_ctx* c, hipStream_t s, const ClShares& in, size_t n_shares, size_t n, size_t bm_words, uint32_t flags, size_t t_piece,
-                         size_t s_piece, const ClScratch& S, uint8_t* d_share_status, uint8_t* d_agg_sigs, uint32_t* d_signer_bits, uint32_t* d_n_signers) {
+// The two stages the optimistic merge runs too (bn254_host.h).  The tuple check: the call's own outputs through the bitmap verify's kernels,
+// decode flags 0 (an identity aggregate is legitimate); a merge over no keys has no rows
+int clo_tuple_check(bn254_ctx* c, hipStream_t s, const ClCall& a, size_t t_piece, const ClScratch& S) {
   int rc;
-  const uint64_t wave_min = (uint64_t)c->collect_wave_min;
-  const uint32_t min_tuple = (uint32_t)c->collect_opt_min_tuple_shares;
-  const unsigned wave_grid = (unsigned)(n < CL_WAVE_MAX_BLOCKS ? n : CL_WAVE_MAX_BLOCKS);
-  const KeyTable kt = {c->key_lines, c->key_st, c->key_inf, (uint32_t)c->n_keys};
   const bool tables = bm_wants_tables(c);
-  // 3. rules 1-3 of every share; 4. the provisional sum of the candidates and the tuples' flags
-  k_clo_precheck<<<grid_for(n_shares), BN_WAVE, 0, s>>>(n_shares, n, in.shares, in.key, in.off, flags, S, c->key_st, (uint32_t)c->n_keys, d_share_status);
-  HIP_TRY(hipGetLastError());
-  k_clo_sum_lane<<<grid_for(n), BN_WAVE, 0, s>>>(in, n, bm_words, wave_min, min_tuple, nullptr, S.flag, d_signer_bits, d_agg_sigs, d_n_signers);
-  HIP_TRY(hipGetLastError());
-  k_clo_sum_wave<<<wave_grid, BN_WAVE, 0, s>>>(in, n, bm_words, wave_min, min_tuple, nullptr, S.flag, d_signer_bits, d_agg_sigs, d_n_signers);
-  HIP_TRY(hipGetLastError());
-  PROF_MARK(1);
-  // 5. the tuple check: the call's own outputs through the bitmap verify's kernels, decode flags 0 (an identity aggregate is legitimate)
-  for (size_t lo = 0; lo < n; lo += t_piece) {
-    const size_t len = n - lo < t_piece ? n - lo : t_piece;
-    if ((rc = launch_decode_g1(c, s, d_agg_sigs + 64 * lo, len, 0, PL_P1X, BY_P1_INF, 0))) return rc;
+  for (size_t lo = 0; lo < a.n; lo += t_piece) {
+    const size_t len = a.n - lo < t_piece ? a.n - lo : t_piece;
+    if ((rc = launch_decode_g1(c, s, a.agg_sigs + 64 * lo, len, 0, PL_P1X, BY_P1_INF, 0))) return rc;
     k_clo_load_h<<<grid_for(len), BN_WAVE, 0, s>>>(len, lo, S, c->ws);
     HIP_TRY(hipGetLastError());
-    if ((rc = launch_bitmap_sum(c, s, d_signer_bits + lo * bm_words, bm_words, len, tables))) return rc;
+    if ((rc = launch_bitmap_sum(c, s, a.signer_bits ? a.signer_bits + lo * a.bm_words : nullptr, a.bm_words, len, tables))) return rc;
     PROF_MARK(2);
     if ((rc = launch_verify_miller_fe(c, s, len, BN_PAIRS_VERIFY, 1, S.verdict + lo, false))) return rc;
   }
   PROF_MARK(3);
-  k_clo_settle<<<grid_for(n), BN_WAVE, 0, s>>>(n, bm_words, S, d_signer_bits);
+  k_clo_settle<<<grid_for(a.n), BN_WAVE, 0, s>>>(a.n, a.bm_words, S, a.signer_bits);
   HIP_TRY(hipGetLastError());
+  return 0;
+}
+// The queue holds at most len entries (one per slot), and the workspace was reserved for a slice's length
+int clo_queue_slice(bn254_ctx* c, hipStream_t s, const ClCall& a, size_t lo, size_t len, const ClScratch& S) {
+  if (const int rc = launch_decode_g1(c, s, a.items + 64 * lo, len, a.flags, PL_P1X, BY_P1_INF, 0)) return rc;
+  k_cl_spread<<<grid_for(len), BN_WAVE, 0, s>>>(len, (uint64_t)lo, a.n, a.off, S, c->ws);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemsetAsync(c->ws.h_cnt, 0, sizeof(uint32_t), s));
+  k_clo_queue<<<grid_for(len), BN_WAVE, 0, s>>>(len, (uint64_t)lo, a.n, a.off, S, a.item_status, c->ws);
+  HIP_TRY(hipGetLastError());
+  k_clo_count<<<1, BN_WAVE, 0, s>>>(c->ws.h_cnt, S.stats);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+// The route behind the hash, the range rule and the fills (cl_collect_run): pre-check, provisional sum, the tuple check in pieces of
+// t_piece tuples, then the exact verify of the queued candidates in slices of s_piece shares and the re-sum.  Everything is enqueued whether
+// or not a tuple fails: the host never learns.  ms[0] = front end + provisional sum, ms[1] = aggregate keys, ms[2] = the tuples' Miller loop
+// and final exponentiation, ms[3] = exact fallback + re-sum (a call in several pieces: the last piece's ms[1] boundary).
+static int cl_optimistic(bn254_ctx* c, hipStream_t s, const ClCall& a, size_t t_piece, size_t s_piece, const ClScratch& S) {
+  int rc;
+  const size_t n = a.n, n_shares = a.n_items;
+  const ClShares in = {a.items, a.aux, a.off, a.item_status, a.tuple_status};
+  const uint64_t wave_min = (uint64_t)c->collect_wave_min;
+  const uint32_t min_tuple = (uint32_t)c->collect_opt_min_tuple_shares;
+  const unsigned wave_grid = (unsigned)(n < CL_WAVE_MAX_BLOCKS ? n : CL_WAVE_MAX_BLOCKS);
+  const KeyTable kt = {c->key_lines, c->key_st, c->key_inf, (uint32_t)c->n_keys};
+  // 3. rules 1-3 of every share; 4. the provisional sum of the candidates and the tuples' flags
+  k_clo_precheck<<<grid_for(n_shares), BN_WAVE, 0, s>>>(n_shares, n, in.shares, in.key, in.off, a.flags, S, c->key_st, (uint32_t)c->n_keys, a.item_status);
+  HIP_TRY(hipGetLastError());
+  k_clo_sum_lane<<<grid_for(n), BN_WAVE, 0, s>>>(in, n, a.bm_words, wave_min, min_tuple, nullptr, S.flag, a.signer_bits, a.agg_sigs, a.n_signers);
+  HIP_TRY(hipGetLastError());
+  k_clo_sum_wave<<<wave_grid, BN_WAVE, 0, s>>>(in, n, a.bm_words, wave_min, min_tuple, nullptr, S.flag, a.signer_bits, a.agg_sigs, a.n_signers);
+  HIP_TRY(hipGetLastError());
+  PROF_MARK(1);
+  // 5. the tuple check of the call's own outputs
+  if ((rc = clo_tuple_check(c, s, a, t_piece, S))) return rc;
   // 6. the candidates of the tuples that go the exact way, verified by the keyed kernels over a queue; then those tuples summed again
   for (size_t lo = 0; lo < n_shares; lo += s_piece) {
     const size_t len = n_shares - lo < s_piece ? n_shares - lo : s_piece;
-    if ((rc = launch_decode_g1(c, s, in.shares + 64 * lo, len, flags, PL_P1X, BY_P1_INF, 0))) return rc;
-    k_cl_spread<<<grid_for(len), BN_WAVE, 0, s>>>(len, (uint64_t)lo, n, in.off, S, c->ws);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemsetAsync(c->ws.h_cnt, 0, sizeof(uint32_t), s));
-    k_clo_queue<<<grid_for(len), BN_WAVE, 0, s>>>(len, (uint64_t)lo, n, in.off, S, d_share_status, c->ws);
-    HIP_TRY(hipGetLastError());
-    k_clo_count<<<1, BN_WAVE, 0, s>>>(c->ws.h_cnt, S.stats);
-    HIP_TRY(hipGetLastError());
+    if ((rc = clo_queue_slice(c, s, a, lo, len, S))) return rc;
     if ((rc = bn254_pair_miller_verify_keyed(len, c->ws, in.key + lo, kt, s, 0, c->ws.h_list, c->ws.h_cnt))) return rc;
-    if ((rc = bn254_pair_final_exp(len, c->ws, 1, d_share_status + lo, c->ws.h_list, c->ws.h_cnt, s))) return rc;
+    if ((rc = bn254_pair_final_exp(len, c->ws, 1, a.item_status + lo, c->ws.h_list, c->ws.h_cnt, s))) return rc;
   }
-  k_clo_sum_lane<<<grid_for(n), BN_WAVE, 0, s>>>(in, n, bm_words, wave_min, min_tuple, S.verdict, S.flag, d_signer_bits, d_agg_sigs, d_n_signers);
+  k_clo_sum_lane<<<grid_for(n), BN_WAVE, 0, s>>>(in, n, a.bm_words, wave_min, min_tuple, S.verdict, S.flag, a.signer_bits, a.agg_sigs, a.n_signers);
   HIP_TRY(hipGetLastError());
-  k_clo_sum_wave<<<wave_grid, BN_WAVE, 0, s>>>(in, n, bm_words, wave_min, min_tuple, S.verdict, S.flag, d_signer_bits, d_agg_sigs, d_n_signers);
+  k_clo_sum_wave<<<wave_grid, BN_WAVE, 0, s>>>(in, n, a.bm_words, wave_min, min_tuple, S.verdict, S.flag, a.signer_bits, a.agg_sigs, a.n_signers);
   PROF_MARK(4);
   prof_done(c, EV_DECODE_FIRST);
   HIP_TRY(hipGetLastError());
   return 0;
 }
 
-// all three calls: seed32 == nullptr and !optimistic is the exact one
-static int cl_collect_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t* d_msg_off, const uint8_t* d_shares,
-                             const uint32_t* d_share_key, const uint64_t* d_share_off, size_t n_shares, size_t n, size_t bm_words,
-                             uint32_t flags, const uint8_t* seed32, bool optimistic, uint8_t* d_share_status, uint8_t* d_tuple_status,
-                             uint8_t* d_agg_sigs, uint32_t* d_signer_bits, uint32_t* d_n_signers, void* stream) {
-  MsgsLenScope msgs_len_scope(c);
-  if (c) c->clr_last_ran = c->clo_last_ran = c->mgo_last_ran = 0;
-  if (!c || bm_words > 0xFFFFFFFFu || n > 0xFFFFFFFFu || n_shares > 0xFFFFFFFFu) return BN254_E_BAD_ARGUMENT;
-  if (bm_words < (c->n_keys + 31) / 32) return BN254_E_BAD_ARGUMENT;       // a bitmap that cannot hold a registered key cannot describe the result
-  if (n && (!d_msgs || !d_msg_off || !d_share_off || !d_tuple_status || !d_agg_sigs || (bm_words && !d_signer_bits))) return BN254_E_BAD_ARGUMENT;
-  if (n && n_shares && (!d_shares || !d_share_key || !d_share_status)) return BN254_E_BAD_ARGUMENT;
-  if (n == 0) return 0;
-  if (misaligned(d_shares) || misaligned(d_share_key) || misaligned(d_agg_sigs) || misaligned(d_signer_bits) || misaligned(d_n_signers) ||
-      ((uintptr_t)d_msg_off & 7u) || ((uintptr_t)d_share_off & 7u))
-    return BN254_E_MISALIGNED;
-  HIP_TRY(hipSetDevice(c->device));
+// all three calls behind their checks, and the threshold call's first step: seed32 == nullptr and !optimistic is the exact one
+int cl_collect_run(bn254_ctx* c, const ClCall& call, const uint8_t* seed32, bool optimistic, hipStream_t s, ClScratch* scratch) {
+  ClCall a = call;
+  const size_t n = a.n, n_shares = a.n_items;
   // every buffer before the first kernel: growing one waits for the context's streams, which must not happen between the steps.  The
   // tuples are hashed, and the shares verified, in pieces of the slicing rule's size; the scratch holds the whole call.
   // The randomised route when the host can tell that it pays: keys to group by, enough shares, enough of them per key (groups are per key: a
@@ -407,8 +443,8 @@ static int cl_collect_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t
   // the optimistic route: keys to sum, and enough shares for one more verify pass to pay.  Else the exact route, same bytes.
   const bool opt = optimistic && c->n_keys && c->key_lines && n_shares && n_shares >= (size_t)c->collect_opt_min_shares;
   // the randomised call's own flags choose the weights; the remaining ones apply to the shares' decode on either route
-  const int mode = rand_mode_of(flags);
-  if (seed32) flags &= BN254_FLAG_G2_SUBGROUP_CHECK | BN254_FLAG_REJECT_IDENTITY;
+  const int mode = rand_mode_of(a.flags);
+  if (seed32) a.flags &= BN254_FLAG_G2_SUBGROUP_CHECK | BN254_FLAG_REJECT_IDENTITY;
   const size_t t_chunk = ws_chunk_for(c, n), s_chunk = n_shares && !rand ? ws_chunk_for(c, n_shares) : 0;
   const size_t t_piece = t_chunk ? t_chunk : n, s_piece = rand ? r_piece : s_chunk ? s_chunk : n_shares;
   const size_t s_entries = rand ? keyed_rand_need(c, s_piece).ws_entries : s_piece;
@@ -419,41 +455,36 @@ static int cl_collect_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t
     if ((rc = stage_reserve(c, 5, need.words * sizeof(uint32_t)))) return rc;
     if ((rc = stage_reserve(c, 7, need.groups_max))) return rc;
   }
-  ClScratch S;
+  ClScratch& S = *scratch;
   if ((rc = cl_scratch_reserve(c, n, &S))) return rc;
   c->clr_stats = S.stats;
   c->clo_stats = S.stats + CLO_STAT_AT;
-  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-  CallDone call_done(c, s);
   if (opt && (rc = bm_prepare(c, s, bm_wants_tables(c)))) return rc;   // the first call after a registration builds here, ahead of the timed intervals
   RandSeed seed = {};
   if (rand) seed = rand_seed_from(seed32);
   if (rand || opt) HIP_TRY(hipMemsetAsync(S.stats, 0, CL_STAT_WORDS * sizeof(uint32_t), s));
   PROF_MARK(opt ? 0 : 1);
   // 1. hash once per tuple; 2. the range rule, the tuples' statuses, share -> tuple
-  if ((rc = cl_hash_and_plan(c, s, d_msgs, d_msg_off, d_share_off, n_shares, n, t_piece, S, d_tuple_status))) return rc;
-  if (bm_words) HIP_TRY(hipMemsetAsync(d_signer_bits, 0, n * bm_words * sizeof(uint32_t), s));
-  if (n_shares) HIP_TRY(hipMemsetAsync(d_share_status, ST_INDEX_OOB, n_shares, s));
+  if ((rc = cl_hash_and_plan(c, s, a, t_piece, S))) return rc;
+  if (a.bm_words) HIP_TRY(hipMemsetAsync(a.signer_bits, 0, n * a.bm_words * sizeof(uint32_t), s));
+  if (n_shares) HIP_TRY(hipMemsetAsync(a.item_status, ST_INDEX_OOB, n_shares, s));
   if (opt) {
-    const ClShares in = {d_shares, d_share_key, d_share_off, d_share_status, d_tuple_status};
-    if ((rc = cl_optimistic(c, s, in, n_shares, n, bm_words, flags, t_piece, s_piece, S, d_share_status, d_agg_sigs, d_signer_bits, d_n_signers))) return rc;
+    if ((rc = cl_optimistic(c, s, a, t_piece, s_piece, S))) return rc;
     c->clo_last_ran = 1;
     return 0;
   }
   // 3. the keyed verify of the share slots
   for (size_t lo = 0; lo < n_shares; lo += s_piece) {
     const size_t len = n_shares - lo < s_piece ? n_shares - lo : s_piece;
-    if ((rc = rand ? cl_verify_slice_rand(c, s, d_shares, d_share_key, d_share_off, n, lo, len, flags, seed, mode, S, d_share_status)
-                   : cl_verify_slice(c, s, d_shares, d_share_key, d_share_off, n, lo, len, flags, S, d_share_status)))
-      return rc;
+    if ((rc = rand ? cl_verify_slice_rand(c, s, a, lo, len, seed, mode, S) : cl_verify_slice(c, s, a, lo, len, S))) return rc;
   }
   if (!n_shares) { PROF_MARK(2); PROF_MARK(3); PROF_MARK(4); }
   // 4. select-and-sum, once, behind the last slice
-  const ClShares in = {d_shares, d_share_key, d_share_off, d_share_status, d_tuple_status};
+  const ClShares in = {a.items, a.aux, a.off, a.item_status, a.tuple_status};
   const uint64_t wave_min = (uint64_t)c->collect_wave_min;
-  k_cl_sum_lane<<<grid_for(n), BN_WAVE, 0, s>>>(in, n, bm_words, wave_min, d_signer_bits, d_agg_sigs, d_n_signers);
+  k_cl_sum_lane<<<grid_for(n), BN_WAVE, 0, s>>>(in, n, a.bm_words, wave_min, a.signer_bits, a.agg_sigs, a.n_signers);
   HIP_TRY(hipGetLastError());
-  k_cl_sum_wave<<<(unsigned)(n < CL_WAVE_MAX_BLOCKS ? n : CL_WAVE_MAX_BLOCKS), BN_WAVE, 0, s>>>(in, n, bm_words, wave_min, d_signer_bits, d_agg_sigs, d_n_signers);
+  k_cl_sum_wave<<<(unsigned)(n < CL_WAVE_MAX_BLOCKS ? n : CL_WAVE_MAX_BLOCKS), BN_WAVE, 0, s>>>(in, n, a.bm_words, wave_min, a.signer_bits, a.agg_sigs, a.n_signers);
   PROF_MARK(0);
   prof_done(c, EV_COLLECT);
   HIP_TRY(hipGetLastError());
@@ -461,39 +492,27 @@ static int cl_collect_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t
   return 0;
 }
 
-// the host-pointer form of both.  The randomised call's grouping scratch lives in stage slots 5 and 7, so its outputs take slot 6.
-static int cl_collect_host(bn254_ctx* c, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* shares, const uint32_t* share_key,
-                           const uint64_t* share_off, size_t n_shares, size_t n, size_t bm_words, uint32_t flags, const uint8_t* seed32,
-                           bool optimistic, uint8_t* share_status, uint8_t* tuple_status, uint8_t* agg_sigs, uint32_t* signer_bits,
-                           uint32_t* n_signers) {
+// the checked entry of the three *_device calls
+static int cl_collect_device(bn254_ctx* c, const ClCall& a, const uint8_t* seed32, bool optimistic, void* stream) {
   MsgsLenScope msgs_len_scope(c);
   if (c) c->clr_last_ran = c->clo_last_ran = c->mgo_last_ran = 0;
-  if (!c || bm_words > 0xFFFFFFFFu || n > 0xFFFFFFFFu || n_shares > 0xFFFFFFFFu) return BN254_E_BAD_ARGUMENT;
-  if (bm_words < (c->n_keys + 31) / 32) return BN254_E_BAD_ARGUMENT;
-  if (n && (!msg_off || !share_off || !tuple_status || !agg_sigs || (bm_words && !signer_bits))) return BN254_E_BAD_ARGUMENT;
-  if (n && n_shares && (!shares || !share_key || !share_status)) return BN254_E_BAD_ARGUMENT;
-  if (n == 0) return 0;
-  HIP_TRY(hipSetDevice(c->device));
-  if (!msgs_ok(msgs, msg_off, n)) return BN254_E_BAD_ARGUMENT;
-  if (share_off[0] != 0 || !offsets_ok(share_off, n) || share_off[n] != n_shares) return BN254_E_BAD_ARGUMENT;
+  int rc = BN254_E_BAD_ARGUMENT;
+  if (!cl_keys_ok(c, a) || !cl_checks_device(c, a, &rc)) return rc;
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  CallDone call_done(c, s);
+  ClScratch S;
+  return cl_collect_run(c, a, seed32, optimistic, s, &S);
+}
+// the host-pointer form of the three.  The randomised call's grouping scratch lives in stage slots 5 and 7, so its outputs take slot 6.
+static int cl_collect_host(bn254_ctx* c, const ClCall& a, const uint8_t* seed32, bool optimistic) {
+  MsgsLenScope msgs_len_scope(c);
+  if (c) c->clr_last_ran = c->clo_last_ran = c->mgo_last_ran = 0;
+  int rc = BN254_E_BAD_ARGUMENT;
+  if (!cl_keys_ok(c, a) || !cl_checks_host(c, a, &rc)) return rc;
   HostStaging st(c);
-  const uint8_t *d_msgs = st.in(0, msgs, (size_t)msg_off[n]), *d_msg_off = st.in(1, msg_off, (n + 1) * sizeof(uint64_t));
-  const uint8_t *d_shares = st.in(2, shares, n_shares * 64), *d_key = st.in(3, share_key, n_shares * sizeof(uint32_t));
-  const uint8_t* d_share_off = st.in(4, share_off, (n + 1) * sizeof(uint64_t));
-  // the five outputs share one slot: the aligned ones first
-  const size_t o_bits = n * 64, o_cnt = o_bits + n * bm_words * sizeof(uint32_t), o_sst = o_cnt + n * sizeof(uint32_t), o_tst = o_sst + n_shares;
-  uint8_t* d_out = st.out(seed32 ? 6 : 5, o_tst + n);
-  if (st.ok()) {
-    st.copy_back(agg_sigs, d_out, n * 64);
-    st.copy_back(signer_bits, d_out + o_bits, n * bm_words * sizeof(uint32_t));
-    st.copy_back(n_signers, d_out + o_cnt, n * sizeof(uint32_t));
-    st.copy_back(share_status, d_out + o_sst, n_shares);
-    st.copy_back(tuple_status, d_out + o_tst, n);
-  }
-  if (st.ok())
-    st.rc = cl_collect_device(c, d_msgs, (const uint64_t*)d_msg_off, d_shares, (const uint32_t*)d_key, (const uint64_t*)d_share_off, n_shares, n, bm_words,
-                              flags, seed32, optimistic, d_out + o_sst, d_out + o_tst, d_out, (uint32_t*)(d_out + o_bits),
-                              n_signers ? (uint32_t*)(d_out + o_cnt) : nullptr, nullptr);
+  ClCall d;
+  cl_stage(st, a, 1, seed32 ? 6 : 5, &d);
+  if (st.ok()) st.rc = cl_collect_device(c, d, seed32, optimistic, nullptr);
   return st.finish();
 }
 
@@ -503,14 +522,18 @@ int bn254_batch_collect_keyed_bitmap_device(bn254_ctx* c, const uint8_t* d_msgs,
                                             const uint32_t* d_share_key, const uint64_t* d_share_off, size_t n_shares, size_t n, size_t bm_words,
                                             uint32_t flags, uint8_t* d_share_status, uint8_t* d_tuple_status, uint8_t* d_agg_sigs,
                                             uint32_t* d_signer_bits, uint32_t* d_n_signers, void* stream) {
-  return cl_collect_device(c, d_msgs, d_msg_off, d_shares, d_share_key, d_share_off, n_shares, n, bm_words, flags, nullptr, false, d_share_status,
-                           d_tuple_status, d_agg_sigs, d_signer_bits, d_n_signers, stream);
+  const ClCall a = {.msgs = d_msgs, .msg_off = d_msg_off, .items = d_shares, .aux = d_share_key, .off = d_share_off, .n_items = n_shares, .n = n,
+                    .bm_words = bm_words, .flags = flags, .item_status = d_share_status, .tuple_status = d_tuple_status, .agg_sigs = d_agg_sigs,
+                    .signer_bits = d_signer_bits, .n_signers = d_n_signers};
+  return cl_collect_device(c, a, nullptr, false, stream);
 }
 int bn254_batch_collect_keyed_bitmap(bn254_ctx* c, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* shares, const uint32_t* share_key,
                                      const uint64_t* share_off, size_t n_shares, size_t n, size_t bm_words, uint32_t flags, uint8_t* share_status,
                                      uint8_t* tuple_status, uint8_t* agg_sigs, uint32_t* signer_bits, uint32_t* n_signers) {
-  return cl_collect_host(c, msgs, msg_off, shares, share_key, share_off, n_shares, n, bm_words, flags, nullptr, false, share_status, tuple_status,
-                         agg_sigs, signer_bits, n_signers);
+  const ClCall a = {.msgs = msgs, .msg_off = msg_off, .items = shares, .aux = share_key, .off = share_off, .n_items = n_shares, .n = n,
+                    .bm_words = bm_words, .flags = flags, .item_status = share_status, .tuple_status = tuple_status, .agg_sigs = agg_sigs,
+                    .signer_bits = signer_bits, .n_signers = n_signers};
+  return cl_collect_host(c, a, nullptr, false);
 }
 int bn254_batch_collect_keyed_bitmap_randomized_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t* d_msg_off, const uint8_t* d_shares,
                                                        const uint32_t* d_share_key, const uint64_t* d_share_off, size_t n_shares, size_t n,
@@ -518,30 +541,38 @@ int bn254_batch_collect_keyed_bitmap_randomized_device(bn254_ctx* c, const uint8
                                                        uint8_t* d_tuple_status, uint8_t* d_agg_sigs, uint32_t* d_signer_bits, uint32_t* d_n_signers,
                                                        void* stream) {
   if (!seed32) return BN254_E_BAD_ARGUMENT;
-  return cl_collect_device(c, d_msgs, d_msg_off, d_shares, d_share_key, d_share_off, n_shares, n, bm_words, flags, seed32, false, d_share_status,
-                           d_tuple_status, d_agg_sigs, d_signer_bits, d_n_signers, stream);
+  const ClCall a = {.msgs = d_msgs, .msg_off = d_msg_off, .items = d_shares, .aux = d_share_key, .off = d_share_off, .n_items = n_shares, .n = n,
+                    .bm_words = bm_words, .flags = flags, .item_status = d_share_status, .tuple_status = d_tuple_status, .agg_sigs = d_agg_sigs,
+                    .signer_bits = d_signer_bits, .n_signers = d_n_signers};
+  return cl_collect_device(c, a, seed32, false, stream);
 }
 int bn254_batch_collect_keyed_bitmap_randomized(bn254_ctx* c, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* shares,
                                                 const uint32_t* share_key, const uint64_t* share_off, size_t n_shares, size_t n, size_t bm_words,
                                                 uint32_t flags, const uint8_t* seed32, uint8_t* share_status, uint8_t* tuple_status, uint8_t* agg_sigs,
                                                 uint32_t* signer_bits, uint32_t* n_signers) {
   if (!seed32) return BN254_E_BAD_ARGUMENT;
-  return cl_collect_host(c, msgs, msg_off, shares, share_key, share_off, n_shares, n, bm_words, flags, seed32, false, share_status, tuple_status,
-                         agg_sigs, signer_bits, n_signers);
+  const ClCall a = {.msgs = msgs, .msg_off = msg_off, .items = shares, .aux = share_key, .off = share_off, .n_items = n_shares, .n = n,
+                    .bm_words = bm_words, .flags = flags, .item_status = share_status, .tuple_status = tuple_status, .agg_sigs = agg_sigs,
+                    .signer_bits = signer_bits, .n_signers = n_signers};
+  return cl_collect_host(c, a, seed32, false);
 }
 int bn254_batch_collect_keyed_bitmap_optimistic_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t* d_msg_off, const uint8_t* d_shares,
                                                        const uint32_t* d_share_key, const uint64_t* d_share_off, size_t n_shares, size_t n,
                                                        size_t bm_words, uint32_t flags, uint8_t* d_share_status, uint8_t* d_tuple_status,
                                                        uint8_t* d_agg_sigs, uint32_t* d_signer_bits, uint32_t* d_n_signers, void* stream) {
-  return cl_collect_device(c, d_msgs, d_msg_off, d_shares, d_share_key, d_share_off, n_shares, n, bm_words, flags, nullptr, true, d_share_status,
-                           d_tuple_status, d_agg_sigs, d_signer_bits, d_n_signers, stream);
+  const ClCall a = {.msgs = d_msgs, .msg_off = d_msg_off, .items = d_shares, .aux = d_share_key, .off = d_share_off, .n_items = n_shares, .n = n,
+                    .bm_words = bm_words, .flags = flags, .item_status = d_share_status, .tuple_status = d_tuple_status, .agg_sigs = d_agg_sigs,
+                    .signer_bits = d_signer_bits, .n_signers = d_n_signers};
+  return cl_collect_device(c, a, nullptr, true, stream);
 }
 int bn254_batch_collect_keyed_bitmap_optimistic(bn254_ctx* c, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* shares,
                                                 const uint32_t* share_key, const uint64_t* share_off, size_t n_shares, size_t n, size_t bm_words,
                                                 uint32_t flags, uint8_t* share_status, uint8_t* tuple_status, uint8_t* agg_sigs,
                                                 uint32_t* signer_bits, uint32_t* n_signers) {
-  return cl_collect_host(c, msgs, msg_off, shares, share_key, share_off, n_shares, n, bm_words, flags, nullptr, true, share_status, tuple_status,
-                         agg_sigs, signer_bits, n_signers);
+  const ClCall a = {.msgs = msgs, .msg_off = msg_off, .items = shares, .aux = share_key, .off = share_off, .n_items = n_shares, .n = n,
+                    .bm_words = bm_words, .flags = flags, .item_status = share_status, .tuple_status = tuple_status, .agg_sigs = agg_sigs,
+                    .signer_bits = signer_bits, .n_signers = n_signers};
+  return cl_collect_host(c, a, nullptr, true);
 }
 
 }  // extern "C"

@@ -363,15 +363,48 @@ struct ClScratch { uint32_t* stats; uint64_t *mx, *hi, *end, *tot; int32_t* hpt;
 #define CLO_STAT_AT 4
 // ... carved for n tuples from the context's collect_buf (grown on demand: before the call's first kernel)
 BN_HIDDEN int cl_scratch_reserve(bn254_ctx* c, size_t n, ClScratch* S);
-// ... the hash of the n messages, once per tuple in pieces of t_piece, and the range rule over the n + 1 offsets d_off into n_items items:
-// d_tuple_status, and S.end for the item -> tuple search
-BN_HIDDEN int cl_hash_and_plan(bn254_ctx* c, hipStream_t s, const uint8_t* d_msgs, const uint64_t* d_msg_off, const uint64_t* d_off, size_t n_items, size_t n,
-                               size_t t_piece, const ClScratch& S, uint8_t* d_tuple_status);
-// ... and H(m) and the hash status of its tuple into workspace entries 0 .. len for the items base .. base + len (an item of no accepted tuple:
-// the generator, decode status 2)
-BN_HIDDEN int launch_cl_spread(bn254_ctx* c, hipStream_t s, size_t len, uint64_t base, size_t n, const uint64_t* d_off, const ClScratch& S);
-// ... and, for a check per TUPLE, H(m) and the hash status of the tuples base .. base + len into workspace entries 0 .. len (k_clo_load_h)
-BN_HIDDEN int launch_clo_load_h(bn254_ctx* c, hipStream_t s, size_t len, size_t base, const ClScratch& S);
+// The arguments of one call of the family, built once by its extern "C" function: n tuples of a message and a range of ITEMS (64 bytes each
+// — the collect's and the threshold call's shares, the merge's partials), item j with aux[j] (the collect: its key index; the merge: its
+// bitmap row, bm_words words).  A host form holds the caller's pointers, its device form the staged ones (cl_stage).
+struct ClCall {
+  const uint8_t* msgs;
+  const uint64_t* msg_off;                             // n + 1
+  const uint8_t* items;
+  const uint32_t* aux;
+  const uint64_t* off;                                 // n + 1, into the items
+  size_t n_items, n, bm_words;
+  uint32_t flags;
+  uint8_t *item_status, *item_taken;                   // per item; taken: the merge only, else null
+  uint8_t *tuple_status, *agg_sigs;                    // per tuple: 1 and 64 bytes
+  uint32_t *signer_bits, *n_signers;                   // per tuple: bm_words words, and the count (or null)
+};
+// the collect's and the threshold call's own check (ahead of the common ones: n == 0 does not excuse it): a bitmap that cannot hold a
+// registered key cannot describe the result; and the items' keys
+static inline bool cl_keys_ok(const bn254_ctx* c, const ClCall& a) { return c && a.bm_words >= (c->n_keys + 31) / 32 && !(a.n && a.n_items && !a.aux); }
+// What every form checks: the context, the 32-bit bounds, the null pointers; n == 0 returns 0; then a host form selects the device and reads
+// the offsets it was given (msgs_ok, and a.off from 0 to n_items without a step back), a device form looks at the alignment and selects
+// the device.  false = the call returns *rc now.
+BN_HIDDEN bool cl_checks_host(bn254_ctx* c, const ClCall& a, int* rc);
+BN_HIDDEN bool cl_checks_device(bn254_ctx* c, const ClCall& a, int* rc);
+// The staging of a host form: the inputs into slots 0 .. 4 (aux_words: uint32 per item of a.aux), every output into slot out_slot — the
+// aligned ones first — with its copy home registered; *d = the same call on the staged buffers.
+BN_HIDDEN void cl_stage(HostStaging& st, const ClCall& a, size_t aux_words, int out_slot, ClCall* d);
+// ... the hash of the n messages, once per tuple in pieces of t_piece, and the range rule over the n + 1 offsets a.off into n_items items:
+// a.tuple_status, and S.end for the item -> tuple search
+BN_HIDDEN int cl_hash_and_plan(bn254_ctx* c, hipStream_t s, const ClCall& a, size_t t_piece, const ClScratch& S);
+// ... and the head of a slice of items lo .. lo + len: their decode into workspace entries 0 .. len and, beside each, H(m) and the hash
+// status of its tuple (an item of no accepted tuple: the generator, decode status 2).  A slice behind the first opens its own front end.
+BN_HIDDEN int cl_slice_head(bn254_ctx* c, hipStream_t s, const ClCall& a, size_t lo, size_t len, const ClScratch& S);
+// The exact collect behind the checks of its entry point (seed32: the randomised one; optimistic), for the threshold call as for the
+// collect's own: every buffer reserved, then the whole call enqueued on s.  *S = the scratch it carved, for what the caller enqueues behind.
+BN_HIDDEN int cl_collect_run(bn254_ctx* c, const ClCall& call, const uint8_t* seed32, bool optimistic, hipStream_t s, ClScratch* S);
+// The two stages the optimistic collect and the optimistic merge share.  The tuple check: in pieces of t_piece tuples
+// the call's own aggregates decoded (flags 0), H(m) beside them, the aggregate keys of the rows (profiling event 2), Miller loop and final
+// exponentiation into S.verdict; then event 3, the rows of the tuples that go the exact way zeroed and the check counted (k_clo_settle).
+BN_HIDDEN int clo_tuple_check(bn254_ctx* c, hipStream_t s, const ClCall& a, size_t t_piece, const ClScratch& S);
+// ... and the head of a fallback slice: decode and spread of the items lo .. lo + len (the call's flags), and their candidates of the tuples
+// that go the exact way queued in the workspace's h_list / h_cnt and counted
+BN_HIDDEN int clo_queue_slice(bn254_ctx* c, hipStream_t s, const ClCall& a, size_t lo, size_t len, const ClScratch& S);
 // the aggregate keys of a device-side QUEUE of tuples on lane pairs (bn254_bitmap_rand.hip: k_bmr_sum_pair_q): lane pair e < *count takes row
 // map[e] of d_bits into the Q planes of entry map[e]; rule 2 is the caller's.  n = the most the queue can hold
 BN_HIDDEN int launch_bitmap_sum_queued(bn254_ctx* c, hipStream_t s, const uint32_t* d_bits, size_t bm_words, size_t n, bool tables, const uint32_t* map,

@@ -2,10 +2,11 @@
 // bn254_batch_merge_keyed_bitmap[_device]) — the inner node of an aggregation tree.  The front end is the collect's
 // (bn254_collect.hip: hash once per tuple, range rule, spread of H(m) over the tuple's partials), the verify of a slice of partials is the
 // bitmap verify's (bn254_bitmap.hip: bm_prepare, launch_bitmap_sum; launch_verify_miller_fe), and the first-fit select-and-sum in two
-// layouts is this unit's; its walk and arithmetic are bn254_merge.h, shared with the CPU suite's host compilation.
+// layouts is this unit's; its walk and arithmetic are bn254_merge.h, shared with the CPU suite's host compilation.  The arguments travel as
+// the collect's record (bn254_host.h: ClCall — items = the partials, aux = their rows), through the collect's checks and staging.
 // bn254_batch_merge_keyed_bitmap_optimistic[_device] verifies each tuple's provisional SUM once, by the same kernels, and
 // sends only the candidates of the tuples that fail — or hold an overlap — through a device-side queue into the bitmap verify's lane-pair
-// kernels (mg_optimistic).
+// kernels (mg_optimistic; the tuple check, its settle and the queue are the optimistic collect's: clo_tuple_check, clo_queue_slice).
 // Per-partial semantics: ECDSA::verify (/root/reference/src/ecdsa.rs:49-64) against the sum of the selected keys (`Add for PublicKey`,
 // src/types.rs:126-132); the sum: `Add for Signature` (src/types.rs:264-270).
 #include <hip/hip_runtime.h>
@@ -77,15 +78,12 @@ KERNEL_SMALL void k_mg_wave(MgParts in, size_t n, size_t bm_words, uint64_t wave
 // one slice of the partials: decode, spread, the aggregate keys of the slice's rows (rule 2 behind the decode status; a partial of no tuple
 // keeps the 2 the spread gave it), the verify; statuses at the partials' own positions.  Profiling: every slice records its intervals, so the
 // last one's stay, as in the collect.
-static int mg_verify_slice(bn254_ctx* c, hipStream_t s, const uint8_t* d_parts, const uint32_t* d_part_bits, const uint64_t* d_part_off, size_t n, size_t lo,
-                           size_t len, size_t bm_words, uint32_t flags, bool tables, const ClScratch& S, uint8_t* d_part_status) {
+static int mg_verify_slice(bn254_ctx* c, hipStream_t s, const ClCall& a, size_t lo, size_t len, bool tables, const ClScratch& S) {
   int rc;
-  if (lo) PROF_MARK(1);
-  if ((rc = launch_decode_g1(c, s, d_parts + 64 * lo, len, flags, PL_P1X, BY_P1_INF, 0))) return rc;
-  if ((rc = launch_cl_spread(c, s, len, (uint64_t)lo, n, d_part_off, S))) return rc;
-  if ((rc = launch_bitmap_sum(c, s, d_part_bits ? d_part_bits + lo * bm_words : nullptr, bm_words, len, tables))) return rc;
+  if ((rc = cl_slice_head(c, s, a, lo, len, S))) return rc;
+  if ((rc = launch_bitmap_sum(c, s, a.aux ? a.aux + lo * a.bm_words : nullptr, a.bm_words, len, tables))) return rc;
   PROF_MARK(2);
-  if ((rc = launch_verify_miller_fe(c, s, len, BN_PAIRS_VERIFY, 1, d_part_status + lo, true))) return rc;
+  if ((rc = launch_verify_miller_fe(c, s, len, BN_PAIRS_VERIFY, 1, a.item_status + lo, true))) return rc;
   PROF_MARK(4);
   return 0;
 }
@@ -103,7 +101,7 @@ KERNEL_SMALL void k_mgo_precheck(size_t n_parts, size_t n, const uint8_t* parts,
 }
 // k_mg_lane / k_mg_wave with the candidates counted and a refused candidate reported.  verdict == nullptr: the PROVISIONAL select-and-sum of
 // every tuple over the pre-check statuses, which also writes the tuple's flag; else the RE-SELECT of the tuples that go the exact way (their
-// rows zeroed by k_mgo_settle) over the final statuses — a tuple that does not go the exact way has length 0 and nothing of it is written.
+// rows zeroed by k_clo_settle) over the final statuses — a tuple that does not go the exact way has length 0 and nothing of it is written.
 KERNEL_SMALL void k_mgo_lane(MgParts in, size_t n, size_t bm_words, uint64_t wave_min, const uint8_t* verdict, uint8_t* flag, uint8_t* part_taken,
                              uint32_t* bits, uint8_t* agg, uint32_t* n_signers) {
   const size_t i = (size_t)blockIdx.x * BN_WAVE + threadIdx.x;
@@ -147,110 +145,59 @@ KERNEL_SMALL void k_mgo_wave(MgParts in, size_t n, size_t bm_words, uint64_t wav
     __syncthreads();
   }
 }
-// behind the tuple check: the rows of the tuples that go the exact way are zeroed for the re-select, and the call's counters take what the
-// check did (one ballot and one vector atomic per wave and counter, as k_clo_settle)
-KERNEL_SMALL void k_mgo_settle(size_t n, size_t bm_words, ClScratch S, uint32_t* bits) {
-  const size_t i = (size_t)blockIdx.x * BN_WAVE + threadIdx.x;
-  const bool live = i < n;
-  const uint8_t flag = live ? S.flag[i] : (uint8_t)CLO_FINAL, verdict = live ? S.verdict[i] : (uint8_t)ST_OK;
-  const bool checked = flag == CLO_CHECK, passed = checked && verdict == ST_OK, exact = clo_goes_exact(flag, verdict);
-  if (exact)
-    for (size_t w = 0; w < bm_words; ++w) bits[i * bm_words + w] = 0;
-  const uint32_t n_checked = (uint32_t)__popcll(__ballot(checked)), n_passed = (uint32_t)__popcll(__ballot(passed)), n_exact = (uint32_t)__popcll(__ballot(exact));
-  if (threadIdx.x == 0) {
-    uint32_t* stats = S.stats + CLO_STAT_AT;
-    if (n_checked) atomicAdd(&stats[0], n_checked);
-    if (n_passed) atomicAdd(&stats[1], n_passed);
-    if (n_exact) atomicAdd(&stats[2], n_exact);
-  }
-}
-// slot j of a slice = partial base + j: queued for the exact verify iff it is a candidate of a tuple that goes the exact way.  The queue
-// holds at most len entries (one per slot), and the workspace was reserved for a slice's length.
-KERNEL_SMALL void k_mgo_queue(size_t len, uint64_t base, size_t n, const uint64_t* off, ClScratch S, const uint8_t* part_status, Ws ws) {
-  const size_t j = (size_t)blockIdx.x * BN_WAVE + threadIdx.x;
-  if (j >= len) return;
-  const size_t t = cl_tuple_of(base + j, S.end, off, n);
-  if (clo_queued(part_status[base + j], t, n, S.flag, S.verdict)) ws.h_list[atomicAdd(&ws.h_cnt[0], 1u)] = (uint32_t)j;
-}
-// ... and the queue's length into the call's counters
-KERNEL_SMALL void k_mgo_count(const uint32_t* h_cnt, uint32_t* stats) {
-  if (threadIdx.x == 0 && h_cnt[0]) atomicAdd(&stats[CLO_STAT_AT + 3], h_cnt[0]);
-}
 // The route behind the hash, the range rule and the fills: pre-check, provisional select-and-sum, the tuple check in pieces of t_piece
 // tuples, then the exact verify of the queued candidates in slices of p_piece partials and the re-select.  Everything is enqueued whether or
 // not a tuple fails: the host never learns.  ms[0] = front end + provisional select-and-sum, ms[1] = aggregate keys of the union rows,
 // ms[2] = the tuples' Miller loop and final exponentiation, ms[3] = fallback + re-select (a call in several pieces: the last piece's ms[1]
 // boundary).
-static int mg_optimistic(bn254_ctx* c, hipStream_t s, const MgParts& in, size_t n_parts, size_t n, size_t bm_words, uint32_t flags, size_t t_piece,
-                         size_t p_piece, bool tables, const ClScratch& S, uint8_t* d_part_status, uint8_t* d_part_taken, uint8_t* d_agg_sigs,
-                         uint32_t* d_signer_bits, uint32_t* d_n_signers) {
+static int mg_optimistic(bn254_ctx* c, hipStream_t s, const ClCall& a, size_t t_piece, size_t p_piece, bool tables, const ClScratch& S) {
   int rc;
+  const size_t n = a.n, n_parts = a.n_items;
+  const MgParts in = {a.items, a.aux, a.off, a.item_status, a.tuple_status};
   const uint64_t wave_min = (uint64_t)c->merge_wave_min;
   const unsigned wave_grid = (unsigned)(n < CL_WAVE_MAX_BLOCKS ? n : CL_WAVE_MAX_BLOCKS);
   const BmKeys K = {c->key_xy, c->key_st, c->key_inf, (const uint32_t*)c->bm_bad, (uint32_t)c->n_keys};
   // 1. rules 1-3 of every partial; 2. the provisional select-and-sum of the candidates; 3. the tuples' flags
-  k_mgo_precheck<<<grid_for(n_parts), BN_WAVE, 0, s>>>(n_parts, n, in.parts, in.rows, in.off, bm_words, flags, S, K, d_part_status);
+  k_mgo_precheck<<<grid_for(n_parts), BN_WAVE, 0, s>>>(n_parts, n, in.parts, in.rows, in.off, a.bm_words, a.flags, S, K, a.item_status);
   HIP_TRY(hipGetLastError());
-  k_mgo_lane<<<grid_for(n), BN_WAVE, 0, s>>>(in, n, bm_words, wave_min, nullptr, S.flag, d_part_taken, d_signer_bits, d_agg_sigs, d_n_signers);
+  k_mgo_lane<<<grid_for(n), BN_WAVE, 0, s>>>(in, n, a.bm_words, wave_min, nullptr, S.flag, a.item_taken, a.signer_bits, a.agg_sigs, a.n_signers);
   HIP_TRY(hipGetLastError());
-  k_mgo_wave<<<wave_grid, BN_WAVE, 0, s>>>(in, n, bm_words, wave_min, nullptr, S.flag, d_part_taken, d_signer_bits, d_agg_sigs, d_n_signers);
+  k_mgo_wave<<<wave_grid, BN_WAVE, 0, s>>>(in, n, a.bm_words, wave_min, nullptr, S.flag, a.item_taken, a.signer_bits, a.agg_sigs, a.n_signers);
   HIP_TRY(hipGetLastError());
   PROF_MARK(1);
-  // 4. the tuple check: the call's own outputs through the bitmap verify's kernels, decode flags 0 (an identity aggregate is legitimate)
-  for (size_t lo = 0; lo < n; lo += t_piece) {
-    const size_t len = n - lo < t_piece ? n - lo : t_piece;
-    if ((rc = launch_decode_g1(c, s, d_agg_sigs + 64 * lo, len, 0, PL_P1X, BY_P1_INF, 0))) return rc;
-    if ((rc = launch_clo_load_h(c, s, len, lo, S))) return rc;
-    if ((rc = launch_bitmap_sum(c, s, d_signer_bits ? d_signer_bits + lo * bm_words : nullptr, bm_words, len, tables))) return rc;
-    PROF_MARK(2);
-    if ((rc = launch_verify_miller_fe(c, s, len, BN_PAIRS_VERIFY, 1, S.verdict + lo, false))) return rc;
-  }
-  PROF_MARK(3);
-  k_mgo_settle<<<grid_for(n), BN_WAVE, 0, s>>>(n, bm_words, S, d_signer_bits);
-  HIP_TRY(hipGetLastError());
+  // 4. the tuple check of the call's own outputs, and 5. what it settles: the collect's (bn254_collect.hip: clo_tuple_check)
+  if ((rc = clo_tuple_check(c, s, a, t_piece, S))) return rc;
   // 6. the candidates of the tuples that go the exact way, verified as the bitmap verify would over a queue; then those tuples selected again
   for (size_t lo = 0; lo < n_parts; lo += p_piece) {
     const size_t len = n_parts - lo < p_piece ? n_parts - lo : p_piece;
-    if ((rc = launch_decode_g1(c, s, in.parts + 64 * lo, len, flags, PL_P1X, BY_P1_INF, 0))) return rc;
-    if ((rc = launch_cl_spread(c, s, len, (uint64_t)lo, n, in.off, S))) return rc;
-    HIP_TRY(hipMemsetAsync(c->ws.h_cnt, 0, sizeof(uint32_t), s));
-    k_mgo_queue<<<grid_for(len), BN_WAVE, 0, s>>>(len, (uint64_t)lo, n, in.off, S, d_part_status, c->ws);
-    HIP_TRY(hipGetLastError());
-    k_mgo_count<<<1, BN_WAVE, 0, s>>>(c->ws.h_cnt, S.stats);
-    HIP_TRY(hipGetLastError());
-    if ((rc = launch_bitmap_sum_queued(c, s, in.rows ? in.rows + lo * bm_words : nullptr, bm_words, len, tables, c->ws.h_list, c->ws.h_cnt))) return rc;
+    if ((rc = clo_queue_slice(c, s, a, lo, len, S))) return rc;
+    if ((rc = launch_bitmap_sum_queued(c, s, in.rows ? in.rows + lo * a.bm_words : nullptr, a.bm_words, len, tables, c->ws.h_list, c->ws.h_cnt))) return rc;
     if ((rc = bn254_pair_miller_verify(len, c->ws, c->ws.h_list, c->ws.h_cnt, s))) return rc;
-    if ((rc = bn254_pair_final_exp(len, c->ws, 1, d_part_status + lo, c->ws.h_list, c->ws.h_cnt, s))) return rc;
+    if ((rc = bn254_pair_final_exp(len, c->ws, 1, a.item_status + lo, c->ws.h_list, c->ws.h_cnt, s))) return rc;
   }
-  k_mgo_lane<<<grid_for(n), BN_WAVE, 0, s>>>(in, n, bm_words, wave_min, S.verdict, S.flag, d_part_taken, d_signer_bits, d_agg_sigs, d_n_signers);
+  k_mgo_lane<<<grid_for(n), BN_WAVE, 0, s>>>(in, n, a.bm_words, wave_min, S.verdict, S.flag, a.item_taken, a.signer_bits, a.agg_sigs, a.n_signers);
   HIP_TRY(hipGetLastError());
-  k_mgo_wave<<<wave_grid, BN_WAVE, 0, s>>>(in, n, bm_words, wave_min, S.verdict, S.flag, d_part_taken, d_signer_bits, d_agg_sigs, d_n_signers);
+  k_mgo_wave<<<wave_grid, BN_WAVE, 0, s>>>(in, n, a.bm_words, wave_min, S.verdict, S.flag, a.item_taken, a.signer_bits, a.agg_sigs, a.n_signers);
   PROF_MARK(4);
   prof_done(c, EV_DECODE_FIRST);
   HIP_TRY(hipGetLastError());
   return 0;
 }
 
+// the merge's own check (ahead of the common ones): the partials' taken flags and, when a row has words, their rows
+static bool mg_parts_ok(const ClCall& a) { return !(a.n && a.n_items && (!a.item_taken || (a.bm_words && !a.aux))); }
 // both calls: !optimistic is the exact one
-static int mg_merge_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t* d_msg_off, const uint8_t* d_parts, const uint32_t* d_part_bits,
-                           const uint64_t* d_part_off, size_t n_parts, size_t n, size_t bm_words, uint32_t flags, bool optimistic, uint8_t* d_part_status,
-                           uint8_t* d_part_taken, uint8_t* d_tuple_status, uint8_t* d_agg_sigs, uint32_t* d_signer_bits, uint32_t* d_n_signers, void* stream) {
+static int mg_merge_device(bn254_ctx* c, const ClCall& a, bool optimistic, void* stream) {
   MsgsLenScope msgs_len_scope(c);
   if (c) c->mgo_last_ran = 0;
-  if (!c || bm_words > 0xFFFFFFFFu || n > 0xFFFFFFFFu || n_parts > 0xFFFFFFFFu) return BN254_E_BAD_ARGUMENT;
-  if (n && (!d_msgs || !d_msg_off || !d_part_off || !d_tuple_status || !d_agg_sigs || (bm_words && !d_signer_bits))) return BN254_E_BAD_ARGUMENT;
-  if (n && n_parts && (!d_parts || !d_part_status || !d_part_taken || (bm_words && !d_part_bits))) return BN254_E_BAD_ARGUMENT;
-  if (n == 0) return 0;
-  if (misaligned(d_parts) || misaligned(d_part_bits) || misaligned(d_agg_sigs) || misaligned(d_signer_bits) || misaligned(d_n_signers) ||
-      ((uintptr_t)d_msg_off & 7u) || ((uintptr_t)d_part_off & 7u))
-    return BN254_E_MISALIGNED;
-  HIP_TRY(hipSetDevice(c->device));
+  int rc = BN254_E_BAD_ARGUMENT;
+  if (!mg_parts_ok(a) || !cl_checks_device(c, a, &rc)) return rc;
+  const size_t n = a.n, n_parts = a.n_items;
   // every buffer before the first kernel, as in the collect: the tuples are hashed, and the partials verified, in pieces of the slicing
   // rule's size; the scratch holds the whole call
   const size_t t_chunk = ws_chunk_for(c, n), p_chunk = n_parts ? ws_chunk_for(c, n_parts) : 0;
   const size_t t_piece = t_chunk ? t_chunk : n, p_piece = p_chunk ? p_chunk : n_parts;
-  int rc = ws_reserve(c, t_piece > p_piece ? t_piece : p_piece);
-  if (rc) return rc;
+  if ((rc = ws_reserve(c, t_piece > p_piece ? t_piece : p_piece))) return rc;
   ClScratch S;
   if ((rc = cl_scratch_reserve(c, n, &S))) return rc;
   c->clr_last_ran = c->clo_last_ran = 0;                 // the scratch is the collect's: its debug hooks have nothing of this call to read
@@ -264,33 +211,30 @@ static int mg_merge_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t* 
   if (opt) HIP_TRY(hipMemsetAsync(S.stats, 0, CL_STAT_WORDS * sizeof(uint32_t), s));
   PROF_MARK(opt ? 0 : 1);
   // 1. hash once per tuple; 2. the range rule, the tuples' statuses, partial -> tuple
-  if ((rc = cl_hash_and_plan(c, s, d_msgs, d_msg_off, d_part_off, n_parts, n, t_piece, S, d_tuple_status))) return rc;
-  if (bm_words) HIP_TRY(hipMemsetAsync(d_signer_bits, 0, n * bm_words * sizeof(uint32_t), s));
+  if ((rc = cl_hash_and_plan(c, s, a, t_piece, S))) return rc;
+  if (a.bm_words) HIP_TRY(hipMemsetAsync(a.signer_bits, 0, n * a.bm_words * sizeof(uint32_t), s));
   if (n_parts) {
-    HIP_TRY(hipMemsetAsync(d_part_status, ST_INDEX_OOB, n_parts, s));
-    HIP_TRY(hipMemsetAsync(d_part_taken, 0, n_parts, s));
+    HIP_TRY(hipMemsetAsync(a.item_status, ST_INDEX_OOB, n_parts, s));
+    HIP_TRY(hipMemsetAsync(a.item_taken, 0, n_parts, s));
   }
   if (opt) {
-    const MgParts in = {d_parts, d_part_bits, d_part_off, d_part_status, d_tuple_status};
-    if ((rc = mg_optimistic(c, s, in, n_parts, n, bm_words, flags, t_piece, p_piece, tables, S, d_part_status, d_part_taken, d_agg_sigs, d_signer_bits,
-                            d_n_signers)))
-      return rc;
+    if ((rc = mg_optimistic(c, s, a, t_piece, p_piece, tables, S))) return rc;
     c->mgo_last_ran = 1;                                 // only a call that enqueued everything has something for the debug hook to read
     return 0;
   }
   // 3. the bitmap verify of the partials
   for (size_t lo = 0; lo < n_parts; lo += p_piece) {
     const size_t len = n_parts - lo < p_piece ? n_parts - lo : p_piece;
-    if ((rc = mg_verify_slice(c, s, d_parts, d_part_bits, d_part_off, n, lo, len, bm_words, flags, tables, S, d_part_status))) return rc;
+    if ((rc = mg_verify_slice(c, s, a, lo, len, tables, S))) return rc;
   }
   if (!n_parts) { PROF_MARK(2); PROF_MARK(3); PROF_MARK(4); }
   // 4. select-and-sum, once, behind the last slice
-  const MgParts in = {d_parts, d_part_bits, d_part_off, d_part_status, d_tuple_status};
+  const MgParts in = {a.items, a.aux, a.off, a.item_status, a.tuple_status};
   const uint64_t wave_min = (uint64_t)c->merge_wave_min;
-  k_mg_lane<<<grid_for(n), BN_WAVE, 0, s>>>(in, n, bm_words, wave_min, d_part_taken, d_signer_bits, d_agg_sigs, d_n_signers);
+  k_mg_lane<<<grid_for(n), BN_WAVE, 0, s>>>(in, n, a.bm_words, wave_min, a.item_taken, a.signer_bits, a.agg_sigs, a.n_signers);
   HIP_TRY(hipGetLastError());
-  k_mg_wave<<<(unsigned)(n < CL_WAVE_MAX_BLOCKS ? n : CL_WAVE_MAX_BLOCKS), BN_WAVE, 0, s>>>(in, n, bm_words, wave_min, d_part_taken, d_signer_bits, d_agg_sigs,
-                                                                                           d_n_signers);
+  k_mg_wave<<<(unsigned)(n < CL_WAVE_MAX_BLOCKS ? n : CL_WAVE_MAX_BLOCKS), BN_WAVE, 0, s>>>(in, n, a.bm_words, wave_min, a.item_taken, a.signer_bits, a.agg_sigs,
+                                                                                           a.n_signers);
   PROF_MARK(0);
   prof_done(c, EV_COLLECT);
   HIP_TRY(hipGetLastError());
@@ -298,38 +242,15 @@ static int mg_merge_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t* 
 }
 
 // the host-pointer form of both
-static int mg_merge_host(bn254_ctx* c, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* parts, const uint32_t* part_bits,
-                         const uint64_t* part_off, size_t n_parts, size_t n, size_t bm_words, uint32_t flags, bool optimistic, uint8_t* part_status,
-                         uint8_t* part_taken, uint8_t* tuple_status, uint8_t* agg_sigs, uint32_t* signer_bits, uint32_t* n_signers) {
+static int mg_merge_host(bn254_ctx* c, const ClCall& a, bool optimistic) {
   MsgsLenScope msgs_len_scope(c);
   if (c) c->mgo_last_ran = 0;
-  if (!c || bm_words > 0xFFFFFFFFu || n > 0xFFFFFFFFu || n_parts > 0xFFFFFFFFu) return BN254_E_BAD_ARGUMENT;
-  if (n && (!msg_off || !part_off || !tuple_status || !agg_sigs || (bm_words && !signer_bits))) return BN254_E_BAD_ARGUMENT;
-  if (n && n_parts && (!parts || !part_status || !part_taken || (bm_words && !part_bits))) return BN254_E_BAD_ARGUMENT;
-  if (n == 0) return 0;
-  HIP_TRY(hipSetDevice(c->device));
-  if (!msgs_ok(msgs, msg_off, n)) return BN254_E_BAD_ARGUMENT;
-  if (part_off[0] != 0 || !offsets_ok(part_off, n) || part_off[n] != n_parts) return BN254_E_BAD_ARGUMENT;
+  int rc = BN254_E_BAD_ARGUMENT;
+  if (!mg_parts_ok(a) || !cl_checks_host(c, a, &rc)) return rc;
   HostStaging st(c);
-  const uint8_t *d_msgs = st.in(0, msgs, (size_t)msg_off[n]), *d_msg_off = st.in(1, msg_off, (n + 1) * sizeof(uint64_t));
-  const uint8_t *d_parts = st.in(2, parts, n_parts * 64), *d_bits = st.in(3, part_bits, n_parts * bm_words * sizeof(uint32_t));
-  const uint8_t* d_part_off = st.in(4, part_off, (n + 1) * sizeof(uint64_t));
-  // the six outputs share one slot: the aligned ones first
-  const size_t o_bits = n * 64, o_cnt = o_bits + n * bm_words * sizeof(uint32_t), o_pst = o_cnt + n * sizeof(uint32_t), o_tkn = o_pst + n_parts,
-               o_tst = o_tkn + n_parts;
-  uint8_t* d_out = st.out(5, o_tst + n);
-  if (st.ok()) {
-    st.copy_back(agg_sigs, d_out, n * 64);
-    st.copy_back(signer_bits, d_out + o_bits, n * bm_words * sizeof(uint32_t));
-    st.copy_back(n_signers, d_out + o_cnt, n * sizeof(uint32_t));
-    st.copy_back(part_status, d_out + o_pst, n_parts);
-    st.copy_back(part_taken, d_out + o_tkn, n_parts);
-    st.copy_back(tuple_status, d_out + o_tst, n);
-  }
-  if (st.ok())
-    st.rc = mg_merge_device(c, d_msgs, (const uint64_t*)d_msg_off, d_parts, bm_words ? (const uint32_t*)d_bits : nullptr, (const uint64_t*)d_part_off, n_parts, n,
-                            bm_words, flags, optimistic, d_out + o_pst, d_out + o_tkn, d_out + o_tst, d_out, (uint32_t*)(d_out + o_bits),
-                            n_signers ? (uint32_t*)(d_out + o_cnt) : nullptr, nullptr);
+  ClCall d;
+  cl_stage(st, a, a.bm_words, 5, &d);
+  if (st.ok()) st.rc = mg_merge_device(c, d, optimistic, nullptr);
   return st.finish();
 }
 
@@ -339,27 +260,35 @@ int bn254_batch_merge_keyed_bitmap_device(bn254_ctx* c, const uint8_t* d_msgs, c
                                           const uint32_t* d_part_bits, const uint64_t* d_part_off, size_t n_parts, size_t n, size_t bm_words,
                                           uint32_t flags, uint8_t* d_part_status, uint8_t* d_part_taken, uint8_t* d_tuple_status, uint8_t* d_agg_sigs,
                                           uint32_t* d_signer_bits, uint32_t* d_n_signers, void* stream) {
-  return mg_merge_device(c, d_msgs, d_msg_off, d_parts, d_part_bits, d_part_off, n_parts, n, bm_words, flags, false, d_part_status, d_part_taken, d_tuple_status,
-                         d_agg_sigs, d_signer_bits, d_n_signers, stream);
+  const ClCall a = {.msgs = d_msgs, .msg_off = d_msg_off, .items = d_parts, .aux = d_part_bits, .off = d_part_off, .n_items = n_parts, .n = n,
+                    .bm_words = bm_words, .flags = flags, .item_status = d_part_status, .item_taken = d_part_taken, .tuple_status = d_tuple_status,
+                    .agg_sigs = d_agg_sigs, .signer_bits = d_signer_bits, .n_signers = d_n_signers};
+  return mg_merge_device(c, a, false, stream);
 }
 int bn254_batch_merge_keyed_bitmap(bn254_ctx* c, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* parts, const uint32_t* part_bits,
                                    const uint64_t* part_off, size_t n_parts, size_t n, size_t bm_words, uint32_t flags, uint8_t* part_status,
                                    uint8_t* part_taken, uint8_t* tuple_status, uint8_t* agg_sigs, uint32_t* signer_bits, uint32_t* n_signers) {
-  return mg_merge_host(c, msgs, msg_off, parts, part_bits, part_off, n_parts, n, bm_words, flags, false, part_status, part_taken, tuple_status, agg_sigs,
-                       signer_bits, n_signers);
+  const ClCall a = {.msgs = msgs, .msg_off = msg_off, .items = parts, .aux = part_bits, .off = part_off, .n_items = n_parts, .n = n,
+                    .bm_words = bm_words, .flags = flags, .item_status = part_status, .item_taken = part_taken, .tuple_status = tuple_status,
+                    .agg_sigs = agg_sigs, .signer_bits = signer_bits, .n_signers = n_signers};
+  return mg_merge_host(c, a, false);
 }
 int bn254_batch_merge_keyed_bitmap_optimistic_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t* d_msg_off, const uint8_t* d_parts,
                                                      const uint32_t* d_part_bits, const uint64_t* d_part_off, size_t n_parts, size_t n, size_t bm_words,
                                                      uint32_t flags, uint8_t* d_part_status, uint8_t* d_part_taken, uint8_t* d_tuple_status,
                                                      uint8_t* d_agg_sigs, uint32_t* d_signer_bits, uint32_t* d_n_signers, void* stream) {
-  return mg_merge_device(c, d_msgs, d_msg_off, d_parts, d_part_bits, d_part_off, n_parts, n, bm_words, flags, true, d_part_status, d_part_taken, d_tuple_status,
-                         d_agg_sigs, d_signer_bits, d_n_signers, stream);
+  const ClCall a = {.msgs = d_msgs, .msg_off = d_msg_off, .items = d_parts, .aux = d_part_bits, .off = d_part_off, .n_items = n_parts, .n = n,
+                    .bm_words = bm_words, .flags = flags, .item_status = d_part_status, .item_taken = d_part_taken, .tuple_status = d_tuple_status,
+                    .agg_sigs = d_agg_sigs, .signer_bits = d_signer_bits, .n_signers = d_n_signers};
+  return mg_merge_device(c, a, true, stream);
 }
 int bn254_batch_merge_keyed_bitmap_optimistic(bn254_ctx* c, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* parts, const uint32_t* part_bits,
                                               const uint64_t* part_off, size_t n_parts, size_t n, size_t bm_words, uint32_t flags, uint8_t* part_status,
                                               uint8_t* part_taken, uint8_t* tuple_status, uint8_t* agg_sigs, uint32_t* signer_bits, uint32_t* n_signers) {
-  return mg_merge_host(c, msgs, msg_off, parts, part_bits, part_off, n_parts, n, bm_words, flags, true, part_status, part_taken, tuple_status, agg_sigs,
-                       signer_bits, n_signers);
+  const ClCall a = {.msgs = msgs, .msg_off = msg_off, .items = parts, .aux = part_bits, .off = part_off, .n_items = n_parts, .n = n,
+                    .bm_words = bm_words, .flags = flags, .item_status = part_status, .item_taken = part_taken, .tuple_status = tuple_status,
+                    .agg_sigs = agg_sigs, .signer_bits = signer_bits, .n_signers = n_signers};
+  return mg_merge_host(c, a, true);
 }
 
 }  // extern "C"

@@ -1,8 +1,9 @@
 // Translation unit of libbn254hip.so: t-of-n threshold signatures over the registered keys and the segmented scalar-weighted sum in G1
 // (include/bn254_hip.h: bn254_batch_threshold_combine_keyed[_device], bn254_batch_g1_msm[_device]).  The threshold call IS
-// the exact collect (bn254_batch_collect_keyed_bitmap_device, called as it stands: front end, range rule, keyed verify slices, claim pass)
-// followed by rank-and-select on the rows it left, one Lagrange coefficient per kept key, and the term and sum kernels of the weighted
-// sum.  The bookkeeping and the arithmetic are bn254_threshold.h and bn254_fr.h, shared with the CPU suite's host compilation.
+// the exact collect (bn254_collect.hip: cl_collect_run, behind the family's shared checks and staging — bn254_host.h: ClCall: front end, range
+// rule, keyed verify slices, claim pass) followed by rank-and-select on the rows it left, one Lagrange coefficient per kept key, and the
+// term and sum kernels of the weighted sum.  The bookkeeping and the arithmetic are bn254_threshold.h and bn254_fr.h, shared with the CPU
+// suite's host compilation.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -152,46 +153,35 @@ KERNEL_SMALL void k_th_coeff(ClShares in, size_t n_shares, size_t n, size_t bm_w
   if (take) fr_to_be(scalars + 32 * s, th_lagrange_row(used + t * bm_words, bm_words, in.key[s]));
 }
 
-// the collect's argument checks, which this call repeats ahead of the scratch it adds (both forms)
-static int th_check(const bn254_ctx* c, size_t n_shares, size_t n, size_t bm_words, uint32_t threshold) {
-  if (!c || threshold == 0 || bm_words > 0xFFFFFFFFu || n > 0xFFFFFFFFu || n_shares > 0xFFFFFFFFu) return BN254_E_BAD_ARGUMENT;
-  if (bm_words < (c->n_keys + 31) / 32) return BN254_E_BAD_ARGUMENT;
-  return 0;
-}
-static int th_combine_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t* d_msg_off, const uint8_t* d_shares, const uint32_t* d_share_key,
-                             const uint64_t* d_share_off, size_t n_shares, size_t n, size_t bm_words, uint32_t threshold, uint32_t flags, uint8_t* d_share_status,
-                             uint8_t* d_tuple_status, uint8_t* d_group_sigs, uint32_t* d_used_bits, uint32_t* d_n_valid, void* stream) {
+// the call's outputs under the collect's names: agg_sigs = the group signatures, signer_bits = the rows of the keys used, n_signers = the counts
+// of keys with a valid share
+static int th_combine_device(bn254_ctx* c, const ClCall& a, uint32_t threshold, void* stream) {
   MsgsLenScope msgs_len_scope(c);
-  int rc = th_check(c, n_shares, n, bm_words, threshold);
-  if (rc) return rc;
-  if (n && (!d_msgs || !d_msg_off || !d_share_off || !d_tuple_status || !d_group_sigs || (bm_words && !d_used_bits))) return BN254_E_BAD_ARGUMENT;
-  if (n && n_shares && (!d_shares || !d_share_key || !d_share_status)) return BN254_E_BAD_ARGUMENT;
-  if (n == 0) return 0;
-  if (misaligned(d_shares) || misaligned(d_share_key) || misaligned(d_group_sigs) || misaligned(d_used_bits) || misaligned(d_n_valid) ||
-      ((uintptr_t)d_msg_off & 7u) || ((uintptr_t)d_share_off & 7u))
-    return BN254_E_MISALIGNED;
-  HIP_TRY(hipSetDevice(c->device));
+  int rc = BN254_E_BAD_ARGUMENT;
+  if (threshold == 0 || !cl_keys_ok(c, a) || !cl_checks_device(c, a, &rc)) return rc;
+  const size_t n = a.n, n_shares = a.n_items, bm_words = a.bm_words;
   // this call's scratch before the first kernel (growing it waits for the context's streams); the collect reserves its own the same way
   ThScratch T;
   if ((rc = th_scratch_reserve(c, n_shares, n * bm_words, true, &T))) return rc;
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   CallDone call_done(c, s);
-  // 1. the exact collect as it stands: share statuses, tuple statuses (2, or the hash's), row V, and the plain sum where the group signature will go
-  if ((rc = bn254_batch_collect_keyed_bitmap_device(c, d_msgs, d_msg_off, d_shares, d_share_key, d_share_off, n_shares, n, bm_words, flags, d_share_status,
-                                                    d_tuple_status, d_group_sigs, d_used_bits, nullptr, stream)))
-    return rc;
-  ClScratch S;                                         // the collect's, as it carved it for n tuples (nothing grows): the share -> tuple search
-  if ((rc = cl_scratch_reserve(c, n, &S))) return rc;
+  // 1. the exact collect behind its checks: share statuses, tuple statuses (2, or the hash's), row V, and the plain sum where the group
+  // signature will go — no counts, which are step 2's; S: the scratch it carved, for the share -> tuple search
+  c->clr_last_ran = c->clo_last_ran = c->mgo_last_ran = 0;
+  ClCall collect = a;
+  collect.n_signers = nullptr;
+  ClScratch S;
+  if ((rc = cl_collect_run(c, collect, nullptr, false, s, &S))) return rc;
   // 2. rank and select; 3. one coefficient per kept key, at the share that claims it; 4. terms and sums over the kept shares
-  k_th_settle<<<grid_for(n), BN_WAVE, 0, s>>>(n, bm_words, threshold, d_used_bits, d_tuple_status, d_group_sigs, d_n_valid);
+  k_th_settle<<<grid_for(n), BN_WAVE, 0, s>>>(n, bm_words, threshold, a.signer_bits, a.tuple_status, a.agg_sigs, a.n_signers);
   HIP_TRY(hipGetLastError());
   if (n * bm_words) HIP_TRY(hipMemsetAsync(T.claim, 0, n * bm_words * sizeof(uint32_t), s));
-  const ClShares in = {d_shares, d_share_key, d_share_off, d_share_status, d_tuple_status};
+  const ClShares in = {a.items, a.aux, a.off, a.item_status, a.tuple_status};
   if (n_shares) {
-    k_th_coeff<<<grid_for(n_shares), BN_WAVE, 0, s>>>(in, n_shares, n, bm_words, S.end, d_used_bits, T.claim, T.scalars, T.mask);
+    k_th_coeff<<<grid_for(n_shares), BN_WAVE, 0, s>>>(in, n_shares, n, bm_words, S.end, a.signer_bits, T.claim, T.scalars, T.mask);
     HIP_TRY(hipGetLastError());
   }
-  if ((rc = launch_msm(c, s, d_shares, T.scalars, T.mask, n_shares, d_share_off, d_tuple_status, n, 0, T, d_group_sigs, nullptr))) return rc;
+  if ((rc = launch_msm(c, s, a.items, T.scalars, T.mask, n_shares, a.off, a.tuple_status, n, 0, T, a.agg_sigs, nullptr))) return rc;
   PROF_MARK(0);                                        // the collect's layout (EV_COLLECT): ms[1] = its select-and-sum and the interpolation
   return 0;
 }
@@ -230,38 +220,25 @@ int bn254_batch_threshold_combine_keyed_device(bn254_ctx* c, const uint8_t* d_ms
                                                const uint32_t* d_share_key, const uint64_t* d_share_off, size_t n_shares, size_t n, size_t bm_words,
                                                uint32_t threshold, uint32_t flags, uint8_t* d_share_status, uint8_t* d_tuple_status, uint8_t* d_group_sigs,
                                                uint32_t* d_used_bits, uint32_t* d_n_valid, void* stream) {
-  return th_combine_device(c, d_msgs, d_msg_off, d_shares, d_share_key, d_share_off, n_shares, n, bm_words, threshold, flags, d_share_status, d_tuple_status,
-                           d_group_sigs, d_used_bits, d_n_valid, stream);
+  const ClCall a = {.msgs = d_msgs, .msg_off = d_msg_off, .items = d_shares, .aux = d_share_key, .off = d_share_off, .n_items = n_shares, .n = n,
+                    .bm_words = bm_words, .flags = flags, .item_status = d_share_status, .tuple_status = d_tuple_status, .agg_sigs = d_group_sigs,
+                    .signer_bits = d_used_bits, .n_signers = d_n_valid};
+  return th_combine_device(c, a, threshold, stream);
 }
-// the host-pointer form: the staging of the collect's (bn254_collect.hip: cl_collect_host), the five outputs in one slot
+// the host-pointer form: the checks and the staging of the collect's (bn254_collect.hip: cl_collect_host), the five outputs in slot 5
 int bn254_batch_threshold_combine_keyed(bn254_ctx* c, const uint8_t* msgs, const uint64_t* msg_off, const uint8_t* shares, const uint32_t* share_key,
                                         const uint64_t* share_off, size_t n_shares, size_t n, size_t bm_words, uint32_t threshold, uint32_t flags,
                                         uint8_t* share_status, uint8_t* tuple_status, uint8_t* group_sigs, uint32_t* used_bits, uint32_t* n_valid) {
+  const ClCall a = {.msgs = msgs, .msg_off = msg_off, .items = shares, .aux = share_key, .off = share_off, .n_items = n_shares, .n = n,
+                    .bm_words = bm_words, .flags = flags, .item_status = share_status, .tuple_status = tuple_status, .agg_sigs = group_sigs,
+                    .signer_bits = used_bits, .n_signers = n_valid};
   MsgsLenScope msgs_len_scope(c);
-  if (const int rc = th_check(c, n_shares, n, bm_words, threshold)) return rc;
-  if (n && (!msg_off || !share_off || !tuple_status || !group_sigs || (bm_words && !used_bits))) return BN254_E_BAD_ARGUMENT;
-  if (n && n_shares && (!shares || !share_key || !share_status)) return BN254_E_BAD_ARGUMENT;
-  if (n == 0) return 0;
-  HIP_TRY(hipSetDevice(c->device));
-  if (!msgs_ok(msgs, msg_off, n)) return BN254_E_BAD_ARGUMENT;
-  if (share_off[0] != 0 || !offsets_ok(share_off, n) || share_off[n] != n_shares) return BN254_E_BAD_ARGUMENT;
+  int rc = BN254_E_BAD_ARGUMENT;
+  if (threshold == 0 || !cl_keys_ok(c, a) || !cl_checks_host(c, a, &rc)) return rc;
   HostStaging st(c);
-  const uint8_t *d_msgs = st.in(0, msgs, (size_t)msg_off[n]), *d_msg_off = st.in(1, msg_off, (n + 1) * sizeof(uint64_t));
-  const uint8_t *d_shares = st.in(2, shares, n_shares * 64), *d_key = st.in(3, share_key, n_shares * sizeof(uint32_t));
-  const uint8_t* d_share_off = st.in(4, share_off, (n + 1) * sizeof(uint64_t));
-  const size_t o_bits = n * 64, o_cnt = o_bits + n * bm_words * sizeof(uint32_t), o_sst = o_cnt + n * sizeof(uint32_t), o_tst = o_sst + n_shares;
-  uint8_t* d_out = st.out(5, o_tst + n);
-  if (st.ok()) {
-    st.copy_back(group_sigs, d_out, n * 64);
-    st.copy_back(used_bits, d_out + o_bits, n * bm_words * sizeof(uint32_t));
-    st.copy_back(n_valid, d_out + o_cnt, n * sizeof(uint32_t));
-    st.copy_back(share_status, d_out + o_sst, n_shares);
-    st.copy_back(tuple_status, d_out + o_tst, n);
-  }
-  if (st.ok())
-    st.rc = th_combine_device(c, d_msgs, (const uint64_t*)d_msg_off, d_shares, (const uint32_t*)d_key, (const uint64_t*)d_share_off, n_shares, n, bm_words,
-                              threshold, flags, d_out + o_sst, d_out + o_tst, d_out, (uint32_t*)(d_out + o_bits),
-                              n_valid ? (uint32_t*)(d_out + o_cnt) : nullptr, nullptr);
+  ClCall d;
+  cl_stage(st, a, 1, 5, &d);
+  if (st.ok()) st.rc = th_combine_device(c, d, threshold, nullptr);
   return st.finish();
 }
 

@@ -649,11 +649,10 @@ class Engine:
         _check("bn254_batch_verify_keyed_bitmap_device",
                self._lib.bn254_batch_verify_keyed_bitmap_device(self._h, d_msgs, d_off, d_sigs, d_signer_bits, bm_words, n, flags, d_status, stream))
 
-    def batch_collect_keyed_bitmap(self, messages, shares, share_keys, sizes, bm_words, flags=0, want_counts=False, seed32=None, optimistic=False):
-        """build signer-bitmap aggregates from individual signatures (include/bn254_hip.h: bn254_batch_collect_keyed_bitmap): tuple i is
-        messages[i] with the next sizes[i] shares (64 B each, share s said to be by registered key share_keys[s]).  Returns (share status
-        bytes, tuple status bytes, the n aggregates, the n * bm_words bitmap words) — and the signer counts with want_counts.
-        seed32: see batch_collect_keyed_bitmap_randomized; optimistic: see batch_collect_keyed_bitmap_optimistic."""
+    @staticmethod
+    def _collect_buffers(messages, shares, share_keys, sizes, bm_words):
+        """what the collect and the threshold call marshal alike: the C arguments behind the context (msgs .. bm_words) and the five output
+        buffers (share statuses, tuple statuses, one G1 point per tuple, the bitmap rows, one count per tuple)"""
         n, n_shares = len(messages), len(share_keys)
         assert len(sizes) == n and all(k >= 0 for k in sizes) and sum(sizes) == n_shares and len(shares) == n_shares * G1_BYTES
         msgs, off = pack_messages(messages)
@@ -662,12 +661,18 @@ class Engine:
             ends.append(ends[-1] + int(k))
         share_off = (ctypes.c_uint64 * (n + 1))(*ends)
         keys = (ctypes.c_uint32 * max(n_shares, 1))(*share_keys)
-        share_st = ctypes.create_string_buffer(max(n_shares, 1))
-        tuple_st = ctypes.create_string_buffer(max(n, 1))
-        agg = ctypes.create_string_buffer(max(n, 1) * G1_BYTES)
-        bits = (ctypes.c_uint32 * max(n * bm_words, 1))()
-        counts = (ctypes.c_uint32 * max(n, 1))()
-        head = (self._h, msgs, off, bytes(shares), keys, share_off, n_shares, n, bm_words, flags)
+        outs = (ctypes.create_string_buffer(max(n_shares, 1)), ctypes.create_string_buffer(max(n, 1)), ctypes.create_string_buffer(max(n, 1) * G1_BYTES),
+                (ctypes.c_uint32 * max(n * bm_words, 1))(), (ctypes.c_uint32 * max(n, 1))())
+        return (msgs, off, bytes(shares), keys, share_off, n_shares, n, bm_words), outs
+
+    def batch_collect_keyed_bitmap(self, messages, shares, share_keys, sizes, bm_words, flags=0, want_counts=False, seed32=None, optimistic=False):
+        """build signer-bitmap aggregates from individual signatures (include/bn254_hip.h: bn254_batch_collect_keyed_bitmap): tuple i is
+        messages[i] with the next sizes[i] shares (64 B each, share s said to be by registered key share_keys[s]).  Returns (share status
+        bytes, tuple status bytes, the n aggregates, the n * bm_words bitmap words) — and the signer counts with want_counts.
+        seed32: see batch_collect_keyed_bitmap_randomized; optimistic: see batch_collect_keyed_bitmap_optimistic."""
+        n, n_shares = len(messages), len(share_keys)
+        args, (share_st, tuple_st, agg, bits, counts) = Engine._collect_buffers(messages, shares, share_keys, sizes, bm_words)
+        head = (self._h,) + args + (flags,)
         tail = (share_st, tuple_st, agg, bits, counts if want_counts else None)
         if optimistic:
             _check("bn254_batch_collect_keyed_bitmap_optimistic", self._lib.bn254_batch_collect_keyed_bitmap_optimistic(*head, *tail))
@@ -683,22 +688,10 @@ class Engine:
         batch_collect_keyed_bitmap and the threshold.  Returns (share status bytes, tuple status bytes, the n group signatures, the
         n * bm_words words of the rows — the keys used, or of a failed tuple the keys that were there —, the counts of keys with a valid share)."""
         n, n_shares = len(messages), len(share_keys)
-        assert len(sizes) == n and all(k >= 0 for k in sizes) and sum(sizes) == n_shares and len(shares) == n_shares * G1_BYTES
+        args, (share_st, tuple_st, sigs, bits, counts) = Engine._collect_buffers(messages, shares, share_keys, sizes, bm_words)
         assert 0 < int(threshold) < 1 << 32, "threshold must be at least 1"
-        msgs, off = pack_messages(messages)
-        ends = [0]
-        for k in sizes:
-            ends.append(ends[-1] + int(k))
-        share_off = (ctypes.c_uint64 * (n + 1))(*ends)
-        keys = (ctypes.c_uint32 * max(n_shares, 1))(*share_keys)
-        share_st = ctypes.create_string_buffer(max(n_shares, 1))
-        tuple_st = ctypes.create_string_buffer(max(n, 1))
-        sigs = ctypes.create_string_buffer(max(n, 1) * G1_BYTES)
-        bits = (ctypes.c_uint32 * max(n * bm_words, 1))()
-        counts = (ctypes.c_uint32 * max(n, 1))()
         _check("bn254_batch_threshold_combine_keyed",
-               self._lib.bn254_batch_threshold_combine_keyed(self._h, msgs, off, bytes(shares), keys, share_off, n_shares, n, bm_words, int(threshold), flags,
-                                                             share_st, tuple_st, sigs, bits, counts))
+               self._lib.bn254_batch_threshold_combine_keyed(self._h, *args, int(threshold), flags, share_st, tuple_st, sigs, bits, counts))
         return share_st.raw[:n_shares], tuple_st.raw[:n], sigs.raw[:n * G1_BYTES], list(bits)[:n * bm_words], list(counts)[:n]
 
     def batch_threshold_combine_keyed_device(self, d_msgs, d_msg_off, d_shares, d_share_key, d_share_off, n_shares, n, bm_words, threshold,

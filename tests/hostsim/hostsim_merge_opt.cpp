@@ -1,8 +1,8 @@
 // hostsim_merge_opt — TEST INFRASTRUCTURE ONLY.
 //
 // Host compilation of the device functions of bn254_batch_merge_keyed_bitmap_optimistic (bn254_amd/csrc/bn254_merge.h: mgo_*, with
-// bn254_collect.h's clo_goes_exact / clo_queued and bn254_bitmap.h's rule 2) — the very functions k_mgo_precheck, k_mgo_lane, k_mgo_wave,
-// k_mgo_settle and k_mgo_queue run — over GIVEN arrays.  The wave layout is emulated as the 64 lanes' select, their partial sums, lane after
+// bn254_collect.h's clo_goes_exact / clo_queued and bn254_bitmap.h's rule 2) — the very functions k_mgo_precheck, k_mgo_lane, k_mgo_wave and,
+// shared with the optimistic collect, k_clo_settle and k_clo_queue run — over GIVEN arrays.  The wave layout is emulated as the 64 lanes' select, their partial sums, lane after
 // lane, plus the collect's tree.  Built plain and with -DBN_TRACK_BOUNDS as a shared library by tests/test_merge_keyed_bitmap_optimistic.py;
 // and with -DHMO_MAIN as a stand-alone program that checks itself on multiples of the generator, which is what the sanitizer build runs.
 #include <cstdint>
@@ -78,7 +78,7 @@ void hmo_select(const uint8_t* parts, const uint32_t* rows, const uint64_t* off,
     if (!verdict) flag[i] = mgo_flag(cand, overlap);
   }
 }
-// k_mgo_settle: the rows of the tuples that go the exact way zeroed; stats = {checked, passed, sent the exact way}
+// k_clo_settle: the rows of the tuples that go the exact way zeroed; stats = {checked, passed, sent the exact way}
 void hmo_settle(size_t n, size_t bm_words, const uint8_t* flag, const uint8_t* verdict, uint32_t* bits, uint32_t* stats) {
   stats[0] = stats[1] = stats[2] = 0;
   for (size_t i = 0; i < n; ++i) {
@@ -87,7 +87,7 @@ void hmo_settle(size_t n, size_t bm_words, const uint8_t* flag, const uint8_t* v
     stats[0] += checked, stats[1] += checked && verdict[i] == ST_OK, stats[2] += exact;
   }
 }
-// k_mgo_queue over the slice [base, base + len): the queued slots (slice-relative), in ascending order -> their number
+// k_clo_queue over the slice [base, base + len): the queued slots (slice-relative), in ascending order -> their number
 uint64_t hmo_queue(const uint64_t* off, const uint8_t* tuple_st, size_t n, uint64_t base, uint64_t len, const uint8_t* part_st, const uint8_t* flag,
                    const uint8_t* verdict, uint32_t* list) {
   const std::vector<uint64_t> end = ends_of(off, tuple_st, n);

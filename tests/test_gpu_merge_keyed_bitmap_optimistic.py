@@ -128,6 +128,20 @@ def test_every_partial_valid(eng, c, keyset, valid):
     check(eng, c, valid, opts={k: 0 for k in SMALL_BATCH})
 
 
+def test_stage_intervals(eng, c, keyset, valid):
+    """bn254_ctx_last_kernel_ms after a profiled optimistic merge (its tuple check and queue stages are the collect's, with their events): four
+    non-negative intervals, and the tuples' Miller loop and final exponentiation among them"""
+    G.reg_set(eng, keyset)
+    try:
+        eng.set_profiling(True)
+        got, hook = opt(eng, valid)
+        ms = eng.last_kernel_ms()
+    finally:
+        eng.set_profiling(False)
+    print("optimistic merge ms", ms)
+    assert hook["passed"] == 9 and len(ms) == 4 and all(v >= 0 for v in ms.values()) and ms["miller_loop"] > 0
+
+
 @pytest.mark.parametrize("flags", [0, E.FLAG_G2_SUBGROUP_CHECK, E.FLAG_REJECT_IDENTITY], ids=["flags0", "g2_subgroup", "reject_identity"])
 def test_plan_a_is_the_exact_merge(eng, c, keyset, cases, flags):
     """wrong, undecodable, out-of-range, refused-key and overlapping partials: a sum off by k * G1 never cancels, so all six outputs are the

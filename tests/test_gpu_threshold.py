@@ -230,6 +230,22 @@ def test_routes_give_the_same_bytes(eng, sets, route):
         check(ks, with_options(eng, opts, lambda: combine(eng, ks.tuples, ks.bm_words, ks.t)), (name, route))
 
 
+def test_stage_intervals(eng, sets):
+    """bn254_ctx_last_kernel_ms after a profiled threshold call (the collect's events, the interpolation inside its last interval): four
+    non-negative intervals, and the shares' Miller loop among them"""
+    ks = sets["dealt9_t5"]
+    ks.register(eng)
+    try:
+        eng.set_profiling(True)
+        got = combine(eng, ks.tuples, ks.bm_words, ks.t)
+        ms = eng.last_kernel_ms()
+    finally:
+        eng.set_profiling(False)
+    print("threshold ms", ms)
+    check(ks, got, "profiled")
+    assert len(ms) == 4 and all(v >= 0 for v in ms.values()) and ms["miller_loop"] > 0
+
+
 def test_flags_and_wider_bitmap(eng, sets):
     """BN254_FLAG_REJECT_IDENTITY: the identity key's all-zero share reads 4 and the key drops out; a bitmap wider than the key set"""
     ks = sets["ident9"]

@@ -7,7 +7,7 @@ them):
       and bn254_batch_g1_sum (host pointers) over the shares that passed, one segment per tuple.  The bitmap, which the caller would also
       assemble by hand, is not counted.
 Both are timed with HIP events on the caller's stream around whole calls, alternating, `--reps` calls each after two warm-up calls: the
-median, with the min and max beside it.  (b)'s interval contains its host work — that is the route.  Per-stage times of one profiled call
+median, with the min and max beside it (and the new call's mean, for an A/B of two builds through BN254_LIB).  (b)'s interval contains its host work — that is the route.  Per-stage times of one profiled call
 of (a) and of the keyed verify: bn254_ctx_last_kernel_ms ((a): ms[0] decode + hash + spread, ms[1] select-and-sum, ms[2] Miller loop,
 ms[3] final exponentiation).  --wave-min sweeps BN254_OPT_COLLECT_WAVE_MIN_SHARES for (a).  One JSON line per shape (default stdout).
 --rand adds bn254_batch_collect_keyed_bitmap_randomized_device with its route forced (options 38 = 0, 39 = 0), 128-bit and 64-bit weights:
@@ -209,7 +209,7 @@ def main():
                 call()
                 kms = eng.last_kernel_ms()
                 eng.set_profiling(False)
-                rand[name] = {"ms": round(statistics.median(t), 3), "min_ms": round(min(t), 3), "max_ms": round(max(t), 3),
+                rand[name] = {"ms": round(statistics.median(t), 3), "min_ms": round(min(t), 3), "max_ms": round(max(t), 3), "mean_ms": round(statistics.mean(t), 3),
                               "stages_ms": [round(kms[x], 3) for x in ("decode", "hash_to_g1", "miller_loop", "final_exp")],
                               "hook": hook, "same_bytes_as_exact": bool(same_bytes)}
             eng.set_option(OPT_COLLECT_RAND_MIN_SHARES, COLLECT_RAND_MIN_SHARES_DEFAULT)
@@ -227,14 +227,14 @@ def main():
             collect_opt()
             kms = eng.last_kernel_ms()
             eng.set_profiling(False)
-            optimistic = {"ms": round(statistics.median(t), 3), "min_ms": round(min(t), 3), "max_ms": round(max(t), 3),
+            optimistic = {"ms": round(statistics.median(t), 3), "min_ms": round(min(t), 3), "max_ms": round(max(t), 3), "mean_ms": round(statistics.mean(t), 3),
                           "stages_ms": [round(kms[x], 3) for x in ("decode", "hash_to_g1", "miller_loop", "final_exp")],
                           "hook": hook, "same_bytes_as_exact": bool(same_bytes)}
             eng.set_option(OPT_COLLECT_OPT_MIN_SHARES, COLLECT_OPT_MIN_SHARES_DEFAULT)
             eng.set_option(OPT_COLLECT_OPT_MIN_TUPLE_SHARES, COLLECT_OPT_MIN_TUPLE_SHARES_DEFAULT)
         med = {x: statistics.median(v) for x, v in ms.items()}
         row = {"shape": "%dx%d" % (n, k), "n": n, "shares_per_tuple": k, "n_shares": n_shares, "mean_signers": round(float(counts.mean()), 1),
-               "a_ms": round(med["a"], 3), "a_min_ms": round(min(ms["a"]), 3), "a_max_ms": round(max(ms["a"]), 3),
+               "a_ms": round(med["a"], 3), "a_min_ms": round(min(ms["a"]), 3), "a_max_ms": round(max(ms["a"]), 3), "a_mean_ms": round(statistics.mean(ms["a"]), 3),
                "b_ms": round(med["b"], 3), "b_min_ms": round(min(ms["b"]), 3), "b_max_ms": round(max(ms["b"]), 3),
                "keyed_verify_alone_ms": round(med["keyed"], 3), "b_over_a": round(med["b"] / med["a"], 2),
                "a_not_slower_beyond_spread": max(ms["a"]) <= min(ms["b"]),

@@ -266,7 +266,8 @@ def main():
             row = {"optimistic": True, "shape": "%dx%d%s" % (n, k, " one-bit" if one_bit else ""), "n": n, "partials_per_tuple": k, "n_parts": n_parts,
                    "bm_words": bm_words, "bad_parts": len(bad), "bad_in_one_tuple": bool(a.bad_one_tuple)}
             for name in legs:
-                row.update({name + "_ms": round(med[name], 3), name + "_min_ms": round(min(ms[name]), 3), name + "_max_ms": round(max(ms[name]), 3)})
+                row.update({name + "_ms": round(med[name], 3), name + "_min_ms": round(min(ms[name]), 3), name + "_max_ms": round(max(ms[name]), 3),
+                            name + "_mean_ms": round(statistics.mean(ms[name]), 3)})
             row.update({"exact_over_opt": round(med["exact"] / med["opt"], 2), "opt_wins_beyond_spread": max(ms["opt"]) < min(ms["exact"]),
                         "opt_loses_beyond_spread": min(ms["opt"]) > max(ms["exact"]),
                         "opt_stages_ms": stages, "opt_stage_slots": "front end + provisional select-and-sum, aggregate keys, tuples' miller + final_exp, fallback + re-select",
@@ -324,7 +325,7 @@ def main():
         med = {x: statistics.median(v) for x, v in ms.items()}
         row = {"shape": "%dx%d%s" % (n, k, " one-bit" if one_bit else ""), "n": n, "partials_per_tuple": k, "n_parts": n_parts, "bm_words": bm_words,
                "mean_signers": round(float(counts.mean()), 1), "partials_taken": int(host["taken"].sum()),
-               "a_ms": round(med["a"], 3), "a_min_ms": round(min(ms["a"]), 3), "a_max_ms": round(max(ms["a"]), 3),
+               "a_ms": round(med["a"], 3), "a_min_ms": round(min(ms["a"]), 3), "a_max_ms": round(max(ms["a"]), 3), "a_mean_ms": round(statistics.mean(ms["a"]), 3),
                "b_ms": round(med["b"], 3), "b_min_ms": round(min(ms["b"]), 3), "b_max_ms": round(max(ms["b"]), 3),
                "b_host_filter_ms": round(med["filter"], 3), "bitmap_verify_alone_ms": round(med["verify"], 3), "b_over_a": round(med["b"] / med["a"], 2),
                "a_not_slower_beyond_spread": max(ms["a"]) <= min(ms["b"]),

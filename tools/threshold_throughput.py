@@ -77,7 +77,7 @@ def lagrange_at_zero(xs):
 
 
 def spread(v):
-    return {"ms": round(statistics.median(v), 3), "min_ms": round(min(v), 3), "max_ms": round(max(v), 3)}
+    return {"ms": round(statistics.median(v), 3), "min_ms": round(min(v), 3), "max_ms": round(max(v), 3), "mean_ms": round(statistics.mean(v), 3)}
 
 
 def msm_rows(eng, lib, h, ts, stream, box, m, reps, out):

@@ -158,6 +158,11 @@ def load():
         L.bn254_batch_threshold_combine_keyed_device.argtypes = [vp, vp, vp, vp, vp, vp, sz, sz, sz, u32, u32, vp, vp, vp, vp, vp, vp]
         L.bn254_debug_fr_op.argtypes = [vp, i32, vp, vp, sz, vp]
         L.bn254_debug_lagrange_at_zero.argtypes = [vp, vp, vp, sz, vp]
+    if hasattr(L, "bn254_batch_threshold_combine_keyed_optimistic"):  # absent from an older build loaded through BN254_LIB
+        L.bn254_ctx_set_group_key.argtypes = [vp, vp, u32, vp]
+        L.bn254_batch_threshold_combine_keyed_optimistic.argtypes = [vp, vp, vp, vp, vp, vp, sz, sz, sz, u32, u32, vp, vp, vp, vp, vp]
+        L.bn254_batch_threshold_combine_keyed_optimistic_device.argtypes = [vp, vp, vp, vp, vp, vp, sz, sz, sz, u32, u32, vp, vp, vp, vp, vp, vp]
+        L.bn254_debug_threshold_opt_last.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     L.bn254_debug_bitmap_rand_last.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     L.bn254_debug_bitmap_rand_sums.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), sz, sz, vp, vp, vp, vp, vp, vp]
     L.bn254_batch_verify_keyed_randomized.argtypes = [vp, vp, vp, vp, vp, sz, u32, vp, vp]
@@ -261,4 +266,6 @@ EXPORTED_SYMBOLS = [
     "bn254_ctx_register_keys_pop", "bn254_mgpu_register_keys_pop",
     "bn254_batch_g1_msm", "bn254_batch_g1_msm_device", "bn254_batch_threshold_combine_keyed", "bn254_batch_threshold_combine_keyed_device",
     "bn254_debug_fr_op", "bn254_debug_lagrange_at_zero",
+    "bn254_ctx_set_group_key", "bn254_batch_threshold_combine_keyed_optimistic", "bn254_batch_threshold_combine_keyed_optimistic_device",
+    "bn254_debug_threshold_opt_last",
 ]

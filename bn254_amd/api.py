@@ -463,6 +463,39 @@ class ECDSA:
         """items: a list of (message, signatures, key_indices), one threshold for all; result[i] is what ECDSA.threshold_combine_keyed returns
         for item i, or the Error it would raise.  A malformed item raises Error(InvalidLength) / Error(IndexOutOfBounds), a threshold below
         1 ValueError, before any device work."""
+        return ECDSA._threshold_batch(items, threshold, engine, n_keys, False)
+
+    @staticmethod
+    def register_group_key(public_key, engine=None):
+        """Name the group key f(0) * G2 of the registered dealing (ECDSA.threshold_group_key computes it from share keys) for
+        threshold_combine_keyed_optimistic; None forgets it.  Raises the Error PublicKey.from_uncompressed would raise for the key, and
+        then no group key is set.  ECDSA.register_keys / register_keys_proven forget the group key: a new key set is a new dealing.  The
+        library does not check that the registered keys interpolate to this key — a key that does not belong to the set only makes the
+        optimistic call as slow as the exact one (include/bn254_hip.h: bn254_ctx_set_group_key)."""
+        eng = engine or _eng()
+        _raise(eng.set_group_key(None if public_key is None else public_key.raw))
+
+    @staticmethod
+    def threshold_combine_keyed_optimistic(message, signatures, key_indices, threshold, engine=None, n_keys=None):
+        """threshold_combine_keyed by interpolating the `threshold` lowest keys with a well-formed share first and verifying the RESULT once
+        under the group key (ECDSA.register_group_key) — the check the signature's consumer will make.  A result that passes is the group
+        signature; then the shares outside the keys used were not verified (their status is None if they are well-formed and name a
+        registered key) and shares whose errors cancel under the coefficients read None.  A result that fails sends the tuple through
+        the exact call: the same return value or Error.  Take threshold_combine_keyed when the per-share verdicts matter
+        (include/bn254_hip.h: bn254_batch_threshold_combine_keyed_optimistic)."""
+        r = ECDSA.batch_threshold_combine_keyed_optimistic([(message, signatures, key_indices)], threshold, engine, n_keys)[0]
+        if isinstance(r, Error):
+            raise r
+        return r
+
+    @staticmethod
+    def batch_threshold_combine_keyed_optimistic(items, threshold, engine=None, n_keys=None):
+        """batch_threshold_combine_keyed, every item as threshold_combine_keyed_optimistic treats it.  A malformed item and a threshold below
+        1 raise as there, an engine without a group key ValueError, all before any device work."""
+        return ECDSA._threshold_batch(items, threshold, engine, n_keys, True)
+
+    @staticmethod
+    def _threshold_batch(items, threshold, engine, n_keys, optimistic):
         if int(threshold) < 1 or int(threshold) >= 1 << 32:
             raise ValueError("threshold must be between 1 and 2^32 - 1")
         rows = []
@@ -482,7 +515,10 @@ class ECDSA:
         if n_keys is None:
             raise ValueError("the engine does not know its registered key count: pass n_keys")
         bm_words = max((int(n_keys) + 31) // 32, 1)
-        share_st, tuple_st, group, bits, _ = eng.batch_threshold_combine_keyed(
+        if optimistic and not getattr(eng, "group_key_set", False):
+            raise ValueError("the engine has no group key: ECDSA.register_group_key first")
+        call = eng.batch_threshold_combine_keyed_optimistic if optimistic else eng.batch_threshold_combine_keyed
+        share_st, tuple_st, group, bits, _ = call(
             [r[0] for r in rows], b"".join(s.raw for r in rows for s in r[1]), [j for r in rows for j in r[2]], [len(r[2]) for r in rows], bm_words,
             int(threshold))
         out, at = [], 0

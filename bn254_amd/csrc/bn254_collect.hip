@@ -217,7 +217,7 @@ static int cl_verify_slice(bn254_ctx* c, hipStream_t s, const ClCall& a, size_t 
   if (c->n_keys == 0 || !c->key_lines) {               // nothing registered: every share that decodes is out of range
     if ((rc = launch_keyed_no_keys(c, s, len, a.item_status + lo))) return rc;
     PROF_MARK(3);
-  } else if ((rc = launch_keyed_miller_fe(c, s, len, a.aux + lo, a.item_status + lo))) return rc;
+  } else if ((rc = launch_keyed_miller_fe(c, s, len, a.aux + lo, a.item_status + lo, ctx_key_table(c), c->key_xy))) return rc;
   PROF_MARK(4);
   return 0;
 }
@@ -388,6 +388,25 @@ int clo_queue_slice(bn254_ctx* c, hipStream_t s, const ClCall& a, size_t lo, siz
   HIP_TRY(hipGetLastError());
   return 0;
 }
+// The same stages one by one, for the optimistic threshold call (bn254_threshold.hip), whose tuple check runs under the group key: rules 1-3
+// of every share; H(m) of the tuples lo .. lo + len beside whatever the caller decoded into entries 0 .. len; the settle behind the verdicts
+int clo_precheck_all(bn254_ctx* c, hipStream_t s, const ClCall& a, const ClScratch& S) {
+  if (!a.n_items) return 0;
+  k_clo_precheck<<<grid_for(a.n_items), BN_WAVE, 0, s>>>(a.n_items, a.n, a.items, a.aux, a.off, a.flags, S, c->key_st, (uint32_t)c->n_keys, a.item_status);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+int clo_load_h(bn254_ctx* c, hipStream_t s, size_t lo, size_t len, const ClScratch& S) {
+  k_clo_load_h<<<grid_for(len), BN_WAVE, 0, s>>>(len, lo, S, c->ws);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+int clo_settle(bn254_ctx* c, hipStream_t s, const ClCall& a, const ClScratch& S) {
+  (void)c;
+  k_clo_settle<<<grid_for(a.n), BN_WAVE, 0, s>>>(a.n, a.bm_words, S, a.signer_bits);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
 // The route behind the hash, the range rule and the fills (cl_collect_run): pre-check, provisional sum, the tuple check in pieces of
 // t_piece tuples, then the exact verify of the queued candidates in slices of s_piece shares and the re-sum.  Everything is enqueued whether
 // or not a tuple fails: the host never learns.  ms[0] = front end + provisional sum, ms[1] = aggregate keys, ms[2] = the tuples' Miller loop
@@ -495,7 +514,7 @@ int cl_collect_run(bn254_ctx* c, const ClCall& call, const uint8_t* seed32, bool
 // the checked entry of the three *_device calls
 static int cl_collect_device(bn254_ctx* c, const ClCall& a, const uint8_t* seed32, bool optimistic, void* stream) {
   MsgsLenScope msgs_len_scope(c);
-  if (c) c->clr_last_ran = c->clo_last_ran = c->mgo_last_ran = 0;
+  if (c) c->clr_last_ran = c->clo_last_ran = c->mgo_last_ran = c->tho_last_ran = 0;
   int rc = BN254_E_BAD_ARGUMENT;
   if (!cl_keys_ok(c, a) || !cl_checks_device(c, a, &rc)) return rc;
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
@@ -506,7 +525,7 @@ static int cl_collect_device(bn254_ctx* c, const ClCall& a, const uint8_t* seed3
 // the host-pointer form of the three.  The randomised call's grouping scratch lives in stage slots 5 and 7, so its outputs take slot 6.
 static int cl_collect_host(bn254_ctx* c, const ClCall& a, const uint8_t* seed32, bool optimistic) {
   MsgsLenScope msgs_len_scope(c);
-  if (c) c->clr_last_ran = c->clo_last_ran = c->mgo_last_ran = 0;
+  if (c) c->clr_last_ran = c->clo_last_ran = c->mgo_last_ran = c->tho_last_ran = 0;
   int rc = BN254_E_BAD_ARGUMENT;
   if (!cl_keys_ok(c, a) || !cl_checks_host(c, a, &rc)) return rc;
   HostStaging st(c);

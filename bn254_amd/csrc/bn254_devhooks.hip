@@ -375,6 +375,18 @@ int bn254_debug_collect_opt_last(bn254_ctx* c, uint64_t out[4]) {
   for (int i = 0; i < 4; ++i) out[i] = st[i];
   return 0;
 }
+// bn254_batch_threshold_combine_keyed_optimistic: {tuples checked, passed, sent the exact way, shares verified exactly} of its last call
+int bn254_debug_threshold_opt_last(bn254_ctx* c, uint64_t out[4]) {
+  if (!c || !out) return BN254_E_BAD_ARGUMENT;
+  for (int i = 0; i < 4; ++i) out[i] = 0;
+  if (!c->tho_last_ran || !c->tho_stats) return 0;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipDeviceSynchronize());
+  uint32_t st[4];
+  HIP_TRY(hipMemcpy(st, c->tho_stats, sizeof st, hipMemcpyDeviceToHost));
+  for (int i = 0; i < 4; ++i) out[i] = st[i];
+  return 0;
+}
 // bn254_batch_merge_keyed_bitmap_optimistic: the same four of its last call, the fourth in partials
 int bn254_debug_merge_opt_last(bn254_ctx* c, uint64_t out[4]) {
   if (!c || !out) return BN254_E_BAD_ARGUMENT;

@@ -793,6 +793,7 @@ int bn254_ctx_create(int hip_device, bn254_ctx** out) {
   c->collect_opt_min_tuple_shares = COLLECT_OPT_MIN_TUPLE_SHARES_DEFAULT;
   c->merge_wave_min = MERGE_WAVE_MIN_PARTS_DEFAULT;
   c->merge_opt_min_parts = MERGE_OPT_MIN_PARTS_DEFAULT;
+  c->th_opt_min_shares = THRESHOLD_OPT_MIN_SHARES_DEFAULT;
   c->trio_max_batch = TRIO_MAX_BATCH_DEFAULT;
   c->hash_direct_width = HASH_DIRECT_WIDTH_DEFAULT;
   c->hash_tail_chunk = HASH_TAIL_CHUNK_DEFAULT;
@@ -876,6 +877,10 @@ void bn254_ctx_destroy(bn254_ctx* c) {
   if (c->bm_tab) (void)hipFree(c->bm_tab);
   if (c->pop_buf) (void)hipFree(c->pop_buf);
   if (c->th_buf) (void)hipFree(c->th_buf);
+  if (c->gk_lines) (void)hipFree(c->gk_lines);
+  if (c->gk_xy) (void)hipFree(c->gk_xy);
+  if (c->gk_st) (void)hipFree(c->gk_st);
+  if (c->gk_inf) (void)hipFree(c->gk_inf);
   for (int i = 0; i < 5; ++i) (void)hipEventDestroy(c->ev[i]);
   (void)hipEventDestroy(c->kd_fork);
   (void)hipEventDestroy(c->kd_join);
@@ -991,6 +996,7 @@ int bn254_ctx_set_option(bn254_ctx* c, int option, int value) {
   if (option == BN254_OPT_COLLECT_WAVE_MIN_SHARES) { if (value < 1) return BN254_E_BAD_ARGUMENT; c->collect_wave_min = value; return 0; }
   if (option == BN254_OPT_COLLECT_RAND_MIN_SHARES) { if (value < 0) return BN254_E_BAD_ARGUMENT; c->collect_rand_min_shares = value; return 0; }
   if (option == BN254_OPT_COLLECT_RAND_MIN_PER_KEY) { if (value < 0) return BN254_E_BAD_ARGUMENT; c->collect_rand_min_per_key = value; return 0; }
+  if (option == BN254_OPT_THRESHOLD_OPT_MIN_SHARES) { if (value < 0) return BN254_E_BAD_ARGUMENT; c->th_opt_min_shares = value; return 0; }
   if (option == BN254_OPT_COLLECT_OPT_MIN_SHARES) { if (value < 0) return BN254_E_BAD_ARGUMENT; c->collect_opt_min_shares = value; return 0; }
   if (option == BN254_OPT_MERGE_WAVE_MIN_PARTS) { if (value < 1) return BN254_E_BAD_ARGUMENT; c->merge_wave_min = value; return 0; }
   if (option == BN254_OPT_MERGE_OPT_MIN_PARTS) { if (value < 0) return BN254_E_BAD_ARGUMENT; c->merge_opt_min_parts = value; return 0; }

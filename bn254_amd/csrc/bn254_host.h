@@ -157,6 +157,14 @@ struct bn254_ctx {
   // threshold call the coefficients, the take flags and the second claim rows, grown on demand
   uint8_t* th_buf;
   size_t th_cap;
+  // ... the optimistic threshold call: the GROUP key (bn254_ctx_set_group_key) in a one-entry key table of its own — lines, status byte,
+  // identity byte, affine words, as k_register_keys leaves one key — allocated by the first call that sets one; a registration forgets it
+  int32_t *gk_lines, *gk_xy;
+  uint8_t *gk_st, *gk_inf;
+  bool gk_set;
+  int th_opt_min_shares;     // BN254_OPT_THRESHOLD_OPT_MIN_SHARES: the optimistic threshold call from this many shares on
+  uint32_t* tho_stats;       // what its last call did on the device (bn254_debug_threshold_opt_last); inside collect_buf
+  int tho_last_ran;          // ... and whether that call took the optimistic route at all
 };
 
 struct ScopedEvents {
@@ -297,7 +305,10 @@ enum BnVerifyPairs { BN_PAIRS_VERIFY = 0, BN_PAIRS_CHECK_PKS = 1 };
 BN_HIDDEN int launch_verify_miller_fe(bn254_ctx* c, hipStream_t s, size_t n, int pairs, int use_hash, uint8_t* d_status, bool mark);
 // the same for a KEYED batch (bn254_rand.hip): item i's key is the registered key d_key_idx[i] — rule 2 of bn254_batch_verify_keyed behind the
 // decode status, then the routing table's keyed kernels; and the statuses of such a batch when no key is registered
-BN_HIDDEN int launch_keyed_miller_fe(bn254_ctx* c, hipStream_t s, size_t n, const uint32_t* d_key_idx, uint8_t* d_status);
+// kt, key_xy: the table the indices point into — the context's registered set (ctx_key_table), or the group key's one entry
+BN_HIDDEN int launch_keyed_miller_fe(bn254_ctx* c, hipStream_t s, size_t n, const uint32_t* d_key_idx, uint8_t* d_status, const KeyTable& kt,
+                                     const int32_t* key_xy);
+static inline KeyTable ctx_key_table(const bn254_ctx* c) { const KeyTable kt = {c->key_lines, c->key_st, c->key_inf, (uint32_t)c->n_keys}; return kt; }
 BN_HIDDEN int launch_keyed_no_keys(bn254_ctx* c, hipStream_t s, size_t n, uint8_t* d_status);
 // a registration in two steps (bn254_rand.hip), shared by bn254_ctx_register_keys and bn254_ctx_register_keys_pop: quiesce, drop the previous set
 // (n_keys = 0, the bitmap call's vector and tables invalid) and make room for n_keys keys; then decode and tabulate the staged keys on c->stream.
@@ -405,6 +416,12 @@ BN_HIDDEN int clo_tuple_check(bn254_ctx* c, hipStream_t s, const ClCall& a, size
 // ... and the head of a fallback slice: decode and spread of the items lo .. lo + len (the call's flags), and their candidates of the tuples
 // that go the exact way queued in the workspace's h_list / h_cnt and counted
 BN_HIDDEN int clo_queue_slice(bn254_ctx* c, hipStream_t s, const ClCall& a, size_t lo, size_t len, const ClScratch& S);
+// ... and the stages of that route the optimistic threshold call (bn254_threshold.hip) enqueues one by one, its tuple check being its own:
+// rules 1-3 of every share into a.item_status; H(m) and the hash status of the tuples lo .. lo + len into workspace entries 0 .. len; and,
+// behind the verdicts, the rows of the tuples that go the exact way zeroed and the check counted (k_clo_settle)
+BN_HIDDEN int clo_precheck_all(bn254_ctx* c, hipStream_t s, const ClCall& a, const ClScratch& S);
+BN_HIDDEN int clo_load_h(bn254_ctx* c, hipStream_t s, size_t lo, size_t len, const ClScratch& S);
+BN_HIDDEN int clo_settle(bn254_ctx* c, hipStream_t s, const ClCall& a, const ClScratch& S);
 // the aggregate keys of a device-side QUEUE of tuples on lane pairs (bn254_bitmap_rand.hip: k_bmr_sum_pair_q): lane pair e < *count takes row
 // map[e] of d_bits into the Q planes of entry map[e]; rule 2 is the caller's.  n = the most the queue can hold
 BN_HIDDEN int launch_bitmap_sum_queued(bn254_ctx* c, hipStream_t s, const uint32_t* d_bits, size_t bm_words, size_t n, bool tables, const uint32_t* map,

@@ -200,7 +200,7 @@ static int mg_merge_device(bn254_ctx* c, const ClCall& a, bool optimistic, void*
   if ((rc = ws_reserve(c, t_piece > p_piece ? t_piece : p_piece))) return rc;
   ClScratch S;
   if ((rc = cl_scratch_reserve(c, n, &S))) return rc;
-  c->clr_last_ran = c->clo_last_ran = 0;                 // the scratch is the collect's: its debug hooks have nothing of this call to read
+  c->clr_last_ran = c->clo_last_ran = c->tho_last_ran = 0;                 // the scratch is the collect's: its debug hooks have nothing of this call to read
   // the optimistic route: keys to sum, the lane-pair kernels the queue runs on, and enough partials.  Else the exact route, same bytes.
   const bool opt = optimistic && c->n_keys && c->key_lines && c->pair_lanes && n_parts && n_parts >= (size_t)c->merge_opt_min_parts;
   c->mgo_stats = S.stats + CLO_STAT_AT;

@@ -178,7 +178,7 @@ int bn254_ctx_register_keys_pop(bn254_ctx* c, const uint8_t* pks, const uint8_t*
     const size_t len = n_keys - lo < chunk ? n_keys - lo : chunk;
     if ((rc = launch_decode_g1(c, s, d_pops + 64 * lo, len, flags & BN254_FLAG_REJECT_IDENTITY, PL_P1X, BY_P1_INF, 0))) return rc;
     if ((rc = launch_hash_rounds(c, s, (const uint8_t*)S.m.msgs, S.m.off + lo, len, PL_P2X, BY_P2_INF, nullptr))) return rc;
-    if ((rc = launch_keyed_miller_fe(c, s, len, S.m.key_idx + lo, S.st + lo))) return rc;
+    if ((rc = launch_keyed_miller_fe(c, s, len, S.m.key_idx + lo, S.st + lo, ctx_key_table(c), c->key_xy))) return rc;
   }
   if ((rc = launch_pop_fold(s, n_keys, c->key_st, S.st))) return rc;
   if ((rc = st.finish())) return rc;

@@ -343,8 +343,7 @@ KERNEL_SMALL void k_neg_g2_key_lines(int32_t* out) {
 
 // the Miller loop and final exponentiation of a keyed batch whose P1 / P2 planes are filled (bn254_host.h): by the routing table the lane
 // machine's keyed form, the expanded keys and the small-batch kernels, or the line tables on lane pairs; profiling event 3 between the two
-int launch_keyed_miller_fe(bn254_ctx* c, hipStream_t s, size_t n, const uint32_t* d_key_idx, uint8_t* d_status) {
-  const KeyTable kt = {c->key_lines, c->key_st, c->key_inf, (uint32_t)c->n_keys};
+int launch_keyed_miller_fe(bn254_ctx* c, hipStream_t s, size_t n, const uint32_t* d_key_idx, uint8_t* d_status, const KeyTable& kt, const int32_t* key_xy) {
   int rc;
   const BnRoute r = route_for(c, n);
   if (r.miller == BN_ML_LANE_MACHINE) {
@@ -355,7 +354,7 @@ int launch_keyed_miller_fe(bn254_ctx* c, hipStream_t s, size_t n, const uint32_t
   } else if (r.miller != BN_ML_LANE_PAIRS) {
     // a batch that cannot fill the chip: latency counts — expand the keys and take the small-batch kernels (2.3 ms instead of the
     // 6 ms of the lane-pair layout; the line tables pay off only where throughput binds)
-    k_keyed_expand<<<grid_for(n), BN_WAVE, 0, s>>>(n, c->ws, d_key_idx, kt, c->key_xy);
+    k_keyed_expand<<<grid_for(n), BN_WAVE, 0, s>>>(n, c->ws, d_key_idx, kt, key_xy);
     if ((rc = launch_verify_miller_fe(c, s, n, BN_PAIRS_VERIFY, 1, d_status, true))) return rc;
   } else {
     if ((rc = bn254_pair_miller_verify_keyed(n, c->ws, d_key_idx, kt, s))) return rc;
@@ -406,6 +405,7 @@ int launch_keyed_rand_checks(bn254_ctx* c, hipStream_t s, size_t n, const uint32
 int register_keys_begin(bn254_ctx* c, size_t n_keys) {
   { int rc_ = ctx_quiesce(c); if (rc_) return rc_; }   // no keyed verify — on c->stream or on the caller's stream of the last call — may still be reading the previous tables
   c->n_keys = 0;
+  c->gk_set = false;                                  // a new key set is a new dealing: the group key of the previous one is forgotten
   c->bm_bad_valid = c->bm_tab_valid = false;          // the bitmap call's bad-bit vector and subset tables belong to the previous set
   if (n_keys == 0) return 0;
   if (n_keys > c->key_cap) {
@@ -447,6 +447,30 @@ int bn254_ctx_register_keys(bn254_ctx* c, const uint8_t* pks, size_t n_keys, uin
   c->n_keys = n_keys;
   return 0;
 }
+// the group key of the optimistic threshold call: one key decoded and tabulated as a registration tabulates its keys, into a table of its own
+int bn254_ctx_set_group_key(bn254_ctx* c, const uint8_t* group_pk, uint32_t flags, uint8_t* status) {
+  if (!c) return BN254_E_BAD_ARGUMENT;
+  HIP_TRY(hipSetDevice(c->device));
+  { int rc_ = ctx_quiesce(c); if (rc_) return rc_; }   // no tuple check may still be reading the previous key's table
+  c->gk_set = false;
+  if (status) *status = ST_OK;
+  if (!group_pk) return 0;
+  if (!c->gk_lines) HIP_TRY(hipMalloc((void**)&c->gk_lines, (size_t)BN_N_FIXED_LINES * BN_KEY_LINE_WORDS * sizeof(int32_t)));
+  if (!c->gk_xy) HIP_TRY(hipMalloc((void**)&c->gk_xy, 4 * BN_LIMBS * sizeof(int32_t)));
+  if (!c->gk_st) HIP_TRY(hipMalloc((void**)&c->gk_st, 1));
+  if (!c->gk_inf) HIP_TRY(hipMalloc((void**)&c->gk_inf, 1));
+  uint8_t key_st = 0xFF;
+  HostStaging st(c);
+  const uint8_t* d_pk = st.in(3, group_pk, 128);
+  st.copy_back(&key_st, c->gk_st, 1);
+  if (!st.ok()) return st.rc;
+  k_register_keys<<<1, BN_WAVE, 0, c->stream>>>(d_pk, 1, flags & FLAG_REJECT_IDENTITY, c->gk_lines, c->gk_st, c->gk_inf, c->gk_xy);
+  HIP_TRY(hipGetLastError());
+  if (const int rc = st.finish()) return rc;
+  if (status) *status = key_st;
+  c->gk_set = key_st == ST_OK;
+  return 0;
+}
 int bn254_batch_verify_keyed_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t* d_off, const uint8_t* d_sigs, const uint32_t* d_key_idx,
                                     size_t n, uint32_t flags, uint8_t* d_status, void* stream) {
   MsgsLenScope msgs_len_scope(c);
@@ -472,7 +496,7 @@ int bn254_batch_verify_keyed_device(bn254_ctx* c, const uint8_t* d_msgs, const u
   PROF_MARK(1);
   if ((rc = launch_hash_rounds(c, s, d_msgs, d_off, n, PL_P2X, BY_P2_INF, nullptr))) return rc;
   PROF_MARK(2);
-  if ((rc = launch_keyed_miller_fe(c, s, n, d_key_idx, d_status))) return rc;
+  if ((rc = launch_keyed_miller_fe(c, s, n, d_key_idx, d_status, ctx_key_table(c), c->key_xy))) return rc;
   PROF_MARK(4);
   prof_done(c, EV_DECODE_FIRST);
   HIP_TRY(hipGetLastError());

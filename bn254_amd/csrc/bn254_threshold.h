@@ -14,6 +14,8 @@
 //     collect's two layouts: a lane walks a short segment in order, the lanes of a wave take the terms l, l + 64, .. of a long one and a
 //     tree of six levels folds their partial sums (msm_lane_sum, msm_wave_partial, msm_tree_level over cl_tree_level).  Statuses follow
 //     bn254_batch_g1_sum: the first non-zero decode status in segment order wins — in the wave layout the lowest index, carried beside it.
+//   * OPTIMISTIC (bn254_batch_threshold_combine_keyed_optimistic): candidate rows, the settle that picks S' before any pairing, and the gates
+//     of the two interpolations (tho_*, below rank and select).
 // Include after bn254_collect.h and bn254_fr.h.
 #pragma once
 
@@ -61,6 +63,50 @@ BN_DEV bool th_take(const ClShares& in, uint64_t s, size_t t, size_t n, const ui
   const uint32_t key = in.key[s];
   if (!th_bit(used + t * bm_words, bm_words, key)) return false;
   return cl_claim(claim + t * bm_words, bm_words, key);
+}
+
+// ---- the optimistic call (bn254_batch_threshold_combine_keyed_optimistic[_device]) ----------------------------------------------------------------
+// Interpolate first, verify the result once per tuple under the GROUP key.  The flags and the verdicts are the optimistic collect's
+// (bn254_collect.h: CLO_FINAL / CLO_CHECK / CLO_EXACT, clo_goes_exact, clo_queued), so its queue and its counters serve this call as they stand.
+//   * CANDIDATE ROW: a share whose pre-check status is 0 claims its key's bit in the tuple's output row; a refused claim is a second
+//     candidate of one key and raises the tuple's duplicate byte (tho_candidate).  No sum: the row is all the first pass needs.
+//   * SETTLE: a tuple whose status is non-zero already is final (empty row, identity, count 0); one with a duplicate or with fewer than t
+//     candidates goes the exact way; else the row is cut down to S' = its t lowest bits and the tuple will be checked (tho_settle).
+//   * SECOND PASS, for the tuples that go the exact way only: their rows are zeroed, their candidates verified, the status-0 shares claim
+//     again (tho_reclaims) and th_settle runs as in the exact call (tho_resettle).  The byte it returns gates the second interpolation:
+//     0 = this tuple combines now, anything else = its outputs stand (a tuple that passed, a final one, or one that just failed).
+BN_DEV void tho_candidate(uint32_t* row, size_t bm_words, uint32_t key, uint8_t* dup) {
+  if (!cl_claim(row, bm_words, key)) *dup = 1;
+}
+// one tuple behind the candidate rows: its flag; the row becomes S' iff the flag is CLO_CHECK.  sig64 is zeroed unless the tuple will be
+// checked (the interpolation then writes it), so the tuple check decodes no byte the call has not written.  count = |C|, 0 for a final tuple.
+BN_DEV uint8_t tho_settle(uint32_t* row, size_t bm_words, uint32_t t, uint8_t tuple_st, uint8_t dup, uint8_t* sig64, uint32_t& count) {
+  uint8_t flag = CLO_FINAL;
+  count = 0;
+  if (tuple_st == ST_OK) {
+    count = th_row_count(row, bm_words);
+    flag = (dup || count < t) ? CLO_EXACT : CLO_CHECK;
+  }
+  if (flag == CLO_CHECK) { th_trim(row, bm_words, t); return flag; }
+  uint32_t* w = (uint32_t*)sig64;
+  for (int k = 0; k < 16; ++k) w[k] = 0;
+  return flag;
+}
+// the first interpolation's gate (MSM_SEG_MASKED below: any non-zero byte masks): only the tuples that will be checked
+BN_DEV uint8_t tho_gate(uint8_t flag) { return flag == CLO_CHECK ? (uint8_t)ST_OK : (uint8_t)0xFF; }
+// does share s — status share_st behind the exact verify of the queue, of tuple t (n: of nobody) — claim its key in the second pass
+BN_DEV bool tho_reclaims(uint8_t share_st, size_t t, size_t n, const uint8_t* flag, const uint8_t* verdict) {
+  return clo_queued(share_st, t, n, flag, verdict);
+}
+// one tuple behind the second claim pass: a tuple that goes the exact way is settled as the exact call settles it (row V in; status, row,
+// signature and count out); every other tuple is left alone.  Returns the second interpolation's gate.
+BN_DEV uint8_t tho_resettle(uint32_t* row, size_t bm_words, uint32_t t, uint8_t flag, uint8_t verdict, uint8_t& tuple_st, uint8_t* sig64, uint32_t& count,
+                            bool& mine) {
+  mine = clo_goes_exact(flag, verdict);
+  if (!mine) return 0xFF;
+  tuple_st = ST_OK;                                    // only an accepted tuple with hash status 0 is ever flagged CLO_CHECK or CLO_EXACT
+  count = th_settle(row, bm_words, t, tuple_st, sig64);
+  return tuple_st == ST_OK ? (uint8_t)ST_OK : (uint8_t)0xFF;
 }
 
 // ---- Lagrange coefficients at zero -------------------------------------------------------------------------------------------------------------

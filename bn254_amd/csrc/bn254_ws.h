@@ -286,6 +286,9 @@ __attribute__((visibility("hidden"))) int bn254_pair_bitmap_sum(const uint32_t* 
 #define MERGE_WAVE_MIN_PARTS_DEFAULT 16            // BN254_OPT_MERGE_WAVE_MIN_PARTS (bn254_merge.hip): tuples with at least this many partials are merged by a
                                                    //     wave each.  Swept over 4 .. 256 partials at rows of 8 and of 128 words: the layouts
                                                    //     cross between 16 and 32 partials at 8 words, at 8 at 128 words; 16 has the smallest worst loss (0.15 ms)
+#define THRESHOLD_OPT_MIN_SHARES_DEFAULT 513      // BN254_OPT_THRESHOLD_OPT_MIN_SHARES: bn254_batch_threshold_combine_keyed_optimistic checks results from this many
+                                                   //     shares on (the smallest measured size, 3 x 171 shares: 3.81 ms against 4.03, beyond the exact call's spread; no
+                                                   //     size measured loses with every share valid, nothing below 513 was measured)
 #define MERGE_OPT_MIN_PARTS_DEFAULT 64             // BN254_OPT_MERGE_OPT_MIN_PARTS: bn254_batch_merge_keyed_bitmap_optimistic checks sums from this many partials
                                                    //     on (the smallest measured size from which it wins beyond the spread, tuples of 16 partials: 4 x 16 wins
                                                    //     by 3 %, 2 x 16 and 1 x 16 tie; nothing measured between 32 and 64)

@@ -63,6 +63,8 @@ OPT_MERGE_WAVE_MIN_PARTS = 43       # merge_keyed_bitmap: tuples with at least t
 MERGE_WAVE_MIN_PARTS_DEFAULT = 16   # ... as bn254_ws.h has it
 OPT_MERGE_OPT_MIN_PARTS = 45        # merge_keyed_bitmap_optimistic: the exact merge below this many partials (default 64, measured: DESIGN.md §10i); 0 = no lower bound
 MERGE_OPT_MIN_PARTS_DEFAULT = 64    # ... as bn254_ws.h has it
+OPT_THRESHOLD_OPT_MIN_SHARES = 46   # threshold_combine_keyed_optimistic: the exact threshold call below this many shares (default 513, measured: DESIGN.md §10l); 0 = no lower bound
+THRESHOLD_OPT_MIN_SHARES_DEFAULT = 513    # ... as bn254_ws.h has it
 OPT_COLLECT_WAVE_MIN_SHARES = 37   # collect_keyed_bitmap: tuples with at least this many shares are summed by a wave each (default 16; swept at three shapes only)
 
 
@@ -241,6 +243,14 @@ class Engine:
         per-tuple minimum), shares verified one by one; all 0 when the call took the exact route as a whole"""
         o = (ctypes.c_uint64 * 4)()
         _check("bn254_debug_collect_opt_last", self._lib.bn254_debug_collect_opt_last(self._h, o))
+        return dict(zip(("checked", "passed", "exact_tuples", "exact_shares"), (int(x) for x in o)))
+
+    def debug_threshold_opt_last(self):
+        """what the last batch_threshold_combine_keyed_optimistic[_device] did, counted on the device: dict(checked, passed, exact_tuples,
+        exact_shares) — tuples checked under the group key, those that passed, tuples sent the exact way (failed, a duplicate, fewer
+        candidates than the threshold), shares verified one by one; all 0 after any call that did not take the route"""
+        o = (ctypes.c_uint64 * 4)()
+        _check("bn254_debug_threshold_opt_last", self._lib.bn254_debug_threshold_opt_last(self._h, o))
         return dict(zip(("checked", "passed", "exact_tuples", "exact_shares"), (int(x) for x in o)))
 
     def debug_merge_opt_last(self):
@@ -581,9 +591,21 @@ class Engine:
         n = len(pks) // G2_BYTES
         assert len(pks) == n * G2_BYTES
         st = ctypes.create_string_buffer(max(n, 1))
+        self.group_key_set = False
         _check("bn254_ctx_register_keys", self._lib.bn254_ctx_register_keys(self._h, bytes(pks), n, flags, st))
         self.n_registered_keys = n
         return st.raw[:n]
+
+    def set_group_key(self, group_pk, flags=0):
+        """the group key f(0) * G2 of batch_threshold_combine_keyed_optimistic (include/bn254_hip.h: bn254_ctx_set_group_key): 128 bytes, or
+        None to forget it.  Returns the key's decode status (registration's codes); a non-zero status leaves no group key set.  A
+        registration (register_keys, register_keys_pop) forgets the group key."""
+        assert group_pk is None or len(group_pk) == G2_BYTES
+        st = ctypes.create_string_buffer(1)
+        self.group_key_set = False
+        _check("bn254_ctx_set_group_key", self._lib.bn254_ctx_set_group_key(self._h, None if group_pk is None else bytes(group_pk), flags, st))
+        self.group_key_set = group_pk is not None and st.raw[0] == 0
+        return st.raw[0]
 
     def register_keys_pop(self, pks, pops, flags=0):
         """register_keys with every key's proof of possession checked (include/bn254_hip.h: bn254_ctx_register_keys_pop): pops = one 64-byte
@@ -594,6 +616,7 @@ class Engine:
         assert len(pks) == n * G2_BYTES and len(pops) == n * G1_BYTES
         st = ctypes.create_string_buffer(max(n, 1))
         self.n_registered_keys = 0
+        self.group_key_set = False
         _check("bn254_ctx_register_keys_pop", self._lib.bn254_ctx_register_keys_pop(self._h, bytes(pks), bytes(pops), n, flags, st))
         self.n_registered_keys = n
         return st.raw[:n]
@@ -693,6 +716,24 @@ class Engine:
         _check("bn254_batch_threshold_combine_keyed",
                self._lib.bn254_batch_threshold_combine_keyed(self._h, *args, int(threshold), flags, share_st, tuple_st, sigs, bits, counts))
         return share_st.raw[:n_shares], tuple_st.raw[:n], sigs.raw[:n * G1_BYTES], list(bits)[:n * bm_words], list(counts)[:n]
+
+    def batch_threshold_combine_keyed_optimistic(self, messages, shares, share_keys, sizes, bm_words, threshold, flags=0):
+        """batch_threshold_combine_keyed by interpolating first and verifying each tuple's result once under the group key (set_group_key;
+        include/bn254_hip.h: bn254_batch_threshold_combine_keyed_optimistic).  Same arguments, same five results; in a tuple that passes its
+        check the shares outside the kept keys read their pre-check status and the count is of candidates."""
+        n, n_shares = len(messages), len(share_keys)
+        args, (share_st, tuple_st, sigs, bits, counts) = Engine._collect_buffers(messages, shares, share_keys, sizes, bm_words)
+        assert 0 < int(threshold) < 1 << 32, "threshold must be at least 1"
+        _check("bn254_batch_threshold_combine_keyed_optimistic",
+               self._lib.bn254_batch_threshold_combine_keyed_optimistic(self._h, *args, int(threshold), flags, share_st, tuple_st, sigs, bits, counts))
+        return share_st.raw[:n_shares], tuple_st.raw[:n], sigs.raw[:n * G1_BYTES], list(bits)[:n * bm_words], list(counts)[:n]
+
+    def batch_threshold_combine_keyed_optimistic_device(self, d_msgs, d_msg_off, d_shares, d_share_key, d_share_off, n_shares, n, bm_words, threshold,
+                                                        d_share_status, d_tuple_status, d_group_sigs, d_used_bits, d_n_valid=None, flags=0, stream=None):
+        _check("bn254_batch_threshold_combine_keyed_optimistic_device",
+               self._lib.bn254_batch_threshold_combine_keyed_optimistic_device(self._h, d_msgs, d_msg_off, d_shares, d_share_key, d_share_off, n_shares, n,
+                                                                               bm_words, threshold, flags, d_share_status, d_tuple_status, d_group_sigs,
+                                                                               d_used_bits, d_n_valid, stream))
 
     def batch_threshold_combine_keyed_device(self, d_msgs, d_msg_off, d_shares, d_share_key, d_share_off, n_shares, n, bm_words, threshold,
                                              d_share_status, d_tuple_status, d_group_sigs, d_used_bits, d_n_valid=None, flags=0, stream=None):

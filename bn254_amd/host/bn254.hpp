@@ -425,6 +425,36 @@ struct ECDSA {
   // that the registered keys lie on one polynomial of degree threshold - 1: that is the dealer's or the DKG's job.
   static std::vector<KeyedAggregateResult> batch_threshold_combine_keyed(const std::vector<ShareItem>& items, size_t n_keys, uint32_t threshold,
                                                                          Engine& e = Engine::default_engine()) {
+    return threshold_batch(items, n_keys, threshold, false, e);
+  }
+  // THE GROUP KEY f(0) * G2 of the registered dealing, for the optimistic calls below (include/bn254_hip.h: bn254_ctx_set_group_key); throws
+  // the key's decode Error, and then no group key is set.  forget_group_key drops it, as register_keys / register_keys_proven do: a new key
+  // set is a new dealing.  The library does not check that the registered keys interpolate to this key.
+  static void register_group_key(const PublicKey& group_key, Engine& e = Engine::default_engine()) {
+    uint8_t st = 0;
+    check_rc("bn254_ctx_set_group_key", bn254_ctx_set_group_key(e.raw(), group_key.raw.data(), 0, &st));
+    check_status(st);
+  }
+  static void forget_group_key(Engine& e = Engine::default_engine()) {
+    check_rc("bn254_ctx_set_group_key", bn254_ctx_set_group_key(e.raw(), nullptr, 0, nullptr));
+  }
+  // batch_threshold_combine_keyed by interpolating the `threshold` lowest keys with a well-formed share first and verifying the RESULT once
+  // under the group key (include/bn254_hip.h: bn254_batch_threshold_combine_keyed_optimistic).  A result that passes is the group signature;
+  // the shares outside the keys used were then not verified (status 0 if well-formed and naming a registered key), and shares whose errors
+  // cancel under the coefficients read 0.  A result that fails sends the item through the exact call: the same result.  Without a group
+  // key the call is refused (bad argument).
+  static std::vector<KeyedAggregateResult> batch_threshold_combine_keyed_optimistic(const std::vector<ShareItem>& items, size_t n_keys, uint32_t threshold,
+                                                                                    Engine& e = Engine::default_engine()) {
+    return threshold_batch(items, n_keys, threshold, true, e);
+  }
+  static KeyedAggregateResult threshold_combine_keyed_optimistic(const std::vector<uint8_t>& message, const std::vector<Signature>& signatures,
+                                                                 const std::vector<uint32_t>& key_indices, size_t n_keys, uint32_t threshold,
+                                                                 Engine& e = Engine::default_engine()) {
+    KeyedAggregateResult r = threshold_batch({ShareItem{message, signatures, key_indices}}, n_keys, threshold, true, e)[0];
+    check_status(r.status);
+    return r;
+  }
+  static std::vector<KeyedAggregateResult> threshold_batch(const std::vector<ShareItem>& items, size_t n_keys, uint32_t threshold, bool optimistic, Engine& e) {
     if (threshold == 0) throw Error(ErrorKind::InvalidLength);
     const size_t n = items.size(), bm_words = (n_keys + 31) / 32 ? (n_keys + 31) / 32 : 1;
     std::vector<uint64_t> off(n + 1, 0), share_off(n + 1, 0);
@@ -444,9 +474,14 @@ struct ECDSA {
     std::vector<uint32_t> bits(n * bm_words + 1, 0);
     shares.resize(shares.size() + 1);
     keys.resize(keys.size() + 1);
-    check_rc("bn254_batch_threshold_combine_keyed",
-             bn254_batch_threshold_combine_keyed(e.raw(), msgs.data(), off.data(), shares.data(), keys.data(), share_off.data(), share_off[n], n, bm_words,
-                                                 threshold, 0, share_st.data(), tuple_st.data(), group.data(), bits.data(), nullptr));
+    if (optimistic)
+      check_rc("bn254_batch_threshold_combine_keyed_optimistic",
+               bn254_batch_threshold_combine_keyed_optimistic(e.raw(), msgs.data(), off.data(), shares.data(), keys.data(), share_off.data(), share_off[n], n,
+                                                              bm_words, threshold, 0, share_st.data(), tuple_st.data(), group.data(), bits.data(), nullptr));
+    else
+      check_rc("bn254_batch_threshold_combine_keyed",
+               bn254_batch_threshold_combine_keyed(e.raw(), msgs.data(), off.data(), shares.data(), keys.data(), share_off.data(), share_off[n], n, bm_words,
+                                                   threshold, 0, share_st.data(), tuple_st.data(), group.data(), bits.data(), nullptr));
     std::vector<KeyedAggregateResult> out(n);
     for (size_t i = 0; i < n; ++i) {
       out[i].status = tuple_st[i];

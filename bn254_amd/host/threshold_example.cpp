@@ -47,6 +47,28 @@ int main() {
       if (e.kind != bn254::ErrorKind::VerificationFailed) return 7;
     }
     printf("threshold signatures: ok\n");
+    // the optimistic form: interpolate first, verify the result once under the group key.  (Option 46 = 0 sends even this tiny call down
+    // the optimistic route; by default a call this small takes the exact one, with the same bytes.)
+    bn254::Engine& eng = bn254::Engine::default_engine();
+    eng.set_option(BN254_OPT_THRESHOLD_OPT_MIN_SHARES, 0);
+    try {
+      bn254::ECDSA::threshold_combine_keyed_optimistic(m, {s[2], s[0]}, {2, 0}, 3, 2);
+      printf("ERROR: accepted without a group key\n");
+      return 8;
+    } catch (const std::runtime_error&) {}
+    bn254::ECDSA::register_group_key(group_key);
+    auto o02 = bn254::ECDSA::threshold_combine_keyed_optimistic(m, {s[2], s[0]}, {2, 0}, 3, 2);
+    auto oall = bn254::ECDSA::threshold_combine_keyed_optimistic(m, {s[0], s[1], s[2]}, {0, 1, 2}, 3, 2);
+    uint64_t did[4];
+    if (bn254_debug_threshold_opt_last(eng.raw(), did) != 0 || did[0] != 1 || did[1] != 1 || did[2] != 0) { printf("ERROR: the route did not run\n"); return 9; }
+    if (o02.signature.raw != r02.signature.raw || oall.signature.raw != r02.signature.raw || oall.signer_indices != std::vector<uint32_t>{0, 1}) {
+      printf("ERROR: optimistic result\n");
+      return 10;
+    }
+    // the bad share again: the result does not verify under the group key, so the item goes the exact way — the exact call's answer
+    auto obad = bn254::ECDSA::batch_threshold_combine_keyed_optimistic({{m, {s[0], s[0]}, {0, 1}}}, 3, 2)[0];
+    if (obad.status != 9 || obad.statuses != bad.statuses || obad.signer_indices != bad.signer_indices) { printf("ERROR: optimistic bad share\n"); return 11; }
+    printf("optimistic: ok\n");
     return 0;
   } catch (const std::exception& e) { printf("failed: %s\n", e.what()); return 1; }
 }

@@ -856,8 +856,8 @@ int bn254_ctx_register_keys_pop(bn254_ctx *ctx, const uint8_t *pks /* n_keys*128
  * same signature bytes.  Unmeasured: other thresholds, invalid shares, more than 256 keys, the host form.
  * Which call when: this one whenever the shares are in hand and the share keys registered; bn254_batch_collect_keyed_bitmap for
  * multi-signatures (no interpolation); bn254_batch_g1_msm for weighted sums of the caller's own points.  DESIGN.md section 10k.
- * Out of scope: an optimistic form that interpolates first and verifies the result once, a randomised form, the multi-GPU layer,
- * compressed shares, key dealing (Shamir sharing, DKG) in the C ABI. */
+ * Out of scope: a randomised form, the multi-GPU layer, compressed shares, key dealing (Shamir sharing, DKG) in the C ABI.  No longer out
+ * of scope: an optimistic form that interpolates first and verifies the result once — bn254_batch_threshold_combine_keyed_optimistic below. */
 int bn254_batch_threshold_combine_keyed(bn254_ctx *ctx, const uint8_t *msgs, const uint64_t *msg_off /* n+1 */,
                                         const uint8_t *shares /* n_shares*64 */, const uint32_t *share_key /* n_shares */,
                                         const uint64_t *share_off /* n+1 */, size_t n_shares, size_t n, size_t bm_words, uint32_t threshold,
@@ -868,6 +868,78 @@ int bn254_batch_threshold_combine_keyed_device(bn254_ctx *ctx, const uint8_t *d_
                                                size_t bm_words, uint32_t threshold, uint32_t flags, uint8_t *d_share_status,
                                                uint8_t *d_tuple_status, uint8_t *d_group_sigs, uint32_t *d_used_bits, uint32_t *d_n_valid,
                                                void *stream);
+
+/* THE GROUP KEY of the optimistic threshold call below: f(0) * G2::one(), the key the consumer of a group signature checks it under.
+ * group_pk = 128 bytes, decoded and tabulated exactly as one key of bn254_ctx_register_keys is (same flags, same status codes; the
+ * identity, 128 zero bytes, is a legal group key as it is a legal registered key), into a one-entry table of its own; NULL forgets the key.
+ * A non-zero decode status is reported in *status (may be NULL) and leaves NO group key set; the call itself returns 0.  Quiesces the
+ * context first, like a registration.  LIFETIME: bn254_ctx_register_keys and bn254_ctx_register_keys_pop forget the group key — a new key
+ * set is a new dealing.  The library does NOT check that the registered keys interpolate to this key: a key that does not belong to the set
+ * sends every tuple of the optimistic call the exact way (slower, the exact call's bytes) and can never make a wrong signature pass,
+ * because what passes has verified under the key the caller named. */
+int bn254_ctx_set_group_key(bn254_ctx *ctx, const uint8_t *group_pk /* 128, or NULL: forget it */, uint32_t flags, uint8_t *status /* 1, or NULL */);
+
+/* OPTIMISTIC THRESHOLD COMBINE: interpolate first, verify the result once per tuple under the group key.  The interpolated signature is
+ * unique: if it verifies under f(0) * G2::one() it is THE group signature whatever the individual shares were, so one pairing check per
+ * tuple proves the output — and proves exactly what the consumer will check.  (The optimistic collect's check of the plain sum cannot be
+ * reused: errors that cancel in the sum of the shares do not cancel under the coefficients.)
+ * Arguments, argument checks, alignment rules, the range rule, the fill of share_status with 2, BN254_OPT_MAX_CHUNK slicing (tuples in pieces
+ * for hash and tuple check, shares in pieces for the queue), bn254_ctx_expect_msgs_len and threshold == 0 are exactly those of
+ * bn254_batch_threshold_combine_keyed[_device]; in addition a context with no group key set returns BN254_E_BAD_ARGUMENT.  The _device form only
+ * enqueues, on the caller's stream, and never synchronises with the host; one call may be in flight per context.
+ * Per accepted tuple i (range rule passed, hash status 0; a refused tuple gets the exact call's bytes):
+ *   1. every share gets the checks short of the pairing (decode, key index, registration status: rules 1-3 of the optimistic collect); a
+ *      share whose status is 0 is a CANDIDATE; C_i = the keys with a candidate.
+ *   2. a tuple in which a key has two candidates, or with |C_i| < threshold, goes the exact way at once.
+ *   3. else S'_i = the `threshold` lowest keys of C_i, and the group signature is sum over j in S'_i of lambda_j(S'_i) sigma_j, by the exact
+ *      call's coefficient, term and sum kernels under a mask.
+ *   4. the tuple check: e(H(m_i), GPK) * e(group_sig_i, -G2) == 1, the signature decoded with flags 0 (the identity is legitimate), by the
+ *      keyed verify's routing (lane machine, expanded key on the small-batch kernels, or lane pairs on the group key's line table).
+ *   5. PASS: tuple_status 0 and group_sigs[i] as computed, used_bits row = S'_i, n_valid[i] = |C_i|, the share statuses the pre-check's.
+ *   6. FAIL, or flagged in 2: the tuple's candidates are verified one by one on the device through a queue, its row is rebuilt from the
+ *      verified statuses, and rank-and-select, the coefficients and the weighted sum run again for these tuples only (a gate masks the
+ *      others; a wave with nothing to take leaves at once).  All five outputs of such a tuple are byte for byte the exact call's.
+ * Everything is enqueued whether or not a tuple fails: the host never learns.  No seed, no randomness.
+ * WHAT IS PROVED: for a tuple with tuple_status 0, bn254_batch_verify of (m_i, group_sigs[i], GPK) returns 0 — the tuple check proved it, or
+ *   the tuple went the exact way and the exact call's own guarantee applies.
+ * IDENTITY A: whenever every share of S'_i is individually valid, tuple_status, group_sigs and the used_bits row equal the exact call's (then
+ *   V contains S' and lies in C, so the lowest t of V are S').
+ * IDENTITY B: a tuple that goes the exact way equals the exact call in all five outputs.
+ * DEVIATION 1: in a passing tuple the shares outside S'_i were not verified: they read their pre-check status and n_valid counts candidates.
+ *   A caller who needs per-share verdicts takes the exact call.
+ * DEVIATION 2: shares of S'_i whose errors cancel under the coefficients (sigma_a + lambda_b D and sigma_b - lambda_a D) read 0 in a passing
+ *   tuple; the group signature is still the valid one.  The exact call would have dropped both keys.
+ * WHOLE-CALL ROUTING: the call IS the exact call (same bytes, by identity B) when n_shares < BN254_OPT_THRESHOLD_OPT_MIN_SHARES, when no keys
+ *   are registered, or with BN254_OPT_PAIR_LANES = 0.
+ * Under bn254_ctx_set_profiling: ms[0] front end and candidate rows, ms[1] coefficients and weighted sum, ms[2] the tuples' Miller loop and
+ * final exponentiation, ms[3] exact fallback and re-interpolation (a call in several pieces: the last piece's ms[1] boundary).
+ * Measured on an MI355X (tools/threshold_throughput.py --optimistic, profiles/threshold_optimistic.jsonl; 256 dealt keys, threshold = two
+ * thirds of a tuple's keys, the true group key set; _device forms under HIP events, the two calls alternating in one process, median [min,
+ * max] of 7; optimistic against exact, ms).  Every share valid: 256 tuples x 171 shares 4.46 [4.43, 4.49] against 11.50 [11.45, 11.59];
+ * 1 024 x 171 11.38 [11.32, 11.40] against 34.59 [34.45, 34.70]; 2 048 x 171 20.33 [20.16, 20.40] against 62.67 [62.39, 63.15]; 4 096 x 11 5.53
+ * [5.49, 5.55] against 11.29 [11.19, 11.44]; 64 x 171 3.84 against 7.49; 36 x 171 3.84 against 5.32; 18 x 171 3.85 against 5.22; 9 x 171 3.87
+ * [3.82, 4.06] against 4.73 [4.68, 4.83]; 3 x 171 3.81 [3.78, 4.00] against 4.03 [3.97, 4.12].  Stages of one profiled call at 256 x 171: front
+ * end 0.20, coefficients and weighted sum 3.22, tuple check 0.94, fallback 0.10; at 2 048 x 171: 0.26, 18.11, 1.66, 0.16 — the weighted sum
+ * (a 128-step ladder per kept share) is what is left, and it grows with the shares where the exact call's pairings grow three times as fast.
+ * When something fails: ONE failing tuple costs the call one pass of the queue's lane-pair kernels, about 7.4 ms whatever the queue's length —
+ * 256 x 171 11.76 [11.74, 11.87] against 12.14 [12.03, 12.18], 2 048 x 171 27.59 [27.46, 28.24] against 64.03 [63.74, 64.50]; 1 % wrong shares
+ * at 1 024 x 171 (708 of 1 024 tuples go exact) 37.12 [36.85, 37.63] against 34.74 [34.59, 35.12]: it LOSES; the WRONG group key at 256 x 171
+ * (every tuple goes exact: the cost of a misconfiguration) 15.53 [15.46, 15.59] against 11.52 [11.39, 11.59]; one tuple of 4 096 shares over
+ * 256 keys (every key several times: a duplicate, exact at once) 9.53 [9.39, 9.62] against 6.27 [6.14, 6.38]: it LOSES.  So: this call when
+ * shares are almost all valid and a tuple names each key once; the exact call when many tuples hold a bad share among their lowest keys, when
+ * tuples repeat keys, or when per-share verdicts matter.  Unmeasured: calls below 513 shares, other thresholds, more than 256 keys, the host form.
+ * DESIGN.md section 10l. */
+int bn254_batch_threshold_combine_keyed_optimistic(bn254_ctx *ctx, const uint8_t *msgs, const uint64_t *msg_off /* n+1 */,
+                                                   const uint8_t *shares /* n_shares*64 */, const uint32_t *share_key /* n_shares */,
+                                                   const uint64_t *share_off /* n+1 */, size_t n_shares, size_t n, size_t bm_words,
+                                                   uint32_t threshold, uint32_t flags, uint8_t *share_status /* n_shares */,
+                                                   uint8_t *tuple_status /* n */, uint8_t *group_sigs /* n*64 */,
+                                                   uint32_t *used_bits /* n*bm_words */, uint32_t *n_valid /* n, or NULL */);
+int bn254_batch_threshold_combine_keyed_optimistic_device(bn254_ctx *ctx, const uint8_t *d_msgs, const uint64_t *d_msg_off, const uint8_t *d_shares,
+                                                          const uint32_t *d_share_key, const uint64_t *d_share_off, size_t n_shares, size_t n,
+                                                          size_t bm_words, uint32_t threshold, uint32_t flags, uint8_t *d_share_status,
+                                                          uint8_t *d_tuple_status, uint8_t *d_group_sigs, uint32_t *d_used_bits,
+                                                          uint32_t *d_n_valid, void *stream);
 
 /* compressed wire formats (src/utils.rs:84-104, :130-158): out = uncompressed point, status as
  * bn::G1::from_compressed / bn::G2::from_compressed report through src/types.rs:91-93, :233-237, checked in the order
@@ -985,6 +1057,11 @@ int bn254_ctx_set_profiling(bn254_ctx *ctx, int enabled);
                                            valid (tuples of 16 partials over 256 keys: 4 x 16 1.81 ms against 1.86; 2 x 16 and 1 x 16 tie;
                                            nothing measured between 32 and 64 partials).  A call whose tuples hold overlapping candidates
                                            loses at any size, which a count of partials cannot see; 0 = no lower bound */
+#define BN254_OPT_THRESHOLD_OPT_MIN_SHARES 46 /* bn254_batch_threshold_combine_keyed_optimistic: calls with fewer shares take the exact call (same
+                                                bytes).  Default 513, the smallest measured size (3 tuples x 171 shares over 256 keys, every share valid: 3.81 ms
+                                                [3.78, 4.00] against 4.03 [3.97, 4.12] — it wins by more than the exact call's own spread); no
+                                                measured size loses with every share valid, and nothing below 513 shares was measured, so
+                                                smaller calls take the exact call; 0 = no lower bound */
 int bn254_ctx_set_option(bn254_ctx *ctx, int option, int value);
 /* per-kernel times of the last verify-shaped call with profiling on (HIP events on the call's stream):
  * ms[0] decode, ms[1] hash-to-G1, ms[2] Miller loop, ms[3] final exponentiation.  The host-pointer bn254_batch_verify runs
@@ -1219,6 +1296,10 @@ int bn254_debug_collect_rand_last(bn254_ctx *ctx, uint64_t out[4]);
  * {tuples checked optimistically, tuples that passed, tuples sent to the exact route (failed, a duplicate, or below the per-tuple minimum),
  * shares verified exactly}; all 0 when the call as a whole took the exact route.  Synchronises the device. */
 int bn254_debug_collect_opt_last(bn254_ctx *ctx, uint64_t out[4]);
+/* what the last bn254_batch_threshold_combine_keyed_optimistic[_device] did, counted by the call's own kernels: out = {tuples checked under the
+ * group key, tuples that passed, tuples sent the exact way (failed, a duplicate, or fewer candidates than the threshold), shares verified
+ * exactly}; all 0 ("did not run") after any call that did not take the optimistic route.  Synchronises the device. */
+int bn254_debug_threshold_opt_last(bn254_ctx *ctx, uint64_t out[4]);
 /* what the last bn254_batch_merge_keyed_bitmap_optimistic[_device] did, counted by the call's own kernels and summed over its slices: out =
  * {tuples checked optimistically, tuples that passed, tuples sent the exact way (failed, or an overlap), partials verified exactly}; all 0
  * ("did not run") after any call that did not take the route — the exact merge and the collect calls included.  Synchronises the device. */

@@ -14,7 +14,16 @@ final exponentiation) — ONE call per leg, not a median, so `interpolation_ms_b
 the whole-call medians, is the figure to quote.  The keys are independent (no dealing): the work is the same, the outputs are compared with route (b)'s bytes.
 --msm adds bn254_batch_g1_msm against bn254_batch_g1_mul + bn254_batch_g1_sum (host forms, wall clock, staging included on both sides) and
 the _device form (events) at `--msm-terms` terms in segments of 16 and in one segment.  One JSON line per shape (default stdout).
-    python tools/threshold_throughput.py [out.jsonl] [--reps R] [--reps-b R] [--msm] [--msm-terms M] [--keys K] [--note TEXT] [shape ...]   shape = n:k"""
+--optimistic measures bn254_batch_threshold_combine_keyed_optimistic_device against the exact call instead, alternating in one process: the
+keys are DEALT (per shape one polynomial of degree t - 1 over the K keys, key j = f(j + 1) * G2) and the true group key f(0) * G2 is set, the
+optimistic route forced (option 46 = 0) so that what is measured is the route and not the default's choice.  --fail chooses what goes wrong:
+none; tuple (every share of the lowest keys of ONE tuple replaced by another point of the curve); percent (1 % of the shares, drawn at
+random); key (the group key of another polynomial: every tuple goes the exact way — the cost of a misconfiguration).  The line carries both
+calls' medians with min and max, what the route did (bn254_debug_threshold_opt_last), whether the three outputs of identity A agree with the
+exact call's, and the four stage times of ONE profiled optimistic call (front end + candidate rows, coefficients + weighted sum, the tuples'
+Miller loop + final exponentiation, exact fallback + re-interpolation).
+    python tools/threshold_throughput.py [out.jsonl] [--reps R] [--reps-b R] [--msm] [--msm-terms M] [--keys K] [--note TEXT]
+                                         [--optimistic [--fail none|tuple|percent|key]] [shape ...]   shape = n:k"""
 import argparse
 import ctypes
 import hashlib
@@ -116,6 +125,84 @@ def msm_rows(eng, lib, h, ts, stream, box, m, reps, out):
         print(json.dumps(row), file=out, flush=True)
 
 
+OPT_THRESHOLD_OPT_MIN_SHARES = 46
+
+
+def optimistic_rows(eng, lib, h, ts, stream, box, shapes, n_keys, reps, fail, out):
+    """--optimistic: one line per shape, the optimistic call against the exact call on dealt keys under the true (or, --fail key, a wrong) group key"""
+    rng = np.random.default_rng(20261020)
+    bm_words = (n_keys + 31) // 32
+    g1, st = eng.batch_g1_mul(None, (1).to_bytes(32, "big"), 1)
+    for n, k in shapes:
+        n_shares = n * k
+        t = max(1, 2 * min(k, n_keys) // 3)
+        coeffs = [int.from_bytes(sk_bytes(7000 + e), "big") % R for e in range(t)]
+        sks = [sum(c * pow(x, e, R) for e, c in enumerate(coeffs)) % R or 1 for x in range(1, n_keys + 1)]
+        pool, st = eng.batch_g2_mul(None, b"".join(s.to_bytes(32, "big") for s in sks), n_keys, reduce_scalar=True)
+        assert st == bytes(n_keys) and eng.register_keys(pool) == bytes(n_keys)
+        f0 = coeffs[0] if fail != "key" else (coeffs[0] + 1) % R
+        gk, st = eng.batch_g2_mul(None, f0.to_bytes(32, "big"), 1, reduce_scalar=True)
+        st_gk = ctypes.create_string_buffer(1)
+        _check(lib.bn254_ctx_set_group_key(h, gk, 0, st_gk))
+        assert st_gk.raw == b"\0"
+        keys = np.concatenate([np.resize(rng.permutation(n_keys), k) for _ in range(n)]).astype(np.uint32)
+        msgs = [hashlib.sha256(b"threshold/opt/%d/%d/%d" % (n, k, i)).digest() for i in range(n)]
+        shares, st = eng.batch_sign([msgs[s // k] for s in range(n_shares)], b"".join(sks[j].to_bytes(32, "big") for j in keys))
+        assert st == bytes(n_shares)
+        bad = []
+        if fail == "tuple":                              # one tuple, the share of its lowest key: the interpolation takes it, the check fails
+            i = n // 2
+            bad = [i * k + int(np.argmin(keys[i * k:(i + 1) * k]))]
+        elif fail == "percent":
+            bad = sorted(int(s) for s in rng.choice(n_shares, max(1, n_shares // 100), replace=False))
+        if bad:
+            buf = bytearray(shares)
+            wrong, st = eng.batch_g1_add(b"".join(shares[64 * s:64 * s + 64] for s in bad), g1 * len(bad), len(bad))
+            assert st == bytes(len(bad))
+            for q, s in enumerate(bad):
+                buf[64 * s:64 * s + 64] = wrong[64 * q:64 * q + 64]
+            shares = bytes(buf)
+        d_msgs, d_moff = dev(b"".join(msgs)), dev((np.arange(n + 1, dtype=np.uint64) * MSG_LEN).tobytes())
+        d_shares, d_keys, d_soff = dev(shares), dev(keys.tobytes()), dev((np.arange(n + 1, dtype=np.uint64) * k).tobytes())
+        outs = {name: [dev(bytes(x)) for x in (n_shares, n, 64 * n, 4 * bm_words * n, 4 * n)] for name in ("opt", "exact")}
+
+        def call(fn, o):
+            _check(fn(h, d_msgs.data_ptr(), d_moff.data_ptr(), d_shares.data_ptr(), d_keys.data_ptr(), d_soff.data_ptr(), n_shares, n, bm_words, t, 0,
+                      o[0].data_ptr(), o[1].data_ptr(), o[2].data_ptr(), o[3].data_ptr(), o[4].data_ptr(), stream))
+
+        def optimistic():
+            call(lib.bn254_batch_threshold_combine_keyed_optimistic_device, outs["opt"])
+
+        def exact():
+            call(lib.bn254_batch_threshold_combine_keyed_device, outs["exact"])
+        eng.set_option(OPT_THRESHOLD_OPT_MIN_SHARES, 0)
+        for fn in (optimistic, exact, optimistic, exact):
+            fn()
+        optimistic()
+        torch.cuda.synchronize()
+        did = (ctypes.c_uint64 * 4)()
+        _check(lib.bn254_debug_threshold_opt_last(h, did))
+        host = {name: [x.cpu().numpy().tobytes() for x in o] for name, o in outs.items()}
+        same_a = all(host["opt"][q][:size] == host["exact"][q][:size] for q, size in ((1, n), (2, 64 * n), (3, 4 * bm_words * n)))
+        same_all = same_a and host["opt"][0][:n_shares] == host["exact"][0][:n_shares] and host["opt"][4][:4 * n] == host["exact"][4][:4 * n]
+        ms = {"opt": [], "exact": []}
+        for _ in range(reps):
+            ms["opt"].append(timed(optimistic, ts))
+            ms["exact"].append(timed(exact, ts))
+        eng.set_profiling(True)
+        optimistic()
+        kms = eng.last_kernel_ms()
+        eng.set_profiling(False)
+        row = {"kind": "threshold_optimistic", "shape": "%dx%d" % (n, k), "n": n, "shares_per_tuple": k, "n_shares": n_shares, "threshold": t, "fail": fail,
+               "bad_shares": len(bad), "optimistic_call": spread(ms["opt"]), "exact_call": spread(ms["exact"]),
+               "hook": dict(zip(("checked", "passed", "exact_tuples", "exact_shares"), (int(x) for x in did))),
+               "stages_ms": [round(kms[x], 3) for x in STAGES],
+               "stage_slots": "front end + candidate rows, coefficients + weighted sum, tuple check (miller + final exp), exact fallback + re-interpolation",
+               "statuses_signatures_rows_as_exact": bool(same_a), "all_five_outputs_as_exact": bool(same_all), **box}
+        print(json.dumps(row), file=out, flush=True)
+        del d_msgs, d_moff, d_shares, d_keys, d_soff, outs
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("out", nargs="?")
@@ -126,6 +213,8 @@ def main():
     ap.add_argument("--msm-terms", type=int, default=65536)
     ap.add_argument("--keys", type=int, default=256)
     ap.add_argument("--note", default=None, help="recorded with every line, e.g. which build ran")
+    ap.add_argument("--optimistic", action="store_true", help="the optimistic threshold call against the exact one, on dealt keys")
+    ap.add_argument("--fail", default="none", choices=("none", "tuple", "percent", "key"))
     a = ap.parse_intermixed_args()
     out = open(a.out, "a") if a.out else sys.stdout
     shapes = [tuple(int(x) for x in s.split(":")) for s in a.shapes] or SHAPES
@@ -138,6 +227,9 @@ def main():
            "n_keys": N_KEYS, "reps": a.reps}
     if a.note:
         box["note"] = a.note
+    if a.optimistic:
+        optimistic_rows(eng, lib, h, ts, stream, box, shapes, N_KEYS, a.reps, a.fail, out)
+        return
     rng = np.random.default_rng(20261020)
     sks = [int.from_bytes(sk_bytes(9000 + j), "big") % R for j in range(N_KEYS)]
     pool, st = eng.batch_g2_mul(None, b"".join(s.to_bytes(32, "big") for s in sks), N_KEYS, reduce_scalar=True)

@@ -163,6 +163,11 @@ def load():
         L.bn254_batch_threshold_combine_keyed_optimistic.argtypes = [vp, vp, vp, vp, vp, vp, sz, sz, sz, u32, u32, vp, vp, vp, vp, vp]
         L.bn254_batch_threshold_combine_keyed_optimistic_device.argtypes = [vp, vp, vp, vp, vp, vp, sz, sz, sz, u32, u32, vp, vp, vp, vp, vp, vp]
         L.bn254_debug_threshold_opt_last.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
+    if hasattr(L, "bn254_ctx_check_dealing"):                         # absent from an older build loaded through BN254_LIB
+        L.bn254_batch_g2_msm.argtypes = [vp, vp, vp, vp, sz, i32, vp, vp]
+        L.bn254_batch_g2_msm_device.argtypes = [vp, vp, vp, vp, sz, i32, vp, vp, vp]
+        L.bn254_ctx_check_dealing.argtypes = [vp, u32, vp, u32, vp, vp, vp]
+        L.bn254_debug_dealing_coefficients.argtypes = [vp, sz, u32, vp, vp]
     L.bn254_debug_bitmap_rand_last.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     L.bn254_debug_bitmap_rand_sums.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), sz, sz, vp, vp, vp, vp, vp, vp]
     L.bn254_batch_verify_keyed_randomized.argtypes = [vp, vp, vp, vp, vp, sz, u32, vp, vp]
@@ -268,4 +273,5 @@ EXPORTED_SYMBOLS = [
     "bn254_debug_fr_op", "bn254_debug_lagrange_at_zero",
     "bn254_ctx_set_group_key", "bn254_batch_threshold_combine_keyed_optimistic", "bn254_batch_threshold_combine_keyed_optimistic_device",
     "bn254_debug_threshold_opt_last",
+    "bn254_batch_g2_msm", "bn254_batch_g2_msm_device", "bn254_ctx_check_dealing", "bn254_debug_dealing_coefficients",
 ]

@@ -450,9 +450,9 @@ class ECDSA:
         `threshold` keys have a valid share, the shares of the `threshold` LOWEST such keys are interpolated at zero.  Returns (the group
         Signature — which ECDSA.verify accepts under the group key, ECDSA.threshold_group_key —, the sorted indices used, statuses) with
         statuses[k] None or the Error ECDSA.batch_verify_keyed would give share k.  Raises Error(VerificationFailed) with fewer valid
-        keys — the error's .signers lists who was there, .statuses the shares' — and the message's Error(HashToPointError).  The library
-        checks every share against its registered key; it does NOT check that the registered keys lie on one polynomial of degree
-        threshold - 1: that is the dealer's or the DKG's job (include/bn254_hip.h: bn254_batch_threshold_combine_keyed)."""
+        keys — the error's .signers lists who was there, .statuses the shares' — and the message's Error(HashToPointError).  This call
+        checks every share against its registered key; that the registered keys lie on one polynomial of degree threshold - 1 is
+        ECDSA.check_dealing's to check, once per key set (include/bn254_hip.h: bn254_batch_threshold_combine_keyed)."""
         r = ECDSA.batch_threshold_combine_keyed([(message, signatures, key_indices)], threshold, engine, n_keys)[0]
         if isinstance(r, Error):
             raise r
@@ -469,9 +469,10 @@ class ECDSA:
     def register_group_key(public_key, engine=None):
         """Name the group key f(0) * G2 of the registered dealing (ECDSA.threshold_group_key computes it from share keys) for
         threshold_combine_keyed_optimistic; None forgets it.  Raises the Error PublicKey.from_uncompressed would raise for the key, and
-        then no group key is set.  ECDSA.register_keys / register_keys_proven forget the group key: a new key set is a new dealing.  The
-        library does not check that the registered keys interpolate to this key — a key that does not belong to the set only makes the
-        optimistic call as slow as the exact one (include/bn254_hip.h: bn254_ctx_set_group_key)."""
+        then no group key is set.  ECDSA.register_keys / register_keys_proven forget the group key: a new key set is a new dealing.  This
+        call does not check that the registered keys interpolate to this key (ECDSA.check_dealing computes the key they do interpolate
+        to) — a key that does not belong to the set only makes the optimistic call as slow as the exact one (include/bn254_hip.h:
+        bn254_ctx_set_group_key)."""
         eng = engine or _eng()
         _raise(eng.set_group_key(None if public_key is None else public_key.raw))
 
@@ -551,6 +552,43 @@ class ECDSA:
         for b in st:
             _raise(b)
         out, st = eng.batch_g2_sum(prod, [0, len(idx)])
+        _raise(st[0])
+        return PublicKey(out)
+
+    @staticmethod
+    def check_dealing(threshold, seed=None, engine=None, register=False):
+        """Are the registered keys (ECDSA.register_keys / register_keys_proven; key j standing for x_j = j + 1) a `threshold`-of-n dealing —
+        do they lie on one polynomial of degree below `threshold`?  Returns the group PublicKey they interpolate to; with register=True
+        it is then named as the group key (ECDSA.register_group_key).  Raises Error(VerificationFailed) for a key set that is no dealing
+        (or has fewer keys than the threshold), and, for a key whose registration status is non-zero, that key's Error with the index
+        in .key.  The check is randomised over `seed` (32 bytes; None draws them from os.urandom): a refusal is always right, an
+        acceptance wrong with probability at most 2^-128 if the seed is fresh — drawn after the keys were fixed — and the keys were
+        registered with the subgroup check, which ECDSA.register_keys always runs (include/bn254_hip.h: bn254_ctx_check_dealing)."""
+        import os
+        if int(threshold) < 1 or int(threshold) >= 1 << 32:
+            raise ValueError("threshold must be between 1 and 2^32 - 1")
+        seed = os.urandom(32) if seed is None else bytes(seed)
+        if len(seed) != 32:
+            raise Error(ErrorKind.InvalidLength)
+        eng = engine or _eng()
+        pk, st, bad = eng.check_dealing(int(threshold), seed)
+        if st:
+            err = Error(st)
+            err.key = None if bad == 0xFFFFFFFF else bad
+            raise err
+        key = PublicKey(pk)
+        if register:
+            ECDSA.register_group_key(key, eng)
+        return key
+
+    @staticmethod
+    def g2_msm(points, scalars, engine=None):
+        """sum scalars[k] * points[k] in G2 (points: PublicKey, scalars: integers, taken mod r) as a PublicKey (include/bn254_hip.h:
+        bn254_batch_g2_msm); raises the first point's decode Error"""
+        pts, ks = list(points), [int(k) % _R for k in scalars]
+        if len(pts) != len(ks) or any(len(p.raw) != _engine.G2_BYTES for p in pts):
+            raise Error(ErrorKind.InvalidLength)
+        out, st = (engine or _eng()).batch_g2_msm(b"".join(p.raw for p in pts), b"".join(k.to_bytes(32, "big") for k in ks), [0, len(pts)])
         _raise(st[0])
         return PublicKey(out)
 

@@ -168,9 +168,10 @@ BN_DEV uint64_t msm_seg_len(const uint64_t* seg, size_t i, uint64_t m, const uin
   return seg[i + 1] - seg[i];
 }
 // one step of either walk: term lo + k of a segment of len terms; `bad` = the index of the first term whose status is non-zero (its status
-// in st), UINT64_MAX while there is none
-BN_DEV void msm_step(G1Jac& acc, uint8_t& st, uint64_t& bad, const G1Jac* terms, const uint8_t* term_st, uint64_t lo, uint64_t len, uint64_t k) {
-  G1Jac t;
+// in st), UINT64_MAX while there is none.  J: G1Jac here, G2Jac for the sum in G2 (bn254_dealing.h)
+template <class J>
+BN_DEV void msm_step(J& acc, uint8_t& st, uint64_t& bad, const J* terms, const uint8_t* term_st, uint64_t lo, uint64_t len, uint64_t k) {
+  J t;
   jac_set_identity(t);
   if (k < len) {
     t = terms[lo + k];
@@ -179,12 +180,14 @@ BN_DEV void msm_step(G1Jac& acc, uint8_t& st, uint64_t& bad, const G1Jac* terms,
   }
   jac_add(acc, acc, t);
 }
-BN_DEV void msm_lane_sum(G1Jac& acc, uint8_t& st, const G1Jac* terms, const uint8_t* term_st, uint64_t lo, uint64_t len) {
+template <class J>
+BN_DEV void msm_lane_sum(J& acc, uint8_t& st, const J* terms, const uint8_t* term_st, uint64_t lo, uint64_t len) {
   uint64_t bad = UINT64_MAX;
   jac_set_identity(acc);
   for (uint64_t k = 0; BN_WAVE_ANY(k < len); ++k) msm_step(acc, st, bad, terms, term_st, lo, len, k);
 }
-BN_DEV void msm_wave_partial(G1Jac& acc, uint8_t& st, uint64_t& bad, const G1Jac* terms, const uint8_t* term_st, uint64_t lo, uint64_t len, unsigned lane) {
+template <class J>
+BN_DEV void msm_wave_partial(J& acc, uint8_t& st, uint64_t& bad, const J* terms, const uint8_t* term_st, uint64_t lo, uint64_t len, unsigned lane) {
   bad = UINT64_MAX;
   st = ST_OK;
   jac_set_identity(acc);

@@ -416,6 +416,40 @@ class Engine:
         _check("bn254_batch_g1_msm_device",
                self._lib.bn254_batch_g1_msm_device(self._h, d_points, d_scalars, d_seg_off, n, int(reduce_scalar), d_out, d_status, stream))
 
+    def batch_g2_msm(self, points, scalars, seg_off, reduce_scalar=False):
+        """segmented scalar-weighted sums in G2 (include/bn254_hip.h: bn254_batch_g2_msm): out[i] = sum of scalars[s] * points[s] over the
+        terms seg_off[i] .. seg_off[i+1], 128-byte points; returns (the n sums, the n status bytes)"""
+        n = len(seg_off) - 1
+        m = int(seg_off[n]) if n >= 0 else 0
+        assert len(points) == m * G2_BYTES and len(scalars) == m * SCALAR_BYTES
+        off = (ctypes.c_uint64 * (n + 1))(*seg_off)
+        out = ctypes.create_string_buffer(max(n, 1) * G2_BYTES)
+        status = ctypes.create_string_buffer(max(n, 1))
+        _check("bn254_batch_g2_msm", self._lib.bn254_batch_g2_msm(self._h, bytes(points), bytes(scalars), off, n, int(reduce_scalar), out, status))
+        return out.raw[:n * G2_BYTES], status.raw[:n]
+
+    def batch_g2_msm_device(self, d_points, d_scalars, d_seg_off, n, d_out, d_status, reduce_scalar=False, stream=None):
+        _check("bn254_batch_g2_msm_device",
+               self._lib.bn254_batch_g2_msm_device(self._h, d_points, d_scalars, d_seg_off, n, int(reduce_scalar), d_out, d_status, stream))
+
+    def check_dealing(self, threshold, seed32):
+        """are the registered keys a `threshold`-of-n dealing, and which group key do they interpolate to (include/bn254_hip.h:
+        bn254_ctx_check_dealing): returns (group key: 128 bytes, zeroed unless the status is 0; status; bad_key: the lowest key with a
+        non-zero registration status, or 0xFFFFFFFF).  Does not install the group key: set_group_key does."""
+        assert len(seed32) == 32
+        pk = ctypes.create_string_buffer(G2_BYTES)
+        st = ctypes.create_string_buffer(1)
+        bad = ctypes.c_uint32(0)
+        _check("bn254_ctx_check_dealing", self._lib.bn254_ctx_check_dealing(self._h, int(threshold), bytes(seed32), 0, pk, st, ctypes.byref(bad)))
+        return pk.raw, st.raw[0], bad.value
+
+    def debug_dealing_coefficients(self, n_keys, threshold, seed32):
+        """the coefficients c_0 .. c_n-1 of check_dealing's degree check -> n_keys * 32 bytes, big-endian, reduced"""
+        assert len(seed32) == 32
+        out = ctypes.create_string_buffer(max(n_keys, 1) * 32)
+        _check("bn254_debug_dealing_coefficients", self._lib.bn254_debug_dealing_coefficients(self._h, n_keys, int(threshold), bytes(seed32), out))
+        return out.raw[:n_keys * 32]
+
     def batch_aggregate_verify(self, messages, pk_pool, sig_pool, tuple_msg, signer_lists, flags=0):
         """messages: M byte strings; pk_pool: S*128 B; sig_pool: M*S*64 B (signer s on message m at m*S+s);
         tuple i verifies messages[tuple_msg[i]] against the aggregate of signer_lists[i]."""

@@ -421,15 +421,15 @@ struct ECDSA {
   // share key f(j + 1) * G2 of a dealing, an item's signatures are the validators' shares.  Every share is verified against its key; with at
   // least `threshold` keys holding a valid share, the shares of the `threshold` lowest such keys are interpolated at zero: `signature` is the
   // group signature (verify accepts it under f(0) * G2) and signer_indices the keys used.  status 9 (VerificationFailed): too few valid keys —
-  // signer_indices then lists who was there and the signature is the identity; else the message's hash ErrorKind.  The library does NOT check
-  // that the registered keys lie on one polynomial of degree threshold - 1: that is the dealer's or the DKG's job.
+  // signer_indices then lists who was there and the signature is the identity; else the message's hash ErrorKind.  That the registered keys
+  // lie on one polynomial of degree threshold - 1 is check_dealing's to check, once per key set.
   static std::vector<KeyedAggregateResult> batch_threshold_combine_keyed(const std::vector<ShareItem>& items, size_t n_keys, uint32_t threshold,
                                                                          Engine& e = Engine::default_engine()) {
     return threshold_batch(items, n_keys, threshold, false, e);
   }
   // THE GROUP KEY f(0) * G2 of the registered dealing, for the optimistic calls below (include/bn254_hip.h: bn254_ctx_set_group_key); throws
   // the key's decode Error, and then no group key is set.  forget_group_key drops it, as register_keys / register_keys_proven do: a new key
-  // set is a new dealing.  The library does not check that the registered keys interpolate to this key.
+  // set is a new dealing.  This call does not check that the registered keys interpolate to this key: check_dealing computes the key they do.
   static void register_group_key(const PublicKey& group_key, Engine& e = Engine::default_engine()) {
     uint8_t st = 0;
     check_rc("bn254_ctx_set_group_key", bn254_ctx_set_group_key(e.raw(), group_key.raw.data(), 0, &st));
@@ -513,6 +513,38 @@ struct ECDSA {
     check_rc("bn254_batch_g1_msm", bn254_batch_g1_msm(e.raw(), p.data(), k.data(), seg, 1, 1, out.raw.data(), &st));
     check_status(st);
     return out;
+  }
+  // ... and in G2 (include/bn254_hip.h: bn254_batch_g2_msm): group keys, sum x^k C_k over a vector of commitments
+  static PublicKey g2_msm(const std::vector<PublicKey>& points, const std::vector<std::array<uint8_t, 32>>& scalars, Engine& e = Engine::default_engine()) {
+    if (points.size() != scalars.size()) throw Error(ErrorKind::InvalidLength);
+    std::vector<uint8_t> p(points.size() * 128 + 4, 0), k(points.size() * 32 + 4, 0);
+    for (size_t i = 0; i < points.size(); ++i) {
+      std::memcpy(&p[128 * i], points[i].raw.data(), 128);
+      std::memcpy(&k[32 * i], scalars[i].data(), 32);
+    }
+    const uint64_t seg[2] = {0, points.size()};
+    PublicKey out;
+    uint8_t st = 0;
+    check_rc("bn254_batch_g2_msm", bn254_batch_g2_msm(e.raw(), p.data(), k.data(), seg, 1, 1, out.raw.data(), &st));
+    check_status(st);
+    return out;
+  }
+  // Are the registered keys (key j standing for x_j = j + 1) a `threshold`-of-n dealing — do they lie on one polynomial of degree below
+  // `threshold` (include/bn254_hip.h: bn254_ctx_check_dealing)?  Returns the group key they interpolate to and, with register_key, names it
+  // as the group key of the optimistic calls.  Throws Error(VerificationFailed) for a key set that is no dealing, and the Error of the lowest
+  // key whose registration status is non-zero, its index then in *bad_key (UINT32_MAX otherwise).  Randomised over the seed: a refusal is
+  // always right, an acceptance wrong with probability at most 2^-128 for a fresh seed — drawn after the keys were fixed — and keys
+  // registered with the subgroup check (register_keys always runs it).
+  static PublicKey check_dealing(uint32_t threshold, const std::array<uint8_t, 32>& seed, bool register_key = false, uint32_t* bad_key = nullptr,
+                                 Engine& e = Engine::default_engine()) {
+    PublicKey key;
+    uint8_t st = 0;
+    uint32_t bad = UINT32_MAX;
+    check_rc("bn254_ctx_check_dealing", bn254_ctx_check_dealing(e.raw(), threshold, seed.data(), 0, key.raw.data(), &st, &bad));
+    if (bad_key) *bad_key = bad;
+    check_status(st);
+    if (register_key) register_group_key(key, e);
+    return key;
   }
   // The inner node of an aggregation tree (include/bn254_hip.h: bn254_batch_merge_keyed_bitmap): one message and PARTIAL aggregates of it,
   // parts[k] = a summed signature and the indices of the registered keys it is said to sum.  Every partial is verified as verify_keyed_signers

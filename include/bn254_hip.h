@@ -280,6 +280,29 @@ int bn254_batch_g1_msm(bn254_ctx *ctx, const uint8_t *points /* m*64 */, const u
                        const uint64_t *seg_off /* n+1 */, size_t n, int reduce_scalar, uint8_t *out /* n*64 */, uint8_t *status /* n */);
 int bn254_batch_g1_msm_device(bn254_ctx *ctx, const uint8_t *d_points, const uint8_t *d_scalars, const uint64_t *d_seg_off, size_t n,
                               int reduce_scalar, uint8_t *d_out, uint8_t *d_status, void *stream);
+/* ... and in G2: out[i] = sum over the terms s in [seg_off[i], seg_off[i+1]) of scalars[s] * points[s], 128-byte points and outputs — the
+ * building block for group keys (sum lambda_k pk_k), for evaluating a vector of commitments (sum x^k C_k) and for the dealing check below.
+ * Same argument list, argument checks, alignment rules and range rule of the _device form as bn254_batch_g1_msm above; the _device form makes
+ * the same single 8-byte copy of d_seg_off[n] and so cannot be captured into a graph either.  Scratch: 217 B per term.
+ * DEFINING IDENTITY: byte for byte bn254_batch_g2_mul(points, scalars, reduce_scalar) followed by bn254_batch_g2_sum of the products over
+ * the same segments, the identity as 128 zero bytes included.  The first non-zero decode status in segment order wins, and the output is
+ * then the identity; an empty segment gives the identity with status 0; a refused segment reads 2.  Points are decoded with flags 0, as
+ * bn254_batch_g2_mul and bn254_batch_g2_sum decode them: on the curve, NO subgroup check.
+ * Cost: a term kernel, one lane per term (decode, the 256-step ladder of bn254_batch_g2_mul, the Jacobian result to scratch — no inversion
+ * per term), then one sum per segment in the collect's two layouts, split by BN254_OPT_COLLECT_WAVE_MIN_SHARES as in G1 (the split was
+ * not swept for G2); one inversion per segment.
+ * Measured on an MI355X (tools/dealing_throughput.py, profiles/dealing.jsonl; host forms under a host clock, staging on both sides, median
+ * [min, max] of 7 alternating runs after 2 warm-up runs; against bn254_batch_g2_mul + bn254_batch_g2_sum): 65 536 terms in 4 096 segments
+ * of 16 — the first length the wave layout takes — 8.59 ms [8.50, 8.92] against 8.00 [7.87, 18.0]: 0.6 ms SLOWER; 65 536 terms in one segment
+ * 35.1 ms [34.95, 35.25] against 1 618 [1 566, 2 077], where g2_sum walks the segment in one lane; 171 terms in one segment 5.37 [5.33, 5.38]
+ * against 9.69 [9.35, 10.55].  The _device form under events: 8.50, 35.04 and 5.33 ms.  Which call when: this one for long segments, for few
+ * segments, or where the products are not wanted; the two old calls for many segments of about 16.  Unmeasured: other segment lengths, a
+ * sweep of the lane/wave split.
+ * DESIGN.md section 10m. */
+int bn254_batch_g2_msm(bn254_ctx *ctx, const uint8_t *points /* m*128 */, const uint8_t *scalars /* m*32, big-endian */,
+                       const uint64_t *seg_off /* n+1 */, size_t n, int reduce_scalar, uint8_t *out /* n*128 */, uint8_t *status /* n */);
+int bn254_batch_g2_msm_device(bn254_ctx *ctx, const uint8_t *d_points, const uint8_t *d_scalars, const uint64_t *d_seg_off, size_t n,
+                              int reduce_scalar, uint8_t *d_out, uint8_t *d_status, void *stream);
 
 /* aggregate verify over shared pools (BASELINE config 3): tuple i names a message tuple_msg[i] and a
  * list of signers signer_idx[tuple_off[i] .. tuple_off[i+1]); status[i] = ECDSA::verify(msg, sum of the
@@ -837,9 +860,10 @@ int bn254_ctx_register_keys_pop(bn254_ctx *ctx, const uint8_t *pks /* n_keys*128
  * DEFINING IDENTITY 3 (closed loop, flags = 0): for registered keys pk_j = f(j + 1) * G2::one() of ONE polynomial of degree threshold - 1,
  * bn254_batch_verify of (m_i, group_sigs[i], f(0) * G2::one()) returns 0 for every tuple with tuple_status 0, whatever subset signed, and
  * group_sigs[i] is the same point for every subset.
- * WHAT IS CHECKED: every share against its registered key.  WHAT IS NOT: that the registered keys lie on one polynomial of degree
- * threshold - 1 — that is the dealer's or the DKG's job.  For a key set that does not, the output is still well defined (the rule for S_i)
- * but is the signature of no key in particular.  Registration statuses apply as in every keyed call (a key registered with a failed proof
+ * WHAT IS CHECKED: every share against its registered key.  WHAT IS NOT, by this call: that the registered keys lie on one polynomial of
+ * degree threshold - 1 — producing such a set is the dealer's or the DKG's job, and bn254_ctx_check_dealing below is the call with which a
+ * committee checks the set it was handed, once per key set.  For a key set that does not, the output is still well defined (the rule for
+ * S_i) but is the signature of no key in particular.  Registration statuses apply as in every keyed call (a key registered with a failed proof
  * of possession has no valid share).
  * Cost: the collect's — one hash per tuple, one keyed verify per share, its select-and-sum — then a lane per tuple for rank and select (the
  * `threshold` lowest bits of the row, counted across its words), a lane per share that claims its kept key and writes the key's
@@ -856,8 +880,9 @@ int bn254_ctx_register_keys_pop(bn254_ctx *ctx, const uint8_t *pks /* n_keys*128
  * same signature bytes.  Unmeasured: other thresholds, invalid shares, more than 256 keys, the host form.
  * Which call when: this one whenever the shares are in hand and the share keys registered; bn254_batch_collect_keyed_bitmap for
  * multi-signatures (no interpolation); bn254_batch_g1_msm for weighted sums of the caller's own points.  DESIGN.md section 10k.
- * Out of scope: a randomised form, the multi-GPU layer, compressed shares, key dealing (Shamir sharing, DKG) in the C ABI.  No longer out
- * of scope: an optimistic form that interpolates first and verifies the result once — bn254_batch_threshold_combine_keyed_optimistic below. */
+ * Out of scope: a randomised form, the multi-GPU layer, compressed shares, and PRODUCING a dealing in the C ABI (Shamir sharing, the
+ * rounds of a DKG, checks of shares against commitments; bn254_batch_g2_msm is the building block for sum x^k C_k).  No longer out of
+ * scope: checking a dealt key set (bn254_ctx_check_dealing), and an optimistic form that interpolates first and verifies the result once — bn254_batch_threshold_combine_keyed_optimistic below. */
 int bn254_batch_threshold_combine_keyed(bn254_ctx *ctx, const uint8_t *msgs, const uint64_t *msg_off /* n+1 */,
                                         const uint8_t *shares /* n_shares*64 */, const uint32_t *share_key /* n_shares */,
                                         const uint64_t *share_off /* n+1 */, size_t n_shares, size_t n, size_t bm_words, uint32_t threshold,
@@ -874,10 +899,49 @@ int bn254_batch_threshold_combine_keyed_device(bn254_ctx *ctx, const uint8_t *d_
  * identity, 128 zero bytes, is a legal group key as it is a legal registered key), into a one-entry table of its own; NULL forgets the key.
  * A non-zero decode status is reported in *status (may be NULL) and leaves NO group key set; the call itself returns 0.  Quiesces the
  * context first, like a registration.  LIFETIME: bn254_ctx_register_keys and bn254_ctx_register_keys_pop forget the group key — a new key
- * set is a new dealing.  The library does NOT check that the registered keys interpolate to this key: a key that does not belong to the set
- * sends every tuple of the optimistic call the exact way (slower, the exact call's bytes) and can never make a wrong signature pass,
+ * set is a new dealing.  This call does NOT check that the registered keys interpolate to this key — bn254_ctx_check_dealing below computes
+ * the key they do interpolate to —: a key that does not belong to the set sends every tuple of the optimistic call the exact way (slower, the exact call's bytes) and can never make a wrong signature pass,
  * because what passes has verified under the key the caller named. */
 int bn254_ctx_set_group_key(bn254_ctx *ctx, const uint8_t *group_pk /* 128, or NULL: forget it */, uint32_t flags, uint8_t *status /* 1, or NULL */);
+
+/* CHECK A DEALING: are the registered keys 0 .. n - 1 (n = the number registered, key j standing for x_j = j + 1) a t-of-n dealing — do they
+ * lie on ONE polynomial of degree below t = threshold — and which group key do they interpolate to.  What a committee runs once on the key
+ * set a dealer or a DKG round handed it, before the threshold calls above are worth anything.  Host-synchronous: like a registration it
+ * quiesces the context first and returns after the outputs are written.  It does NOT install the group key (bn254_ctx_set_group_key does).
+ * BN254_E_BAD_ARGUMENT: threshold == 0, no registered keys, flags != 0, a NULL seed32, group_pk or status.  Otherwise four outcomes, tested
+ * in this order (bad_key may be NULL):
+ *   1. a key has a non-zero registration status (decode fault, failed proof of possession): *status = that status, the LOWEST such key
+ *      wins, *bad_key = its index, group_pk = 128 zero bytes; nothing else is computed.
+ *   2. threshold > n: *status = 9, *bad_key = UINT32_MAX, group_pk zeroed; nothing else is computed.
+ *   3. the degree check fails: *status = 9, *bad_key = UINT32_MAX, group_pk zeroed.
+ *   4. it passes: *status = 0, *bad_key = UINT32_MAX, group_pk = K.  With threshold == n there is nothing to check: 0 and K.
+ * K = sum over k < t of lambda_k pk_k, lambda_k the coefficients bn254_debug_lagrange_at_zero gives for the points 1 .. t.  DEFINING IDENTITY:
+ * K is byte for byte bn254_batch_g2_msm of the first t keys' uncompressed bytes under those scalars.
+ * THE DEGREE CHECK is randomised.  rho_j, for j in [t, n), is the 128-bit weight of index j under seed32 — the first 16 bytes of
+ * SHA-256(seed32 || le64(j)) read little-endian, 0 mapped to 1: the derivation of bn254_batch_verify_randomized.  c_j = rho_j for j >= t, and
+ * c_k = -sum over j in [t, n) of rho_j L_k(x_j) mod r for k < t, L_k(x) = prod over i < t, i != k of (x - x_i) / (x_k - x_i).  The keys pass
+ * iff sum over j < n of c_j pk_j is the identity: key j >= t contributes rho_j (pk_j - the value the first t keys interpolate at x_j).
+ * For a true dealing the sum is the identity under EVERY seed, so a 9 is always exact.  A 0 is wrong with probability <= 2^-128, PROVIDED
+ *   (a) the seed is fresh and unpredictable to whoever produced the keys (drawn after the keys were fixed), and
+ *   (b) the keys are in the order-r subgroup: they were registered with BN254_FLAG_G2_SUBGROUP_CHECK.
+ * Which keys are off the polynomial is not reported.
+ * Cost: the coefficients on the device in Fr — the points are consecutive, so every product of differences is a factorial: a table of
+ * factorials (one wave, a product scan), a table of the inverses of 1 .. n (one inversion per entry, a lane each), then a lane per k < t
+ * walking the j: (n - t) products and one inversion — O(t (n - t)) products and O(n) inversions in all.  Then K and the check as ONE launch
+ * of bn254_batch_g2_msm's kernels over two segments, t + n terms, whose term kernel reads the registered keys' table instead of decoding
+ * bytes; a last kernel settles the verdict, and the host reads 128 + 4 + 1 bytes.  Under bn254_ctx_set_profiling: ms[0] key scan and
+ * coefficients, ms[1] terms, ms[2] sums, ms[3] verdict.
+ * Measured on an MI355X (tools/dealing_throughput.py, profiles/dealing.jsonl; keys dealt from one polynomial and registered; whole calls
+ * under a host clock, median [min, max] of 7): n = 256, t = 171: 7.04 ms [7.03, 7.15] against 16.06 [15.95, 18.47] for the Python-integer
+ * route (the same closed-form coefficients in Python integers, then bn254_batch_g2_mul and bn254_batch_g2_sum over the t + n products) and
+ * 30.3 [29.3, 35.4] for the exact route ((n - t) t = 14 535 products, each key j >= t compared with its interpolation); 1 024, 683: 7.98
+ * [7.92, 8.01] against 69.2 [66.0, 79.1]; 4 096, 2 731: 11.48 [11.42, 11.59] against 593 [574, 599].  Stages of ONE profiled call
+ * (coefficients, terms, sums): 1.76, 4.99, 0.35 ms at 256; 2.32, 5.02, 0.63 at 1 024; 4.57, 5.03, 1.96 at 4 096 — a 256-step G2 ladder is
+ * 5 ms of latency however few lanes walk one, and at 4 096 keys the lane per k that walks 1 365 products and an inversion takes as long.
+ * Unmeasured: other thresholds, key sets that fail (the same work), more than 4 096 keys.
+ * DESIGN.md section 10m.  Out of scope: the multi-GPU layer, compressed keys, locating the keys that are off, 64-bit weights, a bucket-method sum. */
+int bn254_ctx_check_dealing(bn254_ctx *ctx, uint32_t threshold, const uint8_t *seed32 /* host */, uint32_t flags /* must be 0 */,
+                            uint8_t *group_pk /* 128 */, uint8_t *status /* 1 */, uint32_t *bad_key /* 1, or NULL */);
 
 /* OPTIMISTIC THRESHOLD COMBINE: interpolate first, verify the result once per tuple under the group key.  The interpolated signature is
  * unique: if it verifies under f(0) * G2::one() it is THE group signature whatever the individual shares were, so one pairing check per
@@ -1331,6 +1395,10 @@ int bn254_debug_fr_op(bn254_ctx *ctx, int op, const uint8_t *a, const uint8_t *b
  * coefficient of point j within its segment, prod x_k / prod (x_k - x_j) mod r over the segment's other points.  The points of a segment
  * must be distinct and non-zero (a repeated point gives 0).  seg_off[0] == 0, non-decreasing. */
 int bn254_debug_lagrange_at_zero(bn254_ctx *ctx, const uint32_t *x /* m */, const uint64_t *seg_off /* n+1 */, size_t n, uint8_t *out /* m*32 */);
+/* the coefficients c_0 .. c_n_keys-1 of bn254_ctx_check_dealing's degree check for n_keys keys, 1 <= threshold <= n_keys and the seed, by
+ * the call's own kernels; independent of any registration */
+int bn254_debug_dealing_coefficients(bn254_ctx *ctx, size_t n_keys, uint32_t threshold, const uint8_t *seed32,
+                                     uint8_t *out /* n_keys*32, big-endian, reduced */);
 /* the final exponentiation of ECDSA::verify / bn::pairing_batch (src/ecdsa.rs:57-59) on caller-supplied LIMB vectors — n x 12 coefficients
  * (Gt order) x 9 int32 limbs, value = sum limb_k 2^(29 k) in Montgomery form (R = 2^261) — in the layout named: 0 one lane per item, exact
  * exponent, gt = canonical Gt bytes | 1 lane pairs, exact, gt | 2 lane pairs, the == one chain | 3 lane octets (straight-line chains below

@@ -66,6 +66,46 @@ KERNEL_SMALL void k_debug_hash_candidate(const uint8_t* h, size_t n, uint8_t* ou
   encode_g1(out + 64 * i, p);
   status[i] = (uint8_t)((ok ? 0 : 1) | (filt != ok ? 0x80 : 0));
 }
+// The Jacobi symbol of the hash filter, one value per lane (include/bn254_hip.h: bn254_debug_jacobi).  mode 0: a < q straight into
+// u256_is_square_mod_q | 1: a = a candidate x < q through hash_curve_rhs and fp_to_u256 as hash_try_filter does, bit 1 = the square root's
+// answer | 2: the symbol (a / b) through the same passes (u256_jacobi_symbol).  value = what the passes were handed; bit 7 = operand refused.
+__device__ __forceinline__ U256 u256_from_be(const uint8_t* p) {
+  U256 x;
+  const uint32_t* w = (const uint32_t*)p;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) x.w[7 - k] = __builtin_bswap32(w[k]);
+  return x;
+}
+KERNEL_SMALL void k_debug_jacobi(int mode, const uint8_t* a, const uint8_t* b, size_t n, uint8_t* value, uint8_t* flags) {
+  size_t i = (size_t)blockIdx.x * BN_WAVE + threadIdx.x;
+  if (i >= n) return;
+  const U256 x = u256_from_be(a + 32 * i);
+  U256 v = x;
+  uint8_t fl = 0;
+  if (mode == 2) {
+    const U256 m = u256_from_be(b + 32 * i);
+    uint32_t above = m.w[0] & ~1u;                     // an odd m is >= 3 iff it has a bit above bit 0
+#pragma unroll
+    for (int k = 1; k < 8; ++k) above |= m.w[k];
+    const bool ok = (m.w[0] & 1u) && above != 0 && !u256_geq(x.w, m.w);
+    if (ok) fl = (uint8_t)u256_jacobi_symbol(x, m); else fl = 0x80;
+  } else if (u256_geq(x.w, C_Q)) {
+    fl = 0x80;
+  } else if (mode == 1) {
+    Fp xm, rhs;
+    hash_curve_rhs(xm, rhs, x);
+    v = fp_to_u256(rhs);
+    G1Affine p;
+    fl = (uint8_t)((u256_is_square_mod_q(v) ? 1 : 0) | (hash_point_from_candidate(p, x) ? 2 : 0));
+  } else {
+    fl = u256_is_square_mod_q(x) ? 1 : 0;
+  }
+  if (fl & 0x80) { for (int k = 0; k < 8; ++k) v.w[k] = 0; }
+  uint32_t* o = (uint32_t*)(value + 32 * i);
+#pragma unroll
+  for (int k = 0; k < 8; ++k) o[k] = __builtin_bswap32(v.w[7 - k]);
+  flags[i] = fl;
+}
 __device__ __forceinline__ void decode_fp12(Fp12& f, const uint8_t* b) {
   uint32_t any = 0;
   Fp2* c[6] = {&f.c0.c0, &f.c0.c1, &f.c0.c2, &f.c1.c0, &f.c1.c1, &f.c1.c2};
@@ -595,6 +635,19 @@ int bn254_debug_hash_candidate(bn254_ctx* c, const uint8_t* h, size_t n, uint8_t
   uint8_t *d_out = st.out(2, n * 64, out), *d_status = st.out(3, n, status);
   if (!st.ok()) return st.rc;
   k_debug_hash_candidate<<<grid_for(n), BN_WAVE, 0, c->stream>>>(d_h, n, d_out, d_status);
+  HIP_TRY(hipGetLastError());
+  return st.finish();
+}
+int bn254_debug_jacobi(bn254_ctx* c, int mode, const uint8_t* a, const uint8_t* b, size_t n, uint8_t* out_value, uint8_t* out_flags) {
+  if (!c || mode < 0 || mode > 2 || (n && (!a || !out_value || !out_flags)) || (n && mode == 2 && !b)) return BN254_E_BAD_ARGUMENT;
+  if (n == 0) return 0;
+  HIP_TRY(hipSetDevice(c->device));
+  HostStaging st(c);
+  const uint8_t* d_a = st.in(0, a, n * 32);
+  const uint8_t* d_b = mode == 2 ? st.in(1, b, n * 32) : nullptr;
+  uint8_t *d_value = st.out(2, n * 32, out_value), *d_flags = st.out(3, n, out_flags);
+  if (!st.ok()) return st.rc;
+  k_debug_jacobi<<<grid_for(n), BN_WAVE, 0, c->stream>>>(mode, d_a, d_b, n, d_value, d_flags);
   HIP_TRY(hipGetLastError());
   return st.finish();
 }

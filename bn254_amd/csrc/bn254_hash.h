@@ -188,6 +188,26 @@ BN_DEVN bool u256_is_square_mod_q(const U256& a_in) {
   // gcd(a_in, q) = n = 1 for a prime q and 0 < a_in < q
   return zero || (t & 1u) == 0;
 }
+// The Jacobi symbol (a / b) of an odd b >= 3 and 0 <= a < b through the same passes: 0 = symbol +1, 1 = symbol -1, 2 = symbol 0 (a and b share
+// a factor: the passes end with n = gcd(a, b) != 1).  Test driver (bn254_debug_jacobi, mode 2): a modulus of two, four or six words puts a lane
+// straight into a narrow phase, which no value mod q does.  The two drivers STAY IN STEP — the phases, their order and the budget of this one
+// are those of u256_is_square_mod_q above; whoever changes one changes the other.
+BN_DEV uint32_t u256_jacobi_symbol(const U256& a_in, const U256& b_in) {
+  uint32_t a[8], n[8];
+  uint32_t any = 0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) { a[i] = a_in.w[i]; n[i] = b_in.w[i]; any |= a[i]; }
+  uint32_t t = 0;
+  int budget = 600;
+  jacobi_passes<8>(a, n, t, any, budget);
+  jacobi_passes<6>(a, n, t, any, budget);
+  jacobi_passes<4>(a, n, t, any, budget);
+  jacobi_passes<2>(a, n, t, any, budget);
+  uint32_t rest = n[0] ^ 1u;
+#pragma unroll
+  for (int i = 1; i < 8; ++i) rest |= n[i];
+  return rest ? 2u : (t & 1u);
+}
 
 // The range rules applied to a digest value x (hash.rs:49-54): rejected if >= 5q, reduced by mod_u256's strict rule;
 // false = this value yields no x.  (Separate from the SHA-256 so that tests can feed chosen values: no preimage of

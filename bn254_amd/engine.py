@@ -618,6 +618,14 @@ class Engine:
         _check("bn254_debug_hash_candidate", self._lib.bn254_debug_hash_candidate(self._h, bytes(h), n, out, status))
         return out.raw[:n * G1_BYTES], status.raw[:n]
 
+    def debug_jacobi(self, mode, a, b, n):
+        """the hash filter's Jacobi symbol on n 32-byte big-endian integers (include/bn254_hip.h: bn254_debug_jacobi; mode 0 a value below q,
+        1 a candidate x, 2 the symbol (a / b)) -> (n * 32 bytes handed to the passes, n flag bytes)"""
+        value = ctypes.create_string_buffer(max(n, 1) * 32)
+        flags = ctypes.create_string_buffer(max(n, 1))
+        _check("bn254_debug_jacobi", self._lib.bn254_debug_jacobi(self._h, mode, bytes(a), None if b is None else bytes(b), n, value, flags))
+        return value.raw[:n * 32], flags.raw[:n]
+
     # ---- device-pointer entry points (inputs resident in HBM; enqueue only) ---------------
     def register_keys(self, pks, flags=0):
         """replace the context's registered key set (uncompressed G2, 128 B each); returns the per-key status bytes

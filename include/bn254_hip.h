@@ -1412,6 +1412,20 @@ int bn254_debug_final_exp_limbs(bn254_ctx *ctx, int layout, const int32_t *limbs
  * (src/utils.rs:27-37) and G1::from_compressed(0x02 || x) (src/utils.rs:56-63).  status 0: out = the point; 1: the
  * loop would move to the next counter (out = zeros).  Exists because h = k*q has no known preimage. */
 int bn254_debug_hash_candidate(bn254_ctx *ctx, const uint8_t *h /* n*32 */, size_t n, uint8_t *out /* n*64 */, uint8_t *status);
+/* the Jacobi symbol of the hash filter (bn254_hash.h: u256_is_square_mod_q, the test every counter of hash-to-G1 meets before its square
+ * root), element-wise, one lane per item, on 32-byte big-endian integers.  A whole hash only ever hands the filter x^3 + 3 of a digest — a
+ * uniformly random value; this hook hands it chosen ones.
+ *   mode 0: a (an integer below q) goes straight into the filter.  out_flags[i] bit 0 = its answer (1: a square mod q, zero included).
+ *           a >= q: bit 7 and nothing else.
+ *   mode 1: a = a candidate x below q, through x^3 + 3 and the conversion to a plain integer exactly as the filter round does.  out_value =
+ *           the integer the filter is handed; bit 0 = the filter's answer; bit 1 = whether the square root behind the filter yields a
+ *           point (the two bits agree, or a message would get the wrong counter).  a >= q: bit 7 and nothing else.
+ *   mode 2: the symbol (a / b) of the caller's odd b >= 3 and a < b, through the same passes in the same phases under the same budget
+ *           (a modulus of 64, 128 or 192 bits enters the narrower phases directly, which no value mod q does).  out_flags[i] = 0: symbol
+ *           +1, 1: symbol -1, 2: symbol 0 (a and b share a factor).  An even b, b < 3 or a >= b: bit 7 and nothing else.
+ * out_value in modes 0 and 2 = a as the passes received it; zeros where bit 7 is set.  b is read in mode 2 only (may be NULL otherwise).
+ * BN254_E_BAD_ARGUMENT for another mode or a missing buffer; n == 0 returns 0. */
+int bn254_debug_jacobi(bn254_ctx *ctx, int mode, const uint8_t *a, const uint8_t *b, size_t n, uint8_t *out_value /* n*32 */, uint8_t *out_flags /* n */);
 /* un-exponentiated Miller-loop value of each single pair (debugging aid) */
 int bn254_debug_miller_loop(bn254_ctx *ctx, const uint8_t *g1, const uint8_t *g2, size_t n, uint8_t *f /* n*384 */);
 

@@ -508,4 +508,33 @@ int hs_fp_op(int op, const uint8_t* a, const uint8_t* b, uint8_t* out) {
   memcpy(out, to, 32);
   return st;
 }
+// modes, values and flag bits as bn254_debug_jacobi (k_debug_jacobi, bn254_devhooks.hip); b is read in mode 2 only
+int hs_jacobi(int mode, const uint8_t* a, const uint8_t* b, uint8_t* out_value, uint8_t* out_flag) {
+  auto load = [](const uint8_t* p) { U256 x; for (int k = 0; k < 8; ++k) x.w[7 - k] = ((uint32_t)p[4 * k] << 24) | ((uint32_t)p[4 * k + 1] << 16) | ((uint32_t)p[4 * k + 2] << 8) | p[4 * k + 3]; return x; };
+  if (mode < 0 || mode > 2 || !a || !out_value || !out_flag || (mode == 2 && !b)) return -1;
+  const U256 x = load(a);
+  U256 v = x;
+  uint8_t fl = 0;
+  if (mode == 2) {
+    const U256 m = load(b);
+    uint32_t above = m.w[0] & ~1u;
+    for (int k = 1; k < 8; ++k) above |= m.w[k];
+    const bool ok = (m.w[0] & 1u) && above != 0 && !u256_geq(x.w, m.w);
+    if (ok) fl = (uint8_t)u256_jacobi_symbol(x, m); else fl = 0x80;
+  } else if (u256_geq(x.w, C_Q)) {
+    fl = 0x80;
+  } else if (mode == 1) {
+    Fp xm, rhs;
+    hash_curve_rhs(xm, rhs, x);
+    v = fp_to_u256(rhs);
+    G1Affine p;
+    fl = (uint8_t)((u256_is_square_mod_q(v) ? 1 : 0) | (hash_point_from_candidate(p, x) ? 2 : 0));
+  } else {
+    fl = u256_is_square_mod_q(x) ? 1 : 0;
+  }
+  if (fl & 0x80) v = U256{};
+  for (int k = 0; k < 8; ++k) { const uint32_t w = v.w[7 - k]; out_value[4 * k] = (uint8_t)(w >> 24); out_value[4 * k + 1] = (uint8_t)(w >> 16); out_value[4 * k + 2] = (uint8_t)(w >> 8); out_value[4 * k + 3] = (uint8_t)w; }
+  *out_flag = fl;
+  return 0;
+}
 }  // extern "C"

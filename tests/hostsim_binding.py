@@ -42,6 +42,7 @@ def lib():
         L.hs_g2_decompress_raw.argtypes = [cp, cp]
         L.hs_g1_mul_u128.argtypes = [cp, cp, cp]
         L.hs_verify_randomized.argtypes = [cp, ctypes.POINTER(ctypes.c_uint64), cp, cp, ctypes.c_uint64, ctypes.c_uint32, cp, cp, cp]
+        L.hs_jacobi.argtypes = [ctypes.c_int, cp, cp, cp, cp]
         _lib = L
     return _lib
 
@@ -111,6 +112,14 @@ def sign(msg, sk):
 
 def fp_op(op, a, b=None):
     o = _b(32); st = lib().hs_fp_op(op, bytes(a), None if b is None else bytes(b), o); return st, o.raw
+
+
+def jacobi(mode, a, b=None):
+    """modes and flag bits of bn254_debug_jacobi on Python integers -> (the integer handed to the passes, the flag byte)"""
+    v, f = _b(32), _b(1)
+    rc = lib().hs_jacobi(mode, int(a).to_bytes(32, "big"), None if b is None else int(b).to_bytes(32, "big"), v, f)
+    assert rc == 0, (mode, rc)
+    return int.from_bytes(v.raw, "big"), f.raw[0]
 
 
 def fp12_op(op, a, b=None):

@@ -86,6 +86,22 @@ def threshold_deal(secret, t, n, seed):
     return [PrivateKey(sum(c * pow(x, e, _R) for e, c in enumerate(coeffs)) % _R) for x in range(1, int(n) + 1)]
 
 
+def threshold_commitments(secret, t, seed):
+    """The Feldman commitments C_k = a_k * G2::one(), k < t, of the polynomial threshold_deal(secret, t, n, seed) shares — the same
+    coefficients from the same generator — as t PublicKeys, C_0 = the group key.  What a dealer publishes beside the shares:
+    ECDSA.register_keys_from_commitments derives the n share keys from them, ECDSA.batch_verify_dealt_shares checks a share against them.
+    Under the warning of threshold_deal: pure Python integers and the C ABI, for tests and examples."""
+    import random
+    if int(t) < 1:
+        raise ValueError("need 1 <= t")
+    rnd = random.Random(seed)
+    coeffs = [int(secret) % _R] + [rnd.randrange(_R) for _ in range(int(t) - 1)]
+    out, st = _eng().batch_g2_mul(None, b"".join(c.to_bytes(32, "big") for c in coeffs), len(coeffs), reduce_scalar=True)
+    for b in st:
+        _raise(b)
+    return [PublicKey(out[128 * k:128 * k + 128]) for k in range(len(coeffs))]
+
+
 def _neg_fq_bytes(b):
     v = int.from_bytes(b, "big")
     return (0 if v == 0 else _Q - v).to_bytes(32, "big")
@@ -580,6 +596,73 @@ class ECDSA:
         if register:
             ECDSA.register_group_key(key, eng)
         return key
+
+    @staticmethod
+    def commitments_eval(commitments, xs, engine=None):
+        """The polynomial with the G2 coefficients `commitments` (PublicKeys, lowest degree first: a dealer's Feldman commitments) at the
+        integer points xs (each 0 <= x < 2^32): [sum x^k C_k as a PublicKey, ..] (include/bn254_hip.h: bn254_batch_g2_poly_eval).  The share
+        key of key index j is the value at x = j + 1.  Raises the first commitment's decode Error."""
+        cs, xs = list(commitments), [int(x) for x in xs]
+        if any(len(c.raw) != _engine.G2_BYTES for c in cs):
+            raise Error(ErrorKind.InvalidLength)
+        if any(x < 0 or x >= 1 << 32 for x in xs):
+            raise Error(ErrorKind.IndexOutOfBounds)
+        out, st = (engine or _eng()).batch_g2_poly_eval(b"".join(c.raw for c in cs), [0, len(cs)], [0] * len(xs), xs)
+        for b in st:
+            _raise(b)
+        return [PublicKey(out[128 * e:128 * e + 128]) for e in range(len(xs))]
+
+    @staticmethod
+    def register_keys_from_commitments(commitments, n, register_group_key=False, engine=None):
+        """Register the n share keys pk_j = f(j + 1) * G2 of the dealing whose Feldman commitments these are, derived on the device
+        (include/bn254_hip.h: bn254_ctx_register_keys_commitments) — ECDSA.register_keys on commitments_eval(commitments, 1 .. n) without the
+        keys crossing to the host and back.  result[j] is None or the Error register_keys would give key j.  A commitment that does not
+        decode raises its Error, and then NO keys are registered.  With register_group_key=True commitments[0] is then named as the group
+        key (ECDSA.register_group_key, whose checks apply).  ECDSA.check_dealing(len(commitments)) passes on such a set by construction."""
+        cs = list(commitments)
+        if not cs or int(n) < 1 or int(n) >= 1 << 32 or any(len(c.raw) != _engine.G2_BYTES for c in cs):
+            raise Error(ErrorKind.InvalidLength)
+        eng = engine or _eng()
+        key_st, st = eng.register_keys_commitments(b"".join(c.raw for c in cs), int(n))
+        _raise(st)
+        if register_group_key:
+            ECDSA.register_group_key(cs[0], eng)
+        return [None if s == 0 else Error(s) for s in key_st]
+
+    @staticmethod
+    def combine_commitments(vectors, engine=None):
+        """The commitments of the SUM of the qualified dealers' polynomials (a DKG's last step): the element-wise sum of their commitment
+        vectors, all of one length, through bn254_batch_g2_sum — [sum_d vectors[d][k] for k].  Raises the first decode Error."""
+        vs = [list(v) for v in vectors]
+        if not vs or not vs[0] or any(len(v) != len(vs[0]) for v in vs):
+            raise Error(ErrorKind.InvalidLength)
+        t, d = len(vs[0]), len(vs)
+        out, st = (engine or _eng()).batch_g2_sum(b"".join(vs[i][k].raw for k in range(t) for i in range(d)), [k * d for k in range(t + 1)])
+        for b in st:
+            _raise(b)
+        return [PublicKey(out[128 * k:128 * k + 128]) for k in range(t)]
+
+    @staticmethod
+    def batch_verify_dealt_shares(vectors, index, secrets, engine=None):
+        """What the holder of key `index` checks in a DKG round: dealer d's share secrets[d] (a PrivateKey) is good iff secrets[d] * G2::one()
+        equals dealer d's commitment vector vectors[d] evaluated at index + 1.  The left sides by the fixed-base key derivation, the right
+        sides by ONE bn254_batch_g2_poly_eval over all the vectors.  Returns one verdict per dealer: None, Error(VerificationFailed), or the
+        decode Error of that dealer's first faulty commitment."""
+        vs, sks = [list(v) for v in vectors], list(secrets)
+        if len(vs) != len(sks) or int(index) < 0 or int(index) + 1 >= 1 << 32:
+            raise Error(ErrorKind.InvalidLength)
+        if not vs:
+            return []
+        eng = engine or _eng()
+        left, st = eng.batch_g2_mul(None, b"".join(k.to_bytes() for k in sks), len(sks), reduce_scalar=True)
+        for b in st:
+            _raise(b)
+        off = [0]
+        for v in vs:
+            off.append(off[-1] + len(v))
+        right, rst = eng.batch_g2_poly_eval(b"".join(c.raw for v in vs for c in v), off, list(range(len(vs))), [int(index) + 1] * len(vs))
+        return [Error(rst[d]) if rst[d] else None if left[128 * d:128 * d + 128] == right[128 * d:128 * d + 128] else Error(ErrorKind.VerificationFailed)
+                for d in range(len(vs))]
 
     @staticmethod
     def g2_msm(points, scalars, engine=None):

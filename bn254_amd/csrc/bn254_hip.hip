@@ -787,6 +787,7 @@ int bn254_ctx_create(int hip_device, bn254_ctx** out) {
   c->bmr_group_tuples = BITMAP_RAND_GROUP_TUPLES_DEFAULT;
   c->bmr_max_keys = BITMAP_RAND_MAX_KEYS_DEFAULT;
   c->collect_wave_min = COLLECT_WAVE_MIN_SHARES_DEFAULT;
+  c->pe_wave_min = POLY_EVAL_WAVE_MIN_COEFFS_DEFAULT;
   c->collect_rand_min_shares = COLLECT_RAND_MIN_SHARES_DEFAULT;
   c->collect_rand_min_per_key = COLLECT_RAND_MIN_PER_KEY_DEFAULT;
   c->collect_opt_min_shares = COLLECT_OPT_MIN_SHARES_DEFAULT;
@@ -994,6 +995,7 @@ int bn254_ctx_set_option(bn254_ctx* c, int option, int value) {
   if (option == BN254_OPT_BITMAP_RAND_MIN_TUPLES) { if (value < 0) return BN254_E_BAD_ARGUMENT; c->bmr_min_tuples = value; return 0; }
   if (option == BN254_OPT_BITMAP_RAND_MAX_KEYS) { if (value < 0) return BN254_E_BAD_ARGUMENT; c->bmr_max_keys = value; return 0; }
   if (option == BN254_OPT_COLLECT_WAVE_MIN_SHARES) { if (value < 1) return BN254_E_BAD_ARGUMENT; c->collect_wave_min = value; return 0; }
+  if (option == BN254_OPT_POLY_EVAL_WAVE_MIN_COEFFS) { if (value < 1) return BN254_E_BAD_ARGUMENT; c->pe_wave_min = value; return 0; }
   if (option == BN254_OPT_COLLECT_RAND_MIN_SHARES) { if (value < 0) return BN254_E_BAD_ARGUMENT; c->collect_rand_min_shares = value; return 0; }
   if (option == BN254_OPT_COLLECT_RAND_MIN_PER_KEY) { if (value < 0) return BN254_E_BAD_ARGUMENT; c->collect_rand_min_per_key = value; return 0; }
   if (option == BN254_OPT_THRESHOLD_OPT_MIN_SHARES) { if (value < 0) return BN254_E_BAD_ARGUMENT; c->th_opt_min_shares = value; return 0; }

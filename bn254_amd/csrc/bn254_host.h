@@ -162,6 +162,7 @@ struct bn254_ctx {
   int32_t *gk_lines, *gk_xy;
   uint8_t *gk_st, *gk_inf;
   bool gk_set;
+  int pe_wave_min;           // BN254_OPT_POLY_EVAL_WAVE_MIN_COEFFS (bn254_polyeval.hip): polynomials with at least this many coefficients are evaluated by a wave each
   int th_opt_min_shares;     // BN254_OPT_THRESHOLD_OPT_MIN_SHARES: the optimistic threshold call from this many shares on
   uint32_t* tho_stats;       // what its last call did on the device (bn254_debug_threshold_opt_last); inside collect_buf
   int tho_last_ran;          // ... and whether that call took the optimistic route at all

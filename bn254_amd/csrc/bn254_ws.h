@@ -274,7 +274,9 @@ __attribute__((visibility("hidden"))) int bn254_pair_bitmap_sum(const uint32_t* 
 #define BITMAP_RAND_GROUP_TUPLES_DEFAULT 4096      // BN254_OPT_BITMAP_RAND_GROUP_TUPLES: tuples per group of its combined checks (the sweeps at 65 536 and 2^20 x 256)
 #define COLLECT_WAVE_MIN_SHARES_DEFAULT 16         // BN254_OPT_COLLECT_WAVE_MIN_SHARES (bn254_collect.hip): tuples with at least this many shares are summed by a
                                                    //     wave each, the shorter ones by a lane each — swept at three shapes only
-#define COLLECT_RAND_MIN_SHARES_DEFAULT 65664      // BN254_OPT_COLLECT_RAND_MIN_SHARES: bn254_batch_collect_keyed_bitmap_randomized groups the shares from this many on
+#define POLY_EVAL_WAVE_MIN_COEFFS_DEFAULT 16       // BN254_OPT_POLY_EVAL_WAVE_MIN_COEFFS (bn254_polyeval.hip): polynomials with at least this many coefficients are
+                                                   //     evaluated by a wave each, the shorter ones by a lane each — swept: 8 stays with the lanes, 16 ties or wins in waves
+#define COLLECT_RAND_MIN_SHARES_DEFAULT 65664     // BN254_OPT_COLLECT_RAND_MIN_SHARES: bn254_batch_collect_keyed_bitmap_randomized groups the shares from this many on
                                                    //     (the smallest measured size at which it wins; at 45 056 shares it ties or loses: DESIGN.md §10f)
 #define COLLECT_RAND_MIN_PER_KEY_DEFAULT 42        // BN254_OPT_COLLECT_RAND_MIN_PER_KEY: ... and from this many shares per registered key on (the smallest measured
                                                    //     ratio at which it wins; at 10 per key it loses, nothing measured in between)

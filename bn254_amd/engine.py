@@ -65,6 +65,7 @@ OPT_MERGE_OPT_MIN_PARTS = 45        # merge_keyed_bitmap_optimistic: the exact m
 MERGE_OPT_MIN_PARTS_DEFAULT = 64    # ... as bn254_ws.h has it
 OPT_THRESHOLD_OPT_MIN_SHARES = 46   # threshold_combine_keyed_optimistic: the exact threshold call below this many shares (default 513, measured: DESIGN.md §10l); 0 = no lower bound
 THRESHOLD_OPT_MIN_SHARES_DEFAULT = 513    # ... as bn254_ws.h has it
+OPT_POLY_EVAL_WAVE_MIN_COEFFS = 0   # batch_g2_poly_eval, register_keys_commitments: polynomials with at least this many coefficients are evaluated by a wave each (same bytes)
 OPT_COLLECT_WAVE_MIN_SHARES = 37   # collect_keyed_bitmap: tuples with at least this many shares are summed by a wave each (default 16; swept at three shapes only)
 
 
@@ -431,6 +432,43 @@ class Engine:
     def batch_g2_msm_device(self, d_points, d_scalars, d_seg_off, n, d_out, d_status, reduce_scalar=False, stream=None):
         _check("bn254_batch_g2_msm_device",
                self._lib.bn254_batch_g2_msm_device(self._h, d_points, d_scalars, d_seg_off, n, int(reduce_scalar), d_out, d_status, stream))
+
+    def batch_g2_poly_eval(self, coeffs, poly_off, eval_poly, eval_x):
+        """polynomials with G2 coefficients at small integer points (include/bn254_hip.h: bn254_batch_g2_poly_eval): polynomial i is the
+        coefficients poly_off[i] .. poly_off[i+1] of `coeffs` (128 B each, lowest degree first); evaluation e is (eval_poly[e], eval_x[e]),
+        x any uint32.  Returns (the q values sum x^k C_k, the q status bytes)."""
+        p = len(poly_off) - 1
+        m = int(poly_off[p]) if p >= 0 else 0
+        q = len(eval_poly)
+        assert p >= 0 and len(coeffs) == m * G2_BYTES and len(eval_x) == q
+        off = (ctypes.c_uint64 * (p + 1))(*poly_off)
+        polys = (ctypes.c_uint32 * max(q, 1))(*eval_poly)
+        xs = (ctypes.c_uint32 * max(q, 1))(*eval_x)
+        out = ctypes.create_string_buffer(max(q, 1) * G2_BYTES)
+        status = ctypes.create_string_buffer(max(q, 1))
+        _check("bn254_batch_g2_poly_eval", self._lib.bn254_batch_g2_poly_eval(self._h, bytes(coeffs), off, p, polys, xs, q, out, status))
+        return out.raw[:q * G2_BYTES], status.raw[:q]
+
+    def batch_g2_poly_eval_device(self, d_coeffs, d_poly_off, p, d_eval_poly, d_eval_x, q, d_out, d_status, stream=None):
+        _check("bn254_batch_g2_poly_eval_device",
+               self._lib.bn254_batch_g2_poly_eval_device(self._h, d_coeffs, d_poly_off, p, d_eval_poly, d_eval_x, q, d_out, d_status, stream))
+
+    def register_keys_commitments(self, commitments, n_keys, flags=0):
+        """register pk_j = f(j + 1) * G2, j < n_keys, from the t Feldman commitments of f (include/bn254_hip.h:
+        bn254_ctx_register_keys_commitments).  Returns (the per-key status bytes, the call's status): a commitment that does not decode gives
+        (None, its decode status) and leaves the context without keys.  Does not install the group key: set_group_key(commitments[:128]) does."""
+        t = len(commitments) // G2_BYTES
+        assert len(commitments) == t * G2_BYTES
+        key_st = ctypes.create_string_buffer(max(n_keys, 1))
+        st = ctypes.create_string_buffer(1)
+        self.group_key_set = False
+        self.n_registered_keys = 0
+        _check("bn254_ctx_register_keys_commitments",
+               self._lib.bn254_ctx_register_keys_commitments(self._h, bytes(commitments), t, n_keys, flags, key_st, st))
+        if st.raw[0] != 0:
+            return None, st.raw[0]
+        self.n_registered_keys = n_keys
+        return key_st.raw[:n_keys], 0
 
     def check_dealing(self, threshold, seed32):
         """are the registered keys a `threshold`-of-n dealing, and which group key do they interpolate to (include/bn254_hip.h:

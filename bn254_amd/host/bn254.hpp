@@ -546,6 +546,81 @@ struct ECDSA {
     if (register_key) register_group_key(key, e);
     return key;
   }
+  // FELDMAN COMMITMENTS (include/bn254_hip.h: bn254_batch_g2_poly_eval, bn254_ctx_register_keys_commitments).  A dealer publishes the
+  // commitments C_k = a_k * G2 of its polynomial, lowest degree first; the share key of key index j is their value at x = j + 1.
+  // commitments_eval: the polynomial with these coefficients at each of xs, sum x^k C_k; throws the first commitment's decode Error.
+  static std::vector<PublicKey> commitments_eval(const std::vector<PublicKey>& commitments, const std::vector<uint32_t>& xs,
+                                                 Engine& e = Engine::default_engine()) {
+    const size_t t = commitments.size(), q = xs.size();
+    std::vector<uint8_t> c(t * 128 + 4, 0), out(q * 128 + 4, 0), st(q + 1, 0);
+    for (size_t k = 0; k < t; ++k) std::memcpy(&c[128 * k], commitments[k].raw.data(), 128);
+    const uint64_t off[2] = {0, t};
+    const std::vector<uint32_t> poly(q + 1, 0);
+    check_rc("bn254_batch_g2_poly_eval", bn254_batch_g2_poly_eval(e.raw(), c.data(), off, 1, poly.data(), xs.data(), q, out.data(), st.data()));
+    std::vector<PublicKey> values(q);
+    for (size_t i = 0; i < q; ++i) {
+      check_status(st[i]);
+      std::memcpy(values[i].raw.data(), &out[128 * i], 128);
+    }
+    return values;
+  }
+  // register the n share keys of the dealing these commitments belong to, derived on the device: register_keys on
+  // commitments_eval(commitments, 1 .. n) without the keys crossing to the host and back.  result[j] == 0 or the ErrorKind of key j; a
+  // commitment that does not decode throws its Error, and then NO keys are registered.  register_key: commitments[0] is then named as the
+  // group key (register_group_key, whose checks apply).  check_dealing(commitments.size(), seed) passes on such a set by construction.
+  static std::vector<uint8_t> register_keys_from_commitments(const std::vector<PublicKey>& commitments, size_t n, bool register_key = false,
+                                                             Engine& e = Engine::default_engine()) {
+    if (commitments.empty() || n == 0) throw Error(ErrorKind::InvalidLength);
+    std::vector<uint8_t> c(commitments.size() * 128), key_status(n, 0);
+    for (size_t k = 0; k < commitments.size(); ++k) std::memcpy(&c[128 * k], commitments[k].raw.data(), 128);
+    uint8_t st = 0;
+    check_rc("bn254_ctx_register_keys_commitments",
+             bn254_ctx_register_keys_commitments(e.raw(), c.data(), (uint32_t)commitments.size(), n, 0, key_status.data(), &st));
+    check_status(st);
+    if (register_key) register_group_key(commitments[0], e);
+    return key_status;
+  }
+  // the commitments of the SUM of the qualified dealers' polynomials: the element-wise sum of their vectors, all of one length
+  static std::vector<PublicKey> combine_commitments(const std::vector<std::vector<PublicKey>>& vectors, Engine& e = Engine::default_engine()) {
+    if (vectors.empty() || vectors[0].empty()) throw Error(ErrorKind::InvalidLength);
+    const size_t d = vectors.size(), t = vectors[0].size();
+    std::vector<uint8_t> pts(d * t * 128), out(t * 128), st(t, 0);
+    std::vector<uint64_t> seg(t + 1);
+    for (size_t k = 0; k <= t; ++k) seg[k] = k * d;
+    for (size_t i = 0; i < d; ++i) {
+      if (vectors[i].size() != t) throw Error(ErrorKind::InvalidLength);
+      for (size_t k = 0; k < t; ++k) std::memcpy(&pts[128 * (k * d + i)], vectors[i][k].raw.data(), 128);
+    }
+    check_rc("bn254_batch_g2_sum", bn254_batch_g2_sum(e.raw(), pts.data(), seg.data(), t, out.data(), st.data()));
+    std::vector<PublicKey> sum(t);
+    for (size_t k = 0; k < t; ++k) {
+      check_status(st[k]);
+      std::memcpy(sum[k].raw.data(), &out[128 * k], 128);
+    }
+    return sum;
+  }
+  // what the holder of key `index` checks in a DKG round: result[d] == 0 iff secrets[d] * G2::one() equals dealer d's vector at index + 1,
+  // 9 (VerificationFailed) if not, else the decode ErrorKind of that dealer's first faulty commitment
+  static std::vector<uint8_t> batch_verify_dealt_shares(const std::vector<std::vector<PublicKey>>& vectors, uint32_t index,
+                                                        const std::vector<PrivateKey>& secrets, Engine& e = Engine::default_engine()) {
+    const size_t d = vectors.size();
+    if (secrets.size() != d || index == UINT32_MAX) throw Error(ErrorKind::InvalidLength);
+    std::vector<uint64_t> off(d + 1, 0);
+    for (size_t i = 0; i < d; ++i) off[i + 1] = off[i] + vectors[i].size();
+    std::vector<uint8_t> c(off[d] * 128 + 4, 0), right(d * 128 + 4, 0), st(d + 1, 0);
+    std::vector<uint32_t> poly(d + 1, 0), xs(d + 1, index + 1);
+    for (size_t i = 0; i < d; ++i) {
+      poly[i] = (uint32_t)i;
+      for (size_t k = 0; k < vectors[i].size(); ++k) std::memcpy(&c[128 * (off[i] + k)], vectors[i][k].raw.data(), 128);
+    }
+    check_rc("bn254_batch_g2_poly_eval", bn254_batch_g2_poly_eval(e.raw(), c.data(), off.data(), d, poly.data(), xs.data(), d, right.data(), st.data()));
+    std::vector<uint8_t> verdict(d, 0);
+    for (size_t i = 0; i < d; ++i) {
+      const PublicKey left = PublicKey::from_private_key(secrets[i], e);
+      verdict[i] = st[i] ? st[i] : std::memcmp(left.raw.data(), &right[128 * i], 128) == 0 ? 0 : (uint8_t)ErrorKind::VerificationFailed;
+    }
+    return verdict;
+  }
   // The inner node of an aggregation tree (include/bn254_hip.h: bn254_batch_merge_keyed_bitmap): one message and PARTIAL aggregates of it,
   // parts[k] = a summed signature and the indices of the registered keys it is said to sum.  Every partial is verified as verify_keyed_signers
   // verifies it; in the order given, the valid ones whose indices do not overlap what was taken before are added (first fit).

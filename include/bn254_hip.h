@@ -281,7 +281,8 @@ int bn254_batch_g1_msm(bn254_ctx *ctx, const uint8_t *points /* m*64 */, const u
 int bn254_batch_g1_msm_device(bn254_ctx *ctx, const uint8_t *d_points, const uint8_t *d_scalars, const uint64_t *d_seg_off, size_t n,
                               int reduce_scalar, uint8_t *d_out, uint8_t *d_status, void *stream);
 /* ... and in G2: out[i] = sum over the terms s in [seg_off[i], seg_off[i+1]) of scalars[s] * points[s], 128-byte points and outputs — the
- * building block for group keys (sum lambda_k pk_k), for evaluating a vector of commitments (sum x^k C_k) and for the dealing check below.
+ * building block for group keys (sum lambda_k pk_k), for linear combinations of commitments and for the dealing check below (a vector of
+ * commitments at small integer points, sum x^k C_k, has a call of its own that needs no scalars: bn254_batch_g2_poly_eval).
  * Same argument list, argument checks, alignment rules and range rule of the _device form as bn254_batch_g1_msm above; the _device form makes
  * the same single 8-byte copy of d_seg_off[n] and so cannot be captured into a graph either.  Scratch: 217 B per term.
  * DEFINING IDENTITY: byte for byte bn254_batch_g2_mul(points, scalars, reduce_scalar) followed by bn254_batch_g2_sum of the products over
@@ -943,6 +944,67 @@ int bn254_ctx_set_group_key(bn254_ctx *ctx, const uint8_t *group_pk /* 128, or N
 int bn254_ctx_check_dealing(bn254_ctx *ctx, uint32_t threshold, const uint8_t *seed32 /* host */, uint32_t flags /* must be 0 */,
                             uint8_t *group_pk /* 128 */, uint8_t *status /* 1 */, uint32_t *bad_key /* 1, or NULL */);
 
+/* EVALUATE COMMITMENT VECTORS: p polynomials with G2 coefficients (lowest degree first; polynomial i is the coefficients
+ * [poly_off[i], poly_off[i+1]) of the m = poly_off[p] given) and q evaluations; evaluation e is the pair (polynomial eval_poly[e], point
+ * eval_x[e]), x any uint32:  out[e] = sum over k of x^k C_k, with 0^0 = 1, so x = 0 returns C_0.  What a committee does with the t Feldman
+ * commitments C_k = a_k G2 a dealer or a DKG round hands it: pk_j = f(j + 1) G2 for its n validators, and the check of a received share
+ * against a dealer's vector (secret * G2 == the vector at index + 1).
+ * DEFINING IDENTITY: out[e] and status[e] are byte for byte bn254_batch_g2_msm over ONE segment holding that polynomial's coefficients, with
+ * the scalars x^k mod r as 32 big-endian bytes and reduce_scalar = 0.  So: coefficients are decoded with flags 0 (on the curve, NO subgroup
+ * check); the first non-zero decode status in coefficient order wins and the output is then 128 zero bytes; an empty polynomial gives the
+ * identity with status 0; the identity is a legal coefficient.  In addition eval_poly[e] >= p reads status 2 with the identity, and in the
+ * _device form so does a polynomial whose offsets are reversed or run past d_poly_off[p], with no read outside the buffers; a fault in one
+ * polynomial touches only the evaluations that name it.  (The identity is one of group elements of order r.  For a coefficient OUTSIDE the
+ * order-r subgroup — legal under flags 0 — it holds while x^k < r, i.e. where x^k mod r is x^k; beyond that Horner's rule multiplies by the
+ * integer x where the identity's scalar was reduced, and the result is the layout's.  A key made of such coefficients is judged by the
+ * registration's own subgroup check, below.)
+ * Argument checks and alignment are those of bn254_batch_g2_msm: p, q < 2^32, at most 2^32 - 1 coefficients; host form: poly_off
+ * non-decreasing, else BN254_E_BAD_ARGUMENT; _device form: d_poly_off 8-byte aligned, d_coeffs, d_eval_poly, d_eval_x and d_out 4-byte
+ * aligned, else BN254_E_MISALIGNED.  As there the _device form copies d_poly_off[p] home to size its scratch (146 B per coefficient): ONE
+ * 8-byte copy and a wait for the stream before anything is enqueued, so it cannot be captured into a graph.  One call per context in flight.
+ * Cost: the coefficients are decoded ONCE (a lane each), not once per evaluation.  An evaluation of a polynomial of fewer than
+ * BN254_OPT_POLY_EVAL_WAVE_MIN_COEFFS coefficients is one lane's Horner walk from the top coefficient, acc <- x acc + C_k: per coefficient
+ * one doubling per bit of x, one complete addition per set bit, one mixed addition — about 20 group operations for a 9-to-13-bit x where a
+ * 256-step ladder spends about 320 —, the loop bounds those of the longest polynomial and the widest x in the wave.  A longer polynomial is
+ * a wave's: lane c walks the chunk [c L, (c+1) L), L = ceil(len / 64), multiplies its partial by x^(c L) mod r (Fr on the device, then the
+ * 256-step ladder over the partial brought to affine form) and the six-level tree of the sums folds the 64 products; one inversion per
+ * evaluation in either layout, and one per lane in the wave layout.
+ * Measured on an MI355X (tools/poly_eval_throughput.py, profiles/poly_eval.jsonl; whole calls under a host clock, staging on both sides, median
+ * [min, max] of 7 alternating runs after 2 warm-up runs; the baseline is the route that exists without the call: the scalars x^k mod r in
+ * Python integers, then bn254_batch_g2_msm over n segments of t terms, each part timed): the share keys of n = 256, t = 171: 6.11 ms [6.03,
+ * 6.11] against 5.89 [5.85, 6.09] for the scalars + 7.09 [6.86, 7.23] for g2_msm; 1 024, 683: 12.4 [11.3, 28.3] against 98.1 + 73.5
+ * [73.4, 75.0]; 4 096, 2 731: 109.8 [109.5, 110.3] against 1 550 + 1 193 — the baseline there was run on the first 256 keys and SCALED by 16
+ * (in full it stages 1.4 GB of points).  The _device form under events: 5.96, 11.09 and 107.4 ms.  64 polynomials of 171 coefficients at
+ * one 13-bit x (the share check of a DKG round): 5.83 [5.82, 5.83] against 1.50 + 5.49 [5.48, 5.51] — bn254_batch_g2_msm ALONE is 0.3 ms
+ * faster there, outside both spreads; this call wins only by the scalars it does not need.  Which call when: this one for evaluation points
+ * below 2^32 — it needs no scalars, stages every coefficient once and its scratch is 146 B per coefficient, not 217 B per term —;
+ * bn254_batch_g2_msm for scalars that are not powers of a small integer, and, where the scalars are at hand already, for a few dozen
+ * evaluations of polynomials of about 171 coefficients, where the two are within 6 %.  bn254_ctx_register_keys_commitments against
+ * evaluation, keys home, bn254_ctx_register_keys: 13.36 [13.35, 13.38] against 13.46 [13.42, 13.48] at (256, 171), 19.54 against 19.68
+ * (spreads overlap) at (1 024, 683), 116.96 against 116.95 at (4 096, 2 731): a tie — the registration's own line tables are the cost, the
+ * round trip of 128 B per key is not; what the call saves is the host's part.  bn254_batch_g2_msm (171 terms) and bn254_ctx_check_dealing
+ * (256, 171) in this build against the parent's: 5.40 and 7.04 ms against 5.39 and 7.08, within the spreads.
+ * Unmeasured: other thresholds, more than 4 096 keys, x wider than 13 bits at scale, the multi-GPU layer.
+ * DESIGN.md section 10n.  Out of scope: the multi-GPU layer, compressed commitments, a G1 form, non-integer or 256-bit evaluation points, a
+ * forward-difference scheme for consecutive points. */
+int bn254_batch_g2_poly_eval(bn254_ctx *ctx, const uint8_t *coeffs /* m*128 */, const uint64_t *poly_off /* p+1 */, size_t p,
+                             const uint32_t *eval_poly /* q */, const uint32_t *eval_x /* q */, size_t q, uint8_t *out /* q*128 */,
+                             uint8_t *status /* q */);
+int bn254_batch_g2_poly_eval_device(bn254_ctx *ctx, const uint8_t *d_coeffs, const uint64_t *d_poly_off, size_t p, const uint32_t *d_eval_poly,
+                                    const uint32_t *d_eval_x, size_t q, uint8_t *d_out, uint8_t *d_status, void *stream);
+/* REGISTER THE SHARE KEYS OF A COMMITMENT VECTOR: pk_j = f(j + 1) G2 = sum over k < t of (j + 1)^k C_k for j < n_keys, from the t
+ * commitments (host memory, uncompressed).  The evaluation's output stays in device memory and is read where it lies by the kernel every
+ * registration runs; only key_status and one status byte come home.
+ * DEFINING IDENTITY: the context afterwards is indistinguishable from bn254_ctx_register_keys on the n_keys outputs of
+ * bn254_batch_g2_poly_eval at x = 1 .. n_keys with the same flags; registration's own subgroup check still judges every key.  Like every
+ * registration it quiesces the context and drops the previous key set and the group key first.  If a commitment does not decode, *status is
+ * that decode status (the lowest index wins), NO keys are registered (the context then has none) and key_status is untouched; otherwise
+ * *status = 0.  BN254_E_BAD_ARGUMENT: t == 0, n_keys == 0, n_keys >= 2^32, NULL commitments or status.  The call does NOT install the group
+ * key: the caller names C_0 with bn254_ctx_set_group_key, which applies its own checks.  A key set registered this way passes
+ * bn254_ctx_check_dealing at threshold t by construction. */
+int bn254_ctx_register_keys_commitments(bn254_ctx *ctx, const uint8_t *commitments /* t*128, host */, uint32_t t, size_t n_keys, uint32_t flags,
+                                        uint8_t *key_status /* n_keys, or NULL */, uint8_t *status /* 1 */);
+
 /* OPTIMISTIC THRESHOLD COMBINE: interpolate first, verify the result once per tuple under the group key.  The interpolated signature is
  * unique: if it verifies under f(0) * G2::one() it is THE group signature whatever the individual shares were, so one pairing check per
  * tuple proves the output — and proves exactly what the consumer will check.  (The optimistic collect's check of the plain sum cannot be
@@ -1126,6 +1188,15 @@ int bn254_ctx_set_profiling(bn254_ctx *ctx, int enabled);
                                                 [3.78, 4.00] against 4.03 [3.97, 4.12] — it wins by more than the exact call's own spread); no
                                                 measured size loses with every share valid, and nothing below 513 shares was measured, so
                                                 smaller calls take the exact call; 0 = no lower bound */
+#define BN254_OPT_POLY_EVAL_WAVE_MIN_COEFFS 0 /* (number 0: 1 to 46 are taken and tests/test_threshold_optimistic.py pins 46 as the highest)
+                                                  bn254_batch_g2_poly_eval, bn254_ctx_register_keys_commitments: polynomials with at least this many
+                                                  coefficients are evaluated by a wave each, shorter ones by a lane each (same bytes
+                                                  either way; 1 = always a wave, a large value = always a lane).  Default 16, swept (tools/poly_eval_throughput.py --sweep, profiles/poly_eval.jsonl;
+                                                  256 evaluations of one polynomial, host form, median of 7): 8 coefficients 2.63 ms in lanes against
+                                                  5.45 in waves; 16 coefficients 5.44 against 5.45 at a 9-bit x (a tie) and 6.06 [6.04, 6.07]
+                                                  against 5.46 [5.45, 5.46] at a 13-bit x; 32: 11.1 / 12.4 against 5.45 / 5.47; 64: 22.4 / 25.0
+                                                  against 5.45 — 16 is the smallest swept length at which the wave layout wins beyond the
+                                                  spread; nothing between 8 and 16 was measured */
 int bn254_ctx_set_option(bn254_ctx *ctx, int option, int value);
 /* per-kernel times of the last verify-shaped call with profiling on (HIP events on the call's stream):
  * ms[0] decode, ms[1] hash-to-G1, ms[2] Miller loop, ms[3] final exponentiation.  The host-pointer bn254_batch_verify runs

@@ -172,6 +172,10 @@ def load():
         L.bn254_batch_g2_poly_eval.argtypes = [vp, vp, vp, sz, vp, vp, sz, vp, vp]
         L.bn254_batch_g2_poly_eval_device.argtypes = [vp, vp, vp, sz, vp, vp, sz, vp, vp, vp]
         L.bn254_ctx_register_keys_commitments.argtypes = [vp, vp, u32, sz, u32, vp, vp]
+    if hasattr(L, "bn254_ctx_reshare_commitments"):                   # absent from an older build loaded through BN254_LIB
+        L.bn254_batch_g2_vector_combine.argtypes = [vp, vp, vp, sz, sz, i32, vp, vp]
+        L.bn254_batch_g2_vector_combine_device.argtypes = [vp, vp, vp, sz, sz, i32, vp, vp, vp]
+        L.bn254_ctx_reshare_commitments.argtypes = [vp, vp, vp, sz, u32, u32, u32, vp, vp, sz, vp, vp]
     L.bn254_debug_bitmap_rand_last.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     L.bn254_debug_bitmap_rand_sums.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), sz, sz, vp, vp, vp, vp, vp, vp]
     L.bn254_batch_verify_keyed_randomized.argtypes = [vp, vp, vp, vp, vp, sz, u32, vp, vp]
@@ -282,4 +286,5 @@ EXPORTED_SYMBOLS = [
     "bn254_batch_g2_msm", "bn254_batch_g2_msm_device", "bn254_ctx_check_dealing", "bn254_debug_dealing_coefficients",
     "bn254_debug_jacobi",
     "bn254_batch_g2_poly_eval", "bn254_batch_g2_poly_eval_device", "bn254_ctx_register_keys_commitments",
+    "bn254_batch_g2_vector_combine", "bn254_batch_g2_vector_combine_device", "bn254_ctx_reshare_commitments",
 ]

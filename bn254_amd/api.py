@@ -102,6 +102,18 @@ def threshold_commitments(secret, t, seed):
     return [PublicKey(out[128 * k:128 * k + 128]) for k in range(len(coeffs))]
 
 
+def threshold_combine_subshares(used_indices, subshares):
+    """What a member of the NEXT committee keeps after a reshare: sum lambda_i(S) * sub_i mod r as a PrivateKey, over the sub-shares it
+    received from the old members S = used_indices (key indices, x = index + 1; the set ECDSA.reshare_commitments reports), sub_i a
+    PrivateKey — old member i's sub-dealing at this member's point.  Under the warning of threshold_deal: pure Python integers, for tests
+    and examples."""
+    keys, subs = [int(k) for k in used_indices], list(subshares)
+    if len(keys) != len(subs) or len(set(keys)) != len(keys) or not keys:
+        raise ValueError("need one sub-share per distinct used index")
+    lam = _lagrange_at_zero([k + 1 for k in keys])
+    return PrivateKey(sum(l * s.value for l, s in zip(lam, subs)) % _R)
+
+
 def _neg_fq_bytes(b):
     v = int.from_bytes(b, "big")
     return (0 if v == 0 else _Q - v).to_bytes(32, "big")
@@ -674,6 +686,49 @@ class ECDSA:
         out, st = (engine or _eng()).batch_g2_msm(b"".join(p.raw for p in pts), b"".join(k.to_bytes(32, "big") for k in ks), [0, len(pts)])
         _raise(st[0])
         return PublicKey(out)
+
+    @staticmethod
+    def g2_vector_combine(vectors, scalars, engine=None):
+        """[sum_i scalars[i] * vectors[i][k] for k]: vectors of PublicKeys, all of one length, one integer (taken mod r) per vector
+        (include/bn254_hip.h: bn254_batch_g2_vector_combine) — a linear combination of commitment vectors.  Raises the first decode Error."""
+        vs, ks = [list(v) for v in vectors], [int(k) % _R for k in scalars]
+        if not vs or not vs[0] or len(vs) != len(ks) or any(len(v) != len(vs[0]) for v in vs) or any(len(p.raw) != _engine.G2_BYTES for v in vs for p in v):
+            raise Error(ErrorKind.InvalidLength)
+        out, st = (engine or _eng()).batch_g2_vector_combine(b"".join(p.raw for v in vs for p in v), b"".join(k.to_bytes(32, "big") for k in ks),
+                                                             len(vs), len(vs[0]))
+        for b in st:
+            _raise(b)
+        return [PublicKey(out[128 * k:128 * k + 128]) for k in range(len(vs[0]))]
+
+    @staticmethod
+    def reshare_commitments(dealers, threshold, engine=None):
+        """Hand the registered (OLD) committee's group key on to the next committee: dealers is an iterable of (key_index, [PublicKey ..]) —
+        old member key_index's commitments to its sub-dealing, threshold_commitments(share.value, t_new, seed), all of one length t_new; it
+        is sorted by index, and a repeated index raises ValueError.  A dealer qualifies if its key is registered and not refused, its
+        commitments decode and the first one IS its registered key; the `threshold` lowest qualified indices S are combined under their
+        Lagrange coefficients (include/bn254_hip.h: bn254_ctx_reshare_commitments).  Returns (the t_new commitments of the new polynomial as
+        PublicKeys — [0] is the unchanged group key; ECDSA.register_keys_from_commitments registers the new committee from them —, the
+        sorted indices used, statuses) with statuses[i] None or the Error of the i-th dealer in index order.  With fewer qualified dealers
+        it raises Error(VerificationFailed) carrying .statuses and .qualified (their indices).  Not checked: that the registered keys are a
+        dealing (ECDSA.check_dealing), that the private sub-shares match the vectors (each recipient's ECDSA.batch_verify_dealt_shares)."""
+        ds = sorted(((int(k), list(v)) for k, v in dealers), key=lambda kv: kv[0])
+        if any(a[0] == b[0] for a, b in zip(ds, ds[1:])):
+            raise ValueError("a dealer index is repeated")
+        if int(threshold) < 1 or int(threshold) >= 1 << 32:
+            raise ValueError("threshold must be between 1 and 2^32 - 1")
+        if not ds or not ds[0][1] or any(len(v) != len(ds[0][1]) for _, v in ds) or any(len(p.raw) != _engine.G2_BYTES for _, v in ds for p in v):
+            raise Error(ErrorKind.InvalidLength)
+        if any(k < 0 or k >= 1 << 32 for k, _ in ds):
+            raise Error(ErrorKind.IndexOutOfBounds)
+        t_new = len(ds[0][1])
+        out, st, dealer_st, row = (engine or _eng()).reshare_commitments(b"".join(p.raw for _, v in ds for p in v), [k for k, _ in ds], t_new, int(threshold))
+        statuses = [None if s == 0 else Error(s) for s in dealer_st]
+        used = [32 * w + b for w, word in enumerate(row) for b in range(32) if (word >> b) & 1]
+        if st != 0:
+            err = Error(st)
+            err.statuses, err.qualified = statuses, used
+            raise err
+        return [PublicKey(out[128 * k:128 * k + 128]) for k in range(t_new)], used, statuses
 
     @staticmethod
     def g1_msm(points, scalars, engine=None):

@@ -151,6 +151,17 @@ static int launch_g2msm(bn254_ctx* c, hipStream_t s, const G2Src& src, const uin
   if (marks) PROF_MARK(3);
   return 0;
 }
+// the sums alone, over terms another unit has written (bn254_host.h; bn254_reshare.hip: its terms are column-major over decoded points)
+int launch_g2msm_sums(bn254_ctx* c, hipStream_t s, const G2Jac* terms, const uint8_t* term_st, size_t m, const uint64_t* d_seg, const uint8_t* d_gate, size_t n,
+                      uint8_t* d_out, uint8_t* d_status) {
+  const uint64_t wave_min = (uint64_t)c->collect_wave_min;
+  k_g2msm_sum_lane<<<grid_for(n), BN_WAVE, 0, s>>>(terms, term_st, d_seg, (uint64_t)m, d_gate, n, wave_min, d_out, d_status);
+  HIP_TRY(hipGetLastError());
+  k_g2msm_sum_wave<<<(unsigned)(n < CL_WAVE_MAX_BLOCKS ? n : CL_WAVE_MAX_BLOCKS), BN_WAVE, 0, s>>>(terms, term_st, d_seg, (uint64_t)m, d_gate, n, wave_min, d_out,
+                                                                                                 d_status);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
 // the _device form behind its argument checks, the number of terms known
 static int g2msm_device(bn254_ctx* c, const uint8_t* d_points, const uint8_t* d_scalars, const uint64_t* d_seg, size_t m, size_t n, int reduce, uint8_t* d_out,
                         uint8_t* d_status, hipStream_t s) {

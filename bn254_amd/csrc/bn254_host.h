@@ -428,3 +428,9 @@ BN_HIDDEN int clo_settle(bn254_ctx* c, hipStream_t s, const ClCall& a, const ClS
 BN_HIDDEN int launch_bitmap_sum_queued(bn254_ctx* c, hipStream_t s, const uint32_t* d_bits, size_t bm_words, size_t n, bool tables, const uint32_t* map,
                                        const uint32_t* count);
 BN_HIDDEN int launch_encode_g1(bn254_ctx* c, hipStream_t s, size_t n, int px, int inf_plane, uint8_t* out, uint8_t* status_out);
+// vectors of G2 points combined column by column (bn254_reshare.hip) run two kernels of other units: the decode of bn254_polyeval.hip — m points
+// into its 146 B layout — and the two segment sums of bn254_dealing.hip over terms the caller has written (m terms, n segments by d_seg,
+// split by BN254_OPT_COLLECT_WAVE_MIN_SHARES, d_gate as in launch_g2msm)
+BN_HIDDEN int launch_pe_decode(hipStream_t s, const uint8_t* d_points, size_t m, int32_t* xy, uint8_t* inf, uint8_t* st);
+BN_HIDDEN int launch_g2msm_sums(bn254_ctx* c, hipStream_t s, const G2Jac* terms, const uint8_t* term_st, size_t m, const uint64_t* d_seg, const uint8_t* d_gate,
+                                size_t n, uint8_t* d_out, uint8_t* d_status);

@@ -149,6 +149,13 @@ KERNEL void k_pe_eval_wave(PeIn in, size_t q, uint64_t wave_min, uint8_t* out, u
     __syncthreads();
   }
 }
+// the decode alone, for the unit that combines vectors (bn254_host.h; bn254_reshare.hip): m points into the 146 B layout, enqueued on s
+int launch_pe_decode(hipStream_t s, const uint8_t* d_points, size_t m, int32_t* xy, uint8_t* inf, uint8_t* st) {
+  if (m == 0) return 0;
+  k_pe_decode<<<grid_for(m), BN_WAVE, 0, s>>>(d_points, m, xy, inf, st);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
 // decode and both layouts, enqueued on s; P holds m coefficients
 static int launch_poly_eval(bn254_ctx* c, hipStream_t s, const uint8_t* d_coeffs, size_t m, const uint64_t* d_poly_off, size_t p, const uint32_t* d_eval_poly,
                             const uint32_t* d_eval_x, size_t q, const PeScratch& P, uint8_t* d_out, uint8_t* d_status) {

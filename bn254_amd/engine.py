@@ -453,6 +453,39 @@ class Engine:
         _check("bn254_batch_g2_poly_eval_device",
                self._lib.bn254_batch_g2_poly_eval_device(self._h, d_coeffs, d_poly_off, p, d_eval_poly, d_eval_x, q, d_out, d_status, stream))
 
+    def batch_g2_vector_combine(self, vectors, scalars, d, length, reduce_scalar=False):
+        """d vectors of `length` G2 points (vector-major, 128 B each) combined column by column under one 32-byte scalar per vector
+        (include/bn254_hip.h: bn254_batch_g2_vector_combine): out[k] = sum_i scalars[i] * vectors[i][k].  Returns (the `length` sums, the
+        `length` status bytes)."""
+        assert len(vectors) == d * length * G2_BYTES and len(scalars) == d * SCALAR_BYTES
+        out = ctypes.create_string_buffer(max(length, 1) * G2_BYTES)
+        status = ctypes.create_string_buffer(max(length, 1))
+        _check("bn254_batch_g2_vector_combine",
+               self._lib.bn254_batch_g2_vector_combine(self._h, bytes(vectors), bytes(scalars), d, length, int(reduce_scalar), out, status))
+        return out.raw[:length * G2_BYTES], status.raw[:length]
+
+    def batch_g2_vector_combine_device(self, d_vectors, d_scalars, d, length, d_out, d_status, reduce_scalar=False, stream=None):
+        _check("bn254_batch_g2_vector_combine_device",
+               self._lib.bn254_batch_g2_vector_combine_device(self._h, d_vectors, d_scalars, d, length, int(reduce_scalar), d_out, d_status, stream))
+
+    def reshare_commitments(self, vectors, dealer_keys, t_new, threshold, bm_words=None):
+        """the commitments of the next committee's polynomial from the sub-dealings of old members (include/bn254_hip.h:
+        bn254_ctx_reshare_commitments): vectors = len(dealer_keys) * t_new commitments, dealer-major; dealer_keys strictly increasing indices
+        into the registered set (the OLD committee).  Returns (the t_new commitments — zero bytes unless the status is 0 —, the call's status,
+        the per-dealer status bytes, the used row as bm_words integers: S on success, else the qualified dealers)."""
+        d = len(dealer_keys)
+        assert len(vectors) == d * t_new * G2_BYTES
+        if bm_words is None:
+            bm_words = max(1, (self.n_registered_keys + 31) // 32)
+        keys = (ctypes.c_uint32 * max(d, 1))(*dealer_keys)
+        dealer_st = ctypes.create_string_buffer(max(d, 1))
+        row = (ctypes.c_uint32 * max(bm_words, 1))()
+        out = ctypes.create_string_buffer(max(t_new, 1) * G2_BYTES)
+        st = ctypes.create_string_buffer(1)
+        _check("bn254_ctx_reshare_commitments",
+               self._lib.bn254_ctx_reshare_commitments(self._h, bytes(vectors), keys, d, int(t_new), int(threshold), 0, dealer_st, row, bm_words, out, st))
+        return out.raw[:t_new * G2_BYTES], st.raw[0], dealer_st.raw[:d], list(row)[:bm_words]
+
     def register_keys_commitments(self, commitments, n_keys, flags=0):
         """register pk_j = f(j + 1) * G2, j < n_keys, from the t Feldman commitments of f (include/bn254_hip.h:
         bn254_ctx_register_keys_commitments).  Returns (the per-key status bytes, the call's status): a commitment that does not decode gives

@@ -14,11 +14,13 @@
 // group operation runs on the GPU.  A failed verification throws Error{VerificationFailed}, like
 // the reference returns Err(Error::VerificationFailed) (not Ok(false)).
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <cstring>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/bn254_hip.h"
@@ -41,6 +43,12 @@ struct NativeError : std::runtime_error {
 };
 inline void check_rc(const char* fn, int rc) { if (rc != 0) throw NativeError(fn, rc); }
 inline void check_status(uint8_t s) { if (s != 0) throw Error((ErrorKind)s); }
+// what ECDSA::reshare_commitments returns, and what it throws when too few dealers qualify (Error(VerificationFailed) with the details)
+struct ReshareFailed : Error {
+  std::vector<uint8_t> statuses;       // per dealer in index order: 0 or its ErrorKind
+  std::vector<uint32_t> qualified;     // the key indices of the dealers that did qualify
+  ReshareFailed(std::vector<uint8_t> st, std::vector<uint32_t> q) : Error(ErrorKind::VerificationFailed), statuses(std::move(st)), qualified(std::move(q)) {}
+};
 
 class Engine {   // one per GPU; not thread-safe (one thread at a time per context)
  public:
@@ -545,6 +553,63 @@ struct ECDSA {
     check_status(st);
     if (register_key) register_group_key(key, e);
     return key;
+  }
+  // VECTORS OF G2 POINTS combined column by column, one scalar per vector (include/bn254_hip.h: bn254_batch_g2_vector_combine):
+  // result[k] = sum_i scalars[i] * vectors[i][k], the scalars 32 big-endian bytes reduced mod r; throws the first decode Error
+  static std::vector<PublicKey> g2_vector_combine(const std::vector<std::vector<PublicKey>>& vectors, const std::vector<std::array<uint8_t, 32>>& scalars,
+                                                  Engine& e = Engine::default_engine()) {
+    if (vectors.empty() || vectors[0].empty() || vectors.size() != scalars.size()) throw Error(ErrorKind::InvalidLength);
+    const size_t d = vectors.size(), len = vectors[0].size();
+    std::vector<uint8_t> v(d * len * 128), k(d * 32), out(len * 128), st(len, 0);
+    for (size_t i = 0; i < d; ++i) {
+      if (vectors[i].size() != len) throw Error(ErrorKind::InvalidLength);
+      for (size_t j = 0; j < len; ++j) std::memcpy(&v[128 * (i * len + j)], vectors[i][j].raw.data(), 128);
+      std::memcpy(&k[32 * i], scalars[i].data(), 32);
+    }
+    check_rc("bn254_batch_g2_vector_combine", bn254_batch_g2_vector_combine(e.raw(), v.data(), k.data(), d, len, 1, out.data(), st.data()));
+    std::vector<PublicKey> sum(len);
+    for (size_t j = 0; j < len; ++j) {
+      check_status(st[j]);
+      std::memcpy(sum[j].raw.data(), &out[128 * j], 128);
+    }
+    return sum;
+  }
+  // RESHARE (include/bn254_hip.h: bn254_ctx_reshare_commitments): hand the registered (OLD) committee's group key on to the next committee.
+  // dealers: (key index, that old member's commitments to its sub-dealing — t_new of them, the first its registered key), sorted here by
+  // index; a repeated index throws std::invalid_argument.  n_keys: the size of the registered set.  The `threshold` lowest qualified
+  // indices are combined under their Lagrange coefficients: commitments[0] is the unchanged group key, and register_keys_from_commitments
+  // registers the new committee from `commitments`.  Too few qualified dealers: throws ReshareFailed.  Not checked: that the registered keys
+  // are a dealing (check_dealing), that the private sub-shares match the vectors (each recipient's batch_verify_dealt_shares).
+  struct Reshare {
+    std::vector<PublicKey> commitments;
+    std::vector<uint32_t> used;          // S: the key indices combined, increasing
+    std::vector<uint8_t> statuses;       // per dealer in index order: 0 or its ErrorKind
+  };
+  static Reshare reshare_commitments(std::vector<std::pair<uint32_t, std::vector<PublicKey>>> dealers, uint32_t threshold, size_t n_keys,
+                                     Engine& e = Engine::default_engine()) {
+    if (dealers.empty() || dealers[0].second.empty() || n_keys == 0) throw Error(ErrorKind::InvalidLength);
+    std::sort(dealers.begin(), dealers.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
+    const size_t d = dealers.size(), t_new = dealers[0].second.size(), bm_words = (n_keys + 31) / 32;
+    std::vector<uint8_t> v(d * t_new * 128), out(t_new * 128), st(d, 0);
+    std::vector<uint32_t> keys(d), row(bm_words, 0);
+    for (size_t i = 0; i < d; ++i) {
+      if (dealers[i].second.size() != t_new) throw Error(ErrorKind::InvalidLength);
+      if (i && dealers[i].first == dealers[i - 1].first) throw std::invalid_argument("a dealer index is repeated");
+      keys[i] = dealers[i].first;
+      for (size_t k = 0; k < t_new; ++k) std::memcpy(&v[128 * (i * t_new + k)], dealers[i].second[k].raw.data(), 128);
+    }
+    uint8_t status = 0;
+    check_rc("bn254_ctx_reshare_commitments", bn254_ctx_reshare_commitments(e.raw(), v.data(), keys.data(), d, (uint32_t)t_new, threshold, 0, st.data(),
+                                                                            row.data(), bm_words, out.data(), &status));
+    Reshare r;
+    for (size_t w = 0; w < bm_words; ++w)
+      for (uint32_t b = 0; b < 32; ++b)
+        if ((row[w] >> b) & 1u) r.used.push_back((uint32_t)(32 * w + b));
+    if (status != 0) throw ReshareFailed(st, r.used);
+    r.statuses = st;
+    r.commitments.resize(t_new);
+    for (size_t k = 0; k < t_new; ++k) std::memcpy(r.commitments[k].raw.data(), &out[128 * k], 128);
+    return r;
   }
   // FELDMAN COMMITMENTS (include/bn254_hip.h: bn254_batch_g2_poly_eval, bn254_ctx_register_keys_commitments).  A dealer publishes the
   // commitments C_k = a_k * G2 of its polynomial, lowest degree first; the share key of key index j is their value at x = j + 1.

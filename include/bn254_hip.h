@@ -1005,6 +1005,82 @@ int bn254_batch_g2_poly_eval_device(bn254_ctx *ctx, const uint8_t *d_coeffs, con
 int bn254_ctx_register_keys_commitments(bn254_ctx *ctx, const uint8_t *commitments /* t*128, host */, uint32_t t, size_t n_keys, uint32_t flags,
                                         uint8_t *key_status /* n_keys, or NULL */, uint8_t *status /* 1 */);
 
+/* COMBINE VECTORS OF G2 POINTS, one scalar per vector, column by column: d vectors of len points each (vector-major: point k of vector i
+ * is entry i*len + k), d scalars of 32 big-endian bytes:  out[k] = sum over i of scalars[i] * vectors[i][k].  What a linear combination of
+ * commitment vectors is — of the sub-dealings of a reshare (below), of the dealers of a DKG under weights.
+ * DEFINING IDENTITY: out[k] and status[k] are byte for byte bn254_batch_g2_msm over ONE segment holding vectors[0][k], .., vectors[d-1][k]
+ * with the scalars 0 .. d-1 and the same reduce_scalar.  So: points are decoded with flags 0 (on the curve, NO subgroup check); the first
+ * non-zero decode status in vector order wins and the output is then 128 zero bytes; a fault in one column touches that column only; d = 0
+ * gives identities with status 0; scalars >= r are reduced (reduce_scalar != 0) or taken as they are, as there.
+ * Arguments: len = 0 returns 0 and writes nothing; d*len >= 2^32 is BN254_E_BAD_ARGUMENT; otherwise the argument, alignment and NULL rules of
+ * bn254_batch_g2_msm_device (vectors, scalars and out 4-byte aligned in the _device form, else BN254_E_MISALIGNED; vectors and scalars may be
+ * NULL only when d = 0).  Both sizes are arguments, so the _device form copies nothing home: it only enqueues.  One call per context in
+ * flight.  Scratch: 363 B per term (146 B per decoded point, the 216-byte term and its status byte).
+ * Cost: every point is decoded ONCE; one lane per term walks the 256-step ladder over the decoded limbs, in column-major term order (with
+ * d >= 64 a wave holds 64 consecutive vectors of one column: its point loads are strided by len points — one load beside 256 ladder
+ * steps); then the two segment sums of bn254_batch_g2_msm, split by BN254_OPT_COLLECT_WAVE_MIN_SHARES over d.
+ * Which call when: this one where the scalars belong to the vectors — it stages d scalars and no transposed copy, where bn254_batch_g2_msm
+ * takes d*len of each; bn254_batch_g2_msm for a scalar per point.  Measured: under bn254_ctx_reshare_commitments below (a tie to a slight win
+ * against bn254_batch_g2_msm with its inputs staged; the transposed copy and the replicated scalars are what is saved).
+ * Out of scope: the multi-GPU layer, compressed points, a G1 form, a bucket or bit-sliced sum for thousands of vectors, slicing. */
+int bn254_batch_g2_vector_combine(bn254_ctx *ctx, const uint8_t *vectors /* d*len*128, vector-major */, const uint8_t *scalars /* d*32 */,
+                                  size_t d, size_t len, int reduce_scalar, uint8_t *out /* len*128 */, uint8_t *status /* len */);
+int bn254_batch_g2_vector_combine_device(bn254_ctx *ctx, const uint8_t *d_vectors, const uint8_t *d_scalars, size_t d, size_t len,
+                                         int reduce_scalar, uint8_t *d_out, uint8_t *d_status, void *stream);
+/* RESHARE A THRESHOLD KEY: the commitments of the NEXT committee's polynomial from the sub-dealings of the old members.  Old member i —
+ * registered key dealer_key[i] — deals its share s_i with a polynomial g_i of degree t_new - 1, g_i(0) = s_i, and publishes the t_new
+ * commitments D_i (vectors, dealer-major, host memory, uncompressed); D_i,0 must be its registered key.  For a set S of `threshold`
+ * qualified dealers f' = sum lambda_i(S) g_i has f'(0) = f(0): commitments[k] = sum over i in S of lambda_i(S) D_i,k, and the group key stays.
+ * The registered set is the OLD committee; the call reads it and leaves the context as it found it.  Host-synchronous; quiesces first, like
+ * bn254_ctx_check_dealing.
+ * BN254_E_BAD_ARGUMENT: a NULL argument; d = 0, t_new = 0 or threshold = 0; flags != 0; no registered keys; bm_words < ceil(n_keys / 32);
+ * dealer_key not STRICTLY INCREASING (checked on the host: all parties must agree on the order, and two vectors of one dealer are an
+ * equivocation for the protocol to settle, not for this call); d*t_new >= 2^32.
+ * dealer_status[i] is the FIRST that applies: (1) dealer_key[i] >= n_keys: 2; (2) the key's registration status is non-zero: that status — a
+ * failed proof of possession counts, as in every keyed call; (3) a commitment of the vector does not decode (flags 0): the first non-zero
+ * status in coefficient order; (4) D_i,0 is not the registered key as a group element: 9 — field elements are compared, so a registered
+ * identity key needs 128 zero bytes and the negated key (same x, -y) reads 9; (5) else 0.  With Q the dealers of status 0:
+ *   |Q| >= threshold: S = the `threshold` lowest key indices of Q — a choice that depends on nothing but Q —, used_bits = S in the bitmap
+ *     calls' numbering (exactly `threshold` bits), commitments as above with lambda the coefficient of bn254_batch_threshold_combine_keyed
+ *     (x_j = j + 1), *status = 0;
+ *   |Q| < threshold (threshold > n_keys and threshold > d included): *status = 9, commitments are zero bytes, used_bits = Q.
+ * Words of used_bits past the last key are zero.
+ * DEFINING IDENTITY 1: on success commitments is byte for byte bn254_batch_g2_vector_combine of S's vectors in increasing key order with the
+ * scalars bn254_debug_lagrange_at_zero gives for x = key + 1 and reduce_scalar = 0.
+ * DEFINING IDENTITY 2 (closed loop): over registered keys that are an honest threshold-of-n dealing, and honest sub-dealings, commitments[0]
+ * is the group key bn254_ctx_check_dealing(threshold) returns, whatever S; registered with bn254_ctx_register_keys_commitments, the keys of
+ * `commitments` pass bn254_ctx_check_dealing(t_new) with that same key.
+ * NOT checked: that the registered keys are a dealing — bn254_ctx_check_dealing's job, once per set; that the private sub-shares match the
+ * vectors — each recipient's share check against the dealer's vector (secret * G2 == the vector at index + 1, bn254_batch_g2_poly_eval), whose
+ * complaints decide which dealers the caller passes in.
+ * Cost: every commitment is decoded once; a lane per dealer settles its status, one wave ranks the qualified ones, a lane per taken dealer
+ * computes its coefficient in Fr; then threshold * t_new ladders — untaken dealers cost none — and the sums.  One wait brings
+ * dealer_status, the row, the commitments and the status home.  Scratch: 146 B per commitment given, 217 B per term.
+ * Measured on an MI355X (tools/reshare_throughput.py, profiles/reshare.jsonl; whole calls under a host clock, staging on both sides, median
+ * [min, max] of 7 alternating runs after 2 warm-up runs; every old member a dealer, (n, t) -> (n, t); the baseline is the route that exists
+ * without the calls and checks nothing about the dealers: the coefficients of S in Python integers, the vectors of S transposed and the
+ * scalars replicated t times in Python, bn254_batch_g2_msm over t segments of t terms, each part timed).  (256, 171): this call 7.23 ms
+ * [7.03, 7.25] against 5.08 [5.06, 5.15] + 4.68 [4.13, 4.94] + 6.21 [6.18, 6.24]; bn254_batch_g2_vector_combine on the 171 vectors of S 6.16
+ * [6.15, 6.16].  (1 024, 683): this call 63.8 [54.8, 74.4] against 72.6 [72.5, 74.0] + 87.1 [86.1, 94.8] + 53.8 [52.5, 56.2]; the vector
+ * combine 52.4 [52.3, 52.5].  The call's own part is about 10 ms MORE than bn254_batch_g2_msm alone at (1 024, 683), outside the spreads:
+ * it stages and decodes the vectors of all 1 024 dealers (89 MB) to qualify them, where the old route is handed the 683 of S; it wins by the
+ * host's coefficients and staging.  bn254_batch_g2_vector_combine against bn254_batch_g2_msm with everything staged for it: 6.16 against
+ * 6.21 and 52.4 against 53.8 — a tie to a slight win; what it saves is the transposed copy and the replicated scalars.  The same bytes on
+ * all three routes.  bn254_batch_g2_msm (171 terms), bn254_ctx_check_dealing (256, 171) and bn254_batch_g2_poly_eval (256, 171) in this
+ * build against the parent's, two alternating runs each: 5.34 / 5.35 against 5.34 / 5.36, 7.07 / 7.08 against 7.10 / 7.09, 6.09 / 6.09
+ * against 6.09 / 6.08 ms — within each other's spreads, the same output bytes.
+ * Unmeasured: other thresholds and t_new != threshold, fewer dealers than members, more than 1 024 keys, disqualified dealers at scale, the
+ * _device form of the vector combine under events, a sweep of the lane/wave split of the sums for this call.
+ * Which call when: this one for the reshare itself; bn254_batch_g2_vector_combine where the caller has its own qualification rules or its
+ * own scalars — and, for committees of a thousand, where the caller knows S already and would rather not stage the vectors outside it.
+ * Out of scope: a _device form, compressed commitments, the multi-GPU layer, a bucket or bit-sliced sum for committees of
+ * thousands (the cost here is threshold * t_new ladders), slicing, the reshare protocol's rounds and complaints. */
+int bn254_ctx_reshare_commitments(bn254_ctx *ctx, const uint8_t *vectors /* d*t_new*128, host, dealer-major */,
+                                  const uint32_t *dealer_key /* d, host, strictly increasing */, size_t d, uint32_t t_new,
+                                  uint32_t threshold /* the OLD committee's t */, uint32_t flags /* must be 0 */,
+                                  uint8_t *dealer_status /* d */, uint32_t *used_bits /* bm_words */, size_t bm_words,
+                                  uint8_t *commitments /* t_new*128 */, uint8_t *status /* 1 */);
+
 /* OPTIMISTIC THRESHOLD COMBINE: interpolate first, verify the result once per tuple under the group key.  The interpolated signature is
  * unique: if it verifies under f(0) * G2::one() it is THE group signature whatever the individual shares were, so one pairing check per
  * tuple proves the output — and proves exactly what the consumer will check.  (The optimistic collect's check of the plain sum cannot be

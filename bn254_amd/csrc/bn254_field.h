@@ -1368,6 +1368,37 @@ BN_DEVH void fp12_mul_line2(Fp12& r, const Fp12& f, const Fp6& b0, const Fp2& b1
   fp6_site_r<159>(r.c1, u);
 }
 #endif
+// f * (l0 + (l1 + v) w): a TABLE line l0 + l1 w + w^3, whose coefficient at w^3 = v w is one (bn254_pairing.h: KeyLine); l0, l1 tight.
+// The unit needs no product, so the three Fq6 factors of the Karatsuba form are Fq6-by-Fq2 scalings plus a shift by v:
+//   t0 = f0 l0,   t1 = f1 l1 + v f1,   u = (f0 + f1)(l0 + l1) + v (f0 + f1),   r0 = t0 + v t1,   r1 = u - t0 - t1
+// 9 Fq2 products against the 13 of fp12_mul_line, and no Fq6-level Karatsuba sums.  The operand sums stay lazy (two tight values on
+// either side: within the column budget of fp2_mul); the outputs are carried and weakly reduced like those of the siblings.
+// r1 is formed as (f0 + f1)(l0 + l1) - t0 - f1 l1 + v f0: the v f1 of u and of t1 cancel, and written out the limbs of the sum would leave
+// int32 (xi times a lazy sum is 5 units of 2^28, xi times a tight value 3).
+// `skip` (the line's pair contributes one; `any_skip`, wave-uniform: some lane of the wave has such a pair): r = f, selected BEFORE the
+// output sites — f may come from fp12_sqr, whose outputs are carried but not all weakly reduced, and has to pass a reduction here as it
+// does in a product.
+BN_DEVH void fp12_mul_unit_line(Fp12& r, const Fp12& f, const Fp2& l0, const Fp2& l1, bool skip = false, bool any_skip = false) {   // sites 450 .. 455
+  Fp6 t0, p1, t1, s, u;
+  fp6_mul_fp2(t0, f.c0, l0);
+  fp6_mul_fp2(p1, f.c1, l1);
+  fp6_add(s, f.c0, f.c1);
+  fp6_mul_fp2(u, s, fp2_add(l0, l1));
+  fp6_sub(u, u, t0);
+  fp6_sub(u, u, p1);
+  fp6_mul_v(s, f.c0);
+  fp6_add(u, u, s);
+  fp6_mul_v(t1, f.c1);
+  fp6_add(t1, p1, t1);
+  fp6_mul_v(s, t1);
+  fp6_add(s, t0, s);
+  if (any_skip) {
+    s.c0 = fp2_select(skip, f.c0.c0, s.c0); s.c1 = fp2_select(skip, f.c0.c1, s.c1); s.c2 = fp2_select(skip, f.c0.c2, s.c2);
+    u.c0 = fp2_select(skip, f.c1.c0, u.c0); u.c1 = fp2_select(skip, f.c1.c1, u.c1); u.c2 = fp2_select(skip, f.c1.c2, u.c2);
+  }
+  fp6_site_r<450>(r.c0, s);
+  r.c1.c0 = NS(453, u.c0); r.c1.c1 = NR(454, u.c1); r.c1.c2 = NR(455, u.c2);
+}
 // coefficient k of w^k in the polynomial basis: c[2i] = c0.c_i, c[2i+1] = c1.c_i
 BN_DEV Fp2& fp12_coef(Fp12& a, int k) {
   Fp6& h = (k & 1) ? a.c1 : a.c0;

@@ -984,7 +984,7 @@ int bn254_ctx_set_option(bn254_ctx* c, int option, int value) {
   if (option == BN254_OPT_KEY_DEDUP) { if (value < 0 || value > 1) return BN254_E_BAD_ARGUMENT; c->key_dedup = value; return 0; }
   if (option == BN254_OPT_KEY_DEDUP_MAX_KEYS) { if (value < 0 || value > KEY_DEDUP_MAX_KEYS_LIMIT) return BN254_E_BAD_ARGUMENT; c->kd_max_keys = value; return 0; }
   if (option == BN254_OPT_KEY_DEDUP_MIN_MULT) { if (value < 1) return BN254_E_BAD_ARGUMENT; c->kd_min_mult = value; return 0; }
-  if (option == BN254_OPT_KEY_DEDUP_FOLD) { if (value < 0 || value > 1) return BN254_E_BAD_ARGUMENT; c->kd_fold = value; return 0; }
+  if (option == BN254_OPT_KEY_DEDUP_FOLD) { if (value < 0 || value > 2) return BN254_E_BAD_ARGUMENT; c->kd_fold = value; return 0; }
   if (option == BN254_OPT_KEY_DEDUP_FORCE_GENERIC) { c->kd_force_generic = value == 2 ? 2 : value != 0; return 0; }
   if (option == BN254_OPT_KEY_CACHE) { if (value < 0 || value > 1) return BN254_E_BAD_ARGUMENT; c->kd_cache = value; c->kd_cache_valid = false; return 0; }
   if (option == BN254_OPT_KEY_DEDUP_HASH_BITS) { if (value < 0 || value > 32) return BN254_E_BAD_ARGUMENT; c->kd_hash_bits = value; return 0; }
@@ -1099,7 +1099,8 @@ static int verify_tail(bn254_ctx* c, hipStream_t s, size_t n, uint8_t* d_status,
     // once.  The wait for the builder counts in the Miller stage.
     HIP_TRY(hipStreamWaitEvent(s, c->kd_join, 0));
     const KeyTable kt = {kd->lines, kd->st, kd->inf, kd->max_keys};
-    if (c->kd_fold) rc = bn254_pair_miller_verify_keyed_fold(n, c->ws, kd->key_idx, kt, kd->fold, s, 0, nullptr, kd->ctl + KD_CTL_KEYED_N);
+    if (c->kd_fold == 2) rc = bn254_pair_miller_verify_keyed_unit(n, c->ws, kd->key_idx, kt, s, 0, nullptr, kd->ctl + KD_CTL_KEYED_N);
+    else if (c->kd_fold) rc = bn254_pair_miller_verify_keyed_fold(n, c->ws, kd->key_idx, kt, kd->fold, s, 0, nullptr, kd->ctl + KD_CTL_KEYED_N);
     else rc = bn254_pair_miller_verify_keyed(n, c->ws, kd->key_idx, kt, s, 0, nullptr, kd->ctl + KD_CTL_KEYED_N);
     if (rc) return rc;
     if ((rc = bn254_pair_miller_verify(n, c->ws, nullptr, kd->ctl + KD_CTL_GENERIC_N, s))) return rc;

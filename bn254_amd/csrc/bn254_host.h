@@ -89,7 +89,7 @@ struct bn254_ctx {
   int kd_max_keys;           // BN254_OPT_KEY_DEDUP_MAX_KEYS
   int kd_min_mult;           // BN254_OPT_KEY_DEDUP_MIN_MULT
   int kd_force_generic;      // BN254_OPT_KEY_DEDUP_FORCE_GENERIC (developer hook): 1 = the device-side decision always says "generic", 2 = the builder reports a degenerate line
-  int kd_fold;               // BN254_OPT_KEY_DEDUP_FOLD (developer option): the keyed Miller kernel on the folded rows (k_miller_verify_keyed_fold_pair)
+  int kd_fold;               // BN254_OPT_KEY_DEDUP_FOLD (developer option): 1 = the keyed Miller kernel on the folded rows (k_miller_verify_keyed_fold_pair), 2 = on unit lines (k_miller_verify_keyed_unit_pair), 0 = line pairs
   int kd_hash_bits;          // BN254_OPT_KEY_DEDUP_HASH_BITS (test seam): bits of the key hash kept (0 = all), to force collisions
   hipStream_t kd_stream;     // the dedup and the table builder run here, forked from and joined into the call's stream
   hipEvent_t kd_fork, kd_join;

@@ -269,6 +269,40 @@ int bn254_pair_miller_verify_keyed_fold(size_t n, Ws ws, const uint32_t* key_idx
   HIP_TRY(hipGetLastError());
   return 0;
 }
+// The same verify on UNIT LINES (bn254_pairing.h: miller_loop_keyed_unit): the key's plain rows only, each of the two table lines of a step
+// multiplied into f by itself.  Same status merge and the same count / map / base contract as k_miller_verify_keyed_pair.
+KERNEL_PAIR void k_miller_verify_keyed_unit_pair(size_t n, Ws ws, const uint32_t* key_idx, KeyTable kt, size_t base, const uint32_t* map,
+                                                 const uint32_t* count) {
+  size_t i = ((size_t)blockIdx.x * BN_PAIR_WG + threadIdx.x) >> 1;
+  if (i >= n) return;
+  if (count && i >= *count) return;
+  if (map) i = map[i];
+  uint32_t key = key_idx[i];
+  i += base;
+  uint8_t kst = ST_OK;
+  if (key >= kt.n_keys) { kst = ST_INDEX_OOB; key = 0; }
+  else kst = kt.st[key];
+  const bool key_inf = kst != ST_OK || kt.inf[key] != 0;      // a refused key walks the loop as a skipped pair
+  if ((threadIdx.x & 1u) == 0) {
+    const uint8_t prev = ws_byte(ws, BY_ST_DECODE, i);
+    ws_byte(ws, BY_ST_DECODE, i) = prev != ST_OK ? prev : kst;
+  }
+  G1Affine sig, h;
+  ws_load_g1(ws, PL_P1X, BY_P1_INF, i, sig);
+  ws_load_g1(ws, PL_P2X, BY_P2_INF, i, h);
+  __shared__ Fp12PairSlot lds_f[BN_PAIR_WG];
+  Fp12& f = lds_f[threadIdx.x].v;
+  BN_CLK_BEGIN(ws);
+  miller_loop_keyed_unit<true>(f, h, key_inf, kt.lines, key, sig);
+  BN_CLK_END(ws, 0);
+  ws_store_f12_own(ws, i, f);
+}
+int bn254_pair_miller_verify_keyed_unit(size_t n, Ws ws, const uint32_t* key_idx, KeyTable kt, hipStream_t s, size_t base, const uint32_t* map,
+                                        const uint32_t* count) {
+  k_miller_verify_keyed_unit_pair<<<(unsigned)((2 * n + BN_PAIR_WG - 1) / BN_PAIR_WG), BN_PAIR_WG, 0, s>>>(n, ws, key_idx, kt, base, map, count);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
 // generic single pair per lane pair: f = miller(P1, Q)   (bn254_batch_pairing*)
 KERNEL_PAIR void k_miller_var_pair(size_t n, Ws ws) {
   size_t i = ((size_t)blockIdx.x * BN_PAIR_WG + threadIdx.x) >> 1;

@@ -350,6 +350,77 @@ BN_DEVM void miller_loop_keyed_fold(Fp12& f, const G1Affine& pa, bool key_inf, c
   folded_b(r);                                // the two closing lines: row BN_N_FOLD_ROWS - 1
   folded_a(r);
 }
+// ---- the keyed loop on UNIT LINES (key dedup of the exact verify, BN254_OPT_KEY_DEDUP_FOLD = 2) -------------------------------------------
+// Every table line is l0 + l1 w + w^3.  miller_loop_keyed multiplies lineA by lineB (3 Fq2 products) and f by the five-term result (17):
+// 20 per line pair.  Here f takes the two lines one after the other through fp12_mul_unit_line (bn254_field.h), 9 each: 18 per pair, the
+// plain rows only — no folded rows, no monomials.  The first step is peeled: f = 1 there, so its squaring is dropped and the first line
+// pair is ASSIGNED from the three-product line product instead of multiplied into one.
+// Per lane 768 - 12 + 3 + 86 x 18 = 2 307 dual and 87 x 4 = 348 single products (tests/test_kd_unit_lines.py).
+// f <- f * (c0 y + c1 x w + w^3); a skipped pair multiplies by one
+BN_DEV void mul_by_unit_table_line(Fp12& f, const Fp2& c0, const Fp2& c1, const Fp& px, const Fp& py, bool skip, bool any_skip) {
+  const Fp2 l0 = fp2_mul_fp(c0, py), l1 = fp2_mul_fp(c1, px);
+  fp12_mul_unit_line(f, f, l0, l1, skip, any_skip);
+}
+// f = lineA(pa) * lineB(pb), table lines as in mul_by_two_table_lines (whose line product and skip selects these are: sites 460 .. 465
+// stand where it has 280 .. 285), assigned rather than multiplied into f
+BN_DEV void set_two_table_lines(Fp12& f, const KeyLine& la, const Fp& pax, const Fp& pay, bool skip_a, int idx, const Fp& pbx, const Fp& pby,
+                                bool skip_b, bool any_skip) {   // sites 460 .. 465
+  const Fp2 l0 = fp2_mul_fp(la.c0, pay), l1 = fp2_mul_fp(la.c1, pax);
+  const Fp2 m0 = fp2_mul_fp(fp2_load_const(C_NEG_G2_LINES[idx][0]), pby), m1 = fp2_mul_fp(fp2_load_const(C_NEG_G2_LINES[idx][1]), pbx);
+  const Fp2 v0 = fp2_mul(l0, m0), v1 = fp2_mul(l1, m1);
+  const Fp2 x01 = fp2_sub(fp2_sub(fp2_mul(NS(460, fp2_add(l0, l1)), NS(461, fp2_add(m0, m1))), v0), v1);
+  Fp6 b0;
+  b0.c0 = NS(462, fp2_add(v0, fp2_load_const(C_XI_MONT))); b0.c1 = v1; b0.c2 = NS(463, fp2_add(l1, m1));
+  Fp2 b10 = NS(464, x01), b11 = NS(465, fp2_add(l0, m0));
+  if (any_skip) {
+    const Fp2 one = fp2_one(), zero = fp2_zero();
+    const bool both = skip_a && skip_b, only_a = skip_a && !skip_b, only_b = skip_b && !skip_a;
+    b0.c0 = fp2_select(both, one, fp2_select(only_a, m0, fp2_select(only_b, l0, b0.c0)));
+    b0.c1 = fp2_select(skip_a || skip_b, zero, b0.c1);
+    b0.c2 = fp2_select(skip_a || skip_b, zero, b0.c2);
+    b10 = fp2_select(both, zero, fp2_select(only_a, m1, fp2_select(only_b, l1, b10)));
+    b11 = fp2_select(both, zero, fp2_select(skip_a || skip_b, one, b11));
+  }
+  f.c0 = b0;
+  f.c1.c0 = b10; f.c1.c1 = b11; f.c1.c2 = fp2_zero();
+}
+// f = miller(pa, key) * miller(pb, -G2), the value of miller_loop_keyed: `lines` = the plain rows of ALL keys (wave-uniform), `key` the
+// lane's row, as in miller_loop_keyed_fold.  The factors commute: line B goes first, as there.
+template <bool F_LDS = false>
+BN_DEVM void miller_loop_keyed_unit(Fp12& f, const G1Affine& pa, bool key_inf, const int32_t* lines, uint32_t key, const G1Affine& pb) {
+  if constexpr (F_LDS) BN_ASSUME_LDS(&f);
+  lines = bn_wave_uniform(lines);
+  typedef const int32_t (*LinePtr)[2][2][BN_LIMBS];
+  const bool skip_a = pa.inf || key_inf, skip_b = pb.inf;
+#if defined(__HIPCC__)
+  const bool any_skip = __builtin_amdgcn_ballot_w64(skip_a || skip_b) != 0;   // wave-uniform
+#else
+  const bool any_skip = skip_a || skip_b;
+#endif
+  const LinePtr tab = (LinePtr)(lines + (size_t)key * (BN_N_FIXED_LINES * 2 * 2 * BN_LIMBS));
+  int idx = 0;
+  auto pair = [&]() {
+    mul_by_unit_table_line(f, fp2_load_const(C_NEG_G2_LINES[idx][0]), fp2_load_const(C_NEG_G2_LINES[idx][1]), pb.x, pb.y, skip_b, any_skip);
+    mul_by_unit_table_line(f, fp2_load_const(tab[idx][0]), fp2_load_const(tab[idx][1]), pa.x, pa.y, skip_a, any_skip);
+    ++idx;
+  };
+  {                                           // step 0 on f = 1: no squaring, the doubling lines assigned
+    BN_SET_STEP_PRIORITY(0);
+    KeyLine la;
+    la.c0 = fp2_load_const(tab[0][0]); la.c1 = fp2_load_const(tab[0][1]);
+    set_two_table_lines(f, la, pa.x, pa.y, skip_a, 0, pb.x, pb.y, skip_b, any_skip);
+    ++idx;
+    if (C_ATE_NAF[0] != 0) pair();            // wave-uniform
+  }
+  for (int d = 1; d < 64; ++d) {
+    BN_SET_STEP_PRIORITY(d);
+    fp12_sqr(f, f);
+    pair();
+    if (C_ATE_NAF[d] != 0) pair();            // wave-uniform
+  }
+  pair();
+  pair();
+}
 #endif  // BN_SPLIT_FP2
 // mul_by_two_table_lines with lineB = (lb.c0, lb.c1, 1) from a per-lane table instead of the constant one.  A copy rather than a shared
 // body: sharing it moved the register allocation of the keyed verify kernel.  The operands are canonical in both, so the carry sites

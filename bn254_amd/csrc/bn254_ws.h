@@ -226,6 +226,9 @@ __attribute__((visibility("hidden"))) int bn254_pair_miller_verify_keyed(size_t 
 __attribute__((visibility("hidden"))) int bn254_pair_miller_verify_keyed_fold(size_t n, Ws ws, const uint32_t* key_idx, KeyTable kt, const int32_t* fold,
                                                                               hipStream_t s, size_t base = 0, const uint32_t* map = nullptr,
                                                                               const uint32_t* count = nullptr);
+// ... on the plain rows, the two unit lines of a step multiplied into f one at a time (bn254_pairing.h: miller_loop_keyed_unit)
+__attribute__((visibility("hidden"))) int bn254_pair_miller_verify_keyed_unit(size_t n, Ws ws, const uint32_t* key_idx, KeyTable kt, hipStream_t s, size_t base = 0,
+                                                                              const uint32_t* map = nullptr, const uint32_t* count = nullptr);
 // aggregates over distinct messages against registered keys (bn254_aggdist.hip): level 0 over slots of `width` (1 or 2) table pairs whose
 // per-aggregate inclusive slot scan is sl.incl (ceil((hi - lo + 1) / width)); the registered table holds -G2's lines as entry kt.n_keys.
 // Then the aggregates' products from gbase + i to i for the final exponentiation.
@@ -303,7 +306,7 @@ __attribute__((visibility("hidden"))) int bn254_aggd_keyed_slot_map(hipStream_t 
 // KeyTable format above, built on a stream of the context beside decode and hash; the route (tables or the generic loop) is decided on the device
 #define KEY_DEDUP_MAX_KEYS_DEFAULT 1024            // tables for at most this many distinct keys per call (12.5 KB + 7.9 KB of folded rows, which a key's raw c2 shares while it is built)
 #define KEY_DEDUP_MIN_MULT_DEFAULT 16              // ... and only when every key serves this many items on average
-#define KEY_DEDUP_FOLD_DEFAULT 1                   // BN254_OPT_KEY_DEDUP_FOLD: the keyed Miller loop of the dedup reads the folded rows
+#define KEY_DEDUP_FOLD_DEFAULT 2                   // BN254_OPT_KEY_DEDUP_FOLD: the keyed Miller loop of the dedup multiplies unit lines
 #define KEY_DEDUP_MAX_KEYS_LIMIT 16384             // BN254_OPT_KEY_DEDUP_MAX_KEYS at most (338 MB of tables)
 #define KD_MAX_PROBES 64u                          // open addressing: a longer probe sequence sends the call to the generic route
 #define KD_EMPTY 0xFFFFFFFFu

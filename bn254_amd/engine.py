@@ -48,7 +48,7 @@ OPT_HASH_TAIL_CHUNK = 32           # ... test seam: counters per lane group and 
 OPT_BITMAP_RAND_MIN_TUPLES = 33    # randomised signer bitmaps: the exact bitmap call below this many tuples
 OPT_BITMAP_RAND_GROUP_TUPLES = 34  # ... tuples per group of its combined checks (developer option)
 OPT_BITMAP_RAND_MAX_KEYS = 35      # ... the exact bitmap call when more keys than this are registered
-OPT_KEY_DEDUP_FOLD = 44            # key dedup: the keyed Miller loop reads the keys' folded rows (default 1; 0 = line by line)
+OPT_KEY_DEDUP_FOLD = 44            # key dedup: the keyed Miller loop multiplies unit lines (default 2; 1 = the keys' folded rows, 0 = line pairs)
 OPT_KEY_CACHE = 36                 # key dedup: the line tables stay between calls, a call builds only unseen keys (default 1; 0 = build all, drops the cache)
 OPT_COLLECT_RAND_MIN_SHARES = 38   # collect_keyed_bitmap_randomized: the exact collect below this many shares (default 65664)
 OPT_COLLECT_RAND_MIN_PER_KEY = 39  # ... and below this many shares per registered key, n_shares // n_keys (default 42); DESIGN.md §10f

@@ -1431,10 +1431,13 @@ int bn254_mgpu_batch_hash_to_g1(bn254_mgpu *mg, const uint8_t *msgs, const uint6
                                              Miller loop (the fallback path of an overflowing or degenerate batch); 2 = the table builder reports a
                                              degenerate line (flags bit 1) for every key it builds — no key bytes that reach one are known —, so the
                                              device takes the decision it takes for such a key: generic loop, nothing cached; default 0 */
-#define BN254_OPT_KEY_DEDUP_FOLD 44 /* key dedup: 1 (default) = the keyed Miller loop of the dedup reads each key's 22 FOLDED rows — the product of the two
+#define BN254_OPT_KEY_DEDUP_FOLD 44 /* key dedup: 2 (default) = the keyed Miller loop of the dedup reads each key's plain rows and multiplies the two
+                                    table lines of a step into f one at a time, as unit lines (their coefficient at w^3 is one: nine Fq2 products
+                                    each), the first step assigned instead of multiplied (k_miller_verify_keyed_unit_pair); 1 = it reads each
+                                    key's 22 FOLDED rows — the product of the two
                                     lines of a key that meet with no squaring between them (a nonzero digit's doubling and addition line, the two
                                     closing lines), five Fq2 coefficients per row, built with the key's plain rows and cached with them — and
-                                    multiplies one folded element per pair there (k_miller_verify_keyed_fold_pair); 0 = line by line
+                                    multiplies one folded element per pair there (k_miller_verify_keyed_fold_pair); 0 = line pair by line pair
                                     (k_miller_verify_keyed_pair).  The rows are built either way.  Same status bytes. */
 #define BN254_OPT_KEY_DEDUP_HASH_BITS 24 /* test seam: keep only this many low bits of the key hash of the dedup table (0 = all, default), so that
                                          distinct keys collide: the full 128-byte compare and the probe bound (overflow -> generic loop) */

@@ -221,6 +221,8 @@ def load():
     L.bn254_debug_hash_candidate.argtypes = [vp, vp, sz, vp, vp]
     if hasattr(L, "bn254_debug_jacobi"):                              # absent from an older build loaded through BN254_LIB
         L.bn254_debug_jacobi.argtypes = [vp, i32, vp, vp, sz, vp, vp]
+    if hasattr(L, "bn254_debug_fq2_limbs"):                           # absent from an older build loaded through BN254_LIB
+        L.bn254_debug_fq2_limbs.argtypes = [vp, i32, i32, vp, vp, sz, vp, vp]
     L.bn254_probe_issue_rate.argtypes = [vp, i32, i32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(i32)]
     L.bn254_probe_leaf_floor.argtypes = [vp, sz, i32, ctypes.POINTER(ctypes.c_float)]
     L.bn254_probe_fe_program.argtypes = [vp, sz, vp, sz, ctypes.POINTER(ctypes.c_float)]
@@ -284,7 +286,7 @@ EXPORTED_SYMBOLS = [
     "bn254_ctx_set_group_key", "bn254_batch_threshold_combine_keyed_optimistic", "bn254_batch_threshold_combine_keyed_optimistic_device",
     "bn254_debug_threshold_opt_last",
     "bn254_batch_g2_msm", "bn254_batch_g2_msm_device", "bn254_ctx_check_dealing", "bn254_debug_dealing_coefficients",
-    "bn254_debug_jacobi",
+    "bn254_debug_jacobi", "bn254_debug_fq2_limbs",
     "bn254_batch_g2_poly_eval", "bn254_batch_g2_poly_eval_device", "bn254_ctx_register_keys_commitments",
     "bn254_batch_g2_vector_combine", "bn254_batch_g2_vector_combine_device", "bn254_ctx_reshare_commitments",
 ]

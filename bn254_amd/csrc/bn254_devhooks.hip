@@ -15,6 +15,7 @@
 #include "bn254_collect.h"
 #include "bn254_fr.h"
 #include "bn254_threshold.h"
+#include "bn254_fq2_hook.h"
 
 using namespace bn254;
 
@@ -105,6 +106,24 @@ KERNEL_SMALL void k_debug_jacobi(int mode, const uint8_t* a, const uint8_t* b, s
 #pragma unroll
   for (int k = 0; k < 8; ++k) o[k] = __builtin_bswap32(v.w[7 - k]);
   flags[i] = fl;
+}
+// One Fq2 primitive per lane on raw limb vectors, through the classic fp2_* / fp_* of bn254_field.h (bn254_fq2_hook.h holds the one switch all four
+// builds share; the pair layout's kernel is k_debug_fq2_limbs_pair in bn254_pair.hip).  in: n x 4 operands x 18 limbs, coef: n x 4.
+KERNEL_SMALL void k_debug_fq2_limbs(int op, const int32_t* in, const int32_t* coef, size_t n, int32_t* out, uint8_t* flags) {
+  size_t i = (size_t)blockIdx.x * BN_WAVE + threadIdx.x;
+  if (i >= n) return;
+  const int32_t* p = in + i * (BN_FQ2_HOOK_OPERANDS * BN_FQ2_HOOK_WORDS);
+  const Fp2 a = fq2_hook_load(p, 0), b = fq2_hook_load(p + BN_FQ2_HOOK_WORDS, 0), c = fq2_hook_load(p + 2 * BN_FQ2_HOOK_WORDS, 0),
+            d = fq2_hook_load(p + 3 * BN_FQ2_HOOK_WORDS, 0);
+  int32_t k[BN_FQ2_HOOK_OPERANDS];
+#pragma unroll
+  for (int t = 0; t < BN_FQ2_HOOK_OPERANDS; ++t) k[t] = coef[i * BN_FQ2_HOOK_OPERANDS + t];
+  bool flag;
+  const Fp2 r = fq2_hook_op(op, a, b, c, d, b.c0, k, flag);
+  int32_t* o = out + i * BN_FQ2_HOOK_WORDS;
+#pragma unroll
+  for (int j = 0; j < BN_LIMBS; ++j) { o[j] = r.c0.v[j]; o[BN_LIMBS + j] = r.c1.v[j]; }
+  flags[i] = flag ? 1 : 0;
 }
 __device__ __forceinline__ void decode_fp12(Fp12& f, const uint8_t* b) {
   uint32_t any = 0;
@@ -677,6 +696,26 @@ int bn254_debug_final_exp_limbs(bn254_ctx* c, int layout, const int32_t* limbs, 
   }
   if (rc) return rc;
   HIP_TRY(hipGetLastError());
+  return st.finish();
+}
+// layout: 0 one lane per item (k_debug_fq2_limbs above) | 1 one lane pair per item (bn254_pair.hip)
+int bn254_debug_fq2_limbs(bn254_ctx* c, int layout, int op, const int32_t* operands, const int32_t* coef, size_t n, int32_t* out, uint8_t* flags) {
+  if (!c || layout < 0 || layout > 1 || op < 0 || op >= FQ2_OP_COUNT || (n && (!operands || !coef || !out || !flags))) return BN254_E_BAD_ARGUMENT;
+  if (n == 0) return 0;
+  if (n > 0xFFFFFFFFu / (BN_FQ2_HOOK_OPERANDS * BN_FQ2_HOOK_WORDS * sizeof(int32_t))) return BN254_E_BAD_ARGUMENT;
+  HIP_TRY(hipSetDevice(c->device));
+  HostStaging st(c);
+  const uint8_t* d_in = st.in(0, operands, n * BN_FQ2_HOOK_OPERANDS * BN_FQ2_HOOK_WORDS * sizeof(int32_t));
+  const uint8_t* d_coef = st.in(1, coef, n * BN_FQ2_HOOK_OPERANDS * sizeof(int32_t));
+  uint8_t *d_out = st.out(2, n * BN_FQ2_HOOK_WORDS * sizeof(int32_t), out), *d_flags = st.out(3, n, flags);
+  if (!st.ok()) return st.rc;
+  if (layout == 0) {
+    k_debug_fq2_limbs<<<grid_for(n), BN_WAVE, 0, c->stream>>>(op, (const int32_t*)d_in, (const int32_t*)d_coef, n, (int32_t*)d_out, d_flags);
+    HIP_TRY(hipGetLastError());
+  } else {
+    const int rc = bn254_pair_debug_fq2_limbs(op, (const int32_t*)d_in, (const int32_t*)d_coef, n, (int32_t*)d_out, d_flags, c->stream);
+    if (rc) return rc;
+  }
   return st.finish();
 }
 int bn254_debug_fp12_op(bn254_ctx* c, int op, const uint8_t* a, const uint8_t* b, size_t n, uint8_t* out) {

@@ -427,6 +427,9 @@ BN_HIDDEN int clo_settle(bn254_ctx* c, hipStream_t s, const ClCall& a, const ClS
 // map[e] of d_bits into the Q planes of entry map[e]; rule 2 is the caller's.  n = the most the queue can hold
 BN_HIDDEN int launch_bitmap_sum_queued(bn254_ctx* c, hipStream_t s, const uint32_t* d_bits, size_t bm_words, size_t n, bool tables, const uint32_t* map,
                                        const uint32_t* count);
+// developer hook bn254_debug_fq2_limbs, layout 1 (bn254_pair.hip: k_debug_fq2_limbs_pair): one Fq2 primitive per lane pair on raw limbs; the
+// buffers are device memory in the hook's format
+BN_HIDDEN int bn254_pair_debug_fq2_limbs(int op, const int32_t* d_in, const int32_t* d_coef, size_t n, int32_t* d_out, uint8_t* d_flags, hipStream_t s);
 BN_HIDDEN int launch_encode_g1(bn254_ctx* c, hipStream_t s, size_t n, int px, int inf_plane, uint8_t* out, uint8_t* status_out);
 // vectors of G2 points combined column by column (bn254_reshare.hip) run two kernels of other units: the decode of bn254_polyeval.hip — m points
 // into its 146 B layout — and the two segment sums of bn254_dealing.hip over terms the caller has written (m terms, n segments by d_seg,

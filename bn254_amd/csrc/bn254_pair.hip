@@ -6,6 +6,8 @@
 // Replaces, for ECDSA::verify (/root/reference/src/ecdsa.rs:49-64), k_miller_verify + k_final_exp.
 #include <hip/hip_runtime.h>
 
+#include "../../include/bn254_hip.h"   // BN254_E_BAD_ARGUMENT
+
 #define BN_SPLIT_FP2 1
 #if defined(BN_PAIR_FP6_LAZY) && !defined(BN_FP6_LAZY)
 #define BN_FP6_LAZY 1              // Fq6-level lazy reduction in fp12_sqr / fp12_mul_line2 of this translation unit (bn254_field.h: fp6_mul_lazy)
@@ -41,6 +43,7 @@
 #include "bn254_pairing.h"
 #include "bn254_codec_g2.h"
 #include "bn254_keydedup.h"
+#include "bn254_fq2_hook.h"
 
 using namespace bn254;
 
@@ -931,6 +934,41 @@ int bn254_pair_miller_verify(size_t n, Ws ws, const uint32_t* map, const uint32_
 }
 int bn254_pair_miller_var(size_t n, Ws ws, hipStream_t s) {
   k_miller_var_pair<<<(unsigned)((2 * n + BN_PAIR_WG - 1) / BN_PAIR_WG), BN_PAIR_WG, 0, s>>>(n, ws);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// Developer hook (bn254_debug_fq2_limbs, layout 1): one Fq2 primitive per lane pair on raw limb vectors — the fp2_* of bn254_fp2_pair.h as this
+// unit compiles them (DPP exchanges, the asm role prologue of the squaring), in the workgroup shape of the kernels above.  Item = lane >> 1;
+// the even lane takes the real coefficient of every operand, the odd lane the imaginary one.  Both lanes of a pair, and the lanes past the
+// last item, stay active through the arithmetic (they redo the last item): only the stores are guarded.  A predicate's answer is formed in both
+// lanes; the even lane stores it, with bit 7 set should the two lanes ever disagree.
+KERNEL_PAIR void k_debug_fq2_limbs_pair(int op, const int32_t* in, const int32_t* coef, size_t n, int32_t* out, uint8_t* flags) {
+  const int role = (int)(threadIdx.x & 1u);
+  const size_t i = ((size_t)blockIdx.x * BN_PAIR_WG + threadIdx.x) >> 1;
+  const bool live = i < n;
+  const size_t ii = live ? i : n - 1;
+  const int32_t* p = in + ii * (BN_FQ2_HOOK_OPERANDS * BN_FQ2_HOOK_WORDS);
+  const Fp2 a = fq2_hook_load(p, role), b = fq2_hook_load(p + BN_FQ2_HOOK_WORDS, role), c = fq2_hook_load(p + 2 * BN_FQ2_HOOK_WORDS, role),
+            d = fq2_hook_load(p + 3 * BN_FQ2_HOOK_WORDS, role);
+  const Fp s = fq2_hook_fp(p + BN_FQ2_HOOK_WORDS);      // the real coefficient of b, in both lanes
+  int32_t k[BN_FQ2_HOOK_OPERANDS];
+#pragma unroll
+  for (int t = 0; t < BN_FQ2_HOOK_OPERANDS; ++t) k[t] = coef[ii * BN_FQ2_HOOK_OPERANDS + t];
+  bool flag;
+  const Fp2 r = fq2_hook_op(op, a, b, c, d, s, k, flag);
+  const bool partner_flag = bn_partner_word(flag ? 1 : 0) != 0;
+  if (!live) return;
+  int32_t* o = out + i * BN_FQ2_HOOK_WORDS + BN_LIMBS * role;
+#pragma unroll
+  for (int j = 0; j < BN_LIMBS; ++j) o[j] = r.c[0].v[j];
+  if (role == 0) flags[i] = (uint8_t)((flag ? 1 : 0) | (flag != partner_flag ? 0x80 : 0));
+}
+__attribute__((visibility("hidden"))) int bn254_pair_debug_fq2_limbs(int op, const int32_t* d_in, const int32_t* d_coef, size_t n, int32_t* d_out,
+                                                                   uint8_t* d_flags, hipStream_t s) {
+  if (op < 0 || op >= FQ2_OP_COUNT) return BN254_E_BAD_ARGUMENT;
+  if (n == 0) return 0;
+  k_debug_fq2_limbs_pair<<<(unsigned)((2 * n + BN_PAIR_WG - 1) / BN_PAIR_WG), BN_PAIR_WG, 0, s>>>(op, d_in, d_coef, n, d_out, d_flags);
   HIP_TRY(hipGetLastError());
   return 0;
 }

@@ -697,6 +697,22 @@ class Engine:
         _check("bn254_debug_jacobi", self._lib.bn254_debug_jacobi(self._h, mode, bytes(a), None if b is None else bytes(b), n, value, flags))
         return value.raw[:n * 32], flags.raw[:n]
 
+    def debug_fq2_limbs(self, layout, op, operands, coef, n):
+        """one Fq2 primitive per item on raw limbs (include/bn254_hip.h: bn254_debug_fq2_limbs; layout 0 one lane, 1 a lane pair per item).
+        operands: n x 4 x 18 int32, coef: n x 4 int32 — as bytes in native order or as sequences of ints -> (n x 18 int32 as bytes, n flag bytes)"""
+        def words(x, count):
+            if isinstance(x, (bytes, bytearray, memoryview)):
+                x = bytes(x)
+                assert len(x) == 4 * count, (len(x), count)
+                return x
+            assert len(x) == count, (len(x), count)
+            return bytes((ctypes.c_int32 * max(count, 1))(*x))[:4 * count]
+        ops_b, coef_b = words(operands, n * 72), words(coef, n * 4)
+        out = ctypes.create_string_buffer(max(n, 1) * 72)
+        flags = ctypes.create_string_buffer(max(n, 1))
+        _check("bn254_debug_fq2_limbs", self._lib.bn254_debug_fq2_limbs(self._h, layout, op, ops_b, coef_b, n, out, flags))
+        return out.raw[:n * 72], flags.raw[:n]
+
     # ---- device-pointer entry points (inputs resident in HBM; enqueue only) ---------------
     def register_keys(self, pks, flags=0):
         """replace the context's registered key set (uncompressed G2, 128 B each); returns the per-key status bytes

@@ -1576,6 +1576,34 @@ int bn254_debug_hash_candidate(bn254_ctx *ctx, const uint8_t *h /* n*32 */, size
  * out_value in modes 0 and 2 = a as the passes received it; zeros where bit 7 is set.  b is read in mode 2 only (may be NULL otherwise).
  * BN254_E_BAD_ARGUMENT for another mode or a missing buffer; n == 0 returns 0. */
 int bn254_debug_jacobi(bn254_ctx *ctx, int mode, const uint8_t *a, const uint8_t *b, size_t n, uint8_t *out_value /* n*32 */, uint8_t *out_flags /* n */);
+/* ONE Fq / Fq2 primitive of the field layer (bn254_field.h, bn254_fp2_pair.h) per item on RAW limb vectors: an operand is 18 int32 — the 9
+ * limbs of the real coefficient, then of the imaginary one, value = sum limb_k 2^(29 k), Montgomery form (R = 2^261) — handed to the
+ * primitive as it stands: no decoding, no carry, no range check.  The result is 18 int32 as the primitive left them (not canonicalised)
+ * and one flag byte for the predicates.  Exists because the field layer is lazy: the interval tracker of the host builds proves the
+ * formulas under a postcondition it ASSUMES for every primitive, and the device runs other source than the host in the pair layout (DPP
+ * exchanges, the asm prologue of the squaring, the folded negation of the multiplication by xi) — this hook hands the device primitives
+ * chosen in-contract limb vectors at the contract's edge, which no byte decoder produces (tests/fq_limb_cases.py).  The caller keeps every
+ * operand inside the primitive's contract; outside it the limbs returned mean nothing (nothing else can happen: the kernels touch no
+ * memory but these buffers).
+ *   layout 0: one lane per item, the classic fp2_* / fp_* (bn254_devhooks.hip) | 1: one lane PAIR per item, even lane the real and odd lane the
+ *             imaginary coefficient, in the translation unit and workgroup shape of the lane-pair kernels (bn254_pair.hip).  The octet,
+ *             quad, nonet and lane-machine layouts have no entry here: they run these same per-lane primitives, and their exchanges are
+ *             entered by bn254_debug_final_exp_limbs with adversarial limb vectors.
+ *   operands: n x 4 x 18 (a, b, c, d of item i at 72 i); coef: n x 4 int32 (k0 .. k3).  Operands and factors an op does not name are ignored.
+ *   op:  0 a + b | 1 a - b | 2 -a | 3 2 a | 4 conj a | 5 i a | 6 k0 != 0 ? a : b                                (lazy: limb-wise)
+ *        7 norm a | 8 reduce_weak a | 9 lin2_reduce: k0 a + k1 b | 10 lin4_reduce: k0 a + k1 b + k2 c + k3 d (layout 0: coefficient-wise) |
+ *        11 8 a (mul8_spread) | 12 xi a | 13 xi norm(a)     (xi = 9 + i)
+ *        14 a b | 15 a^2 | 16 a times the real coefficient of b (mul_fp) | 17 1 / a (0 gives 0)
+ *        18 canon, coefficient-wise | 19 to_u256, coefficient-wise: the 8 words of the plain integer in limbs 0..7, limb 8 = 0 |
+ *        20 flag = a is zero | 21 flag = a equals b | 22 flag = u512_greater: a above b in the order (im, re) of the canonical integers |
+ *        23 norm_floor, coefficient-wise.       Ops 20 .. 22 return zero limbs.
+ *   (fp2_mul_sum, the sum of N products under one reduction, is instantiated only by the BN_PAIR_FP6_LAZY measurement build, not by this
+ *   library: it has no op.)
+ * flags[i] = 0 / 1; in layout 1 both lanes of the pair form the answer, and bit 7 is set if they ever disagree.
+ * BN254_E_BAD_ARGUMENT for another layout or op, for a missing buffer with n > 0, and for n above 14 913 080 (the operands of a call stay below
+ * 4 GiB); n == 0 returns 0. */
+int bn254_debug_fq2_limbs(bn254_ctx *ctx, int layout, int op, const int32_t *operands /* n*72 */, const int32_t *coef /* n*4 */, size_t n,
+                          int32_t *out /* n*18 */, uint8_t *flags /* n */);
 /* un-exponentiated Miller-loop value of each single pair (debugging aid) */
 int bn254_debug_miller_loop(bn254_ctx *ctx, const uint8_t *g1, const uint8_t *g2, size_t n, uint8_t *f /* n*384 */);
 

@@ -538,3 +538,21 @@ int hs_jacobi(int mode, const uint8_t* a, const uint8_t* b, uint8_t* out_value, 
   return 0;
 }
 }  // extern "C"
+
+// The host twin of bn254_debug_fq2_limbs, layout 0 (k_debug_fq2_limbs, bn254_devhooks.hip): op numbers and buffers as the hook's; the one switch
+// both share is bn254_fq2_hook.h.  In the tracker build every operand's intervals are set from the limbs it was handed (fq2_hook_fp), so a
+// case outside a primitive's contract aborts with BOUND VIOLATION.  Returns -1 for an op or buffer the hook refuses.
+#include "../../bn254_amd/csrc/bn254_fq2_hook.h"
+extern "C" int hs_fq2_limbs(int op, const int32_t* operands, const int32_t* coef, uint64_t n, int32_t* out, uint8_t* flags) {
+  if (op < 0 || op >= FQ2_OP_COUNT || (n && (!operands || !coef || !out || !flags))) return -1;
+  for (uint64_t i = 0; i < n; ++i) {
+    const int32_t* p = operands + i * (BN_FQ2_HOOK_OPERANDS * BN_FQ2_HOOK_WORDS);
+    const Fp2 a = fq2_hook_load(p, 0), b = fq2_hook_load(p + BN_FQ2_HOOK_WORDS, 0), c = fq2_hook_load(p + 2 * BN_FQ2_HOOK_WORDS, 0),
+              d = fq2_hook_load(p + 3 * BN_FQ2_HOOK_WORDS, 0);
+    bool flag;
+    const Fp2 r = fq2_hook_op(op, a, b, c, d, b.c0, coef + i * BN_FQ2_HOOK_OPERANDS, flag);
+    for (int j = 0; j < BN_LIMBS; ++j) { out[i * BN_FQ2_HOOK_WORDS + j] = r.c0.v[j]; out[i * BN_FQ2_HOOK_WORDS + BN_LIMBS + j] = r.c1.v[j]; }
+    flags[i] = flag ? 1 : 0;
+  }
+  return 0;
+}

@@ -20,6 +20,7 @@ static struct BnSiteInit { BnSiteInit() { for (int i = 0; i < 1024; ++i) bn_site
 #include "../../bn254_amd/csrc/bn254_codec_g2.h"
 #include "../../bn254_amd/csrc/bn254_nonet.h"
 #include "../../bn254_amd/csrc/bn254_lmachine.h"
+#include "../../bn254_amd/csrc/bn254_fq2_hook.h"
 
 using namespace bn254;
 
@@ -366,6 +367,22 @@ int hp_g2_decompress(const uint8_t* c65, uint8_t* out128) {
   return st;
 }
 // ... and the decoder's own status and point in this layout, before the subgroup test (hostsim.cpp: hs_g2_decompress_raw)
+// The host twin of bn254_debug_fq2_limbs, layout 1 (k_debug_fq2_limbs_pair, bn254_pair.hip): the host branches of bn254_fp2_pair.h, both lane
+// roles one after the other — the code the bound tracker proved, which the device's DPP branches have to match word for word.  Op numbers and
+// buffers as the hook's (bn254_fq2_hook.h); in the tracker build the operands' intervals come from the limbs handed over.  -1 = refused.
+int hp_fq2_limbs(int op, const int32_t* operands, const int32_t* coef, uint64_t n, int32_t* out, uint8_t* flags) {
+  if (op < 0 || op >= FQ2_OP_COUNT || (n && (!operands || !coef || !out || !flags))) return -1;
+  for (uint64_t i = 0; i < n; ++i) {
+    const int32_t* p = operands + i * (BN_FQ2_HOOK_OPERANDS * BN_FQ2_HOOK_WORDS);
+    const Fp2 a = fq2_hook_load(p, 0), b = fq2_hook_load(p + BN_FQ2_HOOK_WORDS, 0), c = fq2_hook_load(p + 2 * BN_FQ2_HOOK_WORDS, 0),
+              d = fq2_hook_load(p + 3 * BN_FQ2_HOOK_WORDS, 0);
+    bool flag;
+    const Fp2 r = fq2_hook_op(op, a, b, c, d, b.c[0], coef + i * BN_FQ2_HOOK_OPERANDS, flag);
+    for (int j = 0; j < BN_LIMBS; ++j) { out[i * BN_FQ2_HOOK_WORDS + j] = r.c[0].v[j]; out[i * BN_FQ2_HOOK_WORDS + BN_LIMBS + j] = r.c[1].v[j]; }
+    flags[i] = flag ? 1 : 0;
+  }
+  return 0;
+}
 int hp_g2_decompress_raw(const uint8_t* c65, uint8_t* out128) {
   G2Affine q;
   uint8_t st = decompress_g2(q, c65);

@@ -159,6 +159,41 @@ def pair_g2_decompress(c65, raw=False):
     o = _b(128); st = getattr(pair_lib(), "hp_g2_decompress_raw" if raw else "hp_g2_decompress")(bytes(c65), o); return st, o.raw
 
 
+_fq2 = {}
+# the four host twins of bn254_debug_fq2_limbs: (library, entry point) by layout and build
+_FQ2_TWINS = {(0, False): ("libhostsim.so", "hs_fq2_limbs"), (0, True): ("libhostsim_bounds.so", "hs_fq2_limbs"),
+              (1, False): ("libhostsim_pair.so", "hp_fq2_limbs"), (1, True): ("libhostsim_pair_bounds.so", "hp_fq2_limbs")}
+
+
+def fq2_limbs(layout, op, operands, coef, n, bounds=False):
+    """the host twin of bn254_debug_fq2_limbs (layout 0: hs_fq2_limbs, the classic fp2_*; 1: hp_fq2_limbs, the pair layout's host branches) on
+    n x 72 operand words and n x 4 factors given as bytes of native int32 -> (n x 18 int32 as bytes, n flag bytes, violated).  bounds: the
+    BN_TRACK_BOUNDS build, the operands' intervals set from the limbs handed over; it runs with the tracker in its recording mode (bn_bound_soft)
+    and `violated` says whether any precondition or column / limb / value bound failed during the call (always False in the plain builds)."""
+    key = (layout, bool(bounds))
+    if key not in _fq2:
+        name, entry = _FQ2_TWINS[key]
+        if not _built:                                  # only this twin's build: the GPU test needs the two plain ones, not the tracker and sanitizer builds
+            subprocess.check_call(["make", "-s", "-C", _HERE, name], stdout=subprocess.DEVNULL)
+        L = ctypes.CDLL(os.path.join(_HERE, name))
+        f = getattr(L, entry)
+        f.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_char_p, ctypes.c_char_p]
+        _fq2[key] = (L, f)
+    L, f = _fq2[key]
+    operands, coef = bytes(operands), bytes(coef)
+    assert len(operands) == n * 288 and len(coef) == n * 16, (len(operands), len(coef), n)
+    out, fl = _b(max(n, 1) * 72), _b(max(n, 1))
+    if bounds:
+        ctypes.c_int.in_dll(L, "bn_bound_soft").value = 1
+        ctypes.c_int.in_dll(L, "bn_bound_failed").value = 0
+    rc = f(op, operands, coef, n, out, fl)
+    assert rc == 0, (layout, op, rc)
+    violated = bool(ctypes.c_int.in_dll(L, "bn_bound_failed").value) if bounds else False
+    if bounds:
+        ctypes.c_int.in_dll(L, "bn_bound_soft").value = 0
+    return out.raw[:n * 72], fl.raw[:n], violated
+
+
 def g1_msum(pts):
     o = _b(64); st = lib().hs_g1_msum(b"".join(pts), len(pts), o); return st, o.raw
 

@@ -102,6 +102,33 @@ def test_header_is_plain_c_and_the_dev_hooks_can_be_hidden(tmp_path):
     # with the hooks hidden, naming one is an error (implicit declarations are errors under -Werror=implicit-function-declaration)
     p = subprocess.run(["gcc", "-std=c99", "-Werror=implicit-function-declaration", "-DTRY_HOOK", "-fsyntax-only", str(src)], capture_output=True, text=True)
     assert p.returncode != 0 and "bn254_debug_fp_op" in p.stderr
+    # ... the raw-limb hook as well; with the hooks visible its declaration takes exactly the arguments the Python binding declares
+    src2 = tmp_path / "t2.c"
+    src2.write_text('#ifdef HIDE\n#define BN254_NO_DEV_HOOKS 1\n#endif\n#include "%s"\n'
+                    'int hook(bn254_ctx *c, const int32_t *in, const int32_t *k, int32_t *out, uint8_t *fl) {\n'
+                    '  return bn254_debug_fq2_limbs(c, 1, 14, in, k, (size_t)3, out, fl);\n}\n' % hdr)
+    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-fsyntax-only", str(src2)])
+    p = subprocess.run(["gcc", "-std=c99", "-Werror=implicit-function-declaration", "-DHIDE", "-fsyntax-only", str(src2)], capture_output=True, text=True)
+    assert p.returncode != 0 and "bn254_debug_fq2_limbs" in p.stderr
+
+
+def test_fq2_limbs_hook_is_one_switch_in_four_builds():
+    """bn254_debug_fq2_limbs: both device kernels and both host twins go through the ONE switch of bn254_fq2_hook.h (no second copy of an op
+    anywhere), the pair layout's kernel lives in bn254_pair.hip with the workgroup shape of the other pair kernels, and its launcher is
+    declared in bn254_host.h"""
+    csrc = os.path.join(ROOT, "bn254_amd", "csrc")
+    read = lambda *p: open(os.path.join(*p)).read()
+    users = {"bn254_devhooks.hip": read(csrc, "bn254_devhooks.hip"), "bn254_pair.hip": read(csrc, "bn254_pair.hip"),
+             "hostsim.cpp": read(ROOT, "tests", "hostsim", "hostsim.cpp"), "hostsim_pair.cpp": read(ROOT, "tests", "hostsim", "hostsim_pair.cpp")}
+    for name, text in users.items():
+        assert text.count("fq2_hook_op(") == 1 and 'bn254_fq2_hook.h"' in text, name
+    for f in sorted(os.listdir(csrc)):
+        if f != "bn254_fq2_hook.h" and f.endswith((".hip", ".h", ".inc")):
+            assert "case FQ2_" not in read(csrc, f), f
+    assert re.search(r"KERNEL_PAIR void k_debug_fq2_limbs_pair\(", users["bn254_pair.hip"])
+    assert "k_debug_fq2_limbs_pair<<<(unsigned)((2 * n + BN_PAIR_WG - 1) / BN_PAIR_WG), BN_PAIR_WG, 0, s>>>" in users["bn254_pair.hip"]
+    assert "bn254_pair_debug_fq2_limbs(" in read(csrc, "bn254_host.h")
+    assert "bn254_debug_fq2_limbs" in _native.EXPORTED_SYMBOLS
 
 
 def test_routing_table_rows(tmp_path):

@@ -214,6 +214,8 @@ def load():
     L.bn254_batch_aggregate_verify_distinct_keyed_randomized_device.argtypes = [vp, vp, vp, vp, sz, vp, vp, sz, u32, vp, vp, vp]
     L.bn254_batch_g1_decompress.argtypes = [vp, vp, sz, vp, vp]
     L.bn254_batch_g2_decompress.argtypes = [vp, vp, sz, vp, vp]
+    if hasattr(L, "bn254_batch_g1_decompress_device"):                # absent from an older build loaded through BN254_LIB
+        L.bn254_batch_g1_decompress_device.argtypes = [vp, vp, sz, vp, vp, vp]
     L.bn254_debug_fp_op.argtypes = [vp, i32, vp, vp, sz, vp, vp]
     L.bn254_debug_fp12_op.argtypes = [vp, i32, vp, vp, sz, vp]
     L.bn254_debug_final_exp_limbs.argtypes = [vp, i32, vp, sz, vp, vp]
@@ -289,4 +291,5 @@ EXPORTED_SYMBOLS = [
     "bn254_debug_jacobi", "bn254_debug_fq2_limbs",
     "bn254_batch_g2_poly_eval", "bn254_batch_g2_poly_eval_device", "bn254_ctx_register_keys_commitments",
     "bn254_batch_g2_vector_combine", "bn254_batch_g2_vector_combine_device", "bn254_ctx_reshare_commitments",
+    "bn254_batch_g1_decompress_device",
 ]

@@ -363,36 +363,63 @@ class ECDSA:
         return [None if s == 0 else Error(s) for s in st]
 
     @staticmethod
-    def batch_verify_keyed(messages, signatures, key_indices, engine=None):
+    def _g1_input(signatures, compressed):
+        """-> (the list of a call's G1 input points as bytes, the engine flag).  compressed=True: the signatures are the 33-byte wire
+        encodings as `bytes` (Signature.to_compressed) — any other length raises Error(InvalidEncoding), as Signature.from_compressed
+        does — and are decompressed on the device, inside the call (include/bn254_hip.h: BN254_FLAG_G1_COMPRESSED): an encoding that
+        does not decompress gets the Error from_compressed would raise as its status and is never verified, taken or counted.  Else:
+        Signature objects, a raw encoding of the wrong length raises Error(InvalidLength)."""
+        if compressed:
+            raw = [bytes(s) for s in signatures]
+            if any(len(b) != _engine.G1_COMPRESSED_BYTES for b in raw):
+                raise Error(ErrorKind.InvalidEncoding)
+            return raw, _engine.FLAG_G1_COMPRESSED
+        raw = [s.raw for s in signatures]
+        if any(len(b) != _engine.G1_BYTES for b in raw):
+            raise Error(ErrorKind.InvalidLength)
+        return raw, 0
+
+    @staticmethod
+    def _flag_kw(flag):
+        """the keyword a call of the engine takes beyond its arguments without the flag: none for decoded signatures"""
+        return {"flags": flag} if flag else {}
+
+    @staticmethod
+    def batch_verify_keyed(messages, signatures, key_indices, engine=None, compressed=False):
         """batch_verify with public_keys[i] named by its index in the registered set: result[i] is None iff
         ECDSA.verify(messages[i], signatures[i], registered[key_indices[i]]) succeeds, Error(IndexOutOfBounds) for an index
-        outside the set, else the Error verify would raise."""
+        outside the set, else the Error verify would raise.  compressed=True: signatures[i] is the 33-byte wire encoding (bytes); the
+        Error Signature.from_compressed would raise comes first (ECDSA._g1_input)."""
         n = len(messages)
         if not (len(signatures) == n and len(key_indices) == n):
             raise Error(ErrorKind.InvalidLength)
+        raw, flag = ECDSA._g1_input(signatures, compressed)
         eng = engine or _eng()
-        st = eng.batch_verify_keyed([bytes(m) for m in messages], b"".join(s.raw for s in signatures), [int(k) for k in key_indices])
+        st = eng.batch_verify_keyed([bytes(m) for m in messages], b"".join(raw), [int(k) for k in key_indices], **ECDSA._flag_kw(flag))
         return [None if s == 0 else Error(s) for s in st]
 
     @staticmethod
-    def verify_keyed_signers(message, signature, signer_indices, engine=None):
+    def verify_keyed_signers(message, signature, signer_indices, engine=None, compressed=False):
         """One message, one already aggregated signature, and the indices (in the registered set, ECDSA.register_keys) of the keys that
         signed: None iff e(H(message), sum of those keys) * e(signature, -G2) == 1; raises Error(IndexOutOfBounds) for an index outside
         the set, a refused key's registration Error, else what verify raises (include/bn254_hip.h: bn254_batch_verify_keyed_bitmap).
-        Assumes a proof of possession of every registered key (ECDSA.register_keys_proven registers a set with its proofs checked)."""
-        _raise(ECDSA._keyed_signers_status([(message, signature, signer_indices)], engine)[0])
+        Assumes a proof of possession of every registered key (ECDSA.register_keys_proven registers a set with its proofs checked).
+        compressed=True: signature is the 33-byte wire encoding (ECDSA._g1_input)."""
+        _raise(ECDSA._keyed_signers_status([(message, signature, signer_indices)], engine, compressed=compressed)[0])
 
     @staticmethod
-    def _keyed_signers_status(items, engine, seed=None, flags=0):
+    def _keyed_signers_status(items, engine, seed=None, flags=0, compressed=False):
         rows = []
         for item in items:
-            if len(item) != 3 or len(item[1].raw) != _engine.G1_BYTES:
+            if len(item) != 3:
                 raise Error(ErrorKind.InvalidLength)
             message, signature, signer_indices = item
+            raw, flag = ECDSA._g1_input([signature], compressed)
             idx = [int(j) for j in signer_indices]
             if any(j < 0 for j in idx):
                 raise Error(ErrorKind.IndexOutOfBounds)
-            rows.append((bytes(message), signature.raw, idx))
+            rows.append((bytes(message), raw[0], idx))
+        flags |= _engine.FLAG_G1_COMPRESSED if compressed else 0
         eng = engine or _eng()
         # the bitmaps: as wide as the registered set plus ONE bit, on which every index outside the set lands (rule 2 reports the lowest bad
         # bit, and every such index lies above the set); an engine that does not know its set: as wide as the largest index
@@ -406,59 +433,63 @@ class ECDSA:
                 bits[i * bm_words + j // 32] |= 1 << (j % 32)
         if seed is not None:
             return eng.batch_verify_keyed_bitmap_randomized([r[0] for r in rows], b"".join(r[1] for r in rows), bits, bm_words, seed, flags)
-        return eng.batch_verify_keyed_bitmap([r[0] for r in rows], b"".join(r[1] for r in rows), bits, bm_words)
+        return eng.batch_verify_keyed_bitmap([r[0] for r in rows], b"".join(r[1] for r in rows), bits, bm_words, **ECDSA._flag_kw(flags))
 
     @staticmethod
-    def batch_verify_keyed_signers(items, engine=None):
+    def batch_verify_keyed_signers(items, engine=None, compressed=False):
         """items: a list of (message, signature, signer_indices); result[i] is None iff ECDSA.verify_keyed_signers on item i succeeds, else
-        the Error it would raise.  An item that is not such a triple raises Error(InvalidLength) before any device work."""
-        return [None if s == 0 else Error(s) for s in ECDSA._keyed_signers_status(items, engine)]
+        the Error it would raise.  An item that is not such a triple raises Error(InvalidLength) before any device work.
+        compressed=True: every signature is its 33-byte wire encoding (ECDSA._g1_input)."""
+        return [None if s == 0 else Error(s) for s in ECDSA._keyed_signers_status(items, engine, compressed=compressed)]
 
     @staticmethod
-    def aggregate_keyed_signers(message, signatures, key_indices, engine=None, n_keys=None):
+    def aggregate_keyed_signers(message, signatures, key_indices, engine=None, n_keys=None, compressed=False):
         """One message and the individual signatures of some registered keys (signatures[k] said to be by key key_indices[k] of the set,
         ECDSA.register_keys): every signature is verified against its key, those that pass are added — one per key, however many valid
         ones a key sent — and the result is (aggregate Signature, sorted indices of the keys that signed, statuses), statuses[k] None or
         the Error ECDSA.batch_verify_keyed would give signature k.  The pair feeds ECDSA.verify_keyed_signers.  Raises the message's
-        Error(HashToPointError) (include/bn254_hip.h: bn254_batch_collect_keyed_bitmap)."""
-        r = ECDSA.batch_aggregate_keyed_signers([(message, signatures, key_indices)], engine, n_keys)[0]
+        Error(HashToPointError) (include/bn254_hip.h: bn254_batch_collect_keyed_bitmap).  compressed=True: the signatures are their 33-byte
+        wire encodings (ECDSA._g1_input); the aggregate comes back as a Signature."""
+        r = ECDSA.batch_aggregate_keyed_signers([(message, signatures, key_indices)], engine, n_keys, compressed)[0]
         if isinstance(r, Error):
             raise r
         return r
 
     @staticmethod
-    def batch_aggregate_keyed_signers(items, engine=None, n_keys=None):
+    def batch_aggregate_keyed_signers(items, engine=None, n_keys=None, compressed=False):
         """items: a list of (message, signatures, key_indices); result[i] is what ECDSA.aggregate_keyed_signers returns for item i, or the
         Error it would raise.  A malformed item (not such a triple, lengths that differ, an index that is negative or >= 2^32) raises
         before any device work.  n_keys: the size of the registered set, for an engine that did not register it itself."""
-        return ECDSA._aggregate_keyed_signers(items, engine, n_keys)
+        return ECDSA._aggregate_keyed_signers(items, engine, n_keys, compressed=compressed)
 
     @staticmethod
-    def _aggregate_keyed_signers(items, engine, n_keys, seed=None, flags=0, optimistic=False):
+    def _aggregate_keyed_signers(items, engine, n_keys, seed=None, flags=0, optimistic=False, compressed=False):
         rows = []
         for item in items:
             if len(item) != 3:
                 raise Error(ErrorKind.InvalidLength)
             message, signatures, key_indices = item
             sigs, idx = list(signatures), [int(j) for j in key_indices]
-            if len(sigs) != len(idx) or any(len(s.raw) != _engine.G1_BYTES for s in sigs):
+            if len(sigs) != len(idx):
                 raise Error(ErrorKind.InvalidLength)
+            sigs, flag = ECDSA._g1_input(sigs, compressed)
             if any(j < 0 or j >= 1 << 32 for j in idx):
                 raise Error(ErrorKind.IndexOutOfBounds)
             rows.append((bytes(message), sigs, idx))
+        flags |= _engine.FLAG_G1_COMPRESSED if compressed else 0
         eng = engine or _eng()
         if n_keys is None:
             n_keys = getattr(eng, "n_registered_keys", None)
         if n_keys is None:             # the bitmaps are as wide as the registered set, which the items cannot tell
             raise ValueError("the engine does not know its registered key count: pass n_keys")
         bm_words = max((int(n_keys) + 31) // 32, 1)
-        args = ([r[0] for r in rows], b"".join(s.raw for r in rows for s in r[1]), [j for r in rows for j in r[2]], [len(r[2]) for r in rows], bm_words)
+        args = ([r[0] for r in rows], b"".join(s for r in rows for s in r[1]), [j for r in rows for j in r[2]], [len(r[2]) for r in rows], bm_words)
         if optimistic:
-            share_st, tuple_st, agg, bits = eng.batch_collect_keyed_bitmap_optimistic(*args)
+            share_st, tuple_st, agg, bits = eng.batch_collect_keyed_bitmap_optimistic(*args, **ECDSA._flag_kw(flags))
         elif seed is not None:
             share_st, tuple_st, agg, bits = eng.batch_collect_keyed_bitmap_randomized(*args, seed, flags)
         else:
-            share_st, tuple_st, agg, bits = eng.batch_collect_keyed_bitmap(*args)
+            share_st, tuple_st, agg, bits = eng.batch_collect_keyed_bitmap(*args, **ECDSA._flag_kw(flags))
         out, at = [], 0
         for i, (_, _, idx) in enumerate(rows):
             st = share_st[at:at + len(idx)]
@@ -472,7 +503,7 @@ class ECDSA:
         return out
 
     @staticmethod
-    def threshold_combine_keyed(message, signatures, key_indices, threshold, engine=None, n_keys=None):
+    def threshold_combine_keyed(message, signatures, key_indices, threshold, engine=None, n_keys=None, compressed=False):
         """t-of-n threshold BLS over the registered keys (ECDSA.register_keys; key j is the share key f(j + 1) * G2 of a dealing, so index 0
         is a legal signer): every share signatures[k], said to be by key key_indices[k], is verified against its key; if at least
         `threshold` keys have a valid share, the shares of the `threshold` LOWEST such keys are interpolated at zero.  Returns (the group
@@ -481,17 +512,17 @@ class ECDSA:
         keys — the error's .signers lists who was there, .statuses the shares' — and the message's Error(HashToPointError).  This call
         checks every share against its registered key; that the registered keys lie on one polynomial of degree threshold - 1 is
         ECDSA.check_dealing's to check, once per key set (include/bn254_hip.h: bn254_batch_threshold_combine_keyed)."""
-        r = ECDSA.batch_threshold_combine_keyed([(message, signatures, key_indices)], threshold, engine, n_keys)[0]
+        r = ECDSA.batch_threshold_combine_keyed([(message, signatures, key_indices)], threshold, engine, n_keys, compressed)[0]
         if isinstance(r, Error):
             raise r
         return r
 
     @staticmethod
-    def batch_threshold_combine_keyed(items, threshold, engine=None, n_keys=None):
+    def batch_threshold_combine_keyed(items, threshold, engine=None, n_keys=None, compressed=False):
         """items: a list of (message, signatures, key_indices), one threshold for all; result[i] is what ECDSA.threshold_combine_keyed returns
         for item i, or the Error it would raise.  A malformed item raises Error(InvalidLength) / Error(IndexOutOfBounds), a threshold below
-        1 ValueError, before any device work."""
-        return ECDSA._threshold_batch(items, threshold, engine, n_keys, False)
+        1 ValueError, before any device work.  compressed=True: the shares are their 33-byte wire encodings (ECDSA._g1_input)."""
+        return ECDSA._threshold_batch(items, threshold, engine, n_keys, False, compressed)
 
     @staticmethod
     def register_group_key(public_key, engine=None):
@@ -505,26 +536,26 @@ class ECDSA:
         _raise(eng.set_group_key(None if public_key is None else public_key.raw))
 
     @staticmethod
-    def threshold_combine_keyed_optimistic(message, signatures, key_indices, threshold, engine=None, n_keys=None):
+    def threshold_combine_keyed_optimistic(message, signatures, key_indices, threshold, engine=None, n_keys=None, compressed=False):
         """threshold_combine_keyed by interpolating the `threshold` lowest keys with a well-formed share first and verifying the RESULT once
         under the group key (ECDSA.register_group_key) — the check the signature's consumer will make.  A result that passes is the group
         signature; then the shares outside the keys used were not verified (their status is None if they are well-formed and name a
         registered key) and shares whose errors cancel under the coefficients read None.  A result that fails sends the tuple through
         the exact call: the same return value or Error.  Take threshold_combine_keyed when the per-share verdicts matter
         (include/bn254_hip.h: bn254_batch_threshold_combine_keyed_optimistic)."""
-        r = ECDSA.batch_threshold_combine_keyed_optimistic([(message, signatures, key_indices)], threshold, engine, n_keys)[0]
+        r = ECDSA.batch_threshold_combine_keyed_optimistic([(message, signatures, key_indices)], threshold, engine, n_keys, compressed)[0]
         if isinstance(r, Error):
             raise r
         return r
 
     @staticmethod
-    def batch_threshold_combine_keyed_optimistic(items, threshold, engine=None, n_keys=None):
+    def batch_threshold_combine_keyed_optimistic(items, threshold, engine=None, n_keys=None, compressed=False):
         """batch_threshold_combine_keyed, every item as threshold_combine_keyed_optimistic treats it.  A malformed item and a threshold below
         1 raise as there, an engine without a group key ValueError, all before any device work."""
-        return ECDSA._threshold_batch(items, threshold, engine, n_keys, True)
+        return ECDSA._threshold_batch(items, threshold, engine, n_keys, True, compressed)
 
     @staticmethod
-    def _threshold_batch(items, threshold, engine, n_keys, optimistic):
+    def _threshold_batch(items, threshold, engine, n_keys, optimistic, compressed=False):
         if int(threshold) < 1 or int(threshold) >= 1 << 32:
             raise ValueError("threshold must be between 1 and 2^32 - 1")
         rows = []
@@ -533,8 +564,9 @@ class ECDSA:
                 raise Error(ErrorKind.InvalidLength)
             message, signatures, key_indices = item
             sigs, idx = list(signatures), [int(j) for j in key_indices]
-            if len(sigs) != len(idx) or any(len(s.raw) != _engine.G1_BYTES for s in sigs):
+            if len(sigs) != len(idx):
                 raise Error(ErrorKind.InvalidLength)
+            sigs, _ = ECDSA._g1_input(sigs, compressed)
             if any(j < 0 or j >= 1 << 32 for j in idx):
                 raise Error(ErrorKind.IndexOutOfBounds)
             rows.append((bytes(message), sigs, idx))
@@ -548,8 +580,8 @@ class ECDSA:
             raise ValueError("the engine has no group key: ECDSA.register_group_key first")
         call = eng.batch_threshold_combine_keyed_optimistic if optimistic else eng.batch_threshold_combine_keyed
         share_st, tuple_st, group, bits, _ = call(
-            [r[0] for r in rows], b"".join(s.raw for r in rows for s in r[1]), [j for r in rows for j in r[2]], [len(r[2]) for r in rows], bm_words,
-            int(threshold))
+            [r[0] for r in rows], b"".join(s for r in rows for s in r[1]), [j for r in rows for j in r[2]], [len(r[2]) for r in rows], bm_words,
+            int(threshold), **ECDSA._flag_kw(_engine.FLAG_G1_COMPRESSED if compressed else 0))
         out, at = [], 0
         for i, (_, _, idx) in enumerate(rows):
             st = [None if b == 0 else Error(b) for b in share_st[at:at + len(idx)]]
@@ -742,7 +774,7 @@ class ECDSA:
         return Signature(out)
 
     @staticmethod
-    def merge_keyed_signers(message, parts, engine=None, n_keys=None):
+    def merge_keyed_signers(message, parts, engine=None, n_keys=None, compressed=False):
         """One message and some PARTIAL aggregates of it — parts[k] = (Signature, signer_indices), the sum of the signatures of those keys of
         the registered set, as a child of an aggregation tree sends it: every partial is verified as ECDSA.verify_keyed_signers verifies it,
         and, in the order given, the valid ones whose indices do not overlap what was taken before are added (first fit: sort by
@@ -750,17 +782,18 @@ class ECDSA:
         statuses[k] is None or the Error verify_keyed_signers would raise for partial k, taken[k] a bool.  The first two feed
         ECDSA.verify_keyed_signers.  Raises the message's Error(HashToPointError) (include/bn254_hip.h: bn254_batch_merge_keyed_bitmap).
         Assumes a proof of possession of every registered key (ECDSA.register_keys_proven registers a set with its proofs checked)."""
-        r = ECDSA.batch_merge_keyed_signers([(message, parts)], engine, n_keys)[0]
+        r = ECDSA.batch_merge_keyed_signers([(message, parts)], engine, n_keys, compressed=compressed)[0]
         if isinstance(r, Error):
             raise r
         return r
 
     @staticmethod
-    def batch_merge_keyed_signers(items, engine=None, n_keys=None, optimistic=False):
+    def batch_merge_keyed_signers(items, engine=None, n_keys=None, optimistic=False, compressed=False):
         """items: a list of (message, parts); result[i] is what ECDSA.merge_keyed_signers returns for item i, or the Error it would raise.
         A malformed item (not such a pair, a part that is not a pair, a signature of the wrong length, an index that is negative or >= 2^32)
         raises before any device work.  n_keys: the size of the registered set, for an engine that did not register it itself (without
-        either the bitmaps are as wide as the largest index).  optimistic: see batch_merge_keyed_signers_optimistic."""
+        either the bitmaps are as wide as the largest index).  optimistic: see batch_merge_keyed_signers_optimistic.  compressed=True: every
+        part's signature is its 33-byte wire encoding (ECDSA._g1_input); the merged aggregate comes back as a Signature."""
         rows = []
         for item in items:
             if not isinstance(item, (tuple, list)) or len(item) != 2:
@@ -768,12 +801,13 @@ class ECDSA:
             message, parts = item
             sigs, sets = [], []
             for part in parts:
-                if not isinstance(part, (tuple, list)) or len(part) != 2 or len(part[0].raw) != _engine.G1_BYTES:
+                if not isinstance(part, (tuple, list)) or len(part) != 2:
                     raise Error(ErrorKind.InvalidLength)
+                raw, _ = ECDSA._g1_input([part[0]], compressed)
                 idx = [int(j) for j in part[1]]
                 if any(j < 0 or j >= 1 << 32 for j in idx):
                     raise Error(ErrorKind.IndexOutOfBounds)
-                sigs.append(part[0].raw)
+                sigs.append(raw[0])
                 sets.append(idx)
             rows.append((bytes(message), sigs, sets))
         eng = engine or _eng()
@@ -792,7 +826,8 @@ class ECDSA:
                     row[j // 32] |= 1 << (j % 32)
                 bits += row
         merge = eng.merge_keyed_bitmap_optimistic if optimistic else eng.merge_keyed_bitmap
-        part_st, taken, tuple_st, agg, union = merge([r[0] for r in rows], b"".join(s for r in rows for s in r[1]), bits, [len(r[1]) for r in rows], bm_words)
+        part_st, taken, tuple_st, agg, union = merge([r[0] for r in rows], b"".join(s for r in rows for s in r[1]), bits, [len(r[1]) for r in rows], bm_words,
+                                                     **ECDSA._flag_kw(_engine.FLAG_G1_COMPRESSED if compressed else 0))
         out, at = [], 0
         for i, (_, sigs, _) in enumerate(rows):
             st, tk = part_st[at:at + len(sigs)], taken[at:at + len(sigs)]
@@ -806,7 +841,7 @@ class ECDSA:
         return out
 
     @staticmethod
-    def batch_merge_keyed_signers_optimistic(items, engine=None, n_keys=None):
+    def batch_merge_keyed_signers_optimistic(items, engine=None, n_keys=None, compressed=False):
         """batch_merge_keyed_signers with one verify per item — the sum of its partials that pass every check short of the pairing, against
         the keys of the union of their indices — and the partials verified one by one only in an item whose sum fails or in which two such
         partials overlap (include/bn254_hip.h: bn254_batch_merge_keyed_bitmap_optimistic).  The same result list and the same refusals
@@ -814,19 +849,19 @@ class ECDSA:
         partials whose errors cancel within an item that passes (sigma_a + D and sigma_b - D, also with no indices at all) read None and
         are taken — a None there means "taken into a sum that verifies", not "individually valid".  Who needs per-partial verdicts takes
         batch_merge_keyed_signers."""
-        return ECDSA.batch_merge_keyed_signers(items, engine, n_keys, optimistic=True)
+        return ECDSA.batch_merge_keyed_signers(items, engine, n_keys, optimistic=True, compressed=compressed)
 
     @staticmethod
-    def merge_keyed_signers_optimistic(message, parts, engine=None, n_keys=None):
+    def merge_keyed_signers_optimistic(message, parts, engine=None, n_keys=None, compressed=False):
         """merge_keyed_signers through batch_merge_keyed_signers_optimistic: the same quadruple, the same Errors raised, the same one
         deviation (partials whose errors cancel within a sum that verifies read None and are taken)."""
-        r = ECDSA.batch_merge_keyed_signers_optimistic([(message, parts)], engine, n_keys)[0]
+        r = ECDSA.batch_merge_keyed_signers_optimistic([(message, parts)], engine, n_keys, compressed)[0]
         if isinstance(r, Error):
             raise r
         return r
 
     @staticmethod
-    def batch_aggregate_keyed_signers_optimistic(items, engine=None, n_keys=None):
+    def batch_aggregate_keyed_signers_optimistic(items, engine=None, n_keys=None, compressed=False):
         """batch_aggregate_keyed_signers with one verify per item — the sum of its signatures that pass every check short of the pairing,
         against the sum of their keys — and the signatures verified one by one only in an item whose sum fails, that names a key twice, or
         that is too short (include/bn254_hip.h: bn254_batch_collect_keyed_bitmap_optimistic).  The same result list and the same refusals
@@ -834,18 +869,18 @@ class ECDSA:
         deviation: signatures whose errors cancel within an item that passes (sigma_a + D and sigma_b - D) read None and are counted — a
         None there means "counted in a sum that verifies", not "individually valid".  Who needs per-signature verdicts takes
         batch_aggregate_keyed_signers."""
-        return ECDSA._aggregate_keyed_signers(items, engine, n_keys, optimistic=True)
+        return ECDSA._aggregate_keyed_signers(items, engine, n_keys, optimistic=True, compressed=compressed)
 
     @staticmethod
-    def aggregate_keyed_signers_optimistic(message, signatures, key_indices, engine=None, n_keys=None):
+    def aggregate_keyed_signers_optimistic(message, signatures, key_indices, engine=None, n_keys=None, compressed=False):
         """aggregate_keyed_signers through batch_aggregate_keyed_signers_optimistic: the same triple, the same Errors raised."""
-        r = ECDSA.batch_aggregate_keyed_signers_optimistic([(message, signatures, key_indices)], engine, n_keys)[0]
+        r = ECDSA.batch_aggregate_keyed_signers_optimistic([(message, signatures, key_indices)], engine, n_keys, compressed)[0]
         if isinstance(r, Error):
             raise r
         return r
 
     @staticmethod
-    def batch_aggregate_keyed_signers_randomized(items, seed=None, engine=None, n_keys=None, rand64=False):
+    def batch_aggregate_keyed_signers_randomized(items, seed=None, engine=None, n_keys=None, rand64=False, compressed=False):
         """batch_aggregate_keyed_signers with the pairing checks of the signatures combined, 64 signatures of one key at a time across the
         items of the call (include/bn254_hip.h: bn254_batch_collect_keyed_bitmap_randomized): the same result list and the same refusals
         before any device work.  An Error among the statuses is always the exact one; a None is wrong with probability <= 2^-128 per group
@@ -856,18 +891,18 @@ class ECDSA:
             seed = os.urandom(32)
         if len(seed) != 32:
             raise ValueError("seed must be 32 bytes")
-        return ECDSA._aggregate_keyed_signers(items, engine, n_keys, bytes(seed), _engine.FLAG_RAND64 if rand64 else 0)
+        return ECDSA._aggregate_keyed_signers(items, engine, n_keys, bytes(seed), _engine.FLAG_RAND64 if rand64 else 0, compressed=compressed)
 
     @staticmethod
-    def aggregate_keyed_signers_randomized(message, signatures, key_indices, seed=None, engine=None, n_keys=None, rand64=False):
+    def aggregate_keyed_signers_randomized(message, signatures, key_indices, seed=None, engine=None, n_keys=None, rand64=False, compressed=False):
         """aggregate_keyed_signers through batch_aggregate_keyed_signers_randomized: the same triple, the same Errors raised."""
-        r = ECDSA.batch_aggregate_keyed_signers_randomized([(message, signatures, key_indices)], seed, engine, n_keys, rand64)[0]
+        r = ECDSA.batch_aggregate_keyed_signers_randomized([(message, signatures, key_indices)], seed, engine, n_keys, rand64, compressed)[0]
         if isinstance(r, Error):
             raise r
         return r
 
     @staticmethod
-    def batch_verify_keyed_signers_randomized(items, seed=None, engine=None, rand64=False):
+    def batch_verify_keyed_signers_randomized(items, seed=None, engine=None, rand64=False, compressed=False):
         """batch_verify_keyed_signers with the pairing checks of whole groups of items combined (include/bn254_hip.h:
         bn254_batch_verify_keyed_bitmap_randomized): the same result list; an Error is always the exact one, a None is wrong with probability
         <= 2^-128 per group (2^-64 with rand64) for a secret seed (32 bytes; default os.urandom)."""
@@ -877,19 +912,20 @@ class ECDSA:
         if len(seed) != 32:
             raise ValueError("seed must be 32 bytes")
         flags = _engine.FLAG_RAND64 if rand64 else 0
-        return [None if s == 0 else Error(s) for s in ECDSA._keyed_signers_status(items, engine, bytes(seed), flags)]
+        return [None if s == 0 else Error(s) for s in ECDSA._keyed_signers_status(items, engine, bytes(seed), flags, compressed)]
 
     @staticmethod
-    def batch_verify_keyed_randomized(messages, signatures, key_indices, seed=None, engine=None, rand64=False):
+    def batch_verify_keyed_randomized(messages, signatures, key_indices, seed=None, engine=None, rand64=False, compressed=False):
         """batch_verify_keyed through the combined check of items that share a key (64 per pairing product; include/bn254_hip.h:
         bn254_batch_verify_keyed_randomized).  Errors are exact; a None is wrong with probability <= 2^-128 per group."""
         import os
         n = len(messages)
         if not (len(signatures) == n and len(key_indices) == n):
             raise Error(ErrorKind.InvalidLength)
+        raw, flag = ECDSA._g1_input(signatures, compressed)
         eng = engine or _eng()
-        st = eng.batch_verify_keyed_randomized([bytes(m) for m in messages], b"".join(s.raw for s in signatures), [int(k) for k in key_indices],
-                                               seed if seed is not None else os.urandom(32), flags=_engine.FLAG_RAND64 if rand64 else 0)
+        st = eng.batch_verify_keyed_randomized([bytes(m) for m in messages], b"".join(raw), [int(k) for k in key_indices],
+                                               seed if seed is not None else os.urandom(32), flags=(_engine.FLAG_RAND64 if rand64 else 0) | flag)
         return [None if s == 0 else Error(s) for s in st]
 
     @staticmethod

@@ -360,7 +360,7 @@ enum AggdCall { AGGD_UNKEYED, AGGD_KEYED, AGGD_RANDOMIZED };
 static int aggd_call_device(bn254_ctx* c, AggdCall call, const AggdArgs& a, const uint8_t* seed32, void* stream) {
   MsgsLenScope msgs_len_scope(c);
   const void* third = a.keyed ? (const void*)a.d_key_idx : a.d_pks;
-  if (!c || (call == AGGD_RANDOMIZED && !seed32) || !a.d_agg_off || (a.n && (!a.d_sigs || !a.d_status)) || (a.m && (!a.d_msgs || !a.d_msg_off || !third)))
+  if (!c || g1c_flag(a.flags) || (call == AGGD_RANDOMIZED && !seed32) || !a.d_agg_off || (a.n && (!a.d_sigs || !a.d_status)) || (a.m && (!a.d_msgs || !a.d_msg_off || !third)))
     return BN254_E_BAD_ARGUMENT;
   if (a.m > 0xFFFFFFFFu || a.n > 0xFFFFFFFFu) return BN254_E_BAD_ARGUMENT;
   if (call == AGGD_RANDOMIZED) c->aggr_last_ran = 0;
@@ -378,7 +378,7 @@ static int aggd_call_device(bn254_ctx* c, AggdCall call, const AggdArgs& a, cons
 static int aggd_call_host(bn254_ctx* c, AggdCall call, const uint8_t* msgs, const uint64_t* msg_off, const void* third, size_t third_size, size_t m,
                           const uint8_t* agg_sigs, const uint64_t* agg_off, size_t n, uint32_t flags, const uint8_t* seed32, uint8_t* status) {
   MsgsLenScope msgs_len_scope(c);
-  if (!c || (call == AGGD_RANDOMIZED && !seed32) || !msg_off || !agg_off || (n && (!agg_sigs || !status)) || (m && !third)) return BN254_E_BAD_ARGUMENT;
+  if (!c || g1c_flag(flags) || (call == AGGD_RANDOMIZED && !seed32) || !msg_off || !agg_off || (n && (!agg_sigs || !status)) || (m && !third)) return BN254_E_BAD_ARGUMENT;
   if (m > 0xFFFFFFFFu || n > 0xFFFFFFFFu) return BN254_E_BAD_ARGUMENT;
   if (agg_off[0] != 0 || agg_off[n] != m || !offsets_ok(agg_off, n) || !offsets_ok(msg_off, m)) return BN254_E_BAD_ARGUMENT;
   if (call == AGGD_RANDOMIZED) c->aggr_last_ran = 0;

@@ -103,6 +103,10 @@ extern "C" {
 
 int bn254_batch_verify_keyed_bitmap_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t* d_off, const uint8_t* d_sigs, const uint32_t* d_bits,
                                            size_t bm_words, size_t n, uint32_t flags, uint8_t* d_status, void* stream) {
+  if (g1c_flag(flags))                                  // compressed aggregates: staged once, in front of any slicing
+    return g1c_call(c, d_sigs, n, n != 0, d_status, stream, [&](const uint8_t* d_sigs64) {
+      return bn254_batch_verify_keyed_bitmap_device(c, d_msgs, d_off, d_sigs64, d_bits, bm_words, n, flags & ~BN254_FLAG_G1_COMPRESSED, d_status, stream);
+    });
   MsgsLenScope msgs_len_scope(c);
   if (!c || (n && (!d_msgs || !d_off || !d_sigs || !d_status || (bm_words && !d_bits))) || bm_words > 0xFFFFFFFFu) return BN254_E_BAD_ARGUMENT;
   if (n == 0) return 0;
@@ -142,7 +146,7 @@ int bn254_batch_verify_keyed_bitmap(bn254_ctx* c, const uint8_t* msgs, const uin
   if (!msgs_ok(msgs, off, n)) return BN254_E_BAD_ARGUMENT;
   HostStaging st(c);
   const uint8_t *d_msgs = st.in(0, msgs, (size_t)off[n]), *d_off = st.in(1, off, (n + 1) * sizeof(uint64_t));
-  const uint8_t *d_sigs = st.in(2, sigs, n * 64), *d_bits = st.in(3, bits, n * bm_words * sizeof(uint32_t));
+  const uint8_t *d_sigs = st.in(2, sigs, n * g1_item_bytes(flags)), *d_bits = st.in(3, bits, n * bm_words * sizeof(uint32_t));
   uint8_t* d_status = st.out(4, n, status);
   if (st.ok())
     st.rc = bn254_batch_verify_keyed_bitmap_device(c, d_msgs, (const uint64_t*)d_off, d_sigs, (const uint32_t*)d_bits, bm_words, n, flags, d_status, nullptr);

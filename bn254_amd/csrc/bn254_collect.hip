@@ -118,7 +118,7 @@ void cl_stage(HostStaging& st, const ClCall& a, size_t aux_words, int out_slot, 
   *d = a;
   d->msgs = st.in(0, a.msgs, (size_t)a.msg_off[n]);
   d->msg_off = (const uint64_t*)st.in(1, a.msg_off, (n + 1) * sizeof(uint64_t));
-  d->items = st.in(2, a.items, m * 64);
+  d->items = st.in(2, a.items, m * g1_item_bytes(a.flags));
   const uint8_t* d_aux = st.in(3, a.aux, m * aux_words * sizeof(uint32_t));
   d->aux = aux_words ? (const uint32_t*)d_aux : nullptr;
   d->off = (const uint64_t*)st.in(4, a.off, (n + 1) * sizeof(uint64_t));
@@ -513,6 +513,8 @@ int cl_collect_run(bn254_ctx* c, const ClCall& call, const uint8_t* seed32, bool
 
 // the checked entry of the three *_device calls
 static int cl_collect_device(bn254_ctx* c, const ClCall& a, const uint8_t* seed32, bool optimistic, void* stream) {
+  if (g1c_flag(a.flags))                                // compressed shares: staged once, in front of the hash and of any slicing
+    return cl_g1c_call(c, a, stream, [&](const ClCall& d) { return cl_collect_device(c, d, seed32, optimistic, stream); });
   MsgsLenScope msgs_len_scope(c);
   if (c) c->clr_last_ran = c->clo_last_ran = c->mgo_last_ran = c->tho_last_ran = 0;
   int rc = BN254_E_BAD_ARGUMENT;

@@ -656,7 +656,8 @@ int bn254_batch_aggregate_verify_device(bn254_ctx* c, const uint8_t* d_msgs, con
                                         size_t n_signers, const uint8_t* d_sig_pool, const uint32_t* d_tuple_msg, const uint64_t* d_tuple_off,
                                         const uint32_t* d_signer_idx, size_t n, uint32_t flags, uint8_t* d_status, void* stream) {
   MsgsLenScope msgs_len_scope(c);
-  if (!c || !n_msgs || !n_signers || (n && (!d_msgs || !d_msg_off || !d_pk_pool || !d_sig_pool || !d_tuple_msg || !d_tuple_off || !d_signer_idx || !d_status)))
+  if (!c || !n_msgs || !n_signers || g1c_flag(flags) ||
+      (n && (!d_msgs || !d_msg_off || !d_pk_pool || !d_sig_pool || !d_tuple_msg || !d_tuple_off || !d_signer_idx || !d_status)))
     return BN254_E_BAD_ARGUMENT;
   if (n == 0) return 0;
   if (misaligned(d_pk_pool) || misaligned(d_sig_pool) || misaligned(d_tuple_msg) || misaligned(d_signer_idx) || ((uintptr_t)d_msg_off & 7u) ||
@@ -678,7 +679,7 @@ int bn254_batch_aggregate_verify_device(bn254_ctx* c, const uint8_t* d_msgs, con
 int bn254_ctx_register_pools_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t* d_msg_off, size_t n_msgs, const uint8_t* d_pk_pool, size_t n_signers,
                                     const uint8_t* d_sig_pool, uint32_t flags, size_t expect_tuples, void* stream) {
   MsgsLenScope msgs_len_scope(c);
-  if (!c || !n_msgs || !n_signers || !d_msgs || !d_msg_off || !d_pk_pool || !d_sig_pool) return BN254_E_BAD_ARGUMENT;
+  if (!c || !n_msgs || !n_signers || g1c_flag(flags) || !d_msgs || !d_msg_off || !d_pk_pool || !d_sig_pool) return BN254_E_BAD_ARGUMENT;
   if (misaligned(d_pk_pool) || misaligned(d_sig_pool) || ((uintptr_t)d_msg_off & 7u)) return BN254_E_MISALIGNED;
   HIP_TRY(hipSetDevice(c->device));
   { int rc_ = ctx_quiesce(c); if (rc_) return rc_; }   // no aggregate verify may still be reading the previous tables
@@ -690,7 +691,7 @@ int bn254_ctx_register_pools_device(bn254_ctx* c, const uint8_t* d_msgs, const u
 int bn254_ctx_register_pools(bn254_ctx* c, const uint8_t* msgs, const uint64_t* msg_off, size_t n_msgs, const uint8_t* pk_pool, size_t n_signers,
                              const uint8_t* sig_pool, uint32_t flags, size_t expect_tuples) {
   MsgsLenScope msgs_len_scope(c);
-  if (!c || !n_msgs || !n_signers || !msg_off || !pk_pool || !sig_pool) return BN254_E_BAD_ARGUMENT;
+  if (!c || !n_msgs || !n_signers || g1c_flag(flags) || !msg_off || !pk_pool || !sig_pool) return BN254_E_BAD_ARGUMENT;
   if (!msgs_ok(msgs, msg_off, n_msgs)) return BN254_E_BAD_ARGUMENT;
   HIP_TRY(hipSetDevice(c->device));
   HostStaging st(c);
@@ -733,7 +734,8 @@ int bn254_batch_aggregate_verify(bn254_ctx* c, const uint8_t* msgs, const uint64
                                  const uint8_t* sig_pool, const uint32_t* tuple_msg, const uint64_t* tuple_off, const uint32_t* signer_idx, size_t n,
                                  uint32_t flags, uint8_t* status) {
   MsgsLenScope msgs_len_scope(c);
-  if (!c || !n_msgs || !n_signers || (n && (!msg_off || !pk_pool || !sig_pool || !tuple_msg || !tuple_off || !signer_idx || !status))) return BN254_E_BAD_ARGUMENT;
+  if (!c || !n_msgs || !n_signers || g1c_flag(flags) || (n && (!msg_off || !pk_pool || !sig_pool || !tuple_msg || !tuple_off || !signer_idx || !status)))
+    return BN254_E_BAD_ARGUMENT;
   if (n == 0) return 0;
   if (!offsets_ok(tuple_off, n) || !msgs_ok(msgs, msg_off, n_msgs)) return BN254_E_BAD_ARGUMENT;
   HIP_TRY(hipSetDevice(c->device));

@@ -878,6 +878,7 @@ void bn254_ctx_destroy(bn254_ctx* c) {
   if (c->bm_tab) (void)hipFree(c->bm_tab);
   if (c->pop_buf) (void)hipFree(c->pop_buf);
   if (c->th_buf) (void)hipFree(c->th_buf);
+  if (c->g1c_buf) (void)hipFree(c->g1c_buf);
   if (c->gk_lines) (void)hipFree(c->gk_lines);
   if (c->gk_xy) (void)hipFree(c->gk_xy);
   if (c->gk_st) (void)hipFree(c->gk_st);
@@ -1130,7 +1131,7 @@ static int verify_after_decode(bn254_ctx* c, hipStream_t s, const uint8_t* d_msg
 int bn254_batch_verify_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t* d_off, const uint8_t* d_sigs, const uint8_t* d_pks,
                               size_t n, uint32_t flags, uint8_t* d_status, void* stream) {
   MsgsLenScope msgs_len_scope(c);
-  if (!c || (n && (!d_msgs || !d_off || !d_sigs || !d_pks || !d_status))) return BN254_E_BAD_ARGUMENT;
+  if (!c || g1c_flag(flags) || (n && (!d_msgs || !d_off || !d_sigs || !d_pks || !d_status))) return BN254_E_BAD_ARGUMENT;
   if (n == 0) return 0;
   if (misaligned(d_sigs) || misaligned(d_pks) || ((uintptr_t)d_off & 7u)) return BN254_E_MISALIGNED;
   HIP_TRY(hipSetDevice(c->device));
@@ -1337,7 +1338,7 @@ static int verify_host_overlapped(bn254_ctx* c, const uint8_t* msgs, const uint6
 int bn254_batch_verify(bn254_ctx* c, const uint8_t* msgs, const uint64_t* off, const uint8_t* sigs, const uint8_t* pks, size_t n,
                        uint32_t flags, uint8_t* status) {
   MsgsLenScope msgs_len_scope(c);
-  if (!c || (n && (!off || !sigs || !pks || !status))) return BN254_E_BAD_ARGUMENT;
+  if (!c || g1c_flag(flags) || (n && (!off || !sigs || !pks || !status))) return BN254_E_BAD_ARGUMENT;
   if (n == 0) return 0;
   HIP_TRY(hipSetDevice(c->device));
   if (!msgs_ok(msgs, off, n)) return BN254_E_BAD_ARGUMENT;
@@ -1391,7 +1392,7 @@ int bn254_batch_hash_to_g1(bn254_ctx* c, const uint8_t* msgs, const uint64_t* of
 // shared by pairing / pairing_check: mode 0 = reduced Gt + status, 1 = raw Miller value (debug)
 static int pairing_device(bn254_ctx* c, const uint8_t* d_g1, const uint8_t* d_g2, size_t n, size_t k, uint32_t flags, uint8_t* d_gt,
                           uint8_t* d_status, void* stream, int raw_only) {
-  if (!c || k == 0 || (n && (!d_g1 || !d_g2))) return BN254_E_BAD_ARGUMENT;
+  if (!c || k == 0 || g1c_flag(flags) || (n && (!d_g1 || !d_g2))) return BN254_E_BAD_ARGUMENT;
   if (n == 0) return 0;
   if (misaligned(d_g1) || misaligned(d_g2) || (d_gt && misaligned(d_gt))) return BN254_E_MISALIGNED;
   HIP_TRY(hipSetDevice(c->device));
@@ -1431,7 +1432,7 @@ int bn254_batch_pairing_device(bn254_ctx* c, const uint8_t* d_g1, const uint8_t*
 }
 static int pairing_host(bn254_ctx* c, const uint8_t* g1, const uint8_t* g2, size_t n, size_t k, uint32_t flags, uint8_t* gt, uint8_t* status,
                         int raw_only) {
-  if (!c || k == 0 || (n && (!g1 || !g2))) return BN254_E_BAD_ARGUMENT;
+  if (!c || k == 0 || g1c_flag(flags) || (n && (!g1 || !g2))) return BN254_E_BAD_ARGUMENT;
   if (n == 0) return 0;
   HIP_TRY(hipSetDevice(c->device));
   HostStaging st(c);
@@ -1454,7 +1455,7 @@ int bn254_debug_miller_loop(bn254_ctx* c, const uint8_t* g1, const uint8_t* g2, 
 }
 
 int bn254_batch_check_public_keys(bn254_ctx* c, const uint8_t* pk_g2, const uint8_t* pk_g1, size_t n, uint32_t flags, uint8_t* status) {
-  if (!c || (n && (!pk_g2 || !pk_g1 || !status))) return BN254_E_BAD_ARGUMENT;
+  if (!c || g1c_flag(flags) || (n && (!pk_g2 || !pk_g1 || !status))) return BN254_E_BAD_ARGUMENT;
   if (n == 0) return 0;
   HIP_TRY(hipSetDevice(c->device));
   int rc;

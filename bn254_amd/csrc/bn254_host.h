@@ -166,6 +166,10 @@ struct bn254_ctx {
   int th_opt_min_shares;     // BN254_OPT_THRESHOLD_OPT_MIN_SHARES: the optimistic threshold call from this many shares on
   uint32_t* tho_stats;       // what its last call did on the device (bn254_debug_threshold_opt_last); inside collect_buf
   int tho_last_ran;          // ... and whether that call took the optimistic route at all
+  // compressed G1 input of the registered-key calls (bn254_g1stage.hip): per item the 64 bytes the call reads in its place, then the pre-status
+  // bytes, grown on demand
+  uint8_t* g1c_buf;
+  size_t g1c_cap;
 };
 
 struct ScopedEvents {
@@ -427,6 +431,45 @@ BN_HIDDEN int clo_settle(bn254_ctx* c, hipStream_t s, const ClCall& a, const ClS
 // map[e] of d_bits into the Q planes of entry map[e]; rule 2 is the caller's.  n = the most the queue can hold
 BN_HIDDEN int launch_bitmap_sum_queued(bn254_ctx* c, hipStream_t s, const uint32_t* d_bits, size_t bm_words, size_t n, bool tables, const uint32_t* map,
                                        const uint32_t* count);
+// Compressed G1 input (BN254_FLAG_G1_COMPRESSED; bn254_g1stage.hip, bodies in bn254_g1stage.h).  An entry point that does not take the flag
+// refuses it, so that no call reads 33-byte data at a 64-byte stride:
+static inline bool g1c_flag(uint32_t flags) { return (flags & BN254_FLAG_G1_COMPRESSED) != 0; }
+// ... bytes per G1 item of a call's input array under its flags (what a host form stages)
+static inline size_t g1_item_bytes(uint32_t flags) { return g1c_flag(flags) ? 33 : 64; }
+// The three steps around a call that takes it.  g1c_reserve: c->g1c_buf for n items (growing it waits for the context's streams: before the
+// call's first kernel).  g1c_stage: one lane per item, d_in33 (no alignment) -> the 64 bytes the call reads instead at c->g1c_buf + 64 i and
+// the pre-status at g1c_pre(c, n)[i].  g1c_overlay, behind the call: d_status[i] = pre where pre != 0 and the call wrote 6.
+BN_HIDDEN int g1c_reserve(bn254_ctx* c, size_t n);
+BN_HIDDEN int g1c_stage(bn254_ctx* c, hipStream_t s, const uint8_t* d_in33, size_t n);
+BN_HIDDEN int g1c_overlay(bn254_ctx* c, hipStream_t s, size_t n, uint8_t* d_status);
+static inline uint8_t* g1c_pre(const bn254_ctx* c, size_t n) { return c->g1c_buf + 64 * n; }
+// A *_device entry point under the flag, at its outermost entry and before any slicing: stage the n_items encodings, run(items64) = the same
+// call with the flag cleared on the staged items — the existing route, untouched, its own checks included —, then the overlay over d_status.
+// live: the call has work (n != 0).  A call without items, or one whose checks will refuse it anyway (no items array, no status array), runs
+// on a null items pointer: nothing is staged and nothing read.  Profiling: the staging lies in front of the call's first event.
+template <class Run> static inline int g1c_call(bn254_ctx* c, const uint8_t* d_in33, size_t n_items, bool live, uint8_t* d_status, void* stream, Run run) {
+  MsgsLenScope msgs_len_scope(c);
+  if (!c || n_items > 0xFFFFFFFFu) return BN254_E_BAD_ARGUMENT;
+  if (!live || !n_items || !d_in33 || !d_status) return run((const uint8_t*)nullptr);
+  if (const hipError_t e = hipSetDevice(c->device)) return -(int)e;
+  int rc = g1c_reserve(c, n_items);
+  if (rc) return rc;
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  CallDone call_done(c, s);
+  if ((rc = g1c_stage(c, s, d_in33, n_items))) return rc;
+  if ((rc = run((const uint8_t*)c->g1c_buf))) return rc;
+  return g1c_overlay(c, s, n_items, d_status);
+}
+// ... the same for a call of the collect family (items = the shares or the partials, statuses = a.item_status): run(d) with d = the call on
+// the staged items, flag cleared.  cl_stage stages 33 bytes per item under the flag; a host form hands the flag on to its device form.
+template <class Run> static inline int cl_g1c_call(bn254_ctx* c, const ClCall& a, void* stream, Run run) {
+  return g1c_call(c, a.items, a.n_items, a.n != 0, a.item_status, stream, [&](const uint8_t* items64) {
+    ClCall d = a;
+    d.items = items64;
+    d.flags &= ~BN254_FLAG_G1_COMPRESSED;
+    return run(d);
+  });
+}
 // developer hook bn254_debug_fq2_limbs, layout 1 (bn254_pair.hip: k_debug_fq2_limbs_pair): one Fq2 primitive per lane pair on raw limbs; the
 // buffers are device memory in the hook's format
 BN_HIDDEN int bn254_pair_debug_fq2_limbs(int op, const int32_t* d_in, const int32_t* d_coef, size_t n, int32_t* d_out, uint8_t* d_flags, hipStream_t s);

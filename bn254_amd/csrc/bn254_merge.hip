@@ -188,6 +188,8 @@ static int mg_optimistic(bn254_ctx* c, hipStream_t s, const ClCall& a, size_t t_
 static bool mg_parts_ok(const ClCall& a) { return !(a.n && a.n_items && (!a.item_taken || (a.bm_words && !a.aux))); }
 // both calls: !optimistic is the exact one
 static int mg_merge_device(bn254_ctx* c, const ClCall& a, bool optimistic, void* stream) {
+  if (g1c_flag(a.flags))                                // compressed partials: staged once, in front of the hash and of any slicing
+    return cl_g1c_call(c, a, stream, [&](const ClCall& d) { return mg_merge_device(c, d, optimistic, stream); });
   MsgsLenScope msgs_len_scope(c);
   if (c) c->mgo_last_ran = 0;
   int rc = BN254_E_BAD_ARGUMENT;

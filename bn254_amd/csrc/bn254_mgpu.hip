@@ -613,7 +613,7 @@ int bn254_mgpu_last_timing(bn254_mgpu* mg, float* compute_ms, float* collective_
 
 int bn254_mgpu_batch_verify(bn254_mgpu* mg, const uint8_t* msgs, const uint64_t* off, const uint8_t* sigs, const uint8_t* pks, size_t n,
                             uint32_t flags, uint8_t* status) {
-  if (!mg || (n && (!off || !sigs || !pks || !status))) return BN254_E_BAD_ARGUMENT;
+  if (!mg || (flags & BN254_FLAG_G1_COMPRESSED) || (n && (!off || !sigs || !pks || !status))) return BN254_E_BAD_ARGUMENT;
   if (n == 0) return 0;
   if (!offsets_ok(off, n)) return BN254_E_BAD_ARGUMENT;      // the WHOLE array, before any shard starts
   if (off[n] && !msgs) return BN254_E_BAD_ARGUMENT;
@@ -655,7 +655,7 @@ int bn254_mgpu_register_keys(bn254_mgpu* mg, const uint8_t* pks, size_t n_keys, 
   return run_all(mg, job_register_keys, &a);
 }
 int bn254_mgpu_register_keys_pop(bn254_mgpu* mg, const uint8_t* pks, const uint8_t* pops, size_t n_keys, uint32_t flags, uint8_t* key_status) {
-  if (!mg || (n_keys && (!pks || !pops))) return BN254_E_BAD_ARGUMENT;
+  if (!mg || (flags & BN254_FLAG_G1_COMPRESSED) || (n_keys && (!pks || !pops))) return BN254_E_BAD_ARGUMENT;
   DeviceGuard guard;
   mg->err[0] = 0;
   RegisterKeysPopArgs a = {pks, pops, n_keys, flags, key_status};
@@ -664,7 +664,7 @@ int bn254_mgpu_register_keys_pop(bn254_mgpu* mg, const uint8_t* pks, const uint8
 
 int bn254_mgpu_batch_verify_keyed(bn254_mgpu* mg, const uint8_t* msgs, const uint64_t* off, const uint8_t* sigs, const uint32_t* key_idx, size_t n,
                                   uint32_t flags, uint8_t* status) {
-  if (!mg || (n && (!off || !sigs || !key_idx || !status))) return BN254_E_BAD_ARGUMENT;
+  if (!mg || (flags & BN254_FLAG_G1_COMPRESSED) || (n && (!off || !sigs || !key_idx || !status))) return BN254_E_BAD_ARGUMENT;
   if (n == 0) return 0;
   if (!offsets_ok(off, n)) return BN254_E_BAD_ARGUMENT;      // the WHOLE array, before any shard starts
   if (off[n] && !msgs) return BN254_E_BAD_ARGUMENT;
@@ -677,7 +677,9 @@ int bn254_mgpu_batch_verify_keyed(bn254_mgpu* mg, const uint8_t* msgs, const uin
 int bn254_mgpu_batch_aggregate_verify(bn254_mgpu* mg, const uint8_t* msgs, const uint64_t* msg_off, size_t n_msgs, const uint8_t* pk_pool, size_t n_signers,
                                       const uint8_t* sig_pool, const uint32_t* tuple_msg, const uint64_t* tuple_off, const uint32_t* signer_idx, size_t n,
                                       uint32_t flags, uint8_t* status) {
-  if (!mg || !n_msgs || !n_signers || (n && (!msg_off || !pk_pool || !sig_pool || !tuple_msg || !tuple_off || !signer_idx || !status))) return BN254_E_BAD_ARGUMENT;
+  if (!mg || !n_msgs || !n_signers || (flags & BN254_FLAG_G1_COMPRESSED) ||
+      (n && (!msg_off || !pk_pool || !sig_pool || !tuple_msg || !tuple_off || !signer_idx || !status)))
+    return BN254_E_BAD_ARGUMENT;
   if (n == 0) return 0;
   // as the single-GPU entry point (bn254_group.hip): both offset arrays non-decreasing, or nothing is touched.  Every shard's signer slice
   // signer_idx + tuple_off[lo] of length tuple_off[hi] - tuple_off[lo] then lies inside the caller's signer_idx[0 .. tuple_off[n]).
@@ -691,7 +693,7 @@ int bn254_mgpu_batch_aggregate_verify(bn254_mgpu* mg, const uint8_t* msgs, const
 
 int bn254_mgpu_batch_pairing(bn254_mgpu* mg, const uint8_t* g1, const uint8_t* g2, size_t n, size_t k, uint32_t flags, uint8_t* gt,
                              uint8_t* status, uint64_t* checksum) {
-  if (!mg || k == 0 || (n && (!g1 || !g2 || !gt))) return BN254_E_BAD_ARGUMENT;
+  if (!mg || k == 0 || (flags & BN254_FLAG_G1_COMPRESSED) || (n && (!g1 || !g2 || !gt))) return BN254_E_BAD_ARGUMENT;
   if (checksum) *checksum = 0;
   if (n == 0) return 0;
   DeviceGuard guard;
@@ -706,7 +708,7 @@ int bn254_mgpu_batch_pairing(bn254_mgpu* mg, const uint8_t* g1, const uint8_t* g
 
 int bn254_mgpu_batch_verify_device(bn254_mgpu* mg, const uint8_t* const* d_msgs, const uint64_t* const* d_off, const uint8_t* const* d_sigs,
                                    const uint8_t* const* d_pks, size_t n, uint32_t flags, uint8_t* const* d_status_all, void* const* streams) {
-  if (!mg || (n && (!d_msgs || !d_off || !d_sigs || !d_pks || !d_status_all))) return BN254_E_BAD_ARGUMENT;
+  if (!mg || (flags & BN254_FLAG_G1_COMPRESSED) || (n && (!d_msgs || !d_off || !d_sigs || !d_pks || !d_status_all))) return BN254_E_BAD_ARGUMENT;
   if (n == 0) return 0;
   for (int g = 0; g < mg->G; ++g) {
     size_t lo, hi;
@@ -724,7 +726,7 @@ int bn254_mgpu_batch_verify_device(bn254_mgpu* mg, const uint8_t* const* d_msgs,
 
 int bn254_mgpu_batch_pairing_device(bn254_mgpu* mg, const uint8_t* const* d_g1, const uint8_t* const* d_g2, size_t n, size_t k, uint32_t flags,
                                     uint8_t* const* d_gt, uint8_t* const* d_status_all, uint64_t* const* d_checksum, void* const* streams) {
-  if (!mg || k == 0 || (n && (!d_g1 || !d_g2 || !d_status_all)) || (d_checksum && !d_gt)) return BN254_E_BAD_ARGUMENT;
+  if (!mg || k == 0 || (flags & BN254_FLAG_G1_COMPRESSED) || (n && (!d_g1 || !d_g2 || !d_status_all)) || (d_checksum && !d_gt)) return BN254_E_BAD_ARGUMENT;
   if (n == 0) return 0;
   for (int g = 0; g < mg->G; ++g) {
     size_t lo, hi;

@@ -92,7 +92,7 @@ struct PopKeysGuard {
 extern "C" {
 
 int bn254_batch_pop_verify_device(bn254_ctx* c, const uint8_t* d_pks, const uint8_t* d_pops, size_t n, uint32_t flags, uint8_t* d_status, void* stream) {
-  if (!c || (n && (!d_pks || !d_pops || !d_status)) || n > 0xFFFFFFFFu) return BN254_E_BAD_ARGUMENT;
+  if (!c || g1c_flag(flags) || (n && (!d_pks || !d_pops || !d_status)) || n > 0xFFFFFFFFu) return BN254_E_BAD_ARGUMENT;
   if (n == 0) return 0;
   if (misaligned(d_pks) || misaligned(d_pops)) return BN254_E_MISALIGNED;
   HIP_TRY(hipSetDevice(c->device));
@@ -109,7 +109,7 @@ int bn254_batch_pop_verify_device(bn254_ctx* c, const uint8_t* d_pks, const uint
   return bn254_batch_verify_device(c, (const uint8_t*)S.m.msgs, S.m.off, d_pops, d_pks, n, flags | BN254_FLAG_G2_SUBGROUP_CHECK, d_status, stream);
 }
 int bn254_batch_pop_verify(bn254_ctx* c, const uint8_t* pks, const uint8_t* pops, size_t n, uint32_t flags, uint8_t* status) {
-  if (!c || (n && (!pks || !pops || !status)) || n > 0xFFFFFFFFu) return BN254_E_BAD_ARGUMENT;
+  if (!c || g1c_flag(flags) || (n && (!pks || !pops || !status)) || n > 0xFFFFFFFFu) return BN254_E_BAD_ARGUMENT;
   if (n == 0) return 0;
   HIP_TRY(hipSetDevice(c->device));
   HostStaging st(c);
@@ -154,7 +154,7 @@ int bn254_batch_pop_prove(bn254_ctx* c, const uint8_t* sks, size_t n, uint8_t* p
 }
 
 int bn254_ctx_register_keys_pop(bn254_ctx* c, const uint8_t* pks, const uint8_t* pops, size_t n_keys, uint32_t flags, uint8_t* key_status) {
-  if (!c || (n_keys && (!pks || !pops)) || n_keys > 0xFFFFFFFFu) return BN254_E_BAD_ARGUMENT;
+  if (!c || g1c_flag(flags) || (n_keys && (!pks || !pops)) || n_keys > 0xFFFFFFFFu) return BN254_E_BAD_ARGUMENT;
   HIP_TRY(hipSetDevice(c->device));
   int rc = register_keys_begin(c, n_keys);
   if (rc) return rc;

@@ -473,6 +473,10 @@ int bn254_ctx_set_group_key(bn254_ctx* c, const uint8_t* group_pk, uint32_t flag
 }
 int bn254_batch_verify_keyed_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t* d_off, const uint8_t* d_sigs, const uint32_t* d_key_idx,
                                     size_t n, uint32_t flags, uint8_t* d_status, void* stream) {
+  if (g1c_flag(flags))                                  // compressed signatures: staged once, in front of any slicing
+    return g1c_call(c, d_sigs, n, n != 0, d_status, stream, [&](const uint8_t* d_sigs64) {
+      return bn254_batch_verify_keyed_device(c, d_msgs, d_off, d_sigs64, d_key_idx, n, flags & ~BN254_FLAG_G1_COMPRESSED, d_status, stream);
+    });
   MsgsLenScope msgs_len_scope(c);
   if (!c || (n && (!d_msgs || !d_off || !d_sigs || !d_key_idx || !d_status))) return BN254_E_BAD_ARGUMENT;
   if (n == 0) return 0;
@@ -511,7 +515,7 @@ int bn254_batch_verify_keyed(bn254_ctx* c, const uint8_t* msgs, const uint64_t* 
   if (!msgs_ok(msgs, off, n)) return BN254_E_BAD_ARGUMENT;
   HostStaging st(c);
   const uint8_t *d_msgs = st.in(0, msgs, (size_t)off[n]), *d_off = st.in(1, off, (n + 1) * sizeof(uint64_t));
-  const uint8_t *d_sigs = st.in(2, sigs, n * 64), *d_key_idx = st.in(3, key_idx, n * sizeof(uint32_t));
+  const uint8_t *d_sigs = st.in(2, sigs, n * g1_item_bytes(flags)), *d_key_idx = st.in(3, key_idx, n * sizeof(uint32_t));
   uint8_t* d_status = st.out(4, n, status);
   if (st.ok()) st.rc = bn254_batch_verify_keyed_device(c, d_msgs, (const uint64_t*)d_off, d_sigs, (const uint32_t*)d_key_idx, n, flags, d_status, nullptr);
   return st.finish();
@@ -520,6 +524,10 @@ int bn254_batch_verify_keyed(bn254_ctx* c, const uint8_t* msgs, const uint64_t* 
 int bn254_batch_verify_keyed_randomized_device(bn254_ctx* c, const uint8_t* d_msgs, const uint64_t* d_off, const uint8_t* d_sigs,
                                                const uint32_t* d_key_idx, size_t n, uint32_t flags, const uint8_t* seed32, uint8_t* d_status,
                                                void* stream) {
+  if (g1c_flag(flags))                                  // compressed signatures: staged once, whichever route the call takes
+    return g1c_call(c, d_sigs, n, n != 0, d_status, stream, [&](const uint8_t* d_sigs64) {
+      return bn254_batch_verify_keyed_randomized_device(c, d_msgs, d_off, d_sigs64, d_key_idx, n, flags & ~BN254_FLAG_G1_COMPRESSED, seed32, d_status, stream);
+    });
   MsgsLenScope msgs_len_scope(c);
   if (!c || !seed32 || (n && (!d_msgs || !d_off || !d_sigs || !d_key_idx || !d_status))) return BN254_E_BAD_ARGUMENT;
   if (n == 0) return 0;
@@ -554,7 +562,7 @@ int bn254_batch_verify_keyed_randomized(bn254_ctx* c, const uint8_t* msgs, const
   if (!msgs_ok(msgs, off, n)) return BN254_E_BAD_ARGUMENT;
   HostStaging st(c);
   const uint8_t *d_msgs = st.in(0, msgs, (size_t)off[n]), *d_off = st.in(1, off, (n + 1) * sizeof(uint64_t));
-  const uint8_t *d_sigs = st.in(2, sigs, n * 64), *d_key_idx = st.in(3, key_idx, n * sizeof(uint32_t));
+  const uint8_t *d_sigs = st.in(2, sigs, n * g1_item_bytes(flags)), *d_key_idx = st.in(3, key_idx, n * sizeof(uint32_t));
   uint8_t* d_status = st.out(4, n, status);
   if (st.ok())
     st.rc = bn254_batch_verify_keyed_randomized_device(c, d_msgs, (const uint64_t*)d_off, d_sigs, (const uint32_t*)d_key_idx, n, flags, seed32, d_status, nullptr);
@@ -565,7 +573,7 @@ int bn254_batch_verify_randomized_device(bn254_ctx* c, const uint8_t* d_msgs, co
                                          const uint8_t* d_pks, size_t n, uint32_t flags, const uint8_t* seed32, uint8_t* d_status,
                                          uint8_t* d_group_ok, void* stream) {
   MsgsLenScope msgs_len_scope(c);
-  if (!c || !seed32 || (n && (!d_msgs || !d_off || !d_sigs || !d_pks || !d_status))) return BN254_E_BAD_ARGUMENT;
+  if (!c || !seed32 || g1c_flag(flags) || (n && (!d_msgs || !d_off || !d_sigs || !d_pks || !d_status))) return BN254_E_BAD_ARGUMENT;
   if (n == 0) return 0;
   if (n > 0xFFFFFFFFu) return BN254_E_BAD_ARGUMENT;
   if (misaligned(d_sigs) || misaligned(d_pks) || ((uintptr_t)d_off & 7u)) return BN254_E_MISALIGNED;
@@ -633,7 +641,7 @@ int bn254_batch_verify_randomized_device(bn254_ctx* c, const uint8_t* d_msgs, co
 int bn254_batch_verify_randomized(bn254_ctx* c, const uint8_t* msgs, const uint64_t* off, const uint8_t* sigs, const uint8_t* pks, size_t n,
                                   uint32_t flags, const uint8_t* seed32, uint8_t* status, uint8_t* group_ok) {
   MsgsLenScope msgs_len_scope(c);
-  if (!c || !seed32 || (n && (!off || !sigs || !pks || !status))) return BN254_E_BAD_ARGUMENT;
+  if (!c || !seed32 || g1c_flag(flags) || (n && (!off || !sigs || !pks || !status))) return BN254_E_BAD_ARGUMENT;
   if (n == 0) return 0;
   HIP_TRY(hipSetDevice(c->device));
   if (!msgs_ok(msgs, off, n)) return BN254_E_BAD_ARGUMENT;

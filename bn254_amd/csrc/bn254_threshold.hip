@@ -174,6 +174,8 @@ KERNEL_SMALL void k_th_coeff(ClShares in, size_t n_shares, size_t n, size_t bm_w
 // the call's outputs under the collect's names: agg_sigs = the group signatures, signer_bits = the rows of the keys used, n_signers = the counts
 // of keys with a valid share
 static int th_combine_device(bn254_ctx* c, const ClCall& a, uint32_t threshold, void* stream) {
+  if (g1c_flag(a.flags))                                // compressed shares: staged once, in front of the collect and of the interpolation
+    return cl_g1c_call(c, a, stream, [&](const ClCall& d) { return th_combine_device(c, d, threshold, stream); });
   MsgsLenScope msgs_len_scope(c);
   int rc = BN254_E_BAD_ARGUMENT;
   if (threshold == 0 || !cl_keys_ok(c, a) || !cl_checks_device(c, a, &rc)) return rc;
@@ -254,6 +256,8 @@ static int th_interpolate(bn254_ctx* c, hipStream_t s, const ClCall& a, const Cl
   return launch_msm(c, s, a.items, T.scalars, T.mask, n_shares, a.off, gate, n, 0, T, a.agg_sigs, nullptr);
 }
 static int th_combine_opt_device(bn254_ctx* c, const ClCall& a, uint32_t threshold, void* stream) {
+  if (g1c_flag(a.flags))                                // compressed shares: staged once, whichever route the call takes
+    return cl_g1c_call(c, a, stream, [&](const ClCall& d) { return th_combine_opt_device(c, d, threshold, stream); });
   // no group key: nothing to check the result against — whatever route the call would take
   if (threshold == 0 || !c || !c->gk_set) return BN254_E_BAD_ARGUMENT;
   // WHOLE-CALL ROUTING: the exact call (same bytes) for a call too small to pay, for an empty key set and without the lane-pair kernels

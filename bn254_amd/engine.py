@@ -10,6 +10,8 @@ from . import _native
 G1_BYTES, G2_BYTES, GT_BYTES, SCALAR_BYTES = 64, 128, 384, 32
 FLAG_G2_SUBGROUP_CHECK = 1
 FLAG_REJECT_IDENTITY = 2
+FLAG_G1_COMPRESSED = 4          # the call's G1 input array holds 33-byte compressed points (the registered-key calls; include/bn254_hip.h)
+G1_COMPRESSED_BYTES = 33
 FLAG_RAND64 = 0x100
 FLAG_RAND_GLV = 0x200
 POP_TAG = b"BN254G2_POP_V01:"   # BN254_POP_TAG (include/bn254_hip.h): the proof of possession of a key is its holder's signature on POP_TAG + pk
@@ -82,6 +84,11 @@ class NativeError(RuntimeError):
 def _check(fn, rc):
     if rc != 0:
         raise NativeError(fn, rc)
+
+
+def g1_item_bytes(flags):
+    """bytes per point of a call's G1 input array: 33 under FLAG_G1_COMPRESSED, else 64"""
+    return G1_COMPRESSED_BYTES if flags & FLAG_G1_COMPRESSED else G1_BYTES
 
 
 def pack_messages(messages):
@@ -635,6 +642,10 @@ class Engine:
         _check("bn254_batch_g1_decompress", self._lib.bn254_batch_g1_decompress(self._h, bytes(data), n, out, status))
         return out.raw[:n * G1_BYTES], status.raw[:n]
 
+    def batch_g1_decompress_device(self, d_in33, n, d_out64, d_status, stream=None):
+        """the device-pointer form: enqueues only; d_in33 needs no alignment (include/bn254_hip.h: bn254_batch_g1_decompress_device)"""
+        _check("bn254_batch_g1_decompress_device", self._lib.bn254_batch_g1_decompress_device(self._h, d_in33, n, d_out64, d_status, stream))
+
     def batch_g2_decompress(self, data, n):
         out = ctypes.create_string_buffer(max(n, 1) * G2_BYTES)
         status = ctypes.create_string_buffer(max(n, 1))
@@ -778,7 +789,7 @@ class Engine:
 
     def batch_verify_keyed(self, messages, sigs, key_idx, flags=0):
         n = len(messages)
-        assert len(sigs) == n * G1_BYTES and len(key_idx) == n
+        assert len(sigs) == n * g1_item_bytes(flags) and len(key_idx) == n
         msgs, off = pack_messages(messages)
         idx = (ctypes.c_uint32 * max(n, 1))(*key_idx)
         status = ctypes.create_string_buffer(max(n, 1))
@@ -789,7 +800,7 @@ class Engine:
         """same-message aggregates as signer bitmaps over the registered keys: bitmaps = n * bm_words uint32 words (signer j of tuple i = bit
         j % 32 of bitmaps[i * bm_words + j // 32]); returns the status bytes (include/bn254_hip.h: bn254_batch_verify_keyed_bitmap)"""
         n = len(messages)
-        assert len(sigs) == n * G1_BYTES and len(bitmaps) == n * bm_words
+        assert len(sigs) == n * g1_item_bytes(flags) and len(bitmaps) == n * bm_words
         msgs, off = pack_messages(messages)
         bits = (ctypes.c_uint32 * max(len(bitmaps), 1))(*bitmaps)
         status = ctypes.create_string_buffer(max(n, 1))
@@ -802,11 +813,11 @@ class Engine:
                self._lib.bn254_batch_verify_keyed_bitmap_device(self._h, d_msgs, d_off, d_sigs, d_signer_bits, bm_words, n, flags, d_status, stream))
 
     @staticmethod
-    def _collect_buffers(messages, shares, share_keys, sizes, bm_words):
+    def _collect_buffers(messages, shares, share_keys, sizes, bm_words, flags=0):
         """what the collect and the threshold call marshal alike: the C arguments behind the context (msgs .. bm_words) and the five output
         buffers (share statuses, tuple statuses, one G1 point per tuple, the bitmap rows, one count per tuple)"""
         n, n_shares = len(messages), len(share_keys)
-        assert len(sizes) == n and all(k >= 0 for k in sizes) and sum(sizes) == n_shares and len(shares) == n_shares * G1_BYTES
+        assert len(sizes) == n and all(k >= 0 for k in sizes) and sum(sizes) == n_shares and len(shares) == n_shares * g1_item_bytes(flags)
         msgs, off = pack_messages(messages)
         ends = [0]
         for k in sizes:
@@ -819,11 +830,11 @@ class Engine:
 
     def batch_collect_keyed_bitmap(self, messages, shares, share_keys, sizes, bm_words, flags=0, want_counts=False, seed32=None, optimistic=False):
         """build signer-bitmap aggregates from individual signatures (include/bn254_hip.h: bn254_batch_collect_keyed_bitmap): tuple i is
-        messages[i] with the next sizes[i] shares (64 B each, share s said to be by registered key share_keys[s]).  Returns (share status
+        messages[i] with the next sizes[i] shares (64 B each, 33 B under FLAG_G1_COMPRESSED; share s said to be by registered key share_keys[s]).  Returns (share status
         bytes, tuple status bytes, the n aggregates, the n * bm_words bitmap words) — and the signer counts with want_counts.
         seed32: see batch_collect_keyed_bitmap_randomized; optimistic: see batch_collect_keyed_bitmap_optimistic."""
         n, n_shares = len(messages), len(share_keys)
-        args, (share_st, tuple_st, agg, bits, counts) = Engine._collect_buffers(messages, shares, share_keys, sizes, bm_words)
+        args, (share_st, tuple_st, agg, bits, counts) = Engine._collect_buffers(messages, shares, share_keys, sizes, bm_words, flags)
         head = (self._h,) + args + (flags,)
         tail = (share_st, tuple_st, agg, bits, counts if want_counts else None)
         if optimistic:
@@ -840,7 +851,7 @@ class Engine:
         batch_collect_keyed_bitmap and the threshold.  Returns (share status bytes, tuple status bytes, the n group signatures, the
         n * bm_words words of the rows — the keys used, or of a failed tuple the keys that were there —, the counts of keys with a valid share)."""
         n, n_shares = len(messages), len(share_keys)
-        args, (share_st, tuple_st, sigs, bits, counts) = Engine._collect_buffers(messages, shares, share_keys, sizes, bm_words)
+        args, (share_st, tuple_st, sigs, bits, counts) = Engine._collect_buffers(messages, shares, share_keys, sizes, bm_words, flags)
         assert 0 < int(threshold) < 1 << 32, "threshold must be at least 1"
         _check("bn254_batch_threshold_combine_keyed",
                self._lib.bn254_batch_threshold_combine_keyed(self._h, *args, int(threshold), flags, share_st, tuple_st, sigs, bits, counts))
@@ -851,7 +862,7 @@ class Engine:
         include/bn254_hip.h: bn254_batch_threshold_combine_keyed_optimistic).  Same arguments, same five results; in a tuple that passes its
         check the shares outside the kept keys read their pre-check status and the count is of candidates."""
         n, n_shares = len(messages), len(share_keys)
-        args, (share_st, tuple_st, sigs, bits, counts) = Engine._collect_buffers(messages, shares, share_keys, sizes, bm_words)
+        args, (share_st, tuple_st, sigs, bits, counts) = Engine._collect_buffers(messages, shares, share_keys, sizes, bm_words, flags)
         assert 0 < int(threshold) < 1 << 32, "threshold must be at least 1"
         _check("bn254_batch_threshold_combine_keyed_optimistic",
                self._lib.bn254_batch_threshold_combine_keyed_optimistic(self._h, *args, int(threshold), flags, share_st, tuple_st, sigs, bits, counts))
@@ -879,13 +890,13 @@ class Engine:
 
     def merge_keyed_bitmap(self, messages, parts, part_bitmaps, sizes, bm_words, flags=0, want_counts=False, optimistic=False):
         """merge partial signer-bitmap aggregates into one aggregate per message (include/bn254_hip.h: bn254_batch_merge_keyed_bitmap):
-        tuple i is messages[i] with the next sizes[i] partials (64 B each; partial p has the bm_words bitmap words part_bitmaps[p * bm_words
+        tuple i is messages[i] with the next sizes[i] partials (64 B each, 33 B under FLAG_G1_COMPRESSED; partial p has the bm_words bitmap words part_bitmaps[p * bm_words
         ..]).  Returns (partial status bytes, taken bytes, tuple status bytes, the n aggregates, the n * bm_words bitmap words) — and the
         signer counts with want_counts.  optimistic: see merge_keyed_bitmap_optimistic."""
         n = len(messages)
         assert len(sizes) == n and all(k >= 0 for k in sizes)
         n_parts = sum(int(k) for k in sizes)
-        assert len(parts) == n_parts * G1_BYTES and len(part_bitmaps) == n_parts * bm_words
+        assert len(parts) == n_parts * g1_item_bytes(flags) and len(part_bitmaps) == n_parts * bm_words
         name = "bn254_batch_merge_keyed_bitmap_optimistic" if optimistic else "bn254_batch_merge_keyed_bitmap"
         msgs, off = pack_messages(messages)
         ends = [0]
@@ -958,7 +969,7 @@ class Engine:
         """batch_verify_keyed_bitmap with the pairing checks of whole groups of tuples combined under random weights from seed32
         (include/bn254_hip.h: bn254_batch_verify_keyed_bitmap_randomized).  Returns the status bytes."""
         n = len(messages)
-        assert len(sigs) == n * G1_BYTES and len(bitmaps) == n * bm_words and len(seed32) == 32
+        assert len(sigs) == n * g1_item_bytes(flags) and len(bitmaps) == n * bm_words and len(seed32) == 32
         msgs, off = pack_messages(messages)
         bits = (ctypes.c_uint32 * max(len(bitmaps), 1))(*bitmaps)
         status = ctypes.create_string_buffer(max(n, 1))
@@ -974,7 +985,7 @@ class Engine:
 
     def batch_verify_keyed_randomized(self, messages, sigs, key_idx, seed32, flags=0):
         n = len(messages)
-        assert len(sigs) == n * G1_BYTES and len(key_idx) == n and len(seed32) == 32
+        assert len(sigs) == n * g1_item_bytes(flags) and len(key_idx) == n and len(seed32) == 32
         msgs, off = pack_messages(messages)
         idx = (ctypes.c_uint32 * max(n, 1))(*key_idx)
         status = ctypes.create_string_buffer(max(n, 1))

@@ -128,6 +128,20 @@ struct Signature : PointBytes<64> {
     return r;
   }
 };
+// A signature as it arrives off the wire — 0x02 / 0x03 || x, 33 bytes — and NOT yet decoded: the registered-key calls of ECDSA take it as it is
+// and decompress on the device, inside the call (include/bn254_hip.h: BN254_FLAG_G1_COMPRESSED).  An encoding that does not decompress gets the
+// ErrorKind Signature::from_compressed would throw as its status and is never verified, taken or counted.
+struct CompressedSignature {
+  std::array<uint8_t, 33> raw{};
+  static CompressedSignature from_bytes(const uint8_t* data, size_t len) {
+    if (len != 33) throw Error(ErrorKind::InvalidEncoding);        // as Signature::from_compressed
+    CompressedSignature s; std::memcpy(s.raw.data(), data, 33);
+    return s;
+  }
+};
+// the flag a call passes for an input array of such points
+template <class Sig> constexpr uint32_t g1_input_flag() { return std::tuple_size<decltype(Sig::raw)>::value == 33 ? BN254_FLAG_G1_COMPRESSED : 0u; }
+
 struct PublicKeyG1 : PointBytes<64> {
   static PublicKeyG1 from_private_key(const PrivateKey& k, Engine& e = Engine::default_engine()) {   // types.rs:155-157
     PublicKeyG1 r; uint8_t st = 0;       // points = nullptr: G1::one(), the fixed-base table of the generator
@@ -283,33 +297,46 @@ struct ECDSA {
   // result[i] == 0 iff verify(messages[i], signatures[i], registered[key_indices[i]]) succeeds; 2 (IndexOutOfBounds) outside the set
   static std::vector<uint8_t> batch_verify_keyed(const std::vector<std::vector<uint8_t>>& messages, const std::vector<Signature>& signatures,
                                                  const std::vector<uint32_t>& key_indices, Engine& e = Engine::default_engine()) {
+    return verify_keyed_impl<Signature>(messages, signatures, key_indices, e);
+  }
+  // ... from the 33-byte wire encodings: a signature that does not decompress reads the ErrorKind Signature::from_compressed would throw (first rule)
+  static std::vector<uint8_t> batch_verify_keyed(const std::vector<std::vector<uint8_t>>& messages, const std::vector<CompressedSignature>& signatures,
+                                                 const std::vector<uint32_t>& key_indices, Engine& e = Engine::default_engine()) {
+    return verify_keyed_impl<CompressedSignature>(messages, signatures, key_indices, e);
+  }
+  template <class Sig> static std::vector<uint8_t> verify_keyed_impl(const std::vector<std::vector<uint8_t>>& messages, const std::vector<Sig>& signatures,
+                                                                      const std::vector<uint32_t>& key_indices, Engine& e) {
     size_t n = messages.size();
     if (signatures.size() != n || key_indices.size() != n) throw Error(ErrorKind::InvalidLength);
+    const size_t sz = sizeof signatures[0].raw;
     std::vector<uint64_t> off(n + 1, 0);
-    std::vector<uint8_t> msgs, sigs(n * 64), status(n, 0);
+    std::vector<uint8_t> msgs, sigs(n * sz), status(n, 0);
     for (size_t i = 0; i < n; ++i) {
       off[i] = msgs.size();
       msgs.insert(msgs.end(), messages[i].begin(), messages[i].end());
-      std::memcpy(&sigs[64 * i], signatures[i].raw.data(), 64);
+      std::memcpy(&sigs[sz * i], signatures[i].raw.data(), sz);
     }
     off[n] = msgs.size();
-    check_rc("bn254_batch_verify_keyed", bn254_batch_verify_keyed(e.raw(), msgs.data(), off.data(), sigs.data(), key_indices.data(), n, 0, status.data()));
+    check_rc("bn254_batch_verify_keyed",
+             bn254_batch_verify_keyed(e.raw(), msgs.data(), off.data(), sigs.data(), key_indices.data(), n, g1_input_flag<Sig>(), status.data()));
     return status;
   }
   // One message, one already aggregated signature and the indices (in the registered set of n_keys keys) of the keys that signed
   // (include/bn254_hip.h: bn254_batch_verify_keyed_bitmap): result[i] == 0 iff e(H(m_i), sum of the named keys) * e(sigma_i, -G2) == 1;
   // 2 (IndexOutOfBounds) for an index outside the set — every such index lands on the one bit the bitmaps carry past the set.
-  struct SignerItem { std::vector<uint8_t> message; Signature signature; std::vector<uint32_t> signer_indices; };
+  template <class Sig> struct SignerItemT { std::vector<uint8_t> message; Sig signature; std::vector<uint32_t> signer_indices; };
+  using SignerItem = SignerItemT<Signature>;
+  using CompressedSignerItem = SignerItemT<CompressedSignature>;      // the aggregate as its 33-byte wire encoding
   // the items packed as the bitmap calls take them
   struct PackedSigners { size_t bm_words; std::vector<uint64_t> off; std::vector<uint8_t> msgs, sigs; std::vector<uint32_t> bits; };
-  static PackedSigners pack_signers(const std::vector<SignerItem>& items, size_t n_keys) {
-    const size_t n = items.size();
-    PackedSigners p{n_keys / 32 + 1, std::vector<uint64_t>(n + 1, 0), {}, std::vector<uint8_t>(n * 64), {}};
+  template <class Sig> static PackedSigners pack_signers(const std::vector<SignerItemT<Sig>>& items, size_t n_keys) {
+    const size_t n = items.size(), sz = std::tuple_size<decltype(Sig::raw)>::value;
+    PackedSigners p{n_keys / 32 + 1, std::vector<uint64_t>(n + 1, 0), {}, std::vector<uint8_t>(n * sz), {}};
     p.bits.assign(n * p.bm_words, 0);
     for (size_t i = 0; i < n; ++i) {
       p.off[i] = p.msgs.size();
       p.msgs.insert(p.msgs.end(), items[i].message.begin(), items[i].message.end());
-      std::memcpy(&p.sigs[64 * i], items[i].signature.raw.data(), 64);
+      std::memcpy(&p.sigs[sz * i], items[i].signature.raw.data(), sz);
       for (uint32_t j : items[i].signer_indices) {
         const size_t b = j < n_keys ? j : n_keys;
         p.bits[i * p.bm_words + b / 32] |= 1u << (b % 32);
@@ -319,41 +346,68 @@ struct ECDSA {
     return p;
   }
   static std::vector<uint8_t> batch_verify_keyed_signers(const std::vector<SignerItem>& items, size_t n_keys, Engine& e = Engine::default_engine()) {
-    const PackedSigners p = pack_signers(items, n_keys);
+    return verify_keyed_signers_impl<Signature>(items, n_keys, nullptr, 0, e);
+  }
+  static std::vector<uint8_t> batch_verify_keyed_signers(const std::vector<CompressedSignerItem>& items, size_t n_keys, Engine& e = Engine::default_engine()) {
+    return verify_keyed_signers_impl<CompressedSignature>(items, n_keys, nullptr, 0, e);
+  }
+  template <class Sig> static std::vector<uint8_t> verify_keyed_signers_impl(const std::vector<SignerItemT<Sig>>& items, size_t n_keys, const uint8_t* seed32,
+                                                                              uint32_t flags, Engine& e) {
+    const PackedSigners p = pack_signers<Sig>(items, n_keys);
     std::vector<uint8_t> status(items.size(), 0);
-    check_rc("bn254_batch_verify_keyed_bitmap", bn254_batch_verify_keyed_bitmap(e.raw(), p.msgs.data(), p.off.data(), p.sigs.data(), p.bits.data(), p.bm_words,
-                                                                                items.size(), 0, status.data()));
+    flags |= g1_input_flag<Sig>();
+    if (seed32)
+      check_rc("bn254_batch_verify_keyed_bitmap_randomized",
+               bn254_batch_verify_keyed_bitmap_randomized(e.raw(), p.msgs.data(), p.off.data(), p.sigs.data(), p.bits.data(), p.bm_words, items.size(), flags,
+                                                          seed32, status.data()));
+    else
+      check_rc("bn254_batch_verify_keyed_bitmap", bn254_batch_verify_keyed_bitmap(e.raw(), p.msgs.data(), p.off.data(), p.sigs.data(), p.bits.data(), p.bm_words,
+                                                                                  items.size(), flags, status.data()));
     return status;
   }
   // the same through the combined checks of whole groups of items (include/bn254_hip.h: bn254_batch_verify_keyed_bitmap_randomized): a non-zero
   // status is exact, a zero is wrong with probability <= 2^-128 per group (2^-64 with rand64) for a fresh secret seed
   static std::vector<uint8_t> batch_verify_keyed_signers_randomized(const std::vector<SignerItem>& items, size_t n_keys, const std::array<uint8_t, 32>& seed,
                                                                     bool rand64 = false, Engine& e = Engine::default_engine()) {
-    const PackedSigners p = pack_signers(items, n_keys);
-    std::vector<uint8_t> status(items.size(), 0);
-    check_rc("bn254_batch_verify_keyed_bitmap_randomized",
-             bn254_batch_verify_keyed_bitmap_randomized(e.raw(), p.msgs.data(), p.off.data(), p.sigs.data(), p.bits.data(), p.bm_words, items.size(),
-                                                        rand64 ? BN254_FLAG_RAND64 : 0, seed.data(), status.data()));
-    return status;
+    return verify_keyed_signers_impl<Signature>(items, n_keys, seed.data(), rand64 ? BN254_FLAG_RAND64 : 0, e);
+  }
+  static std::vector<uint8_t> batch_verify_keyed_signers_randomized(const std::vector<CompressedSignerItem>& items, size_t n_keys,
+                                                                    const std::array<uint8_t, 32>& seed, bool rand64 = false,
+                                                                    Engine& e = Engine::default_engine()) {
+    return verify_keyed_signers_impl<CompressedSignature>(items, n_keys, seed.data(), rand64 ? BN254_FLAG_RAND64 : 0, e);
   }
   static void verify_keyed_signers(const std::vector<uint8_t>& message, const Signature& signature, const std::vector<uint32_t>& signer_indices,
                                    size_t n_keys, Engine& e = Engine::default_engine()) {
     check_status(batch_verify_keyed_signers({SignerItem{message, signature, signer_indices}}, n_keys, e)[0]);
   }
+  static void verify_keyed_signers(const std::vector<uint8_t>& message, const CompressedSignature& signature, const std::vector<uint32_t>& signer_indices,
+                                   size_t n_keys, Engine& e = Engine::default_engine()) {
+    check_status(batch_verify_keyed_signers({CompressedSignerItem{message, signature, signer_indices}}, n_keys, e)[0]);
+  }
   // The producer of such an item (include/bn254_hip.h: bn254_batch_collect_keyed_bitmap): one message and individual signatures, signatures[k]
   // said to be by registered key key_indices[k].  Every signature is verified against its key; those that pass are added, one per key.
   // status: 0, or the message's hash ErrorKind (then nothing was added); statuses[k]: what batch_verify_keyed gives signature k.
-  struct ShareItem { std::vector<uint8_t> message; std::vector<Signature> signatures; std::vector<uint32_t> key_indices; };
+  template <class Sig> struct ShareItemT { std::vector<uint8_t> message; std::vector<Sig> signatures; std::vector<uint32_t> key_indices; };
+  using ShareItem = ShareItemT<Signature>;
+  using CompressedShareItem = ShareItemT<CompressedSignature>;        // the shares as their 33-byte wire encodings; the results are the same
   struct KeyedAggregateResult { uint8_t status; Signature signature; std::vector<uint32_t> signer_indices; std::vector<uint8_t> statuses; };
   static std::vector<KeyedAggregateResult> batch_aggregate_keyed_signers(const std::vector<ShareItem>& items, size_t n_keys, Engine& e = Engine::default_engine()) {
-    return aggregate_keyed_signers_impl(items, n_keys, nullptr, 0, e);
+    return aggregate_keyed_signers_impl<Signature>(items, n_keys, nullptr, 0, e);
+  }
+  static std::vector<KeyedAggregateResult> batch_aggregate_keyed_signers(const std::vector<CompressedShareItem>& items, size_t n_keys,
+                                                                         Engine& e = Engine::default_engine()) {
+    return aggregate_keyed_signers_impl<CompressedSignature>(items, n_keys, nullptr, 0, e);
   }
   // the same with ONE verify per item — the sum of its signatures that pass every check short of the pairing, against the sum of their keys —
   // and the signatures verified one by one only where that fails (include/bn254_hip.h: bn254_batch_collect_keyed_bitmap_optimistic).  No
   // seed.  Signatures whose errors cancel within a passing item read 0 and are counted: a 0 there means "counted in a sum that verifies".
   static std::vector<KeyedAggregateResult> batch_aggregate_keyed_signers_optimistic(const std::vector<ShareItem>& items, size_t n_keys,
                                                                                     Engine& e = Engine::default_engine()) {
-    return aggregate_keyed_signers_impl(items, n_keys, nullptr, 0, e, true);
+    return aggregate_keyed_signers_impl<Signature>(items, n_keys, nullptr, 0, e, true);
+  }
+  static std::vector<KeyedAggregateResult> batch_aggregate_keyed_signers_optimistic(const std::vector<CompressedShareItem>& items, size_t n_keys,
+                                                                                    Engine& e = Engine::default_engine()) {
+    return aggregate_keyed_signers_impl<CompressedSignature>(items, n_keys, nullptr, 0, e, true);
   }
   // the same through the combined checks of 64 signatures of one key at a time, across the items of the call (include/bn254_hip.h:
   // bn254_batch_collect_keyed_bitmap_randomized): the same results; a non-zero status is exact, a zero is wrong with probability <= 2^-128 per
@@ -361,10 +415,17 @@ struct ECDSA {
   static std::vector<KeyedAggregateResult> batch_aggregate_keyed_signers_randomized(const std::vector<ShareItem>& items, size_t n_keys,
                                                                                     const std::array<uint8_t, 32>& seed, bool rand64 = false,
                                                                                     Engine& e = Engine::default_engine()) {
-    return aggregate_keyed_signers_impl(items, n_keys, seed.data(), rand64 ? BN254_FLAG_RAND64 : 0, e);
+    return aggregate_keyed_signers_impl<Signature>(items, n_keys, seed.data(), rand64 ? BN254_FLAG_RAND64 : 0, e);
   }
-  static std::vector<KeyedAggregateResult> aggregate_keyed_signers_impl(const std::vector<ShareItem>& items, size_t n_keys, const uint8_t* seed32, uint32_t flags,
-                                                                        Engine& e, bool optimistic = false) {
+  static std::vector<KeyedAggregateResult> batch_aggregate_keyed_signers_randomized(const std::vector<CompressedShareItem>& items, size_t n_keys,
+                                                                                    const std::array<uint8_t, 32>& seed, bool rand64 = false,
+                                                                                    Engine& e = Engine::default_engine()) {
+    return aggregate_keyed_signers_impl<CompressedSignature>(items, n_keys, seed.data(), rand64 ? BN254_FLAG_RAND64 : 0, e);
+  }
+  template <class Sig> static std::vector<KeyedAggregateResult> aggregate_keyed_signers_impl(const std::vector<ShareItemT<Sig>>& items, size_t n_keys,
+                                                                                             const uint8_t* seed32, uint32_t flags, Engine& e,
+                                                                                             bool optimistic = false) {
+    flags |= g1_input_flag<Sig>();
     const size_t n = items.size(), bm_words = (n_keys + 31) / 32 ? (n_keys + 31) / 32 : 1;
     std::vector<uint64_t> off(n + 1, 0), share_off(n + 1, 0);
     std::vector<uint8_t> msgs, shares;
@@ -374,7 +435,7 @@ struct ECDSA {
       off[i] = msgs.size();
       share_off[i] = keys.size();
       msgs.insert(msgs.end(), items[i].message.begin(), items[i].message.end());
-      for (const Signature& s : items[i].signatures) shares.insert(shares.end(), s.raw.begin(), s.raw.end());
+      for (const Sig& s : items[i].signatures) shares.insert(shares.end(), s.raw.begin(), s.raw.end());
       keys.insert(keys.end(), items[i].key_indices.begin(), items[i].key_indices.end());
     }
     off[n] = msgs.size();
@@ -386,14 +447,14 @@ struct ECDSA {
     if (optimistic)
       check_rc("bn254_batch_collect_keyed_bitmap_optimistic",
                bn254_batch_collect_keyed_bitmap_optimistic(e.raw(), msgs.data(), off.data(), shares.data(), keys.data(), share_off.data(), share_off[n], n,
-                                                           bm_words, 0, share_st.data(), tuple_st.data(), agg.data(), bits.data(), nullptr));
+                                                           bm_words, flags, share_st.data(), tuple_st.data(), agg.data(), bits.data(), nullptr));
     else if (seed32)
       check_rc("bn254_batch_collect_keyed_bitmap_randomized",
                bn254_batch_collect_keyed_bitmap_randomized(e.raw(), msgs.data(), off.data(), shares.data(), keys.data(), share_off.data(), share_off[n], n,
                                                            bm_words, flags, seed32, share_st.data(), tuple_st.data(), agg.data(), bits.data(), nullptr));
     else
       check_rc("bn254_batch_collect_keyed_bitmap",
-               bn254_batch_collect_keyed_bitmap(e.raw(), msgs.data(), off.data(), shares.data(), keys.data(), share_off.data(), share_off[n], n, bm_words, 0,
+               bn254_batch_collect_keyed_bitmap(e.raw(), msgs.data(), off.data(), shares.data(), keys.data(), share_off.data(), share_off[n], n, bm_words, flags,
                                                 share_st.data(), tuple_st.data(), agg.data(), bits.data(), nullptr));
     std::vector<KeyedAggregateResult> out(n);
     for (size_t i = 0; i < n; ++i) {
@@ -408,6 +469,12 @@ struct ECDSA {
   static KeyedAggregateResult aggregate_keyed_signers(const std::vector<uint8_t>& message, const std::vector<Signature>& signatures,
                                                       const std::vector<uint32_t>& key_indices, size_t n_keys, Engine& e = Engine::default_engine()) {
     KeyedAggregateResult r = batch_aggregate_keyed_signers({ShareItem{message, signatures, key_indices}}, n_keys, e)[0];
+    check_status(r.status);
+    return r;
+  }
+  static KeyedAggregateResult aggregate_keyed_signers(const std::vector<uint8_t>& message, const std::vector<CompressedSignature>& signatures,
+                                                      const std::vector<uint32_t>& key_indices, size_t n_keys, Engine& e = Engine::default_engine()) {
+    KeyedAggregateResult r = batch_aggregate_keyed_signers({CompressedShareItem{message, signatures, key_indices}}, n_keys, e)[0];
     check_status(r.status);
     return r;
   }
@@ -433,7 +500,11 @@ struct ECDSA {
   // lie on one polynomial of degree threshold - 1 is check_dealing's to check, once per key set.
   static std::vector<KeyedAggregateResult> batch_threshold_combine_keyed(const std::vector<ShareItem>& items, size_t n_keys, uint32_t threshold,
                                                                          Engine& e = Engine::default_engine()) {
-    return threshold_batch(items, n_keys, threshold, false, e);
+    return threshold_batch<Signature>(items, n_keys, threshold, false, e);
+  }
+  static std::vector<KeyedAggregateResult> batch_threshold_combine_keyed(const std::vector<CompressedShareItem>& items, size_t n_keys, uint32_t threshold,
+                                                                         Engine& e = Engine::default_engine()) {
+    return threshold_batch<CompressedSignature>(items, n_keys, threshold, false, e);
   }
   // THE GROUP KEY f(0) * G2 of the registered dealing, for the optimistic calls below (include/bn254_hip.h: bn254_ctx_set_group_key); throws
   // the key's decode Error, and then no group key is set.  forget_group_key drops it, as register_keys / register_keys_proven do: a new key
@@ -453,17 +524,23 @@ struct ECDSA {
   // key the call is refused (bad argument).
   static std::vector<KeyedAggregateResult> batch_threshold_combine_keyed_optimistic(const std::vector<ShareItem>& items, size_t n_keys, uint32_t threshold,
                                                                                     Engine& e = Engine::default_engine()) {
-    return threshold_batch(items, n_keys, threshold, true, e);
+    return threshold_batch<Signature>(items, n_keys, threshold, true, e);
+  }
+  static std::vector<KeyedAggregateResult> batch_threshold_combine_keyed_optimistic(const std::vector<CompressedShareItem>& items, size_t n_keys,
+                                                                                    uint32_t threshold, Engine& e = Engine::default_engine()) {
+    return threshold_batch<CompressedSignature>(items, n_keys, threshold, true, e);
   }
   static KeyedAggregateResult threshold_combine_keyed_optimistic(const std::vector<uint8_t>& message, const std::vector<Signature>& signatures,
                                                                  const std::vector<uint32_t>& key_indices, size_t n_keys, uint32_t threshold,
                                                                  Engine& e = Engine::default_engine()) {
-    KeyedAggregateResult r = threshold_batch({ShareItem{message, signatures, key_indices}}, n_keys, threshold, true, e)[0];
+    KeyedAggregateResult r = threshold_batch<Signature>({ShareItem{message, signatures, key_indices}}, n_keys, threshold, true, e)[0];
     check_status(r.status);
     return r;
   }
-  static std::vector<KeyedAggregateResult> threshold_batch(const std::vector<ShareItem>& items, size_t n_keys, uint32_t threshold, bool optimistic, Engine& e) {
+  template <class Sig> static std::vector<KeyedAggregateResult> threshold_batch(const std::vector<ShareItemT<Sig>>& items, size_t n_keys, uint32_t threshold,
+                                                                                bool optimistic, Engine& e) {
     if (threshold == 0) throw Error(ErrorKind::InvalidLength);
+    const uint32_t flags = g1_input_flag<Sig>();
     const size_t n = items.size(), bm_words = (n_keys + 31) / 32 ? (n_keys + 31) / 32 : 1;
     std::vector<uint64_t> off(n + 1, 0), share_off(n + 1, 0);
     std::vector<uint8_t> msgs, shares;
@@ -473,7 +550,7 @@ struct ECDSA {
       off[i] = msgs.size();
       share_off[i] = keys.size();
       msgs.insert(msgs.end(), items[i].message.begin(), items[i].message.end());
-      for (const Signature& s : items[i].signatures) shares.insert(shares.end(), s.raw.begin(), s.raw.end());
+      for (const Sig& s : items[i].signatures) shares.insert(shares.end(), s.raw.begin(), s.raw.end());
       keys.insert(keys.end(), items[i].key_indices.begin(), items[i].key_indices.end());
     }
     off[n] = msgs.size();
@@ -485,11 +562,11 @@ struct ECDSA {
     if (optimistic)
       check_rc("bn254_batch_threshold_combine_keyed_optimistic",
                bn254_batch_threshold_combine_keyed_optimistic(e.raw(), msgs.data(), off.data(), shares.data(), keys.data(), share_off.data(), share_off[n], n,
-                                                              bm_words, threshold, 0, share_st.data(), tuple_st.data(), group.data(), bits.data(), nullptr));
+                                                              bm_words, threshold, flags, share_st.data(), tuple_st.data(), group.data(), bits.data(), nullptr));
     else
       check_rc("bn254_batch_threshold_combine_keyed",
                bn254_batch_threshold_combine_keyed(e.raw(), msgs.data(), off.data(), shares.data(), keys.data(), share_off.data(), share_off[n], n, bm_words,
-                                                   threshold, 0, share_st.data(), tuple_st.data(), group.data(), bits.data(), nullptr));
+                                                   threshold, flags, share_st.data(), tuple_st.data(), group.data(), bits.data(), nullptr));
     std::vector<KeyedAggregateResult> out(n);
     for (size_t i = 0; i < n; ++i) {
       out[i].status = tuple_st[i];
@@ -504,6 +581,20 @@ struct ECDSA {
                                                       const std::vector<uint32_t>& key_indices, size_t n_keys, uint32_t threshold,
                                                       Engine& e = Engine::default_engine()) {
     KeyedAggregateResult r = batch_threshold_combine_keyed({ShareItem{message, signatures, key_indices}}, n_keys, threshold, e)[0];
+    check_status(r.status);
+    return r;
+  }
+  static KeyedAggregateResult threshold_combine_keyed(const std::vector<uint8_t>& message, const std::vector<CompressedSignature>& signatures,
+                                                      const std::vector<uint32_t>& key_indices, size_t n_keys, uint32_t threshold,
+                                                      Engine& e = Engine::default_engine()) {
+    KeyedAggregateResult r = batch_threshold_combine_keyed({CompressedShareItem{message, signatures, key_indices}}, n_keys, threshold, e)[0];
+    check_status(r.status);
+    return r;
+  }
+  static KeyedAggregateResult threshold_combine_keyed_optimistic(const std::vector<uint8_t>& message, const std::vector<CompressedSignature>& signatures,
+                                                                 const std::vector<uint32_t>& key_indices, size_t n_keys, uint32_t threshold,
+                                                                 Engine& e = Engine::default_engine()) {
+    KeyedAggregateResult r = threshold_batch<CompressedSignature>({CompressedShareItem{message, signatures, key_indices}}, n_keys, threshold, true, e)[0];
     check_status(r.status);
     return r;
   }
@@ -690,20 +781,34 @@ struct ECDSA {
   // parts[k] = a summed signature and the indices of the registered keys it is said to sum.  Every partial is verified as verify_keyed_signers
   // verifies it; in the order given, the valid ones whose indices do not overlap what was taken before are added (first fit).
   // status: 0, or the message's hash ErrorKind (then nothing was added); statuses[k]: what verify_keyed_signers gives partial k; taken[k]: 1 or 0.
-  struct PartialAggregate { Signature signature; std::vector<uint32_t> signer_indices; };
-  struct MergeItem { std::vector<uint8_t> message; std::vector<PartialAggregate> parts; };
+  template <class Sig> struct PartialAggregateT { Sig signature; std::vector<uint32_t> signer_indices; };
+  template <class Sig> struct MergeItemT { std::vector<uint8_t> message; std::vector<PartialAggregateT<Sig>> parts; };
+  using PartialAggregate = PartialAggregateT<Signature>;
+  using MergeItem = MergeItemT<Signature>;
+  using CompressedPartialAggregate = PartialAggregateT<CompressedSignature>;     // the partials as their 33-byte wire encodings
+  using CompressedMergeItem = MergeItemT<CompressedSignature>;
   struct KeyedMergeResult { uint8_t status; Signature signature; std::vector<uint32_t> signer_indices; std::vector<uint8_t> statuses, taken; };
   static std::vector<KeyedMergeResult> batch_merge_keyed_signers(const std::vector<MergeItem>& items, size_t n_keys, Engine& e = Engine::default_engine(),
                                                                  bool optimistic = false) {
+    return merge_keyed_signers_impl<Signature>(items, n_keys, e, optimistic);
+  }
+  static std::vector<KeyedMergeResult> batch_merge_keyed_signers(const std::vector<CompressedMergeItem>& items, size_t n_keys,
+                                                                 Engine& e = Engine::default_engine(), bool optimistic = false) {
+    return merge_keyed_signers_impl<CompressedSignature>(items, n_keys, e, optimistic);
+  }
+  template <class Sig> static std::vector<KeyedMergeResult> merge_keyed_signers_impl(const std::vector<MergeItemT<Sig>>& items, size_t n_keys, Engine& e,
+                                                                                     bool optimistic) {
     const size_t n = items.size(), bm_words = n_keys / 32 + 1;   // one bit past the set: every index outside it lands there -> IndexOutOfBounds
+    const size_t sz = std::tuple_size<decltype(Sig::raw)>::value;
+    const uint32_t flags = g1_input_flag<Sig>();
     std::vector<uint64_t> off(n + 1, 0), part_off(n + 1, 0);
     std::vector<uint8_t> msgs, parts;
     std::vector<uint32_t> rows;
     for (size_t i = 0; i < n; ++i) {
       off[i] = msgs.size();
-      part_off[i] = parts.size() / 64;
+      part_off[i] = parts.size() / sz;
       msgs.insert(msgs.end(), items[i].message.begin(), items[i].message.end());
-      for (const PartialAggregate& p : items[i].parts) {
+      for (const PartialAggregateT<Sig>& p : items[i].parts) {
         parts.insert(parts.end(), p.signature.raw.begin(), p.signature.raw.end());
         rows.resize(rows.size() + bm_words, 0);
         for (uint32_t j : p.signer_indices) {
@@ -713,7 +818,7 @@ struct ECDSA {
       }
     }
     off[n] = msgs.size();
-    part_off[n] = parts.size() / 64;
+    part_off[n] = parts.size() / sz;
     const size_t n_parts = (size_t)part_off[n];
     std::vector<uint8_t> part_st(n_parts + 1, 0), taken(n_parts + 1, 0), tuple_st(n + 1, 0), agg(n * 64 + 1, 0);
     std::vector<uint32_t> bits(n * bm_words + 1, 0);
@@ -721,11 +826,11 @@ struct ECDSA {
     rows.resize(rows.size() + 1);
     if (optimistic)
       check_rc("bn254_batch_merge_keyed_bitmap_optimistic",
-               bn254_batch_merge_keyed_bitmap_optimistic(e.raw(), msgs.data(), off.data(), parts.data(), rows.data(), part_off.data(), n_parts, n, bm_words, 0,
+               bn254_batch_merge_keyed_bitmap_optimistic(e.raw(), msgs.data(), off.data(), parts.data(), rows.data(), part_off.data(), n_parts, n, bm_words, flags,
                                                          part_st.data(), taken.data(), tuple_st.data(), agg.data(), bits.data(), nullptr));
     else
       check_rc("bn254_batch_merge_keyed_bitmap",
-               bn254_batch_merge_keyed_bitmap(e.raw(), msgs.data(), off.data(), parts.data(), rows.data(), part_off.data(), n_parts, n, bm_words, 0, part_st.data(),
+               bn254_batch_merge_keyed_bitmap(e.raw(), msgs.data(), off.data(), parts.data(), rows.data(), part_off.data(), n_parts, n, bm_words, flags, part_st.data(),
                                               taken.data(), tuple_st.data(), agg.data(), bits.data(), nullptr));
     std::vector<KeyedMergeResult> out(n);
     for (size_t i = 0; i < n; ++i) {
@@ -744,11 +849,21 @@ struct ECDSA {
     check_status(r.status);
     return r;
   }
+  static KeyedMergeResult merge_keyed_signers(const std::vector<uint8_t>& message, const std::vector<CompressedPartialAggregate>& parts, size_t n_keys,
+                                              Engine& e = Engine::default_engine()) {
+    KeyedMergeResult r = batch_merge_keyed_signers({CompressedMergeItem{message, parts}}, n_keys, e)[0];
+    check_status(r.status);
+    return r;
+  }
   // ... with ONE verify per item — the sum of its partials that pass every check short of the pairing, against the keys of the union of their
   // indices — and the partials verified one by one only where that fails or two of them overlap (include/bn254_hip.h:
   // bn254_batch_merge_keyed_bitmap_optimistic).  The same results, with one deviation: partials whose errors cancel within an item that passes
   // read 0 and are taken; the aggregate is still the valid one for the union.  Who needs per-partial verdicts takes batch_merge_keyed_signers.
   static std::vector<KeyedMergeResult> batch_merge_keyed_signers_optimistic(const std::vector<MergeItem>& items, size_t n_keys,
+                                                                            Engine& e = Engine::default_engine()) {
+    return batch_merge_keyed_signers(items, n_keys, e, true);
+  }
+  static std::vector<KeyedMergeResult> batch_merge_keyed_signers_optimistic(const std::vector<CompressedMergeItem>& items, size_t n_keys,
                                                                             Engine& e = Engine::default_engine()) {
     return batch_merge_keyed_signers(items, n_keys, e, true);
   }

@@ -59,6 +59,35 @@ typedef struct bn254_ctx bn254_ctx;
 
 #define BN254_FLAG_G2_SUBGROUP_CHECK 1u /* decode G2 inputs with the order-r check AffineG2::new performs */
 #define BN254_FLAG_REJECT_IDENTITY 2u   /* treat all-zero encodings as InvalidGroupPoint (from_uncompressed behaviour) */
+#define BN254_FLAG_G1_COMPRESSED 4u     /* the call's G1 INPUT array holds 33-byte compressed points (0x02 / 0x03 || x, Signature::from_compressed:
+                                           src/serde.rs:39, src/utils.rs:84-104) and needs no alignment, also in the _device forms.  Every other
+                                           array and every output is unchanged; aggregates the library WRITES stay 64 bytes (the identity is a
+                                           legitimate aggregate and has no compressed form).  Taken, in the host-pointer and the _device form, by:
+                                             bn254_batch_verify_keyed, bn254_batch_verify_keyed_randomized                        (sigs),
+                                             bn254_batch_verify_keyed_bitmap, bn254_batch_verify_keyed_bitmap_randomized          (sigs),
+                                             bn254_batch_collect_keyed_bitmap, its _randomized and its _optimistic form           (shares),
+                                             bn254_batch_merge_keyed_bitmap and its _optimistic form                              (parts),
+                                             bn254_batch_threshold_combine_keyed and its _optimistic form                         (shares).
+                                           Every other entry point that reads 64-byte G1 points under a flags argument returns
+                                           BN254_E_BAD_ARGUMENT when the bit is set (verify, verify_randomized, the aggregate and distinct-message
+                                           families, the pairing and public-key checks, the pop calls, the multi-GPU layer): no call reads 33-byte
+                                           data at a 64-byte stride.  Under the flag the array holds fewer than 2^32 items.
+                                           THE DEFINING IDENTITY.  For an encoding c let (st, u) be what bn254_batch_g1_decompress returns for it
+                                           (checks in the order documented there: x >= q gives 6, no square root gives 6, only then a bad prefix
+                                           gives 3).  S(c) = u if st = 0, else the 64 bytes BE32(q) || 0..0, a stand-in whose decode status is 6
+                                           under every flags value.  A call with the flag returns, byte for byte, what the same call without the
+                                           flag returns on the items S(c) — with one change: an item with st != 0 whose status byte reads 6 in that
+                                           run reports st instead.  (That byte is necessarily the item's own decode status: decode is the first
+                                           rule everywhere, and the one thing that can precede it, the fill with 2 of an item of no accepted
+                                           tuple, keeps reading 2.)  So such an item is never verified, taken, counted or made a candidate; the
+                                           rule orders, the optimistic and randomised fallbacks with their documented deviations, and the
+                                           BN254_OPT_MAX_CHUNK slicing hold unchanged.  BN254_FLAG_REJECT_IDENTITY has nothing to act on in the
+                                           compressed array (no encoding decompresses to the identity).  The decompression runs once per call, on
+                                           the device, in front of the call's first profiling event.  WHICH CALL WHEN: whoever holds compressed
+                                           signatures passes them with this flag — measured (whole host-pointer calls) it
+                                           is faster than decompressing through bn254_batch_g1_decompress and calling without the flag at every
+                                           shape tried (by 0.14 ms at 43 776 shares to 1.4 ms at 350 208), and 0.11 to 0.6 ms slower than the
+                                           same call on points that are ALREADY uncompressed: who holds those passes those. */
 #define BN254_FLAG_RAND64 0x100u        /* bn254_batch_verify_randomized: 64-bit instead of 128-bit random scalars */
 #define BN254_FLAG_RAND_GLV 0x200u      /* ... : r_i = k1 + k2*lambda mod r with k1, k2 the two 64-bit halves of the 128 random bits
                                            (lambda = 0xb3c4d79d41a917585bfc41088d8daaa78b17ea66b99c90dd, the eigenvalue of
@@ -519,7 +548,7 @@ int bn254_batch_verify_keyed_bitmap_randomized_device(bn254_ctx *ctx, const uint
  * segment in one lane.  Whole-call intervals of both routes, as far as they were measured: DESIGN.md section 10e.
  * Which call when: this one for calls of few shares, or of few shares per registered key; bn254_batch_collect_keyed_bitmap_randomized below where
  * the keys have many shares each across the tuples of the call.
- * Out of scope: the multi-GPU layer, compressed shares. */
+ * Compressed shares: BN254_FLAG_G1_COMPRESSED (33 bytes per share, no alignment).  Out of scope: the multi-GPU layer. */
 int bn254_batch_collect_keyed_bitmap(bn254_ctx *ctx, const uint8_t *msgs, const uint64_t *msg_off /* n+1 */,
                                      const uint8_t *shares /* n_shares*64 */, const uint32_t *share_key /* n_shares */,
                                      const uint64_t *share_off /* n+1 */, size_t n_shares, size_t n, size_t bm_words, uint32_t flags,
@@ -632,7 +661,7 @@ int bn254_batch_collect_keyed_bitmap_randomized_device(bn254_ctx *ctx, const uin
  * 1 539 shares, tuples of 3 and of 12 .. 170 shares, key sets between 256 and 4 096 keys, wrong shares over 4 096 keys beyond 256 x 171.
  * Profiling: ms[0] = front end (hash, range rule, pre-check) and provisional sum, ms[1] = aggregate keys, ms[2] = the tuples' Miller loop and
  * final exponentiation, ms[3] = exact fallback and re-sum.
- * Out of scope: a randomised fallback, the multi-GPU layer, compressed shares. */
+ * Compressed shares: BN254_FLAG_G1_COMPRESSED.  Out of scope: a randomised fallback, the multi-GPU layer. */
 int bn254_batch_collect_keyed_bitmap_optimistic(bn254_ctx *ctx, const uint8_t *msgs, const uint64_t *msg_off /* n+1 */,
                                                 const uint8_t *shares /* n_shares*64 */, const uint32_t *share_key /* n_shares */,
                                                 const uint64_t *share_off /* n+1 */, size_t n_shares, size_t n, size_t bm_words, uint32_t flags,
@@ -699,7 +728,7 @@ int bn254_batch_collect_keyed_bitmap_optimistic_device(bn254_ctx *ctx, const uin
  * wave, costs 0.39 us per partial and is the largest stage; the collect sums the same shares in 0.27 ms, so a caller whose partials are all
  * single shares takes the collect.  No shape at which the call loses was found; shapes with invalid partials were not measured.
  * The optimistic form (one verify of the tuple's sum when its partials are pairwise disjoint) is bn254_batch_merge_keyed_bitmap_optimistic,
- * below.  Out of scope: a randomised form, the multi-GPU layer, compressed input. */
+ * below.  Compressed partials: BN254_FLAG_G1_COMPRESSED (33 bytes per partial, no alignment).  Out of scope: a randomised form, the multi-GPU layer. */
 int bn254_batch_merge_keyed_bitmap(bn254_ctx *ctx, const uint8_t *msgs, const uint64_t *msg_off /* n+1 */,
                                    const uint8_t *parts /* n_parts*64 */, const uint32_t *part_bits /* n_parts*bm_words */,
                                    const uint64_t *part_off /* n+1 */, size_t n_parts, size_t n, size_t bm_words, uint32_t flags,
@@ -772,7 +801,7 @@ int bn254_batch_merge_keyed_bitmap_device(bn254_ctx *ctx, const uint8_t *d_msgs,
  * tuples, key sets other than 256 keys, wrong partials beyond the four shapes named.
  * Profiling: ms[0] = front end (hash, range rule, pre-check) and provisional select-and-sum, ms[1] = aggregate keys of the union rows, ms[2] =
  * the tuples' Miller loop and final exponentiation, ms[3] = fallback and re-select.
- * Out of scope: a short queue served by the small-batch kernels, a randomised merge, the multi-GPU layer, compressed input. */
+ * Compressed partials: BN254_FLAG_G1_COMPRESSED.  Out of scope: a short queue served by the small-batch kernels, a randomised merge, the multi-GPU layer. */
 int bn254_batch_merge_keyed_bitmap_optimistic(bn254_ctx *ctx, const uint8_t *msgs, const uint64_t *msg_off /* n+1 */,
                                               const uint8_t *parts /* n_parts*64 */, const uint32_t *part_bits /* n_parts*bm_words */,
                                               const uint64_t *part_off /* n+1 */, size_t n_parts, size_t n, size_t bm_words, uint32_t flags,
@@ -881,7 +910,7 @@ int bn254_ctx_register_keys_pop(bn254_ctx *ctx, const uint8_t *pks /* n_keys*128
  * same signature bytes.  Unmeasured: other thresholds, invalid shares, more than 256 keys, the host form.
  * Which call when: this one whenever the shares are in hand and the share keys registered; bn254_batch_collect_keyed_bitmap for
  * multi-signatures (no interpolation); bn254_batch_g1_msm for weighted sums of the caller's own points.  DESIGN.md section 10k.
- * Out of scope: a randomised form, the multi-GPU layer, compressed shares, and PRODUCING a dealing in the C ABI (Shamir sharing, the
+ * Compressed shares: BN254_FLAG_G1_COMPRESSED.  Out of scope: a randomised form, the multi-GPU layer, and PRODUCING a dealing in the C ABI (Shamir sharing, the
  * rounds of a DKG, checks of shares against commitments; bn254_batch_g2_msm is the building block for sum x^k C_k).  No longer out of
  * scope: checking a dealt key set (bn254_ctx_check_dealing), and an optimistic form that interpolates first and verifies the result once — bn254_batch_threshold_combine_keyed_optimistic below. */
 int bn254_batch_threshold_combine_keyed(bn254_ctx *ctx, const uint8_t *msgs, const uint64_t *msg_off /* n+1 */,
@@ -1154,6 +1183,12 @@ int bn254_batch_threshold_combine_keyed_optimistic_device(bn254_ctx *ctx, const 
  * src/error.rs:44-51 turns into NotMemberError; library versions before 0.6 returned 3 here.) */
 int bn254_batch_g1_decompress(bn254_ctx *ctx, const uint8_t *in /* n*33 */, size_t n, uint8_t *out /* n*64 */, uint8_t *status);
 int bn254_batch_g2_decompress(bn254_ctx *ctx, const uint8_t *in /* n*65 */, size_t n, uint8_t *out /* n*128 */, uint8_t *status);
+/* The _device form of bn254_batch_g1_decompress: the same bytes (a failed item: its status and 64 zero bytes), device pointers, only
+ * enqueues.  d_in33 needs no alignment, d_out64 is 4-byte aligned (else BN254_E_MISALIGNED); n < 2^32; n == 0 returns 0.  A caller that
+ * goes on into a registered-key call does not need it: BN254_FLAG_G1_COMPRESSED decompresses inside the call and keeps the statuses apart
+ * (a failed item's 64 zero bytes here are the identity, which decodes). */
+int bn254_batch_g1_decompress_device(bn254_ctx *ctx, const uint8_t *d_in33 /* n*33 */, size_t n, uint8_t *d_out64 /* n*64 */,
+                                     uint8_t *d_status /* n */, void *stream);
 
 /* timing of the most recent batch_verify*(…) on this context, from HIP events recorded on the
  * launch stream around each kernel: ms[0] decode, ms[1] hash-to-G1, ms[2] Miller loop,

@@ -176,6 +176,14 @@ def load():
         L.bn254_batch_g2_vector_combine.argtypes = [vp, vp, vp, sz, sz, i32, vp, vp]
         L.bn254_batch_g2_vector_combine_device.argtypes = [vp, vp, vp, sz, sz, i32, vp, vp, vp]
         L.bn254_ctx_reshare_commitments.argtypes = [vp, vp, vp, sz, u32, u32, u32, vp, vp, sz, vp, vp]
+    if hasattr(L, "bn254_batch_aggregate_keys_bitmap"):              # absent from an older build loaded through BN254_LIB
+        L.bn254_batch_aggregate_keys_bitmap.argtypes = [vp, vp, sz, sz, u32, vp, vp]
+        L.bn254_batch_aggregate_keys_bitmap_device.argtypes = [vp, vp, sz, sz, u32, vp, vp, vp]
+        L.bn254_batch_verify_keyed_bitmap_export.argtypes = [vp, vp, vp, vp, vp, sz, sz, u32, vp, vp, vp]
+        L.bn254_batch_verify_keyed_bitmap_export_device.argtypes = [vp, vp, vp, vp, vp, sz, sz, u32, vp, vp, vp, vp]
+        L.bn254_ctx_set_key_weights.argtypes = [vp, vp, sz]
+        L.bn254_batch_bitmap_weights.argtypes = [vp, vp, sz, sz, vp, vp]
+        L.bn254_batch_bitmap_weights_device.argtypes = [vp, vp, sz, sz, vp, vp, vp]
     L.bn254_debug_bitmap_rand_last.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     L.bn254_debug_bitmap_rand_sums.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), sz, sz, vp, vp, vp, vp, vp, vp]
     L.bn254_batch_verify_keyed_randomized.argtypes = [vp, vp, vp, vp, vp, sz, u32, vp, vp]
@@ -292,4 +300,7 @@ EXPORTED_SYMBOLS = [
     "bn254_batch_g2_poly_eval", "bn254_batch_g2_poly_eval_device", "bn254_ctx_register_keys_commitments",
     "bn254_batch_g2_vector_combine", "bn254_batch_g2_vector_combine_device", "bn254_ctx_reshare_commitments",
     "bn254_batch_g1_decompress_device",
+    "bn254_batch_aggregate_keys_bitmap", "bn254_batch_aggregate_keys_bitmap_device",
+    "bn254_batch_verify_keyed_bitmap_export", "bn254_batch_verify_keyed_bitmap_export_device",
+    "bn254_ctx_set_key_weights", "bn254_batch_bitmap_weights", "bn254_batch_bitmap_weights_device",
 ]

@@ -408,32 +408,106 @@ class ECDSA:
         _raise(ECDSA._keyed_signers_status([(message, signature, signer_indices)], engine, compressed=compressed)[0])
 
     @staticmethod
-    def _keyed_signers_status(items, engine, seed=None, flags=0, compressed=False):
+    def _signer_rows(items, compressed):
+        """(message, signature, signer_indices) triples -> (message bytes, signature bytes, indices as integers)"""
         rows = []
         for item in items:
             if len(item) != 3:
                 raise Error(ErrorKind.InvalidLength)
             message, signature, signer_indices = item
             raw, flag = ECDSA._g1_input([signature], compressed)
-            idx = [int(j) for j in signer_indices]
-            if any(j < 0 for j in idx):
-                raise Error(ErrorKind.IndexOutOfBounds)
-            rows.append((bytes(message), raw[0], idx))
-        flags |= _engine.FLAG_G1_COMPRESSED if compressed else 0
-        eng = engine or _eng()
-        # the bitmaps: as wide as the registered set plus ONE bit, on which every index outside the set lands (rule 2 reports the lowest bad
-        # bit, and every such index lies above the set); an engine that does not know its set: as wide as the largest index
+            rows.append((bytes(message), raw[0], ECDSA._signer_indices(signer_indices)))
+        return rows
+
+    @staticmethod
+    def _signer_indices(signer_indices):
+        idx = [int(j) for j in signer_indices]
+        if any(j < 0 for j in idx):
+            raise Error(ErrorKind.IndexOutOfBounds)
+        return idx
+
+    @staticmethod
+    def _signer_bitmaps(eng, idx_lists):
+        """-> (bitmap words, bm_words): as wide as the registered set plus ONE bit, on which every index outside the set lands (rule 2 reports
+        the lowest bad bit, and every such index lies above the set); an engine that does not know its set: as wide as the largest index"""
         n_keys = getattr(eng, "n_registered_keys", None)
-        top = n_keys if n_keys is not None else max([j for _, _, idx in rows for j in idx], default=-1)
+        top = n_keys if n_keys is not None else max([j for idx in idx_lists for j in idx], default=-1)
         bm_words = top // 32 + 1
-        bits = [0] * (len(rows) * bm_words)
-        for i, (_, _, idx) in enumerate(rows):
+        bits = [0] * (len(idx_lists) * bm_words)
+        for i, idx in enumerate(idx_lists):
             for j in idx:
                 j = min(j, top)
                 bits[i * bm_words + j // 32] |= 1 << (j % 32)
+        return bits, bm_words
+
+    @staticmethod
+    def _keyed_signers_status(items, engine, seed=None, flags=0, compressed=False):
+        rows = ECDSA._signer_rows(items, compressed)
+        flags |= _engine.FLAG_G1_COMPRESSED if compressed else 0
+        eng = engine or _eng()
+        bits, bm_words = ECDSA._signer_bitmaps(eng, [r[2] for r in rows])
         if seed is not None:
             return eng.batch_verify_keyed_bitmap_randomized([r[0] for r in rows], b"".join(r[1] for r in rows), bits, bm_words, seed, flags)
         return eng.batch_verify_keyed_bitmap([r[0] for r in rows], b"".join(r[1] for r in rows), bits, bm_words, **ECDSA._flag_kw(flags))
+
+    @staticmethod
+    def batch_aggregate_public_keys_signers(signer_lists, engine=None):
+        """result[i]: the PublicKey that is the sum of the registered keys signer_lists[i] names (the identity for an empty list or a sum
+        that cancels), or Error(IndexOutOfBounds) for an index outside the set / a refused key's registration Error — summed on the
+        device from the set's subset tables (include/bn254_hip.h: bn254_batch_aggregate_keys_bitmap)"""
+        eng = engine or _eng()
+        lists = [ECDSA._signer_indices(idx) for idx in signer_lists]
+        bits, bm_words = ECDSA._signer_bitmaps(eng, lists)
+        keys, st = eng.batch_aggregate_keys_bitmap(bits, bm_words, len(lists))
+        return [PublicKey(keys[128 * i:128 * i + 128]) if s == 0 else Error(s) for i, s in enumerate(st)]
+
+    @staticmethod
+    def aggregate_public_key_signers(signer_indices, engine=None):
+        """the sum of the registered keys signer_indices names; raises the Error batch_aggregate_public_keys_signers would return"""
+        res = ECDSA.batch_aggregate_public_keys_signers([signer_indices], engine)[0]
+        if isinstance(res, Error):
+            raise res
+        return res
+
+    @staticmethod
+    def batch_verify_keyed_signers_export(items, engine=None, compressed=False):
+        """batch_verify_keyed_signers that also returns what the device computed: result[i] = (None or the Error, H(message) as 64 bytes,
+        the signers' aggregate PublicKey).  The two outputs are zero bytes / the identity key unless the item passed every check before the
+        pairing (Error None or VerificationFailed) — include/bn254_hip.h: bn254_batch_verify_keyed_bitmap_export"""
+        rows = ECDSA._signer_rows(items, compressed)
+        flags = _engine.FLAG_G1_COMPRESSED if compressed else 0
+        eng = engine or _eng()
+        bits, bm_words = ECDSA._signer_bitmaps(eng, [r[2] for r in rows])
+        st, hashes, keys = eng.batch_verify_keyed_bitmap_export([r[0] for r in rows], b"".join(r[1] for r in rows), bits, bm_words, **ECDSA._flag_kw(flags))
+        return [(None if s == 0 else Error(s), hashes[64 * i:64 * i + 64], PublicKey(keys[128 * i:128 * i + 128])) for i, s in enumerate(st)]
+
+    @staticmethod
+    def verify_keyed_signers_export(message, signature, signer_indices, engine=None, compressed=False):
+        """one item of batch_verify_keyed_signers_export: (None or the Error, H(message) bytes, aggregate PublicKey) — nothing is raised"""
+        return ECDSA.batch_verify_keyed_signers_export([(message, signature, signer_indices)], engine, compressed)[0]
+
+    @staticmethod
+    def register_key_weights(weights, engine=None):
+        """voting weights of the registered keys, one non-negative integer below 2^64 per key (None forgets them); a total of 2^64 or more
+        or a count other than the registered one is refused.  Every registration forgets the weights."""
+        (engine or _eng()).set_key_weights(None if weights is None else [int(w) for w in weights])
+
+    @staticmethod
+    def batch_signers_weight(signer_lists, engine=None):
+        """result[i]: the sum of the weights of the registered keys signer_lists[i] names, or the Error of the first bad index (as
+        batch_aggregate_public_keys_signers).  A registered identity key counts its weight."""
+        eng = engine or _eng()
+        lists = [ECDSA._signer_indices(idx) for idx in signer_lists]
+        bits, bm_words = ECDSA._signer_bitmaps(eng, lists)
+        weight, st = eng.batch_bitmap_weights(bits, bm_words, len(lists))
+        return [w if s == 0 else Error(s) for w, s in zip(weight, st)]
+
+    @staticmethod
+    def signers_weight(signer_indices, engine=None):
+        res = ECDSA.batch_signers_weight([signer_indices], engine)[0]
+        if isinstance(res, Error):
+            raise res
+        return res
 
     @staticmethod
     def batch_verify_keyed_signers(items, engine=None, compressed=False):
@@ -1074,3 +1148,16 @@ def format_pairing_check_values(message, signature, public_key):
     sig = Signature.from_compressed(signature)
     pk = PublicKey.from_compressed(public_key)
     return format_pairing_check_uncompressed_values(message, sig.raw, pk.raw)
+
+
+def format_pairing_check_keyed_signers(message, signature, signer_indices, engine=None, compressed=False):
+    """format_pairing_check_uncompressed_values(message, signature, apk) for apk = the sum of the registered keys signer_indices names
+    (the reference's layout, src/utils.rs:216-239), from ONE device call: the bitmap verify that returns H(message) and apk
+    (ECDSA.verify_keyed_signers_export).  Raises the item's Error for any failure — VerificationFailed included: a failing aggregate is
+    never formatted — and Error(PointInJacobian) for an identity aggregate key, as PublicKey.to_uncompressed does.  compressed=True:
+    signature is the 33-byte wire encoding; the formatted signature is its decompressed form."""
+    err, h, apk = ECDSA.verify_keyed_signers_export(message, signature, signer_indices, engine, compressed)
+    if err is not None:
+        raise err
+    sig = Signature.from_compressed(signature).raw if compressed else bytes(signature.raw)
+    return [(_le_chunks(h), _le_chunks(apk.to_uncompressed())), (_le_chunks(sig[:64]), _le_chunks(_neg_g2_one()))]

@@ -876,6 +876,7 @@ void bn254_ctx_destroy(bn254_ctx* c) {
   if (c->kd_buf) (void)hipFree(c->kd_buf);
   if (c->bm_bad) (void)hipFree(c->bm_bad);
   if (c->bm_tab) (void)hipFree(c->bm_tab);
+  if (c->bw_tab) (void)hipFree(c->bw_tab);
   if (c->pop_buf) (void)hipFree(c->pop_buf);
   if (c->th_buf) (void)hipFree(c->th_buf);
   if (c->g1c_buf) (void)hipFree(c->g1c_buf);

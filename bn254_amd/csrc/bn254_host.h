@@ -125,6 +125,11 @@ struct bn254_ctx {
   bool bm_bad_valid, bm_tab_valid;
   int bm_table_max_keys;     // BN254_OPT_BITMAP_TABLE_MAX_KEYS: tables while n_keys <= this (0 = never)
   int bm_route;              // BN254_OPT_BITMAP_ROUTE (developer option): 0 by the rule above, 1 always tables, 2 never
+  // ... the voting weights of the registered keys (bn254_bitmap_out.hip: bn254_ctx_set_key_weights): byte-indexed tables of u64 subset sums,
+  // 2 KB per 8 keys, grown on demand; a registration forgets them (register_keys_begin)
+  uint8_t* bw_tab;
+  size_t bw_tab_cap;
+  bool bw_set;
   // ... randomised (bn254_bitmap_rand.hip), as the aggr_* members above
   int bmr_min_tuples;        // BN254_OPT_BITMAP_RAND_MIN_TUPLES: the randomised bitmap call from this many tuples on
   int bmr_group_tuples;      // BN254_OPT_BITMAP_RAND_GROUP_TUPLES: tuples per group of its combined checks

@@ -407,6 +407,7 @@ int register_keys_begin(bn254_ctx* c, size_t n_keys) {
   c->n_keys = 0;
   c->gk_set = false;                                  // a new key set is a new dealing: the group key of the previous one is forgotten
   c->bm_bad_valid = c->bm_tab_valid = false;          // the bitmap call's bad-bit vector and subset tables belong to the previous set
+  c->bw_set = false;                                  // ... and so do the voting weights: a new set is a new committee
   if (n_keys == 0) return 0;
   if (n_keys > c->key_cap) {
     if (c->key_lines) { HIP_TRY(hipFree(c->key_lines)); c->key_lines = nullptr; }

@@ -812,6 +812,64 @@ class Engine:
         _check("bn254_batch_verify_keyed_bitmap_device",
                self._lib.bn254_batch_verify_keyed_bitmap_device(self._h, d_msgs, d_off, d_sigs, d_signer_bits, bm_words, n, flags, d_status, stream))
 
+    # ---- what a bitmap call knows besides a status byte (include/bn254_hip.h: aggregate keys, H(m), voting weight) ----
+    def batch_aggregate_keys_bitmap(self, bitmaps, bm_words, n, flags=0):
+        """(aggregate keys, status bytes) of n bitmap rows: 128 bytes per row — the uncompressed sum of the set registered keys, zeros for the
+        identity and where the status (rule 2 of the bitmap verify) is non-zero"""
+        assert len(bitmaps) == n * bm_words
+        bits = (ctypes.c_uint32 * max(len(bitmaps), 1))(*bitmaps)
+        keys = ctypes.create_string_buffer(max(n, 1) * G2_BYTES)
+        status = ctypes.create_string_buffer(max(n, 1))
+        _check("bn254_batch_aggregate_keys_bitmap", self._lib.bn254_batch_aggregate_keys_bitmap(self._h, bits, bm_words, n, flags, keys, status))
+        return keys.raw[:n * G2_BYTES], status.raw[:n]
+
+    def batch_aggregate_keys_bitmap_device(self, d_signer_bits, bm_words, n, d_agg_keys, d_status, flags=0, stream=None):
+        _check("bn254_batch_aggregate_keys_bitmap_device",
+               self._lib.bn254_batch_aggregate_keys_bitmap_device(self._h, d_signer_bits, bm_words, n, flags, d_agg_keys, d_status, stream))
+
+    def batch_verify_keyed_bitmap_export(self, messages, sigs, bitmaps, bm_words, flags=0, want_hashes=True, want_keys=True):
+        """batch_verify_keyed_bitmap that also returns what it computed: (status bytes, H(m) 64 B each or None, aggregate keys 128 B each or
+        None); the outputs of a tuple whose status is neither 0 nor 9 are zero bytes"""
+        n = len(messages)
+        assert len(sigs) == n * g1_item_bytes(flags) and len(bitmaps) == n * bm_words
+        msgs, off = pack_messages(messages)
+        bits = (ctypes.c_uint32 * max(len(bitmaps), 1))(*bitmaps)
+        status = ctypes.create_string_buffer(max(n, 1))
+        hashes = ctypes.create_string_buffer(max(n, 1) * G1_BYTES) if want_hashes else None
+        keys = ctypes.create_string_buffer(max(n, 1) * G2_BYTES) if want_keys else None
+        _check("bn254_batch_verify_keyed_bitmap_export",
+               self._lib.bn254_batch_verify_keyed_bitmap_export(self._h, msgs, off, bytes(sigs), bits, bm_words, n, flags, status, hashes, keys))
+        return status.raw[:n], hashes.raw[:n * G1_BYTES] if want_hashes else None, keys.raw[:n * G2_BYTES] if want_keys else None
+
+    def batch_verify_keyed_bitmap_export_device(self, d_msgs, d_off, d_sigs, d_signer_bits, bm_words, n, d_status, d_hashes, d_agg_keys, flags=0, stream=None):
+        _check("bn254_batch_verify_keyed_bitmap_export_device",
+               self._lib.bn254_batch_verify_keyed_bitmap_export_device(self._h, d_msgs, d_off, d_sigs, d_signer_bits, bm_words, n, flags, d_status, d_hashes,
+                                                                       d_agg_keys, stream))
+
+    def set_key_weights(self, weights):
+        """voting weights of the registered keys (one unsigned 64-bit integer per key, total below 2^64), or None to forget them; every
+        registration forgets them"""
+        if weights is None:
+            _check("bn254_ctx_set_key_weights", self._lib.bn254_ctx_set_key_weights(self._h, None, 0))
+            return
+        n = len(weights)
+        if any(w < 0 or w >> 64 for w in weights):
+            raise ValueError("a weight does not fit 64 bits")
+        arr = (ctypes.c_uint64 * max(n, 1))(*weights)
+        _check("bn254_ctx_set_key_weights", self._lib.bn254_ctx_set_key_weights(self._h, arr, n))
+
+    def batch_bitmap_weights(self, bitmaps, bm_words, n):
+        """(weights, status bytes) of n bitmap rows: the sum of the set keys' weights where rule 2 of the bitmap verify gives 0, else 0"""
+        assert len(bitmaps) == n * bm_words
+        bits = (ctypes.c_uint32 * max(len(bitmaps), 1))(*bitmaps)
+        weight = (ctypes.c_uint64 * max(n, 1))()
+        status = ctypes.create_string_buffer(max(n, 1))
+        _check("bn254_batch_bitmap_weights", self._lib.bn254_batch_bitmap_weights(self._h, bits, bm_words, n, weight, status))
+        return list(weight[:n]), status.raw[:n]
+
+    def batch_bitmap_weights_device(self, d_signer_bits, bm_words, n, d_weight, d_status, stream=None):
+        _check("bn254_batch_bitmap_weights_device", self._lib.bn254_batch_bitmap_weights_device(self._h, d_signer_bits, bm_words, n, d_weight, d_status, stream))
+
     @staticmethod
     def _collect_buffers(messages, shares, share_keys, sizes, bm_words, flags=0):
         """what the collect and the threshold call marshal alike: the C arguments behind the context (msgs .. bm_words) and the five output

@@ -6,6 +6,8 @@
 //   bn254::ECDSA::aggregate_verify_keyed / batch_aggregate_verify_distinct_keyed   (... against registered keys)
 //   bn254::ECDSA::verify_keyed_signers / batch_verify_keyed_signers                 (one message, an aggregated signature, the signers' indices)
 //   bn254::ECDSA::batch_aggregate_verify_distinct_keyed_randomized                  (... with the group checks combined)
+//   bn254::ECDSA::aggregate_public_key_signers / verify_keyed_signers_export / register_key_weights / signers_weight   (what a bitmap call returns)
+//   bn254::format_pairing_check_values / _uncompressed_values / _keyed_signers        src/utils.rs:197-239
 //   bn254::check_public_keys                        /root/reference/src/ecdsa.rs:78-93
 //   bn254::PrivateKey / PublicKey / PublicKeyG1 / Signature   /root/reference/src/types.rs:13,81,151,222
 //   bn254::Error                                    /root/reference/src/error.rs:6-29
@@ -383,6 +385,94 @@ struct ECDSA {
   static void verify_keyed_signers(const std::vector<uint8_t>& message, const CompressedSignature& signature, const std::vector<uint32_t>& signer_indices,
                                    size_t n_keys, Engine& e = Engine::default_engine()) {
     check_status(batch_verify_keyed_signers({CompressedSignerItem{message, signature, signer_indices}}, n_keys, e)[0]);
+  }
+  // What a bitmap call knows besides a status (include/bn254_hip.h: bn254_batch_aggregate_keys_bitmap, bn254_batch_verify_keyed_bitmap_export,
+  // bn254_ctx_set_key_weights, bn254_batch_bitmap_weights).  The bitmap rows of plain index lists, as pack_signers builds them:
+  static std::vector<uint32_t> signer_bitmaps(const std::vector<std::vector<uint32_t>>& signer_lists, size_t n_keys, size_t* bm_words) {
+    *bm_words = n_keys / 32 + 1;
+    std::vector<uint32_t> bits(signer_lists.size() * *bm_words, 0);
+    for (size_t i = 0; i < signer_lists.size(); ++i)
+      for (uint32_t j : signer_lists[i]) {
+        const size_t b = j < n_keys ? j : n_keys;
+        bits[i * *bm_words + b / 32] |= 1u << (b % 32);
+      }
+    return bits;
+  }
+  // result[i]: status 0 and the sum of the registered keys signer_lists[i] names (the identity for an empty list or a sum that cancels), or the
+  // ErrorKind of the lowest bad index (2 outside the set, else the key's registration status) and the identity
+  struct AggregateKeyResult { uint8_t status; PublicKey key; };
+  static std::vector<AggregateKeyResult> batch_aggregate_public_keys_signers(const std::vector<std::vector<uint32_t>>& signer_lists, size_t n_keys,
+                                                                             Engine& e = Engine::default_engine()) {
+    size_t bm_words = 0;
+    const std::vector<uint32_t> bits = signer_bitmaps(signer_lists, n_keys, &bm_words);
+    const size_t n = signer_lists.size();
+    std::vector<uint8_t> keys(n * 128 + 1), status(n + 1);
+    check_rc("bn254_batch_aggregate_keys_bitmap", bn254_batch_aggregate_keys_bitmap(e.raw(), bits.data(), bm_words, n, 0, keys.data(), status.data()));
+    std::vector<AggregateKeyResult> out(n);
+    for (size_t i = 0; i < n; ++i) { out[i].status = status[i]; std::memcpy(out[i].key.raw.data(), &keys[128 * i], 128); }
+    return out;
+  }
+  static PublicKey aggregate_public_key_signers(const std::vector<uint32_t>& signer_indices, size_t n_keys, Engine& e = Engine::default_engine()) {
+    const AggregateKeyResult r = batch_aggregate_public_keys_signers({signer_indices}, n_keys, e)[0];
+    check_status(r.status);
+    return r.key;
+  }
+  // verify_keyed_signers that also returns what the device computed: the status, H(message) and the signers' aggregate key — both zero bytes
+  // unless the item passed every check before the pairing (status 0 or VerificationFailed).  Nothing is thrown for a non-zero status.
+  struct ExportResult { uint8_t status; Signature hash; PublicKey key; };
+  template <class Sig> static std::vector<ExportResult> verify_keyed_signers_export_impl(const std::vector<SignerItemT<Sig>>& items, size_t n_keys, Engine& e) {
+    const PackedSigners p = pack_signers<Sig>(items, n_keys);
+    const size_t n = items.size();
+    std::vector<uint8_t> status(n + 1), hashes(n * 64 + 1), keys(n * 128 + 1);
+    check_rc("bn254_batch_verify_keyed_bitmap_export",
+             bn254_batch_verify_keyed_bitmap_export(e.raw(), p.msgs.data(), p.off.data(), p.sigs.data(), p.bits.data(), p.bm_words, n, g1_input_flag<Sig>(),
+                                                    status.data(), hashes.data(), keys.data()));
+    std::vector<ExportResult> out(n);
+    for (size_t i = 0; i < n; ++i) {
+      out[i].status = status[i];
+      std::memcpy(out[i].hash.raw.data(), &hashes[64 * i], 64);
+      std::memcpy(out[i].key.raw.data(), &keys[128 * i], 128);
+    }
+    return out;
+  }
+  static std::vector<ExportResult> batch_verify_keyed_signers_export(const std::vector<SignerItem>& items, size_t n_keys, Engine& e = Engine::default_engine()) {
+    return verify_keyed_signers_export_impl<Signature>(items, n_keys, e);
+  }
+  static std::vector<ExportResult> batch_verify_keyed_signers_export(const std::vector<CompressedSignerItem>& items, size_t n_keys,
+                                                                     Engine& e = Engine::default_engine()) {
+    return verify_keyed_signers_export_impl<CompressedSignature>(items, n_keys, e);
+  }
+  static ExportResult verify_keyed_signers_export(const std::vector<uint8_t>& message, const Signature& signature, const std::vector<uint32_t>& signer_indices,
+                                                  size_t n_keys, Engine& e = Engine::default_engine()) {
+    return batch_verify_keyed_signers_export({SignerItem{message, signature, signer_indices}}, n_keys, e)[0];
+  }
+  static ExportResult verify_keyed_signers_export(const std::vector<uint8_t>& message, const CompressedSignature& signature,
+                                                  const std::vector<uint32_t>& signer_indices, size_t n_keys, Engine& e = Engine::default_engine()) {
+    return batch_verify_keyed_signers_export({CompressedSignerItem{message, signature, signer_indices}}, n_keys, e)[0];
+  }
+  // voting weights of the registered keys: one per key, total below 2^64 (else NativeError); every registration forgets them
+  static void register_key_weights(const std::vector<uint64_t>& weights, Engine& e = Engine::default_engine()) {
+    static const uint64_t none = 0;
+    check_rc("bn254_ctx_set_key_weights", bn254_ctx_set_key_weights(e.raw(), weights.empty() ? &none : weights.data(), weights.size()));
+  }
+  static void forget_key_weights(Engine& e = Engine::default_engine()) { check_rc("bn254_ctx_set_key_weights", bn254_ctx_set_key_weights(e.raw(), nullptr, 0)); }
+  // result[i]: status 0 and the sum of the weights of the keys signer_lists[i] names (a registered identity key counts), or the ErrorKind and 0
+  struct WeightResult { uint8_t status; uint64_t weight; };
+  static std::vector<WeightResult> batch_signers_weight(const std::vector<std::vector<uint32_t>>& signer_lists, size_t n_keys, Engine& e = Engine::default_engine()) {
+    size_t bm_words = 0;
+    const std::vector<uint32_t> bits = signer_bitmaps(signer_lists, n_keys, &bm_words);
+    const size_t n = signer_lists.size();
+    std::vector<uint64_t> weight(n + 1);
+    std::vector<uint8_t> status(n + 1);
+    check_rc("bn254_batch_bitmap_weights", bn254_batch_bitmap_weights(e.raw(), bits.data(), bm_words, n, weight.data(), status.data()));
+    std::vector<WeightResult> out(n);
+    for (size_t i = 0; i < n; ++i) out[i] = WeightResult{status[i], weight[i]};
+    return out;
+  }
+  static uint64_t signers_weight(const std::vector<uint32_t>& signer_indices, size_t n_keys, Engine& e = Engine::default_engine()) {
+    const WeightResult r = batch_signers_weight({signer_indices}, n_keys, e)[0];
+    check_status(r.status);
+    return r.weight;
   }
   // The producer of such an item (include/bn254_hip.h: bn254_batch_collect_keyed_bitmap): one message and individual signatures, signatures[k]
   // said to be by registered key key_indices[k].  Every signature is verified against its key; those that pass are added, one per key.
@@ -945,6 +1035,73 @@ inline void check_public_keys(const PublicKey& pk_g2, const PublicKeyG1& pk_g1, 
   uint8_t st = 0;
   check_rc("bn254_batch_check_public_keys", bn254_batch_check_public_keys(e.raw(), pk_g2.raw.data(), pk_g1.raw.data(), 1, 0, &st));
   check_status(st);
+}
+
+// The reference's precompile formatters (src/utils.rs:197-239): the two (G1, G2) pairs of the verification equation
+// e(H(m), pk) * e(sig, -G2::one()) with every 32-byte big-endian coordinate byte-reversed (zeropool-bn's little-endian affine form), for an
+// on-chain alt_bn128 pairing precompile.
+struct PairingCheckValues {
+  std::array<uint8_t, 64> g1[2];      // H(m), the signature
+  std::array<uint8_t, 128> g2[2];     // the public key, -G2::one()
+  bool operator==(const PairingCheckValues& o) const { return g1[0] == o.g1[0] && g1[1] == o.g1[1] && g2[0] == o.g2[0] && g2[1] == o.g2[1]; }
+};
+template <size_t N> inline std::array<uint8_t, N> le_chunks(const std::array<uint8_t, N>& be) {
+  std::array<uint8_t, N> r{};
+  for (size_t i = 0; i < N; i += 32) std::reverse_copy(be.begin() + i, be.begin() + i + 32, r.begin() + i);
+  return r;
+}
+inline const PublicKey& neg_g2_one(Engine& e = Engine::default_engine()) {      // (r - 1) * G2::one()
+  static const PublicKey neg = [&e] {
+    PrivateKey k;
+    const uint8_t r_minus_1[32] = {0x30, 0x64, 0x4E, 0x72, 0xE1, 0x31, 0xA0, 0x29, 0xB8, 0x50, 0x45, 0xB6, 0x81, 0x81, 0x58, 0x5D,
+                                   0x28, 0x33, 0xE8, 0x48, 0x79, 0xB9, 0x70, 0x91, 0x43, 0xE1, 0xF5, 0x93, 0xF0, 0x00, 0x00, 0x00};
+    std::memcpy(k.bytes.data(), r_minus_1, 32);
+    return PublicKey::from_private_key(k, e);
+  }();
+  return neg;
+}
+inline PairingCheckValues pairing_check_values_of(const Signature& hash, const Signature& signature, const PublicKey& key, Engine& e) {
+  PairingCheckValues v;
+  v.g1[0] = le_chunks(hash.raw); v.g2[0] = le_chunks(key.raw);
+  v.g1[1] = le_chunks(signature.raw); v.g2[1] = le_chunks(neg_g2_one(e).raw);
+  return v;
+}
+// src/utils.rs:216-239: like the reference this does NOT validate the signature or the key (it only re-orders bytes); a message that does not
+// hash throws its Error
+inline PairingCheckValues format_pairing_check_uncompressed_values(const std::vector<uint8_t>& message, const Signature& signature, const PublicKey& public_key,
+                                                                   Engine& e = Engine::default_engine()) {
+  Signature h;
+  const uint64_t off[2] = {0, message.size()};
+  uint8_t st = 0;
+  check_rc("bn254_batch_hash_to_g1", bn254_batch_hash_to_g1(e.raw(), message.data(), off, 1, h.raw.data(), &st, nullptr));
+  check_status(st);
+  return pairing_check_values_of(h, signature, public_key, e);
+}
+// src/utils.rs:197-214: the same from the COMPRESSED signature (33 B) and public key (65 B); both are decoded, and thereby validated, first
+inline PairingCheckValues format_pairing_check_values(const std::vector<uint8_t>& message, const std::vector<uint8_t>& signature33,
+                                                      const std::vector<uint8_t>& public_key65, Engine& e = Engine::default_engine()) {
+  const Signature sig = Signature::from_compressed(signature33.data(), signature33.size(), e);
+  const PublicKey pk = PublicKey::from_compressed(public_key65.data(), public_key65.size(), e);
+  return format_pairing_check_uncompressed_values(message, sig, pk, e);
+}
+// format_pairing_check_uncompressed_values(message, signature, apk) for apk = the sum of the registered keys signer_indices names, from ONE
+// device call (ECDSA::verify_keyed_signers_export).  Throws the item's Error for any non-zero status, VerificationFailed included — a failing
+// aggregate is never formatted — and Error{PointInJacobian} for an identity aggregate key, as PublicKey::to_uncompressed does.
+inline PairingCheckValues format_pairing_check_keyed_signers(const std::vector<uint8_t>& message, const Signature& signature,
+                                                             const std::vector<uint32_t>& signer_indices, size_t n_keys,
+                                                             Engine& e = Engine::default_engine()) {
+  const ECDSA::ExportResult r = ECDSA::verify_keyed_signers_export(message, signature, signer_indices, n_keys, e);
+  check_status(r.status);
+  r.key.to_uncompressed();
+  return pairing_check_values_of(r.hash, signature, r.key, e);
+}
+inline PairingCheckValues format_pairing_check_keyed_signers(const std::vector<uint8_t>& message, const CompressedSignature& signature,
+                                                             const std::vector<uint32_t>& signer_indices, size_t n_keys,
+                                                             Engine& e = Engine::default_engine()) {
+  const ECDSA::ExportResult r = ECDSA::verify_keyed_signers_export(message, signature, signer_indices, n_keys, e);
+  check_status(r.status);
+  r.key.to_uncompressed();
+  return pairing_check_values_of(r.hash, Signature::from_compressed(signature.raw.data(), signature.raw.size(), e), r.key, e);
 }
 
 }  // namespace bn254

@@ -502,6 +502,60 @@ int bn254_batch_verify_keyed_bitmap_randomized_device(bn254_ctx *ctx, const uint
                                                       const uint32_t *d_signer_bits, size_t bm_words, size_t n, uint32_t flags,
                                                       const uint8_t *seed32 /* host memory */, uint8_t *d_status, void *stream);
 
+/* WHAT A BITMAP CALL KNOWS BESIDES A STATUS BYTE — for the party that hands a bitmap aggregate on to a verifier that holds no validator set (a
+ * contract, another chain): the aggregate public key, H(m) and the voting weight behind the bitmap.  Bitmaps are read as in
+ * bn254_batch_verify_keyed_bitmap (bm_words smaller or larger than needed, or 0 with a NULL bitmap); the argument checks, the _device
+ * conventions (device pointers, only enqueues, one call in flight per context) and the BN254_OPT_MAX_CHUNK slicing are that call's.
+ *
+ * A. bn254_batch_aggregate_keys_bitmap[_device]: status[i] is RULE 2 of the bitmap verify and nothing else — for the lowest bad set bit, 2 if
+ *    it is at or above n_keys, else that key's registration status; with no keys registered any set bit gives 2.  Where status[i] == 0,
+ *    agg_keys[i] is the uncompressed sum of the set keys — 128 zero bytes when the sum is the identity (an empty row, only identity keys, a
+ *    key and its negation; the status stays 0) — and 128 zero bytes where status[i] != 0.  DEFINING IDENTITY: for a tuple of status 0 the
+ *    bytes are those of bn254_batch_g2_sum over one segment holding the registered encodings of the set keys in ascending order.  The same
+ *    bytes on every route of the sum (subset tables or key by key, lane pairs or one lane).  flags must be 0 (BN254_E_BAD_ARGUMENT);
+ *    d_signer_bits and d_agg_keys are 4-byte aligned (BN254_E_MISALIGNED); n == 0 returns 0.  Cost: the bitmap verify's sum (n_keys / 8
+ *    table additions and one inversion per tuple) and one encode kernel.
+ *
+ * B. bn254_batch_verify_keyed_bitmap_export[_device]: the status bytes are byte for byte those of bn254_batch_verify_keyed_bitmap with the
+ *    same arguments and flags (BN254_FLAG_REJECT_IDENTITY and BN254_FLAG_G1_COMPRESSED included).  A tuple whose status is 0 or 9 has
+ *    passed rules 1-3: hashes[i] is the 64 bytes bn254_batch_hash_to_g1 gives for m_i and agg_keys[i] the 128 bytes call A gives for row i.
+ *    For every other tuple both outputs are zero bytes.  Either output pointer may be NULL; with both NULL the call is the verify.  The
+ *    output pointers of the _device form are 4-byte aligned.  Profiling intervals as the bitmap verify's (the emit counts in ms[1]).
+ *    H(m), the key and the signature are what the reference's precompile formatters take (src/utils.rs:197-239).
+ *
+ * C. bn254_ctx_set_key_weights gives registered key j the voting weight weights[j] (host memory; NULL forgets the weights).  Host-synchronous,
+ *    quiesces like a registration.  BN254_E_BAD_ARGUMENT if n_keys differs from the registered count or the weights total 2^64 or more (so no
+ *    subset sum wraps); a refused call leaves no weights set.  EVERY registration call forgets the weights: a new set is a new committee.
+ *    bn254_batch_bitmap_weights[_device] (BN254_E_BAD_ARGUMENT while no weights are set): status[i] is rule 2 as in A, weight[i] the sum of
+ *    the set keys' weights where the status is 0, else 0.  A registered IDENTITY key counts its weight — it is a member with status 0; a
+ *    set that must not hold one registers with BN254_FLAG_REJECT_IDENTITY.  The calls read bitmaps only: the used_bits rows of the collect,
+ *    merge and threshold calls go straight in.  d_weight is 8-byte aligned.  The caller compares the weight with its quorum.  Cost: one
+ *    lookup per bitmap byte in tables of u64 subset sums (2 KB of device memory per 8 keys), one path at every size; the call takes no
+ *    workspace and is not sliced.
+ * Measured on an MI355X (profiles/bitmap_out.jsonl; median of 7 alternating runs, whole host-pointer calls, two thirds of 256 keys signing;
+ * DESIGN.md section 10q has the spreads): at 65 536 tuples the export call 11.9 ms against 320 ms for the route that existed (bitmap verify +
+ * bn254_batch_hash_to_g1 + host gather of 22 KB per tuple + bn254_batch_g2_sum) and 10.9 for the plain verify; at 256 tuples 1.59 against 7.44
+ * and 1.58; 256 tuples over 4 096 keys 6.36 against 96.3 and 6.40.  Under events the _device export equals the _device verify within its
+ * spread (10.51 ms both).  Keys alone: 1.07 against 315 ms, 0.40 against 5.7, 5.2 against 90.  Weights: 0.21 ms against 17.2 for a numpy bit
+ * walk at 65 536 tuples, but 0.049 against 0.034 at 256 — a host caller with a few hundred bitmaps may walk them itself; the _device form
+ * takes 0.026 / 0.015 ms.  Which call when: the export call whenever H(m) or the key is wanted beside the verdict; call A for keys without a
+ * signature.  Unmeasured: key sets between 256 and 4 096, compressed sigmas on the export, failing tuples at scale. */
+int bn254_batch_aggregate_keys_bitmap(bn254_ctx *ctx, const uint32_t *signer_bits /* n*bm_words */, size_t bm_words, size_t n,
+                                      uint32_t flags /* must be 0 */, uint8_t *agg_keys /* n*128 */, uint8_t *status /* n */);
+int bn254_batch_aggregate_keys_bitmap_device(bn254_ctx *ctx, const uint32_t *d_signer_bits, size_t bm_words, size_t n, uint32_t flags,
+                                             uint8_t *d_agg_keys, uint8_t *d_status, void *stream);
+int bn254_batch_verify_keyed_bitmap_export(bn254_ctx *ctx, const uint8_t *msgs, const uint64_t *msg_off /* n+1 */, const uint8_t *sigs /* n*64 */,
+                                           const uint32_t *signer_bits /* n*bm_words */, size_t bm_words, size_t n, uint32_t flags,
+                                           uint8_t *status /* n */, uint8_t *hashes /* n*64, or NULL */, uint8_t *agg_keys /* n*128, or NULL */);
+int bn254_batch_verify_keyed_bitmap_export_device(bn254_ctx *ctx, const uint8_t *d_msgs, const uint64_t *d_msg_off, const uint8_t *d_sigs,
+                                                  const uint32_t *d_signer_bits, size_t bm_words, size_t n, uint32_t flags, uint8_t *d_status,
+                                                  uint8_t *d_hashes, uint8_t *d_agg_keys, void *stream);
+int bn254_ctx_set_key_weights(bn254_ctx *ctx, const uint64_t *weights /* n_keys, host; NULL: forget */, size_t n_keys);
+int bn254_batch_bitmap_weights(bn254_ctx *ctx, const uint32_t *signer_bits /* n*bm_words */, size_t bm_words, size_t n, uint64_t *weight /* n */,
+                               uint8_t *status /* n */);
+int bn254_batch_bitmap_weights_device(bn254_ctx *ctx, const uint32_t *d_signer_bits, size_t bm_words, size_t n,
+                                      uint64_t *d_weight /* 8-byte aligned */, uint8_t *d_status, void *stream);
+
 /* BUILDING a signer-bitmap aggregate — the producer half of bn254_batch_verify_keyed_bitmap: per message the node holds individual signatures
  * ("shares"), each said to be by one registered key, and needs every share checked against its key (one bad share poisons the sum, and the
  * sum cannot say which), the sum of those that passed, and the bitmap of who they were.  Tuple i is the message msgs[msg_off[i] ..
